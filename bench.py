@@ -15,11 +15,24 @@ argpartition on every rank; that merge is inside the timed region.
 
 Scaling mode: N = 1 times exactly K steps.  N > 1 defaults to STRONG scaling, the statement north_star / SURVEY 8(d)
 make ("images/s = 2975 / t", ">= 6x at 8 GPUs"): the fixed 2975-frame pool is split over the ranks, `value` = 2975 /
-max-over-ranks time, `steps` = the batches each rank ran (`requested_steps` keeps K); the weak figure (every rank
-scores exactly K batches of its shard) is timed right after and reported beside it as `weak`.  `--scaling weak`
-makes the weak figure the headline instead.
+max-over-ranks time, `steps` = the batches each rank ran (`requested_steps` keeps K); with `--full` the weak figure
+(every rank scores exactly K batches of its shard) is timed right after and reported beside it as `weak`.
+`--scaling weak` makes the weak figure the headline instead.
 
-Rank 0 prints ONE JSON line (contract in the task statement) carrying
+A plain run sets up, warms up, times the K steps, writes the outputs of the timed path when `--dump-outputs DIR` is
+given, and prints ONE JSON line with the headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step`, ...).  Everything else is measured or checked only with `--full`:
+
+    python bench.py --full [--no-roofline] [--no-secondary] [--no-cpu-baseline]
+
+`--dump-outputs DIR` (after the timed steps, rank 0): what the timed path returned, as float64 .npy files --
+`scores.npy` / `frame_ids.npy` (the per-image scores of the last timed step and the frames they belong to),
+`top_k.npy` (the sorted top-128 selection made by the merge that closes the timed region) and `pool_frame_ids.npy` /
+`pool_scores.npy` (every frame the timed region scored, once, in frame-id order; at most the 2975 pool frames).
+The inputs are seeded synthetic frames and weights, so the same arguments give the same inputs on every run.
+
+With `--full`, rank 0's line also carries
+  `weak`            (N > 1, strong scaling) the weak figure, timed right after the strong one,
   `roofline`        dominant kernel, HIP-event timed live on the launch stream in a separate profiling pass,
   `roofline_all`    the same figures for EVERY kernel symbol of the pass (avg us, algorithmic flops / bytes per launch,
                     bound, frac, PMC traffic per launch from the committed profiles/<round>_pmc passes),
@@ -30,7 +43,8 @@ Rank 0 prints ONE JSON line (contract in the task statement) carrying
                     tests check against the oracle AND against the table entry, bit for bit,
   `secondary`       (N = 1) short legs of the other single-GPU BASELINE configs: c4 = configs[3] ICNet / margin,
                     c5 = configs[4] ENet RGB+NIR, 6 classes / entropy -- each with value, ms_per_step, roofline, digest,
-  `cpu_baseline`    the torch-CPU restatement of the reference path, timed on this box's host cores (N = 1 only).
+  `cpu_baseline`    the torch-CPU restatement of the reference path, timed on this box's host cores (N = 1 only),
+and writes the full result to the detail file it names (a plain run writes one only when `--detail-file` is given).
 """
 import argparse
 import datetime
@@ -131,6 +145,12 @@ def parse(argv=None):
                          "frames, converted inside the Initial kernel (same bits out)")
     ap.add_argument("--resident-gib", type=float, default=96.0,
                     help="cap on device memory used for resident input frames (wraps beyond it)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the weak figure beside a strong one, the roofline leg, the secondary legs, "
+                         "the CPU baseline, the score digest against the committed table and the detail file (the --no-* "
+                         "options below switch single parts off)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-roofline", action="store_true")
@@ -147,9 +167,9 @@ def parse(argv=None):
     ap.add_argument("--knob", action="append", default=[], metavar="NAME=VALUE",
                     help="measurement runs only: ssal_debug_set_knob(NAME, VALUE) before anything is timed (needs "
                          "--allow-nondefault-knobs; the JSON line reports the knobs)")
-    ap.add_argument("--detail-file", default=DETAIL_FILE,
+    ap.add_argument("--detail-file", default=None,
                     help="full result (per-kernel flops / bytes / traffic, whole secondary legs); the stdout line carries "
-                         "the compact form and names this file")
+                         "the compact form and names this file (default with --full: DETAIL_FILE)")
     ap.add_argument("--full-line", action="store_true",
                     help="tools/*.sh: print the full result object on stdout instead of the compact line")
     ap.add_argument("--allow-digest-mismatch", action="store_true",
@@ -170,14 +190,20 @@ def load_score_table(key):
         return None
 
 
-def score_digest(index, score, key):
-    """SHA-256 of the float64 scores (frame-id order) of the frames actually scored, vs the committed table"""
+def unique_frames(index, score):
+    """(frame ids, scores) of the frames scored, once each, in frame-id order (a wrapped batch list may score a frame
+    twice: same bits, keep one; padding entries of a short shard have index -1)"""
     index = np.asarray(index, dtype=np.int64)
     score = np.asarray(score, dtype=np.float64)
     keep = index >= 0
     index, score = index[keep], score[keep]
-    first = np.unique(index, return_index=True)[1]  # a wrapped batch list may score a frame twice: same bits, keep one
-    index, score = index[first], score[first]
+    first = np.unique(index, return_index=True)[1]
+    return index[first], score[first]
+
+
+def score_digest(index, score, key):
+    """SHA-256 of the float64 scores (frame-id order) of the frames actually scored, vs the committed table"""
+    index, score = unique_frames(index, score)
     out = {"frames": int(len(index)), "sha256": hashlib.sha256(np.ascontiguousarray(score).tobytes()).hexdigest(),
            "table": "tests/golden/pool_scores.npz[%s]" % key, "expected_sha256": None, "match": None}
     table = load_score_table(key)
@@ -187,6 +213,18 @@ def score_digest(index, score, key):
         out["match"] = bool(out["sha256"] == out["expected_sha256"])
         out["max_abs_diff"] = float(np.max(np.abs(score - want)))
     return out
+
+
+def dump_outputs(head, out_dir):
+    """--dump-outputs: what the timed path returned, as float64 arrays (at most a few POOL-sized vectors, ~100 KB)"""
+    ids, scores = head["last_step"]
+    pool_ids, pool_scores = unique_frames(head["index"], head["score"])
+    arrays = {"scores": scores.cpu().numpy(), "frame_ids": ids.cpu().numpy(), "top_k": np.sort(head["low"]),
+              "pool_frame_ids": pool_ids, "pool_scores": pool_scores}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    log("outputs of the timed path written to %s (%s)" % (out_dir, ", ".join(sorted(arrays))))
 
 
 # ---- CPU baseline -----------------------------------------------------------------------------------------
@@ -482,6 +520,7 @@ class Leg:
                 score_chunks.append(self.net.score(xb, measure=self.measure, arithmetic=self.arithmetic))
             idx_chunks.append(ib)
             frames += xb.shape[0]
+        self.last_step = (idx_chunks[-1], score_chunks[-1]) if k else None  # what the last step returned (--dump-outputs)
         return torch.cat(idx_chunks), torch.cat(score_chunks), frames
 
     def merge_and_select(self, index, score, pad_steps):
@@ -521,7 +560,7 @@ class Leg:
                 total_frames = float(frames)
         log("%s: %d steps, %.0f frames over all ranks in %.3f s (max over ranks)" % (what, steps, total_frames, elapsed))
         return {"elapsed": elapsed, "frames": total_frames, "steps": steps, "low": low,
-                "index": all_index, "score": all_score}
+                "index": all_index, "score": all_score, "last_step": self.last_step}
 
     def key(self):
         return table_key(self.model, self.c, self.classes, self.h, self.w, self.measure, self.seed)
@@ -639,7 +678,10 @@ def main(argv=None):
     per_rank = (POOL + world - 1) // world
     strong_steps = (per_rank + bs - 1) // bs
     requested_steps, warmup = args.steps, args.warmup
-    need = max(strong_steps if (scaling == "strong" or world > 1) else 0, args.steps + warmup)
+    # the headline region; with --full and N > 1 the other scaling mode is timed beside it
+    time_strong = scaling == "strong" or (world > 1 and args.full)
+    time_weak = scaling == "weak" or (world > 1 and args.full)
+    need = max(strong_steps if time_strong else 0, args.steps + warmup)
     n_resident = leg.make_resident(need)
     log("%d resident batches of %d frames (%.1f GiB) generated on device" %
         (n_resident, bs, n_resident * leg.bytes_per_batch / 2 ** 30))
@@ -653,12 +695,12 @@ def main(argv=None):
 
     # ---- timed regions ----------------------------------------------------------------------------
     weak = strong = None
-    if scaling == "strong" or world > 1:
+    if time_strong:
         # total work fixed: each rank scores its whole shard of the 2975-frame pool once (a short shard's missing
         # last batch wraps onto batch 0 so that every rank issues the same number of steps; the duplicate is
         # dropped by the scatter-by-index, which writes the same bits twice)
         strong = leg.timed(strong_steps, 0, "strong (pool / %d ranks)" % world)
-    if scaling == "weak" or world > 1:
+    if time_weak:
         weak = leg.timed(requested_steps, warmup, "weak (%d steps per rank)" % requested_steps)
     head = strong if scaling == "strong" else weak
 
@@ -687,31 +729,34 @@ def main(argv=None):
             "requested_steps": requested_steps,
             "knobs": knobs,
         }
-        if world > 1:
+        if world > 1 and args.full:
             other = weak if scaling == "strong" else strong
             oname = "weak" if scaling == "strong" else "strong"
             oframes = other["frames"] if oname == "weak" else float(POOL)
             result[oname] = {"value": oframes / other["elapsed"], "unit": "images/s", "steps": other["steps"],
                              "ms_per_step": 1e3 * other["elapsed"] / other["steps"], "frames_scored": int(oframes),
                              "scaling": oname}
-        # result check: digest of the scores of the frames the timed region scored vs the committed table
-        result["score_digest"] = score_digest(head["index"], head["score"], leg.key())
-        if args.arithmetic != "f32":  # the mode's own gate: within 1e-6 of the exact table (tests/test_gpu_bf16x3.py)
-            dg = result["score_digest"]
-            dg["tolerance"] = 1e-6
-            dg["bit_identical_to_table"] = bool(dg["sha256"] == dg["expected_sha256"])
-            dg["match"] = bool(dg.get("max_abs_diff") is not None and dg["max_abs_diff"] <= 1e-6)
+        if args.full:
+            # result check: digest of the scores of the frames the timed region scored vs the committed table
+            result["score_digest"] = score_digest(head["index"], head["score"], leg.key())
+            if args.arithmetic != "f32":  # the mode's own gate: within 1e-6 of the exact table (tests/test_gpu_bf16x3.py)
+                dg = result["score_digest"]
+                dg["tolerance"] = 1e-6
+                dg["bit_identical_to_table"] = bool(dg["sha256"] == dg["expected_sha256"])
+                dg["match"] = bool(dg.get("max_abs_diff") is not None and dg["max_abs_diff"] <= 1e-6)
         whole_pool = len(np.unique(head["index"][head["index"] >= 0])) >= POOL
         result["top_k_checksum"] = int(np.sort(head["low"]).astype(np.int64).sum()) if whole_pool else None
+        if args.dump_outputs:
+            dump_outputs(head, args.dump_outputs)
 
     # ---- roofline leg: per-kernel HIP-event timing of extra batches (rank 0, outside the clock) ----
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         result["roofline"], result["roofline_all"] = roofline_leg(leg.net, leg.batches[0][0], args.measure, args.model,
                                                                   arithmetic=args.arithmetic)
         log("roofline leg done")
 
     # ---- the other single-GPU BASELINE configs (rank 0, N = 1 only) ---------------------------------
-    if rank == 0 and world == 1 and not args.no_secondary and args.model == "enet" and (h, w) == (1024, 2048):
+    if rank == 0 and world == 1 and args.full and not args.no_secondary and args.model == "enet" and (h, w) == (1024, 2048):
         leg.batches = leg.batches[:1]  # free the resident pool shard (keeps the roofline batch)
         torch.cuda.empty_cache()
         result["secondary"] = {
@@ -730,7 +775,7 @@ def main(argv=None):
         log("secondary legs done")
 
     # ---- CPU baseline leg (rank 0, N=1 only) ------------------------------------------------------
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         P = syn.enet_params_dict(leg.net)
         c1 = None
         if args.model == "enet":
@@ -743,14 +788,17 @@ def main(argv=None):
 
     rc = 0
     if rank == 0:
-        digests = [("headline", result["score_digest"])]
-        for nm, sec in result.get("secondary", {}).items():
-            digests.append((nm, sec["score_digest"]))
-        bad = [nm for nm, dg in digests if dg["match"] is False]
-        result["score_digest_verdict"] = ("MISMATCH: " + ", ".join(bad)) if bad else (
-            "ok" if all(dg["match"] for _, dg in digests) else "ok (no committed table entry for: %s)"
-            % ", ".join(nm for nm, dg in digests if dg["match"] is None))
-        detail = write_detail(result, args.detail_file)
+        bad = []
+        if args.full:
+            digests = [("headline", result["score_digest"])]
+            for nm, sec in result.get("secondary", {}).items():
+                digests.append((nm, sec["score_digest"]))
+            bad = [nm for nm, dg in digests if dg["match"] is False]
+            result["score_digest_verdict"] = ("MISMATCH: " + ", ".join(bad)) if bad else (
+                "ok" if all(dg["match"] for _, dg in digests) else "ok (no committed table entry for: %s)"
+                % ", ".join(nm for nm, dg in digests if dg["match"] is None))
+        detail_path = args.detail_file or (DETAIL_FILE if args.full else None)
+        detail = write_detail(result, detail_path) if detail_path else None
         print(json.dumps(result) if args.full_line else compact_line(result, detail), flush=True)
         if bad and not args.allow_digest_mismatch:
             log("score digest MISMATCH (%s): the timed kernels did not produce the committed scores" % ", ".join(bad))

@@ -102,11 +102,13 @@ def test_rccl_backend_executes_with_one_rank(tmp_path):
     assert open(tmp_path / "rccl_ok").read() == "1"
 
 
-def _run_bench(extra, nproc, tmp_path, tag):
+def _run_bench(extra, nproc, tmp_path, tag, full=True):
     import json
     import subprocess
     env = dict(os.environ, SSAL_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    common = ["--height", "64", "--width", "128", "--warmup", "1", "--no-cpu-baseline", "--no-roofline", "--no-secondary"]
+    common = ["--height", "64", "--width", "128", "--warmup", "1"]
+    if full:  # the weak figure beside the strong one and the score digest are --full parts of the line
+        common += ["--full", "--no-cpu-baseline", "--no-roofline", "--no-secondary"]
     bench = os.path.join(ROOT, "bench.py")
     if nproc == 1:
         cmd = [sys.executable, bench, "--gpus", "1"] + common + extra
@@ -147,6 +149,32 @@ def test_bench_missing_rank_exits_nonzero_instead_of_hanging(tmp_path):
     assert b"{\"metric\"" not in r.stdout
 
 
+def test_bench_plain_run_times_steps_and_dumps_outputs(tmp_path):
+    """a plain run (no --full) times exactly --steps steps, prints the headline without the --full parts, and
+    --dump-outputs writes what the timed path returned: the last step's scores match the oracle"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from helpers import frames, make_model
+    from oracle import enet_oracle as orc
+    out = tmp_path / "out"
+    line = _run_bench(["--steps", "4", "--dump-outputs", str(out)], 1, tmp_path, "plain", full=False)
+    assert line["steps"] == 4 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert k in line, k
+    for k in ("roofline", "roofline_all", "secondary", "cpu_baseline", "score_digest", "weak"):
+        assert k not in line, k
+    got = {n: np.load(out / (n + ".npy")) for n in ("scores", "frame_ids", "top_k", "pool_frame_ids", "pool_scores")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    # the timed region starts after the warm-up batch: frames 8 .. 39, the last step scores 32 .. 39
+    assert got["frame_ids"].tolist() == list(range(32, 40)) and got["pool_frame_ids"].tolist() == list(range(8, 40))
+    assert (got["pool_scores"][-8:] == got["scores"]).all()
+    from semanticsegmentationactivelearning_amd import active_learning as al
+    low, _ = al.finish_ranking(got["pool_frame_ids"].astype(np.int64), got["pool_scores"], 2975, np.arange(2975), 128)
+    assert got["top_k"].tolist() == sorted(low.tolist())
+    _, P = make_model(19, 3, seed=0)
+    want = orc.score_images(P, frames(np.arange(32, 40), 64, 128, 3), "entropy")[0]
+    assert np.abs(got["scores"] - want).max() <= 1e-6
+
+
 def _prefetch_worker(rank, world, port, out_dir, pool_dir):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -179,10 +207,13 @@ def _prefetch_worker(rank, world, port, out_dir, pool_dir):
         dist.destroy_process_group()
 
 
-def test_two_ranks_prefetch_from_tfrecords_five_streams(tmp_path):
+def test_two_ranks_prefetch_from_tfrecords_five_streams(tmp_path, monkeypatch):
     """the five-stream case -- each of two ranks (sharing the one GPU, collectives over gloo) runs
     rank_confidence(prefetch=2) on ITS shard of a pool of real TFRecords: caller's stream + 2 image-group chains + the
     prefetch copy stream (+ the collective).  Both ranks must select what a single-process float32 pass selects."""
+    # the ranks must start from the package's own queue default (checked in _prefetch_worker), not from a smaller value
+    # the launching shell exported
+    monkeypatch.delenv("GPU_MAX_HW_QUEUES", raising=False)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from helpers import frames, make_model
     from oracle import enet_oracle as orc

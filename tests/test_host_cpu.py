@@ -343,6 +343,26 @@ def test_bench_scaling_default_and_common_step_count():
             assert mine <= per <= steps * bs
 
 
+def test_bench_plain_run_options_and_dump_outputs(tmp_path):
+    """a plain run leaves the --full parts and the detail file off; dump_outputs writes float64 arrays of the timed
+    path's results: the last step, the top-k selection, every scored frame once in frame-id order (padding dropped)"""
+    import torch
+    import bench
+    a = bench.parse([])
+    assert not a.full and a.dump_outputs is None and a.detail_file is None
+    a = bench.parse(["--full", "--dump-outputs", str(tmp_path)])
+    assert a.full and a.dump_outputs == str(tmp_path)
+    head = {"index": np.array([5, 3, 4, -1, 3]), "score": np.array([0.5, 0.3, 0.4, 9.0, 0.3]), "low": np.array([4, 3]),
+            "last_step": (torch.tensor([4, -1, 3]), torch.tensor([0.4, 9.0, 0.3], dtype=torch.float64))}
+    bench.dump_outputs(head, str(tmp_path / "out"))
+    got = {n: np.load(tmp_path / "out" / (n + ".npy")) for n in ("scores", "frame_ids", "top_k", "pool_frame_ids",
+                                                                  "pool_scores")}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert got["scores"].tolist() == [0.4, 9.0, 0.3] and got["frame_ids"].tolist() == [4, -1, 3]
+    assert got["top_k"].tolist() == [3, 4]
+    assert got["pool_frame_ids"].tolist() == [3, 4, 5] and got["pool_scores"].tolist() == [0.3, 0.4, 0.5]
+
+
 def test_bench_kernel_roofline_rows_and_committed_pmc():
     """bench.kernel_roofline: bound from the arithmetic intensity against the fp32 ridge, achieved / frac per launch, PMC
     traffic per launch from the newest committed pass (profiles/r05_pmc, with the opt-in kernels' own pass merged in); packed-vector

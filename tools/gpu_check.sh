@@ -18,7 +18,7 @@ step() {  # step <name> <timeout_s> <cmd...>
 STEPS=${BENCH_STEPS:-24}
 step smoke 300 python __graft_entry__.py smoke
 step pytest_gpu 900 python -m pytest tests -m gpu -q -p no:cacheprovider ${PYTEST_ARGS:-}
-step bench 600 python bench.py --steps $STEPS --warmup 2
+step bench 600 python bench.py --full --steps $STEPS --warmup 2
 if [ "${SKIP_PROF:-0}" != "1" ]; then
     export TMPDIR=/tmp
     step rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 bench.py --steps 6 --warmup 1 --no-cpu-baseline --no-secondary --no-roofline
