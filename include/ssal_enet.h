@@ -114,6 +114,19 @@ int ssal_enet_score_nhwc_arith(ssal_enet *net, const void *x_dev, int x_is_u8, i
                                float threshold, int arithmetic, double *scores_dev, uint8_t *label_dev, uint8_t *mask_dev,
                                float *conf_dev, void *ws_dev, int64_t ws_bytes, void *stream);
 
+/* Validation pass, fused: ENet.call(training=False) -> argmax -> masked confusion matrix, the val / test branch of the
+ * reference loop (active_learning.py:277-282 val_net and val_pred = argmax(val_logits); tensortools.metrics.Metrics
+ * :390-427 with its confusion update, tensortools/metrics.py:8-27,226-257).  The logits and the predicted labels never
+ * reach HBM: the Final kernel reads labels_dev / mask_dev [n,h,w] uint8 (mask_dev NULL = weight 1) and ADDS
+ * bincount(classes * label + argmax, weights = mask) into confusion_dev int64 [classes][classes] (row = label, column =
+ * prediction; a key >= classes^2, e.g. label 255, is dropped), as the reference's assign_add does -- zero it first for a
+ * per-batch matrix.  x_dev and arithmetic as in ssal_enet_score_nhwc_arith.  The workspace is
+ * ssal_enet_eval_workspace_bytes (>= ssal_enet_workspace_bytes; the first part is laid out as a score call's). */
+int64_t ssal_enet_eval_workspace_bytes(const ssal_enet *net, int n, int h, int w);
+int ssal_enet_evaluate_nhwc_arith(ssal_enet *net, const void *x_dev, int x_is_u8, int n, int h, int w, int arithmetic,
+                                  const uint8_t *labels_dev, const uint8_t *mask_dev, int64_t *confusion_dev,
+                                  void *ws_dev, int64_t ws_bytes, void *stream);
+
 /* Byte offsets into the workspace of the last forward/score call of the tensors behind
  * ENet.endpoint_outputs (models/enet/enet.py:311-318): offs[0] bottleneck5_1 [n,h/2,w/2,16],
  * offs[1] bottleneck4_2 [n,h/4,w/4,64], offs[2] bottleneck3_8 [n,h/8,w/8,128]. */
@@ -150,6 +163,14 @@ int ssal_score_logits_nhwc(const float *logits_dev, int n, int h, int w, int cla
                            float threshold, double *scores_dev, uint8_t *label_dev,
                            uint8_t *mask_dev, float *conf_dev, void *ws_dev, int64_t ws_bytes,
                            void *stream);
+
+/* tensortools.metrics.confusion_mat (tensortools/metrics.py:226-257) accumulated like Metrics' assign_add (:8-27):
+ * confusion_dev int64 [classes][classes] += bincount(classes * labels + pred, weights, minlength = maxlength = classes^2)
+ * over `pixels` uint8 elements of pred_dev / labels_dev / weights_dev (weights_dev NULL = weight 1; a weight is its full
+ * uint8 value).  Keys >= classes^2 are dropped.  classes in [2, 32].  Integer counts: bitwise reproducible. */
+int64_t ssal_confusion_workspace_bytes(int classes);
+int ssal_confusion_matrix(const uint8_t *pred_dev, const uint8_t *labels_dev, const uint8_t *weights_dev, int64_t pixels,
+                          int classes, int64_t *confusion_dev, void *ws_dev, int64_t ws_bytes, void *stream);
 
 /* tensortools.losses.masked_softmax_cross_entropy forward (tensortools/losses.py:3-74): label
  * smoothing, optional ENet-style class weighting (weight > 1), fp32 sum over the batch axis, float64
@@ -224,14 +245,15 @@ int ssal_debug_probe(float *out_dev_256, void *stream);
  * groups on G library-owned side streams, forked from / joined into the caller's stream with events -- default 2, 1 =
  * everything on the caller's stream; "ic_front": ICNet score path, bit 0 (default 1) = conv1_sub1 + conv2_sub1 as one launch,
  * bit 1 (default 0) = conv1_1_3x3_s2 + conv1_2_3x3 as one launch; "ic_dual": ICNet score path, 1 (default) = a block's projection
- * shortcut is evaluated inside its 1x1 increase launch).  Every setting produces bit-identical results
+ * shortcut is evaluated inside its 1x1 increase launch; "conf_reps": replicas of the confusion accumulator the evaluation
+ * pass and ssal_confusion_matrix add into, 1 .. 64, default 8).  Every setting produces bit-identical results
  * (tests/test_gpu_parity.py, tests/test_icnet_gpu.py); SSAL_EINVAL for
  * an unknown name.  The product build reads no environment variable and contains no work-skipping switch: phase
  * ablation ("ablate") and the SSAL_* environment defaults exist only in -DSSAL_MEASURE builds (tools/phase_trace.py),
  * whose ssal_version() says so. */
 int ssal_debug_set_knob(const char *name, int value);
 /* JSON object with the state of every switch that can change what a launch does or costs: kernel_family, bnk_tw, bnk_o4,
- * bnk_xcd, img_groups, img_span, fuse_ends, img_lag, ig_div, ic_front, ic_dual, ablate, measure_build, profiling, defaults (1 iff all are at their shipping values).  bench.py prints it
+ * bnk_xcd, img_groups, img_span, fuse_ends, img_lag, ig_div, ic_front, ic_dual, conf_reps, ablate, measure_build, profiling, defaults (1 iff all are at their shipping values).  bench.py prints it
  * in its result line and refuses to time anything else. */
 int ssal_debug_get_knobs(char *json_out, int64_t cap);
 

@@ -104,12 +104,16 @@ PROTOTYPES = {
     "ssal_enet_forward_nhwc_arith": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i64, _vp]),
     "ssal_enet_score_nhwc_arith": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "ssal_enet_run_layer_arith": (_i, [_vp, _c.c_char_p, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_enet_eval_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
+    "ssal_enet_evaluate_nhwc_arith": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
     "ssal_enet_endpoint_offsets": (_i, [_vp, _i, _i, _i, _c.POINTER(_i64)]),
     "ssal_enet_export_argmax": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp, _vp]),
     "ssal_enet_run_layer": (_i, [_vp, _c.c_char_p, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
     "ssal_enet_layer_workspace_bytes": (_i64, [_vp, _c.c_char_p, _i, _i, _i]),
     "ssal_score_workspace_bytes": (_i64, [_i, _i, _i]),
     "ssal_score_logits_nhwc": (_i, [_vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_confusion_workspace_bytes": (_i64, [_i]),
+    "ssal_confusion_matrix": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _i64, _vp]),
     "ssal_xent_workspace_bytes": (_i64, [_i, _i]),
     "ssal_masked_softmax_cross_entropy": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _i64, _vp]),
     "ssal_max_pool_with_argmax_2x2": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),

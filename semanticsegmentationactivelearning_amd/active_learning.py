@@ -222,6 +222,47 @@ def rank_confidence(net, batches, num_examples, unlabelled, selection_size, meas
     return merge_and_rank(local_index, local_score, num_examples, unlabelled, selection_size, group, ragged)
 
 
+def evaluate(net, batches, num_classes, group=None, prefetch=2, arithmetic="f32"):
+    """The validation / test pass of the reference loop (active_learning.py:277-282 ``val_net`` + ``val_pred``, the
+    ``Metrics`` update :390-427, read back at :616-630 and :655-680): ``batches`` yields ``(image, label, mask, ...)``
+    as ``InputStage``'s evaluation path produces them (centre crop, ``generate_mask``); extra items are ignored.  Each
+    batch is counted on the device by ``net.evaluate`` (ENet: fused into the Final kernel; ICNet: label plane + the
+    confusion op) into one int64 K x K accumulator; host batches are copied ``prefetch`` batches ahead on a side stream
+    (``prefetch_to_device``).  With a process group (every rank evaluates its own shard) the K x K matrices are summed
+    with exactly ONE all-reduce.  Returns ``tensortools.metrics.create_metrics`` of the total (``MeanIoU`` decides the
+    reference's early stopping)."""
+    from .tensortools import metrics as _metrics
+    torch = _lib.require_gpu()
+    k = int(num_classes)
+    confusion = torch.zeros((k, k), dtype=torch.int64, device=torch.device("cuda", torch.cuda.current_device()))
+    items = ((b[0], tuple(b[1:3])) for b in batches)  # (images, (label, mask)): prefetch copies the images only
+    if prefetch > 0:
+        items = prefetch_to_device(items, depth=prefetch)
+    for images, (label, mask) in items:
+        if arithmetic == "f32":
+            net.evaluate(images, label, mask, confusion=confusion)
+        else:
+            net.evaluate(images, label, mask, confusion=confusion, arithmetic=arithmetic)
+    return _metrics.create_metrics(all_reduce_confusion(confusion, group))
+
+
+def all_reduce_confusion(confusion, group=None):
+    """ONE all-reduce(SUM) of an int64 K x K confusion matrix over the process group (RCCL for GPU tensors; gloo runs
+    it on a CPU copy); the matrix itself when no group of more than one rank is up.  Integer sums: every rank ends with
+    the same matrix bit for bit."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return confusion
+    home = confusion.device
+    t = confusion.contiguous()
+    if t.is_cuda and dist.get_backend(group) == "gloo":
+        t = t.cpu()
+    elif t.data_ptr() == confusion.data_ptr():
+        t = t.clone()
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return t.to(home)
+
+
 def merge_and_rank(local_index, local_score, num_examples, unlabelled, selection_size, group=None, ragged=False):
     """the collective + host tail of a ranking pass (shared by ``rank_confidence`` and ``bench.py``)"""
     import torch.distributed as dist

@@ -6,6 +6,7 @@
 #include "ssal_prof.h"
 #include "ssal_bottleneck_args.h"
 #include "ssal_bf16x3.h"
+#include "ssal_confusion.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -757,6 +758,11 @@ struct FinalOut {
     uint8_t *label, *mask;
     float *conf;
     int arith = SSAL_ARITH_F32;  // arithmetic mode of the whole call (rides here: every run_net caller builds one)
+    // evaluation pass (ssal_enet_evaluate_nhwc_arith): non-NULL eval_rep selects the confusion-matrix tail of the Final
+    // kernel; eval_label / eval_mask are the ground truth of the whole batch [n,h,w] (eval_mask NULL = weight 1)
+    const uint8_t *eval_label = nullptr, *eval_mask = nullptr;
+    unsigned long long *eval_rep = nullptr;
+    int eval_reps = 1;
 };
 
 // the ranking pass (no logits / label / mask / confidence output) evaluates Bottleneck5_1 inside the Final + score kernel:
@@ -772,6 +778,18 @@ hipError_t run_final(const ssal_enet *net, const NetWorkspace &V, const FinalOut
                      hipStream_t s)
 {
     const long px = (long)h * w;
+    if (f.eval_rep) {
+        const uint8_t *gl = f.eval_label + i0 * px, *gm = f.eval_mask ? f.eval_mask + i0 * px : nullptr;
+        if (fuse_5_1(net, f)) {
+            const DevLayer &L = net->layers[27];
+            return launch_bnk4_final_eval(V.a0, n, h / 2, w / 2, L.proj_w, L.proj_scale, L.proj_shift, L.proj_alpha, L.conv_w,
+                                          L.conv_scale, L.conv_shift, L.conv_alpha, L.exp_w, L.exp_scale, L.exp_shift,
+                                          L.res_alpha, net->layers[kNumLayers - 1].w, net->classes, gl, gm, f.eval_rep,
+                                          f.eval_reps, s);
+        }
+        return launch_final_eval(V.a1, n, h / 2, w / 2, net->layers[kNumLayers - 1].w, net->classes, gl, gm, f.eval_rep,
+                                 f.eval_reps, s);
+    }
     if (fuse_5_1(net, f)) {
         const DevLayer &L = net->layers[27];
         return launch_bnk4_final_score(V.a0, n, h / 2, w / 2, L.proj_w, L.proj_scale, L.proj_shift, L.proj_alpha, L.conv_w,
@@ -951,6 +969,46 @@ SSAL_API int ssal_enet_score_nhwc_arith(ssal_enet *net, const void *x_dev, int x
                      ws_bytes, stream, arithmetic);
 }
 
+// ---- evaluation pass: forward + argmax + confusion matrix, fused (validation epoch of active_learning.py) ----
+static int64_t conf_replica_bytes(int classes)
+{
+    return (int64_t)ssal::kConfMaxReps * ssal::conf_rep_stride(classes * classes) * 8;
+}
+
+SSAL_API int64_t ssal_enet_eval_workspace_bytes(const ssal_enet *net, int n, int h, int w)
+{
+    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0) return -1;
+    NetWorkspace W = carve(net, nullptr, 0, n, h, w);
+    return (W.bytes + 255) / 256 * 256 + conf_replica_bytes(net->classes) + 256;
+}
+
+SSAL_API int ssal_enet_evaluate_nhwc_arith(ssal_enet *net, const void *x_dev, int x_is_u8, int n, int h, int w, int arithmetic,
+                                           const uint8_t *labels_dev, const uint8_t *mask_dev, int64_t *confusion_dev,
+                                           void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    int rc = check_dims(net, n, h, w);
+    if (rc) return rc;
+    if ((rc = check_arith(arithmetic))) return rc;
+    if (!x_dev || !labels_dev || !confusion_dev || !ws_dev) return fail(SSAL_EINVAL, "NULL device pointer");
+    const int64_t need = ssal_enet_eval_workspace_bytes(net, n, h, w);
+    NetWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
+    if (!W.ok || ws_bytes < need)
+        return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need, (long long)ws_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    const int K = net->classes, reps = ssal::knobs().conf_reps;
+    unsigned long long *rep = (unsigned long long *)((char *)ws_dev + (W.bytes + 255) / 256 * 256);
+    HIP_TRY(hipMemsetAsync(rep, 0, (size_t)reps * ssal::conf_rep_stride(K * K) * 8, s));
+    FinalOut fin = {nullptr, SSAL_MEASURE_CONFIDENCE, 0.0f, nullptr, nullptr, nullptr};
+    fin.arith = arithmetic;
+    fin.eval_label = labels_dev;
+    fin.eval_mask = mask_dev;
+    fin.eval_rep = rep;
+    fin.eval_reps = reps;
+    HIP_TRY(run_net(net, x_dev, x_is_u8 != 0, n, h, w, W, fin, s));
+    HIP_TRY(launch_confusion_fold(rep, reps, K, confusion_dev, s));
+    return SSAL_OK;
+}
+
 // byte offsets (into the workspace passed to forward/score) of the tensors behind
 // ENet.endpoint_outputs (enet.py:311-318): [0] bottleneck5_1 [n,h/2,w/2,16],
 // [1] bottleneck4_2 [n,h/4,w/4,64], [2] bottleneck3_8 [n,h/8,w/8,128]; valid until the next call.
@@ -1127,6 +1185,33 @@ SSAL_API int ssal_score_logits_nhwc(const float *logits_dev, int n, int h, int w
     HIP_TRY(launch_score_logits(logits_dev, n, h, w, classes, measure, threshold, partial, label_dev,
                                 mask_dev, conf_dev, s));
     HIP_TRY(launch_reduce_mean(partial, n, score_blocks(h, w), (double)h * (double)w, scores_dev, s));
+    return SSAL_OK;
+}
+
+SSAL_API int64_t ssal_confusion_workspace_bytes(int classes)
+{
+    if (classes < 2 || classes > ssal::kConfMaxClasses) return -1;
+    return conf_replica_bytes(classes) + 256;
+}
+
+SSAL_API int ssal_confusion_matrix(const uint8_t *pred_dev, const uint8_t *labels_dev, const uint8_t *weights_dev,
+                                   int64_t pixels, int classes, int64_t *confusion_dev, void *ws_dev, int64_t ws_bytes,
+                                   void *stream)
+{
+    if (classes < 2 || classes > ssal::kConfMaxClasses)
+        return fail(SSAL_EINVAL, "classes must be in [2,32] (got %d)", classes);
+    if (pixels < 0) return fail(SSAL_EINVAL, "bad pixel count %lld", (long long)pixels);
+    if (!pred_dev || !labels_dev || !confusion_dev || !ws_dev) return fail(SSAL_EINVAL, "NULL device pointer");
+    if (ws_bytes < ssal_confusion_workspace_bytes(classes))
+        return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
+                    (long long)ssal_confusion_workspace_bytes(classes), (long long)ws_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    const int reps = ssal::knobs().conf_reps;
+    Bump b(ws_dev, ws_bytes);
+    unsigned long long *rep = b.take<unsigned long long>((int64_t)reps * ssal::conf_rep_stride(classes * classes));
+    HIP_TRY(hipMemsetAsync(rep, 0, (size_t)reps * ssal::conf_rep_stride(classes * classes) * 8, s));
+    HIP_TRY(launch_confusion(pred_dev, labels_dev, weights_dev, pixels, classes, rep, reps, s));
+    HIP_TRY(launch_confusion_fold(rep, reps, classes, confusion_dev, s));
     return SSAL_OK;
 }
 
@@ -1462,6 +1547,7 @@ SSAL_API int ssal_debug_set_knob(const char *name, int value)
     else if (n == "ic_dual") k.ic_dual = value != 0;
     else if (n == "ig_sb") k.ig_sb = value;
     else if (n == "ic_groups") k.ic_groups = value;
+    else if (n == "conf_reps") k.conf_reps = value < 1 ? 1 : value > ssal::kConfMaxReps ? ssal::kConfMaxReps : value;
 #ifdef SSAL_MEASURE
     else if (n == "ablate") k.ablate = value;
     else if (n == "bnk_split") k.bnk_split = value;
@@ -1481,11 +1567,11 @@ SSAL_API int ssal_debug_get_knobs(char *json_out, int64_t cap)
     measure = 1;
     ablate = k.ablate + 100 * k.bnk_split;  // any non-zero value makes `defaults` 0: bench.py refuses to time it as a result
 #endif
-    const int dflt = g_use_mfma && k.bnk_tw == 0 && k.bnk_o4 == 2 && k.bnk_xcd == 1 && k.asym_tw16 == ssal::ASYM_TW16_DEFAULT && k.bnk_qepi == ssal::BNK_QEPI_DEFAULT && k.img_groups == 2 && k.img_span == 4 && k.fuse_ends == 3 && k.img_lag == 0 && k.ig_div == 0 && k.ic_front == ssal::IC_FRONT_DEFAULT && k.ic_dual == ssal::IC_DUAL_DEFAULT && k.ig_sb == ssal::IG_SB_DEFAULT && k.ic_groups == ssal::IC_GROUPS_DEFAULT && ablate == 0 && !ssal::prof_enabled()
+    const int dflt = g_use_mfma && k.bnk_tw == 0 && k.bnk_o4 == 2 && k.bnk_xcd == 1 && k.asym_tw16 == ssal::ASYM_TW16_DEFAULT && k.bnk_qepi == ssal::BNK_QEPI_DEFAULT && k.img_groups == 2 && k.img_span == 4 && k.fuse_ends == 3 && k.img_lag == 0 && k.ig_div == 0 && k.ic_front == ssal::IC_FRONT_DEFAULT && k.ic_dual == ssal::IC_DUAL_DEFAULT && k.ig_sb == ssal::IG_SB_DEFAULT && k.ic_groups == ssal::IC_GROUPS_DEFAULT && k.conf_reps == ssal::CONF_REPS_DEFAULT && ablate == 0 && !ssal::prof_enabled()
                      && ssal::g_trace_buf == nullptr;
     snprintf(json_out, (size_t)cap, "{\"kernel_family\": %d, \"bnk_tw\": %d, \"bnk_o4\": %d, \"bnk_xcd\": %d, \"asym_tw16\": %d, \"bnk_qepi\": %d, \"img_groups\": %d, \"img_span\": %d, \"fuse_ends\": %d, "
-             "\"img_lag\": %d, \"ig_div\": %d, \"ic_front\": %d, \"ic_dual\": %d, \"ig_sb\": %d, \"ic_groups\": %d, \"ablate\": %d, \"measure_build\": %d, \"profiling\": %d, \"defaults\": %d}", g_use_mfma ? 1 : 0,
-             k.bnk_tw, k.bnk_o4, k.bnk_xcd, k.asym_tw16, k.bnk_qepi, k.img_groups, k.img_span, k.fuse_ends, k.img_lag, k.ig_div, k.ic_front, k.ic_dual, k.ig_sb, k.ic_groups, ablate, measure, ssal::prof_enabled() ? 1 : 0, dflt);
+             "\"img_lag\": %d, \"ig_div\": %d, \"ic_front\": %d, \"ic_dual\": %d, \"ig_sb\": %d, \"ic_groups\": %d, \"conf_reps\": %d, \"ablate\": %d, \"measure_build\": %d, \"profiling\": %d, \"defaults\": %d}", g_use_mfma ? 1 : 0,
+             k.bnk_tw, k.bnk_o4, k.bnk_xcd, k.asym_tw16, k.bnk_qepi, k.img_groups, k.img_span, k.fuse_ends, k.img_lag, k.ig_div, k.ic_front, k.ic_dual, k.ig_sb, k.ic_groups, k.conf_reps, ablate, measure, ssal::prof_enabled() ? 1 : 0, dflt);
     return SSAL_OK;
 }
 

@@ -57,6 +57,21 @@ hipError_t launch_bnk4_final_score(const float *x5, int N, int H, int W, const f
                                    const float *pa, const float *wc, const float *cs, const float *ct, const float *ca,
                                    const float *we, const float *es, const float *et, const float *ra, const float *wF, int K,
                                    int measure, double *partial, hipStream_t s);
+// The same two kernels with the evaluation tail (validation pass, active_learning.py:277-282 + tensortools/metrics.py):
+// argmax only, counted into a confusion histogram (ssal_confusion.h) whose per-workgroup sums are added into replica
+// (workgroup % reps) of rep [reps][conf_rep_stride(K * K)] u64.  gt_label / gt_mask [N,2H,2W] uint8, gt_mask NULL = 1.
+hipError_t launch_final_eval(const float *x, int N, int H, int W, const float *wF, int K, const uint8_t *gt_label,
+                             const uint8_t *gt_mask, unsigned long long *rep, int reps, hipStream_t s);
+hipError_t launch_bnk4_final_eval(const float *x5, int N, int H, int W, const float *wp, const float *ps, const float *pt,
+                                  const float *pa, const float *wc, const float *cs, const float *ct, const float *ca,
+                                  const float *we, const float *es, const float *et, const float *ra, const float *wF, int K,
+                                  const uint8_t *gt_label, const uint8_t *gt_mask, unsigned long long *rep, int reps,
+                                  hipStream_t s);
+// stand-alone confusion histogram (tensortools/metrics.py:226-257) into the replicas, and the fold of the replicas into the
+// caller's int64 [K][K] (adds)
+hipError_t launch_confusion(const uint8_t *pred, const uint8_t *labels, const uint8_t *weights, int64_t pixels, int K,
+                            unsigned long long *rep, int reps, hipStream_t s);
+hipError_t launch_confusion_fold(const unsigned long long *rep, int reps, int K, int64_t *confusion, hipStream_t s);
 // scores[n] = sum(partial[n, 0..blocks)) / pixels, fixed summation order (bitwise reproducible)
 hipError_t launch_reduce_mean(const double *partial, int N, int blocks, double pixels,
                               double *scores, hipStream_t s);
@@ -128,6 +143,7 @@ hipError_t launch_upsample_mfma(const float *x, float *y, const uint8_t *code, i
 // product build produces identical results.  Work-skipping "ablate" and the SSAL_* environment reads exist only in
 // -DSSAL_MEASURE builds).
 constexpr int IC_FRONT_DEFAULT = 3, IC_DUAL_DEFAULT = 1, ASYM_TW16_DEFAULT = 1, IG_SB_DEFAULT = 3, IC_GROUPS_DEFAULT = 1, BNK_QEPI_DEFAULT = 2;
+constexpr int CONF_REPS_DEFAULT = 8;
 struct Knobs {
     int bnk_tw;      // 16 = force 8x16 tiles in the 128-channel bottleneck kernels
     int bnk_o4;      // k_bottleneck_o4 (8x16 tiles, four workgroups per CU): 2 (default) = where the phase sub-image is <= 16 wide, 1 = everywhere, 0 = never
@@ -143,6 +159,7 @@ struct Knobs {
     int img_lag;     // chain g of the image-group schedule starts this many layers behind chain g - 1 (default 0)
     int img_span;    // which layers run in image groups: 0 = Bottleneck2_1..3_8, 1 = + 2_0, 2 = 1_0..5_1, 3 = Initial..5_1, 4 = Initial..Final + score (default)
     int img_groups;  // ENet: the layers of img_span run as this many image groups on side streams (default 2; 1 = everything on the caller's stream)
+    int conf_reps;   // replicas of the confusion accumulator the evaluation tails add into (1 .. 64; default 8)
 #ifdef SSAL_MEASURE
     int ablate;      // measurement builds only: 1 = stop after the projection phase, 2 = skip it (results invalid)
     int bnk_split;   // measurement builds only: 1 = the regular 128-channel bottleneck on bf16x3 split operands (ssal_split_probe.hip; NOT bit-identical)

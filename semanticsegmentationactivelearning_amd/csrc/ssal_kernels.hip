@@ -11,6 +11,7 @@
 #include "ssal_internal.h"
 #include "ssal_prof.h"
 #include "ssal_score.h"
+#include "ssal_confusion.h"
 #include <float.h>
 
 namespace ssal {
@@ -417,24 +418,52 @@ struct Bnk4Args {
 };
 constexpr int F51_PW = FS_TP + 2;    // projected window: 19 x 19
 
+// Evaluation tail (EVAL instantiations, OUT = false): the ground-truth planes of the OUTPUT pixels and the confusion
+// accumulator replicas (ssal_confusion.h).  gt_mask NULL = weight 1.
+struct EvalArgs {
+    const uint8_t *gt_label, *gt_mask;  // [N, 2H, 2W]
+    unsigned long long *rep;            // [reps][conf_rep_stride(K * K)]
+    int reps;
+};
+
 // OUT = false: score only (the ranking pass): logits / label / mask / conf are not touched, which frees the
 // SGPRs their pointers would pin and lets the kernel taps stream two input channels at a time.
-template <int K, bool OUT, bool F51 = false>
+// EVAL = true (with OUT = false): the validation pass -- the same logits and argmax (pixel_score's first-maximum rule),
+// no softmax / measure / fp64 partials; each output pixel adds its mask value at (gt label, argmax) of the workgroup's LDS
+// histogram, flushed into replica (workgroup % reps) of the confusion accumulator.
+template <int K, bool OUT, bool F51 = false, bool EVAL = false>
 __global__ __launch_bounds__(256) void k_final_score(const float *__restrict__ x, int N, int H,
                                                      int W, const float *__restrict__ wF,
                                                      float *__restrict__ logits, int measure,
                                                      float threshold, double *__restrict__ partial,
                                                      uint8_t *__restrict__ label,
                                                      uint8_t *__restrict__ mask,
-                                                     float *__restrict__ conf, Bnk4Args b5)
+                                                     float *__restrict__ conf, Bnk4Args b5, EvalArgs ev)
 {
+    static_assert(!(EVAL && OUT), "the evaluation tail has no per-pixel outputs");
     __shared__ double red[4];
     __shared__ __attribute__((aligned(16))) float tile[FS_TP * FS_TP * FS_PS];
     __shared__ __attribute__((aligned(16))) float p1[F51 ? F51_PW * F51_PW * 4 : 4];
+    __shared__ unsigned hist[EVAL ? K * K : 1];
     const int n = blockIdx.y;
     const long HW = (long)H * W;
     const int tiles_x = (W + FS_T - 1) / FS_T;
     const int i0 = (int)(blockIdx.x / tiles_x) * FS_T, j0 = (int)(blockIdx.x % tiles_x) * FS_T;
+    // EVAL: the ground truth of this thread's 2 x 2 output quad is requested first, so that it arrives while the window
+    // is staged (four label + four mask bytes, packed into one register each after the staging barrier)
+    uint8_t gtl[4] = {0, 0, 0, 0}, gtm[4] = {1, 1, 1, 1};
+    if constexpr (EVAL) {
+        hist_zero(hist, K * K);  // ordered before the adds by the barrier after the staging
+        const int gi = i0 + (int)threadIdx.x / FS_T, gj = j0 + (int)threadIdx.x % FS_T;
+        if (gi < H && gj < W) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const long op = ((long)n * 2 * H + 2 * gi + (q >> 1)) * (2L * W) + 2 * gj + (q & 1);
+                gtl[q] = ev.gt_label[op];
+                if (ev.gt_mask) gtm[q] = ev.gt_mask[op];
+            }
+        }
+    }
     if (F51) {
         const float *x5 = b5.x5 + (long)n * HW * 16;
         // ---- phase P: both passes' loads are requested first (361 pixels over 256 threads)
@@ -549,6 +578,8 @@ __global__ __launch_bounds__(256) void k_final_score(const float *__restrict__ x
     const bool valid = i < H && j < W;
     double local = 0.0;
     if (valid) {
+        const unsigned gl4 = gtl[0] | gtl[1] << 8 | gtl[2] << 16 | (unsigned)gtl[3] << 24;
+        const unsigned gm4 = gtm[0] | gtm[1] << 8 | gtm[2] << 16 | (unsigned)gtm[3] << 24;
         float va[16], vb[16], vc[16], vd[16];
         const float *la = tile + ((ti + 1) * FS_TP + tj + 1) * FS_PS;  // own pixel; b = above, c = left, d = above-left
 #pragma unroll
@@ -564,7 +595,8 @@ __global__ __launch_bounds__(256) void k_final_score(const float *__restrict__ x
         }
         const float inv_logK = 1.0f / __logf((float)K);
         const int Wo = 2 * W;
-        typedef FsTap<K, (!OUT && 2 * ((K + 1) / 2) <= 20) ? 2 : 1> FT;
+        // (EVAL: one input channel per group -- the histogram's wave-level peel needs SGPRs too; with G = 2 ~170 of them spill)
+        typedef FsTap<K, (!OUT && !EVAL && 2 * ((K + 1) / 2) <= 20) ? 2 : 1> FT;
         constexpr int KP = FT::KP, TS = FT::TS;
         float w0[FT::WN], w1[FT::WN];
         f32x2 acc2[KP];
@@ -576,6 +608,15 @@ __global__ __launch_bounds__(256) void k_final_score(const float *__restrict__ x
             for (int k = 0; k < K; ++k) acc[k] = (k & 1) ? acc2[k >> 1].y : acc2[k >> 1].x;
 #pragma unroll
             for (int k = 0; k < KP; ++k) acc2[k] = (f32x2){0.0f, 0.0f};
+            if constexpr (EVAL) {
+                float m = acc[0];
+                int am = 0;
+#pragma unroll
+                for (int k = 1; k < K; ++k)
+                    if (acc[k] > m) { m = acc[k]; am = k; }
+                hist_add_wave(hist, ((gl4 >> (8 * quad)) & 0xFFu) * K + (unsigned)am, (gm4 >> (8 * quad)) & 0xFFu, K * K);
+                return;
+            }
             const int oy = 2 * i + (quad >> 1), ox = 2 * j + (quad & 1);
             const long op = ((long)n * 2 * H + oy) * Wo + ox;
             if (OUT && logits) {
@@ -610,6 +651,11 @@ __global__ __launch_bounds__(256) void k_final_score(const float *__restrict__ x
         FT::apply(acc2, va, tap(1, 1), nullptr, w0, w1);
         finish_quad(3);
     }
+    if constexpr (EVAL) {
+        __syncthreads();
+        hist_flush(hist, K * K, ev.rep + (long)conf_rep_stride(K * K) * (((long)n * gridDim.x + blockIdx.x) % ev.reps));
+        return;
+    }
     const double r = block_sum_256(local, red);
     if (threadIdx.x == 0) partial[(long)n * gridDim.x + blockIdx.x] = r;
 }
@@ -630,7 +676,7 @@ hipError_t launch_bnk4_final_score(const float *x5, int N, int H, int W, const f
 #define SSAL_FS51(KK)                                                                                               \
     case KK:                                                                                                        \
         hipLaunchKernelGGL((k_final_score<KK, false, true>), grid, block, 0, s, nullptr, N, H, W, wF, nullptr, measure, \
-                           0.0f, partial, nullptr, nullptr, nullptr, b);                                            \
+                           0.0f, partial, nullptr, nullptr, nullptr, b, EvalArgs{});                                \
         break;
     switch (K) {
         SSAL_FS51(2) SSAL_FS51(3) SSAL_FS51(4) SSAL_FS51(5) SSAL_FS51(6) SSAL_FS51(7) SSAL_FS51(8) SSAL_FS51(9)
@@ -659,10 +705,10 @@ hipError_t launch_final_score(const float *x, int N, int H, int W, const float *
     case KK:                                                                                               \
         if (out)                                                                                           \
             hipLaunchKernelGGL((k_final_score<KK, true>), grid, block, 0, s, x, N, H, W, wF, logits, measure, \
-                               threshold, partial, label, mask, conf, b);                                  \
+                               threshold, partial, label, mask, conf, b, EvalArgs{});                      \
         else                                                                                               \
             hipLaunchKernelGGL((k_final_score<KK, false>), grid, block, 0, s, x, N, H, W, wF, logits, measure, \
-                               threshold, partial, label, mask, conf, b);                                  \
+                               threshold, partial, label, mask, conf, b, EvalArgs{});                      \
         break;
     switch (K) {
         SSAL_FS(2) SSAL_FS(3) SSAL_FS(4) SSAL_FS(5) SSAL_FS(6) SSAL_FS(7) SSAL_FS(8) SSAL_FS(9)
@@ -675,6 +721,57 @@ hipError_t launch_final_score(const float *x, int N, int H, int W, const float *
     }
 #undef SSAL_FS
     return hipGetLastError();
+}
+
+// Evaluation tails: the Final kernel (plain, or with Bottleneck5_1 inside when x5 / the 5_1 tensors are given) with the
+// confusion-matrix tail instead of the score.  gt_label / gt_mask [N, 2H, 2W]; rep [reps][conf_rep_stride(K * K)] u64.
+static hipError_t final_eval_any(const float *x, int N, int H, int W, const float *wF, int K, const Bnk4Args *b5,
+                                 const uint8_t *gt_label, const uint8_t *gt_mask, unsigned long long *rep, int reps,
+                                 hipStream_t s)
+{
+    dim3 grid(final_score_blocks(H, W), N), block(256);
+    const double pix = (double)N * H * W;
+    ProfScope prof(b5 ? "k_final_eval<fused 5_1>" : "k_final_eval",
+                   2.0 * pix * 9 * 16 * K + (b5 ? 2.0 * pix * (16.0 * 4 + 9.0 * 4 * 4 + 4.0 * 16) : 0.0),
+                   4.0 * pix * 16 + 4.0 * pix * (gt_mask ? 2 : 1), s);
+    const Bnk4Args none = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const EvalArgs ev = {gt_label, gt_mask, rep, reps};
+#define SSAL_FE(KK)                                                                                                   \
+    case KK:                                                                                                          \
+        if (b5)                                                                                                       \
+            hipLaunchKernelGGL((k_final_score<KK, false, true, true>), grid, block, 0, s, nullptr, N, H, W, wF, nullptr, \
+                               0, 0.0f, nullptr, nullptr, nullptr, nullptr, *b5, ev);                                \
+        else                                                                                                          \
+            hipLaunchKernelGGL((k_final_score<KK, false, false, true>), grid, block, 0, s, x, N, H, W, wF, nullptr,     \
+                               0, 0.0f, nullptr, nullptr, nullptr, nullptr, none, ev);                               \
+        break;
+    switch (K) {
+        SSAL_FE(2) SSAL_FE(3) SSAL_FE(4) SSAL_FE(5) SSAL_FE(6) SSAL_FE(7) SSAL_FE(8) SSAL_FE(9)
+        SSAL_FE(10) SSAL_FE(11) SSAL_FE(12) SSAL_FE(13) SSAL_FE(14) SSAL_FE(15) SSAL_FE(16)
+        SSAL_FE(17) SSAL_FE(18) SSAL_FE(19) SSAL_FE(20) SSAL_FE(21) SSAL_FE(22) SSAL_FE(23)
+        SSAL_FE(24) SSAL_FE(25) SSAL_FE(26) SSAL_FE(27) SSAL_FE(28) SSAL_FE(29) SSAL_FE(30)
+        SSAL_FE(31) SSAL_FE(32)
+    default:
+        return hipErrorInvalidValue;
+    }
+#undef SSAL_FE
+    return hipGetLastError();
+}
+
+hipError_t launch_bnk4_final_eval(const float *x5, int N, int H, int W, const float *wp, const float *ps, const float *pt,
+                                  const float *pa, const float *wc, const float *cs, const float *ct, const float *ca,
+                                  const float *we, const float *es, const float *et, const float *ra, const float *wF, int K,
+                                  const uint8_t *gt_label, const uint8_t *gt_mask, unsigned long long *rep, int reps,
+                                  hipStream_t s)
+{
+    const Bnk4Args b = {x5, wp, ps, pt, pa, wc, cs, ct, ca, we, es, et, ra};
+    return final_eval_any(nullptr, N, H, W, wF, K, &b, gt_label, gt_mask, rep, reps, s);
+}
+
+hipError_t launch_final_eval(const float *x, int N, int H, int W, const float *wF, int K, const uint8_t *gt_label,
+                             const uint8_t *gt_mask, unsigned long long *rep, int reps, hipStream_t s)
+{
+    return final_eval_any(x, N, H, W, wF, K, nullptr, gt_label, gt_mask, rep, reps, s);
 }
 
 // scores[n] = (sum of partial[n,:]) / pixels; one block per image; fixed order => reproducible.

@@ -269,6 +269,44 @@ class ENet(_lib.DeviceState):
             return scores, {"label": label, "mask": mask, "confidence": conf}
         return scores
 
+    # ---- fused validation pass (active_learning.py:277-282 + tensortools.metrics.Metrics :390-427) ----------------------
+    def evaluate(self, inputs, labels, mask=None, confusion=None, arithmetic="f32"):
+        """forward(training=False) + argmax + masked confusion matrix in one pass: the logits and the predicted labels
+        never reach HBM (the Final kernel counts them, ``ssal_enet_evaluate_nhwc_arith``).
+
+        ``inputs`` as ``score`` accepts (float32 or decoded uint8 NHWC); ``labels`` / ``mask`` [N, H, W] uint8-valued
+        (``mask`` None = weight 1; a mask value is the pixel's weight, as in the reference's bincount).  Returns an
+        int64 [K, K] device tensor (row = label, column = prediction); with ``confusion`` given (int64 [K, K] on the
+        input's device) the batch is ADDED into it and it is returned.  Keys >= K * K (label 255) are dropped."""
+        from ...tensortools import metrics as _metrics
+        arith = _lib.arithmetic_code(arithmetic)
+        torch = _lib.require_gpu()
+        x = self._prepare(inputs, False)
+        n, h, w, _ = x.shape
+        lab = _metrics._as_u8(labels, x.device, "labels")
+        msk = _metrics._as_u8(mask, x.device, "mask") if mask is not None else None
+        for name, t in (("labels", lab), ("mask", msk)):
+            if t is not None and tuple(t.shape) != (n, h, w):
+                raise ValueError("%s must have shape %s (got %s)" % (name, (n, h, w), tuple(t.shape)))
+        k = self.classes
+        if confusion is None:
+            confusion = torch.zeros((k, k), dtype=torch.int64, device=x.device)
+        elif (confusion.dtype != torch.int64 or tuple(confusion.shape) != (k, k) or confusion.device != x.device
+              or not confusion.is_contiguous()):
+            raise ValueError("confusion must be a contiguous int64 [%d, %d] tensor on %s" % (k, k, x.device))
+        L = _lib.lib()
+        with torch.cuda.device(x.device):
+            handle = self._sync_handle()
+            nbytes = L.ssal_enet_eval_workspace_bytes(handle, n, h, w)
+            if nbytes < 0:
+                raise ValueError("bad input dims %s" % (tuple(x.shape),))
+            ws = self._workspace(nbytes, x.device)
+            _lib.check(L.ssal_enet_evaluate_nhwc_arith(
+                handle, _lib.dev_ptr(x), int(x.dtype == torch.uint8), n, h, w, arith, _lib.dev_ptr(lab), _lib.dev_ptr(msk),
+                _lib.dev_ptr(confusion), _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))
+            self._note_call(ws, (n, h, w), "score")
+        return confusion
+
     # ---- single layer (Layer.__call__) -----------------------------------------------------
     def _run_layer(self, layer, x, argmax_in, want_argmax, arithmetic="f32"):
         torch = _lib.require_gpu()

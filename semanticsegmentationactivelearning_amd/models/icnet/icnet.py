@@ -228,6 +228,24 @@ class ICNet(_lib.DeviceState):
             return scores, {"label": label, "mask": mask, "confidence": conf}
         return scores
 
+    # ---- validation pass (active_learning.py:277-282 + tensortools.metrics.Metrics :390-427) ----------------------------
+    def evaluate(self, inputs, labels, mask=None, confusion=None):
+        """forward(training=False) + argmax + masked confusion matrix: ``ENet.evaluate``'s contract (int64 [K, K] device
+        tensor, row = label, column = prediction; ADDED into ``confusion`` when given).  Two steps: ``score(...,
+        return_label=True)`` writes the argmax plane (uint8, 1 B / pixel), then the device op
+        ``tensortools.metrics.confusion_mat`` counts it.  (A tail fused into the up-sampling score kernel, as ENet's is
+        into its Final kernel, is not implemented: DESIGN.md §12.)"""
+        from ...tensortools import metrics as _metrics
+        _, extra = self.score(inputs, measure="confidence", return_label=True)
+        pred = extra["label"]
+        n, h, w = pred.shape
+        lab = _metrics._as_u8(labels, pred.device, "labels")
+        msk = _metrics._as_u8(mask, pred.device, "mask") if mask is not None else None
+        for name, t in (("labels", lab), ("mask", msk)):
+            if t is not None and tuple(t.shape) != (n, h, w):
+                raise ValueError("%s must have shape %s (got %s)" % (name, (n, h, w), tuple(t.shape)))
+        return _metrics.confusion_mat(lab, pred, self.classes, weights=msk, out=confusion)
+
     # ---- intermediate tensors of the most recent call --------------------------------------
     def endpoint_names(self):
         L = _lib.lib()
