@@ -268,6 +268,43 @@ int ssal_debug_set_trace(void *buf_dev, int64_t bytes);
 int ssal_profile_enable(int on);
 int ssal_profile_collect(char *json_out, int64_t cap);
 
+/* ---- PNG decode (no reference counterpart: tensortools/input.py decodes with tf.image.decode_image, :246-248) ----
+ * A batch of zlib payloads (the concatenated IDAT data of 8-bit, non-interlaced PNGs of colour type 0, 2, 3 or 6) is
+ * inflated, unfiltered and placed straight into NHWC batch tensors on the device.  Each stream is described by
+ * SSAL_PNG_DESC int64 fields:
+ *   [0] payload offset, [1] payload length (bytes, in payload_dev), [2] width, [3] height, [4] bytes per pixel (1, 3, 4),
+ *   [5] workspace offset (filled by ssal_png_plan), [6] destination frame, [7] role (SSAL_PNG_ROLE_*),
+ *   [8] destination channel offset and [9] channel count (image role: source channels [0, count) go to channels
+ *   [offset, offset + count) of the batch), [10] crop top, [11] crop left, [12] left-right flip (0 / 1), [13..15] zero.
+ * The image role writes image_dev (uint8, or float32 = u8 * float32(1/255) when image_f32) and, when image_dist_dev is
+ * given, clip(image * scale_dev[frame][channel], 0, 1) (float32); the label role writes channel 0 through generate_mask
+ * (tensortools/input.py:17-31): label_dev = value, 0 where value == 255; mask_dev = value != 255.  All outputs are
+ * [frames][height][width]([channels]) with the batch's height x width the crop window.
+ * status_dev int32 [n_streams] receives one SSAL_PNG_* word per stream; a stream that is not SSAL_PNG_OK writes nothing to
+ * the outputs.  Every read stays inside the stream's payload extent and every write inside its workspace slot and its
+ * destination planes, whatever the payload bytes hold (descriptors out of range give SSAL_PNG_UNSUPPORTED). */
+#define SSAL_PNG_DESC 16
+#define SSAL_PNG_ROLE_IMAGE 0
+#define SSAL_PNG_ROLE_LABEL 1
+#define SSAL_PNG_OK 0
+#define SSAL_PNG_TRUNCATED 1     /* the input ends before the final block or the Adler-32 trailer */
+#define SSAL_PNG_BAD_CODES 2     /* invalid block type, stored length, code-length set or symbol */
+#define SSAL_PNG_BAD_DISTANCE 3  /* a match reaches before the start of the output */
+#define SSAL_PNG_SIZE 4          /* the output is longer (or shorter) than height * (1 + width * bpp) */
+#define SSAL_PNG_ADLER 5         /* Adler-32 mismatch */
+#define SSAL_PNG_BAD_FILTER 6    /* a scanline filter type > 4 */
+#define SSAL_PNG_UNSUPPORTED 7   /* zlib header CM != 8 / FDICT = 1 / bad check bits, or a descriptor out of range */
+/* assigns every stream its workspace slot (field [5]) and returns the workspace size in bytes; -1 on a bad descriptor */
+int64_t ssal_png_plan(int64_t n_streams, int64_t *desc_host);
+int ssal_png_decode_nhwc(const uint8_t *payload_dev, int64_t payload_bytes, const int64_t *desc_dev, int64_t n_streams,
+                         int frames, int height, int width, int channels, const float *scale_dev, void *image_dev,
+                         int image_f32, float *image_dist_dev, uint8_t *label_dev, uint8_t *mask_dev, int32_t *status_dev,
+                         void *ws_dev, int64_t ws_bytes, void *stream);
+/* the same inflate / unfilter source on the host, single-threaded (tests): a zlib stream into out[0, out_cap)
+ * (*out_len = bytes produced), and an in-place unfilter of height rows of (1 filter byte + width * bpp); *status as above */
+int ssal_inflate_host(const uint8_t *in, int64_t in_len, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t *status);
+int ssal_png_unfilter_host(uint8_t *raw, int height, int width, int bpp, int32_t *status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -154,6 +154,11 @@ PROTOTYPES = {
     "ssal_pyramid_pooling": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i64, _vp]),
     "ssal_upscore_workspace_bytes": (_i64, [_i, _i, _i]),
     "ssal_upscore_logits_nhwc": (_i, [_vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    # ---- PNG decode (include/ssal_enet.h) ----
+    "ssal_png_plan": (_i64, [_i64, _vp]),
+    "ssal_png_decode_nhwc": (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_inflate_host": (_i, [_vp, _i64, _vp, _i64, _c.POINTER(_i64), _c.POINTER(_c.c_int32)]),
+    "ssal_png_unfilter_host": (_i, [_vp, _i, _i, _i, _c.POINTER(_c.c_int32)]),
     # ---- measurement aids (include/ssal_enet.h) ----
     "ssal_profile_enable": (_i, [_i]),
     "ssal_profile_collect": (_i, [_c.c_char_p, _i64]),

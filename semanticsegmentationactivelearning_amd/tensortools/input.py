@@ -29,6 +29,7 @@ import weakref
 import numpy as np
 
 from . import tfrecord
+from . import _gpu_decode
 from .._lib import usable_cores
 
 DEFAULT_FORMAT = {  # reference input.py:165-172 (key -> FixedLenFeature default)
@@ -99,7 +100,7 @@ class InputStage:
     """Holds named datasets and ONE re-initialisable iterator shared by them (reference :34-233)."""
 
     def __init__(self, input_shape=[512, 512], scope="Dataset", modalities=(), seed=None, workers=None,
-                 image_dtype=np.float32, pin_memory=False, pin_buffers=6):
+                 image_dtype=np.float32, pin_memory=False, pin_buffers=6, decode="cpu", decode_ahead=256):
         """``image_dtype=np.uint8`` (not in the reference): hand out the undistorted image as the decoded uint8
         frame instead of float32 in [0,1]; ``ENet.score`` converts it on the GPU (same bits, a quarter of the
         host-to-device bytes).
@@ -107,7 +108,15 @@ class InputStage:
         ``pin_memory=True`` (not in the reference; needs the GPU runtime): the image batch is assembled directly
         in page-locked memory and handed out as a CPU torch tensor, so that ``rank_confidence(..., prefetch=2)``
         copies it asynchronously while the previous batch is being scored.  The batches are views of a ring of
-        ``pin_buffers`` buffers: a batch stays valid until ``pin_buffers - 1`` further batches have been drawn."""
+        ``pin_buffers`` buffers: a batch stays valid until ``pin_buffers - 1`` further batches have been drawn.
+
+        ``decode="gpu"`` (not in the reference; needs the GPU runtime): PNG frames are decoded on the GPU
+        (``_lib`` ``ssal_png_decode_nhwc``).  The workers only read the records and parse the PNG chunks
+        (``tensortools.png``); the compressed payloads travel through the page-locked ring, and ``decode_ahead`` frames
+        are inflated per launch while the previous launch's batches are being consumed.  Batches come out as CUDA
+        tensors with the CPU path's layout and bits.  An image the device decoder does not take (JPEG, 16-bit, bit
+        depths below 8, interlaced, colour type 4, a zlib preset dictionary) or whose stream fails on the device is
+        decoded by the Pillow path instead, one example at a time; ``decode_stats`` counts both kinds."""
         self.logger = logging.getLogger(__name__)
         if np.dtype(image_dtype) not in (np.dtype(np.float32), np.dtype(np.uint8)):
             raise ValueError("image_dtype must be float32 or uint8")
@@ -130,6 +139,13 @@ class InputStage:
             self.shape = [None, None, None]
         self.modalities = tuple(modalities)
         self.datasets = {}
+        if decode not in ("cpu", "gpu"):
+            raise ValueError("decode must be 'cpu' or 'gpu' (got %r)" % (decode,))
+        self.decode = decode
+        self.decode_ahead = int(decode_ahead)
+        if self.decode_ahead < 1:
+            raise ValueError("decode_ahead must be >= 1")
+        self.decode_stats = {"gpu": 0, "fallback": 0}  # examples decoded on the GPU / by the Pillow path
         self._rng = np.random.default_rng(seed)
         self._workers = workers if workers is not None else max(1, usable_cores(cap=32) - 1)
         self._iter = None
@@ -191,6 +207,9 @@ class InputStage:
 
     def _batches(self, files, aux, batch_size, augment):
         seeds = self._rng.integers(0, 2 ** 63 - 1, size=len(files))
+        if self.decode == "gpu":
+            yield from _gpu_decode.batches(self, files, aux, batch_size, augment, seeds)
+            return
         with ThreadPoolExecutor(self._workers) as pool:
             window = max(2 * batch_size, self._workers)  # prefetch depth (reference: prefetch(batch_size))
             futures = []
@@ -225,7 +244,15 @@ class InputStage:
         shape = (len(images),) + tuple(images[0].shape)
         dtype = torch.uint8 if images[0].dtype == np.uint8 else torch.float32
         need = int(np.prod(shape))
-        slot = self._pin_pos % self.pin_buffers
+        out = self._pin_slot(need, dtype)[:need].view(shape)
+        np.stack(images, out=out.numpy())
+        return out
+
+    def _pin_slot(self, need, dtype, ring=None):
+        """the next buffer of the page-locked ring (of ``ring`` buffers, default ``pin_buffers``), at least ``need``
+        elements of ``dtype``, once no copy reads it"""
+        import torch
+        slot = self._pin_pos % (ring or self.pin_buffers)
         self._pin_pos += 1
         if slot >= len(self._pinned):
             self._pinned.append(None)
@@ -239,9 +266,7 @@ class InputStage:
             buf = self._pinned[slot]
             _PINNED_SLOTS[buf.data_ptr()] = (buf.numel() * buf.element_size(), weakref.ref(self), slot)
             self._slot_bases.add(buf.data_ptr())
-        out = self._pinned[slot][:need].view(shape)
-        np.stack(images, out=out.numpy())
-        return out
+        return self._pinned[slot]
 
     def copy_issued(self, tensor, event):
         """see the module-level ``copy_issued``"""
