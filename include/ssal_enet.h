@@ -257,6 +257,22 @@ int ssal_debug_set_knob(const char *name, int value);
  * in its result line and refuses to time anything else. */
 int ssal_debug_get_knobs(char *json_out, int64_t cap);
 
+/* Host-only query of the layer dispatch (no handle, no device; debug aid for tests): which kernel a layer of the given form
+ * would launch on an h x w input (SSAL_LAYER_INITIAL: the h x w image, asking for the Initial + Bottleneck1_0 launch) under
+ * the current kernel family and knobs.  kind: SSAL_LAYER_*; cin / cout / f: input, output and bottleneck-width channels;
+ * asym: the asymmetric (5,1) + (1,5) block; arithmetic: SSAL_ARITH_*.  An upsample is asked for pooling-derived indices (the
+ * window-code form every whole-network call uses).  Writes SSAL_DISPATCH_* to *kernel_out: the generic kernels, the fused fp32
+ * kernel, or the fused kernel of the opt-in bf16x3 mode.  The fused kernels compute offsets inside one image in 32 bits; a
+ * shape beyond a fused launcher's per-image limit is dispatched to the exact fp32 kernels instead. */
+#define SSAL_LAYER_INITIAL 0
+#define SSAL_LAYER_REGULAR 1
+#define SSAL_LAYER_DOWN    2
+#define SSAL_LAYER_UP      3
+#define SSAL_DISPATCH_GENERIC       0
+#define SSAL_DISPATCH_FUSED         1
+#define SSAL_DISPATCH_FUSED_BF16X3  2
+int ssal_debug_layer_dispatch(int kind, int cin, int cout, int f, int asym, int h, int w, int arithmetic, int *kernel_out);
+
 /* measurement aid, only functional in a -DSSAL_PHASE_TRACE build (tools/phase_trace.py; SSAL_ENOTIMPL
  * otherwise): the fused bottleneck kernels write 16 x uint64 per wave (shader-clock phase marks,
  * 100 MHz realtime of first / last mark, HW_ID, XCC_ID) into buf_dev; NULL switches it off. */

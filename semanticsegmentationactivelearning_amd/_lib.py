@@ -131,6 +131,7 @@ PROTOTYPES = {
     "ssal_debug_set_trace": (_i, [_vp, _i64]),
     "ssal_debug_set_knob": (_i, [ctypes.c_char_p, _i]),
     "ssal_debug_get_knobs": (_i, [_c.c_char_p, _i64]),
+    "ssal_debug_layer_dispatch": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _c.POINTER(_i)]),
     # ---- include/ssal_icnet.h ----
     "ssal_icnet_create": (_i, [_i, _i, _c.POINTER(_vp)]),
     "ssal_icnet_destroy": (_i, [_vp]),
@@ -431,6 +432,19 @@ def get_knobs():
     inj = sorted(set(ENV_INJECTED) | ({"GPU_MAX_HW_QUEUES"} if os.environ.get("SSAL_BENCH_INJECTED_HWQ") else set()))
     out["env"] = {"GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES"), "injected": inj}
     return out
+
+
+LAYER_KINDS = {"initial": 0, "regular": 1, "down": 2, "up": 3}           # SSAL_LAYER_*
+DISPATCH_NAMES = {0: "generic", 1: "fused", 2: "fused_bf16x3"}        # SSAL_DISPATCH_*
+
+
+def layer_dispatch(kind, cin, cout, f, asym, h, w, arithmetic="f32"):
+    """host-only: which kernel the layer dispatch picks for a layer of this form on an h x w input ("generic", "fused" or
+    "fused_bf16x3"; include/ssal_enet.h: ssal_debug_layer_dispatch).  Needs no GPU."""
+    out = _c.c_int(-1)
+    check(lib().ssal_debug_layer_dispatch(LAYER_KINDS[kind], int(cin), int(cout), int(f), int(bool(asym)), int(h), int(w),
+                                          arithmetic_code(arithmetic), _c.byref(out)))
+    return DISPATCH_NAMES[out.value]
 
 
 def set_knob(name, value):

@@ -182,6 +182,15 @@ def pad_to_length(index, score, length):
     return index, score
 
 
+def _check_arithmetic(net_call, arithmetic):
+    """ValueError, before any GPU work, for an unknown mode or a non-default one the model's call does not take (ICNet has
+    no opt-in arithmetic: its score / evaluate take no ``arithmetic`` argument)"""
+    import inspect
+    _lib.arithmetic_code(arithmetic)
+    if arithmetic != "f32" and "arithmetic" not in inspect.signature(net_call).parameters:
+        raise ValueError("arithmetic=%r: %s has no such mode (only 'f32')" % (arithmetic, type(net_call.__self__).__name__))
+
+
 def rank_confidence(net, batches, num_examples, unlabelled, selection_size, measure="entropy",
                     group=None, prefetch=0, ragged=False, arithmetic="f32"):
     """Mirror of ``rank_confidence()`` (reference :682-715).
@@ -200,6 +209,7 @@ def rank_confidence(net, batches, num_examples, unlabelled, selection_size, meas
     length (+ one flag entry).  A rank whose shard is longer raises ``ValueError`` -- on EVERY rank, after the
     collective, so nobody is left blocking in it.  ``ragged=True`` is for callers that split the pool some other way
     (shard lengths unknown to the other ranks): it costs one extra all-reduce(MAX) to agree on the length."""
+    _check_arithmetic(net.score, arithmetic)
     torch = _lib.require_gpu()
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
@@ -232,6 +242,7 @@ def evaluate(net, batches, num_classes, group=None, prefetch=2, arithmetic="f32"
     with exactly ONE all-reduce.  Returns ``tensortools.metrics.create_metrics`` of the total (``MeanIoU`` decides the
     reference's early stopping)."""
     from .tensortools import metrics as _metrics
+    _check_arithmetic(net.evaluate, arithmetic)
     torch = _lib.require_gpu()
     k = int(num_classes)
     confusion = torch.zeros((k, k), dtype=torch.int64, device=torch.device("cuda", torch.cuda.current_device()))

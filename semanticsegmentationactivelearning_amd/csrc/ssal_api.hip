@@ -526,26 +526,41 @@ ConvArgs conv_args(const float *x, int N, int H, int W, int Cin, const float *w,
 // shape is supported (default), 0 = generic kernels everywhere.  Both are bit-identical.
 bool g_use_mfma = true;
 
+// Which kernel a layer launches (ssal_debug_layer_dispatch reports the same decision): a fused kernel only where its launcher
+// supports the layer's form and its per-image size limit admits h x w (the *_fits functions next to the kernels: 32-bit
+// offsets inside one image); the opt-in bf16x3 kernel only where, in addition, the layer carries packed bf16x3 weights and
+// that launcher's own limit admits the shape.  Everything else runs the exact fp32 kernels, fused or generic.
+enum Path { P_GENERIC = SSAL_DISPATCH_GENERIC, P_FUSED = SSAL_DISPATCH_FUSED, P_BF16X3 = SSAL_DISPATCH_FUSED_BF16X3 };
+
 // Bottleneck.call (enet_modules.py:526-599)
-// size guards of the fused launchers (32-bit byte offsets inside one image)
-bool regular_fused(const DevLayer &L, int h, int w)
+Path regular_path(const DevLayer &L, int h, int w, int arith)
 {
-    return g_use_mfma && (long)h * w * L.cin <= (1L << 29) && bottleneck_mfma_supported(L.cin, L.f, L.asym);
+    if (!g_use_mfma || !bottleneck_mfma_supported(L.cin, L.f, L.asym) || !bottleneck_mfma_fits(L.cin, h, w)) return P_GENERIC;
+    return arith == SSAL_ARITH_BF16X3 && L.bf3 && bottleneck_bf16x3_fits(h, w) ? P_BF16X3 : P_FUSED;
 }
-bool down_fused(const DevLayer &L, int h, int w)
+Path down_path(const DevLayer &L, int h, int w, int arith)
 {
-    return g_use_mfma && (long)h * w * L.cout < (1L << 31) && downsample_mfma_supported(L.cin, L.cout);
+    if (!g_use_mfma || !downsample_mfma_supported(L.cin, L.cout) || !downsample_mfma_fits(L.cin, h, w)) return P_GENERIC;
+    return arith == SSAL_ARITH_BF16X3 && L.bf3 && downsample_bf16x3_fits(h, w) ? P_BF16X3 : P_FUSED;
 }
-bool up_fused(const DevLayer &L, int h, int w)
+// has_code: pooling-derived indices in window-code form (the fused kernels gather; arbitrary indices take the scatter form)
+Path up_path(const DevLayer &L, int h, int w, bool has_code, int arith)
 {
-    return g_use_mfma && (long)h * w * 4 * L.cout < (1L << 31) && upsample_mfma_supported(L.cin, L.cout);
+    if (!has_code || !g_use_mfma || !upsample_mfma_supported(L.cin, L.cout) || !upsample_mfma_fits(L.cin, h, w)) return P_GENERIC;
+    return arith == SSAL_ARITH_BF16X3 && L.bf3 && upsample_bf16x3_fits(h, w) ? P_BF16X3 : P_FUSED;
+}
+// Initial + Bottleneck1_0 in one launch (k_initial_down16); h x w = the image.  run_layer_idx adds the frame alignment.
+bool initial_fused(int c_in, int h, int w)
+{
+    return (ssal::knobs().fuse_ends & 1) && g_use_mfma && initial_down16_supported(c_in) && initial_down16_fits(h, w);
 }
 
 hipError_t run_regular(const DevLayer &L, const float *x, int n, int h, int w, float *y,
                        const LayerTemps &T, hipStream_t s, int arith = SSAL_ARITH_F32)
 {
     const int C = L.cin, f = L.f;
-    if (arith == SSAL_ARITH_BF16X3 && L.bf3 && regular_fused(L, h, w)) {  // opt-in: split-operand bf16 MFMAs, NOT bit-identical
+    const Path path = regular_path(L, h, w, arith);
+    if (path == P_BF16X3) {  // opt-in: split-operand bf16 MFMAs, NOT bit-identical
         BnkArgs a;
         memset(&a, 0, sizeof(a));
         a.x = x; a.y = y;
@@ -555,7 +570,7 @@ hipError_t run_regular(const DevLayer &L, const float *x, int n, int h, int w, f
         a.N = n; a.H = h; a.W = w; a.dil = L.dil;
         return launch_bottleneck_bf16x3(a, L.bf3, s);
     }
-    if (regular_fused(L, h, w))
+    if (path == P_FUSED)
         return launch_bottleneck_mfma(x, y, n, h, w, C, L.dil, L.proj_w, L.proj_scale, L.proj_shift,
                                       L.proj_alpha, L.conv_w, L.asym ? L.conv_w1 : nullptr,
                                       L.conv_scale, L.conv_shift, L.conv_alpha, L.exp_w, L.exp_scale,
@@ -588,7 +603,8 @@ hipError_t run_down(const DevLayer &L, const float *x, int n, int h, int w, floa
                     const LayerTemps &T, hipStream_t s, int arith = SSAL_ARITH_F32)
 {
     const int C = L.cin, f = L.f;
-    if (arith == SSAL_ARITH_BF16X3 && L.bf3 && down_fused(L, h, w)) {  // opt-in mode; the pooling residual / codes stay exact
+    const Path path = down_path(L, h, w, arith);
+    if (path == P_BF16X3) {  // opt-in mode; the pooling residual / codes stay exact
         DownArgs a;
         memset(&a, 0, sizeof(a));
         a.x = x; a.y = y; a.code = code;
@@ -598,7 +614,7 @@ hipError_t run_down(const DevLayer &L, const float *x, int n, int h, int w, floa
         a.N = n; a.H = h; a.W = w;
         return launch_downsample_bf16x3(a, L.bf3, s);
     }
-    if (down_fused(L, h, w))
+    if (path == P_FUSED)
         return launch_downsample_mfma(x, y, code, n, h, w, C, L.proj_w, L.proj_scale, L.proj_shift,
                                       L.proj_alpha, L.conv_w, L.conv_scale, L.conv_shift, L.conv_alpha,
                                       L.exp_w, L.exp_scale, L.exp_shift, L.res_alpha, s);
@@ -620,7 +636,8 @@ hipError_t run_up(const DevLayer &L, const float *x, int n, int h, int w, float 
                   const uint8_t *code, const int64_t *argmax, const LayerTemps &T, hipStream_t s, int arith = SSAL_ARITH_F32)
 {
     const int C = L.cin, pf = L.f, cf = L.cf;
-    if (arith == SSAL_ARITH_BF16X3 && L.bf3 && code && up_fused(L, h, w)) {  // opt-in mode; the unpool gather is the exact kernel's
+    const Path path = up_path(L, h, w, code != nullptr, arith);
+    if (path == P_BF16X3) {  // opt-in mode; the unpool gather is the exact kernel's
         UpArgs a;
         memset(&a, 0, sizeof(a));
         a.x = x; a.y = y; a.code = code;
@@ -630,7 +647,7 @@ hipError_t run_up(const DevLayer &L, const float *x, int n, int h, int w, float 
         a.N = n; a.H = h; a.W = w; a.dil = 1;
         return launch_upsample_bf16x3(a, L.bf3, s);
     }
-    if (code && up_fused(L, h, w))
+    if (path == P_FUSED)
         return launch_upsample_mfma(x, y, code, n, h, w, C, L.proj_w, L.proj_scale, L.proj_shift,
                                     L.proj_alpha, L.convT_stacked, L.conv_scale, L.conv_shift,
                                     L.conv_alpha, L.exp_w, L.exp_scale, L.exp_shift, L.res_w,
@@ -731,8 +748,7 @@ hipError_t run_layer_idx(const ssal_enet *net, int li, const void *x, bool x_is_
     // Initial + Bottleneck1_0 in one launch: Initial's output (a0; no endpoint) is never written
     // (the image window is read in quads of four elements there: a frame pointer that is not aligned to a quad -- 16 bytes for
     // float32 frames, 4 for uint8 frames -- takes the two-launch form)
-    const bool fuse01 = (ssal::knobs().fuse_ends & 1) && g_use_mfma && initial_down16_supported(net->c_in) &&
-                        (long)h * w * 16 < (1L << 31) && ((uintptr_t)x & (x_is_u8 ? 3 : 15)) == 0;
+    const bool fuse01 = initial_fused(net->c_in, h, w) && ((uintptr_t)x & (x_is_u8 ? 3 : 15)) == 0;
     if (li == 0) return fuse01 ? hipSuccess : launch_initial(x, x_is_u8, n, h, w, net->c_in, L.w, L.scale, L.shift, L.alpha, V.a0, s);
     if (li == 1 && fuse01) {
         const DevLayer &I = net->layers[0];
@@ -1554,6 +1570,39 @@ SSAL_API int ssal_debug_set_knob(const char *name, int value)
 #endif
     else return fail(SSAL_EINVAL, "unknown knob '%s'", name);
     return SSAL_OK;
+}
+
+SSAL_API int ssal_debug_layer_dispatch(int kind, int cin, int cout, int f, int asym, int h, int w, int arithmetic,
+                                       int *kernel_out)
+{
+    if (!kernel_out) return fail(SSAL_EINVAL, "NULL kernel_out");
+    if (int rc = check_arith(arithmetic)) return rc;
+    if (cin <= 0 || cout <= 0 || f <= 0 || h <= 0 || w <= 0)
+        return fail(SSAL_EINVAL, "bad layer form cin=%d cout=%d f=%d h=%d w=%d", cin, cout, f, h, w);
+    static const float packed = 0.0f;  // stands for DevLayer::bf3: set by commit exactly where the mode has a kernel
+    DevLayer L;
+    L.cin = cin; L.cout = cout; L.f = f; L.cf = f; L.dil = 1; L.asym = asym != 0;
+    switch (kind) {
+    case SSAL_LAYER_INITIAL:
+        *kernel_out = initial_fused(cin, h, w) ? SSAL_DISPATCH_FUSED : SSAL_DISPATCH_GENERIC;
+        return SSAL_OK;
+    case SSAL_LAYER_REGULAR:
+        L.kind = K_REGULAR;
+        L.bf3 = bottleneck_bf16x3_supported(cin, f) ? &packed : nullptr;
+        *kernel_out = regular_path(L, h, w, arithmetic);
+        return SSAL_OK;
+    case SSAL_LAYER_DOWN:
+        L.kind = K_DOWN;
+        L.bf3 = downsample_bf16x3_supported(cin, cout) ? &packed : nullptr;
+        *kernel_out = down_path(L, h, w, arithmetic);
+        return SSAL_OK;
+    case SSAL_LAYER_UP:
+        L.kind = K_UP;
+        L.bf3 = upsample_bf16x3_supported(cin, cout) ? &packed : nullptr;
+        *kernel_out = up_path(L, h, w, true, arithmetic);
+        return SSAL_OK;
+    }
+    return fail(SSAL_EINVAL, "unknown layer kind %d", kind);
 }
 
 // {"kernel_family": 1, "bnk_tw": 0, "bnk_xcd": 1, "measure_build": 0, "defaults": 1}; bench.py prints it and

@@ -862,11 +862,19 @@ __global__ __launch_bounds__(256, 3) void k_upsample_bf16x3(UpArgs a, const uint
 
 bool upsample_bf16x3_supported(int Cin, int Cout) { return Cin == C && Cout == CU; }
 
+// Per-image size limits (ssal_internal.h): the output stores are k_upsample_mfma's (int byte offsets into y [2H,2W,64], the
+// 0x80000000 sentinel), so the same 4 * H * W * 64 <= 2^29.  The regular block's are k_bottleneck_mfma's: H * W * 128 <= 2^29.
+// The downsample's y offsets ((pixel * C) * 4 in int) would hold up to (H/2) * (W/2) * 128 <= 2^29; its launcher admits the
+// H * W * 64 <= 2^29 it always has, and the layer dispatch runs larger shapes on the exact fp32 kernels.
+bool upsample_bf16x3_fits(int H, int W) { return (long)4 * H * W * CU <= (1L << 29); }
+bool bottleneck_bf16x3_fits(int H, int W) { return (long)H * W * C <= (1L << 29); }
+bool downsample_bf16x3_fits(int H, int W) { return (long)H * W * DC <= (1L << 29); }
+
 // x [N,H,W,128] -> y [N,2H,2W,64] with the window codes [N,H,W,64] of the matching downsample; packed = bf16x3::pack_up_layer(...)
 hipError_t launch_upsample_bf16x3(const UpArgs &a0, const void *packed, hipStream_t s)
 {
     UpArgs a = a0;
-    if (!packed || !a.code || a.H < 1 || a.W < 1 || (long)4 * a.H * a.W * CU > (1L << 29)) return hipErrorInvalidValue;
+    if (!packed || !a.code || a.H < 1 || a.W < 1 || !upsample_bf16x3_fits(a.H, a.W)) return hipErrorInvalidValue;
     a.TH = TH;
     a.tiles_y = (a.H + TH - 1) / TH;
     a.tiles_x = (a.W + TW - 1) / TW;
@@ -887,7 +895,7 @@ bool downsample_bf16x3_supported(int Cin, int Cout) { return Cin == DC && Cout =
 hipError_t launch_downsample_bf16x3(const DownArgs &a0, const void *packed, hipStream_t s)
 {
     DownArgs a = a0;
-    if (!packed || a.H % 2 || a.W % 2 || a.H < 2 || a.W < 2 || (long)a.H * a.W * DC > (1L << 29)) return hipErrorInvalidValue;
+    if (!packed || a.H % 2 || a.W % 2 || a.H < 2 || a.W < 2 || !downsample_bf16x3_fits(a.H, a.W)) return hipErrorInvalidValue;
     const int Ho = a.H / 2, Wo = a.W / 2;
     a.TH = TH;
     a.tiles_y = (Ho + TH - 1) / TH;
@@ -912,7 +920,7 @@ hipError_t launch_bottleneck_bf16x3(const BnkArgs &a0, const void *packed, hipSt
     a.tiles_y = (Hp + TH - 1) / TH;
     a.tiles_x = (Wp + TW - 1) / TW;
     const long grid = (long)a.N * a.dil * a.dil * a.tiles_y * a.tiles_x;
-    if (grid <= 0 || grid > 0x3fffffffL || (long)a.H * a.W * C > (1L << 29)) return hipErrorInvalidValue;
+    if (grid <= 0 || grid > 0x3fffffffL || !bottleneck_bf16x3_fits(a.H, a.W)) return hipErrorInvalidValue;
     a.ntiles = (int)grid;
     a.xcd_chunk = knobs().bnk_xcd ? (int)((grid + 7) / 8) : 0;
     const long launch_grid = a.xcd_chunk ? 8L * a.xcd_chunk : grid;

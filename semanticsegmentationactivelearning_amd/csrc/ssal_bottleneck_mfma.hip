@@ -431,7 +431,7 @@ __device__ __forceinline__ void conv_exp_store(const BnkArgs &a, const float *xi
         }
         return;
     }
-    // raw buffer resources over image n of x and y (num_records = image bytes <= 2 GiB); kOOB is an
+    // raw buffer resources over image n of x and y (num_records = image bytes <= 2 GiB: bottleneck_mfma_fits); kOOB is an
     // offset the range check always rejects, even after the +384 B N-tile immediates
     constexpr unsigned kOOB = 0x80000000u;
     const unsigned img_bytes = (unsigned)(a.H * a.W * C) * 4u;
@@ -1050,7 +1050,7 @@ __global__ __launch_bounds__(256, 2) void k_downsample_mfma(DownArgs a)
     // ---- phase B: 3x3 conv -> expansion D[co][pixel] -> + pooled residual (registers) -> float4 stores ----
     const float *wel = WE + h * C + j;  // We[2s + h][nt*32 + j] = wel[2s*C + nt*32]
     const float *bnl = BNV + 4 * h;     // vectors of channels nt*32 + 8g + 4h .. +3
-    const rsrc_t yrs = make_rsrc(yimg, (unsigned)(Ho * Wo * C) * 4u);  // launcher: Ho * Wo * C < 2^29
+    const rsrc_t yrs = make_rsrc(yimg, (unsigned)(Ho * Wo * C) * 4u);  // downsample_mfma_fits: Ho * Wo * C <= 2^29
 #pragma unroll
     for (int k = 0; k < MPW; ++k) {
         const int mt = wave + 4 * k;
@@ -1285,7 +1285,7 @@ __global__ __launch_bounds__(256, 2) void k_upsample_mfma(UpArgs a)
     // ---- phase B: transposed conv (2 stacked accumulators) -> expansion per parity class -> unpool-gated
     // residual -> float4 stores ----------------------------------------------------------------------------
     const rsrc_t wsrs = make_rsrc(a.ws, 6 * F * 32 * 4);
-    const rsrc_t yrs = make_rsrc(yimg, (unsigned)(4 * a.H * a.W * CUP) * 4u);  // launcher: 4 * H * W * 64 < 2^29
+    const rsrc_t yrs = make_rsrc(yimg, (unsigned)(4 * a.H * a.W * CUP) * 4u);  // upsample_mfma_fits: 4 * H * W * 64 <= 2^29
     const float *bnl = BNV + 4 * h;
 #pragma unroll
     for (int k = 0; k < MPW; ++k) {
@@ -1485,11 +1485,37 @@ hipError_t launch_probe_swap(float *out, hipStream_t s)
 
 // 16x16x4 family (ssal_bottleneck_mfma16.hip)
 bool bottleneck_mfma16_supported(int Cin, int f);
+bool bottleneck16_fits(int Cin, int H, int W);
 hipError_t launch_bottleneck_mfma16(const BnkArgs &a, int Cin, hipStream_t s);
 bool downsample_mfma16_supported(int Cin, int Cout);
+bool downsample16_fits(int H, int W);
 hipError_t launch_downsample_mfma16(const DownArgs &a, hipStream_t s);
 bool upsample_mfma16_supported(int Cin, int Cout);
+bool upsample16_fits(int H, int W);
 hipError_t launch_upsample_mfma16(const UpArgs &a, hipStream_t s);
+
+// Per-image size limits (ssal_internal.h).  The 32x32x2 kernels of this file address the residual / output of ONE image
+// through raw buffer resources: byte offsets are evaluated in int ((pixel * C + c) * 4 and the like), num_records is the
+// image's byte count, and a row outside the image gets the offset 0x80000000, which the range check must reject -- so the
+// image may hold at most 2^31 bytes (2^29 floats).  Past that the sentinel lands inside the buffer (a ragged tile's idle
+// lanes overwrite a valid pixel), and past 2^32 bytes num_records wraps.
+//   k_bottleneck_mfma* / k_bottleneck_o4 (128 ch): x and y [H,W,128]           H * W * 128 <= 2^29
+//   k_downsample_mfma (64 -> 128): y [H/2,W/2,128] (x, codes: 64-bit offsets)   (H/2) * (W/2) * 128 <= 2^29 (kept as H * W * 128 < 2^31)
+//   k_upsample_mfma (128 -> 64): y [2H,2W,64] (x, codes: 64-bit offsets)        4 * H * W * 64 <= 2^29
+bool bottleneck_mfma_fits(int Cin, int H, int W)
+{
+    return Cin == C ? (long)H * W * C <= (1L << 29) : bottleneck16_fits(Cin, H, W);
+}
+
+bool downsample_mfma_fits(int Cin, int H, int W)
+{
+    return Cin == CDN ? (long)H * W * C < (1L << 31) : downsample16_fits(H, W);
+}
+
+bool upsample_mfma_fits(int Cin, int H, int W)
+{
+    return Cin == C ? (long)4 * H * W * CUP <= (1L << 29) : upsample16_fits(H, W);
+}
 
 bool downsample_mfma_supported(int Cin, int Cout)
 {
@@ -1502,7 +1528,7 @@ hipError_t launch_downsample_mfma(const float *x, float *y, uint8_t *code, int N
                                   const float *we, const float *es, const float *et, const float *ra,
                                   hipStream_t s)
 {
-    if (H % 2 || W % 2) return hipErrorInvalidValue;
+    if (H % 2 || W % 2 || !downsample_mfma_fits(Cin, H, W)) return hipErrorInvalidValue;
     DownArgs a;
     a.x = x; a.y = y; a.code = code;
     a.trace = nullptr;
@@ -1541,6 +1567,7 @@ hipError_t launch_upsample_mfma(const float *x, float *y, const uint8_t *code, i
                                 const float *we, const float *es, const float *et, const float *wr,
                                 const float *ra, hipStream_t s)
 {
+    if (!upsample_mfma_fits(Cin, H, W)) return hipErrorInvalidValue;
     UpArgs a;
     a.x = x; a.y = y; a.code = code;
     a.trace = nullptr;
@@ -1579,7 +1606,7 @@ hipError_t launch_bottleneck_mfma(const float *x, float *y, int N, int H, int W,
                                   const float *ca, const float *we, const float *es, const float *et,
                                   const float *ra, hipStream_t s, const float *wq)
 {
-    if (dil < 1 || dil > 64) return hipErrorInvalidValue;
+    if (dil < 1 || dil > 64 || !bottleneck_mfma_fits(Cin, H, W)) return hipErrorInvalidValue;
     const bool asym = wc2 != nullptr;
     if (Cin == C && !wq && (!asym || knobs().asym_tw16)) return hipErrorInvalidValue;  // these kernels read the quad layout
     if (asym && (dil != 1 || Cin != C)) return hipErrorInvalidValue;

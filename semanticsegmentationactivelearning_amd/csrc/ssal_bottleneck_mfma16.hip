@@ -920,9 +920,21 @@ __global__ __launch_bounds__(256, 3) void k_upsample16(UpArgs a)
 // =================================================================================================
 bool bottleneck_mfma16_supported(int Cin, int f) { return (Cin == 64 && f == 16) || (Cin == 16 && f == 4); }
 
+// Per-image size limits (ssal_internal.h).  k_bottleneck16 keeps the element offset of a lane's pixel in an int (offk:
+// pixel * C + 4g, stores at offk + 16 nt), so its arithmetic holds up to H * W * C <= 2^31; the launcher admits the 2^29 the
+// layer dispatch has always used (and the tests cover).  k_downsample16, k_initial_down16 and k_upsample16 address in 64 bits
+// (k_upsample16 keeps the INPUT pixel index iy * W + ix in an int); their launchers admit the bounds the layer dispatch has
+// always used: k_downsample16 H * W * 64 < 2^31 (input [H,W,16] in bytes), k_initial_down16 H * W * 16 < 2^31 (H x W = the
+// image), k_upsample16 4 * H * W * 16 < 2^31 (output [2H,2W,16] in floats).
+bool bottleneck16_fits(int Cin, int H, int W) { return (long)H * W * Cin <= (1L << 29); }
+bool downsample16_fits(int H, int W) { return (long)H * W * 64 < (1L << 31); }
+bool initial_down16_fits(int H, int W) { return (long)H * W * 16 < (1L << 31); }
+bool upsample16_fits(int H, int W) { return (long)4 * H * W * 16 < (1L << 31); }
+
 hipError_t launch_bottleneck_mfma16(const BnkArgs &a0, int Cin, hipStream_t s)
 {
     BnkArgs a = a0;
+    if (!bottleneck16_fits(Cin, a.H, a.W)) return hipErrorInvalidValue;
     a.TH = 8;
     const int Hp = (a.H + a.dil - 1) / a.dil, Wp = (a.W + a.dil - 1) / a.dil;
     const bool wide = Wp > 16;
@@ -954,7 +966,7 @@ bool downsample_mfma16_supported(int Cin, int Cout) { return Cin == 16 && Cout =
 hipError_t launch_downsample_mfma16(const DownArgs &a0, hipStream_t s)
 {
     DownArgs a = a0;
-    if (a.H % 2 || a.W % 2) return hipErrorInvalidValue;
+    if (a.H % 2 || a.W % 2 || !downsample16_fits(a.H, a.W)) return hipErrorInvalidValue;
     a.TH = 8;
     const int Ho = a.H / 2, Wo = a.W / 2;
     const bool wide = Wo > 16;
@@ -980,7 +992,7 @@ hipError_t launch_initial_down16(const void *img, bool img_is_u8, int N, int H, 
                                  const float *cs, const float *ct, const float *ca, const float *we, const float *es,
                                  const float *et, const float *ra, hipStream_t s)
 {
-    if (H % 4 || W % 4 || !initial_down16_supported(c_in)) return hipErrorInvalidValue;
+    if (H % 4 || W % 4 || !initial_down16_supported(c_in) || !initial_down16_fits(H, W)) return hipErrorInvalidValue;
     InitDownArgs A;
     A.img = img; A.iw = iw; A.iscale = iscale; A.ishift = ishift; A.ialpha = ialpha;
     A.d.x = nullptr; A.d.y = y; A.d.code = code;
@@ -1015,6 +1027,7 @@ bool upsample_mfma16_supported(int Cin, int Cout) { return Cin == 64 && Cout == 
 hipError_t launch_upsample_mfma16(const UpArgs &a0, hipStream_t s)
 {
     UpArgs a = a0;
+    if (!upsample16_fits(a.H, a.W)) return hipErrorInvalidValue;
     a.dil = 1;
     a.TH = 8;
     const bool wide = a.W > 16;

@@ -98,6 +98,18 @@ hipError_t launch_argmax_to_codes(const int64_t *argmax, int N, int Ho, int Wo, 
 hipError_t launch_codes_to_argmax(const uint8_t *code, int N, int Ho, int Wo, int C,
                                   int64_t *argmax, hipStream_t s);
 
+// Per-image size limits of the fused launchers.  Every fused kernel computes offsets inside one image in 32 bits; each
+// *_fits(H, W) states the largest image its launcher admits (the launcher returns hipErrorInvalidValue beyond it) and the
+// layer dispatch in ssal_api.hip asks the same function.  H, W = the layer's input (Initial + Bottleneck1_0: the image).
+// The arithmetic behind each bound is written next to the function.
+bool bottleneck_mfma_fits(int Cin, int H, int W);  // k_bottleneck_mfma* / k_bottleneck_o4 (Cin 128), k_bottleneck16 (64, 16)
+bool downsample_mfma_fits(int Cin, int H, int W);  // k_downsample_mfma (Cin 64), k_downsample16 (16)
+bool upsample_mfma_fits(int Cin, int H, int W);    // k_upsample_mfma (Cin 128), k_upsample16 (64)
+bool initial_down16_fits(int H, int W);            // k_initial_down16
+bool bottleneck_bf16x3_fits(int H, int W);         // k_bottleneck_bf16x3 / k_bottleneck_asym_bf16x3
+bool downsample_bf16x3_fits(int H, int W);         // k_downsample_bf16x3
+bool upsample_bf16x3_fits(int H, int W);           // k_upsample_bf16x3
+
 // MFMA-fused regular / dilated bottleneck (ssal_bottleneck_mfma.hip)
 bool bottleneck_mfma_supported(int Cin, int f, bool asym);
 hipError_t launch_bottleneck_mfma(const float *x, float *y, int N, int H, int W, int Cin, int dil,

@@ -207,6 +207,22 @@ def test_training_mode_is_rejected_without_touching_the_gpu():
         net.score(np.zeros((1, 8, 8, 3), np.float32), measure="bald")
 
 
+def test_icnet_bf16x3_is_rejected_without_touching_the_gpu():
+    """the opt-in bf16x3 mode is ENet's: asked of an ICNet, rank_confidence / evaluate raise ValueError before any GPU
+    work (the batches are never read)"""
+    def never():
+        raise AssertionError("batches were read")
+        yield
+
+    net = ssal.ICNet(19)
+    with pytest.raises(ValueError, match="bf16x3"):
+        al.rank_confidence(net, never(), 4, np.arange(4), 2, arithmetic="bf16x3")
+    with pytest.raises(ValueError, match="bf16x3"):
+        al.evaluate(net, never(), 19, arithmetic="bf16x3")
+    with pytest.raises(ValueError):
+        al.rank_confidence(ssal.ENet(19), never(), 4, np.arange(4), 2, arithmetic="fp16")
+
+
 def test_no_cpu_fallback_when_no_gpu():
     import torch
     if torch.cuda.is_available():
