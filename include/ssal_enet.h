@@ -164,6 +164,54 @@ int ssal_score_logits_nhwc(const float *logits_dev, int n, int h, int w, int cla
                            uint8_t *mask_dev, float *conf_dev, void *ws_dev, int64_t ws_bytes,
                            void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Region scores (region-level acquisition; no reference counterpart: the reference ranks whole frames,
+ * active_learning.py:682-715 -- the per-pixel measures are the same ones, :239-263)
+ *
+ * A region is a window of rh x rw output pixels on a grid anchored at pixel (0, 0): RY = ceil(h / rh) by RX = ceil(w / rw)
+ * regions, the bottom row / right column clipped by the frame.  region_scores [n][RY][RX] float64 = the mean of the per-pixel
+ * confidence over the region's pixels inside the frame, accumulated in float64 in a fixed order (csrc/ssal_regions.h) that
+ * does not know the batch size, the image-group chain a frame ran on or any ssal_debug_set_knob setting.  Region outputs
+ * are caller-provided; rh <= 0 or rw <= 0 is SSAL_EINVAL.
+ * ---------------------------------------------------------------------------------------------- */
+#define SSAL_REGION_FORM_TILES 0 /* float64 sums of 32 x 32 pixel tiles [n][ceil(h / 32)][ceil(w / 32)], row-major */
+#define SSAL_REGION_FORM_PLANE 1 /* fp32 per-pixel confidence [n][h][w] */
+
+/* host only: the region grid of an h x w frame */
+int ssal_region_grid(int h, int w, int rh, int rw, int *ry, int *rx);
+
+/* ssal_enet_score_nhwc_arith plus region scores, fused: the Final + score kernel already leaves one float64 sum per
+ * 32 x 32 output tile in the workspace; one more small launch folds them into regions (tiles of a region in row-major
+ * order), so rh and rw must be multiples of 32 (anything else: SSAL_EINVAL; ssal_region_means_plane serves those sizes).
+ * scores_dev and the optional label / mask / conf outputs keep their meaning, and the per-image score has the bits
+ * ssal_enet_score_nhwc_arith gives; with none of the optional outputs the score-only fused form runs.  The workspace is
+ * ssal_enet_workspace_bytes, as for the plain entry. */
+int ssal_enet_score_regions_nhwc_arith(ssal_enet *net, const void *x_dev, int x_is_u8, int n, int h, int w, int measure,
+                                       float threshold, int arithmetic, int rh, int rw, double *scores_dev,
+                                       double *region_scores_dev, uint8_t *label_dev, uint8_t *mask_dev, float *conf_dev,
+                                       void *ws_dev, int64_t ws_bytes, void *stream);
+
+/* stand-alone: region means of a device plane [n][h][w] fp32; any rh, rw >= 1.  Reads the plane once (16-byte loads when
+ * plane_dev is 16-byte aligned and w a multiple of 4; the result has the same bits either way).  Within a region: row
+ * partials first, then rows top to bottom; no floating-point atomics. */
+int ssal_region_means_plane(const float *plane_dev, int n, int h, int w, int rh, int rw, double *region_scores_dev,
+                            void *stream);
+
+/* region sibling of ssal_score_logits_nhwc (which is unchanged): the same outputs plus region_scores_dev, through the
+ * confidence plane and ssal_region_means_plane.  conf_dev stays optional: without it the plane lives in the workspace,
+ * which is why the workspace is ssal_score_regions_workspace_bytes here. */
+int64_t ssal_score_regions_workspace_bytes(int n, int h, int w);
+int ssal_score_logits_regions_nhwc(const float *logits_dev, int n, int h, int w, int classes, int measure, float threshold,
+                                   int rh, int rw, double *scores_dev, double *region_scores_dev, uint8_t *label_dev,
+                                   uint8_t *mask_dev, float *conf_dev, void *ws_dev, int64_t ws_bytes, void *stream);
+
+/* host only: the reduction core of the two kernels run on the CPU (the same source, csrc/ssal_regions.h).  form:
+ * SSAL_REGION_FORM_*; in_host: the tiles (float64) or the plane (fp32) of n frames; region_scores_host [n][RY][RX];
+ * counts_host (nullable) int64 [RY][RX]: the clipped pixel count of every region.  The tile form needs rh, rw multiples
+ * of 32. */
+int ssal_region_reduce_host(int form, const void *in_host, int n, int h, int w, int rh, int rw, double *region_scores_host,
+                            int64_t *counts_host);
+
 /* tensortools.metrics.confusion_mat (tensortools/metrics.py:226-257) accumulated like Metrics' assign_add (:8-27):
  * confusion_dev int64 [classes][classes] += bincount(classes * labels + pred, weights, minlength = maxlength = classes^2)
  * over `pixels` uint8 elements of pred_dev / labels_dev / weights_dev (weights_dev NULL = weight 1; a weight is its full

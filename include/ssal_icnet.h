@@ -53,6 +53,17 @@ int ssal_icnet_score_nhwc_u8(ssal_icnet *net, const uint8_t *x_dev, int n, int h
                              float threshold, double *scores_dev, uint8_t *label_dev, uint8_t *mask_dev,
                              float *conf_dev, void *ws_dev, int64_t ws_bytes, void *stream);
 
+/* ssal_icnet_score_nhwc (_u8 when x_is_u8 != 0) plus region scores [n][RY][RX] float64 (include/ssal_enet.h, "Region
+ * scores"); any rh, rw >= 1.  ICNet's score kernel keeps its partial sums per linear 256-pixel block, not per tile, so this
+ * entry goes through the per-pixel confidence plane and ssal_region_means_plane: conf_dev stays optional, and without it
+ * the plane lives behind the network's buffers in the workspace -- hence ssal_icnet_regions_workspace_bytes.  scores_dev
+ * has the bits ssal_icnet_score_nhwc gives. */
+int64_t ssal_icnet_regions_workspace_bytes(const ssal_icnet *net, int n, int h, int w);
+int ssal_icnet_score_regions_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w, int measure,
+                                  float threshold, int rh, int rw, double *scores_dev, double *region_scores_dev,
+                                  uint8_t *label_dev, uint8_t *mask_dev, float *conf_dev, void *ws_dev, int64_t ws_bytes,
+                                  void *stream);
+
 /* Named intermediate tensors of the LAST forward/score call on a workspace (every ICNET_SPEC layer output that is
  * materialised keeps its own buffer): byte offset into the workspace and NHWC dims.  SSAL_EINVAL for a name that
  * is not materialised (the 2x interpolations are evaluated inside the consuming convolution).  Every endpoint is valid

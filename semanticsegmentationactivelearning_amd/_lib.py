@@ -112,6 +112,14 @@ PROTOTYPES = {
     "ssal_enet_layer_workspace_bytes": (_i64, [_vp, _c.c_char_p, _i, _i, _i]),
     "ssal_score_workspace_bytes": (_i64, [_i, _i, _i]),
     "ssal_score_logits_nhwc": (_i, [_vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    # ---- region scores (include/ssal_enet.h) ----
+    "ssal_region_grid": (_i, [_i, _i, _i, _i, _c.POINTER(_i), _c.POINTER(_i)]),
+    "ssal_enet_score_regions_nhwc_arith": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                _i64, _vp]),
+    "ssal_region_means_plane": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ssal_score_regions_workspace_bytes": (_i64, [_i, _i, _i]),
+    "ssal_score_logits_regions_nhwc": (_i, [_vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_region_reduce_host": (_i, [_i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "ssal_confusion_workspace_bytes": (_i64, [_i]),
     "ssal_confusion_matrix": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _i64, _vp]),
     "ssal_xent_workspace_bytes": (_i64, [_i, _i]),
@@ -144,6 +152,8 @@ PROTOTYPES = {
     "ssal_icnet_forward_nhwc_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i64, _vp]),
     "ssal_icnet_score_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "ssal_icnet_score_nhwc_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_icnet_regions_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
+    "ssal_icnet_score_regions_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "ssal_icnet_num_endpoints": (_i, [_vp]),
     "ssal_icnet_endpoint_name": (_i, [_vp, _i, _c.POINTER(_c.c_char_p)]),
     "ssal_icnet_endpoint_info": (_i, [_vp, _c.c_char_p, _i, _i, _i, _c.POINTER(_i64), _c.POINTER(_i64)]),
@@ -450,3 +460,57 @@ def layer_dispatch(kind, cin, cout, f, asym, h, w, arithmetic="f32"):
 def set_knob(name, value):
     """tuning / A-B knob of the fused bottleneck launchers (include/ssal_enet.h: ssal_debug_set_knob)"""
     check(lib().ssal_debug_set_knob(name.encode(), int(value)))
+
+
+# ---- region-level acquisition (include/ssal_enet.h, "Region scores") ------------------------------------------------
+REGION_TILE = 32                                  # the fused ENet route folds 32 x 32 pixel tiles
+REGION_FORMS = {"tiles": 0, "plane": 1}           # SSAL_REGION_FORM_*
+
+
+def region_size(region):
+    """``region`` as the public calls take it -- an int or ``(rh, rw)`` -- as a pair of ints"""
+    if isinstance(region, (int, np.integer)):
+        return int(region), int(region)
+    rh, rw = region
+    return int(rh), int(rw)
+
+
+def region_grid(h, w, region):
+    """host-only: ``(RY, RX) = (ceil(h / rh), ceil(w / rw))``; ValueError for a region size <= 0"""
+    rh, rw = region_size(region)
+    ry, rx = _c.c_int(0), _c.c_int(0)
+    check(lib().ssal_region_grid(int(h), int(w), rh, rw, _c.byref(ry), _c.byref(rx)))
+    return ry.value, rx.value
+
+
+def region_means_plane(plane, region):
+    """region means [N, RY, RX] float64 of a per-pixel plane [N, H, W] float32 on the GPU (``ssal_region_means_plane``:
+    any region size; within a region row partials first, then rows top to bottom)"""
+    torch = require_gpu()
+    x = as_device_f32(plane)
+    if x.dim() != 3:
+        raise ValueError("plane must be [N,H,W]")
+    n, h, w = x.shape
+    rh, rw = region_size(region)
+    ry, rx = region_grid(h, w, (rh, rw))
+    out = torch.empty((n, ry, rx), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        check(lib().ssal_region_means_plane(dev_ptr(x), n, h, w, rh, rw, dev_ptr(out), stream_ptr()))
+    return out
+
+
+def region_reduce_host(data, h, w, region, form="plane"):
+    """the reduction core of the two region kernels run on the CPU (``ssal_region_reduce_host``, the same source):
+    ``data`` is [N, H, W] float32 (form "plane") or the float64 sums of its 32 x 32 tiles [N, ceil(H/32), ceil(W/32)]
+    (form "tiles").  Returns ``(region means [N, RY, RX] float64, clipped pixel counts [RY, RX] int64)``.  Needs no GPU."""
+    rh, rw = region_size(region)
+    ry, rx = region_grid(h, w, (rh, rw))
+    a = np.ascontiguousarray(data, dtype=np.float32 if form == "plane" else np.float64)
+    want = (h, w) if form == "plane" else (-(-h // REGION_TILE), -(-w // REGION_TILE))
+    if a.ndim != 3 or tuple(a.shape[1:]) != want:
+        raise ValueError("%s input must be [N, %d, %d] (got %s)" % (form, want[0], want[1], a.shape))
+    out = np.empty((a.shape[0], ry, rx), dtype=np.float64)
+    counts = np.empty((ry, rx), dtype=np.int64)
+    check(lib().ssal_region_reduce_host(REGION_FORMS[form], a.ctypes.data_as(_vp), a.shape[0], int(h), int(w), rh, rw,
+                                        out.ctypes.data_as(_vp), counts.ctypes.data_as(_vp)))
+    return out, counts

@@ -44,11 +44,14 @@ class ScoringConfig:
 
 
 def score_logits(logits, measure="entropy", threshold=0.0, return_label=False, return_mask=False,
-                 return_confidence=False):
+                 return_confidence=False, region=None):
     """softmax -> {entropy, margin, confidence} -> float64 mean over (H, W) on materialised logits
     (reference :239-263): ``pseudo_mean_confidence`` [N] float64, plus optionally ``pseudo_label``
     (uint8 argmax, :234-236), ``pseudo_mask`` (conf < threshold -> 0 else 1, :265-269) and the
-    per-pixel ``pseudo_confidence``.  Raises NotImplementedError for an unknown measure (:259-260)."""
+    per-pixel ``pseudo_confidence``.  Raises NotImplementedError for an unknown measure (:259-260).
+
+    ``region`` (an int or ``(rh, rw)``, any size >= 1) adds the region scores [N, RY, RX] float64 as the second return
+    value: ``(scores, region_scores[, maps])`` (``ssal_score_logits_regions_nhwc``; the per-image scores keep their bits)."""
     if measure not in _lib.MEASURES:
         raise NotImplementedError("Uncertainty function not implemented.")
     torch = _lib.require_gpu()
@@ -57,6 +60,23 @@ def score_logits(logits, measure="entropy", threshold=0.0, return_label=False, r
         raise ValueError("logits must be [N,H,W,classes]")
     n, h, w, k = x.shape
     L = _lib.lib()
+    if region is not None:
+        rh, rw = _lib.region_size(region)
+        ry, rx = _lib.region_grid(h, w, (rh, rw))
+        with torch.cuda.device(x.device):
+            ws = torch.empty(int(L.ssal_score_regions_workspace_bytes(n, h, w)), dtype=torch.uint8, device=x.device)
+            scores = torch.empty((n,), dtype=torch.float64, device=x.device)
+            regions = torch.empty((n, ry, rx), dtype=torch.float64, device=x.device)
+            label = torch.empty((n, h, w), dtype=torch.uint8, device=x.device) if return_label else None
+            mask = torch.empty((n, h, w), dtype=torch.uint8, device=x.device) if return_mask else None
+            conf = torch.empty((n, h, w), dtype=torch.float32, device=x.device) if return_confidence else None
+            _lib.check(L.ssal_score_logits_regions_nhwc(
+                _lib.dev_ptr(x), n, h, w, k, _lib.MEASURES[measure], float(threshold), rh, rw,
+                _lib.dev_ptr(scores), _lib.dev_ptr(regions), _lib.dev_ptr(label), _lib.dev_ptr(mask), _lib.dev_ptr(conf),
+                _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))
+        if return_label or return_mask or return_confidence:
+            return scores, regions, {"label": label, "mask": mask, "confidence": conf}
+        return scores, regions
     with torch.cuda.device(x.device):
         nbytes = L.ssal_score_workspace_bytes(n, h, w)
         ws = torch.empty(int(nbytes), dtype=torch.uint8, device=x.device)
@@ -107,18 +127,22 @@ def all_gather_scores(local_index, local_score, group=None):
 
 def _gather_pairs(local_index, local_score, group=None):
     """the collective itself (also what the single-rank RCCL smoke test drives): pack the index next to the score in a
-    float64 pair -> [per, 2], one ``all_gather_into_tensor``"""
+    float64 pair -> [per, 2], one ``all_gather_into_tensor``.  ``local_score`` may carry trailing dimensions (the region
+    pass: [per, RY, RX]); a row is then the index followed by the flattened scores -> [per, 1 + RY * RX], still one
+    collective, and the scores come back in their shape."""
     import torch
     import torch.distributed as dist
     world = dist.get_world_size(group)
-    packed = torch.stack([local_index.to(torch.float64), local_score.to(torch.float64)], dim=1).contiguous()
+    tail = tuple(local_score.shape[1:])
+    packed = torch.cat([local_index.to(torch.float64).reshape(-1, 1),
+                        local_score.to(torch.float64).reshape(local_index.numel(), -1)], dim=1).contiguous()
     home = packed.device
     if packed.is_cuda and dist.get_backend(group) == "gloo":
         packed = packed.cpu()  # rehearsals of the multi-rank path on one GPU run over gloo: collectives on CPU tensors
-    gathered = torch.empty((world * packed.shape[0], 2), dtype=torch.float64, device=packed.device)
+    gathered = torch.empty((world * packed.shape[0], packed.shape[1]), dtype=torch.float64, device=packed.device)
     dist.all_gather_into_tensor(gathered, packed, group=group)
     gathered = gathered.to(home)
-    return gathered[:, 0].to(torch.int64), gathered[:, 1]
+    return gathered[:, 0].to(torch.int64), gathered[:, 1:].reshape((gathered.shape[0],) + tail)
 
 
 def prefetch_to_device(batches, depth=2):
@@ -171,14 +195,16 @@ def prefetch_to_device(batches, depth=2):
 def pad_to_length(index, score, length):
     """Local (collective-free) padding of one rank's ``(index, score)`` shard to ``length`` entries with the
     ``(-1, +inf)`` sentinel.  ``shard_positions`` gives every rank ``ceil(num_examples / world)`` positions, so
-    a rank that scored its whole shard pads to exactly that length without asking the others."""
+    a rank that scored its whole shard pads to exactly that length without asking the others.  ``score`` may carry
+    trailing dimensions (region scores [len, RY, RX]); the sentinel rows are +inf throughout."""
     import torch
     pad = int(length) - index.numel()
     if pad < 0:
         raise ValueError("shard has %d entries, more than the per-rank length %d" % (index.numel(), length))
     if pad > 0:
         index = torch.cat([index, torch.full((pad,), -1, dtype=torch.int64, device=index.device)])
-        score = torch.cat([score, torch.full((pad,), float("inf"), dtype=torch.float64, device=score.device)])
+        score = torch.cat([score, torch.full((pad,) + tuple(score.shape[1:]), float("inf"), dtype=torch.float64,
+                                             device=score.device)])
     return index, score
 
 
@@ -276,6 +302,13 @@ def all_reduce_confusion(confusion, group=None):
 
 def merge_and_rank(local_index, local_score, num_examples, unlabelled, selection_size, group=None, ragged=False):
     """the collective + host tail of a ranking pass (shared by ``rank_confidence`` and ``bench.py``)"""
+    all_index, all_score = _merge_shards(local_index, local_score, num_examples, group, ragged)
+    return finish_ranking(all_index, all_score, num_examples, unlabelled, selection_size)
+
+
+def _merge_shards(local_index, local_score, num_examples, group=None, ragged=False):
+    """the collective of a ranking pass: every rank's ``(index, score)`` rows on every rank, as numpy (sentinel rows
+    kept).  ``local_score`` is [len] (image scores) or [len, RY, RX] (region scores)."""
     import torch.distributed as dist
     world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
     overflow = False
@@ -298,12 +331,12 @@ def merge_and_rank(local_index, local_score, num_examples, unlabelled, selection
     all_index, all_score = all_gather_scores(local_index, local_score, group)
     all_index, all_score = all_index.cpu().numpy(), all_score.cpu().numpy()
     if world > 1 and not ragged:
-        bad = np.nonzero((all_index < 0) & np.isneginf(all_score))[0]
+        bad = np.nonzero((all_index < 0) & np.isneginf(all_score.reshape(len(all_index), -1)[:, 0]))[0]
         if len(bad):
             raise ValueError("rank(s) %s handed merge_and_rank a shard longer than ceil(num_examples / world) = %d "
                              "entries; split the pool with shard_positions() or pass ragged=True"
                              % (sorted(set((bad // (per + 1)).tolist())), per))
-    return finish_ranking(all_index, all_score, num_examples, unlabelled, selection_size)
+    return all_index, all_score
 
 
 def _pad_to_common_length(index, score, group):
@@ -331,3 +364,117 @@ def finish_ranking(all_index, all_score, num_examples, unlabelled, selection_siz
     example_indices = select_lowest(unlabelled_confidence, selection_size)
     low_conf_examples = unlabelled[example_indices]
     return low_conf_examples, unlabelled_confidence
+
+
+# ---- region-level acquisition ------------------------------------------------------------------------------------------
+def select_regions(region_confidence, examples, selection_size, max_per_image=None, annotated=None):
+    """The ``selection_size`` least confident regions of a pool (host, numpy).
+
+    ``region_confidence`` [E, RY, RX] float32 (rounded from the float64 region scores the way ``finish_ranking`` rounds
+    image scores); ``examples`` [E] the example id of every row; ``annotated`` an optional bool array of the same shape:
+    those regions are never selected.  Regions are taken in the TOTAL order (score ascending, example id, ry, rx), so every
+    tie has one answer and every rank picks the same rows; with ``max_per_image = m`` the walk skips the regions of an
+    example that already has ``m`` selected.  Returns int64 [k, 3] rows ``(example id, ry, rx)`` in selection order,
+    ``k = min(selection_size, candidates)``."""
+    conf = np.asarray(region_confidence, dtype=np.float32)
+    if conf.ndim != 3:
+        raise ValueError("region_confidence must be [E, RY, RX] (got shape %s)" % (conf.shape,))
+    e = conf.shape[0]
+    examples = np.asarray(examples, dtype=np.int64).reshape(-1)
+    if len(examples) != e:
+        raise ValueError("examples has %d entries for %d rows of region_confidence" % (len(examples), e))
+    if max_per_image is not None and int(max_per_image) < 1:
+        raise ValueError("max_per_image must be >= 1 or None (got %r)" % (max_per_image,))
+    free = np.ones(conf.shape, dtype=bool)
+    if annotated is not None:
+        annotated = np.asarray(annotated, dtype=bool)
+        if annotated.shape != conf.shape:
+            raise ValueError("annotated must have shape %s (got %s)" % (conf.shape, annotated.shape))
+        free = ~annotated
+    row, yy, xx = np.nonzero(free)
+    order = np.lexsort((xx, yy, examples[row], conf[row, yy, xx]))  # lexsort: the LAST key is the primary one
+    row, yy, xx = row[order], yy[order], xx[order]
+    want = max(0, int(selection_size))
+    if max_per_image is None:
+        keep = np.arange(min(want, len(row)))
+    else:
+        # position of every candidate among the candidates of its own example id, in walk order: a capped walk takes a
+        # candidate iff fewer than m of its example's candidates came before it
+        ex = examples[row]
+        by_ex = np.argsort(ex, kind="stable")
+        sorted_ex = ex[by_ex]
+        first = np.searchsorted(sorted_ex, sorted_ex, side="left")
+        before = np.empty(len(row), dtype=np.int64)
+        before[by_ex] = np.arange(len(row)) - first
+        keep = np.nonzero(before < int(max_per_image))[0][:want]
+    return np.stack([examples[row[keep]], yy[keep], xx[keep]], axis=1).astype(np.int64).reshape(-1, 3)
+
+
+def finish_region_ranking(all_index, all_region_score, num_examples, unlabelled, selection_size, max_per_image=None,
+                          annotated=None):
+    """Host tail of ``rank_regions``, the region twin of ``finish_ranking``: scatter the gathered rows into a float32
+    [num_examples, RY, RX] array by example index (the float64 -> float32 rounding happens here), keep the unlabelled
+    examples, ``select_regions``.  ``annotated`` is aligned with ``unlabelled``: [len(unlabelled), RY, RX]."""
+    all_region_score = np.asarray(all_region_score)
+    confidence = np.zeros((num_examples,) + all_region_score.shape[1:], dtype=np.float32)
+    valid = all_index >= 0
+    confidence[all_index[valid]] = all_region_score[valid]
+    unlabelled = np.asarray(unlabelled, dtype=np.int64)
+    region_confidence = confidence[unlabelled]
+    selected = select_regions(region_confidence, unlabelled, selection_size, max_per_image, annotated)
+    return selected, region_confidence
+
+
+def merge_and_rank_regions(local_index, local_region_score, num_examples, unlabelled, selection_size, max_per_image=None,
+                           annotated=None, group=None, ragged=False):
+    """the collective + host tail of a region ranking pass: ``merge_and_rank`` with ``(index, RY * RX scores)`` rows --
+    the same ONE all-gather, the same behaviour on a too-long shard"""
+    all_index, all_score = _merge_shards(local_index, local_region_score, num_examples, group, ragged)
+    return finish_region_ranking(all_index, all_score, num_examples, unlabelled, selection_size, max_per_image, annotated)
+
+
+def rank_regions(net, batches, num_examples, unlabelled, selection_size, region=(128, 128), measure="entropy",
+                 max_per_image=None, annotated=None, group=None, prefetch=0, ragged=False, arithmetic="f32"):
+    """The region twin of ``rank_confidence``: which WINDOWS of the pool's frames is the network least sure about.
+
+    ``batches``, ``num_examples``, ``unlabelled``, ``group``, ``prefetch``, ``ragged`` and ``arithmetic`` as in
+    ``rank_confidence`` (the same strided shards, the same ``prefetch_to_device``); every batch goes through
+    ``net.score_regions(images, region, measure)``.  ``annotated`` (optional bool [len(unlabelled), RY, RX]) marks regions
+    that already have labels; ``max_per_image`` caps the regions taken from one frame (``select_regions``).  Returns
+    ``(selected [k, 3] int64 rows (example id, ry, rx) in selection order, region_confidence [len(unlabelled), RY, RX]
+    float32)``.
+
+    Collectives per pass: exactly ONE all-gather, of ``(index, RY * RX scores)`` rows; a rank whose shard is longer than
+    ``ceil(num_examples / world)`` makes EVERY rank raise ``ValueError`` after the collective (``ragged=True``: one extra
+    all-reduce(MAX) instead).  Every frame of the pool must have the same size (one region grid), and every rank scores at
+    least one batch (the grid comes from the frames) unless ``annotated`` states it."""
+    _check_arithmetic(net.score_regions, arithmetic)
+    torch = _lib.require_gpu()
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+        _lib.warn_if_few_hw_queues()  # caller + 2 chains + prefetch copy + RCCL = 5 streams (once per process)
+    rh, rw = _lib.region_size(region)
+    idx_chunks, score_chunks = [], []
+    if prefetch > 0:
+        batches = prefetch_to_device(batches, depth=prefetch)
+    for images, indices in batches:
+        if arithmetic == "f32":
+            _, r = net.score_regions(images, region=(rh, rw), measure=measure)
+        else:
+            _, r = net.score_regions(images, region=(rh, rw), measure=measure, arithmetic=arithmetic)
+        if score_chunks and tuple(r.shape[1:]) != tuple(score_chunks[0].shape[1:]):
+            raise ValueError("every frame of a region ranking pass must have the same size: region grid %s after %s"
+                             % (tuple(r.shape[1:]), tuple(score_chunks[0].shape[1:])))
+        score_chunks.append(r)  # [n, RY, RX] float64 on device, stream-ordered
+        idx_chunks.append(torch.as_tensor(np.asarray(indices, dtype=np.int64), device=r.device))
+    if score_chunks:
+        local_score = torch.cat(score_chunks)
+        local_index = torch.cat(idx_chunks)
+    else:
+        if annotated is None:
+            raise ValueError("rank_regions got no batch on this rank and no `annotated` array to take the region grid from")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        local_score = torch.zeros((0,) + tuple(np.shape(annotated)[1:]), dtype=torch.float64, device=dev)
+        local_index = torch.zeros((0,), dtype=torch.int64, device=dev)
+    return merge_and_rank_regions(local_index, local_score, num_examples, unlabelled, selection_size, max_per_image,
+                                  annotated, group, ragged)

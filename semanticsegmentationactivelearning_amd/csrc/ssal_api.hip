@@ -985,6 +985,25 @@ SSAL_API int ssal_enet_score_nhwc_arith(ssal_enet *net, const void *x_dev, int x
                      ws_bytes, stream, arithmetic);
 }
 
+// ---- region-level acquisition: the score pass, then the tile partials it leaves in the workspace folded into regions ----
+SSAL_API int ssal_enet_score_regions_nhwc_arith(ssal_enet *net, const void *x_dev, int x_is_u8, int n, int h, int w, int measure,
+                                                float threshold, int arithmetic, int rh, int rw, double *scores_dev,
+                                                double *region_scores_dev, uint8_t *label_dev, uint8_t *mask_dev,
+                                                float *conf_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    // the region arguments are judged first: they need neither a handle nor a device
+    int rc = region_check(h, w, rh, rw, true);
+    if (rc) return rc;
+    if (!region_scores_dev) return fail(SSAL_EINVAL, "region_scores_dev is NULL");
+    if ((rc = score_any(net, x_dev, x_is_u8 != 0, n, h, w, measure, threshold, scores_dev, label_dev, mask_dev, conf_dev,
+                        ws_dev, ws_bytes, stream, arithmetic)))
+        return rc;
+    // score_any has joined the image-group chains into the caller's stream and folded the same partials into scores_dev
+    const NetWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
+    HIP_TRY(launch_reduce_regions(W.partial, n, h, w, rh, rw, region_scores_dev, (hipStream_t)stream));
+    return SSAL_OK;
+}
+
 // ---- evaluation pass: forward + argmax + confusion matrix, fused (validation epoch of active_learning.py) ----
 static int64_t conf_replica_bytes(int classes)
 {

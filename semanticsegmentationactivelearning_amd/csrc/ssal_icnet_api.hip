@@ -606,6 +606,41 @@ SSAL_API int ssal_icnet_score_nhwc_u8(ssal_icnet *net, const uint8_t *x_dev, int
                      ws_bytes, stream);
 }
 
+// ---- region-level acquisition through the confidence plane (a fused tail inside k_upscore is not built: its partials
+// are linear 256-pixel blocks, not tiles) ----
+SSAL_API int64_t ssal_icnet_regions_workspace_bytes(const ssal_icnet *net, int n, int h, int w)
+{
+    const int64_t base = ssal_icnet_workspace_bytes(net, n, h, w);
+    return base < 0 ? base : base + (int64_t)n * h * w * 4 + 256;
+}
+
+SSAL_API int ssal_icnet_score_regions_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w, int measure,
+                                           float threshold, int rh, int rw, double *scores_dev, double *region_scores_dev,
+                                           uint8_t *label_dev, uint8_t *mask_dev, float *conf_dev, void *ws_dev,
+                                           int64_t ws_bytes, void *stream)
+{
+    // the region arguments are judged first: they need neither a handle nor a device
+    int rc = region_check(h, w, rh, rw, false);
+    if (rc) return rc;
+    if (!region_scores_dev) return fail(SSAL_EINVAL, "region_scores_dev is NULL");
+    if ((rc = check_dims(net, n, h, w))) return rc;
+    if (!region_plane_fits(n, h, w, rh, rw))
+        return fail(SSAL_EINVAL, "too many regions for one launch (n=%d h=%d w=%d rh=%d rw=%d): split the batch", n, h, w, rh, rw);
+    float *plane = conf_dev;
+    if (!plane && ws_dev) {  // the plane sits behind the buffers of the plain score call
+        Bump b(ws_dev, ws_bytes);
+        b.off = carve(net, nullptr, 0, n, h, w).bytes;
+        plane = b.take<float>((int64_t)n * h * w);
+        if (!b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
+                               (long long)ssal_icnet_regions_workspace_bytes(net, n, h, w), (long long)ws_bytes);
+    }
+    if ((rc = score_any(net, x_dev, x_is_u8 != 0, n, h, w, measure, threshold, scores_dev, label_dev, mask_dev, plane, ws_dev,
+                        ws_bytes, stream)))
+        return rc;
+    HIP_TRY(launch_region_means_plane(plane, n, h, w, rh, rw, region_scores_dev, (hipStream_t)stream));
+    return SSAL_OK;
+}
+
 SSAL_API int ssal_icnet_num_endpoints(const ssal_icnet *net) { return net ? (int)net->acts.size() : 0; }
 
 SSAL_API int ssal_icnet_endpoint_name(const ssal_icnet *net, int i, const char **name)

@@ -76,6 +76,16 @@ hipError_t launch_confusion_fold(const unsigned long long *rep, int reps, int K,
 hipError_t launch_reduce_mean(const double *partial, int N, int blocks, double pixels,
                               double *scores, hipStream_t s);
 
+// region-level acquisition (ssal_regions.hip; summation orders: ssal_regions.h).  h, w = the OUTPUT frame.
+// region_check: SSAL_OK or SSAL_EINVAL with the message set (whole_tiles: rh, rw must be multiples of 32)
+int region_check(int h, int w, int rh, int rw, bool whole_tiles);
+// out[n][RY][RX] = region means of the fused score pass' tile partials [N][ceil(h / 32)][ceil(w / 32)]
+hipError_t launch_reduce_regions(const double *partial, int N, int h, int w, int rh, int rw, double *out, hipStream_t s);
+// out[n][RY][RX] = region means of an fp32 plane [N,h,w]; any rh, rw >= 1.  64-bit offsets inside; region_plane_fits
+// states the one limit (a one-dimensional grid), the launcher returns hipErrorInvalidValue beyond it
+bool region_plane_fits(int n, int h, int w, int rh, int rw);
+hipError_t launch_region_means_plane(const float *plane, int n, int h, int w, int rh, int rw, double *out, hipStream_t s);
+
 // stand-alone score on materialised logits [N,H,W,K]
 int score_blocks(int H, int W);
 hipError_t launch_score_logits(const float *logits, int N, int H, int W, int K, int measure,

@@ -75,3 +75,19 @@ def run_inference(net, batches, output_dir, embedding_reversed=None, colormap=No
             write_png(path, out[k])
             written.append(path)
     return written
+
+
+def region_boxes(selected, region, size):
+    """Pixel boxes of selected regions for the annotation tool: ``selected`` [k, 3] rows ``(example id, ry, rx)`` as
+    ``active_learning.select_regions`` / ``rank_regions`` return them, ``region`` an int or ``(rh, rw)``, ``size`` the
+    frame's ``(h, w)``.  Returns int64 [k, 4] rows ``(y0, x0, y1, x1)`` (end-exclusive), clipped to the frame; a region
+    outside the frame's grid raises ValueError."""
+    rh, rw = _lib.region_size(region)
+    h, w = int(size[0]), int(size[1])
+    if rh <= 0 or rw <= 0 or h <= 0 or w <= 0:
+        raise ValueError("region and size must be positive (got region=%r size=%r)" % (region, size))
+    sel = np.asarray(selected, dtype=np.int64).reshape(-1, 3)
+    y0, x0 = sel[:, 1] * rh, sel[:, 2] * rw
+    if len(sel) and (sel[:, 1:].min() < 0 or y0.max() >= h or x0.max() >= w):
+        raise ValueError("a selected region lies outside the %d x %d grid of a %d x %d frame" % (-(-h // rh), -(-w // rw), h, w))
+    return np.stack([y0, x0, np.minimum(y0 + rh, h), np.minimum(x0 + rw, w)], axis=1).astype(np.int64).reshape(-1, 4)

@@ -269,6 +269,53 @@ class ENet(_lib.DeviceState):
             return scores, {"label": label, "mask": mask, "confidence": conf}
         return scores
 
+    # ---- region-level acquisition: per-image scores + per-region scores in one pass -------------------------------------
+    def score_regions(self, inputs, region=(128, 128), measure="entropy", threshold=0.0, return_label=False,
+                      return_mask=False, return_confidence=False, arithmetic="f32"):
+        """``score`` plus the mean confidence of every ``region`` (an int or ``(rh, rw)`` output pixels; grid anchored at
+        pixel (0, 0), bottom / right regions clipped by the frame).
+
+        Returns ``(scores [N] float64, region_scores [N, RY, RX] float64)`` on the device, plus the dict of per-pixel maps
+        when one was requested.  ``scores`` has the bits ``score`` gives.  A region size that is a multiple of 32 in both
+        directions takes the fused route: the Final kernel's 32 x 32 tile sums, which the pass computes anyway, are folded
+        into regions by one small launch (``ssal_enet_score_regions_nhwc_arith``; nothing per-pixel reaches HBM unless a
+        map was requested).  Any other size goes through the per-pixel confidence plane and ``ssal_region_means_plane``."""
+        if measure not in _lib.MEASURES:
+            raise NotImplementedError("Uncertainty function not implemented.")
+        arith = _lib.arithmetic_code(arithmetic)
+        rh, rw = _lib.region_size(region)
+        want_maps = return_label or return_mask or return_confidence
+        if rh <= 0 or rw <= 0 or (rh % _lib.REGION_TILE == 0 and rw % _lib.REGION_TILE == 0):
+            torch = _lib.require_gpu()
+            x = self._prepare(inputs, False)
+            n, h, w, _ = x.shape
+            ry, rx = _lib.region_grid(h, w, (rh, rw))  # ValueError for a size <= 0
+            L = _lib.lib()
+            with torch.cuda.device(x.device):
+                handle = self._sync_handle()
+                nbytes = L.ssal_enet_workspace_bytes(handle, n, h, w)
+                if nbytes < 0:
+                    raise ValueError("bad input dims %s" % (tuple(x.shape),))
+                ws = self._workspace(nbytes, x.device)
+                scores = torch.empty((n,), dtype=torch.float64, device=x.device)
+                regions = torch.empty((n, ry, rx), dtype=torch.float64, device=x.device)
+                label = torch.empty((n, h, w), dtype=torch.uint8, device=x.device) if return_label else None
+                mask = torch.empty((n, h, w), dtype=torch.uint8, device=x.device) if return_mask else None
+                conf = torch.empty((n, h, w), dtype=torch.float32, device=x.device) if return_confidence else None
+                _lib.check(L.ssal_enet_score_regions_nhwc_arith(
+                    handle, _lib.dev_ptr(x), int(x.dtype == torch.uint8), n, h, w, _lib.MEASURES[measure], float(threshold),
+                    arith, rh, rw, _lib.dev_ptr(scores), _lib.dev_ptr(regions), _lib.dev_ptr(label), _lib.dev_ptr(mask),
+                    _lib.dev_ptr(conf), _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))
+                self._note_call(ws, (n, h, w), "score")
+            maps = {"label": label, "mask": mask, "confidence": conf}
+        else:
+            scores, maps = self.score(inputs, measure=measure, threshold=threshold, return_label=return_label,
+                                      return_mask=return_mask, return_confidence=True, arithmetic=arithmetic)
+            regions = _lib.region_means_plane(maps["confidence"], (rh, rw))
+            if not return_confidence:
+                maps["confidence"] = None
+        return (scores, regions, maps) if want_maps else (scores, regions)
+
     # ---- fused validation pass (active_learning.py:277-282 + tensortools.metrics.Metrics :390-427) ----------------------
     def evaluate(self, inputs, labels, mask=None, confusion=None, arithmetic="f32"):
         """forward(training=False) + argmax + masked confusion matrix in one pass: the logits and the predicted labels

@@ -228,6 +228,40 @@ class ICNet(_lib.DeviceState):
             return scores, {"label": label, "mask": mask, "confidence": conf}
         return scores
 
+    # ---- region-level acquisition ------------------------------------------------------------------------------------------
+    def score_regions(self, inputs, region=(128, 128), measure="margin", threshold=0.0, return_label=False,
+                      return_mask=False, return_confidence=False):
+        """``score`` plus the mean confidence of every ``region`` (an int or ``(rh, rw)`` output pixels, any size >= 1; grid
+        anchored at pixel (0, 0), bottom / right regions clipped).  Returns ``(scores [N] float64, region_scores
+        [N, RY, RX] float64)`` on the device, plus the dict of per-pixel maps when one was requested; ``scores`` has the bits
+        ``score`` gives.  ICNet's route goes through the per-pixel confidence plane (``ssal_icnet_score_regions_nhwc``)."""
+        if measure not in _lib.MEASURES:
+            raise NotImplementedError("Uncertainty function not implemented.")
+        rh, rw = _lib.region_size(region)
+        torch = _lib.require_gpu()
+        x = self._prepare(inputs, False)
+        n, h, w, _ = x.shape
+        ry, rx = _lib.region_grid(h, w, (rh, rw))  # ValueError for a size <= 0
+        L = _lib.lib()
+        with torch.cuda.device(x.device):
+            handle = self._sync_handle()
+            # with a caller-visible confidence plane the plain workspace is enough; otherwise the plane lives behind it
+            nbytes = (L.ssal_icnet_workspace_bytes if return_confidence else L.ssal_icnet_regions_workspace_bytes)(handle, n, h, w)
+            ws = self._workspace(nbytes, x.device)
+            scores = torch.empty((n,), dtype=torch.float64, device=x.device)
+            regions = torch.empty((n, ry, rx), dtype=torch.float64, device=x.device)
+            label = torch.empty((n, h, w), dtype=torch.uint8, device=x.device) if return_label else None
+            mask = torch.empty((n, h, w), dtype=torch.uint8, device=x.device) if return_mask else None
+            conf = torch.empty((n, h, w), dtype=torch.float32, device=x.device) if return_confidence else None
+            _lib.check(L.ssal_icnet_score_regions_nhwc(
+                handle, _lib.dev_ptr(x), int(x.dtype == torch.uint8), n, h, w, _lib.MEASURES[measure], float(threshold),
+                rh, rw, _lib.dev_ptr(scores), _lib.dev_ptr(regions), _lib.dev_ptr(label), _lib.dev_ptr(mask),
+                _lib.dev_ptr(conf), _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))
+            self._note_call(ws, (n, h, w), "score")
+        if return_label or return_mask or return_confidence:
+            return scores, regions, {"label": label, "mask": mask, "confidence": conf}
+        return scores, regions
+
     # ---- validation pass (active_learning.py:277-282 + tensortools.metrics.Metrics :390-427) ----------------------------
     def evaluate(self, inputs, labels, mask=None, confusion=None):
         """forward(training=False) + argmax + masked confusion matrix: ``ENet.evaluate``'s contract (int64 [K, K] device
