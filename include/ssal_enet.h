@@ -369,6 +369,40 @@ int ssal_png_decode_nhwc(const uint8_t *payload_dev, int64_t payload_bytes, cons
 int ssal_inflate_host(const uint8_t *in, int64_t in_len, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t *status);
 int ssal_png_unfilter_host(uint8_t *raw, int height, int width, int bpp, int32_t *status);
 
+/* ---- Output-layer training (active_learning.py:283-326 with -r/--reinitialize-output-layer, :905-909, 461-462) ----
+ * The gradient of tensortools.losses.masked_softmax_cross_entropy (tensortools/losses.py:3-74, the semantics of
+ * ssal_masked_softmax_cross_entropy) with respect to Final.kernel (enet_modules.py:1294-1381), and the TF-1.13
+ * AdamOptimizer update that train_op = optimizer.minimize(cost) (active_learning.py:321-324) applies to it.  The trunk is
+ * frozen and evaluated with training=False.
+ *
+ * ssal_final_grad_nhwc: features_dev [n,h,w,16] fp32 (Bottleneck5_1's output, ENet.endpoint_outputs), kernel_dev
+ * [3][3][classes][16] (TF HW-O-I), labels_dev uint8 / mask_dev fp32 [n,2h,2w].  Writes loss_dev (one float64: the loss
+ * the forward op gives, up to the order of its float64 sums) and grad_dev [3][3][classes][16] fp32 = d loss / d kernel
+ * (TensorFlow's gradient: softmax - one_hot for the cross entropy, the derivative of the class weight through p_class when
+ * weight > 1).  The logits never reach HBM; there are no float atomics (two calls give the same bits).  SSAL_EINVAL for
+ * classes outside [2, 32], bad sizes, or h x w beyond the kernel's limit (2h + 1, 2w + 1 and the count of 16 x 16 tiles
+ * must fit an int); ssal_final_grad_workspace_bytes then returns -1. */
+int64_t ssal_final_grad_workspace_bytes(int n, int h, int w, int classes);
+int ssal_final_grad_nhwc(const float *features_dev, int n, int h, int w, int classes, const float *kernel_dev,
+                         const uint8_t *labels_dev, const float *mask_dev, float weight, float label_smoothing,
+                         double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream);
+/* The same from images x_dev [n,h,w,c_in] (fp32, or uint8 with x_is_u8): the committed trunk's launchers up to
+ * Bottleneck5_1, then the gradient kernel on its output; labels_dev / mask_dev [n,h,w]; kernel_dev as above (the kernel
+ * being trained: the handle's own Final weights are not used).  The workspace holds the forward workspace and the
+ * gradient's partials. */
+int64_t ssal_enet_train_final_workspace_bytes(const ssal_enet *net, int n, int h, int w);
+int ssal_enet_train_final_nhwc(ssal_enet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                               const uint8_t *labels_dev, const float *mask_dev, const float *kernel_dev, float weight,
+                               float label_smoothing, double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes,
+                               void *stream);
+/* Keras l1_l2(l1, l2) regulariser gradient (2 l2 w + l1 sign(w), sign(0) = 0) and TF-1.13 ApplyAdam, in place on count
+ * elements of var / m / v (fp32): alpha = lr sqrt(1 - beta2_power) / (1 - beta1_power); m += (g - m)(1 - beta1);
+ * v += (g^2 - v)(1 - beta2); var -= (m alpha) / (sqrt(v) + eps).  sqrt and the divisions are correctly rounded.  The
+ * caller keeps the fp32 beta powers (multiplied by beta1 / beta2 after each step) and the learning rate schedule. */
+int ssal_adam_apply(float *var_dev, float *m_dev, float *v_dev, const float *grad_dev, int64_t count, float lr,
+                    float beta1, float beta2, float eps, float beta1_power, float beta2_power, float l1, float l2,
+                    void *stream);
+
 #ifdef __cplusplus
 }
 #endif

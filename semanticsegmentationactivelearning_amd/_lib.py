@@ -170,6 +170,12 @@ PROTOTYPES = {
     "ssal_png_decode_nhwc": (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "ssal_inflate_host": (_i, [_vp, _i64, _vp, _i64, _c.POINTER(_i64), _c.POINTER(_c.c_int32)]),
     "ssal_png_unfilter_host": (_i, [_vp, _i, _i, _i, _c.POINTER(_c.c_int32)]),
+    # ---- output-layer training (include/ssal_enet.h) ----
+    "ssal_final_grad_workspace_bytes": (_i64, [_i, _i, _i, _i]),
+    "ssal_final_grad_nhwc": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_enet_train_final_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
+    "ssal_enet_train_final_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_adam_apply": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _f, _f, _f, _vp]),
     # ---- measurement aids (include/ssal_enet.h) ----
     "ssal_profile_enable": (_i, [_i]),
     "ssal_profile_collect": (_i, [_c.c_char_p, _i64]),

@@ -478,3 +478,38 @@ def rank_regions(net, batches, num_examples, unlabelled, selection_size, region=
         local_index = torch.zeros((0,), dtype=torch.int64, device=dev)
     return merge_and_rank_regions(local_index, local_score, num_examples, unlabelled, selection_size, max_per_image,
                                   annotated, group, ragged)
+
+
+def training_targets(labelled, labels, mask, pseudo_label, pseudo_mask):
+    """The training batch's targets (active_learning.py:272-275): per image, the annotation where the example is
+    labelled and the pseudo annotation (``score(return_label=True, return_mask=True)``) where it is not --
+    ``tf.where(train_labelled, train_label, pseudo_label)`` and the same for the mask.
+
+    ``labelled`` [N] bool; ``labels`` / ``mask`` / ``pseudo_label`` / ``pseudo_mask`` [N, H, W] (numpy arrays or torch
+    tensors, all of one kind).  The pseudo planes are cast to the dtype of the annotation, as the reference builds them
+    (:265-269).  Returns ``(label, mask)``."""
+    try:
+        import torch
+        is_torch = isinstance(labels, torch.Tensor)
+    except ImportError:  # pragma: no cover
+        is_torch = False
+    if is_torch:
+        sel = torch.as_tensor(labelled, dtype=torch.bool, device=labels.device)
+        if sel.dim() != 1 or sel.shape[0] != labels.shape[0]:
+            raise ValueError("labelled must be a [N] vector (N = %d)" % labels.shape[0])
+        for name, t in (("mask", mask), ("pseudo_label", pseudo_label), ("pseudo_mask", pseudo_mask)):
+            if tuple(t.shape) != tuple(labels.shape):
+                raise ValueError("%s must have shape %s (got %s)" % (name, tuple(labels.shape), tuple(t.shape)))
+        sel = sel.view((-1,) + (1,) * (labels.dim() - 1))
+        return (torch.where(sel, labels, pseudo_label.to(device=labels.device, dtype=labels.dtype)),
+                torch.where(sel, mask, pseudo_mask.to(device=mask.device, dtype=mask.dtype)))
+    labels, mask = np.asarray(labels), np.asarray(mask)
+    sel = np.asarray(labelled, dtype=bool)
+    if sel.ndim != 1 or sel.shape[0] != labels.shape[0]:
+        raise ValueError("labelled must be a [N] vector (N = %d)" % labels.shape[0])
+    for name, t in (("mask", mask), ("pseudo_label", pseudo_label), ("pseudo_mask", pseudo_mask)):
+        if np.shape(t) != labels.shape:
+            raise ValueError("%s must have shape %s (got %s)" % (name, labels.shape, np.shape(t)))
+    sel = sel.reshape((-1,) + (1,) * (labels.ndim - 1))
+    return (np.where(sel, labels, np.asarray(pseudo_label).astype(labels.dtype)),
+            np.where(sel, mask, np.asarray(pseudo_mask).astype(mask.dtype)))

@@ -1701,3 +1701,99 @@ SSAL_API int ssal_profile_collect(char *json_out, int64_t cap)
     memcpy(json_out, js.c_str(), js.size() + 1);
     return SSAL_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Output-layer training (include/ssal_enet.h, "Output-layer training")
+// ------------------------------------------------------------------------------------------------
+static int final_grad_check(int n, int h, int w, int classes)
+{
+    if (classes < 2 || classes > 32) return fail(SSAL_EINVAL, "classes must be in [2,32] (got %d)", classes);
+    if (n <= 0 || h <= 0 || w <= 0) return fail(SSAL_EINVAL, "bad dims n=%d h=%d w=%d", n, h, w);
+    if (!final_grad_fits(h, w))
+        return fail(SSAL_EINVAL, "feature map %dx%d is beyond the output-layer gradient kernel's limit", h, w);
+    return SSAL_OK;
+}
+
+// part [G][9 * K * 16] fp32, then lpart [G][2] float64 (G = final_grad_workgroups)
+static void final_grad_carve(Bump &b, int h, int w, int classes, float **part, double **lpart)
+{
+    const int64_t G = final_grad_workgroups(h, w);
+    *part = b.take<float>(G * 9 * classes * 16);
+    *lpart = b.take<double>(2 * G);
+}
+
+SSAL_API int64_t ssal_final_grad_workspace_bytes(int n, int h, int w, int classes)
+{
+    if (classes < 2 || classes > 32 || n <= 0 || h <= 0 || w <= 0 || !final_grad_fits(h, w)) return -1;
+    Bump b(nullptr, 0);
+    float *part;
+    double *lpart;
+    final_grad_carve(b, h, w, classes, &part, &lpart);
+    return b.off + 256;
+}
+
+SSAL_API int ssal_final_grad_nhwc(const float *features_dev, int n, int h, int w, int classes, const float *kernel_dev,
+                                  const uint8_t *labels_dev, const float *mask_dev, float weight, float label_smoothing,
+                                  double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    if (int rc = final_grad_check(n, h, w, classes)) return rc;
+    if (!features_dev || !kernel_dev || !labels_dev || !mask_dev || !loss_dev || !grad_dev || !ws_dev)
+        return fail(SSAL_EINVAL, "NULL device pointer");
+    const int64_t need = ssal_final_grad_workspace_bytes(n, h, w, classes);
+    if (ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
+                                     (long long)ws_bytes);
+    Bump b(ws_dev, ws_bytes);
+    float *part;
+    double *lpart;
+    final_grad_carve(b, h, w, classes, &part, &lpart);
+    HIP_TRY(launch_final_grad(features_dev, n, h, w, kernel_dev, classes, labels_dev, mask_dev, weight, label_smoothing,
+                              part, lpart, loss_dev, grad_dev, (hipStream_t)stream));
+    return SSAL_OK;
+}
+
+SSAL_API int64_t ssal_enet_train_final_workspace_bytes(const ssal_enet *net, int n, int h, int w)
+{
+    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 8 || w % 8) return -1;
+    const int64_t g = ssal_final_grad_workspace_bytes(n, h / 2, w / 2, net->classes);
+    if (g < 0) return -1;
+    return carve(net, nullptr, 0, n, h, w).bytes + 256 + g;
+}
+
+SSAL_API int ssal_enet_train_final_nhwc(ssal_enet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                                        const uint8_t *labels_dev, const float *mask_dev, const float *kernel_dev,
+                                        float weight, float label_smoothing, double *loss_dev, float *grad_dev,
+                                        void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    int rc = check_dims(net, n, h, w);
+    if (rc) return rc;
+    if ((rc = final_grad_check(n, h / 2, w / 2, net->classes))) return rc;
+    if (!x_dev || !labels_dev || !mask_dev || !kernel_dev || !loss_dev || !grad_dev || !ws_dev)
+        return fail(SSAL_EINVAL, "NULL device pointer");
+    const int64_t need = ssal_enet_train_final_workspace_bytes(net, n, h, w);
+    if (ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
+                                     (long long)ws_bytes);
+    NetWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
+    char *gws = (char *)ws_dev + (W.bytes + 255) / 256 * 256;
+    Bump b(gws, ws_bytes - (gws - (char *)ws_dev));
+    float *part;
+    double *lpart;
+    final_grad_carve(b, h / 2, w / 2, net->classes, &part, &lpart);
+    if (!W.ok || !b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes", (long long)need);
+    hipStream_t s = (hipStream_t)stream;
+    // the trunk, training=False: Initial .. Bottleneck5_1 on the caller's stream (its output lands in W.a1)
+    for (int li = 0; li < kNumLayers - 1; ++li) HIP_TRY(run_layer_idx(net, li, x_dev, x_is_u8 != 0, W, n, h, w, s));
+    HIP_TRY(launch_final_grad(W.a1, n, h / 2, w / 2, kernel_dev, net->classes, labels_dev, mask_dev, weight,
+                              label_smoothing, part, lpart, loss_dev, grad_dev, s));
+    return SSAL_OK;
+}
+
+SSAL_API int ssal_adam_apply(float *var_dev, float *m_dev, float *v_dev, const float *grad_dev, int64_t count, float lr,
+                             float beta1, float beta2, float eps, float beta1_power, float beta2_power, float l1, float l2,
+                             void *stream)
+{
+    if (!var_dev || !m_dev || !v_dev || !grad_dev) return fail(SSAL_EINVAL, "NULL device pointer");
+    if (count <= 0 || count > ((int64_t)1 << 36)) return fail(SSAL_EINVAL, "bad element count %lld", (long long)count);
+    HIP_TRY(launch_adam(var_dev, m_dev, v_dev, grad_dev, count, lr, beta1, beta2, eps, beta1_power, beta2_power, l1, l2,
+                        (hipStream_t)stream));
+    return SSAL_OK;
+}

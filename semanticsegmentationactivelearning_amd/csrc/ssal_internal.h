@@ -98,6 +98,18 @@ hipError_t launch_masked_xent(const float *logits, const uint8_t *labels, const 
                               int H, int W, int K, float weight, float label_smoothing,
                               double *partial, double *out, hipStream_t s);
 
+// output-layer training (ssal_train_final.hip).  x [N,H,W,16] = Bottleneck5_1's output, wk [3][3][K][16] (TF HW-O-I),
+// labels uint8 / mask fp32 [N,2H,2W].  part: final_grad_workgroups(H, W) * 9 * K * 16 floats, lpart: 2 * that many
+// doubles; loss one double, grad [3][3][K][16].  64-bit offsets; final_grad_fits states the int limits (the launcher
+// returns hipErrorInvalidValue beyond them).
+bool final_grad_fits(int H, int W);
+int final_grad_workgroups(int H, int W);
+hipError_t launch_final_grad(const float *x, int N, int H, int W, const float *wk, int K, const uint8_t *labels,
+                             const float *mask, float weight, float label_smoothing, float *part, double *lpart,
+                             double *loss, float *grad, hipStream_t s);
+hipError_t launch_adam(float *var, float *m, float *v, const float *grad, long count, float lr, float beta1, float beta2,
+                       float eps, float beta1_power, float beta2_power, float l1, float l2, hipStream_t s);
+
 // pooling / unpooling with reference int64 indices
 hipError_t launch_maxpool_argmax(const float *x, int N, int H, int W, int C, float *y,
                                  int64_t *argmax, int include_batch, hipStream_t s);

@@ -12,6 +12,7 @@
 #include "ssal_prof.h"
 #include "ssal_score.h"
 #include "ssal_confusion.h"
+#include "ssal_xent.h"
 #include <float.h>
 
 namespace ssal {
@@ -900,24 +901,7 @@ __global__ __launch_bounds__(256) void k_masked_xent(const float *__restrict__ l
             float x[K];
 #pragma unroll
             for (int k = 0; k < K; ++k) x[k] = l[k];
-            float m = x[0];
-#pragma unroll
-            for (int k = 1; k < K; ++k) m = fmaxf(m, x[k]);
-            float S = 0.0f;
-#pragma unroll
-            for (int k = 0; k < K; ++k) S += expf(x[k] - m);
-            const float logS = logf(S);
-            float ce = 0.0f, pc = 0.0f;
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                const float yk = (k == lab) ? on_value : off_value;
-                const float d = x[k] - m;
-                ce += yk * (logS - d);
-                pc += yk * (expf(d) / S);
-            }
-            ce *= mk;
-            if (weight > 1.0f) ce *= 1.0f / logf(weight + (1.718281828459045f - weight) * pc);
-            bsum += ce;
+            bsum += xent_pixel<K>(x, lab, mk, weight, on_value, off_value).ce;  // ssal_xent.h (shared with k_final_grad)
             msum += (double)mk;
         }
         loss = (double)bsum;

@@ -1,0 +1,230 @@
+"""Training of ENet's output layer on the MI355X: the reference's ``-r/--reinitialize-output-layer`` case
+(active_learning.py:905-909, 461-462) followed by its ``train_op`` (:283-326) restricted to ``Final.kernel``.
+
+``FinalLayerTrainer(net, ...)`` keeps the Adam state of ``net.Final.kernel`` on the device.  One ``step`` runs the frozen
+trunk (``training=False``: moving averages, no dropout), then ONE fused kernel that recomputes the Final logits, the
+masked softmax cross entropy and dL/dlogit and contracts them with the Bottleneck5_1 features into dL/dW (the logits never
+reach HBM), then the Keras ``l1_l2`` regulariser gradient and TF-1.13 ``ApplyAdam``.  The one deliberate difference from the
+reference: its ``train_op`` trains every layer with batch statistics; here the trunk is frozen and evaluated in inference
+mode.
+"""
+import numpy as np
+
+from . import _lib
+from .models.enet import enet_modules as _mod
+
+
+class FinalLayerTrainer:
+    """Adam on ``net.Final.kernel`` [3, 3, K, 16] of an ``ENet``; hyper-parameters as in the reference's JSON
+    (``from_params``).  ``loginverse_scaling`` is the loss' ``weight`` (ENet class weighting when > 1)."""
+
+    def __init__(self, net, learning_rate, beta1=0.9, beta2=0.999, epsilon=1e-8, l1=0.0, l2=0.0, loginverse_scaling=0.0,
+                 label_smoothing=0.0, learning_rate_decay=0.0, decay_steps=None):
+        from .models.enet.enet import ENet
+        if not isinstance(net, ENet):
+            raise NotImplementedError("output-layer training is implemented for ENet only (got %s)" % type(net).__name__)
+        if not (2 <= int(net.classes) <= 32):
+            raise ValueError("classes must be in [2, 32] (got %d)" % net.classes)
+        if learning_rate_decay > 0.0 and not decay_steps:
+            raise ValueError("learning_rate_decay > 0 needs decay_steps (the reference uses the batches per epoch)")
+        self.net = net
+        self.learning_rate = float(learning_rate)
+        self.beta1, self.beta2, self.epsilon = float(beta1), float(beta2), float(epsilon)
+        self.l1, self.l2 = float(l1), float(l2)
+        self.weight = float(loginverse_scaling)
+        self.label_smoothing = float(label_smoothing)
+        self.learning_rate_decay = float(learning_rate_decay)
+        self.decay_steps = decay_steps
+        self._dev = None  # device tensors: w, m, v, grad, loss
+        self._t = 0
+        self._b1p, self._b2p = np.float32(self.beta1), np.float32(self.beta2)  # AdamOptimizer's beta powers (fp32)
+        self._m0 = self._v0 = None
+
+    @classmethod
+    def from_params(cls, net, params, decay_steps=None):
+        """The reference's JSON layout (conf/*.json): ``hyperparams.learning_rate``, ``.learning_rate_decay``,
+        ``.optimizer.kwargs`` (beta1, beta2, epsilon), ``.weight_reg.{L1, L2}``, ``.softmax.{loginverse_scaling,
+        label_smoothing, multiscale}``.  ``params`` may be the whole file or its ``hyperparams`` section."""
+        hp = params.get("hyperparams", params)
+        sm = hp.get("softmax", {})
+        if sm.get("multiscale", False):
+            raise NotImplementedError("softmax.multiscale: the auxiliary heads are not trained here")
+        opt = hp.get("optimizer", {})
+        if opt.get("type", "Adam") != "Adam":
+            raise NotImplementedError("optimizer %r: only Adam is implemented" % opt.get("type"))
+        kw = dict(opt.get("kwargs", {}))
+        reg = hp.get("weight_reg", {})
+        return cls(net, learning_rate=hp["learning_rate"], beta1=kw.get("beta1", 0.9), beta2=kw.get("beta2", 0.999),
+                   epsilon=kw.get("epsilon", 1e-8), l1=reg.get("L1", 0.0) or 0.0, l2=reg.get("L2", 0.0) or 0.0,
+                   loginverse_scaling=sm.get("loginverse_scaling", 0.0) or 0.0,
+                   label_smoothing=sm.get("label_smoothing", 0.0) or 0.0,
+                   learning_rate_decay=hp.get("learning_rate_decay", 0.0) or 0.0, decay_steps=decay_steps)
+
+    # ---- state -----------------------------------------------------------------------------------------------------
+    def _kernel_var(self):
+        if not self.net.built:
+            raise RuntimeError("build the model (call it once, or .build(input_shape)) before training")
+        return self.net.Final.kernel
+
+    def reinitialize(self, seed=None):
+        """``sess.run(train_net.Final.kernel.initializer)`` (active_learning.py:461-462): glorot-uniform, the layer's default
+        initializer, drawn from ``seed``.  The optimizer state is reset too."""
+        var = self._kernel_var()
+        var.assign(_mod.glorot_uniform(seed)(var.shape))
+        self.load_state({"m": np.zeros(var.shape, np.float32), "v": np.zeros(var.shape, np.float32), "t": 0})
+
+    @property
+    def state(self):
+        """``{"m", "v"}`` float32 host copies of Adam's slots and ``"t"`` (steps taken)"""
+        if self._dev is None:
+            shape = self._kernel_var().shape
+            m = self._m0 if self._m0 is not None else np.zeros(shape, np.float32)
+            v = self._v0 if self._v0 is not None else np.zeros(shape, np.float32)
+            return {"m": m.copy(), "v": v.copy(), "t": self._t}
+        return {"m": self._dev["m"].cpu().numpy(), "v": self._dev["v"].cpu().numpy(), "t": self._t}
+
+    def load_state(self, state):
+        shape = self._kernel_var().shape
+        m = np.ascontiguousarray(state["m"], dtype=np.float32)
+        v = np.ascontiguousarray(state["v"], dtype=np.float32)
+        if m.shape != shape or v.shape != shape:
+            raise ValueError("m / v must have shape %s" % (shape,))
+        self._t = int(state["t"])
+        self._b1p = np.float32(1.0)
+        self._b2p = np.float32(1.0)
+        for _ in range(self._t + 1):  # beta powers as AdamOptimizer holds them before step t + 1 (fp32 products)
+            self._b1p = np.float32(self._b1p * np.float32(self.beta1))
+            self._b2p = np.float32(self._b2p * np.float32(self.beta2))
+        self._m0, self._v0 = m, v
+        self._dev = None
+
+    def current_learning_rate(self):
+        """tf.train.inverse_time_decay(lr, global_step, decay_steps, decay_rate) (not staircase), fp32 as TF computes it;
+        global_step = the number of steps taken so far"""
+        lr = np.float32(self.learning_rate)
+        if self.learning_rate_decay > 0.0:
+            p = np.float32(np.float32(self._t) / np.float32(self.decay_steps))
+            lr = np.float32(lr / np.float32(np.float32(1.0) + np.float32(self.learning_rate_decay) * p))
+        return lr
+
+    def _device_state(self, device):
+        torch = _lib.require_gpu()
+        var = self._kernel_var()
+        if self._dev is None or self._dev["w"].device != device or self._dev["version"] != var.version:
+            shape = var.shape
+            m = self._m0 if self._m0 is not None else (self._dev["m"].cpu().numpy() if self._dev else np.zeros(shape, np.float32))
+            v = self._v0 if self._v0 is not None else (self._dev["v"].cpu().numpy() if self._dev else np.zeros(shape, np.float32))
+            self._dev = {
+                "w": torch.from_numpy(np.array(var.numpy(), dtype=np.float32)).to(device),
+                "m": torch.from_numpy(np.array(m)).to(device),
+                "v": torch.from_numpy(np.array(v)).to(device),
+                "grad": torch.empty(shape, dtype=torch.float32, device=device),
+                "version": var.version,
+            }
+            self._m0 = self._v0 = None
+        return self._dev
+
+    # ---- gradients ---------------------------------------------------------------------------------------------------
+    def _targets(self, labels, mask, shape, device):
+        torch = _lib.require_gpu()
+        lab = labels if isinstance(labels, torch.Tensor) else torch.as_tensor(np.asarray(labels))
+        mk = mask if isinstance(mask, torch.Tensor) else torch.as_tensor(np.asarray(mask))
+        if tuple(lab.shape) != shape:
+            raise ValueError("labels must have shape %s (got %s)" % (shape, tuple(lab.shape)))
+        if tuple(mk.shape) != shape:
+            raise ValueError("mask must have shape %s (got %s)" % (shape, tuple(mk.shape)))
+        lab = lab.to(device=device, dtype=torch.uint8).contiguous()
+        mk = mk.to(device=device, dtype=torch.float32).contiguous()
+        return lab, mk
+
+    def gradient_features(self, features, labels, mask, kernel=None):
+        """(loss float64 [1], dL/dW [3, 3, K, 16] fp32) on the device for Bottleneck5_1 features [N, h, w, 16] and
+        labels / mask [N, 2h, 2w]; ``kernel`` defaults to ``net.Final.kernel``.  No update."""
+        torch = _lib.require_gpu()
+        x = _lib.as_device_f32(features)
+        if x.dim() != 4 or x.shape[-1] != 16:
+            raise ValueError("features must be [N,h,w,16] (got %s)" % (tuple(x.shape),))
+        n, h, w, _ = x.shape
+        k = self.net.classes
+        lab, mk = self._targets(labels, mask, (n, 2 * h, 2 * w), x.device)
+        kern = _lib.as_device_f32(self._kernel_var().numpy() if kernel is None else kernel).to(x.device)
+        if tuple(kern.shape) != (3, 3, k, 16):
+            raise ValueError("kernel must be [3,3,%d,16] (got %s)" % (k, tuple(kern.shape)))
+        L = _lib.lib()
+        with torch.cuda.device(x.device):
+            nbytes = L.ssal_final_grad_workspace_bytes(n, h, w, k)
+            if nbytes < 0:
+                raise ValueError("feature map %dx%d is beyond the gradient kernel's limit" % (h, w))
+            ws = torch.empty(int(nbytes), dtype=torch.uint8, device=x.device)
+            loss = torch.empty((1,), dtype=torch.float64, device=x.device)
+            grad = torch.empty((3, 3, k, 16), dtype=torch.float32, device=x.device)
+            _lib.check(L.ssal_final_grad_nhwc(_lib.dev_ptr(x), n, h, w, k, _lib.dev_ptr(kern), _lib.dev_ptr(lab),
+                                              _lib.dev_ptr(mk), self.weight, self.label_smoothing, _lib.dev_ptr(loss),
+                                              _lib.dev_ptr(grad), _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))
+        return loss, grad
+
+    def _trunk_handle(self):
+        """the net's handle for the current device.  Only Final.kernel changes between steps, and this entry takes the
+        kernel as an argument: the whole weight set (1.5 MB) is pushed and committed again only when a TRUNK variable
+        changed.  The handle's pushed-versions record keeps the old Final version, so the next score / evaluate / call
+        pushes the new kernel."""
+        torch = _lib.require_gpu()
+        net = self.net
+        ent = net._handles.get(torch.cuda.current_device())
+        if ent is not None and ent[1] is not None:
+            trunk = tuple(v.version for v in net.variables)[:-1]
+            if trunk == ent[1][:-1]:
+                return ent[0]
+        return net._sync_handle()
+
+    def _apply(self, dev, grad):
+        lr = self.current_learning_rate()
+        _lib.check(_lib.lib().ssal_adam_apply(_lib.dev_ptr(dev["w"]), _lib.dev_ptr(dev["m"]), _lib.dev_ptr(dev["v"]),
+                                              _lib.dev_ptr(grad), dev["w"].numel(), float(lr), self.beta1, self.beta2,
+                                              self.epsilon, float(self._b1p), float(self._b2p), self.l1, self.l2,
+                                              _lib.stream_ptr()))
+        self._t += 1
+        self._b1p = np.float32(self._b1p * np.float32(self.beta1))
+        self._b2p = np.float32(self._b2p * np.float32(self.beta2))
+        # the host variable is the model's weight of record: score / evaluate / __call__ push it on their next call
+        host = dev["w"].cpu().numpy()  # (synchronises the stream: 11 KB at K = 19)
+        self.net.Final.kernel.assign(host)
+        dev["version"] = self.net.Final.kernel.version
+
+    def step_features(self, features, labels, mask):
+        """one Adam step from cached Bottleneck5_1 features (``ENet.endpoint_outputs[0][1]``); returns the loss (float64
+        device scalar) of the kernel BEFORE the step, as ``sess.run([loss, train_op])`` does"""
+        x = _lib.as_device_f32(features)
+        dev = self._device_state(x.device)
+        loss, grad = self.gradient_features(x, labels, mask, kernel=dev["w"])
+        self._apply(dev, grad)
+        return loss[0]
+
+    def step(self, images, labels, mask):
+        """one Adam step from images [N, H, W, C] (fp32 or decoded uint8) and labels / mask [N, H, W]: the frozen trunk
+        up to Bottleneck5_1, the fused gradient kernel, Adam.  Returns the loss (float64 device scalar) before the step."""
+        torch = _lib.require_gpu()
+        net = self.net
+        x = net._prepare(images, False)
+        n, h, w, _ = x.shape
+        k = net.classes
+        lab, mk = self._targets(labels, mask, (n, h, w), x.device)
+        L = _lib.lib()
+        with torch.cuda.device(x.device):
+            dev = self._device_state(x.device)
+            handle = self._trunk_handle()
+            nbytes = L.ssal_enet_train_final_workspace_bytes(handle, n, h, w)
+            if nbytes < 0:
+                raise ValueError("bad input dims %s" % (tuple(x.shape),))
+            ws = net._workspace(nbytes, x.device)
+            loss = torch.empty((1,), dtype=torch.float64, device=x.device)
+            _lib.check(L.ssal_enet_train_final_nhwc(handle, _lib.dev_ptr(x), int(x.dtype == torch.uint8), n, h, w,
+                                                    _lib.dev_ptr(lab), _lib.dev_ptr(mk), _lib.dev_ptr(dev["w"]), self.weight,
+                                                    self.label_smoothing, _lib.dev_ptr(loss), _lib.dev_ptr(dev["grad"]),
+                                                    _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))
+            net._note_call(ws, (n, h, w), "train")
+            self._apply(dev, dev["grad"])
+        return loss[0]
+
+
+__all__ = ["FinalLayerTrainer"]
