@@ -395,6 +395,39 @@ int ssal_enet_train_final_nhwc(ssal_enet *net, const void *x_dev, int x_is_u8, i
                                const uint8_t *labels_dev, const float *mask_dev, const float *kernel_dev, float weight,
                                float label_smoothing, double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes,
                                void *stream);
+/* ---- The semi-supervised step and the training metrics (active_learning.py:226-275, 339-342) ----
+ * The same gradient with the batch's targets built inside the kernel: labelled_dev uint8 [n], 1 = image i is trained on
+ * the caller's labels_dev / mask_dev planes, 0 = on its own pseudo annotation (:229-275): pseudo_label = the first maximum
+ * of the pixel's Final logits, pseudo_mask = confidence < threshold ? 0 : 1 with the confidence of `measure`
+ * (SSAL_MEASURE_*), the arithmetic of ssal_enet_score_nhwc (a NaN confidence gives 1, as tf.math.less does).  The pseudo
+ * logits are those of features_raw_dev [n,h,w,16] (Bottleneck5_1 of the undistorted frame, :231) under kernel_dev, or of
+ * features_dev itself when features_raw_dev is NULL.  No gradient flows through the pseudo annotation (tf.stop_gradient,
+ * :233).  labelled_dev NULL = every image labelled.  The label / mask planes of an unlabelled image are never read, and
+ * labels_dev / mask_dev may be NULL when labelled_dev marks NO image as labelled -- which the library cannot verify: it is
+ * the caller's contract.
+ * Optional outputs (NULL to skip): confusion_dev int64 [classes][classes], the training-pass metrics of :339-342 --
+ * confusion[label][argmax of the TRAINING logits] += (int)mask over every pixel of the batch (the targets actually trained
+ * on; the matrix is accumulated, not overwritten, like ssal_enet_evaluate_nhwc_arith; the mask must satisfy 0 <= mask < 256
+ * and is truncated like tf.cast(mask, int32); a key >= classes^2 is dropped) -- and pseudo_pixels_dev int64 [n] = the
+ * count of pixels of image i whose pseudo mask is 1 (0 for a labelled image; overwritten).
+ * loss_dev / grad_dev hold exactly what ssal_final_grad_nhwc gives for the composed targets; integer counts, no float
+ * atomics: two calls give the same bits.  Statuses as ssal_final_grad_nhwc, plus SSAL_ENOTIMPL for an unknown measure and
+ * SSAL_ENOMEM for a short workspace. */
+int64_t ssal_final_grad_semi_workspace_bytes(int n, int h, int w, int classes);
+int ssal_final_grad_semi_nhwc(const float *features_dev, const float *features_raw_dev, int n, int h, int w, int classes,
+                              const float *kernel_dev, const uint8_t *labels_dev, const float *mask_dev,
+                              const uint8_t *labelled_dev, int measure, float threshold, float weight, float label_smoothing,
+                              double *loss_dev, float *grad_dev, int64_t *confusion_dev, int64_t *pseudo_pixels_dev,
+                              void *ws_dev, int64_t ws_bytes, void *stream);
+/* The same from images: the committed trunk up to Bottleneck5_1 on x_raw_dev first when it is given (its features stay in
+ * a second slot of the workspace: with_raw = 1 in the size query), then on x_dev, then the kernel.  x_raw_dev has the shape
+ * and element type of x_dev. */
+int64_t ssal_enet_train_final_semi_workspace_bytes(const ssal_enet *net, int n, int h, int w, int with_raw);
+int ssal_enet_train_final_semi_nhwc(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h,
+                                    int w, const uint8_t *labels_dev, const float *mask_dev, const uint8_t *labelled_dev,
+                                    int measure, float threshold, const float *kernel_dev, float weight,
+                                    float label_smoothing, double *loss_dev, float *grad_dev, int64_t *confusion_dev,
+                                    int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream);
 /* Keras l1_l2(l1, l2) regulariser gradient (2 l2 w + l1 sign(w), sign(0) = 0) and TF-1.13 ApplyAdam, in place on count
  * elements of var / m / v (fp32): alpha = lr sqrt(1 - beta2_power) / (1 - beta1_power); m += (g - m)(1 - beta1);
  * v += (g^2 - v)(1 - beta2); var -= (m alpha) / (sqrt(v) + eps).  sqrt and the divisions are correctly rounded.  The

@@ -175,6 +175,12 @@ PROTOTYPES = {
     "ssal_final_grad_nhwc": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _i64, _vp]),
     "ssal_enet_train_final_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
     "ssal_enet_train_final_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_final_grad_semi_workspace_bytes": (_i64, [_i, _i, _i, _i]),
+    "ssal_final_grad_semi_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _vp, _vp, _vp, _vp,
+                                       _vp, _i64, _vp]),
+    "ssal_enet_train_final_semi_workspace_bytes": (_i64, [_vp, _i, _i, _i, _i]),
+    "ssal_enet_train_final_semi_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _f, _f, _vp, _vp,
+                                             _vp, _vp, _vp, _i64, _vp]),
     "ssal_adam_apply": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _f, _f, _f, _vp]),
     # ---- measurement aids (include/ssal_enet.h) ----
     "ssal_profile_enable": (_i, [_i]),

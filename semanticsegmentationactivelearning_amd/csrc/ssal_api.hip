@@ -1787,6 +1787,120 @@ SSAL_API int ssal_enet_train_final_nhwc(ssal_enet *net, const void *x_dev, int x
     return SSAL_OK;
 }
 
+// ---- the semi-supervised form: the gradient's partials, then the confusion replicas ----
+static void final_grad_semi_carve(Bump &b, int h, int w, int classes, float **part, double **lpart, unsigned long long **rep)
+{
+    final_grad_carve(b, h, w, classes, part, lpart);
+    *rep = b.take<unsigned long long>((int64_t)ssal::kConfMaxReps * ssal::conf_rep_stride(classes * classes));
+}
+
+SSAL_API int64_t ssal_final_grad_semi_workspace_bytes(int n, int h, int w, int classes)
+{
+    if (classes < 2 || classes > 32 || n <= 0 || h <= 0 || w <= 0 || !final_grad_fits(h, w)) return -1;
+    Bump b(nullptr, 0);
+    float *part;
+    double *lpart;
+    unsigned long long *rep;
+    final_grad_semi_carve(b, h, w, classes, &part, &lpart, &rep);
+    return b.off + 256;
+}
+
+// the part both entries share: zero the replicas, the kernel, the fold into the caller's matrix
+static int final_grad_semi_run(const float *x, const float *x_raw, int n, int h, int w, int classes, const float *kernel_dev,
+                               const uint8_t *labels_dev, const float *mask_dev, const uint8_t *labelled_dev, int measure,
+                               float threshold, float weight, float label_smoothing, double *loss_dev, float *grad_dev,
+                               int64_t *confusion_dev, int64_t *pseudo_pixels_dev, float *part, double *lpart,
+                               unsigned long long *rep, hipStream_t s)
+{
+    const int reps = ssal::knobs().conf_reps;
+    if (confusion_dev) HIP_TRY(hipMemsetAsync(rep, 0, (size_t)reps * ssal::conf_rep_stride(classes * classes) * 8, s));
+    HIP_TRY(launch_final_grad_semi(x, x_raw, n, h, w, kernel_dev, classes, labels_dev, mask_dev, labelled_dev, measure,
+                                   threshold, weight, label_smoothing, part, lpart, loss_dev, grad_dev,
+                                   confusion_dev ? rep : nullptr, reps, pseudo_pixels_dev, s));
+    if (confusion_dev) HIP_TRY(launch_confusion_fold(rep, reps, classes, confusion_dev, s));
+    return SSAL_OK;
+}
+
+static int final_grad_semi_check(int measure, const void *labels_dev, const void *mask_dev, const void *labelled_dev)
+{
+    if (measure < 0 || measure > 2)
+        return fail(SSAL_ENOTIMPL, "Uncertainty function not implemented (measure=%d)", measure);
+    if (!labelled_dev && (!labels_dev || !mask_dev))
+        return fail(SSAL_EINVAL, "labels_dev / mask_dev may be NULL only when labelled_dev marks no image as labelled");
+    return SSAL_OK;
+}
+
+SSAL_API int ssal_final_grad_semi_nhwc(const float *features_dev, const float *features_raw_dev, int n, int h, int w,
+                                       int classes, const float *kernel_dev, const uint8_t *labels_dev,
+                                       const float *mask_dev, const uint8_t *labelled_dev, int measure, float threshold,
+                                       float weight, float label_smoothing, double *loss_dev, float *grad_dev,
+                                       int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes,
+                                       void *stream)
+{
+    if (int rc = final_grad_check(n, h, w, classes)) return rc;
+    if (int rc = final_grad_semi_check(measure, labels_dev, mask_dev, labelled_dev)) return rc;
+    if (!features_dev || !kernel_dev || !loss_dev || !grad_dev || !ws_dev) return fail(SSAL_EINVAL, "NULL device pointer");
+    const int64_t need = ssal_final_grad_semi_workspace_bytes(n, h, w, classes);
+    if (ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
+                                     (long long)ws_bytes);
+    Bump b(ws_dev, ws_bytes);
+    float *part;
+    double *lpart;
+    unsigned long long *rep;
+    final_grad_semi_carve(b, h, w, classes, &part, &lpart, &rep);
+    return final_grad_semi_run(features_dev, features_raw_dev, n, h, w, classes, kernel_dev, labels_dev, mask_dev,
+                               labelled_dev, measure, threshold, weight, label_smoothing, loss_dev, grad_dev, confusion_dev,
+                               pseudo_pixels_dev, part, lpart, rep, (hipStream_t)stream);
+}
+
+// forward workspace | gradient partials + confusion replicas | [with_raw: Bottleneck5_1 of x_raw, n * (h/2) * (w/2) * 16 floats]
+SSAL_API int64_t ssal_enet_train_final_semi_workspace_bytes(const ssal_enet *net, int n, int h, int w, int with_raw)
+{
+    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 8 || w % 8) return -1;
+    const int64_t g = ssal_final_grad_semi_workspace_bytes(n, h / 2, w / 2, net->classes);
+    if (g < 0) return -1;
+    const int64_t raw = with_raw ? (int64_t)n * (h / 2) * (w / 2) * 16 * 4 + 256 : 0;
+    return carve(net, nullptr, 0, n, h, w).bytes + 256 + g + raw;
+}
+
+SSAL_API int ssal_enet_train_final_semi_nhwc(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
+                                             int h, int w, const uint8_t *labels_dev, const float *mask_dev,
+                                             const uint8_t *labelled_dev, int measure, float threshold,
+                                             const float *kernel_dev, float weight, float label_smoothing, double *loss_dev,
+                                             float *grad_dev, int64_t *confusion_dev, int64_t *pseudo_pixels_dev,
+                                             void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    int rc = check_dims(net, n, h, w);
+    if (rc) return rc;
+    if ((rc = final_grad_check(n, h / 2, w / 2, net->classes))) return rc;
+    if ((rc = final_grad_semi_check(measure, labels_dev, mask_dev, labelled_dev))) return rc;
+    if (!x_dev || !kernel_dev || !loss_dev || !grad_dev || !ws_dev) return fail(SSAL_EINVAL, "NULL device pointer");
+    const int64_t need = ssal_enet_train_final_semi_workspace_bytes(net, n, h, w, x_raw_dev != nullptr);
+    if (ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
+                                     (long long)ws_bytes);
+    NetWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
+    char *gws = (char *)ws_dev + (W.bytes + 255) / 256 * 256;
+    Bump b(gws, ws_bytes - (gws - (char *)ws_dev));
+    float *part, *raw = nullptr;
+    double *lpart;
+    unsigned long long *rep;
+    final_grad_semi_carve(b, h / 2, w / 2, net->classes, &part, &lpart, &rep);
+    if (x_raw_dev) raw = b.take<float>((int64_t)n * (h / 2) * (w / 2) * 16);
+    if (!W.ok || !b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes", (long long)need);
+    hipStream_t s = (hipStream_t)stream;
+    // the trunk, training=False, on the undistorted frames first: Bottleneck5_1 (the one layer that writes a1) lands in
+    // the raw slot; then on the training frames (a1)
+    if (x_raw_dev) {
+        NetWorkspace R = W;
+        R.a1 = raw;
+        for (int li = 0; li < kNumLayers - 1; ++li) HIP_TRY(run_layer_idx(net, li, x_raw_dev, x_is_u8 != 0, R, n, h, w, s));
+    }
+    for (int li = 0; li < kNumLayers - 1; ++li) HIP_TRY(run_layer_idx(net, li, x_dev, x_is_u8 != 0, W, n, h, w, s));
+    return final_grad_semi_run(W.a1, raw, n, h / 2, w / 2, net->classes, kernel_dev, labels_dev, mask_dev, labelled_dev,
+                               measure, threshold, weight, label_smoothing, loss_dev, grad_dev, confusion_dev,
+                               pseudo_pixels_dev, part, lpart, rep, s);
+}
+
 SSAL_API int ssal_adam_apply(float *var_dev, float *m_dev, float *v_dev, const float *grad_dev, int64_t count, float lr,
                              float beta1, float beta2, float eps, float beta1_power, float beta2_power, float l1, float l2,
                              void *stream)

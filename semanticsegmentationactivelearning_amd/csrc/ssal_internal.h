@@ -107,6 +107,14 @@ int final_grad_workgroups(int H, int W);
 hipError_t launch_final_grad(const float *x, int N, int H, int W, const float *wk, int K, const uint8_t *labels,
                              const float *mask, float weight, float label_smoothing, float *part, double *lpart,
                              double *loss, float *grad, hipStream_t s);
+// the semi-supervised form: labelled [N] uint8 (0 = pseudo-annotate the image from the Final logits of
+// x_raw, or of x when x_raw is NULL; its label / mask planes are not read), rep = zeroed confusion replicas as for
+// launch_final_eval, pseudo_pixels int64 [N]; x_raw, labelled, rep and pseudo_pixels may each be NULL
+hipError_t launch_final_grad_semi(const float *x, const float *x_raw, int N, int H, int W, const float *wk, int K,
+                                  const uint8_t *labels, const float *mask, const uint8_t *labelled, int measure,
+                                  float threshold, float weight, float label_smoothing, float *part, double *lpart,
+                                  double *loss, float *grad, unsigned long long *rep, int reps, int64_t *pseudo_pixels,
+                                  hipStream_t s);
 hipError_t launch_adam(float *var, float *m, float *v, const float *grad, long count, float lr, float beta1, float beta2,
                        float eps, float beta1_power, float beta2_power, float l1, float l2, hipStream_t s);
 

@@ -7,6 +7,11 @@ masked softmax cross entropy and dL/dlogit and contracts them with the Bottlenec
 reach HBM), then the Keras ``l1_l2`` regulariser gradient and TF-1.13 ``ApplyAdam``.  The one deliberate difference from the
 reference: its ``train_op`` trains every layer with batch statistics; here the trunk is frozen and evaluated in inference
 mode.
+
+The semi-supervised step of the reference (active_learning.py:226-275, 339-342) is the same kernel with the targets built
+inside it: ``labelled`` marks, per image, whether the caller's annotation or the image's own pseudo annotation (argmax and
+``confidence >= threshold`` of the logits the kernel already holds) is trained on, ``confusion`` collects the training-pass
+confusion matrix and ``return_pseudo_pixels`` the count of pixels the threshold lets through.
 """
 import numpy as np
 
@@ -19,7 +24,7 @@ class FinalLayerTrainer:
     (``from_params``).  ``loginverse_scaling`` is the loss' ``weight`` (ENet class weighting when > 1)."""
 
     def __init__(self, net, learning_rate, beta1=0.9, beta2=0.999, epsilon=1e-8, l1=0.0, l2=0.0, loginverse_scaling=0.0,
-                 label_smoothing=0.0, learning_rate_decay=0.0, decay_steps=None):
+                 label_smoothing=0.0, learning_rate_decay=0.0, decay_steps=None, measure="entropy", threshold=0.0):
         from .models.enet.enet import ENet
         if not isinstance(net, ENet):
             raise NotImplementedError("output-layer training is implemented for ENet only (got %s)" % type(net).__name__)
@@ -35,6 +40,9 @@ class FinalLayerTrainer:
         self.label_smoothing = float(label_smoothing)
         self.learning_rate_decay = float(learning_rate_decay)
         self.decay_steps = decay_steps
+        if measure not in _lib.MEASURES:
+            raise NotImplementedError("Uncertainty function not implemented.")
+        self.measure, self.threshold = measure, float(threshold)  # defaults of the pseudo annotation's keywords
         self._dev = None  # device tensors: w, m, v, grad, loss
         self._t = 0
         self._b1p, self._b2p = np.float32(self.beta1), np.float32(self.beta2)  # AdamOptimizer's beta powers (fp32)
@@ -44,7 +52,8 @@ class FinalLayerTrainer:
     def from_params(cls, net, params, decay_steps=None):
         """The reference's JSON layout (conf/*.json): ``hyperparams.learning_rate``, ``.learning_rate_decay``,
         ``.optimizer.kwargs`` (beta1, beta2, epsilon), ``.weight_reg.{L1, L2}``, ``.softmax.{loginverse_scaling,
-        label_smoothing, multiscale}``.  ``params`` may be the whole file or its ``hyperparams`` section."""
+        label_smoothing, multiscale}``.  ``params`` may be the whole file or its ``hyperparams`` section; the whole file also
+        gives ``active_learning.{measure, threshold}``, the defaults of the pseudo annotation."""
         hp = params.get("hyperparams", params)
         sm = hp.get("softmax", {})
         if sm.get("multiscale", False):
@@ -54,11 +63,13 @@ class FinalLayerTrainer:
             raise NotImplementedError("optimizer %r: only Adam is implemented" % opt.get("type"))
         kw = dict(opt.get("kwargs", {}))
         reg = hp.get("weight_reg", {})
+        al = params.get("active_learning", {}) if "hyperparams" in params else {}
         return cls(net, learning_rate=hp["learning_rate"], beta1=kw.get("beta1", 0.9), beta2=kw.get("beta2", 0.999),
                    epsilon=kw.get("epsilon", 1e-8), l1=reg.get("L1", 0.0) or 0.0, l2=reg.get("L2", 0.0) or 0.0,
                    loginverse_scaling=sm.get("loginverse_scaling", 0.0) or 0.0,
                    label_smoothing=sm.get("label_smoothing", 0.0) or 0.0,
-                   learning_rate_decay=hp.get("learning_rate_decay", 0.0) or 0.0, decay_steps=decay_steps)
+                   learning_rate_decay=hp.get("learning_rate_decay", 0.0) or 0.0, decay_steps=decay_steps,
+                   measure=al.get("measure", "entropy"), threshold=al.get("threshold", 0.0))
 
     # ---- state -----------------------------------------------------------------------------------------------------
     def _kernel_var(self):
@@ -137,31 +148,100 @@ class FinalLayerTrainer:
         mk = mk.to(device=device, dtype=torch.float32).contiguous()
         return lab, mk
 
-    def gradient_features(self, features, labels, mask, kernel=None):
+    def _semi(self, n, labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels):
+        """the semi-supervised keywords, judged on the host before any device work: None when the call is today's plain
+        one (no ``labelled``, no ``confusion``, no pseudo-pixel request), else ``(labelled uint8 [n] host array or torch
+        tensor, or None; measure code; threshold)``"""
+        measure = self.measure if measure is None else measure
+        if measure not in _lib.MEASURES:
+            raise NotImplementedError("Uncertainty function not implemented.")
+        threshold = self.threshold if threshold is None else float(threshold)
+        if labelled is not None:
+            if tuple(np.shape(labelled)) != (n,):
+                raise ValueError("labelled must be a [N] vector (N = %d; got shape %s)" % (n, tuple(np.shape(labelled))))
+        if confusion is not None:
+            k = int(self.net.classes)
+            if tuple(np.shape(confusion)) != (k, k) or "int64" not in str(getattr(confusion, "dtype", "")):
+                raise ValueError("confusion must be an int64 [%d, %d] device tensor" % (k, k))
+        if labels is None or mask is None:
+            host = None if labelled is None else (labelled.cpu().numpy() if hasattr(labelled, "cpu") else np.asarray(labelled))
+            if host is None or host.astype(bool).any():
+                raise ValueError("labels / mask may be None only when labelled marks no image as labelled")
+        if labelled is None and confusion is None and not return_pseudo_pixels:
+            return None
+        return labelled, _lib.MEASURES[measure], threshold
+
+    def _semi_device(self, semi, n, device, labels, mask, shape):
+        """device forms of the semi-supervised arguments: labelled uint8 [n] (or None), label / mask planes (or None), the
+        pseudo-pixel counts"""
+        torch = _lib.require_gpu()
+        labelled = semi[0]
+        if labelled is not None:
+            t = labelled if isinstance(labelled, torch.Tensor) else torch.as_tensor(np.asarray(labelled))
+            labelled = (t != 0).to(device=device, dtype=torch.uint8).contiguous()
+        lab = mk = None
+        if labels is not None and mask is not None:
+            lab, mk = self._targets(labels, mask, shape, device)
+        return labelled, lab, mk
+
+    def gradient_features(self, features, labels, mask, kernel=None, labelled=None, measure=None, threshold=None,
+                          features_raw=None, confusion=None, return_pseudo_pixels=False):
         """(loss float64 [1], dL/dW [3, 3, K, 16] fp32) on the device for Bottleneck5_1 features [N, h, w, 16] and
-        labels / mask [N, 2h, 2w]; ``kernel`` defaults to ``net.Final.kernel``.  No update."""
+        labels / mask [N, 2h, 2w]; ``kernel`` defaults to ``net.Final.kernel``.  No update.
+
+        The semi-supervised step (active_learning.py:226-275, 339-342): ``labelled`` [N] (bool / uint8, numpy or torch) marks
+        the images trained on ``labels`` / ``mask``; the others are trained on their own pseudo annotation -- the argmax of
+        their Final logits under ``kernel`` and ``confidence >= threshold`` for ``measure`` (defaults: the trainer's, i.e.
+        "entropy" / 0.0 or ``from_params``' ``active_learning`` section) -- whose label / mask planes are never read
+        (``labels`` / ``mask`` may be None when no image is labelled).  ``features_raw`` [N, h, w, 16]: the features of the
+        undistorted frames, which the pseudo annotation is then computed from.  ``confusion`` (int64 [K, K] device tensor)
+        is added the training-pass confusion matrix of the targets trained on against the argmax of the training logits;
+        ``return_pseudo_pixels`` appends the int64 [N] count of pseudo-mask-1 pixels per image to the result."""
+        semi = self._semi(int(np.shape(features)[0]) if len(np.shape(features)) else 0, labels, mask, labelled, measure,
+                          threshold, confusion, return_pseudo_pixels)
         torch = _lib.require_gpu()
         x = _lib.as_device_f32(features)
         if x.dim() != 4 or x.shape[-1] != 16:
             raise ValueError("features must be [N,h,w,16] (got %s)" % (tuple(x.shape),))
         n, h, w, _ = x.shape
         k = self.net.classes
-        lab, mk = self._targets(labels, mask, (n, 2 * h, 2 * w), x.device)
         kern = _lib.as_device_f32(self._kernel_var().numpy() if kernel is None else kernel).to(x.device)
         if tuple(kern.shape) != (3, 3, k, 16):
             raise ValueError("kernel must be [3,3,%d,16] (got %s)" % (k, tuple(kern.shape)))
         L = _lib.lib()
+        if semi is None:
+            lab, mk = self._targets(labels, mask, (n, 2 * h, 2 * w), x.device)
+            with torch.cuda.device(x.device):
+                nbytes = L.ssal_final_grad_workspace_bytes(n, h, w, k)
+                if nbytes < 0:
+                    raise ValueError("feature map %dx%d is beyond the gradient kernel's limit" % (h, w))
+                ws = torch.empty(int(nbytes), dtype=torch.uint8, device=x.device)
+                loss = torch.empty((1,), dtype=torch.float64, device=x.device)
+                grad = torch.empty((3, 3, k, 16), dtype=torch.float32, device=x.device)
+                _lib.check(L.ssal_final_grad_nhwc(_lib.dev_ptr(x), n, h, w, k, _lib.dev_ptr(kern), _lib.dev_ptr(lab),
+                                                  _lib.dev_ptr(mk), self.weight, self.label_smoothing, _lib.dev_ptr(loss),
+                                                  _lib.dev_ptr(grad), _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))
+            return loss, grad
+        lbd, lab, mk = self._semi_device(semi, n, x.device, labels, mask, (n, 2 * h, 2 * w))
+        xr = None
+        if features_raw is not None and features_raw is not features:
+            xr = _lib.as_device_f32(features_raw).to(x.device)
+            if tuple(xr.shape) != tuple(x.shape):
+                raise ValueError("features_raw must have the shape of features %s (got %s)" % (tuple(x.shape), tuple(xr.shape)))
         with torch.cuda.device(x.device):
-            nbytes = L.ssal_final_grad_workspace_bytes(n, h, w, k)
+            nbytes = L.ssal_final_grad_semi_workspace_bytes(n, h, w, k)
             if nbytes < 0:
                 raise ValueError("feature map %dx%d is beyond the gradient kernel's limit" % (h, w))
             ws = torch.empty(int(nbytes), dtype=torch.uint8, device=x.device)
             loss = torch.empty((1,), dtype=torch.float64, device=x.device)
             grad = torch.empty((3, 3, k, 16), dtype=torch.float32, device=x.device)
-            _lib.check(L.ssal_final_grad_nhwc(_lib.dev_ptr(x), n, h, w, k, _lib.dev_ptr(kern), _lib.dev_ptr(lab),
-                                              _lib.dev_ptr(mk), self.weight, self.label_smoothing, _lib.dev_ptr(loss),
-                                              _lib.dev_ptr(grad), _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))
-        return loss, grad
+            pp = torch.empty((n,), dtype=torch.int64, device=x.device) if return_pseudo_pixels else None
+            _lib.check(L.ssal_final_grad_semi_nhwc(
+                _lib.dev_ptr(x), _lib.dev_ptr(xr), n, h, w, k, _lib.dev_ptr(kern), _lib.dev_ptr(lab), _lib.dev_ptr(mk),
+                _lib.dev_ptr(lbd), semi[1], semi[2], self.weight, self.label_smoothing, _lib.dev_ptr(loss),
+                _lib.dev_ptr(grad), _lib.dev_ptr(confusion, torch.int64, "confusion"), _lib.dev_ptr(pp), _lib.dev_ptr(ws),
+                ws.numel(), _lib.stream_ptr()))
+        return (loss, grad, pp) if return_pseudo_pixels else (loss, grad)
 
     def _trunk_handle(self):
         """the net's handle for the current device.  Only Final.kernel changes between steps, and this entry takes the
@@ -191,40 +271,84 @@ class FinalLayerTrainer:
         self.net.Final.kernel.assign(host)
         dev["version"] = self.net.Final.kernel.version
 
-    def step_features(self, features, labels, mask):
+    def step_features(self, features, labels, mask, labelled=None, measure=None, threshold=None, features_raw=None,
+                      confusion=None, return_pseudo_pixels=False):
         """one Adam step from cached Bottleneck5_1 features (``ENet.endpoint_outputs[0][1]``); returns the loss (float64
-        device scalar) of the kernel BEFORE the step, as ``sess.run([loss, train_op])`` does"""
+        device scalar) of the kernel BEFORE the step, as ``sess.run([loss, train_op])`` does.  The keywords are those of
+        ``gradient_features``; with ``return_pseudo_pixels`` the result is ``(loss, pseudo_pixels)``."""
+        semi = self._semi(int(np.shape(features)[0]) if len(np.shape(features)) else 0, labels, mask, labelled, measure,
+                          threshold, confusion, return_pseudo_pixels)
         x = _lib.as_device_f32(features)
         dev = self._device_state(x.device)
-        loss, grad = self.gradient_features(x, labels, mask, kernel=dev["w"])
-        self._apply(dev, grad)
-        return loss[0]
+        if semi is None:
+            loss, grad = self.gradient_features(x, labels, mask, kernel=dev["w"])
+            self._apply(dev, grad)
+            return loss[0]
+        out = self.gradient_features(x, labels, mask, kernel=dev["w"], labelled=labelled, measure=measure,
+                                     threshold=threshold, features_raw=features_raw, confusion=confusion,
+                                     return_pseudo_pixels=return_pseudo_pixels)
+        self._apply(dev, out[1])
+        return (out[0][0], out[2]) if return_pseudo_pixels else out[0][0]
 
-    def step(self, images, labels, mask):
+    def step(self, images, labels, mask, labelled=None, measure=None, threshold=None, images_raw=None, confusion=None,
+             return_pseudo_pixels=False):
         """one Adam step from images [N, H, W, C] (fp32 or decoded uint8) and labels / mask [N, H, W]: the frozen trunk
-        up to Bottleneck5_1, the fused gradient kernel, Adam.  Returns the loss (float64 device scalar) before the step."""
+        up to Bottleneck5_1, the fused gradient kernel, Adam.  Returns the loss (float64 device scalar) before the step.
+
+        ``labelled`` / ``measure`` / ``threshold`` / ``confusion`` / ``return_pseudo_pixels`` as in ``gradient_features``
+        (the result is then ``(loss, pseudo_pixels)``); ``images_raw``: the undistorted frames (``InputStage``'s ``image``
+        next to its ``image_dist``), same shape and dtype as ``images`` -- the trunk runs on them too and the pseudo
+        annotation comes from their logits, as the reference's ``pseudo_logits`` do (active_learning.py:231)."""
+        semi = self._semi(int(np.shape(images)[0]) if len(np.shape(images)) else 0, labels, mask, labelled, measure,
+                          threshold, confusion, return_pseudo_pixels)
         torch = _lib.require_gpu()
         net = self.net
         x = net._prepare(images, False)
         n, h, w, _ = x.shape
         k = net.classes
-        lab, mk = self._targets(labels, mask, (n, h, w), x.device)
         L = _lib.lib()
+        if semi is None:
+            lab, mk = self._targets(labels, mask, (n, h, w), x.device)
+            with torch.cuda.device(x.device):
+                dev = self._device_state(x.device)
+                handle = self._trunk_handle()
+                nbytes = L.ssal_enet_train_final_workspace_bytes(handle, n, h, w)
+                if nbytes < 0:
+                    raise ValueError("bad input dims %s" % (tuple(x.shape),))
+                ws = net._workspace(nbytes, x.device)
+                loss = torch.empty((1,), dtype=torch.float64, device=x.device)
+                _lib.check(L.ssal_enet_train_final_nhwc(handle, _lib.dev_ptr(x), int(x.dtype == torch.uint8), n, h, w,
+                                                        _lib.dev_ptr(lab), _lib.dev_ptr(mk), _lib.dev_ptr(dev["w"]), self.weight,
+                                                        self.label_smoothing, _lib.dev_ptr(loss), _lib.dev_ptr(dev["grad"]),
+                                                        _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))
+                net._note_call(ws, (n, h, w), "train")
+                self._apply(dev, dev["grad"])
+            return loss[0]
+        lbd, lab, mk = self._semi_device(semi, n, x.device, labels, mask, (n, h, w))
+        xr = None
+        if images_raw is not None and images_raw is not images:
+            xr = net._prepare(images_raw, False)
+            if tuple(xr.shape) != tuple(x.shape) or xr.dtype != x.dtype or xr.device != x.device:
+                raise ValueError("images_raw must have the shape and dtype of images %s %s (got %s %s)"
+                                 % (tuple(x.shape), x.dtype, tuple(xr.shape), xr.dtype))
         with torch.cuda.device(x.device):
             dev = self._device_state(x.device)
             handle = self._trunk_handle()
-            nbytes = L.ssal_enet_train_final_workspace_bytes(handle, n, h, w)
+            nbytes = L.ssal_enet_train_final_semi_workspace_bytes(handle, n, h, w, int(xr is not None))
             if nbytes < 0:
                 raise ValueError("bad input dims %s" % (tuple(x.shape),))
             ws = net._workspace(nbytes, x.device)
             loss = torch.empty((1,), dtype=torch.float64, device=x.device)
-            _lib.check(L.ssal_enet_train_final_nhwc(handle, _lib.dev_ptr(x), int(x.dtype == torch.uint8), n, h, w,
-                                                    _lib.dev_ptr(lab), _lib.dev_ptr(mk), _lib.dev_ptr(dev["w"]), self.weight,
-                                                    self.label_smoothing, _lib.dev_ptr(loss), _lib.dev_ptr(dev["grad"]),
-                                                    _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))
+            pp = torch.empty((n,), dtype=torch.int64, device=x.device) if return_pseudo_pixels else None
+            _lib.check(L.ssal_enet_train_final_semi_nhwc(
+                handle, _lib.dev_ptr(x), _lib.dev_ptr(xr), int(x.dtype == torch.uint8), n, h, w, _lib.dev_ptr(lab),
+                _lib.dev_ptr(mk), _lib.dev_ptr(lbd), semi[1], semi[2], _lib.dev_ptr(dev["w"]), self.weight,
+                self.label_smoothing, _lib.dev_ptr(loss), _lib.dev_ptr(dev["grad"]),
+                _lib.dev_ptr(confusion, torch.int64, "confusion"), _lib.dev_ptr(pp), _lib.dev_ptr(ws), ws.numel(),
+                _lib.stream_ptr()))
             net._note_call(ws, (n, h, w), "train")
             self._apply(dev, dev["grad"])
-        return loss[0]
+        return (loss[0], pp) if return_pseudo_pixels else loss[0]
 
 
 __all__ = ["FinalLayerTrainer"]
