@@ -436,6 +436,45 @@ int ssal_adam_apply(float *var_dev, float *m_dev, float *v_dev, const float *gra
                     float beta1, float beta2, float eps, float beta1_power, float beta2_power, float l1, float l2,
                     void *stream);
 
+/* ---- Last-block training: Bottleneck5_1 + Final (enet_modules.py:526-599, 1294-1381) ----
+ * The gradient of masked_softmax_cross_entropy through Final's transposed convolution and through Bottleneck5_1 in
+ * inference mode: the moving means / variances are constants, there is no dropout, batch-norm is the affine map
+ * y = gamma (x - mean) / sqrt(variance + 1e-3) + beta with gamma and beta trainable.  Everything below Bottleneck5_1 is
+ * frozen.  PReLU is relu(x) - alpha relu(-x); at x == 0 both derivatives are 0 (TensorFlow's ReluGrad).
+ *
+ * The 13 trained variables (Final.kernel and the 12 of Bottleneck5_1), the six moving statistics and Final.kernel travel in ONE packed fp32 block of
+ * ssal_train_block_param_floats(classes) = 400 + 144 classes floats (offsets in floats, C order inside each tensor):
+ *      0  proj_kernel [16][4]        64  proj_gamma [4]      68  proj_beta [4]      72  proj_alpha [4]
+ *     76  conv_kernel [3][3][4][4]  220  conv_gamma [4]     224  conv_beta [4]     228  conv_alpha [4]
+ *    232  exp_kernel [4][16]        296  exp_gamma [16]     312  exp_beta [16]     328  residual_alpha [16]
+ *    344  proj_mean [4]             348  proj_variance [4]  352  conv_mean [4]     356  conv_variance [4]
+ *    360  exp_mean [16]             376  exp_variance [16]  392  8 floats of padding
+ *    400  Final.kernel [3][3][classes][16] (TF HW-O-I)
+ * grad_dev has the same layout (0 in [344, 400)), so Adam's slots can too: ssal_adam_apply runs on sub-ranges of it.
+ *
+ * ssal_train_block_grad_nhwc: features_dev [n,h,w,16] fp32 = Bottleneck5_0's output, labels_dev uint8 / mask_dev fp32
+ * [n,2h,2w].  Writes loss_dev (one float64; the per-pixel terms are those of the forward op on ssal_enet_forward_nhwc's
+ * logits) and grad_dev.  The logits and their gradient never reach HBM; dL/d(Bottleneck5_1 output) [n,h,w,16] passes
+ * through the workspace once.  No float atomics: two calls give the same bits.  Limits and statuses as
+ * ssal_final_grad_nhwc (the workspace query returns -1 at the same boundaries). */
+int64_t ssal_train_block_param_floats(int classes);
+int64_t ssal_train_block_grad_workspace_bytes(int n, int h, int w, int classes);
+int ssal_train_block_grad_nhwc(const float *features_dev, int n, int h, int w, int classes, const float *params_dev,
+                               const uint8_t *labels_dev, const float *mask_dev, float weight, float label_smoothing,
+                               double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream);
+/* The same from images x_dev [n,h,w,c_in] (fp32, or uint8 with x_is_u8): the committed trunk's launchers up to
+ * Bottleneck5_0 on the caller's stream, then the training kernels on its output with params_dev (the handle's own
+ * Bottleneck5_1 / Final weights are not used); labels_dev / mask_dev [n,h,w]. */
+int64_t ssal_enet_train_block_workspace_bytes(const ssal_enet *net, int n, int h, int w);
+int ssal_enet_train_block_nhwc(ssal_enet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                               const uint8_t *labels_dev, const float *mask_dev, const float *params_dev, float weight,
+                               float label_smoothing, double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes,
+                               void *stream);
+/* Byte offset, into the workspace of ssal_enet_forward_nhwc / ssal_enet_score_nhwc / ssal_enet_train_block_nhwc, of
+ * Bottleneck5_0's output [n,h/2,w/2,16] (the features_dev of ssal_train_block_grad_nhwc); valid until the next call.
+ * -1 for dims the net does not take. */
+int64_t ssal_enet_train_block_features_offset(const ssal_enet *net, int n, int h, int w);
+
 #ifdef __cplusplus
 }
 #endif

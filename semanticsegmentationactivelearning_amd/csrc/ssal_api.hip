@@ -7,6 +7,7 @@
 #include "ssal_bottleneck_args.h"
 #include "ssal_bf16x3.h"
 #include "ssal_confusion.h"
+#include "ssal_train_block.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -1909,5 +1910,97 @@ SSAL_API int ssal_adam_apply(float *var_dev, float *m_dev, float *v_dev, const f
     if (count <= 0 || count > ((int64_t)1 << 36)) return fail(SSAL_EINVAL, "bad element count %lld", (long long)count);
     HIP_TRY(launch_adam(var_dev, m_dev, v_dev, grad_dev, count, lr, beta1, beta2, eps, beta1_power, beta2_power, l1, l2,
                         (hipStream_t)stream));
+    return SSAL_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Last-block training: Bottleneck5_1 + Final (include/ssal_enet.h, "Last-block training")
+// ------------------------------------------------------------------------------------------------
+static TrainBlockWs train_block_carve(Bump &b, int64_t n, int h, int w, int classes)
+{
+    const int64_t G = train_block_workgroups(h, w);
+    TrainBlockWs t;
+    t.fold = b.take<float>(TB_FINAL);
+    t.dy = b.take<float>(n * h * w * 16);
+    t.part_f = b.take<float>(G * 9 * classes * 16);
+    t.part_b = b.take<float>(G * TB_ROWS * TB_TRAINED);
+    t.lpart = b.take<double>(2 * G);
+    return t;
+}
+
+SSAL_API int64_t ssal_train_block_param_floats(int classes)
+{
+    if (classes < 2 || classes > 32) return -1;
+    return train_block_floats(classes);
+}
+
+SSAL_API int64_t ssal_train_block_grad_workspace_bytes(int n, int h, int w, int classes)
+{
+    if (classes < 2 || classes > 32 || n <= 0 || h <= 0 || w <= 0 || !train_block_fits(h, w)) return -1;
+    Bump b(nullptr, 0);
+    train_block_carve(b, n, h, w, classes);
+    return b.off + 256;
+}
+
+SSAL_API int ssal_train_block_grad_nhwc(const float *features_dev, int n, int h, int w, int classes, const float *params_dev,
+                                        const uint8_t *labels_dev, const float *mask_dev, float weight,
+                                        float label_smoothing, double *loss_dev, float *grad_dev, void *ws_dev,
+                                        int64_t ws_bytes, void *stream)
+{
+    if (int rc = final_grad_check(n, h, w, classes)) return rc;
+    if (!features_dev || !params_dev || !labels_dev || !mask_dev || !loss_dev || !grad_dev || !ws_dev)
+        return fail(SSAL_EINVAL, "NULL device pointer");
+    const int64_t need = ssal_train_block_grad_workspace_bytes(n, h, w, classes);
+    if (ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
+                                     (long long)ws_bytes);
+    Bump b(ws_dev, ws_bytes);
+    const TrainBlockWs t = train_block_carve(b, n, h, w, classes);
+    if (!b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes", (long long)need);
+    HIP_TRY(launch_train_block_grad(features_dev, n, h, w, classes, params_dev, labels_dev, mask_dev, weight,
+                                    label_smoothing, t, loss_dev, grad_dev, (hipStream_t)stream));
+    return SSAL_OK;
+}
+
+SSAL_API int64_t ssal_enet_train_block_workspace_bytes(const ssal_enet *net, int n, int h, int w)
+{
+    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 8 || w % 8) return -1;
+    const int64_t g = ssal_train_block_grad_workspace_bytes(n, h / 2, w / 2, net->classes);
+    if (g < 0) return -1;
+    return carve(net, nullptr, 0, n, h, w).bytes + 256 + g;
+}
+
+// byte offset (into the workspace passed to forward / score / train_block) of Bottleneck5_0's output [n,h/2,w/2,16],
+// the features ssal_train_block_grad_nhwc takes; valid until the next call.  -1 for dims the net does not take.
+SSAL_API int64_t ssal_enet_train_block_features_offset(const ssal_enet *net, int n, int h, int w)
+{
+    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 8 || w % 8) return -1;
+    NetWorkspace W = carve(net, (void *)256, ((int64_t)1 << 62), n, h, w);
+    return (const char *)W.a0 - (const char *)256;
+}
+
+SSAL_API int ssal_enet_train_block_nhwc(ssal_enet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                                        const uint8_t *labels_dev, const float *mask_dev, const float *params_dev,
+                                        float weight, float label_smoothing, double *loss_dev, float *grad_dev,
+                                        void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    int rc = check_dims(net, n, h, w);
+    if (rc) return rc;
+    if ((rc = final_grad_check(n, h / 2, w / 2, net->classes))) return rc;
+    if (!x_dev || !labels_dev || !mask_dev || !params_dev || !loss_dev || !grad_dev || !ws_dev)
+        return fail(SSAL_EINVAL, "NULL device pointer");
+    const int64_t need = ssal_enet_train_block_workspace_bytes(net, n, h, w);
+    if (ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
+                                     (long long)ws_bytes);
+    NetWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
+    char *gws = (char *)ws_dev + (W.bytes + 255) / 256 * 256;
+    Bump b(gws, ws_bytes - (gws - (char *)ws_dev));
+    const TrainBlockWs t = train_block_carve(b, n, h / 2, w / 2, net->classes);
+    if (!W.ok || !b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes", (long long)need);
+    hipStream_t s = (hipStream_t)stream;
+    // the frozen trunk, training=False: Initial .. Bottleneck5_0 on the caller's stream (its output lands in W.a0);
+    // Bottleneck5_1 is evaluated inside the training kernels from params_dev, not from the handle's committed weights
+    for (int li = 0; li < kNumLayers - 2; ++li) HIP_TRY(run_layer_idx(net, li, x_dev, x_is_u8 != 0, W, n, h, w, s));
+    HIP_TRY(launch_train_block_grad(W.a0, n, h / 2, w / 2, net->classes, params_dev, labels_dev, mask_dev, weight,
+                                    label_smoothing, t, loss_dev, grad_dev, s));
     return SSAL_OK;
 }

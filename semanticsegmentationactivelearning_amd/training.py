@@ -351,4 +351,281 @@ class FinalLayerTrainer:
         return (loss[0], pp) if return_pseudo_pixels else loss[0]
 
 
-__all__ = ["FinalLayerTrainer"]
+# ---- the last block: Bottleneck5_1 + Final ---------------------------------------------------------
+# the packed block of include/ssal_enet.h ("Last-block training"): (variable, layer attribute, float offset, regularised)
+_BLOCK = "Bottleneck5_1"
+_BLOCK_LAYOUT = (
+    ("proj_kernel", 0, True), ("proj_gamma", 64, False), ("proj_beta", 68, False), ("proj_alpha", 72, True),
+    ("conv_kernel", 76, True), ("conv_gamma", 220, False), ("conv_beta", 224, False), ("conv_alpha", 228, True),
+    ("exp_kernel", 232, True), ("exp_gamma", 296, False), ("exp_beta", 312, False), ("residual_alpha", 328, True),
+)
+_BLOCK_STATS = (("proj_mean", 344), ("proj_variance", 348), ("conv_mean", 352), ("conv_variance", 356),
+                ("exp_mean", 360), ("exp_variance", 376))
+_FINAL_OFFSET = 400
+# Adam runs on these float ranges of the packed block; True = with the l1_l2 regulariser gradient
+_ADAM_RANGES = ((0, 64, True), (64, 72, False), (72, 220, True), (220, 228, False), (228, 296, True), (296, 328, False),
+                (328, 344, True))
+
+
+class LastBlockTrainer(FinalLayerTrainer):
+    """Adam on the 13 variables of ENet's last block: ``Final.kernel`` and ``Bottleneck5_1``'s ``proj_kernel``,
+    ``proj_gamma``, ``proj_beta``, ``proj_alpha``, ``conv_kernel``, ``conv_gamma``, ``conv_beta``, ``conv_alpha``,
+    ``exp_kernel``, ``exp_gamma``, ``exp_beta`` and ``residual_alpha``: the first backward pass through a bottleneck.
+
+    The one deliberate difference from the reference carries over from ``FinalLayerTrainer``: its ``train_op`` trains every
+    layer with batch statistics and dropout.  Here everything below Bottleneck5_1 is frozen and runs with
+    ``training=False``, and Bottleneck5_1 itself is trained in INFERENCE mode: its moving means and variances are constants
+    (the ``*_mean`` / ``*_variance`` variables are never written), there is no spatial dropout, and batch-norm is the affine
+    map ``y = gamma (x - mean) / sqrt(var + 1e-3) + beta`` with ``gamma`` and ``beta`` trainable.
+
+    Regulariser: the Keras ``l1_l2`` gradient goes to exactly the variables the reference attaches ``kernel_regularizer``
+    to: ``proj_kernel`` (enet_modules.py:366-373), ``proj_alpha`` (:375-382), ``conv_kernel`` (:433-440), ``conv_alpha``
+    (:442-449), ``exp_kernel`` (:477-484), ``residual_alpha`` (:516-523) and ``Final.kernel`` (the ``Final`` layer's only
+    weight).  The batch-norm ``gamma`` / ``beta`` (:398-411, :463-474, :500-513) carry none and get the plain Adam update.
+    ``weight_reg.glorot_scaling`` (``regularization_scaling``, :350-362) is not implemented.
+
+    PReLU is ``relu(x) - alpha relu(-x)`` (extra_ops.py:9-26); at an input of exactly 0 both derivatives are 0, as
+    TensorFlow's ``ReluGrad`` gives them.
+
+    ``state`` / ``load_state``: ``{"m": {name: array}, "v": {name: array}, "t": steps}`` keyed by variable name
+    (``"Final.kernel"``, ``"Bottleneck5_1.proj_kernel"``, ...)."""
+
+    def __init__(self, net, *args, **kwargs):
+        super().__init__(net, *args, **kwargs)
+        self._m0 = self._v0 = None  # packed host copies waiting for the device
+
+    @classmethod
+    def from_params(cls, net, params, decay_steps=None):
+        hp = params.get("hyperparams", params)
+        if (hp.get("weight_reg", {}) or {}).get("glorot_scaling", False):
+            raise NotImplementedError("weight_reg.glorot_scaling: the per-kernel regulariser scaling is not implemented")
+        return super().from_params(net, params, decay_steps=decay_steps)
+
+    # ---- the packed block ------------------------------------------------------------------------------------------------
+    def _named(self):
+        """[(name, Variable, float offset, regularised)] of the 13 trained variables, Final.kernel first"""
+        if not self.net.built:
+            raise RuntimeError("build the model (call it once, or .build(input_shape)) before training")
+        blk = getattr(self.net, _BLOCK)
+        return [("Final.kernel", self.net.Final.kernel, _FINAL_OFFSET, True)] + [
+            ("%s.%s" % (_BLOCK, a), getattr(blk, a), off, reg) for a, off, reg in _BLOCK_LAYOUT]
+
+    @property
+    def variable_names(self):
+        return [n for n, _, _, _ in self._named()]
+
+    def _floats(self):
+        return _FINAL_OFFSET + 144 * int(self.net.classes)
+
+    def _pack(self, arrays=None):
+        """the packed block from the host variables (``arrays`` None; the statistics included) or from a name -> array
+        mapping (statistics and padding 0)"""
+        out = np.zeros(self._floats(), np.float32)
+        for name, var, off, _ in self._named():
+            a = var.numpy() if arrays is None else np.ascontiguousarray(arrays[name], dtype=np.float32)
+            if a.shape != var.shape:
+                raise ValueError("%s must have shape %s (got %s)" % (name, var.shape, a.shape))
+            out[off:off + a.size] = a.reshape(-1)
+        if arrays is None:
+            blk = getattr(self.net, _BLOCK)
+            for a, off in _BLOCK_STATS:
+                v = getattr(blk, a).numpy()
+                out[off:off + v.size] = v
+        return out
+
+    def _unpack(self, packed):
+        return {name: np.array(packed[off:off + int(np.prod(var.shape))]).reshape(var.shape)
+                for name, var, off, _ in self._named()}
+
+    def _versions(self):
+        blk = getattr(self.net, _BLOCK)
+        return tuple(v.version for v in [self.net.Final.kernel] + list(blk.variables))
+
+    # ---- state -----------------------------------------------------------------------------------------------------------
+    def reinitialize(self, seed=None):
+        """re-draws ``Final.kernel`` only (as ``FinalLayerTrainer.reinitialize``) and resets all optimiser state"""
+        var = self._kernel_var()
+        var.assign(_mod.glorot_uniform(seed)(var.shape))
+        zeros = {n: np.zeros(v.shape, np.float32) for n, v, _, _ in self._named()}
+        self.load_state({"m": zeros, "v": dict(zeros), "t": 0})
+
+    @property
+    def state(self):
+        if self._dev is None:
+            zero = np.zeros(self._floats(), np.float32)
+            m = self._m0 if self._m0 is not None else zero
+            v = self._v0 if self._v0 is not None else zero
+        else:
+            m, v = self._dev["m"].cpu().numpy(), self._dev["v"].cpu().numpy()
+        return {"m": self._unpack(m), "v": self._unpack(v), "t": self._t}
+
+    def load_state(self, state):
+        names = set(self.variable_names)
+        for key in ("m", "v"):
+            if not isinstance(state[key], dict) or set(state[key]) != names:
+                raise ValueError("state[%r] must map exactly the 13 variable names to arrays" % key)
+        m, v = self._pack(state["m"]), self._pack(state["v"])
+        self._t = int(state["t"])
+        self._b1p = np.float32(1.0)
+        self._b2p = np.float32(1.0)
+        for _ in range(self._t + 1):
+            self._b1p = np.float32(self._b1p * np.float32(self.beta1))
+            self._b2p = np.float32(self._b2p * np.float32(self.beta2))
+        self._m0, self._v0 = m, v
+        self._dev = None
+
+    def _device_state(self, device):
+        torch = _lib.require_gpu()
+        ver = self._versions()
+        if self._dev is None or self._dev["w"].device != device or self._dev["version"] != ver:
+            zero = np.zeros(self._floats(), np.float32)
+            m = self._m0 if self._m0 is not None else (self._dev["m"].cpu().numpy() if self._dev else zero)
+            v = self._v0 if self._v0 is not None else (self._dev["v"].cpu().numpy() if self._dev else zero)
+            self._dev = {
+                "w": torch.from_numpy(self._pack()).to(device),
+                "m": torch.from_numpy(np.array(m)).to(device),
+                "v": torch.from_numpy(np.array(v)).to(device),
+                "grad": torch.empty(self._floats(), dtype=torch.float32, device=device),
+                "version": ver,
+            }
+            self._m0 = self._v0 = None
+        return self._dev
+
+    # ---- gradients -------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _no_semi(**kw):
+        for name, value in kw.items():
+            if value is not None and value is not False:
+                raise NotImplementedError("%s: the semi-supervised step is implemented for the output layer only "
+                                          "(FinalLayerTrainer)" % name)
+
+    def _grad_dict(self, grad):
+        return {name: grad[off:off + int(np.prod(var.shape))].view(var.shape) for name, var, off, _ in self._named()}
+
+    def _grad_packed(self, x, labels, mask, params_dev):
+        torch = _lib.require_gpu()
+        if x.dim() != 4 or x.shape[-1] != 16:
+            raise ValueError("features must be [N,h,w,16] (got %s)" % (tuple(x.shape),))
+        n, h, w, _ = x.shape
+        k = int(self.net.classes)
+        lab, mk = self._targets(labels, mask, (n, 2 * h, 2 * w), x.device)
+        L = _lib.lib()
+        with torch.cuda.device(x.device):
+            nbytes = L.ssal_train_block_grad_workspace_bytes(n, h, w, k)
+            if nbytes < 0:
+                raise ValueError("feature map %dx%d is beyond the gradient kernel's limit" % (h, w))
+            ws = torch.empty(int(nbytes), dtype=torch.uint8, device=x.device)
+            loss = torch.empty((1,), dtype=torch.float64, device=x.device)
+            grad = torch.empty(self._floats(), dtype=torch.float32, device=x.device)
+            _lib.check(L.ssal_train_block_grad_nhwc(_lib.dev_ptr(x), n, h, w, k, _lib.dev_ptr(params_dev), _lib.dev_ptr(lab),
+                                                    _lib.dev_ptr(mk), self.weight, self.label_smoothing, _lib.dev_ptr(loss),
+                                                    _lib.dev_ptr(grad), _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))
+        return loss, grad
+
+    def gradient_features(self, features5_0, labels, mask, params=None, **semi):
+        """(loss float64 [1], {name: gradient}) on the device for Bottleneck5_0's output [N, h, w, 16] and labels / mask
+        [N, 2h, 2w].  ``params``: a name -> array mapping that overrides any of the 13 variables (the others, and the
+        moving statistics, are the model's).  No update.  The packed gradient is 0 in the statistics and padding slots."""
+        self._no_semi(**semi)
+        x = _lib.as_device_f32(features5_0)
+        params = dict(params or {})
+        unknown = set(params) - set(self.variable_names)
+        if unknown:
+            raise ValueError("unknown variables %s (the moving statistics always come from the model)" % sorted(unknown))
+        packed = self._pack()
+        for name, var, off, _ in self._named():
+            if name in params:
+                a = params[name]
+                a = np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a, dtype=np.float32)
+                if a.shape != var.shape:
+                    raise ValueError("%s must have shape %s (got %s)" % (name, var.shape, a.shape))
+                packed[off:off + a.size] = a.reshape(-1)
+        torch = _lib.require_gpu()
+        loss, grad = self._grad_packed(x, labels, mask, torch.from_numpy(packed).to(x.device))
+        return loss, self._grad_dict(grad)
+
+    def features(self, images):
+        """Bottleneck5_0's output [N, H/2, W/2, 16] for ``images`` (a copy): what ``step_features`` and
+        ``gradient_features`` take.  One forward pass of the frozen trunk; the frozen layers never change, so the result
+        can be cached across steps."""
+        net = self.net
+        x = net._prepare(images, False)
+        n, h, w, _ = x.shape
+        net(x, training=False)
+        off = _lib.lib().ssal_enet_train_block_features_offset(net._handle, n, h, w)
+        if off < 0:
+            raise ValueError("bad input dims %s" % (tuple(x.shape),))
+        torch = _lib.require_gpu()
+        shape = (n, h // 2, w // 2, 16)
+        return net._ws[off:off + 4 * n * (h // 2) * (w // 2) * 16].view(torch.float32).view(shape).clone()
+
+    def _trunk_handle(self):
+        """the net's handle for the current device: reused while every variable BELOW Bottleneck5_1 is unchanged (the
+        training kernels take the 13 variables and the block's statistics from the packed device block).  The handle's
+        pushed-versions record keeps the old versions, so the next score / evaluate / call pushes the new weights once."""
+        torch = _lib.require_gpu()
+        net = self.net
+        ent = net._handles.get(torch.cuda.current_device())
+        tail = len(getattr(net, _BLOCK).variables) + 1
+        if ent is not None and ent[1] is not None:
+            if tuple(v.version for v in net.variables)[:-tail] == ent[1][:-tail]:
+                return ent[0]
+        return net._sync_handle()
+
+    def _apply(self, dev, grad):
+        lr = self.current_learning_rate()
+        L = _lib.lib()
+        torch = _lib.require_gpu()
+        w, m, v = dev["w"], dev["m"], dev["v"]
+        for lo, hi, reg in _ADAM_RANGES + ((_FINAL_OFFSET, self._floats(), True),):
+            _lib.check(L.ssal_adam_apply(_lib.dev_ptr(w[lo:hi]), _lib.dev_ptr(m[lo:hi]), _lib.dev_ptr(v[lo:hi]),
+                                         _lib.dev_ptr(grad[lo:hi]), hi - lo, float(lr), self.beta1, self.beta2, self.epsilon,
+                                         float(self._b1p), float(self._b2p), self.l1 if reg else 0.0,
+                                         self.l2 if reg else 0.0, _lib.stream_ptr()))
+        self._t += 1
+        self._b1p = np.float32(self._b1p * np.float32(self.beta1))
+        self._b2p = np.float32(self._b2p * np.float32(self.beta2))
+        # the host variables are the weights of record (12.5 KB at K = 19; synchronises the stream)
+        host = w.cpu().numpy()
+        for name, var, off, _ in self._named():
+            var.assign(host[off:off + int(np.prod(var.shape))].reshape(var.shape))
+        dev["version"] = self._versions()
+
+    def step_features(self, features5_0, labels, mask, **semi):
+        """one Adam step from cached Bottleneck5_0 features [N, h, w, 16]; returns the loss (float64 device scalar) BEFORE
+        the step, as ``sess.run([loss, train_op])`` does"""
+        self._no_semi(**semi)
+        x = _lib.as_device_f32(features5_0)
+        dev = self._device_state(x.device)
+        loss, grad = self._grad_packed(x, labels, mask, dev["w"])
+        self._apply(dev, grad)
+        return loss[0]
+
+    def step(self, images, labels, mask, **semi):
+        """one Adam step from images [N, H, W, C] (fp32 or decoded uint8) and labels / mask [N, H, W]: the frozen trunk up
+        to Bottleneck5_0, the training kernels, Adam.  Returns the loss (float64 device scalar) before the step."""
+        self._no_semi(**semi)
+        torch = _lib.require_gpu()
+        net = self.net
+        x = net._prepare(images, False)
+        n, h, w, _ = x.shape
+        L = _lib.lib()
+        lab, mk = self._targets(labels, mask, (n, h, w), x.device)
+        with torch.cuda.device(x.device):
+            dev = self._device_state(x.device)
+            handle = self._trunk_handle()
+            nbytes = L.ssal_enet_train_block_workspace_bytes(handle, n, h, w)
+            if nbytes < 0:
+                raise ValueError("bad input dims %s" % (tuple(x.shape),))
+            ws = net._workspace(nbytes, x.device)
+            loss = torch.empty((1,), dtype=torch.float64, device=x.device)
+            _lib.check(L.ssal_enet_train_block_nhwc(handle, _lib.dev_ptr(x), int(x.dtype == torch.uint8), n, h, w,
+                                                    _lib.dev_ptr(lab), _lib.dev_ptr(mk), _lib.dev_ptr(dev["w"]), self.weight,
+                                                    self.label_smoothing, _lib.dev_ptr(loss), _lib.dev_ptr(dev["grad"]),
+                                                    _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))
+            net._note_call(ws, (n, h, w), "train")
+            self._apply(dev, dev["grad"])
+        return loss[0]
+
+
+__all__ = ["FinalLayerTrainer", "LastBlockTrainer"]
