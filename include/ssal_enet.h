@@ -475,6 +475,54 @@ int ssal_enet_train_block_nhwc(ssal_enet *net, const void *x_dev, int x_is_u8, i
  * -1 for dims the net does not take. */
 int64_t ssal_enet_train_block_features_offset(const ssal_enet *net, int n, int h, int w);
 
+/* ---- Last-stage training: Bottleneck5_0 + Bottleneck5_1 + Final (enet_modules.py:940-1292) ----
+ * The same gradient one block further down: through Bottleneck5_0, the last upsampling stage (1x1 projection 64 -> 16, 3x3
+ * stride-2 transposed convolution 16 -> 8, 1x1 expansion 8 -> 16, 1x1 residual convolution 64 -> 16 + max-unpool), in
+ * inference mode as above.  Everything below Bottleneck5_0 is frozen; no gradient is produced for its input.  The unpool's
+ * backward is the gather of the gradient at the position each pooling index names.
+ *
+ * The 26 trained variables and the 12 moving statistics travel in ONE packed fp32 block of
+ * ssal_train_stage_param_floats(classes) = ssal_train_block_param_floats(classes) + 3536 floats: the last-block block above,
+ * unchanged, then Bottleneck5_0's part at float offset S = 400 + 144 classes (offsets from S, C order inside each tensor):
+ *      0  proj_kernel [64][16]     1024  proj_gamma [16]    1040  proj_beta [16]    1056  proj_alpha [16]
+ *   1072  conv_kernel [3][3][8][16] (TF HW-O-I)             2224  conv_gamma [8]    2232  conv_beta [8]    2240  conv_alpha [8]
+ *   2248  exp_kernel [8][16]       2376  exp_gamma [16]     2392  exp_beta [16]
+ *   2408  res_kernel [64][16]      3432  residual_alpha [16]
+ *   3448  proj_mean [16]           3464  proj_variance [16] 3480  conv_mean [8]     3488  conv_variance [8]
+ *   3496  exp_mean [16]            3512  exp_variance [16]  3528  8 floats of padding
+ * grad_dev has the same layout (0 in the statistics and padding), so Adam's slots can too.
+ *
+ * ssal_train_stage_grad_nhwc: features_dev [n,h,w,64] fp32 = Bottleneck4_2's output; argmax_dev int64 [n,h,w,16] = the
+ * pooling indices of Bottleneck1_0 in the reference's per-image form (y * 2w + x) * 16 + c, converted to window codes on the
+ * device (an index outside its own 2x2 window and channel is taken as the window's first position: callers validate);
+ * labels_dev uint8 / mask_dev fp32 [n,4h,4w].  Bottleneck5_0's output is computed by the forward path's own kernel from
+ * weights folded on the device as ssal_enet_commit folds them, so loss_dev is the forward op's value on
+ * ssal_enet_forward_nhwc's logits.  max_workgroups: 0 = the default, min(16x16 tiles of the [2h,2w] map, 1024); a smaller
+ * positive value lowers the workgroup count of every gradient kernel (a tuning knob; the summation order, not the
+ * semantics, depends on it).  No float atomics: two calls give the same bits.  The workspace query returns -1, and the
+ * call SSAL_EINVAL, for classes outside [2,32] and beyond the limits of ssal_final_grad_nhwc on [2h,2w] and of the fused
+ * Bottleneck5_0 kernel (64 h w < 2^31). */
+int64_t ssal_train_stage_param_floats(int classes);
+int64_t ssal_train_stage_grad_workspace_bytes(int n, int h, int w, int classes);
+int ssal_train_stage_grad_nhwc(const float *features_dev, const int64_t *argmax_dev, int n, int h, int w, int classes,
+                               const float *params_dev, const uint8_t *labels_dev, const float *mask_dev, float weight,
+                               float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev, void *ws_dev,
+                               int64_t ws_bytes, void *stream);
+/* The same from images x_dev [n,h,w,c_in] (fp32, or uint8 with x_is_u8): the committed trunk's launchers up to
+ * Bottleneck4_2 on the caller's stream, then the stage with params_dev (the handle's own Bottleneck5_0 / Bottleneck5_1 /
+ * Final weights are not used) and the window codes the trunk's pooling left; labels_dev / mask_dev [n,h,w]. */
+int64_t ssal_enet_train_stage_workspace_bytes(const ssal_enet *net, int n, int h, int w);
+int ssal_enet_train_stage_nhwc(ssal_enet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                               const uint8_t *labels_dev, const float *mask_dev, const float *params_dev, float weight,
+                               float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev, void *ws_dev,
+                               int64_t ws_bytes, void *stream);
+/* Byte offsets, into the workspace of ssal_enet_forward_nhwc / ssal_enet_score_nhwc / ssal_enet_train_stage_nhwc, of
+ * Bottleneck4_2's output [n,h/4,w/4,64] (the features_dev of ssal_train_stage_grad_nhwc) and of the 1-byte window codes
+ * [n,h/4,w/4,16] of Bottleneck1_0's pooling (ssal_enet_export_argmax(which = 1) turns them into argmax_dev); valid until the
+ * next call.  -1 for dims the net does not take. */
+int64_t ssal_enet_train_stage_features_offset(const ssal_enet *net, int n, int h, int w);
+int64_t ssal_enet_train_stage_code_offset(const ssal_enet *net, int n, int h, int w);
+
 #ifdef __cplusplus
 }
 #endif

@@ -188,6 +188,13 @@ PROTOTYPES = {
     "ssal_enet_train_block_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
     "ssal_enet_train_block_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _i64, _vp]),
     "ssal_enet_train_block_features_offset": (_i64, [_vp, _i, _i, _i]),
+    "ssal_train_stage_param_floats": (_i64, [_i]),
+    "ssal_train_stage_grad_workspace_bytes": (_i64, [_i, _i, _i, _i]),
+    "ssal_train_stage_grad_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_enet_train_stage_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
+    "ssal_enet_train_stage_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_enet_train_stage_features_offset": (_i64, [_vp, _i, _i, _i]),
+    "ssal_enet_train_stage_code_offset": (_i64, [_vp, _i, _i, _i]),
     # ---- measurement aids (include/ssal_enet.h) ----
     "ssal_profile_enable": (_i, [_i]),
     "ssal_profile_collect": (_i, [_c.c_char_p, _i64]),

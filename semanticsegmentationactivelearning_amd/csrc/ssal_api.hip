@@ -8,6 +8,7 @@
 #include "ssal_bf16x3.h"
 #include "ssal_confusion.h"
 #include "ssal_train_block.h"
+#include "ssal_train_stage.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -2002,5 +2003,119 @@ SSAL_API int ssal_enet_train_block_nhwc(ssal_enet *net, const void *x_dev, int x
     for (int li = 0; li < kNumLayers - 2; ++li) HIP_TRY(run_layer_idx(net, li, x_dev, x_is_u8 != 0, W, n, h, w, s));
     HIP_TRY(launch_train_block_grad(W.a0, n, h / 2, w / 2, net->classes, params_dev, labels_dev, mask_dev, weight,
                                     label_smoothing, t, loss_dev, grad_dev, s));
+    return SSAL_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Last-stage training: Bottleneck5_0 + Bottleneck5_1 + Final (include/ssal_enet.h, "Last-stage training")
+// ------------------------------------------------------------------------------------------------
+// h, w = the dims of Bottleneck4_2's output; own = the call brings no a5_0 / window-code buffers of its own
+static TrainStageWs train_stage_carve(Bump &b, int64_t n, int h, int w, int classes, bool own)
+{
+    TrainStageWs t;
+    t.tb = train_block_carve(b, n, 2 * h, 2 * w, classes);
+    t.dx = b.take<float>(n * 4 * h * w * 16);
+    t.sfold = b.take<float>(TF_FLOATS);
+    t.part_s = b.take<float>((int64_t)train_stage_workgroups(h, w, 0) * TS_TRAINED);
+    t.bad = b.take<int>(1);
+    t.a5 = own ? b.take<float>(n * 4 * h * w * 16) : nullptr;
+    t.code = own ? b.take<uint8_t>(n * h * w * 16) : nullptr;
+    return t;
+}
+
+static int train_stage_check(int n, int h, int w, int classes, int max_workgroups)
+{
+    if (classes < 2 || classes > 32) return fail(SSAL_EINVAL, "classes must be in [2,32] (got %d)", classes);
+    if (n <= 0 || h <= 0 || w <= 0) return fail(SSAL_EINVAL, "bad dims n=%d h=%d w=%d", n, h, w);
+    if (max_workgroups < 0) return fail(SSAL_EINVAL, "max_workgroups must be >= 0 (got %d)", max_workgroups);
+    if (!train_stage_fits(h, w))
+        return fail(SSAL_EINVAL, "feature map %dx%d is beyond the last-stage gradient kernels' limit", h, w);
+    return SSAL_OK;
+}
+
+SSAL_API int64_t ssal_train_stage_param_floats(int classes)
+{
+    if (classes < 2 || classes > 32) return -1;
+    return train_stage_floats(classes);
+}
+
+SSAL_API int64_t ssal_train_stage_grad_workspace_bytes(int n, int h, int w, int classes)
+{
+    if (classes < 2 || classes > 32 || n <= 0 || h <= 0 || w <= 0 || !train_stage_fits(h, w)) return -1;
+    Bump b(nullptr, 0);
+    train_stage_carve(b, n, h, w, classes, true);
+    return b.off + 256;
+}
+
+SSAL_API int ssal_train_stage_grad_nhwc(const float *features_dev, const int64_t *argmax_dev, int n, int h, int w, int classes,
+                                        const float *params_dev, const uint8_t *labels_dev, const float *mask_dev, float weight,
+                                        float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev,
+                                        void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    if (int rc = train_stage_check(n, h, w, classes, max_workgroups)) return rc;
+    if (!features_dev || !argmax_dev || !params_dev || !labels_dev || !mask_dev || !loss_dev || !grad_dev || !ws_dev)
+        return fail(SSAL_EINVAL, "NULL device pointer");
+    const int64_t need = ssal_train_stage_grad_workspace_bytes(n, h, w, classes);
+    if (ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
+                                     (long long)ws_bytes);
+    Bump b(ws_dev, ws_bytes);
+    const TrainStageWs t = train_stage_carve(b, n, h, w, classes, true);
+    if (!b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes", (long long)need);
+    HIP_TRY(launch_train_stage_grad(features_dev, argmax_dev, n, h, w, classes, params_dev, labels_dev, mask_dev, weight,
+                                    label_smoothing, max_workgroups, t, loss_dev, grad_dev, (hipStream_t)stream));
+    return SSAL_OK;
+}
+
+SSAL_API int64_t ssal_enet_train_stage_workspace_bytes(const ssal_enet *net, int n, int h, int w)
+{
+    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 8 || w % 8) return -1;
+    if (net->classes < 2 || net->classes > 32 || !train_stage_fits(h / 4, w / 4)) return -1;
+    Bump b(nullptr, 0);
+    train_stage_carve(b, n, h / 4, w / 4, net->classes, false);
+    return carve(net, nullptr, 0, n, h, w).bytes + 256 + b.off + 256;
+}
+
+// byte offsets (into the workspace passed to forward / score / train_stage) of Bottleneck4_2's output [n,h/4,w/4,64] and of
+// the window codes [n,h/4,w/4,16] of Bottleneck1_0's pooling; valid until the next call.  -1 for dims the net does not take.
+SSAL_API int64_t ssal_enet_train_stage_features_offset(const ssal_enet *net, int n, int h, int w)
+{
+    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 8 || w % 8) return -1;
+    NetWorkspace W = carve(net, (void *)256, ((int64_t)1 << 62), n, h, w);
+    return (const char *)W.s1a - (const char *)256;
+}
+
+SSAL_API int64_t ssal_enet_train_stage_code_offset(const ssal_enet *net, int n, int h, int w)
+{
+    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 8 || w % 8) return -1;
+    NetWorkspace W = carve(net, (void *)256, ((int64_t)1 << 62), n, h, w);
+    return (const char *)W.code1 - (const char *)256;
+}
+
+SSAL_API int ssal_enet_train_stage_nhwc(ssal_enet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                                        const uint8_t *labels_dev, const float *mask_dev, const float *params_dev,
+                                        float weight, float label_smoothing, int max_workgroups, double *loss_dev,
+                                        float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    int rc = check_dims(net, n, h, w);
+    if (rc) return rc;
+    if ((rc = train_stage_check(n, h / 4, w / 4, net->classes, max_workgroups))) return rc;
+    if (!x_dev || !labels_dev || !mask_dev || !params_dev || !loss_dev || !grad_dev || !ws_dev)
+        return fail(SSAL_EINVAL, "NULL device pointer");
+    const int64_t need = ssal_enet_train_stage_workspace_bytes(net, n, h, w);
+    if (ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
+                                     (long long)ws_bytes);
+    NetWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
+    char *gws = (char *)ws_dev + (W.bytes + 255) / 256 * 256;
+    Bump b(gws, ws_bytes - (gws - (char *)ws_dev));
+    TrainStageWs t = train_stage_carve(b, n, h / 4, w / 4, net->classes, false);
+    if (!W.ok || !b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes", (long long)need);
+    hipStream_t s = (hipStream_t)stream;
+    // the frozen trunk, training=False: Initial .. Bottleneck4_2 on the caller's stream (its output lands in W.s1a, the window
+    // codes of Bottleneck1_0's pooling in W.code1); Bottleneck5_0 runs from params_dev into W.a0, where the forward leaves it
+    for (int li = 0; li < kNumLayers - 3; ++li) HIP_TRY(run_layer_idx(net, li, x_dev, x_is_u8 != 0, W, n, h, w, s));
+    t.a5 = W.a0;
+    t.code = W.code1;
+    HIP_TRY(launch_train_stage_grad(W.s1a, nullptr, n, h / 4, w / 4, net->classes, params_dev, labels_dev, mask_dev, weight,
+                                    label_smoothing, max_workgroups, t, loss_dev, grad_dev, s));
     return SSAL_OK;
 }

@@ -39,9 +39,11 @@ struct TrainBlockWs {
 };
 
 // x5 [N,H,W,16] = Bottleneck5_0's output; params / grad: the packed block of train_block_floats(K) floats; labels uint8 /
-// mask fp32 [N,2H,2W]; loss one double.
+// mask fp32 [N,2H,2W]; loss one double.  dx (may be NULL) [N,H,W,16]: the block's input gradient dL/d x5, before the
+// 1 / sum(mask) factor (what the last-stage trainer goes on from, ssal_train_stage.h); max_workgroups > 0 lowers the
+// workgroup count below train_block_workgroups(H, W).  Neither changes a bit of loss or grad at the default count.
 hipError_t launch_train_block_grad(const float *x5, int N, int H, int W, int K, const float *params, const uint8_t *labels,
                                    const float *mask, float weight, float label_smoothing, const TrainBlockWs &ws,
-                                   double *loss, float *grad, hipStream_t s);
+                                   double *loss, float *grad, hipStream_t s, float *dx = nullptr, int max_workgroups = 0);
 
 }  // namespace ssal

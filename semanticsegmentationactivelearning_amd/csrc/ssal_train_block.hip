@@ -382,8 +382,12 @@ __device__ __forceinline__ int tb_elem_slot(int e)
 // gamma / beta gradients are produced directly: d gamma = sum dL/dy (acc - mean) / sqrt(var + 1e-3), d beta = sum dL/dy.
 // part [TB_ROWS gridDim.x][TB_TRAINED] (zeroed by the launcher): row 3 g + third; the per-channel sums (folded over the 256
 // threads in thread order) go to row 3 g.
+// DX (the last-stage trainer): the block's INPUT gradient of the tile's pixels -> dx [N,H,W,16]: the
+// residual path (dL/du, handed from C to D through lx) plus the projection's input gradient through BN and PReLU.
+template <bool DX>
 __global__ __launch_bounds__(256) void k_tb_block(const float *__restrict__ x5, const float *__restrict__ dy, int N, int H,
-                                                  int W, const float *__restrict__ fold, float *__restrict__ part)
+                                                  int W, const float *__restrict__ fold, float *__restrict__ part,
+                                                  float *__restrict__ dx)
 {
     __shared__ __attribute__((aligned(16))) float p1[TB_PW * TB_PW * 4];
     __shared__ __attribute__((aligned(16))) float dac[TB_AW * TB_AW * 4];
@@ -456,6 +460,11 @@ __global__ __launch_bounds__(256) void k_tb_block(const float *__restrict__ x5, 
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
                         reinterpret_cast<float4 *>(lde)[p * 4 + q] = make_float4(de[4 * q], de[4 * q + 1], de[4 * q + 2], de[4 * q + 3]);
+                    if constexpr (DX) {  // dL/du of the pixel: lx is free until D writes x into it
+#pragma unroll
+                        for (int co = 0; co < 16; ++co)
+                            lx[p * 16 + co] = (ok ? dv[co] : 0.0f) * tb_dprelu(r.u[co], fold[TB_RA + co]);
+                    }
                 }
             }
             __syncthreads();
@@ -489,6 +498,23 @@ __global__ __launch_bounds__(256) void k_tb_block(const float *__restrict__ x5, 
                     dap[k] = valid ? dyp * fold[TB_PG + k] : 0.0f;
                 }
                 reinterpret_cast<float4 *>(ldp)[tid] = make_float4(dap[0], dap[1], dap[2], dap[3]);
+                if constexpr (DX) {
+                    if (valid) {
+                        float4 *o4 = reinterpret_cast<float4 *>(dx + (((long)n * H + i0 + ti) * W + j0 + tj) * 16);
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            float g[4];
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) {
+                                float a = 0.0f;
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) a = fmaf(dap[k], fold[TB_WP + (4 * q + c) * 4 + k], a);
+                                g[c] = lx[tid * 16 + 4 * q + c] + a;
+                            }
+                            o4[q] = make_float4(g[0], g[1], g[2], g[3]);
+                        }
+                    }
+                }
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
                     reinterpret_cast<float4 *>(lx)[tid * 4 + q] = make_float4(xv[4 * q], xv[4 * q + 1], xv[4 * q + 2], xv[4 * q + 3]);
@@ -582,10 +608,11 @@ __global__ __launch_bounds__(256) void k_tb_finish(const float *__restrict__ par
 
 hipError_t launch_train_block_grad(const float *x5, int N, int H, int W, int K, const float *params, const uint8_t *labels,
                                    const float *mask, float weight, float label_smoothing, const TrainBlockWs &ws,
-                                   double *loss, float *grad, hipStream_t s)
+                                   double *loss, float *grad, hipStream_t s, float *dx, int max_workgroups)
 {
     if (N < 1 || K < 2 || K > 32 || !train_block_fits(H, W)) return hipErrorInvalidValue;
-    const int G = train_block_workgroups(H, W);
+    int G = train_block_workgroups(H, W);
+    if (max_workgroups > 0 && max_workgroups < G) G = max_workgroups;
     const float on_value = 1.0f - label_smoothing, off_value = label_smoothing / ((float)K - 1.0f);
     const double pix = (double)N * H * W;
     const float *wk = params + TB_FINAL;
@@ -618,7 +645,8 @@ hipError_t launch_train_block_grad(const float *x5, int N, int H, int W, int K, 
     }
     {
         ProfScope prof("k_tb_block", 2.0 * pix * (272.0 * 1.6 + 272.0 * 2 + 64.0), 4.0 * pix * 16 * 2 + 4.0 * G * TB_ROWS * TB_TRAINED, s);
-        hipLaunchKernelGGL(k_tb_block, dim3(G), dim3(256), 0, s, x5, ws.dy, N, H, W, ws.fold, ws.part_b);
+        if (dx) hipLaunchKernelGGL(k_tb_block<true>, dim3(G), dim3(256), 0, s, x5, ws.dy, N, H, W, ws.fold, ws.part_b, dx);
+        else    hipLaunchKernelGGL(k_tb_block<false>, dim3(G), dim3(256), 0, s, x5, ws.dy, N, H, W, ws.fold, ws.part_b, dx);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

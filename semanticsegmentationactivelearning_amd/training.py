@@ -463,7 +463,7 @@ class LastBlockTrainer(FinalLayerTrainer):
         names = set(self.variable_names)
         for key in ("m", "v"):
             if not isinstance(state[key], dict) or set(state[key]) != names:
-                raise ValueError("state[%r] must map exactly the 13 variable names to arrays" % key)
+                raise ValueError("state[%r] must map exactly the %d variable names to arrays" % (key, len(names)))
         m, v = self._pack(state["m"]), self._pack(state["v"])
         self._t = int(state["t"])
         self._b1p = np.float32(1.0)
@@ -559,6 +559,14 @@ class LastBlockTrainer(FinalLayerTrainer):
         shape = (n, h // 2, w // 2, 16)
         return net._ws[off:off + 4 * n * (h // 2) * (w // 2) * 16].view(torch.float32).view(shape).clone()
 
+    def _trained_tail(self):
+        """how many of ``net.variables``, counted from the end, the training kernels take from the packed block"""
+        return len(getattr(self.net, _BLOCK).variables) + 1
+
+    def _adam_ranges(self):
+        """(lo, hi, regularised) float ranges of the packed block Adam runs on"""
+        return _ADAM_RANGES + ((_FINAL_OFFSET, _FINAL_OFFSET + 144 * int(self.net.classes), True),)
+
     def _trunk_handle(self):
         """the net's handle for the current device: reused while every variable BELOW Bottleneck5_1 is unchanged (the
         training kernels take the 13 variables and the block's statistics from the packed device block).  The handle's
@@ -566,7 +574,7 @@ class LastBlockTrainer(FinalLayerTrainer):
         torch = _lib.require_gpu()
         net = self.net
         ent = net._handles.get(torch.cuda.current_device())
-        tail = len(getattr(net, _BLOCK).variables) + 1
+        tail = self._trained_tail()
         if ent is not None and ent[1] is not None:
             if tuple(v.version for v in net.variables)[:-tail] == ent[1][:-tail]:
                 return ent[0]
@@ -577,7 +585,7 @@ class LastBlockTrainer(FinalLayerTrainer):
         L = _lib.lib()
         torch = _lib.require_gpu()
         w, m, v = dev["w"], dev["m"], dev["v"]
-        for lo, hi, reg in _ADAM_RANGES + ((_FINAL_OFFSET, self._floats(), True),):
+        for lo, hi, reg in self._adam_ranges():
             _lib.check(L.ssal_adam_apply(_lib.dev_ptr(w[lo:hi]), _lib.dev_ptr(m[lo:hi]), _lib.dev_ptr(v[lo:hi]),
                                          _lib.dev_ptr(grad[lo:hi]), hi - lo, float(lr), self.beta1, self.beta2, self.epsilon,
                                          float(self._b1p), float(self._b2p), self.l1 if reg else 0.0,
@@ -628,4 +636,219 @@ class LastBlockTrainer(FinalLayerTrainer):
         return loss[0]
 
 
-__all__ = ["FinalLayerTrainer", "LastBlockTrainer"]
+# ---- the last stage: Bottleneck5_0 + Bottleneck5_1 + Final ------------------------------------------
+# Bottleneck5_0's part of the packed stage block (include/ssal_enet.h, "Last-stage training"), offsets from its start
+_STAGE = "Bottleneck5_0"
+_STAGE_LAYOUT = (
+    ("proj_kernel", 0, True), ("proj_gamma", 1024, False), ("proj_beta", 1040, False), ("proj_alpha", 1056, True),
+    ("conv_kernel", 1072, True), ("conv_gamma", 2224, False), ("conv_beta", 2232, False), ("conv_alpha", 2240, True),
+    ("exp_kernel", 2248, True), ("exp_gamma", 2376, False), ("exp_beta", 2392, False), ("res_kernel", 2408, True),
+    ("residual_alpha", 3432, True),
+)
+_STAGE_STATS = (("proj_mean", 3448), ("proj_variance", 3464), ("conv_mean", 3480), ("conv_variance", 3488),
+                ("exp_mean", 3496), ("exp_variance", 3512))
+_STAGE_FLOATS = 3536
+_STAGE_ADAM_RANGES = ((0, 1024, True), (1024, 1056, False), (1056, 2224, True), (2224, 2240, False), (2240, 2376, True),
+                      (2376, 2408, False), (2408, 3448, True))
+
+
+class LastStageTrainer(LastBlockTrainer):
+    """Adam on the 26 variables of ENet's last decoder stage: the 13 of ``LastBlockTrainer`` and ``Bottleneck5_0``'s
+    ``proj_kernel``, ``proj_gamma``, ``proj_beta``, ``proj_alpha``, ``conv_kernel``, ``conv_gamma``, ``conv_beta``,
+    ``conv_alpha``, ``exp_kernel``, ``exp_gamma``, ``exp_beta``, ``res_kernel`` and ``residual_alpha``: the backward pass
+    through the network's last upsampling block (a transposed convolution, a max-unpool, a resolution change).
+
+    The deviation from the reference is ``LastBlockTrainer``'s: everything below Bottleneck5_0 is frozen and runs with
+    ``training=False``; both trained blocks run in INFERENCE mode (constant moving statistics, never written; no spatial
+    dropout; batch-norm ``y = gamma (x - mean) / sqrt(var + 1e-3) + beta`` with ``gamma`` / ``beta`` trainable).  The
+    unpool's backward is the gather of the gradient at each element's pooling position.
+
+    Regulariser: the Keras ``l1_l2`` gradient goes, next to ``LastBlockTrainer``'s set, to the variables of Bottleneck5_0 the
+    reference passes a regulariser to (enet_modules.py:1070-1214): ``proj_kernel``, ``proj_alpha``, ``conv_kernel``,
+    ``conv_alpha``, ``exp_kernel``, ``res_kernel``, ``residual_alpha``; ``gamma`` / ``beta`` get the plain Adam update.
+
+    The inputs are Bottleneck4_2's output [N, h, w, 64] and ``argmax1`` [N, h, w, 16] int64, the pooling indices of
+    Bottleneck1_0 in the reference's per-image form ``(y * 2w + x) * 16 + c`` (``features(images)`` returns both)."""
+
+    def _stage_offset(self):
+        return _FINAL_OFFSET + 144 * int(self.net.classes)
+
+    def _named(self):
+        """[(name, Variable, float offset, regularised)] of the 26 trained variables: the last block's, then Bottleneck5_0's"""
+        base = super()._named()
+        blk, s0 = getattr(self.net, _STAGE), self._stage_offset()
+        return base + [("%s.%s" % (_STAGE, a), getattr(blk, a), s0 + off, reg) for a, off, reg in _STAGE_LAYOUT]
+
+    def _floats(self):
+        return self._stage_offset() + _STAGE_FLOATS
+
+    def _pack(self, arrays=None):
+        out = super()._pack(arrays)
+        if arrays is None:
+            blk, s0 = getattr(self.net, _STAGE), self._stage_offset()
+            for a, off in _STAGE_STATS:
+                v = getattr(blk, a).numpy()
+                out[s0 + off:s0 + off + v.size] = v
+        return out
+
+    def _versions(self):
+        return super()._versions() + tuple(v.version for v in getattr(self.net, _STAGE).variables)
+
+    def _trained_tail(self):
+        return super()._trained_tail() + len(getattr(self.net, _STAGE).variables)
+
+    def _adam_ranges(self):
+        s0 = self._stage_offset()
+        return super()._adam_ranges() + tuple((s0 + lo, s0 + hi, reg) for lo, hi, reg in _STAGE_ADAM_RANGES)
+
+    # ---- arguments, judged on the host ---------------------------------------------------------------------------------------
+    def _check_argmax(self, feature_shape, argmax1):
+        """``argmax1`` as an int64 tensor (on whatever device it lives) after the checks: shape [N, h, w, 16], every index
+        inside its own 2 x 2 window and channel.  A torch tensor that passed is remembered, so a cached one is checked once."""
+        import torch
+        a = argmax1 if isinstance(argmax1, torch.Tensor) else torch.as_tensor(np.asarray(argmax1))
+        shape = tuple(feature_shape)
+        if len(shape) != 4 or shape[-1] != 64:
+            raise ValueError("features must be [N,h,w,64] (got %s)" % (shape,))
+        want = shape[:3] + (16,)
+        if tuple(a.shape) != want:
+            raise ValueError("argmax1 must have shape %s (got %s)" % (want, tuple(a.shape)))
+        if a.dtype != torch.int64:
+            if a.dtype.is_floating_point or a.dtype == torch.bool:
+                raise ValueError("argmax1 must be an integer tensor (got %s)" % a.dtype)
+            a = a.to(torch.int64)
+        seen = getattr(self, "_argmax_ok", None)  # (the caller's tensor itself, its version): kept alive, so never confused
+        if not (seen is not None and seen[0] is argmax1 and seen[1] == argmax1._version):
+            _, h, w, _ = want
+            c = torch.arange(16, device=a.device).view(1, 1, 1, 16)
+            i = torch.arange(h, device=a.device).view(1, h, 1, 1)
+            j = torch.arange(w, device=a.device).view(1, 1, w, 1)
+            pix = torch.div(a, 16, rounding_mode="floor")
+            y, x = torch.div(pix, 2 * w, rounding_mode="floor"), pix % (2 * w)
+            ok = (a >= 0) & (a % 16 == c) & (torch.div(y, 2, rounding_mode="floor") == i) & \
+                 (torch.div(x, 2, rounding_mode="floor") == j)
+            if not bool(ok.all()):
+                raise ValueError("argmax1 holds %d indices outside their own 2x2 window / channel"
+                                 % int((~ok).sum()))
+            self._argmax_ok = (argmax1, argmax1._version) if isinstance(argmax1, torch.Tensor) else None
+        return a
+
+    def _check_params(self, params):
+        params = dict(params or {})
+        unknown = set(params) - set(self.variable_names)
+        frozen = self.net._layer_names[:self.net._layer_names.index(_STAGE)]
+        below = sorted(n for n in unknown if n.split(".")[0] in frozen)
+        if below:
+            raise NotImplementedError("training below Bottleneck5_0 is not implemented (got %s)" % below)
+        if unknown:
+            raise ValueError("unknown variables %s (the moving statistics always come from the model)" % sorted(unknown))
+        return params
+
+    @staticmethod
+    def _check_workgroups(max_workgroups):
+        if int(max_workgroups) < 0:
+            raise ValueError("max_workgroups must be >= 0 (got %r)" % (max_workgroups,))
+        return int(max_workgroups)
+
+    # ---- gradients -------------------------------------------------------------------------------------------------------
+    def _grad_packed(self, x, argmax, labels, mask, params_dev, max_workgroups=0):
+        torch = _lib.require_gpu()
+        n, h, w, _ = x.shape
+        k = int(self.net.classes)
+        lab, mk = self._targets(labels, mask, (n, 4 * h, 4 * w), x.device)
+        am = argmax.to(device=x.device).contiguous()
+        L = _lib.lib()
+        with torch.cuda.device(x.device):
+            nbytes = L.ssal_train_stage_grad_workspace_bytes(n, h, w, k)
+            if nbytes < 0:
+                raise ValueError("feature map %dx%d is beyond the gradient kernels' limit" % (h, w))
+            ws = torch.empty(int(nbytes), dtype=torch.uint8, device=x.device)
+            loss = torch.empty((1,), dtype=torch.float64, device=x.device)
+            grad = torch.empty(self._floats(), dtype=torch.float32, device=x.device)
+            _lib.check(L.ssal_train_stage_grad_nhwc(_lib.dev_ptr(x), _lib.dev_ptr(am), n, h, w, k, _lib.dev_ptr(params_dev),
+                                                    _lib.dev_ptr(lab), _lib.dev_ptr(mk), self.weight, self.label_smoothing,
+                                                    max_workgroups, _lib.dev_ptr(loss), _lib.dev_ptr(grad), _lib.dev_ptr(ws),
+                                                    ws.numel(), _lib.stream_ptr()))
+        return loss, grad
+
+    def gradient_features(self, features4_2, argmax1, labels, mask, params=None, max_workgroups=0, **semi):
+        """(loss float64 [1], {name: gradient}) on the device for Bottleneck4_2's output [N, h, w, 64], the pooling indices
+        ``argmax1`` [N, h, w, 16] and labels / mask [N, 4h, 4w].  ``params``: a name -> array mapping that overrides any of
+        the 26 variables (the others, and the moving statistics, are the model's).  ``max_workgroups``: 0 = the default,
+        min(tiles, 1024); a tuning knob.  No update."""
+        self._no_semi(**semi)
+        params = self._check_params(params)
+        max_workgroups = self._check_workgroups(max_workgroups)
+        am = self._check_argmax(np.shape(features4_2), argmax1)
+        packed = self._pack()
+        for name, var, off, _ in self._named():
+            if name in params:
+                a = params[name]
+                a = np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a, dtype=np.float32)
+                if a.shape != var.shape:
+                    raise ValueError("%s must have shape %s (got %s)" % (name, var.shape, a.shape))
+                packed[off:off + a.size] = a.reshape(-1)
+        x = _lib.as_device_f32(features4_2)
+        torch = _lib.require_gpu()
+        loss, grad = self._grad_packed(x, am, labels, mask, torch.from_numpy(packed).to(x.device), max_workgroups)
+        return loss, self._grad_dict(grad)
+
+    def features(self, images):
+        """(Bottleneck4_2's output [N, H/4, W/4, 64] (a copy), argmax1 [N, H/4, W/4, 16] int64) for ``images``: what
+        ``step_features`` and ``gradient_features`` take.  One forward pass of the frozen trunk; the frozen layers never
+        change, so the result can be cached across steps."""
+        net = self.net
+        x = net._prepare(images, False)
+        n, h, w, _ = x.shape
+        net(x, training=False)
+        off = _lib.lib().ssal_enet_train_stage_features_offset(net._handle, n, h, w)
+        if off < 0:
+            raise ValueError("bad input dims %s" % (tuple(x.shape),))
+        torch = _lib.require_gpu()
+        shape = (n, h // 4, w // 4, 64)
+        feats = net._ws[off:off + 4 * n * (h // 4) * (w // 4) * 64].view(torch.float32).view(shape).clone()
+        return feats, net.pooling_argmax()[0]
+
+    def step_features(self, features4_2, argmax1, labels, mask, max_workgroups=0, **semi):
+        """one Adam step from cached Bottleneck4_2 features and pooling indices (``features(images)``); returns the loss
+        (float64 device scalar) BEFORE the step, as ``sess.run([loss, train_op])`` does"""
+        self._no_semi(**semi)
+        max_workgroups = self._check_workgroups(max_workgroups)
+        am = self._check_argmax(np.shape(features4_2), argmax1)
+        x = _lib.as_device_f32(features4_2)
+        dev = self._device_state(x.device)
+        loss, grad = self._grad_packed(x, am, labels, mask, dev["w"], max_workgroups)
+        self._apply(dev, grad)
+        return loss[0]
+
+    def step(self, images, labels, mask, max_workgroups=0, **semi):
+        """one Adam step from images [N, H, W, C] (fp32 or decoded uint8) and labels / mask [N, H, W]: the frozen trunk up
+        to Bottleneck4_2, the stage's forward and training kernels, Adam.  Returns the loss (float64 device scalar) before
+        the step."""
+        self._no_semi(**semi)
+        max_workgroups = self._check_workgroups(max_workgroups)
+        torch = _lib.require_gpu()
+        net = self.net
+        x = net._prepare(images, False)
+        n, h, w, _ = x.shape
+        L = _lib.lib()
+        lab, mk = self._targets(labels, mask, (n, h, w), x.device)
+        with torch.cuda.device(x.device):
+            dev = self._device_state(x.device)
+            handle = self._trunk_handle()
+            nbytes = L.ssal_enet_train_stage_workspace_bytes(handle, n, h, w)
+            if nbytes < 0:
+                raise ValueError("bad input dims %s" % (tuple(x.shape),))
+            ws = net._workspace(nbytes, x.device)
+            loss = torch.empty((1,), dtype=torch.float64, device=x.device)
+            _lib.check(L.ssal_enet_train_stage_nhwc(handle, _lib.dev_ptr(x), int(x.dtype == torch.uint8), n, h, w,
+                                                    _lib.dev_ptr(lab), _lib.dev_ptr(mk), _lib.dev_ptr(dev["w"]), self.weight,
+                                                    self.label_smoothing, max_workgroups, _lib.dev_ptr(loss),
+                                                    _lib.dev_ptr(dev["grad"]), _lib.dev_ptr(ws), ws.numel(),
+                                                    _lib.stream_ptr()))
+            net._note_call(ws, (n, h, w), "train")
+            self._apply(dev, dev["grad"])
+        return loss[0]
+
+
+__all__ = ["FinalLayerTrainer", "LastBlockTrainer", "LastStageTrainer"]
