@@ -523,6 +523,47 @@ int ssal_enet_train_stage_nhwc(ssal_enet *net, const void *x_dev, int x_is_u8, i
 int64_t ssal_enet_train_stage_features_offset(const ssal_enet *net, int n, int h, int w);
 int64_t ssal_enet_train_stage_code_offset(const ssal_enet *net, int n, int h, int w);
 
+/* ---- The semi-supervised step of the deeper trainers (active_learning.py:226-275, 339-342) ----
+ * ssal_train_block_grad_nhwc / ssal_train_stage_grad_nhwc and their image forms with the batch's targets built inside the
+ * head kernel.  labelled_dev, measure, threshold, confusion_dev and pseudo_pixels_dev mean exactly what they mean for
+ * ssal_final_grad_semi_nhwc above (labelled_dev NULL = every image labelled; labels_dev / mask_dev may be NULL only when
+ * labelled_dev marks no image as labelled, the caller's contract; the planes of an unlabelled image are never read; the
+ * confusion matrix is accumulated; pseudo_pixels_dev is overwritten and 0 for a labelled image).  The pseudo logits are
+ * those of the logits the kernel trains on, under params_dev, or -- features_raw_dev / x_raw_dev given -- those of the
+ * undistorted frames: a target-only launch of the same kernel writes one byte per output pixel (label | mask << 7) into
+ * the workspace first (with_raw = 1 in the size query), which the training launch reads.  The stage's raw side brings its
+ * own pooling indices argmax_raw_dev (given together with features_raw_dev or not at all).  loss_dev / grad_dev hold
+ * exactly what the plain entry gives for the composed targets, bit for bit; integer counts, no float atomics.  Limits
+ * and statuses as the plain entries (the queries return -1 at the same boundaries), plus SSAL_ENOTIMPL for an unknown
+ * measure; every argument is judged before any device work. */
+int64_t ssal_train_block_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw);
+int ssal_train_block_grad_semi_nhwc(const float *features_dev, const float *features_raw_dev, int n, int h, int w,
+                                    int classes, const float *params_dev, const uint8_t *labels_dev, const float *mask_dev,
+                                    const uint8_t *labelled_dev, int measure, float threshold, float weight,
+                                    float label_smoothing, double *loss_dev, float *grad_dev, int64_t *confusion_dev,
+                                    int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream);
+int64_t ssal_enet_train_block_semi_workspace_bytes(const ssal_enet *net, int n, int h, int w, int with_raw);
+int ssal_enet_train_block_semi_nhwc(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h,
+                                    int w, const uint8_t *labels_dev, const float *mask_dev, const uint8_t *labelled_dev,
+                                    int measure, float threshold, const float *params_dev, float weight,
+                                    float label_smoothing, double *loss_dev, float *grad_dev, int64_t *confusion_dev,
+                                    int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream);
+int64_t ssal_train_stage_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw);
+int ssal_train_stage_grad_semi_nhwc(const float *features_dev, const int64_t *argmax_dev, const float *features_raw_dev,
+                                    const int64_t *argmax_raw_dev, int n, int h, int w, int classes,
+                                    const float *params_dev, const uint8_t *labels_dev, const float *mask_dev,
+                                    const uint8_t *labelled_dev, int measure, float threshold, float weight,
+                                    float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev,
+                                    int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes,
+                                    void *stream);
+int64_t ssal_enet_train_stage_semi_workspace_bytes(const ssal_enet *net, int n, int h, int w, int with_raw);
+int ssal_enet_train_stage_semi_nhwc(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h,
+                                    int w, const uint8_t *labels_dev, const float *mask_dev, const uint8_t *labelled_dev,
+                                    int measure, float threshold, const float *params_dev, float weight,
+                                    float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev,
+                                    int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes,
+                                    void *stream);
+
 #ifdef __cplusplus
 }
 #endif

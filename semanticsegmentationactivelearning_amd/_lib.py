@@ -195,6 +195,19 @@ PROTOTYPES = {
     "ssal_enet_train_stage_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _i64, _vp]),
     "ssal_enet_train_stage_features_offset": (_i64, [_vp, _i, _i, _i]),
     "ssal_enet_train_stage_code_offset": (_i64, [_vp, _i, _i, _i]),
+    # ---- the semi-supervised step of the last-block / last-stage trainers ----
+    "ssal_train_block_grad_semi_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
+    "ssal_train_block_grad_semi_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _vp, _vp, _vp,
+                                             _vp, _vp, _i64, _vp]),
+    "ssal_enet_train_block_semi_workspace_bytes": (_i64, [_vp, _i, _i, _i, _i]),
+    "ssal_enet_train_block_semi_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _f, _f, _vp, _vp,
+                                             _vp, _vp, _vp, _i64, _vp]),
+    "ssal_train_stage_grad_semi_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
+    "ssal_train_stage_grad_semi_nhwc": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _i,
+                                             _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_enet_train_stage_semi_workspace_bytes": (_i64, [_vp, _i, _i, _i, _i]),
+    "ssal_enet_train_stage_semi_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _f, _f, _i, _vp,
+                                             _vp, _vp, _vp, _vp, _i64, _vp]),
     # ---- measurement aids (include/ssal_enet.h) ----
     "ssal_profile_enable": (_i, [_i]),
     "ssal_profile_collect": (_i, [_c.c_char_p, _i64]),

@@ -2119,3 +2119,220 @@ SSAL_API int ssal_enet_train_stage_nhwc(ssal_enet *net, const void *x_dev, int x
                                     label_smoothing, max_workgroups, t, loss_dev, grad_dev, s));
     return SSAL_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// The semi-supervised step of the last-block and last-stage trainers (include/ssal_enet.h, "The semi-supervised step of the
+// deeper trainers").  Workspace: the plain entry's, then the confusion replicas, then (with_raw) the
+// packed pseudo-target plane of the undistorted frames, one byte per output pixel.
+// ------------------------------------------------------------------------------------------------
+struct TrainSemiWs {
+    unsigned long long *rep;
+    uint8_t *tgt;
+};
+
+// out_pix = output pixels per image ([2h, 2w] of the block's map)
+static TrainSemiWs train_semi_carve(Bump &b, int64_t n, int64_t out_pix, int classes, bool with_raw)
+{
+    TrainSemiWs t;
+    t.rep = b.take<unsigned long long>((int64_t)ssal::kConfMaxReps * ssal::conf_rep_stride(classes * classes));
+    t.tgt = with_raw ? b.take<uint8_t>(n * out_pix) : nullptr;
+    return t;
+}
+
+static TrainBlockSemi train_semi_args(const TrainSemiWs &sw, const uint8_t *labelled_dev, int measure, float threshold,
+                                      bool with_raw, int64_t *confusion_dev, int64_t *pseudo_pixels_dev)
+{
+    TrainBlockSemi sa;
+    sa.labelled = labelled_dev;
+    sa.measure = measure;
+    sa.threshold = threshold;
+    sa.tgt = sw.tgt;
+    sa.use_tgt = with_raw && labelled_dev;
+    sa.rep = confusion_dev ? sw.rep : nullptr;
+    sa.reps = ssal::knobs().conf_reps;
+    sa.pseudo_pixels = pseudo_pixels_dev;
+    return sa;
+}
+
+static int train_semi_zero(const TrainBlockSemi &sa, int classes, hipStream_t s)
+{
+    if (sa.rep) HIP_TRY(hipMemsetAsync(sa.rep, 0, (size_t)sa.reps * ssal::conf_rep_stride(classes * classes) * 8, s));
+    return SSAL_OK;
+}
+
+static int train_semi_fold(const TrainBlockSemi &sa, int classes, int64_t *confusion_dev, hipStream_t s)
+{
+    if (sa.rep) HIP_TRY(launch_confusion_fold(sa.rep, sa.reps, classes, confusion_dev, s));
+    return SSAL_OK;
+}
+
+SSAL_API int64_t ssal_train_block_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw)
+{
+    if (classes < 2 || classes > 32 || n <= 0 || h <= 0 || w <= 0 || !train_block_fits(h, w)) return -1;
+    Bump b(nullptr, 0);
+    train_block_carve(b, n, h, w, classes);
+    train_semi_carve(b, n, 4 * (int64_t)h * w, classes, with_raw != 0);
+    return b.off + 256;
+}
+
+SSAL_API int ssal_train_block_grad_semi_nhwc(const float *features_dev, const float *features_raw_dev, int n, int h, int w,
+                                             int classes, const float *params_dev, const uint8_t *labels_dev,
+                                             const float *mask_dev, const uint8_t *labelled_dev, int measure,
+                                             float threshold, float weight, float label_smoothing, double *loss_dev,
+                                             float *grad_dev, int64_t *confusion_dev, int64_t *pseudo_pixels_dev,
+                                             void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    if (int rc = final_grad_check(n, h, w, classes)) return rc;
+    if (int rc = final_grad_semi_check(measure, labels_dev, mask_dev, labelled_dev)) return rc;
+    if (!features_dev || !params_dev || !loss_dev || !grad_dev || !ws_dev) return fail(SSAL_EINVAL, "NULL device pointer");
+    const bool raw = features_raw_dev != nullptr;
+    const int64_t need = ssal_train_block_grad_semi_workspace_bytes(n, h, w, classes, raw);
+    if (ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
+                                     (long long)ws_bytes);
+    Bump b(ws_dev, ws_bytes);
+    const TrainBlockWs t = train_block_carve(b, n, h, w, classes);
+    const TrainSemiWs sw = train_semi_carve(b, n, 4 * (int64_t)h * w, classes, raw);
+    if (!b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes", (long long)need);
+    hipStream_t s = (hipStream_t)stream;
+    const TrainBlockSemi sa = train_semi_args(sw, labelled_dev, measure, threshold, raw, confusion_dev, pseudo_pixels_dev);
+    if (int rc = train_semi_zero(sa, classes, s)) return rc;
+    if (raw) HIP_TRY(launch_train_block_targets(features_raw_dev, n, h, w, classes, params_dev, sa, t, s));
+    HIP_TRY(launch_train_block_grad(features_dev, n, h, w, classes, params_dev, labels_dev, mask_dev, weight,
+                                    label_smoothing, t, loss_dev, grad_dev, s, nullptr, 0, &sa));
+    return train_semi_fold(sa, classes, confusion_dev, s);
+}
+
+SSAL_API int64_t ssal_enet_train_block_semi_workspace_bytes(const ssal_enet *net, int n, int h, int w, int with_raw)
+{
+    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 8 || w % 8) return -1;
+    const int64_t g = ssal_train_block_grad_semi_workspace_bytes(n, h / 2, w / 2, net->classes, with_raw);
+    if (g < 0) return -1;
+    return carve(net, nullptr, 0, n, h, w).bytes + 256 + g;
+}
+
+SSAL_API int ssal_enet_train_block_semi_nhwc(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
+                                             int h, int w, const uint8_t *labels_dev, const float *mask_dev,
+                                             const uint8_t *labelled_dev, int measure, float threshold,
+                                             const float *params_dev, float weight, float label_smoothing,
+                                             double *loss_dev, float *grad_dev, int64_t *confusion_dev,
+                                             int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    int rc = check_dims(net, n, h, w);
+    if (rc) return rc;
+    if ((rc = final_grad_check(n, h / 2, w / 2, net->classes))) return rc;
+    if ((rc = final_grad_semi_check(measure, labels_dev, mask_dev, labelled_dev))) return rc;
+    if (!x_dev || !params_dev || !loss_dev || !grad_dev || !ws_dev) return fail(SSAL_EINVAL, "NULL device pointer");
+    const bool raw = x_raw_dev != nullptr;
+    const int64_t need = ssal_enet_train_block_semi_workspace_bytes(net, n, h, w, raw);
+    if (ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
+                                     (long long)ws_bytes);
+    NetWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
+    char *gws = (char *)ws_dev + (W.bytes + 255) / 256 * 256;
+    Bump b(gws, ws_bytes - (gws - (char *)ws_dev));
+    const TrainBlockWs t = train_block_carve(b, n, h / 2, w / 2, net->classes);
+    const TrainSemiWs sw = train_semi_carve(b, n, (int64_t)h * w, net->classes, raw);
+    if (!W.ok || !b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes", (long long)need);
+    hipStream_t s = (hipStream_t)stream;
+    const TrainBlockSemi sa = train_semi_args(sw, labelled_dev, measure, threshold, raw, confusion_dev, pseudo_pixels_dev);
+    if ((rc = train_semi_zero(sa, net->classes, s))) return rc;
+    // the frozen trunk on the undistorted frames first: their Bottleneck5_0 output (W.a0) is consumed by the target-only
+    // launch, which leaves one byte per output pixel, so the training frames can go through the same slots afterwards
+    if (raw && labelled_dev) {
+        for (int li = 0; li < kNumLayers - 2; ++li) HIP_TRY(run_layer_idx(net, li, x_raw_dev, x_is_u8 != 0, W, n, h, w, s));
+        HIP_TRY(launch_train_block_targets(W.a0, n, h / 2, w / 2, net->classes, params_dev, sa, t, s));
+    }
+    for (int li = 0; li < kNumLayers - 2; ++li) HIP_TRY(run_layer_idx(net, li, x_dev, x_is_u8 != 0, W, n, h, w, s));
+    HIP_TRY(launch_train_block_grad(W.a0, n, h / 2, w / 2, net->classes, params_dev, labels_dev, mask_dev, weight,
+                                    label_smoothing, t, loss_dev, grad_dev, s, nullptr, 0, &sa));
+    return train_semi_fold(sa, net->classes, confusion_dev, s);
+}
+
+SSAL_API int64_t ssal_train_stage_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw)
+{
+    if (classes < 2 || classes > 32 || n <= 0 || h <= 0 || w <= 0 || !train_stage_fits(h, w)) return -1;
+    Bump b(nullptr, 0);
+    train_stage_carve(b, n, h, w, classes, true);
+    train_semi_carve(b, n, 16 * (int64_t)h * w, classes, with_raw != 0);
+    return b.off + 256;
+}
+
+SSAL_API int ssal_train_stage_grad_semi_nhwc(const float *features_dev, const int64_t *argmax_dev,
+                                             const float *features_raw_dev, const int64_t *argmax_raw_dev, int n, int h,
+                                             int w, int classes, const float *params_dev, const uint8_t *labels_dev,
+                                             const float *mask_dev, const uint8_t *labelled_dev, int measure,
+                                             float threshold, float weight, float label_smoothing, int max_workgroups,
+                                             double *loss_dev, float *grad_dev, int64_t *confusion_dev,
+                                             int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    if (int rc = train_stage_check(n, h, w, classes, max_workgroups)) return rc;
+    if (int rc = final_grad_semi_check(measure, labels_dev, mask_dev, labelled_dev)) return rc;
+    if (!features_dev || !argmax_dev || !params_dev || !loss_dev || !grad_dev || !ws_dev)
+        return fail(SSAL_EINVAL, "NULL device pointer");
+    if ((features_raw_dev == nullptr) != (argmax_raw_dev == nullptr))
+        return fail(SSAL_EINVAL, "features_raw_dev and argmax_raw_dev are given together or not at all");
+    const bool raw = features_raw_dev != nullptr;
+    const int64_t need = ssal_train_stage_grad_semi_workspace_bytes(n, h, w, classes, raw);
+    if (ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
+                                     (long long)ws_bytes);
+    Bump b(ws_dev, ws_bytes);
+    const TrainStageWs t = train_stage_carve(b, n, h, w, classes, true);
+    const TrainSemiWs sw = train_semi_carve(b, n, 16 * (int64_t)h * w, classes, raw);
+    if (!b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes", (long long)need);
+    hipStream_t s = (hipStream_t)stream;
+    const TrainBlockSemi sa = train_semi_args(sw, labelled_dev, measure, threshold, raw, confusion_dev, pseudo_pixels_dev);
+    if (int rc = train_semi_zero(sa, classes, s)) return rc;
+    if (raw) HIP_TRY(launch_train_stage_targets(features_raw_dev, argmax_raw_dev, n, h, w, classes, params_dev, max_workgroups,
+                                                t, sa, s));
+    HIP_TRY(launch_train_stage_grad(features_dev, argmax_dev, n, h, w, classes, params_dev, labels_dev, mask_dev, weight,
+                                    label_smoothing, max_workgroups, t, loss_dev, grad_dev, s, &sa));
+    return train_semi_fold(sa, classes, confusion_dev, s);
+}
+
+SSAL_API int64_t ssal_enet_train_stage_semi_workspace_bytes(const ssal_enet *net, int n, int h, int w, int with_raw)
+{
+    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 8 || w % 8) return -1;
+    if (net->classes < 2 || net->classes > 32 || !train_stage_fits(h / 4, w / 4)) return -1;
+    Bump b(nullptr, 0);
+    train_stage_carve(b, n, h / 4, w / 4, net->classes, false);
+    train_semi_carve(b, n, (int64_t)h * w, net->classes, with_raw != 0);
+    return carve(net, nullptr, 0, n, h, w).bytes + 256 + b.off + 256;
+}
+
+SSAL_API int ssal_enet_train_stage_semi_nhwc(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
+                                             int h, int w, const uint8_t *labels_dev, const float *mask_dev,
+                                             const uint8_t *labelled_dev, int measure, float threshold,
+                                             const float *params_dev, float weight, float label_smoothing,
+                                             int max_workgroups, double *loss_dev, float *grad_dev, int64_t *confusion_dev,
+                                             int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    int rc = check_dims(net, n, h, w);
+    if (rc) return rc;
+    if ((rc = train_stage_check(n, h / 4, w / 4, net->classes, max_workgroups))) return rc;
+    if ((rc = final_grad_semi_check(measure, labels_dev, mask_dev, labelled_dev))) return rc;
+    if (!x_dev || !params_dev || !loss_dev || !grad_dev || !ws_dev) return fail(SSAL_EINVAL, "NULL device pointer");
+    const bool raw = x_raw_dev != nullptr;
+    const int64_t need = ssal_enet_train_stage_semi_workspace_bytes(net, n, h, w, raw);
+    if (ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
+                                     (long long)ws_bytes);
+    NetWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
+    char *gws = (char *)ws_dev + (W.bytes + 255) / 256 * 256;
+    Bump b(gws, ws_bytes - (gws - (char *)ws_dev));
+    TrainStageWs t = train_stage_carve(b, n, h / 4, w / 4, net->classes, false);
+    const TrainSemiWs sw = train_semi_carve(b, n, (int64_t)h * w, net->classes, raw);
+    if (!W.ok || !b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes", (long long)need);
+    hipStream_t s = (hipStream_t)stream;
+    t.a5 = W.a0;
+    t.code = W.code1;
+    const TrainBlockSemi sa = train_semi_args(sw, labelled_dev, measure, threshold, raw, confusion_dev, pseudo_pixels_dev);
+    if ((rc = train_semi_zero(sa, net->classes, s))) return rc;
+    // the frozen trunk on the undistorted frames first (Bottleneck4_2 in W.s1a, their own window codes in W.code1), the
+    // stage's forward on them and the target-only launch; then the training frames through the same slots
+    if (raw && labelled_dev) {
+        for (int li = 0; li < kNumLayers - 3; ++li) HIP_TRY(run_layer_idx(net, li, x_raw_dev, x_is_u8 != 0, W, n, h, w, s));
+        HIP_TRY(launch_train_stage_targets(W.s1a, nullptr, n, h / 4, w / 4, net->classes, params_dev, max_workgroups, t, sa, s));
+    }
+    for (int li = 0; li < kNumLayers - 3; ++li) HIP_TRY(run_layer_idx(net, li, x_dev, x_is_u8 != 0, W, n, h, w, s));
+    HIP_TRY(launch_train_stage_grad(W.s1a, nullptr, n, h / 4, w / 4, net->classes, params_dev, labels_dev, mask_dev, weight,
+                                    label_smoothing, max_workgroups, t, loss_dev, grad_dev, s, &sa));
+    return train_semi_fold(sa, net->classes, confusion_dev, s);
+}

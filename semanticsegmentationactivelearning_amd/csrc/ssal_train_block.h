@@ -38,12 +38,38 @@ struct TrainBlockWs {
     double *lpart;
 };
 
+// The semi-supervised step.  labelled [N] uint8, NULL = all labelled: an image with labelled[n] == 0 is
+// trained on its pseudo annotation (argmax / confidence >= threshold of its logits for `measure`, a code of ssal_enet.h) and
+// its label / mask planes are never read.  use_tgt: the pseudo annotation is read from tgt [N,2H,2W] (a byte per output
+// pixel: the label in bits 0..6, the mask in bit 7), which launch_train_block_targets wrote from the undistorted frame's
+// features; otherwise it comes from the training logits.  rep [reps][conf_rep_stride(K * K)] u64 (NULL = no confusion
+// matrix) must be zero on entry, the caller folds it with launch_confusion_fold; pseudo_pixels [N] (NULL = not counted) is
+// zeroed by launch_train_block_grad.
+struct TrainBlockSemi {
+    const uint8_t *labelled;
+    int measure;
+    float threshold;
+    uint8_t *tgt;
+    bool use_tgt;
+    unsigned long long *rep;
+    int reps;
+    int64_t *pseudo_pixels;
+};
+
 // x5 [N,H,W,16] = Bottleneck5_0's output; params / grad: the packed block of train_block_floats(K) floats; labels uint8 /
 // mask fp32 [N,2H,2W]; loss one double.  dx (may be NULL) [N,H,W,16]: the block's input gradient dL/d x5, before the
 // 1 / sum(mask) factor (what the last-stage trainer goes on from, ssal_train_stage.h); max_workgroups > 0 lowers the
 // workgroup count below train_block_workgroups(H, W).  Neither changes a bit of loss or grad at the default count.
+// semi (may be NULL: the plain step, whose launches are unchanged): labels / mask may then be NULL when no image is labelled.
 hipError_t launch_train_block_grad(const float *x5, int N, int H, int W, int K, const float *params, const uint8_t *labels,
                                    const float *mask, float weight, float label_smoothing, const TrainBlockWs &ws,
-                                   double *loss, float *grad, hipStream_t s, float *dx = nullptr, int max_workgroups = 0);
+                                   double *loss, float *grad, hipStream_t s, float *dx = nullptr, int max_workgroups = 0,
+                                   const TrainBlockSemi *semi = nullptr);
+
+// The target-only launch of the head kernel: the packed pseudo targets of the unlabelled images of x5_raw [N,H,W,16] (the
+// undistorted frames' Bottleneck5_0 output) -> semi.tgt.  Uses ws.fold only; stream-ordered before launch_train_block_grad.
+hipError_t launch_train_block_targets(const float *x5_raw, int N, int H, int W, int K, const float *params,
+                                      const TrainBlockSemi &semi, const TrainBlockWs &ws, hipStream_t s,
+                                      int max_workgroups = 0);
 
 }  // namespace ssal

@@ -4,17 +4,23 @@
 //   k_tb_head    Bottleneck5_1's forward on an 18 x 18 window, the Final logits, the masked softmax cross entropy and
 //                dL/dlogit on a 17 x 17 window of 2 x 2 output quads; dL/dW of Final.kernel as per-workgroup partials and
 //                dL/d(Bottleneck5_1 output) to HBM (neither the logits nor dL/dlogit reach HBM)
+//   k_tb_head<K, true>  (profiled as k_tb_head_semi) the same with the semi-supervised targets and the training metrics in
+//                the kernel: an unlabelled image is trained on its own pseudo annotation, the
+//                tile's pixels are counted into the confusion matrix; as a target-only launch it writes the packed pseudo
+//                targets of the undistorted frame instead
 //   k_tb_block   Bottleneck5_1's forward again and its backward: per-workgroup partials of the 13 block gradients
 //   k_tb_finish  fixed-order fold of the partials, times 1 / sum(mask); the float64 loss
 // Semantics: enet_modules.py:526-599 in inference mode (moving statistics are constants, no dropout), Final's transposed
 // convolution, tensortools/losses.py:3-74.  PReLU is relu(x) - alpha relu(-x) (extra_ops.py:9-26):
 // at x == 0 TensorFlow's ReluGrad gives 0 on both branches, so d/dx = 0 and d/dalpha = 0 there.  No floating-point atomics:
 // two runs give the same bits.
+#include "ssal_confusion.h"
 #include "ssal_internal.h"
 #include "ssal_prof.h"
 #include "ssal_score.h"
 #include "ssal_train_block.h"
 #include "ssal_xent.h"
+#include <type_traits>
 
 namespace ssal {
 
@@ -155,12 +161,37 @@ __global__ __launch_bounds__(512) void k_tb_fold(const float *__restrict__ param
 //         the taps of quad q, one thread per 4 x 4 (class, channel) block, accumulators in registers across tiles, images
 //     (c) dL/dx[p][c] += sum_k gl[p'][k] * wk[tap][k][c] over the (pixel, tap) pairs of quad q that read pixel p
 //   then dL/dx of the tile's pixels -> dy.
-template <int K>
+//
+// SEMI: sa.labelled[n] == 0 replaces the label / mask of image n, which are then never read, by the
+// pseudo annotation of active_learning.py:229-275 -- (conf, lab) = pixel_score (ssal_score.h, the code of k_final_score) of
+// the logits the thread holds, mask = conf < threshold ? 0 : 1 (NaN -> 1) -- for the tile's own pixels and the 33 second-pass
+// pixels alike.  The targets are constants (tf.stop_gradient, :233): nothing else in (a), (b), (c) changes.  With sa.tgt_in
+// the targets of an unlabelled image come from that plane instead (a byte per output pixel: the label in bits 0..6, the mask
+// in bit 7), which a TARGET-ONLY launch (sa.tgt_out, x5 = the undistorted frame's features) wrote: P, C and the logits of
+// the own pixels of the unlabelled images, nothing else -- no gradient, no partials, no sums.  sa.rep: every OWN pixel adds
+// (int)mask at [label][first maximum of the TRAINING logits] of a u32 LDS histogram (ssal_confusion.h), flushed into
+// replica (workgroup % reps) at the end; a second-pass pixel is another tile's own pixel and is counted there.
+// sa.pseudo_pixels[n] += the image's own pixels with pseudo mask 1 (one integer atomic per wave, tile and unlabelled image).
+struct TbHeadSemi {
+    const uint8_t *labelled;    // [N], NULL = all labelled
+    int measure;
+    float threshold;
+    const uint8_t *tgt_in;      // [N,2H,2W] packed pseudo targets of the undistorted frames, NULL = from the training logits
+    uint8_t *tgt_out;           // non-NULL: the target-only launch
+    unsigned long long *rep;    // confusion replicas, NULL = no metrics
+    int reps;
+    unsigned long long *pseudo_pixels;  // [N] (zeroed by the launcher), NULL = not counted
+};
+
+struct TbHeadPlain {};  // SEMI = false: no argument
+
+template <int K, bool SEMI>
 __global__ __launch_bounds__(256) void k_tb_head(const float *__restrict__ x5, int N, int H, int W,
                                                  const float *__restrict__ fold, const float *__restrict__ wk,
                                                  const uint8_t *__restrict__ labels, const float *__restrict__ mask,
                                                  float weight, float on_value, float off_value, float *__restrict__ dy,
-                                                 float *__restrict__ part, double *__restrict__ lpart)
+                                                 float *__restrict__ part, double *__restrict__ lpart,
+                                                 std::conditional_t<SEMI, TbHeadSemi, TbHeadPlain> sa)
 {
     constexpr int K4 = (K + 3) / 4 * 4, KB = K4 / 4;
     constexpr int NB = 9 * KB * 4, BPT = (NB + 255) / 256;
@@ -168,6 +199,7 @@ __global__ __launch_bounds__(256) void k_tb_head(const float *__restrict__ x5, i
     __shared__ __attribute__((aligned(16))) float p1[TB_PW * TB_PW * 4];
     __shared__ __attribute__((aligned(16))) float tile[TB_AW * TB_AW * 16];
     __shared__ __attribute__((aligned(16))) float gl[TB_GW * TB_GW * K4];
+    __shared__ unsigned hist[SEMI ? K * K : 1];  // (never referenced, so not allocated, without SEMI)
     const int tid = threadIdx.x;
     const int tiles_x = (W + TB_T - 1) / TB_T, tiles = tiles_x * ((H + TB_T - 1) / TB_T);
     const int ti = tid / TB_T, tj = tid % TB_T;
@@ -182,11 +214,23 @@ __global__ __launch_bounds__(256) void k_tb_head(const float *__restrict__ x5, i
     double loss = 0.0, msum = 0.0;
     float wc = 1.0f, dwc_cw = 0.0f;
     const float cw = kXentEuler - weight;
+    bool tgt_only = false;
+    if constexpr (SEMI) {
+        tgt_only = sa.tgt_out != nullptr;
+        if (sa.rep) hist_zero(hist, K * K);  // (ordered before the first add by the barriers of the first image)
+    }
     for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
         const int i0 = (t / tiles_x) * TB_T, j0 = (t % tiles_x) * TB_T;
         const bool valid = i0 + ti < H && j0 + tj < W;
         float bsum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         for (int n = 0; n < N; ++n) {
+            // SEMI: image n is pseudo-annotated (workgroup-uniform)
+            bool pseudo = false;
+            int npseudo = 0;
+            if constexpr (SEMI) {
+                pseudo = sa.labelled && sa.labelled[n] == 0;
+                if (tgt_only && !pseudo) continue;  // a labelled image needs no pseudo targets
+            }
             const float *xn = x5 + (long)n * HW * 16;
             __syncthreads();  // the previous image is done with p1 / tile / gl
             tb_phase_p(xn, H, W, i0, j0, fold, p1);
@@ -214,7 +258,7 @@ __global__ __launch_bounds__(256) void k_tb_head(const float *__restrict__ x5, i
                 // ---- (a)
 #pragma unroll 1
                 for (int ps = 0; ps < 2; ++ps) {
-                    if (ps == 1 && tid >= 2 * TB_T + 1) break;
+                    if (ps == 1 && (tid >= 2 * TB_T + 1 || tgt_only)) break;
                     const int gi = ps ? hi : ti, gj = ps ? hj : tj;
                     const bool own = ps == 0;
                     // a pixel below / right of the tile: only the quads that read a pixel of the tile
@@ -245,8 +289,39 @@ __global__ __launch_bounds__(256) void k_tb_head(const float *__restrict__ x5, i
                         else if (q == 2) { tap(la, 1, 0); tap(lc, 1, 2); }
                         else { tap(la, 1, 1); }
                         const long op = ((long)n * Ho + 2 * i + (q >> 1)) * Wo + 2 * j + (q & 1);
-                        const int lab = labels[op];
-                        const float mk = mask[op];
+                        int lab;
+                        float mk;
+                        if constexpr (SEMI) {
+                            if (tgt_only) {
+                                const float conf = pixel_score<K>(xl, sa.measure, 1.0f / __logf((float)K), lab);
+                                sa.tgt_out[op] = (uint8_t)((unsigned)lab | (conf < sa.threshold ? 0u : 0x80u));
+                                continue;
+                            }
+                            if (pseudo) {
+                                if (sa.tgt_in) {
+                                    const unsigned b = sa.tgt_in[op];
+                                    lab = (int)(b & 0x7Fu);
+                                    mk = (b & 0x80u) ? 1.0f : 0.0f;
+                                } else {
+                                    mk = pixel_score<K>(xl, sa.measure, 1.0f / __logf((float)K), lab) < sa.threshold ? 0.0f : 1.0f;
+                                }
+                                if (own) npseudo += mk != 0.0f;
+                            } else {
+                                lab = labels[op];
+                                mk = mask[op];
+                            }
+                            if (sa.rep && own) {  // train_pred = tf.math.argmax(train_logits): the first maximum
+                                float pm = xl[0];
+                                int pred = 0;
+#pragma unroll
+                                for (int k = 1; k < K; ++k)
+                                    if (xl[k] > pm) { pm = xl[k]; pred = k; }
+                                hist_add_wave(hist, (unsigned)lab * K + (unsigned)pred, (unsigned)(int)mk, K * K);
+                            }
+                        } else {
+                            lab = labels[op];
+                            mk = mask[op];
+                        }
                         const XentPix r = xent_pixel<K>(xl, lab, mk, weight, on_value, off_value);
                         if (own) {
                             bsum[q] += r.ce;
@@ -272,6 +347,9 @@ __global__ __launch_bounds__(256) void k_tb_head(const float *__restrict__ x5, i
 #pragma unroll
                         for (int k = 0; k < K4; ++k) gq[k] = 0.0f;
                     }
+                }
+                if constexpr (SEMI) {
+                    if (tgt_only) continue;  // (workgroup-uniform: no barrier is skipped by a part of the workgroup)
                 }
                 __syncthreads();
                 // ---- (b)
@@ -319,6 +397,14 @@ __global__ __launch_bounds__(256) void k_tb_head(const float *__restrict__ x5, i
                 }
                 __syncthreads();
             }
+            if constexpr (SEMI) {
+                if (tgt_only) continue;
+                if (pseudo && sa.pseudo_pixels) {
+#pragma unroll
+                    for (int off = 32; off > 0; off >>= 1) npseudo += __shfl_down(npseudo, off, 64);
+                    if ((tid & 63) == 0 && npseudo) atomicAdd(sa.pseudo_pixels + n, (unsigned long long)npseudo);
+                }
+            }
             if (valid) {
                 float4 *o = reinterpret_cast<float4 *>(dy + (((long)n * H + i0 + ti) * W + j0 + tj) * 16);
 #pragma unroll
@@ -328,6 +414,9 @@ __global__ __launch_bounds__(256) void k_tb_head(const float *__restrict__ x5, i
         if (valid)
 #pragma unroll
             for (int q = 0; q < 4; ++q) loss += (double)bsum[q];
+    }
+    if constexpr (SEMI) {
+        if (tgt_only) return;
     }
     float *pw = part + (long)blockIdx.x * (9 * K * 16);
 #pragma unroll
@@ -350,6 +439,12 @@ __global__ __launch_bounds__(256) void k_tb_head(const float *__restrict__ x5, i
     if (tid == 0) {
         lpart[2 * (long)blockIdx.x] = r0;
         lpart[2 * (long)blockIdx.x + 1] = r1;
+    }
+    if constexpr (SEMI) {
+        if (sa.rep) {
+            __syncthreads();
+            hist_flush(hist, K * K, sa.rep + (long)conf_rep_stride(K * K) * (blockIdx.x % sa.reps));
+        }
     }
 }
 
@@ -606,29 +701,23 @@ __global__ __launch_bounds__(256) void k_tb_finish(const float *__restrict__ par
     grad[o] = (o >= TB_TRAINED && o < TB_FINAL) ? 0.0f : acc * scale;
 }
 
-hipError_t launch_train_block_grad(const float *x5, int N, int H, int W, int K, const float *params, const uint8_t *labels,
-                                   const float *mask, float weight, float label_smoothing, const TrainBlockWs &ws,
-                                   double *loss, float *grad, hipStream_t s, float *dx, int max_workgroups)
+// the head launch: plain (semi NULL), semi-supervised, or the target-only launch (tgt_out non-NULL: x5 = the undistorted
+// frame's features; nothing but tgt_out is written)
+static hipError_t launch_tb_head(const float *x5, int N, int H, int W, int K, int G, const float *params, const uint8_t *labels,
+                                 const float *mask, float weight, float label_smoothing, const TrainBlockWs &ws,
+                                 const TrainBlockSemi *semi, uint8_t *tgt_out, hipStream_t s)
 {
-    if (N < 1 || K < 2 || K > 32 || !train_block_fits(H, W)) return hipErrorInvalidValue;
-    int G = train_block_workgroups(H, W);
-    if (max_workgroups > 0 && max_workgroups < G) G = max_workgroups;
     const float on_value = 1.0f - label_smoothing, off_value = label_smoothing / ((float)K - 1.0f);
     const double pix = (double)N * H * W;
     const float *wk = params + TB_FINAL;
-    hipLaunchKernelGGL(k_tb_fold, dim3(1), dim3(512), 0, s, params, ws.fold);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(ws.part_b, 0, (size_t)G * TB_ROWS * TB_TRAINED * sizeof(float), s);
-    if (e != hipSuccess) return e;
-    {
+    if (!semi) {
         // logits, the Final.kernel contraction and the input gradient: 144 K FMAs per feature pixel each; the block: 272
         ProfScope prof("k_tb_head", 2.0 * pix * (3.0 * 144 * K + 272.0 * 1.6),
                        4.0 * pix * 16 * 2 + 4.0 * pix * (1 + 4) + 4.0 * G * 9.0 * 16 * K, s);
 #define SSAL_TB(KK)                                                                                                    \
     case KK:                                                                                                           \
-        hipLaunchKernelGGL((k_tb_head<KK>), dim3(G), dim3(256), 0, s, x5, N, H, W, ws.fold, wk, labels, mask, weight,  \
-                           on_value, off_value, ws.dy, ws.part_f, ws.lpart);                                           \
+        hipLaunchKernelGGL((k_tb_head<KK, false>), dim3(G), dim3(256), 0, s, x5, N, H, W, ws.fold, wk, labels, mask,   \
+                           weight, on_value, off_value, ws.dy, ws.part_f, ws.lpart, TbHeadPlain{});                    \
         break;
         switch (K) {
             SSAL_TB(2) SSAL_TB(3) SSAL_TB(4) SSAL_TB(5) SSAL_TB(6) SSAL_TB(7) SSAL_TB(8) SSAL_TB(9)
@@ -640,9 +729,80 @@ hipError_t launch_train_block_grad(const float *x5, int N, int H, int W, int K, 
             return hipErrorInvalidValue;
         }
 #undef SSAL_TB
-        e = hipGetLastError();
+        return hipGetLastError();
+    }
+    TbHeadSemi sa;
+    sa.labelled = semi->labelled;
+    sa.measure = semi->measure;
+    sa.threshold = semi->threshold;
+    sa.tgt_in = tgt_out ? nullptr : (semi->use_tgt ? semi->tgt : nullptr);
+    sa.tgt_out = tgt_out;
+    sa.rep = tgt_out ? nullptr : semi->rep;
+    sa.reps = semi->reps;
+    sa.pseudo_pixels = tgt_out ? nullptr : (unsigned long long *)semi->pseudo_pixels;
+    // the target-only launch: the block and the logits (the own pixels of the unlabelled images; counted for all)
+    ProfScope prof(tgt_out ? "k_tb_head_targets" : "k_tb_head_semi",
+                   tgt_out ? 2.0 * pix * (144.0 * K + 272.0 * 1.6) : 2.0 * pix * (3.0 * 144 * K + 272.0 * 1.6),
+                   tgt_out ? 4.0 * pix * 16 * 2 + 4.0 * pix
+                           : 4.0 * pix * 16 * 2 + 4.0 * pix * (1 + 4) + 4.0 * G * 9.0 * 16 * K, s);
+#define SSAL_TB(KK)                                                                                                    \
+    case KK:                                                                                                           \
+        hipLaunchKernelGGL((k_tb_head<KK, true>), dim3(G), dim3(256), 0, s, x5, N, H, W, ws.fold, wk, labels, mask,    \
+                           weight, on_value, off_value, ws.dy, ws.part_f, ws.lpart, sa);                               \
+        break;
+    switch (K) {
+        SSAL_TB(2) SSAL_TB(3) SSAL_TB(4) SSAL_TB(5) SSAL_TB(6) SSAL_TB(7) SSAL_TB(8) SSAL_TB(9)
+        SSAL_TB(10) SSAL_TB(11) SSAL_TB(12) SSAL_TB(13) SSAL_TB(14) SSAL_TB(15) SSAL_TB(16)
+        SSAL_TB(17) SSAL_TB(18) SSAL_TB(19) SSAL_TB(20) SSAL_TB(21) SSAL_TB(22) SSAL_TB(23)
+        SSAL_TB(24) SSAL_TB(25) SSAL_TB(26) SSAL_TB(27) SSAL_TB(28) SSAL_TB(29) SSAL_TB(30)
+        SSAL_TB(31) SSAL_TB(32)
+    default:
+        return hipErrorInvalidValue;
+    }
+#undef SSAL_TB
+    return hipGetLastError();
+}
+
+static bool train_block_semi_ok(const TrainBlockSemi *semi)
+{
+    return !semi || (semi->measure >= 0 && semi->measure <= 2 && (!semi->rep || semi->reps >= 1));
+}
+
+hipError_t launch_train_block_targets(const float *x5_raw, int N, int H, int W, int K, const float *params,
+                                      const TrainBlockSemi &semi, const TrainBlockWs &ws, hipStream_t s, int max_workgroups)
+{
+    if (N < 1 || K < 2 || K > 32 || !train_block_fits(H, W) || !train_block_semi_ok(&semi) || !semi.tgt || !x5_raw)
+        return hipErrorInvalidValue;
+    if (!semi.labelled) return hipSuccess;  // every image is labelled: no pseudo target is read
+    int G = train_block_workgroups(H, W);
+    if (max_workgroups > 0 && max_workgroups < G) G = max_workgroups;
+    hipLaunchKernelGGL(k_tb_fold, dim3(1), dim3(512), 0, s, params, ws.fold);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_tb_head(x5_raw, N, H, W, K, G, params, nullptr, nullptr, 0.0f, 0.0f, ws, &semi, semi.tgt, s);
+}
+
+hipError_t launch_train_block_grad(const float *x5, int N, int H, int W, int K, const float *params, const uint8_t *labels,
+                                   const float *mask, float weight, float label_smoothing, const TrainBlockWs &ws,
+                                   double *loss, float *grad, hipStream_t s, float *dx, int max_workgroups,
+                                   const TrainBlockSemi *semi)
+{
+    if (N < 1 || K < 2 || K > 32 || !train_block_fits(H, W) || !train_block_semi_ok(semi)) return hipErrorInvalidValue;
+    int G = train_block_workgroups(H, W);
+    if (max_workgroups > 0 && max_workgroups < G) G = max_workgroups;
+    const double pix = (double)N * H * W;
+    hipError_t e;
+    if (semi && semi->pseudo_pixels) {
+        e = hipMemsetAsync(semi->pseudo_pixels, 0, (size_t)N * sizeof(int64_t), s);
         if (e != hipSuccess) return e;
     }
+    hipLaunchKernelGGL(k_tb_fold, dim3(1), dim3(512), 0, s, params, ws.fold);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(ws.part_b, 0, (size_t)G * TB_ROWS * TB_TRAINED * sizeof(float), s);
+    if (e != hipSuccess) return e;
+    e = launch_tb_head(x5, N, H, W, K, G, params, labels, mask, weight, label_smoothing, ws, semi, nullptr, s);
+    if (e != hipSuccess) return e;
     {
         ProfScope prof("k_tb_block", 2.0 * pix * (272.0 * 1.6 + 272.0 * 2 + 64.0), 4.0 * pix * 16 * 2 + 4.0 * G * TB_ROWS * TB_TRAINED, s);
         if (dx) hipLaunchKernelGGL(k_tb_block<true>, dim3(G), dim3(256), 0, s, x5, ws.dy, N, H, W, ws.fold, ws.part_b, dx);

@@ -59,6 +59,14 @@ struct TrainStageWs {
 // train_stage_floats(K) floats; labels uint8 / mask fp32 [N,4H,4W]; loss one double.
 hipError_t launch_train_stage_grad(const float *x4, const int64_t *argmax, int N, int H, int W, int K, const float *params,
                                    const uint8_t *labels, const float *mask, float weight, float label_smoothing,
-                                   int max_workgroups, const TrainStageWs &ws, double *loss, float *grad, hipStream_t s);
+                                   int max_workgroups, const TrainStageWs &ws, double *loss, float *grad, hipStream_t s,
+                                   const TrainBlockSemi *semi = nullptr);
+
+// The semi-supervised step with undistorted frames (semi as in ssal_train_block.h, on the [2H, 2W] map): x4_raw [N,H,W,64]
+// and argmax_raw (NULL: ws.code already holds the raw frame's window codes) -> the packed pseudo targets semi.tgt
+// [N,4H,4W].  Uses ws.code, ws.a5, ws.sfold and ws.tb.fold, all of which launch_train_stage_grad writes again afterwards.
+hipError_t launch_train_stage_targets(const float *x4_raw, const int64_t *argmax_raw, int N, int H, int W, int K,
+                                      const float *params, int max_workgroups, const TrainStageWs &ws,
+                                      const TrainBlockSemi &semi, hipStream_t s);
 
 }  // namespace ssal

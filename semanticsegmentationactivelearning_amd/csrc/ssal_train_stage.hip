@@ -441,7 +441,8 @@ __global__ __launch_bounds__(256) void k_ts_finish(const float *__restrict__ par
 
 hipError_t launch_train_stage_grad(const float *x4, const int64_t *argmax, int N, int H, int W, int K, const float *params,
                                    const uint8_t *labels, const float *mask, float weight, float label_smoothing,
-                                   int max_workgroups, const TrainStageWs &ws, double *loss, float *grad, hipStream_t s)
+                                   int max_workgroups, const TrainStageWs &ws, double *loss, float *grad, hipStream_t s,
+                                   const TrainBlockSemi *semi)
 {
     if (N < 1 || K < 2 || K > 32 || !train_stage_fits(H, W)) return hipErrorInvalidValue;
     const int G = train_stage_workgroups(H, W, max_workgroups);
@@ -459,7 +460,7 @@ hipError_t launch_train_stage_grad(const float *x4, const int64_t *argmax, int N
                              F + TF_CT, P + TS_CA, P + TS_WE, F + TF_ES, F + TF_ET, P + TS_WR, P + TS_RA, s);
     if (e != hipSuccess) return e;
     e = launch_train_block_grad(ws.a5, N, 2 * H, 2 * W, K, params, labels, mask, weight, label_smoothing, ws.tb, loss, grad, s,
-                                ws.dx, G);
+                                ws.dx, G, semi);
     if (e != hipSuccess) return e;
     const double qpix = (double)N * H * W;
     {
@@ -476,6 +477,31 @@ hipError_t launch_train_stage_grad(const float *x4, const int64_t *argmax, int N
     hipLaunchKernelGGL(k_ts_finish, dim3((TS_FLOATS + 255) / 256), dim3(256), 0, s, ws.part_s, ws.tb.lpart, G,
                        grad + train_block_floats(K));
     return hipGetLastError();
+}
+
+// The pseudo targets of the undistorted frames: their window codes and Bottleneck5_0 through the
+// scoring path's kernel into ws.code / ws.a5 (which the training call overwrites afterwards, in stream order), then the
+// target-only launch of the head kernel -> semi.tgt.
+hipError_t launch_train_stage_targets(const float *x4_raw, const int64_t *argmax_raw, int N, int H, int W, int K,
+                                      const float *params, int max_workgroups, const TrainStageWs &ws,
+                                      const TrainBlockSemi &semi, hipStream_t s)
+{
+    if (N < 1 || K < 2 || K > 32 || !train_stage_fits(H, W) || !x4_raw) return hipErrorInvalidValue;
+    if (!semi.labelled) return hipSuccess;  // every image is labelled: no pseudo target is read
+    const int G = train_stage_workgroups(H, W, max_workgroups);
+    const float *P = params + train_block_floats(K), *F = ws.sfold;
+    hipError_t e;
+    if (argmax_raw) {
+        e = launch_argmax_to_codes(argmax_raw, N, H, W, 16, ws.code, ws.bad, s);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_ts_fold, dim3(1), dim3(256), 0, s, P, ws.sfold);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = launch_upsample_mfma(x4_raw, ws.a5, ws.code, N, H, W, 64, P + TS_WP, F + TF_PS, F + TF_PT, P + TS_PA, F + TF_WS, F + TF_CS,
+                             F + TF_CT, P + TS_CA, P + TS_WE, F + TF_ES, F + TF_ET, P + TS_WR, P + TS_RA, s);
+    if (e != hipSuccess) return e;
+    return launch_train_block_targets(ws.a5, N, 2 * H, 2 * W, K, params, semi, ws.tb, s, G);
 }
 
 }  // namespace ssal

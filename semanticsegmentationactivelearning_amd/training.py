@@ -851,4 +851,226 @@ class LastStageTrainer(LastBlockTrainer):
         return loss[0]
 
 
-__all__ = ["FinalLayerTrainer", "LastBlockTrainer", "LastStageTrainer"]
+# ---- the semi-supervised step of the two deeper trainers ---------------------------------------------
+class _DeepSemiMixin:
+    """The semi-supervised keywords of ``FinalLayerTrainer`` (``labelled``, ``measure``, ``threshold``, ``features_raw`` /
+    ``images_raw``, ``confusion``, ``return_pseudo_pixels``; meaning, defaults and validation are its ``_semi`` /
+    ``_semi_device``) on ``LastBlockTrainer`` / ``LastStageTrainer``: the head kernel builds the targets of an unlabelled
+    image from the logits it holds (or reads the packed targets a target-only launch wrote from the undistorted frame),
+    counts the tile's pixels into the confusion matrix and the pseudo pixels per image.  With none of the keywords given
+    a call goes through the parent class's plain entry exactly as before."""
+
+    _deep_stage = False  # True: the inputs are Bottleneck4_2's output + argmax1 (LastStageTrainer)
+
+    def _packed_with(self, params):
+        """the packed block of the host variables with ``params`` (name -> array) laid over it"""
+        params = dict(params or {})
+        if self._deep_stage:
+            params = self._check_params(params)
+        else:
+            unknown = set(params) - set(self.variable_names)
+            if unknown:
+                raise ValueError("unknown variables %s (the moving statistics always come from the model)" % sorted(unknown))
+        packed = self._pack()
+        for name, var, off, _ in self._named():
+            if name in params:
+                a = params[name]
+                a = np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a, dtype=np.float32)
+                if a.shape != var.shape:
+                    raise ValueError("%s must have shape %s (got %s)" % (name, var.shape, a.shape))
+                packed[off:off + a.size] = a.reshape(-1)
+        return packed
+
+    @staticmethod
+    def _batch(t):
+        return int(np.shape(t)[0]) if len(np.shape(t)) else 0
+
+    def _raw_host(self, features, features_raw, argmax1=None, argmax1_raw=None):
+        """(raw features or None, checked raw argmax or None), judged on the host before any device work"""
+        if self._deep_stage and (features_raw is None) != (argmax1_raw is None):
+            raise ValueError("features_raw and argmax1_raw are given together or not at all (the undistorted frame's "
+                             "pooling indices are its own)")
+        if features_raw is None or (features_raw is features and (argmax1_raw is None or argmax1_raw is argmax1)):
+            return None, None
+        if tuple(np.shape(features_raw)) != tuple(np.shape(features)):
+            raise ValueError("features_raw must have the shape of the features %s (got %s)"
+                             % (tuple(np.shape(features)), tuple(np.shape(features_raw))))
+        return features_raw, (self._check_argmax(np.shape(features_raw), argmax1_raw) if self._deep_stage else None)
+
+    def _semi_grad_packed(self, x, argmax, xr, argmax_raw, labels, mask, params_dev, semi, confusion, return_pseudo_pixels,
+                          max_workgroups=0):
+        """(loss, packed gradient, pseudo pixels or None) through the features entry of the C ABI"""
+        torch = _lib.require_gpu()
+        c = 64 if self._deep_stage else 16
+        if x.dim() != 4 or x.shape[-1] != c:
+            raise ValueError("features must be [N,h,w,%d] (got %s)" % (c, tuple(x.shape)))
+        n, h, w, _ = x.shape
+        k = int(self.net.classes)
+        up = 4 if self._deep_stage else 2
+        lbd, lab, mk = self._semi_device(semi, n, x.device, labels, mask, (n, up * h, up * w))
+        L = _lib.lib()
+        with torch.cuda.device(x.device):
+            query = L.ssal_train_stage_grad_semi_workspace_bytes if self._deep_stage else L.ssal_train_block_grad_semi_workspace_bytes
+            nbytes = query(n, h, w, k, int(xr is not None))
+            if nbytes < 0:
+                raise ValueError("feature map %dx%d is beyond the gradient kernels' limit" % (h, w))
+            ws = torch.empty(int(nbytes), dtype=torch.uint8, device=x.device)
+            loss = torch.empty((1,), dtype=torch.float64, device=x.device)
+            grad = torch.empty(self._floats(), dtype=torch.float32, device=x.device)
+            pp = torch.empty((n,), dtype=torch.int64, device=x.device) if return_pseudo_pixels else None
+            conf = _lib.dev_ptr(confusion, torch.int64, "confusion")
+            if self._deep_stage:
+                am = argmax.to(device=x.device).contiguous()
+                amr = argmax_raw.to(device=x.device).contiguous() if argmax_raw is not None else None
+                _lib.check(L.ssal_train_stage_grad_semi_nhwc(
+                    _lib.dev_ptr(x), _lib.dev_ptr(am), _lib.dev_ptr(xr), _lib.dev_ptr(amr), n, h, w, k,
+                    _lib.dev_ptr(params_dev), _lib.dev_ptr(lab), _lib.dev_ptr(mk), _lib.dev_ptr(lbd), semi[1], semi[2],
+                    self.weight, self.label_smoothing, max_workgroups, _lib.dev_ptr(loss), _lib.dev_ptr(grad), conf,
+                    _lib.dev_ptr(pp), _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))
+            else:
+                _lib.check(L.ssal_train_block_grad_semi_nhwc(
+                    _lib.dev_ptr(x), _lib.dev_ptr(xr), n, h, w, k, _lib.dev_ptr(params_dev), _lib.dev_ptr(lab),
+                    _lib.dev_ptr(mk), _lib.dev_ptr(lbd), semi[1], semi[2], self.weight, self.label_smoothing,
+                    _lib.dev_ptr(loss), _lib.dev_ptr(grad), conf, _lib.dev_ptr(pp), _lib.dev_ptr(ws), ws.numel(),
+                    _lib.stream_ptr()))
+        return loss, grad, pp
+
+    def _semi_step_images(self, images, labels, mask, semi, images_raw, confusion, return_pseudo_pixels, max_workgroups=0):
+        torch = _lib.require_gpu()
+        net = self.net
+        x = net._prepare(images, False)
+        n, h, w, _ = x.shape
+        L = _lib.lib()
+        lbd, lab, mk = self._semi_device(semi, n, x.device, labels, mask, (n, h, w))
+        xr = None
+        if images_raw is not None and images_raw is not images:
+            xr = net._prepare(images_raw, False)
+            if tuple(xr.shape) != tuple(x.shape) or xr.dtype != x.dtype or xr.device != x.device:
+                raise ValueError("images_raw must have the shape and dtype of images %s %s (got %s %s)"
+                                 % (tuple(x.shape), x.dtype, tuple(xr.shape), xr.dtype))
+        with torch.cuda.device(x.device):
+            dev = self._device_state(x.device)
+            handle = self._trunk_handle()
+            query = L.ssal_enet_train_stage_semi_workspace_bytes if self._deep_stage else L.ssal_enet_train_block_semi_workspace_bytes
+            nbytes = query(handle, n, h, w, int(xr is not None))
+            if nbytes < 0:
+                raise ValueError("bad input dims %s" % (tuple(x.shape),))
+            ws = net._workspace(nbytes, x.device)
+            loss = torch.empty((1,), dtype=torch.float64, device=x.device)
+            pp = torch.empty((n,), dtype=torch.int64, device=x.device) if return_pseudo_pixels else None
+            head = (handle, _lib.dev_ptr(x), _lib.dev_ptr(xr), int(x.dtype == torch.uint8), n, h, w, _lib.dev_ptr(lab),
+                    _lib.dev_ptr(mk), _lib.dev_ptr(lbd), semi[1], semi[2], _lib.dev_ptr(dev["w"]), self.weight,
+                    self.label_smoothing)
+            tail = (_lib.dev_ptr(loss), _lib.dev_ptr(dev["grad"]), _lib.dev_ptr(confusion, torch.int64, "confusion"),
+                    _lib.dev_ptr(pp), _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr())
+            if self._deep_stage:
+                _lib.check(L.ssal_enet_train_stage_semi_nhwc(*(head + (max_workgroups,) + tail)))
+            else:
+                _lib.check(L.ssal_enet_train_block_semi_nhwc(*(head + tail)))
+            net._note_call(ws, (n, h, w), "train")
+            self._apply(dev, dev["grad"])
+        return (loss[0], pp) if return_pseudo_pixels else loss[0]
+
+
+class SemiSupervisedBlockTrainer(_DeepSemiMixin, LastBlockTrainer):
+    """``LastBlockTrainer`` with the reference's semi-supervised step (active_learning.py:226-275, 339-342) built into its
+    head kernel: ``gradient_features``, ``step_features`` and ``step`` accept ``labelled``, ``measure``, ``threshold``,
+    ``features_raw`` / ``images_raw``, ``confusion`` and ``return_pseudo_pixels`` with ``FinalLayerTrainer``'s meaning,
+    defaults and validation (the pseudo annotation is that of the logits under the variables being trained).  Loss and the
+    13 gradients are bit-identical to ``LastBlockTrainer`` on the composed targets.  ``state`` /
+    ``load_state`` are interchangeable with ``LastBlockTrainer``'s."""
+
+    def gradient_features(self, features5_0, labels, mask, params=None, labelled=None, measure=None, threshold=None,
+                          features_raw=None, confusion=None, return_pseudo_pixels=False):
+        semi = self._semi(self._batch(features5_0), labels, mask, labelled, measure, threshold, confusion,
+                          return_pseudo_pixels)
+        if semi is None:
+            return super().gradient_features(features5_0, labels, mask, params=params)
+        packed = self._packed_with(params)
+        xr, _ = self._raw_host(features5_0, features_raw)
+        x = _lib.as_device_f32(features5_0)
+        xr = None if xr is None else _lib.as_device_f32(xr).to(x.device)
+        torch = _lib.require_gpu()
+        loss, grad, pp = self._semi_grad_packed(x, None, xr, None, labels, mask, torch.from_numpy(packed).to(x.device),
+                                                semi, confusion, return_pseudo_pixels)
+        return (loss, self._grad_dict(grad), pp) if return_pseudo_pixels else (loss, self._grad_dict(grad))
+
+    def step_features(self, features5_0, labels, mask, labelled=None, measure=None, threshold=None, features_raw=None,
+                      confusion=None, return_pseudo_pixels=False):
+        semi = self._semi(self._batch(features5_0), labels, mask, labelled, measure, threshold, confusion,
+                          return_pseudo_pixels)
+        if semi is None:
+            return super().step_features(features5_0, labels, mask)
+        xr, _ = self._raw_host(features5_0, features_raw)
+        x = _lib.as_device_f32(features5_0)
+        xr = None if xr is None else _lib.as_device_f32(xr).to(x.device)
+        dev = self._device_state(x.device)
+        loss, grad, pp = self._semi_grad_packed(x, None, xr, None, labels, mask, dev["w"], semi, confusion,
+                                                return_pseudo_pixels)
+        self._apply(dev, grad)
+        return (loss[0], pp) if return_pseudo_pixels else loss[0]
+
+    def step(self, images, labels, mask, labelled=None, measure=None, threshold=None, images_raw=None, confusion=None,
+             return_pseudo_pixels=False):
+        semi = self._semi(self._batch(images), labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels)
+        if semi is None:
+            return super().step(images, labels, mask)
+        return self._semi_step_images(images, labels, mask, semi, images_raw, confusion, return_pseudo_pixels)
+
+
+class SemiSupervisedStageTrainer(_DeepSemiMixin, LastStageTrainer):
+    """``LastStageTrainer`` with the semi-supervised step built into the head kernel (see ``SemiSupervisedBlockTrainer``);
+    the undistorted frame's side of the feature entries is ``features_raw`` [N, h, w, 64] with its own pooling indices
+    ``argmax1_raw`` (what ``features(images_raw)`` returns).  Loss and the 26 gradients are bit-identical to
+    ``LastStageTrainer`` on the composed targets; ``state`` / ``load_state`` are interchangeable with its."""
+
+    _deep_stage = True
+
+    def gradient_features(self, features4_2, argmax1, labels, mask, params=None, max_workgroups=0, labelled=None,
+                          measure=None, threshold=None, features_raw=None, argmax1_raw=None, confusion=None,
+                          return_pseudo_pixels=False):
+        semi = self._semi(self._batch(features4_2), labels, mask, labelled, measure, threshold, confusion,
+                          return_pseudo_pixels)
+        if semi is None:
+            return super().gradient_features(features4_2, argmax1, labels, mask, params=params,
+                                             max_workgroups=max_workgroups)
+        max_workgroups = self._check_workgroups(max_workgroups)
+        am = self._check_argmax(np.shape(features4_2), argmax1)
+        packed = self._packed_with(params)
+        xr, amr = self._raw_host(features4_2, features_raw, argmax1, argmax1_raw)
+        x = _lib.as_device_f32(features4_2)
+        xr = None if xr is None else _lib.as_device_f32(xr).to(x.device)
+        torch = _lib.require_gpu()
+        loss, grad, pp = self._semi_grad_packed(x, am, xr, amr, labels, mask, torch.from_numpy(packed).to(x.device), semi,
+                                                confusion, return_pseudo_pixels, max_workgroups)
+        return (loss, self._grad_dict(grad), pp) if return_pseudo_pixels else (loss, self._grad_dict(grad))
+
+    def step_features(self, features4_2, argmax1, labels, mask, max_workgroups=0, labelled=None, measure=None,
+                      threshold=None, features_raw=None, argmax1_raw=None, confusion=None, return_pseudo_pixels=False):
+        semi = self._semi(self._batch(features4_2), labels, mask, labelled, measure, threshold, confusion,
+                          return_pseudo_pixels)
+        if semi is None:
+            return super().step_features(features4_2, argmax1, labels, mask, max_workgroups=max_workgroups)
+        max_workgroups = self._check_workgroups(max_workgroups)
+        am = self._check_argmax(np.shape(features4_2), argmax1)
+        xr, amr = self._raw_host(features4_2, features_raw, argmax1, argmax1_raw)
+        x = _lib.as_device_f32(features4_2)
+        xr = None if xr is None else _lib.as_device_f32(xr).to(x.device)
+        dev = self._device_state(x.device)
+        loss, grad, pp = self._semi_grad_packed(x, am, xr, amr, labels, mask, dev["w"], semi, confusion,
+                                                return_pseudo_pixels, max_workgroups)
+        self._apply(dev, grad)
+        return (loss[0], pp) if return_pseudo_pixels else loss[0]
+
+    def step(self, images, labels, mask, max_workgroups=0, labelled=None, measure=None, threshold=None, images_raw=None,
+             confusion=None, return_pseudo_pixels=False):
+        semi = self._semi(self._batch(images), labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels)
+        if semi is None:
+            return super().step(images, labels, mask, max_workgroups=max_workgroups)
+        max_workgroups = self._check_workgroups(max_workgroups)
+        return self._semi_step_images(images, labels, mask, semi, images_raw, confusion, return_pseudo_pixels,
+                                      max_workgroups)
+
+
+__all__ = ["FinalLayerTrainer", "LastBlockTrainer", "LastStageTrainer", "SemiSupervisedBlockTrainer",
+           "SemiSupervisedStageTrainer"]

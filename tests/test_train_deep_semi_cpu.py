@@ -1,0 +1,204 @@
+"""The semi-supervised step of the last-block and last-stage trainers without a GPU: the ABI symbols and
+their ctypes signatures, the host-only workspace queries and their limits, the statuses given before a device is touched, the
+keyword validation of the two new classes, and the two parent classes' refusal, which stays."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import semanticsegmentationactivelearning_amd as ssal
+from semanticsegmentationactivelearning_amd import _lib, training
+from semanticsegmentationactivelearning_amd.training import (FinalLayerTrainer, LastBlockTrainer, LastStageTrainer,
+                                                             SemiSupervisedBlockTrainer, SemiSupervisedStageTrainer)
+
+import last_stage_train_oracle as lso
+
+SYMBOLS = ("ssal_train_block_grad_semi_workspace_bytes", "ssal_train_block_grad_semi_nhwc",
+           "ssal_enet_train_block_semi_workspace_bytes", "ssal_enet_train_block_semi_nhwc",
+           "ssal_train_stage_grad_semi_workspace_bytes", "ssal_train_stage_grad_semi_nhwc",
+           "ssal_enet_train_stage_semi_workspace_bytes", "ssal_enet_train_stage_semi_nhwc")
+AL_PARAMS = {"hyperparams": {"learning_rate": 0.0005, "learning_rate_decay": 0.0,
+                             "optimizer": {"type": "Adam", "kwargs": {"beta1": 0.9, "beta2": 0.99}},
+                             "weight_reg": {"L2": 0.0002, "L1": 0.0},
+                             "softmax": {"label_smoothing": 0.0, "loginverse_scaling": 1.02, "multiscale": False}},
+             "active_learning": {"measure": "margin", "threshold": 0.25}}
+
+
+def _net(k=19):
+    net = ssal.ENet(k)
+    net.build((None, None, None, 3))
+    return net
+
+
+def test_abi_symbols_and_signatures():
+    """fails on a library without the entries of section 19"""
+    L = _lib.lib()
+    vp, i, i64, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
+    for sym in SYMBOLS:
+        assert hasattr(L, sym), sym
+    for sym in SYMBOLS[0::2]:
+        assert getattr(L, sym).restype is i64 and len(getattr(L, sym).argtypes) == 5, sym
+    # the argument order follows ssal_final_grad_semi_nhwc / ssal_enet_train_final_semi_nhwc: the plain entry's arguments with
+    # the raw input after the training input, (labelled, measure, threshold) after the mask, (confusion, pseudo_pixels)
+    # after the gradient
+    fin = list(L.ssal_final_grad_semi_nhwc.argtypes)
+    assert list(L.ssal_train_block_grad_semi_nhwc.argtypes) == fin
+    assert list(L.ssal_enet_train_block_semi_nhwc.argtypes) == list(L.ssal_enet_train_final_semi_nhwc.argtypes)
+    assert list(L.ssal_train_stage_grad_semi_nhwc.argtypes) == \
+        [vp, vp, vp, vp, i, i, i, i, vp, vp, vp, vp, i, f, f, f, i, vp, vp, vp, vp, vp, i64, vp]
+    assert list(L.ssal_enet_train_stage_semi_nhwc.argtypes) == \
+        [vp, vp, vp, i, i, i, i, vp, vp, vp, i, f, vp, f, f, i, vp, vp, vp, vp, vp, i64, vp]
+    # the plain entries keep their signatures
+    assert len(L.ssal_train_block_grad_nhwc.argtypes) == 15 and len(L.ssal_train_stage_grad_nhwc.argtypes) == 17
+    header = open(_lib.__file__.replace("semanticsegmentationactivelearning_amd/_lib.py", "include/ssal_enet.h")).read()
+    for sym in SYMBOLS:
+        assert sym + "(" in header, sym
+
+
+def test_workspace_queries_limits_and_with_raw():
+    """-1 exactly where the plain queries return -1; with_raw adds one byte per output pixel; the confusion replicas are in"""
+    L = _lib.lib()
+    for semi, plain, up in ((L.ssal_train_block_grad_semi_workspace_bytes, L.ssal_train_block_grad_workspace_bytes, 2),
+                            (L.ssal_train_stage_grad_semi_workspace_bytes, L.ssal_train_stage_grad_workspace_bytes, 4)):
+        cases = [(1, 64, 64, 1), (1, 64, 64, 2), (1, 64, 64, 32), (1, 64, 64, 33), (0, 64, 64, 19), (1, 0, 64, 19),
+                 (1, 64, -1, 19), (1, 4096, 8191, 19), (1, 4096, 8192, 19), (1, 1, (1 << 25) - 1, 19), (1, 1, 1 << 25, 19),
+                 (1, 1 << 29, 1, 19), (1, (1 << 30) - 1, 1, 19), (1, 1 << 30, 1, 19), (1, 1, (1 << 30) - 1, 2)]
+        for n, h, w, k in cases:
+            for raw in (0, 1):
+                assert (semi(n, h, w, k, raw) == -1) == (plain(n, h, w, k) == -1), (n, h, w, k, raw)
+                assert semi(n, h, w, k, raw) == -1 or semi(n, h, w, k, raw) > plain(n, h, w, k), (n, h, w, k, raw)
+        n, h, w, k = 2, 20, 34, 19
+        replicas = 64 * ((k * k + 15) // 16 * 16) * 8
+        assert semi(n, h, w, k, 0) - plain(n, h, w, k) >= replicas
+        grow = semi(n, h, w, k, 1) - semi(n, h, w, k, 0)
+        assert n * up * up * h * w <= grow <= n * up * up * h * w + 512, grow
+    for q in (L.ssal_enet_train_block_semi_workspace_bytes, L.ssal_enet_train_stage_semi_workspace_bytes):
+        assert q(None, 1, 64, 64, 0) == -1 and q(None, 1, 64, 64, 1) == -1
+
+
+def test_statuses_before_any_device_work():
+    """bad arguments are judged on the host: the pointers below are never dereferenced"""
+    L = _lib.lib()
+    p = ctypes.c_void_p(16)
+
+    def block(n=1, h=8, w=8, k=19, params=p, labels=p, labelled=p, measure=0, nbytes=1 << 24, raw=None):
+        return L.ssal_train_block_grad_semi_nhwc(p, raw, n, h, w, k, params, labels, p if labels else None, labelled, measure,
+                                                 0.5, 0.0, 0.0, p, p, None, None, p, nbytes, None)
+
+    def stage(n=1, h=8, w=8, k=19, params=p, labels=p, labelled=p, measure=0, nbytes=1 << 24, raw=None, araw=None, mw=0):
+        return L.ssal_train_stage_grad_semi_nhwc(p, p, raw, araw, n, h, w, k, params, labels, p if labels else None, labelled,
+                                                 measure, 0.5, 0.0, 0.0, mw, p, p, None, None, p, nbytes, None)
+
+    for call in (block, stage):
+        assert call(k=33) == _lib.SSAL_EINVAL and b"classes must be in [2,32]" in L.ssal_last_error()
+        assert call(k=1) == _lib.SSAL_EINVAL
+        assert call(n=0) == _lib.SSAL_EINVAL
+        assert call(h=1 << 30) == _lib.SSAL_EINVAL
+        assert call(measure=3) == _lib.SSAL_ENOTIMPL and b"Uncertainty function not implemented" in L.ssal_last_error()
+        assert call(measure=-1) == _lib.SSAL_ENOTIMPL
+        assert call(labels=None, labelled=None) == _lib.SSAL_EINVAL and b"may be NULL only" in L.ssal_last_error()
+        assert call(params=None) == _lib.SSAL_EINVAL and b"NULL device pointer" in L.ssal_last_error()
+        assert call(nbytes=16) == _lib.SSAL_ENOMEM and b"workspace too small" in L.ssal_last_error()
+    assert stage(mw=-1) == _lib.SSAL_EINVAL and b"max_workgroups" in L.ssal_last_error()
+    assert stage(raw=p) == _lib.SSAL_EINVAL and b"together" in L.ssal_last_error()
+    assert stage(araw=p) == _lib.SSAL_EINVAL
+    # the raw side needs the larger workspace
+    need0 = L.ssal_train_block_grad_semi_workspace_bytes(1, 8, 8, 19, 0)
+    assert block(raw=p, nbytes=need0) == _lib.SSAL_ENOMEM
+    for entry, extra in ((L.ssal_enet_train_block_semi_nhwc, ()), (L.ssal_enet_train_stage_semi_nhwc, (0,))):
+        rc = entry(None, p, None, 0, 1, 64, 64, p, p, p, 0, 0.5, p, 0.0, 0.0, *extra, p, p, None, None, p, 1 << 24, None)
+        assert rc == _lib.SSAL_EINVAL  # no handle
+
+
+def test_new_classes_are_exported_and_share_the_parents_state():
+    for name in ("SemiSupervisedBlockTrainer", "SemiSupervisedStageTrainer", "LastBlockTrainer", "LastStageTrainer"):
+        assert name in training.__all__
+    net = _net(6)
+    tb, ts = SemiSupervisedBlockTrainer(net, 1e-3), SemiSupervisedStageTrainer(net, 1e-3)
+    assert isinstance(tb, LastBlockTrainer) and not isinstance(tb, LastStageTrainer) and isinstance(ts, LastStageTrainer)
+    assert type(tb).__mro__[1] is type(ts).__mro__[1]  # one mixin
+    pb, ps = LastBlockTrainer(net, 1e-3), LastStageTrainer(net, 1e-3)
+    assert tb.variable_names == pb.variable_names and ts.variable_names == ps.variable_names
+    assert tb._floats() == pb._floats() and ts._floats() == ps._floats() and ts._adam_ranges() == ps._adam_ranges()
+    rng = np.random.default_rng(0)
+    for new, parent in ((tb, pb), (ts, ps)):
+        st = new.state
+        m = {n: rng.standard_normal(a.shape).astype(np.float32) for n, a in st["m"].items()}
+        v = {n: rng.uniform(size=a.shape).astype(np.float32) for n, a in st["v"].items()}
+        parent.load_state({"m": m, "v": v, "t": 3})
+        new.load_state(parent.state)
+        back = new.state
+        assert back["t"] == 3 and all(np.array_equal(back["m"][n], m[n]) and np.array_equal(back["v"][n], v[n]) for n in m)
+    # from_params: the active_learning section gives the defaults of the pseudo annotation, as for FinalLayerTrainer
+    for cls in (SemiSupervisedBlockTrainer, SemiSupervisedStageTrainer):
+        tr = cls.from_params(_net(), AL_PARAMS)
+        ref = FinalLayerTrainer.from_params(_net(), AL_PARAMS)
+        assert (tr.measure, tr.threshold) == (ref.measure, ref.threshold) == ("margin", 0.25)
+        assert (tr.learning_rate, tr.beta2, tr.l2, tr.weight) == (0.0005, 0.99, 0.0002, 1.02)
+        with pytest.raises(NotImplementedError):
+            cls(_net(), 1e-3, measure="bald")
+
+
+def _calls(tr, stage):
+    """the three methods as callables of the keyword dict, on host arrays (no device is reached when validation fails)"""
+    lab, mk = np.zeros((2, 16, 16), np.uint8), np.ones((2, 16, 16), np.float32)
+    if stage:
+        x = np.zeros((2, 4, 4, 64), np.float32)
+        am = lso.random_argmax(np.random.default_rng(0), 2, 4, 4)
+        feat = (x, am)
+    else:
+        feat = (np.zeros((2, 8, 8, 16), np.float32),)
+    img = np.zeros((2, 16, 16, 3), np.float32)
+    return feat, lab, mk, (lambda l, m, **kw: tr.gradient_features(*feat, l, m, **kw),
+                           lambda l, m, **kw: tr.step_features(*feat, l, m, **kw),
+                           lambda l, m, **kw: tr.step(img, l, m, **kw))
+
+
+@pytest.mark.parametrize("stage", (False, True), ids=("block", "stage"))
+def test_keyword_validation_of_the_new_classes(stage):
+    """FinalLayerTrainer's rules, judged on the host"""
+    tr = (SemiSupervisedStageTrainer if stage else SemiSupervisedBlockTrainer)(_net(), 1e-3)
+    feat, lab, mk, calls = _calls(tr, stage)
+    for call in calls:
+        with pytest.raises(NotImplementedError, match="Uncertainty function not implemented."):
+            call(lab, mk, labelled=[0, 1], measure="bald")
+        with pytest.raises(ValueError, match="labelled"):
+            call(lab, mk, labelled=np.ones(3))
+        with pytest.raises(ValueError, match="confusion"):
+            call(lab, mk, confusion=np.zeros((19, 19), np.int32))
+        with pytest.raises(ValueError, match="confusion"):
+            call(lab, mk, confusion=np.zeros((18, 19), np.int64))
+        with pytest.raises(ValueError, match="None only"):
+            call(None, None, labelled=np.array([0, 1]))
+        with pytest.raises(ValueError, match="None only"):
+            call(None, None, confusion=np.zeros((19, 19), np.int64))
+    grad, step_f = calls[0], calls[1]
+    for call in (grad, step_f):
+        with pytest.raises(ValueError, match="features_raw"):
+            call(lab, mk, labelled=[0, 1], features_raw=np.zeros((2, 8, 4, feat[0].shape[-1]), np.float32),
+                 **({"argmax1_raw": feat[1]} if stage else {}))
+    with pytest.raises(ValueError, match="unknown variables"):
+        grad(lab, mk, labelled=[0, 1], params={"Bottleneck5_1.proj_mean": np.zeros((4,), np.float32)})
+    if stage:
+        for call in (grad, step_f):
+            with pytest.raises(ValueError, match="together"):
+                call(lab, mk, labelled=[0, 1], features_raw=feat[0].copy())
+            with pytest.raises(ValueError, match="together"):
+                call(lab, mk, labelled=[0, 1], argmax1_raw=feat[1].copy())
+            with pytest.raises(ValueError, match="argmax1"):
+                call(lab, mk, labelled=[0, 1], features_raw=feat[0].copy(), argmax1_raw=feat[1] + 32)
+            with pytest.raises(ValueError, match="max_workgroups"):
+                call(lab, mk, labelled=[0, 1], max_workgroups=-1)
+        with pytest.raises(NotImplementedError):
+            grad(lab, mk, labelled=[0, 1], params={"Bottleneck4_2.proj_kernel": np.zeros((1, 1, 64, 16), np.float32)})
+
+
+def test_parent_classes_still_refuse():
+    net = _net()
+    for tr, stage in ((LastBlockTrainer(net, 1e-3), False), (LastStageTrainer(net, 1e-3), True)):
+        _, lab, mk, calls = _calls(tr, stage)
+        for kw in ({"labelled": np.array([0, 1])}, {"confusion": np.zeros((19, 19), np.int64)}, {"return_pseudo_pixels": True},
+                   {"measure": "entropy"}, {"threshold": 0.5}):
+            for call in calls:
+                with pytest.raises(NotImplementedError, match="output layer only"):
+                    call(lab, mk, **kw)
