@@ -1705,8 +1705,45 @@ SSAL_API int ssal_profile_collect(char *json_out, int64_t cap)
 }
 
 // ------------------------------------------------------------------------------------------------
-// Output-layer training (include/ssal_enet.h, "Output-layer training")
+// Training of ENet's tail over a frozen trunk (include/ssal_enet.h, "Output-layer training" to "The semi-supervised step of
+// the deeper trainers"; DESIGN.md sections 15-19).  Three depths -- the output layer, the last block, the last stage -- each
+// entered from cached features or from images, plain or semi-supervised.  Every depth has ONE body (final_grad_run,
+// train_block_run, train_stage_run) that takes the features and an optional SemiArgs; the public entries validate (dims,
+// then semi arguments, then NULL pointers, then the workspace size, all before any launch), carve the workspace and call it.
 // ------------------------------------------------------------------------------------------------
+// what every entry is given besides its inputs and parameters: targets, the loss' knobs, outputs, workspace, stream
+struct CallArgs {
+    const uint8_t *labels;
+    const float *mask;
+    float weight, label_smoothing;
+    double *loss;
+    float *grad;
+    void *ws;
+    int64_t ws_bytes;
+    hipStream_t s;
+};
+
+// the semi-supervised side of a call as the public entries take it (DESIGN.md sections 16 and 19); NULL = the plain step
+struct SemiArgs {
+    const uint8_t *labelled;
+    int measure;
+    float threshold;
+    int64_t *confusion, *pseudo_pixels;
+    bool with_raw;
+};
+
+// ---- the steps the entries share ----
+static bool net_dims_ok(const ssal_enet *net, int n, int h, int w)
+{
+    return net && net->committed && n > 0 && h > 0 && w > 0 && h % 8 == 0 && w % 8 == 0;
+}
+
+// fits = the depth's own limit (final_grad_fits, train_block_fits, train_stage_fits)
+static bool grad_dims_ok(int n, int h, int w, int classes, bool (*fits)(int, int))
+{
+    return classes >= 2 && classes <= 32 && n > 0 && h > 0 && w > 0 && fits(h, w);
+}
+
 static int final_grad_check(int n, int h, int w, int classes)
 {
     if (classes < 2 || classes > 32) return fail(SSAL_EINVAL, "classes must be in [2,32] (got %d)", classes);
@@ -1716,49 +1753,166 @@ static int final_grad_check(int n, int h, int w, int classes)
     return SSAL_OK;
 }
 
-// part [G][9 * K * 16] fp32, then lpart [G][2] float64 (G = final_grad_workgroups)
-static void final_grad_carve(Bump &b, int h, int w, int classes, float **part, double **lpart)
+// the semi arguments, then the pointers (`inputs`: the entry's own features / frames / parameters, and-ed); a semi call's
+// label and mask planes may be NULL when no image is labelled
+static int args_check(bool inputs, const CallArgs &a, const SemiArgs *semi)
+{
+    if (semi && (semi->measure < 0 || semi->measure > 2))
+        return fail(SSAL_ENOTIMPL, "Uncertainty function not implemented (measure=%d)", semi->measure);
+    if (semi && !semi->labelled && (!a.labels || !a.mask))
+        return fail(SSAL_EINVAL, "labels_dev / mask_dev may be NULL only when labelled_dev marks no image as labelled");
+    if (!inputs || !a.loss || !a.grad || !a.ws || (!semi && (!a.labels || !a.mask)))
+        return fail(SSAL_EINVAL, "NULL device pointer");
+    return SSAL_OK;
+}
+
+// judged once the call's pieces are carved from b (pointer arithmetic only), before anything is launched
+static int ws_check(int64_t need, const Bump &b, const CallArgs &a)
+{
+    if (a.ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
+                                       (long long)a.ws_bytes);
+    return b.ok ? SSAL_OK : fail(SSAL_ENOMEM, "workspace too small: need %lld bytes", (long long)need);
+}
+
+// carves the forward workspace into W and returns a Bump positioned behind it (not ok when W is not)
+static Bump carve_behind_trunk(const ssal_enet *net, const CallArgs &a, int n, int h, int w, NetWorkspace *W)
+{
+    *W = carve(net, a.ws, a.ws_bytes, n, h, w);
+    char *gws = (char *)a.ws + (W->bytes + 255) / 256 * 256;
+    Bump b(gws, a.ws_bytes - (gws - (char *)a.ws));
+    b.ok = W->ok;
+    return b;
+}
+
+// bytes of an images entry: the forward workspace, then `g`, the bytes of the depth's features entry (-1 stays -1)
+static int64_t behind_trunk_bytes(const ssal_enet *net, int n, int h, int w, int64_t g)
+{
+    return g < 0 ? -1 : carve(net, nullptr, 0, n, h, w).bytes + 256 + g;
+}
+
+// the frozen trunk, training=False: layers [0, upto) on stream s
+static int run_trunk(const ssal_enet *net, int upto, const void *x_dev, int x_is_u8, const NetWorkspace &W, int n, int h, int w,
+                     hipStream_t s)
+{
+    for (int li = 0; li < upto; ++li) HIP_TRY(run_layer_idx(net, li, x_dev, x_is_u8 != 0, W, n, h, w, s));
+    return SSAL_OK;
+}
+
+// a features entry has its features already: nothing to run where an images entry runs the trunk
+static int no_trunk(bool) { return SSAL_OK; }
+
+// launches(rep, reps) with the confusion replicas zeroed before and folded into the caller's matrix after it; without a
+// matrix (a plain call, or a semi call that asks for none) rep is NULL and neither the memset nor the fold is issued
+template <typename Launches>
+static int with_confusion(unsigned long long *rep, int classes, int64_t *confusion_dev, hipStream_t s, Launches launches)
+{
+    const int reps = ssal::knobs().conf_reps;
+    if (confusion_dev) HIP_TRY(hipMemsetAsync(rep, 0, (size_t)reps * ssal::conf_rep_stride(classes * classes) * 8, s));
+    if (int rc = launches(confusion_dev ? rep : nullptr, reps)) return rc;
+    if (confusion_dev) HIP_TRY(launch_confusion_fold(rep, reps, classes, confusion_dev, s));
+    return SSAL_OK;
+}
+
+// ---- the output layer (DESIGN.md sections 15 and 16) ----
+// part [G][9 * K * 16] fp32, then lpart [G][2] float64 (G = final_grad_workgroups); semi: then the confusion replicas
+struct FinalGradWs {
+    float *part;
+    double *lpart;
+    unsigned long long *rep;
+};
+
+static FinalGradWs final_grad_carve(Bump &b, int h, int w, int classes, bool semi)
 {
     const int64_t G = final_grad_workgroups(h, w);
-    *part = b.take<float>(G * 9 * classes * 16);
-    *lpart = b.take<double>(2 * G);
+    FinalGradWs t;
+    t.part = b.take<float>(G * 9 * classes * 16);
+    t.lpart = b.take<double>(2 * G);
+    t.rep = semi ? b.take<unsigned long long>((int64_t)ssal::kConfMaxReps * ssal::conf_rep_stride(classes * classes)) : nullptr;
+    return t;
+}
+
+static int64_t final_grad_bytes(int n, int h, int w, int classes, bool semi)
+{
+    if (!grad_dims_ok(n, h, w, classes, final_grad_fits)) return -1;
+    Bump b(nullptr, 0);
+    final_grad_carve(b, h, w, classes, semi);
+    return b.off + 256;
+}
+
+// forward workspace | gradient partials [+ confusion replicas] | [with_raw: Bottleneck5_1 of x_raw, n * (h/2) * (w/2) * 16 floats]
+static int64_t final_train_bytes(const ssal_enet *net, int n, int h, int w, bool semi, bool with_raw)
+{
+    if (!net_dims_ok(net, n, h, w)) return -1;
+    const int64_t g = behind_trunk_bytes(net, n, h, w, final_grad_bytes(n, h / 2, w / 2, net->classes, semi));
+    return g < 0 || !with_raw ? g : g + (int64_t)n * (h / 2) * (w / 2) * 16 * 4 + 256;
+}
+
+// x / x_raw [n,h,w,16]: Bottleneck5_1 of the training / the undistorted frames (x_raw may be NULL)
+static int final_grad_run(const float *x, const float *x_raw, int n, int h, int w, int classes, const float *kernel_dev,
+                          const CallArgs &a, const FinalGradWs &t, const SemiArgs *semi)
+{
+    return with_confusion(t.rep, classes, semi ? semi->confusion : nullptr, a.s, [&](unsigned long long *rep, int reps) -> int {
+        if (!semi)
+            HIP_TRY(launch_final_grad(x, n, h, w, kernel_dev, classes, a.labels, a.mask, a.weight, a.label_smoothing, t.part,
+                                      t.lpart, a.loss, a.grad, a.s));
+        else
+            HIP_TRY(launch_final_grad_semi(x, x_raw, n, h, w, kernel_dev, classes, a.labels, a.mask, semi->labelled,
+                                           semi->measure, semi->threshold, a.weight, a.label_smoothing, t.part, t.lpart, a.loss,
+                                           a.grad, rep, reps, semi->pseudo_pixels, a.s));
+        return SSAL_OK;
+    });
+}
+
+static int final_grad_entry(const float *features_dev, const float *features_raw_dev, int n, int h, int w, int classes,
+                            const float *kernel_dev, const CallArgs &a, const SemiArgs *semi)
+{
+    if (int rc = final_grad_check(n, h, w, classes)) return rc;
+    if (int rc = args_check(features_dev && kernel_dev, a, semi)) return rc;
+    Bump b(a.ws, a.ws_bytes);
+    const FinalGradWs t = final_grad_carve(b, h, w, classes, semi != nullptr);
+    if (int rc = ws_check(final_grad_bytes(n, h, w, classes, semi != nullptr), b, a)) return rc;
+    return final_grad_run(features_dev, features_raw_dev, n, h, w, classes, kernel_dev, a, t, semi);
+}
+
+static int final_train_entry(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h, int w,
+                             const float *kernel_dev, const CallArgs &a, const SemiArgs *semi)
+{
+    int rc = check_dims(net, n, h, w);
+    if (rc) return rc;
+    if ((rc = final_grad_check(n, h / 2, w / 2, net->classes))) return rc;
+    if ((rc = args_check(x_dev && kernel_dev, a, semi))) return rc;
+    NetWorkspace W;
+    Bump b = carve_behind_trunk(net, a, n, h, w, &W);
+    const FinalGradWs t = final_grad_carve(b, h / 2, w / 2, net->classes, semi != nullptr);
+    float *raw = x_raw_dev ? b.take<float>((int64_t)n * (h / 2) * (w / 2) * 16) : nullptr;
+    if ((rc = ws_check(final_train_bytes(net, n, h, w, semi != nullptr, x_raw_dev != nullptr), b, a))) return rc;
+    // Initial .. Bottleneck5_1, on the undistorted frames first: Bottleneck5_1 (the one layer that writes a1) lands in the
+    // raw slot; then on the training frames (a1)
+    if (x_raw_dev) {
+        NetWorkspace R = W;
+        R.a1 = raw;
+        if ((rc = run_trunk(net, kNumLayers - 1, x_raw_dev, x_is_u8, R, n, h, w, a.s))) return rc;
+    }
+    if ((rc = run_trunk(net, kNumLayers - 1, x_dev, x_is_u8, W, n, h, w, a.s))) return rc;
+    return final_grad_run(W.a1, raw, n, h / 2, w / 2, net->classes, kernel_dev, a, t, semi);
 }
 
 SSAL_API int64_t ssal_final_grad_workspace_bytes(int n, int h, int w, int classes)
 {
-    if (classes < 2 || classes > 32 || n <= 0 || h <= 0 || w <= 0 || !final_grad_fits(h, w)) return -1;
-    Bump b(nullptr, 0);
-    float *part;
-    double *lpart;
-    final_grad_carve(b, h, w, classes, &part, &lpart);
-    return b.off + 256;
+    return final_grad_bytes(n, h, w, classes, false);
 }
 
 SSAL_API int ssal_final_grad_nhwc(const float *features_dev, int n, int h, int w, int classes, const float *kernel_dev,
                                   const uint8_t *labels_dev, const float *mask_dev, float weight, float label_smoothing,
                                   double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    if (int rc = final_grad_check(n, h, w, classes)) return rc;
-    if (!features_dev || !kernel_dev || !labels_dev || !mask_dev || !loss_dev || !grad_dev || !ws_dev)
-        return fail(SSAL_EINVAL, "NULL device pointer");
-    const int64_t need = ssal_final_grad_workspace_bytes(n, h, w, classes);
-    if (ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
-                                     (long long)ws_bytes);
-    Bump b(ws_dev, ws_bytes);
-    float *part;
-    double *lpart;
-    final_grad_carve(b, h, w, classes, &part, &lpart);
-    HIP_TRY(launch_final_grad(features_dev, n, h, w, kernel_dev, classes, labels_dev, mask_dev, weight, label_smoothing,
-                              part, lpart, loss_dev, grad_dev, (hipStream_t)stream));
-    return SSAL_OK;
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return final_grad_entry(features_dev, nullptr, n, h, w, classes, kernel_dev, a, nullptr);
 }
 
 SSAL_API int64_t ssal_enet_train_final_workspace_bytes(const ssal_enet *net, int n, int h, int w)
 {
-    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 8 || w % 8) return -1;
-    const int64_t g = ssal_final_grad_workspace_bytes(n, h / 2, w / 2, net->classes);
-    if (g < 0) return -1;
-    return carve(net, nullptr, 0, n, h, w).bytes + 256 + g;
+    return final_train_bytes(net, n, h, w, false, false);
 }
 
 SSAL_API int ssal_enet_train_final_nhwc(ssal_enet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
@@ -1766,70 +1920,13 @@ SSAL_API int ssal_enet_train_final_nhwc(ssal_enet *net, const void *x_dev, int x
                                         float weight, float label_smoothing, double *loss_dev, float *grad_dev,
                                         void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    int rc = check_dims(net, n, h, w);
-    if (rc) return rc;
-    if ((rc = final_grad_check(n, h / 2, w / 2, net->classes))) return rc;
-    if (!x_dev || !labels_dev || !mask_dev || !kernel_dev || !loss_dev || !grad_dev || !ws_dev)
-        return fail(SSAL_EINVAL, "NULL device pointer");
-    const int64_t need = ssal_enet_train_final_workspace_bytes(net, n, h, w);
-    if (ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
-                                     (long long)ws_bytes);
-    NetWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
-    char *gws = (char *)ws_dev + (W.bytes + 255) / 256 * 256;
-    Bump b(gws, ws_bytes - (gws - (char *)ws_dev));
-    float *part;
-    double *lpart;
-    final_grad_carve(b, h / 2, w / 2, net->classes, &part, &lpart);
-    if (!W.ok || !b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes", (long long)need);
-    hipStream_t s = (hipStream_t)stream;
-    // the trunk, training=False: Initial .. Bottleneck5_1 on the caller's stream (its output lands in W.a1)
-    for (int li = 0; li < kNumLayers - 1; ++li) HIP_TRY(run_layer_idx(net, li, x_dev, x_is_u8 != 0, W, n, h, w, s));
-    HIP_TRY(launch_final_grad(W.a1, n, h / 2, w / 2, kernel_dev, net->classes, labels_dev, mask_dev, weight,
-                              label_smoothing, part, lpart, loss_dev, grad_dev, s));
-    return SSAL_OK;
-}
-
-// ---- the semi-supervised form: the gradient's partials, then the confusion replicas ----
-static void final_grad_semi_carve(Bump &b, int h, int w, int classes, float **part, double **lpart, unsigned long long **rep)
-{
-    final_grad_carve(b, h, w, classes, part, lpart);
-    *rep = b.take<unsigned long long>((int64_t)ssal::kConfMaxReps * ssal::conf_rep_stride(classes * classes));
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return final_train_entry(net, x_dev, nullptr, x_is_u8, n, h, w, kernel_dev, a, nullptr);
 }
 
 SSAL_API int64_t ssal_final_grad_semi_workspace_bytes(int n, int h, int w, int classes)
 {
-    if (classes < 2 || classes > 32 || n <= 0 || h <= 0 || w <= 0 || !final_grad_fits(h, w)) return -1;
-    Bump b(nullptr, 0);
-    float *part;
-    double *lpart;
-    unsigned long long *rep;
-    final_grad_semi_carve(b, h, w, classes, &part, &lpart, &rep);
-    return b.off + 256;
-}
-
-// the part both entries share: zero the replicas, the kernel, the fold into the caller's matrix
-static int final_grad_semi_run(const float *x, const float *x_raw, int n, int h, int w, int classes, const float *kernel_dev,
-                               const uint8_t *labels_dev, const float *mask_dev, const uint8_t *labelled_dev, int measure,
-                               float threshold, float weight, float label_smoothing, double *loss_dev, float *grad_dev,
-                               int64_t *confusion_dev, int64_t *pseudo_pixels_dev, float *part, double *lpart,
-                               unsigned long long *rep, hipStream_t s)
-{
-    const int reps = ssal::knobs().conf_reps;
-    if (confusion_dev) HIP_TRY(hipMemsetAsync(rep, 0, (size_t)reps * ssal::conf_rep_stride(classes * classes) * 8, s));
-    HIP_TRY(launch_final_grad_semi(x, x_raw, n, h, w, kernel_dev, classes, labels_dev, mask_dev, labelled_dev, measure,
-                                   threshold, weight, label_smoothing, part, lpart, loss_dev, grad_dev,
-                                   confusion_dev ? rep : nullptr, reps, pseudo_pixels_dev, s));
-    if (confusion_dev) HIP_TRY(launch_confusion_fold(rep, reps, classes, confusion_dev, s));
-    return SSAL_OK;
-}
-
-static int final_grad_semi_check(int measure, const void *labels_dev, const void *mask_dev, const void *labelled_dev)
-{
-    if (measure < 0 || measure > 2)
-        return fail(SSAL_ENOTIMPL, "Uncertainty function not implemented (measure=%d)", measure);
-    if (!labelled_dev && (!labels_dev || !mask_dev))
-        return fail(SSAL_EINVAL, "labels_dev / mask_dev may be NULL only when labelled_dev marks no image as labelled");
-    return SSAL_OK;
+    return final_grad_bytes(n, h, w, classes, true);
 }
 
 SSAL_API int ssal_final_grad_semi_nhwc(const float *features_dev, const float *features_raw_dev, int n, int h, int w,
@@ -1839,30 +1936,14 @@ SSAL_API int ssal_final_grad_semi_nhwc(const float *features_dev, const float *f
                                        int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes,
                                        void *stream)
 {
-    if (int rc = final_grad_check(n, h, w, classes)) return rc;
-    if (int rc = final_grad_semi_check(measure, labels_dev, mask_dev, labelled_dev)) return rc;
-    if (!features_dev || !kernel_dev || !loss_dev || !grad_dev || !ws_dev) return fail(SSAL_EINVAL, "NULL device pointer");
-    const int64_t need = ssal_final_grad_semi_workspace_bytes(n, h, w, classes);
-    if (ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
-                                     (long long)ws_bytes);
-    Bump b(ws_dev, ws_bytes);
-    float *part;
-    double *lpart;
-    unsigned long long *rep;
-    final_grad_semi_carve(b, h, w, classes, &part, &lpart, &rep);
-    return final_grad_semi_run(features_dev, features_raw_dev, n, h, w, classes, kernel_dev, labels_dev, mask_dev,
-                               labelled_dev, measure, threshold, weight, label_smoothing, loss_dev, grad_dev, confusion_dev,
-                               pseudo_pixels_dev, part, lpart, rep, (hipStream_t)stream);
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, features_raw_dev != nullptr};
+    return final_grad_entry(features_dev, features_raw_dev, n, h, w, classes, kernel_dev, a, &semi);
 }
 
-// forward workspace | gradient partials + confusion replicas | [with_raw: Bottleneck5_1 of x_raw, n * (h/2) * (w/2) * 16 floats]
 SSAL_API int64_t ssal_enet_train_final_semi_workspace_bytes(const ssal_enet *net, int n, int h, int w, int with_raw)
 {
-    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 8 || w % 8) return -1;
-    const int64_t g = ssal_final_grad_semi_workspace_bytes(n, h / 2, w / 2, net->classes);
-    if (g < 0) return -1;
-    const int64_t raw = with_raw ? (int64_t)n * (h / 2) * (w / 2) * 16 * 4 + 256 : 0;
-    return carve(net, nullptr, 0, n, h, w).bytes + 256 + g + raw;
+    return final_train_bytes(net, n, h, w, true, with_raw != 0);
 }
 
 SSAL_API int ssal_enet_train_final_semi_nhwc(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
@@ -1872,35 +1953,9 @@ SSAL_API int ssal_enet_train_final_semi_nhwc(ssal_enet *net, const void *x_dev, 
                                              float *grad_dev, int64_t *confusion_dev, int64_t *pseudo_pixels_dev,
                                              void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    int rc = check_dims(net, n, h, w);
-    if (rc) return rc;
-    if ((rc = final_grad_check(n, h / 2, w / 2, net->classes))) return rc;
-    if ((rc = final_grad_semi_check(measure, labels_dev, mask_dev, labelled_dev))) return rc;
-    if (!x_dev || !kernel_dev || !loss_dev || !grad_dev || !ws_dev) return fail(SSAL_EINVAL, "NULL device pointer");
-    const int64_t need = ssal_enet_train_final_semi_workspace_bytes(net, n, h, w, x_raw_dev != nullptr);
-    if (ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
-                                     (long long)ws_bytes);
-    NetWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
-    char *gws = (char *)ws_dev + (W.bytes + 255) / 256 * 256;
-    Bump b(gws, ws_bytes - (gws - (char *)ws_dev));
-    float *part, *raw = nullptr;
-    double *lpart;
-    unsigned long long *rep;
-    final_grad_semi_carve(b, h / 2, w / 2, net->classes, &part, &lpart, &rep);
-    if (x_raw_dev) raw = b.take<float>((int64_t)n * (h / 2) * (w / 2) * 16);
-    if (!W.ok || !b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes", (long long)need);
-    hipStream_t s = (hipStream_t)stream;
-    // the trunk, training=False, on the undistorted frames first: Bottleneck5_1 (the one layer that writes a1) lands in
-    // the raw slot; then on the training frames (a1)
-    if (x_raw_dev) {
-        NetWorkspace R = W;
-        R.a1 = raw;
-        for (int li = 0; li < kNumLayers - 1; ++li) HIP_TRY(run_layer_idx(net, li, x_raw_dev, x_is_u8 != 0, R, n, h, w, s));
-    }
-    for (int li = 0; li < kNumLayers - 1; ++li) HIP_TRY(run_layer_idx(net, li, x_dev, x_is_u8 != 0, W, n, h, w, s));
-    return final_grad_semi_run(W.a1, raw, n, h / 2, w / 2, net->classes, kernel_dev, labels_dev, mask_dev, labelled_dev,
-                               measure, threshold, weight, label_smoothing, loss_dev, grad_dev, confusion_dev,
-                               pseudo_pixels_dev, part, lpart, rep, s);
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev != nullptr};
+    return final_train_entry(net, x_dev, x_raw_dev, x_is_u8, n, h, w, kernel_dev, a, &semi);
 }
 
 SSAL_API int ssal_adam_apply(float *var_dev, float *m_dev, float *v_dev, const float *grad_dev, int64_t count, float lr,
@@ -1914,9 +1969,7 @@ SSAL_API int ssal_adam_apply(float *var_dev, float *m_dev, float *v_dev, const f
     return SSAL_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
-// Last-block training: Bottleneck5_1 + Final (include/ssal_enet.h, "Last-block training")
-// ------------------------------------------------------------------------------------------------
+// ---- the last block: Bottleneck5_1 + Final (DESIGN.md sections 17 and 19) ----
 static TrainBlockWs train_block_carve(Bump &b, int64_t n, int h, int w, int classes)
 {
     const int64_t G = train_block_workgroups(h, w);
@@ -1929,18 +1982,105 @@ static TrainBlockWs train_block_carve(Bump &b, int64_t n, int h, int w, int clas
     return t;
 }
 
+// What a semi call of the block or the stage adds behind the plain workspace: the confusion replicas, then (with_raw) the
+// packed pseudo-target plane of the undistorted frames, one byte per output pixel (out_pix per image).  Plain: nothing.
+struct TrainSemiWs {
+    unsigned long long *rep;
+    uint8_t *tgt;
+};
+
+static TrainSemiWs train_semi_carve(Bump &b, int64_t n, int64_t out_pix, int classes, bool semi, bool with_raw)
+{
+    TrainSemiWs t;
+    t.rep = semi ? b.take<unsigned long long>((int64_t)ssal::kConfMaxReps * ssal::conf_rep_stride(classes * classes)) : nullptr;
+    t.tgt = semi && with_raw ? b.take<uint8_t>(n * out_pix) : nullptr;
+    return t;
+}
+
+// the launchers' form of a semi call (ssal_train_block.h)
+static TrainBlockSemi train_semi_args(const SemiArgs &semi, const TrainSemiWs &sw, unsigned long long *rep, int reps)
+{
+    // labelled, measure, threshold, tgt, use_tgt, rep, reps, pseudo_pixels
+    return {semi.labelled, semi.measure, semi.threshold, sw.tgt, semi.with_raw && semi.labelled, rep, reps, semi.pseudo_pixels};
+}
+
+static int64_t train_block_bytes(int n, int h, int w, int classes, bool semi, bool with_raw)
+{
+    if (!grad_dims_ok(n, h, w, classes, train_block_fits)) return -1;
+    Bump b(nullptr, 0);
+    train_block_carve(b, n, h, w, classes);
+    train_semi_carve(b, n, 4 * (int64_t)h * w, classes, semi, with_raw);
+    return b.off + 256;
+}
+
+static int64_t enet_train_block_bytes(const ssal_enet *net, int n, int h, int w, bool semi, bool with_raw)
+{
+    if (!net_dims_ok(net, n, h, w)) return -1;
+    return behind_trunk_bytes(net, n, h, w, train_block_bytes(n, h / 2, w / 2, net->classes, semi, with_raw));
+}
+
+// b: where the call's own pieces go, need: the entry's whole workspace.  x5 / x5_raw [n,h,w,16]: Bottleneck5_0 of the training
+// / the undistorted frames, which trunk(raw) brings about (an images entry: one after the other in W.a0) or the caller has.
+// x5_raw not NULL: the target-only launch runs on it; it leaves one byte per output pixel, so the training frames can go
+// through the same slots afterwards.
+template <typename Trunk>
+static int train_block_run(Bump &b, int64_t need, Trunk trunk, const float *x5, const float *x5_raw, int n, int h, int w,
+                           int classes, const float *params_dev, const CallArgs &a, const SemiArgs *semi)
+{
+    const TrainBlockWs t = train_block_carve(b, n, h, w, classes);
+    const TrainSemiWs sw = train_semi_carve(b, n, 4 * (int64_t)h * w, classes, semi != nullptr, semi && semi->with_raw);
+    if (int rc = ws_check(need, b, a)) return rc;
+    return with_confusion(sw.rep, classes, semi ? semi->confusion : nullptr, a.s, [&](unsigned long long *rep, int reps) -> int {
+        TrainBlockSemi sa = {};
+        if (semi) sa = train_semi_args(*semi, sw, rep, reps);
+        if (x5_raw) {
+            if (int rc = trunk(true)) return rc;
+            HIP_TRY(launch_train_block_targets(x5_raw, n, h, w, classes, params_dev, sa, t, a.s));
+        }
+        if (int rc = trunk(false)) return rc;
+        HIP_TRY(launch_train_block_grad(x5, n, h, w, classes, params_dev, a.labels, a.mask, a.weight, a.label_smoothing, t,
+                                        a.loss, a.grad, a.s, nullptr, 0, semi ? &sa : nullptr));
+        return SSAL_OK;
+    });
+}
+
+static int train_block_grad_entry(const float *features_dev, const float *features_raw_dev, int n, int h, int w, int classes,
+                                  const float *params_dev, const CallArgs &a, const SemiArgs *semi)
+{
+    if (int rc = final_grad_check(n, h, w, classes)) return rc;
+    if (int rc = args_check(features_dev && params_dev, a, semi)) return rc;
+    Bump b(a.ws, a.ws_bytes);
+    return train_block_run(b, train_block_bytes(n, h, w, classes, semi != nullptr, features_raw_dev != nullptr), no_trunk,
+                           features_dev, features_raw_dev, n, h, w, classes, params_dev, a, semi);
+}
+
+static int enet_train_block_entry(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h, int w,
+                                  const float *params_dev, const CallArgs &a, const SemiArgs *semi)
+{
+    int rc = check_dims(net, n, h, w);
+    if (rc) return rc;
+    if ((rc = final_grad_check(n, h / 2, w / 2, net->classes))) return rc;
+    if ((rc = args_check(x_dev && params_dev, a, semi))) return rc;
+    NetWorkspace W;
+    Bump b = carve_behind_trunk(net, a, n, h, w, &W);
+    // the frozen trunk is Initial .. Bottleneck5_0 (its output lands in W.a0); Bottleneck5_1 is evaluated inside the training
+    // kernels from params_dev, not from the handle's committed weights
+    auto trunk = [&](bool of_raw) {
+        return run_trunk(net, kNumLayers - 2, of_raw ? x_raw_dev : x_dev, x_is_u8, W, n, h, w, a.s);
+    };
+    // (the undistorted frames go through the trunk only with `labelled_dev`; the features entry goes by the raw features alone)
+    return train_block_run(b, enet_train_block_bytes(net, n, h, w, semi != nullptr, x_raw_dev != nullptr), trunk, W.a0,
+                           x_raw_dev && semi->labelled ? W.a0 : nullptr, n, h / 2, w / 2, net->classes, params_dev, a, semi);
+}
+
 SSAL_API int64_t ssal_train_block_param_floats(int classes)
 {
-    if (classes < 2 || classes > 32) return -1;
-    return train_block_floats(classes);
+    return classes < 2 || classes > 32 ? -1 : train_block_floats(classes);
 }
 
 SSAL_API int64_t ssal_train_block_grad_workspace_bytes(int n, int h, int w, int classes)
 {
-    if (classes < 2 || classes > 32 || n <= 0 || h <= 0 || w <= 0 || !train_block_fits(h, w)) return -1;
-    Bump b(nullptr, 0);
-    train_block_carve(b, n, h, w, classes);
-    return b.off + 256;
+    return train_block_bytes(n, h, w, classes, false, false);
 }
 
 SSAL_API int ssal_train_block_grad_nhwc(const float *features_dev, int n, int h, int w, int classes, const float *params_dev,
@@ -1948,33 +2088,20 @@ SSAL_API int ssal_train_block_grad_nhwc(const float *features_dev, int n, int h,
                                         float label_smoothing, double *loss_dev, float *grad_dev, void *ws_dev,
                                         int64_t ws_bytes, void *stream)
 {
-    if (int rc = final_grad_check(n, h, w, classes)) return rc;
-    if (!features_dev || !params_dev || !labels_dev || !mask_dev || !loss_dev || !grad_dev || !ws_dev)
-        return fail(SSAL_EINVAL, "NULL device pointer");
-    const int64_t need = ssal_train_block_grad_workspace_bytes(n, h, w, classes);
-    if (ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
-                                     (long long)ws_bytes);
-    Bump b(ws_dev, ws_bytes);
-    const TrainBlockWs t = train_block_carve(b, n, h, w, classes);
-    if (!b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes", (long long)need);
-    HIP_TRY(launch_train_block_grad(features_dev, n, h, w, classes, params_dev, labels_dev, mask_dev, weight,
-                                    label_smoothing, t, loss_dev, grad_dev, (hipStream_t)stream));
-    return SSAL_OK;
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return train_block_grad_entry(features_dev, nullptr, n, h, w, classes, params_dev, a, nullptr);
 }
 
 SSAL_API int64_t ssal_enet_train_block_workspace_bytes(const ssal_enet *net, int n, int h, int w)
 {
-    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 8 || w % 8) return -1;
-    const int64_t g = ssal_train_block_grad_workspace_bytes(n, h / 2, w / 2, net->classes);
-    if (g < 0) return -1;
-    return carve(net, nullptr, 0, n, h, w).bytes + 256 + g;
+    return enet_train_block_bytes(net, n, h, w, false, false);
 }
 
 // byte offset (into the workspace passed to forward / score / train_block) of Bottleneck5_0's output [n,h/2,w/2,16],
 // the features ssal_train_block_grad_nhwc takes; valid until the next call.  -1 for dims the net does not take.
 SSAL_API int64_t ssal_enet_train_block_features_offset(const ssal_enet *net, int n, int h, int w)
 {
-    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 8 || w % 8) return -1;
+    if (!net_dims_ok(net, n, h, w)) return -1;
     NetWorkspace W = carve(net, (void *)256, ((int64_t)1 << 62), n, h, w);
     return (const char *)W.a0 - (const char *)256;
 }
@@ -1984,31 +2111,45 @@ SSAL_API int ssal_enet_train_block_nhwc(ssal_enet *net, const void *x_dev, int x
                                         float weight, float label_smoothing, double *loss_dev, float *grad_dev,
                                         void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    int rc = check_dims(net, n, h, w);
-    if (rc) return rc;
-    if ((rc = final_grad_check(n, h / 2, w / 2, net->classes))) return rc;
-    if (!x_dev || !labels_dev || !mask_dev || !params_dev || !loss_dev || !grad_dev || !ws_dev)
-        return fail(SSAL_EINVAL, "NULL device pointer");
-    const int64_t need = ssal_enet_train_block_workspace_bytes(net, n, h, w);
-    if (ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
-                                     (long long)ws_bytes);
-    NetWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
-    char *gws = (char *)ws_dev + (W.bytes + 255) / 256 * 256;
-    Bump b(gws, ws_bytes - (gws - (char *)ws_dev));
-    const TrainBlockWs t = train_block_carve(b, n, h / 2, w / 2, net->classes);
-    if (!W.ok || !b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes", (long long)need);
-    hipStream_t s = (hipStream_t)stream;
-    // the frozen trunk, training=False: Initial .. Bottleneck5_0 on the caller's stream (its output lands in W.a0);
-    // Bottleneck5_1 is evaluated inside the training kernels from params_dev, not from the handle's committed weights
-    for (int li = 0; li < kNumLayers - 2; ++li) HIP_TRY(run_layer_idx(net, li, x_dev, x_is_u8 != 0, W, n, h, w, s));
-    HIP_TRY(launch_train_block_grad(W.a0, n, h / 2, w / 2, net->classes, params_dev, labels_dev, mask_dev, weight,
-                                    label_smoothing, t, loss_dev, grad_dev, s));
-    return SSAL_OK;
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return enet_train_block_entry(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, a, nullptr);
 }
 
-// ------------------------------------------------------------------------------------------------
-// Last-stage training: Bottleneck5_0 + Bottleneck5_1 + Final (include/ssal_enet.h, "Last-stage training")
-// ------------------------------------------------------------------------------------------------
+SSAL_API int64_t ssal_train_block_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw)
+{
+    return train_block_bytes(n, h, w, classes, true, with_raw != 0);
+}
+
+SSAL_API int ssal_train_block_grad_semi_nhwc(const float *features_dev, const float *features_raw_dev, int n, int h, int w,
+                                             int classes, const float *params_dev, const uint8_t *labels_dev,
+                                             const float *mask_dev, const uint8_t *labelled_dev, int measure,
+                                             float threshold, float weight, float label_smoothing, double *loss_dev,
+                                             float *grad_dev, int64_t *confusion_dev, int64_t *pseudo_pixels_dev,
+                                             void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, features_raw_dev != nullptr};
+    return train_block_grad_entry(features_dev, features_raw_dev, n, h, w, classes, params_dev, a, &semi);
+}
+
+SSAL_API int64_t ssal_enet_train_block_semi_workspace_bytes(const ssal_enet *net, int n, int h, int w, int with_raw)
+{
+    return enet_train_block_bytes(net, n, h, w, true, with_raw != 0);
+}
+
+SSAL_API int ssal_enet_train_block_semi_nhwc(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
+                                             int h, int w, const uint8_t *labels_dev, const float *mask_dev,
+                                             const uint8_t *labelled_dev, int measure, float threshold,
+                                             const float *params_dev, float weight, float label_smoothing,
+                                             double *loss_dev, float *grad_dev, int64_t *confusion_dev,
+                                             int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev != nullptr};
+    return enet_train_block_entry(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, a, &semi);
+}
+
+// ---- the last stage: Bottleneck5_0 + Bottleneck5_1 + Final (DESIGN.md sections 18 and 19) ----
 // h, w = the dims of Bottleneck4_2's output; own = the call brings no a5_0 / window-code buffers of its own
 static TrainStageWs train_stage_carve(Bump &b, int64_t n, int h, int w, int classes, bool own)
 {
@@ -2033,18 +2174,89 @@ static int train_stage_check(int n, int h, int w, int classes, int max_workgroup
     return SSAL_OK;
 }
 
+static int64_t train_stage_bytes(int n, int h, int w, int classes, bool own, bool semi, bool with_raw)
+{
+    if (!grad_dims_ok(n, h, w, classes, train_stage_fits)) return -1;
+    Bump b(nullptr, 0);
+    train_stage_carve(b, n, h, w, classes, own);
+    train_semi_carve(b, n, 16 * (int64_t)h * w, classes, semi, with_raw);
+    return b.off + 256;
+}
+
+static int64_t enet_train_stage_bytes(const ssal_enet *net, int n, int h, int w, bool semi, bool with_raw)
+{
+    if (!net_dims_ok(net, n, h, w)) return -1;
+    return behind_trunk_bytes(net, n, h, w, train_stage_bytes(n, h / 4, w / 4, net->classes, false, semi, with_raw));
+}
+
+// b, need, trunk and what x4_raw sets off: as for train_block_run.  x4 / x4_raw [n,h,w,64]: Bottleneck4_2 of the training /
+// the undistorted frames with their pooling indices argmax / argmax_raw; an images entry has both in W.s1a, one after the other,
+// gives no indices (trunk leaves the window codes in `code`) and has Bottleneck5_0 written to a5, where the forward leaves it.
+template <typename Trunk>
+static int train_stage_run(Bump &b, int64_t need, Trunk trunk, const float *x4, const int64_t *argmax, const float *x4_raw,
+                           const int64_t *argmax_raw, float *a5, uint8_t *code, int n, int h, int w, int classes,
+                           const float *params_dev, int max_workgroups, const CallArgs &a, const SemiArgs *semi)
+{
+    TrainStageWs t = train_stage_carve(b, n, h, w, classes, a5 == nullptr);
+    const TrainSemiWs sw = train_semi_carve(b, n, 16 * (int64_t)h * w, classes, semi != nullptr, semi && semi->with_raw);
+    if (int rc = ws_check(need, b, a)) return rc;
+    t.a5 = a5 ? a5 : t.a5;  // an images entry: both live in the forward workspace
+    t.code = a5 ? code : t.code;
+    return with_confusion(sw.rep, classes, semi ? semi->confusion : nullptr, a.s, [&](unsigned long long *rep, int reps) -> int {
+        TrainBlockSemi sa = {};
+        if (semi) sa = train_semi_args(*semi, sw, rep, reps);
+        if (x4_raw) {
+            if (int rc = trunk(true)) return rc;
+            HIP_TRY(launch_train_stage_targets(x4_raw, argmax_raw, n, h, w, classes, params_dev, max_workgroups, t, sa, a.s));
+        }
+        if (int rc = trunk(false)) return rc;
+        HIP_TRY(launch_train_stage_grad(x4, argmax, n, h, w, classes, params_dev, a.labels, a.mask, a.weight, a.label_smoothing,
+                                        max_workgroups, t, a.loss, a.grad, a.s, semi ? &sa : nullptr));
+        return SSAL_OK;
+    });
+}
+
+static int train_stage_grad_entry(const float *features_dev, const int64_t *argmax_dev, const float *features_raw_dev,
+                                  const int64_t *argmax_raw_dev, int n, int h, int w, int classes, const float *params_dev,
+                                  int max_workgroups, const CallArgs &a, const SemiArgs *semi)
+{
+    if (int rc = train_stage_check(n, h, w, classes, max_workgroups)) return rc;
+    if (int rc = args_check(features_dev && argmax_dev && params_dev, a, semi)) return rc;
+    if ((features_raw_dev == nullptr) != (argmax_raw_dev == nullptr))
+        return fail(SSAL_EINVAL, "features_raw_dev and argmax_raw_dev are given together or not at all");
+    Bump b(a.ws, a.ws_bytes);
+    return train_stage_run(b, train_stage_bytes(n, h, w, classes, true, semi != nullptr, features_raw_dev != nullptr), no_trunk,
+                           features_dev, argmax_dev, features_raw_dev, argmax_raw_dev, nullptr, nullptr, n, h, w, classes,
+                           params_dev, max_workgroups, a, semi);
+}
+
+static int enet_train_stage_entry(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h, int w,
+                                  const float *params_dev, int max_workgroups, const CallArgs &a, const SemiArgs *semi)
+{
+    int rc = check_dims(net, n, h, w);
+    if (rc) return rc;
+    if ((rc = train_stage_check(n, h / 4, w / 4, net->classes, max_workgroups))) return rc;
+    if ((rc = args_check(x_dev && params_dev, a, semi))) return rc;
+    NetWorkspace W;
+    Bump b = carve_behind_trunk(net, a, n, h, w, &W);
+    // the frozen trunk is Initial .. Bottleneck4_2 (its output lands in W.s1a, the window codes of Bottleneck1_0's pooling
+    // in W.code1); Bottleneck5_0 runs from params_dev into W.a0, where the forward leaves it
+    auto trunk = [&](bool of_raw) {
+        return run_trunk(net, kNumLayers - 3, of_raw ? x_raw_dev : x_dev, x_is_u8, W, n, h, w, a.s);
+    };
+    return train_stage_run(b, enet_train_stage_bytes(net, n, h, w, semi != nullptr, x_raw_dev != nullptr), trunk, W.s1a,
+                           nullptr, x_raw_dev && semi->labelled ? W.s1a : nullptr, nullptr, W.a0, W.code1, n, h / 4, w / 4,
+                           net->classes, params_dev, max_workgroups, a, semi);
+}
+
 SSAL_API int64_t ssal_train_stage_param_floats(int classes)
 {
-    if (classes < 2 || classes > 32) return -1;
-    return train_stage_floats(classes);
+    return classes < 2 || classes > 32 ? -1 : train_stage_floats(classes);
 }
 
 SSAL_API int64_t ssal_train_stage_grad_workspace_bytes(int n, int h, int w, int classes)
 {
-    if (classes < 2 || classes > 32 || n <= 0 || h <= 0 || w <= 0 || !train_stage_fits(h, w)) return -1;
-    Bump b(nullptr, 0);
-    train_stage_carve(b, n, h, w, classes, true);
-    return b.off + 256;
+    return train_stage_bytes(n, h, w, classes, true, false, false);
 }
 
 SSAL_API int ssal_train_stage_grad_nhwc(const float *features_dev, const int64_t *argmax_dev, int n, int h, int w, int classes,
@@ -2052,41 +2264,28 @@ SSAL_API int ssal_train_stage_grad_nhwc(const float *features_dev, const int64_t
                                         float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev,
                                         void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    if (int rc = train_stage_check(n, h, w, classes, max_workgroups)) return rc;
-    if (!features_dev || !argmax_dev || !params_dev || !labels_dev || !mask_dev || !loss_dev || !grad_dev || !ws_dev)
-        return fail(SSAL_EINVAL, "NULL device pointer");
-    const int64_t need = ssal_train_stage_grad_workspace_bytes(n, h, w, classes);
-    if (ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
-                                     (long long)ws_bytes);
-    Bump b(ws_dev, ws_bytes);
-    const TrainStageWs t = train_stage_carve(b, n, h, w, classes, true);
-    if (!b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes", (long long)need);
-    HIP_TRY(launch_train_stage_grad(features_dev, argmax_dev, n, h, w, classes, params_dev, labels_dev, mask_dev, weight,
-                                    label_smoothing, max_workgroups, t, loss_dev, grad_dev, (hipStream_t)stream));
-    return SSAL_OK;
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return train_stage_grad_entry(features_dev, argmax_dev, nullptr, nullptr, n, h, w, classes, params_dev, max_workgroups, a,
+                                  nullptr);
 }
 
 SSAL_API int64_t ssal_enet_train_stage_workspace_bytes(const ssal_enet *net, int n, int h, int w)
 {
-    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 8 || w % 8) return -1;
-    if (net->classes < 2 || net->classes > 32 || !train_stage_fits(h / 4, w / 4)) return -1;
-    Bump b(nullptr, 0);
-    train_stage_carve(b, n, h / 4, w / 4, net->classes, false);
-    return carve(net, nullptr, 0, n, h, w).bytes + 256 + b.off + 256;
+    return enet_train_stage_bytes(net, n, h, w, false, false);
 }
 
 // byte offsets (into the workspace passed to forward / score / train_stage) of Bottleneck4_2's output [n,h/4,w/4,64] and of
 // the window codes [n,h/4,w/4,16] of Bottleneck1_0's pooling; valid until the next call.  -1 for dims the net does not take.
 SSAL_API int64_t ssal_enet_train_stage_features_offset(const ssal_enet *net, int n, int h, int w)
 {
-    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 8 || w % 8) return -1;
+    if (!net_dims_ok(net, n, h, w)) return -1;
     NetWorkspace W = carve(net, (void *)256, ((int64_t)1 << 62), n, h, w);
     return (const char *)W.s1a - (const char *)256;
 }
 
 SSAL_API int64_t ssal_enet_train_stage_code_offset(const ssal_enet *net, int n, int h, int w)
 {
-    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 8 || w % 8) return -1;
+    if (!net_dims_ok(net, n, h, w)) return -1;
     NetWorkspace W = carve(net, (void *)256, ((int64_t)1 << 62), n, h, w);
     return (const char *)W.code1 - (const char *)256;
 }
@@ -2096,164 +2295,13 @@ SSAL_API int ssal_enet_train_stage_nhwc(ssal_enet *net, const void *x_dev, int x
                                         float weight, float label_smoothing, int max_workgroups, double *loss_dev,
                                         float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    int rc = check_dims(net, n, h, w);
-    if (rc) return rc;
-    if ((rc = train_stage_check(n, h / 4, w / 4, net->classes, max_workgroups))) return rc;
-    if (!x_dev || !labels_dev || !mask_dev || !params_dev || !loss_dev || !grad_dev || !ws_dev)
-        return fail(SSAL_EINVAL, "NULL device pointer");
-    const int64_t need = ssal_enet_train_stage_workspace_bytes(net, n, h, w);
-    if (ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
-                                     (long long)ws_bytes);
-    NetWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
-    char *gws = (char *)ws_dev + (W.bytes + 255) / 256 * 256;
-    Bump b(gws, ws_bytes - (gws - (char *)ws_dev));
-    TrainStageWs t = train_stage_carve(b, n, h / 4, w / 4, net->classes, false);
-    if (!W.ok || !b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes", (long long)need);
-    hipStream_t s = (hipStream_t)stream;
-    // the frozen trunk, training=False: Initial .. Bottleneck4_2 on the caller's stream (its output lands in W.s1a, the window
-    // codes of Bottleneck1_0's pooling in W.code1); Bottleneck5_0 runs from params_dev into W.a0, where the forward leaves it
-    for (int li = 0; li < kNumLayers - 3; ++li) HIP_TRY(run_layer_idx(net, li, x_dev, x_is_u8 != 0, W, n, h, w, s));
-    t.a5 = W.a0;
-    t.code = W.code1;
-    HIP_TRY(launch_train_stage_grad(W.s1a, nullptr, n, h / 4, w / 4, net->classes, params_dev, labels_dev, mask_dev, weight,
-                                    label_smoothing, max_workgroups, t, loss_dev, grad_dev, s));
-    return SSAL_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// The semi-supervised step of the last-block and last-stage trainers (include/ssal_enet.h, "The semi-supervised step of the
-// deeper trainers").  Workspace: the plain entry's, then the confusion replicas, then (with_raw) the
-// packed pseudo-target plane of the undistorted frames, one byte per output pixel.
-// ------------------------------------------------------------------------------------------------
-struct TrainSemiWs {
-    unsigned long long *rep;
-    uint8_t *tgt;
-};
-
-// out_pix = output pixels per image ([2h, 2w] of the block's map)
-static TrainSemiWs train_semi_carve(Bump &b, int64_t n, int64_t out_pix, int classes, bool with_raw)
-{
-    TrainSemiWs t;
-    t.rep = b.take<unsigned long long>((int64_t)ssal::kConfMaxReps * ssal::conf_rep_stride(classes * classes));
-    t.tgt = with_raw ? b.take<uint8_t>(n * out_pix) : nullptr;
-    return t;
-}
-
-static TrainBlockSemi train_semi_args(const TrainSemiWs &sw, const uint8_t *labelled_dev, int measure, float threshold,
-                                      bool with_raw, int64_t *confusion_dev, int64_t *pseudo_pixels_dev)
-{
-    TrainBlockSemi sa;
-    sa.labelled = labelled_dev;
-    sa.measure = measure;
-    sa.threshold = threshold;
-    sa.tgt = sw.tgt;
-    sa.use_tgt = with_raw && labelled_dev;
-    sa.rep = confusion_dev ? sw.rep : nullptr;
-    sa.reps = ssal::knobs().conf_reps;
-    sa.pseudo_pixels = pseudo_pixels_dev;
-    return sa;
-}
-
-static int train_semi_zero(const TrainBlockSemi &sa, int classes, hipStream_t s)
-{
-    if (sa.rep) HIP_TRY(hipMemsetAsync(sa.rep, 0, (size_t)sa.reps * ssal::conf_rep_stride(classes * classes) * 8, s));
-    return SSAL_OK;
-}
-
-static int train_semi_fold(const TrainBlockSemi &sa, int classes, int64_t *confusion_dev, hipStream_t s)
-{
-    if (sa.rep) HIP_TRY(launch_confusion_fold(sa.rep, sa.reps, classes, confusion_dev, s));
-    return SSAL_OK;
-}
-
-SSAL_API int64_t ssal_train_block_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw)
-{
-    if (classes < 2 || classes > 32 || n <= 0 || h <= 0 || w <= 0 || !train_block_fits(h, w)) return -1;
-    Bump b(nullptr, 0);
-    train_block_carve(b, n, h, w, classes);
-    train_semi_carve(b, n, 4 * (int64_t)h * w, classes, with_raw != 0);
-    return b.off + 256;
-}
-
-SSAL_API int ssal_train_block_grad_semi_nhwc(const float *features_dev, const float *features_raw_dev, int n, int h, int w,
-                                             int classes, const float *params_dev, const uint8_t *labels_dev,
-                                             const float *mask_dev, const uint8_t *labelled_dev, int measure,
-                                             float threshold, float weight, float label_smoothing, double *loss_dev,
-                                             float *grad_dev, int64_t *confusion_dev, int64_t *pseudo_pixels_dev,
-                                             void *ws_dev, int64_t ws_bytes, void *stream)
-{
-    if (int rc = final_grad_check(n, h, w, classes)) return rc;
-    if (int rc = final_grad_semi_check(measure, labels_dev, mask_dev, labelled_dev)) return rc;
-    if (!features_dev || !params_dev || !loss_dev || !grad_dev || !ws_dev) return fail(SSAL_EINVAL, "NULL device pointer");
-    const bool raw = features_raw_dev != nullptr;
-    const int64_t need = ssal_train_block_grad_semi_workspace_bytes(n, h, w, classes, raw);
-    if (ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
-                                     (long long)ws_bytes);
-    Bump b(ws_dev, ws_bytes);
-    const TrainBlockWs t = train_block_carve(b, n, h, w, classes);
-    const TrainSemiWs sw = train_semi_carve(b, n, 4 * (int64_t)h * w, classes, raw);
-    if (!b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes", (long long)need);
-    hipStream_t s = (hipStream_t)stream;
-    const TrainBlockSemi sa = train_semi_args(sw, labelled_dev, measure, threshold, raw, confusion_dev, pseudo_pixels_dev);
-    if (int rc = train_semi_zero(sa, classes, s)) return rc;
-    if (raw) HIP_TRY(launch_train_block_targets(features_raw_dev, n, h, w, classes, params_dev, sa, t, s));
-    HIP_TRY(launch_train_block_grad(features_dev, n, h, w, classes, params_dev, labels_dev, mask_dev, weight,
-                                    label_smoothing, t, loss_dev, grad_dev, s, nullptr, 0, &sa));
-    return train_semi_fold(sa, classes, confusion_dev, s);
-}
-
-SSAL_API int64_t ssal_enet_train_block_semi_workspace_bytes(const ssal_enet *net, int n, int h, int w, int with_raw)
-{
-    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 8 || w % 8) return -1;
-    const int64_t g = ssal_train_block_grad_semi_workspace_bytes(n, h / 2, w / 2, net->classes, with_raw);
-    if (g < 0) return -1;
-    return carve(net, nullptr, 0, n, h, w).bytes + 256 + g;
-}
-
-SSAL_API int ssal_enet_train_block_semi_nhwc(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
-                                             int h, int w, const uint8_t *labels_dev, const float *mask_dev,
-                                             const uint8_t *labelled_dev, int measure, float threshold,
-                                             const float *params_dev, float weight, float label_smoothing,
-                                             double *loss_dev, float *grad_dev, int64_t *confusion_dev,
-                                             int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
-{
-    int rc = check_dims(net, n, h, w);
-    if (rc) return rc;
-    if ((rc = final_grad_check(n, h / 2, w / 2, net->classes))) return rc;
-    if ((rc = final_grad_semi_check(measure, labels_dev, mask_dev, labelled_dev))) return rc;
-    if (!x_dev || !params_dev || !loss_dev || !grad_dev || !ws_dev) return fail(SSAL_EINVAL, "NULL device pointer");
-    const bool raw = x_raw_dev != nullptr;
-    const int64_t need = ssal_enet_train_block_semi_workspace_bytes(net, n, h, w, raw);
-    if (ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
-                                     (long long)ws_bytes);
-    NetWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
-    char *gws = (char *)ws_dev + (W.bytes + 255) / 256 * 256;
-    Bump b(gws, ws_bytes - (gws - (char *)ws_dev));
-    const TrainBlockWs t = train_block_carve(b, n, h / 2, w / 2, net->classes);
-    const TrainSemiWs sw = train_semi_carve(b, n, (int64_t)h * w, net->classes, raw);
-    if (!W.ok || !b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes", (long long)need);
-    hipStream_t s = (hipStream_t)stream;
-    const TrainBlockSemi sa = train_semi_args(sw, labelled_dev, measure, threshold, raw, confusion_dev, pseudo_pixels_dev);
-    if ((rc = train_semi_zero(sa, net->classes, s))) return rc;
-    // the frozen trunk on the undistorted frames first: their Bottleneck5_0 output (W.a0) is consumed by the target-only
-    // launch, which leaves one byte per output pixel, so the training frames can go through the same slots afterwards
-    if (raw && labelled_dev) {
-        for (int li = 0; li < kNumLayers - 2; ++li) HIP_TRY(run_layer_idx(net, li, x_raw_dev, x_is_u8 != 0, W, n, h, w, s));
-        HIP_TRY(launch_train_block_targets(W.a0, n, h / 2, w / 2, net->classes, params_dev, sa, t, s));
-    }
-    for (int li = 0; li < kNumLayers - 2; ++li) HIP_TRY(run_layer_idx(net, li, x_dev, x_is_u8 != 0, W, n, h, w, s));
-    HIP_TRY(launch_train_block_grad(W.a0, n, h / 2, w / 2, net->classes, params_dev, labels_dev, mask_dev, weight,
-                                    label_smoothing, t, loss_dev, grad_dev, s, nullptr, 0, &sa));
-    return train_semi_fold(sa, net->classes, confusion_dev, s);
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return enet_train_stage_entry(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, max_workgroups, a, nullptr);
 }
 
 SSAL_API int64_t ssal_train_stage_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw)
 {
-    if (classes < 2 || classes > 32 || n <= 0 || h <= 0 || w <= 0 || !train_stage_fits(h, w)) return -1;
-    Bump b(nullptr, 0);
-    train_stage_carve(b, n, h, w, classes, true);
-    train_semi_carve(b, n, 16 * (int64_t)h * w, classes, with_raw != 0);
-    return b.off + 256;
+    return train_stage_bytes(n, h, w, classes, true, true, with_raw != 0);
 }
 
 SSAL_API int ssal_train_stage_grad_semi_nhwc(const float *features_dev, const int64_t *argmax_dev,
@@ -2264,38 +2312,15 @@ SSAL_API int ssal_train_stage_grad_semi_nhwc(const float *features_dev, const in
                                              double *loss_dev, float *grad_dev, int64_t *confusion_dev,
                                              int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    if (int rc = train_stage_check(n, h, w, classes, max_workgroups)) return rc;
-    if (int rc = final_grad_semi_check(measure, labels_dev, mask_dev, labelled_dev)) return rc;
-    if (!features_dev || !argmax_dev || !params_dev || !loss_dev || !grad_dev || !ws_dev)
-        return fail(SSAL_EINVAL, "NULL device pointer");
-    if ((features_raw_dev == nullptr) != (argmax_raw_dev == nullptr))
-        return fail(SSAL_EINVAL, "features_raw_dev and argmax_raw_dev are given together or not at all");
-    const bool raw = features_raw_dev != nullptr;
-    const int64_t need = ssal_train_stage_grad_semi_workspace_bytes(n, h, w, classes, raw);
-    if (ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
-                                     (long long)ws_bytes);
-    Bump b(ws_dev, ws_bytes);
-    const TrainStageWs t = train_stage_carve(b, n, h, w, classes, true);
-    const TrainSemiWs sw = train_semi_carve(b, n, 16 * (int64_t)h * w, classes, raw);
-    if (!b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes", (long long)need);
-    hipStream_t s = (hipStream_t)stream;
-    const TrainBlockSemi sa = train_semi_args(sw, labelled_dev, measure, threshold, raw, confusion_dev, pseudo_pixels_dev);
-    if (int rc = train_semi_zero(sa, classes, s)) return rc;
-    if (raw) HIP_TRY(launch_train_stage_targets(features_raw_dev, argmax_raw_dev, n, h, w, classes, params_dev, max_workgroups,
-                                                t, sa, s));
-    HIP_TRY(launch_train_stage_grad(features_dev, argmax_dev, n, h, w, classes, params_dev, labels_dev, mask_dev, weight,
-                                    label_smoothing, max_workgroups, t, loss_dev, grad_dev, s, &sa));
-    return train_semi_fold(sa, classes, confusion_dev, s);
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, features_raw_dev != nullptr};
+    return train_stage_grad_entry(features_dev, argmax_dev, features_raw_dev, argmax_raw_dev, n, h, w, classes, params_dev,
+                                  max_workgroups, a, &semi);
 }
 
 SSAL_API int64_t ssal_enet_train_stage_semi_workspace_bytes(const ssal_enet *net, int n, int h, int w, int with_raw)
 {
-    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 8 || w % 8) return -1;
-    if (net->classes < 2 || net->classes > 32 || !train_stage_fits(h / 4, w / 4)) return -1;
-    Bump b(nullptr, 0);
-    train_stage_carve(b, n, h / 4, w / 4, net->classes, false);
-    train_semi_carve(b, n, (int64_t)h * w, net->classes, with_raw != 0);
-    return carve(net, nullptr, 0, n, h, w).bytes + 256 + b.off + 256;
+    return enet_train_stage_bytes(net, n, h, w, true, with_raw != 0);
 }
 
 SSAL_API int ssal_enet_train_stage_semi_nhwc(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
@@ -2305,34 +2330,7 @@ SSAL_API int ssal_enet_train_stage_semi_nhwc(ssal_enet *net, const void *x_dev, 
                                              int max_workgroups, double *loss_dev, float *grad_dev, int64_t *confusion_dev,
                                              int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    int rc = check_dims(net, n, h, w);
-    if (rc) return rc;
-    if ((rc = train_stage_check(n, h / 4, w / 4, net->classes, max_workgroups))) return rc;
-    if ((rc = final_grad_semi_check(measure, labels_dev, mask_dev, labelled_dev))) return rc;
-    if (!x_dev || !params_dev || !loss_dev || !grad_dev || !ws_dev) return fail(SSAL_EINVAL, "NULL device pointer");
-    const bool raw = x_raw_dev != nullptr;
-    const int64_t need = ssal_enet_train_stage_semi_workspace_bytes(net, n, h, w, raw);
-    if (ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
-                                     (long long)ws_bytes);
-    NetWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
-    char *gws = (char *)ws_dev + (W.bytes + 255) / 256 * 256;
-    Bump b(gws, ws_bytes - (gws - (char *)ws_dev));
-    TrainStageWs t = train_stage_carve(b, n, h / 4, w / 4, net->classes, false);
-    const TrainSemiWs sw = train_semi_carve(b, n, (int64_t)h * w, net->classes, raw);
-    if (!W.ok || !b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes", (long long)need);
-    hipStream_t s = (hipStream_t)stream;
-    t.a5 = W.a0;
-    t.code = W.code1;
-    const TrainBlockSemi sa = train_semi_args(sw, labelled_dev, measure, threshold, raw, confusion_dev, pseudo_pixels_dev);
-    if ((rc = train_semi_zero(sa, net->classes, s))) return rc;
-    // the frozen trunk on the undistorted frames first (Bottleneck4_2 in W.s1a, their own window codes in W.code1), the
-    // stage's forward on them and the target-only launch; then the training frames through the same slots
-    if (raw && labelled_dev) {
-        for (int li = 0; li < kNumLayers - 3; ++li) HIP_TRY(run_layer_idx(net, li, x_raw_dev, x_is_u8 != 0, W, n, h, w, s));
-        HIP_TRY(launch_train_stage_targets(W.s1a, nullptr, n, h / 4, w / 4, net->classes, params_dev, max_workgroups, t, sa, s));
-    }
-    for (int li = 0; li < kNumLayers - 3; ++li) HIP_TRY(run_layer_idx(net, li, x_dev, x_is_u8 != 0, W, n, h, w, s));
-    HIP_TRY(launch_train_stage_grad(W.s1a, nullptr, n, h / 4, w / 4, net->classes, params_dev, labels_dev, mask_dev, weight,
-                                    label_smoothing, max_workgroups, t, loss_dev, grad_dev, s, &sa));
-    return train_semi_fold(sa, net->classes, confusion_dev, s);
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev != nullptr};
+    return enet_train_stage_entry(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, max_workgroups, a, &semi);
 }

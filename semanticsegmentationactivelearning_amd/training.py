@@ -45,8 +45,8 @@ class FinalLayerTrainer:
         self.measure, self.threshold = measure, float(threshold)  # defaults of the pseudo annotation's keywords
         self._dev = None  # device tensors: w, m, v, grad, loss
         self._t = 0
-        self._b1p, self._b2p = np.float32(self.beta1), np.float32(self.beta2)  # AdamOptimizer's beta powers (fp32)
-        self._m0 = self._v0 = None
+        self._reset_beta_powers()  # AdamOptimizer's beta powers (fp32)
+        self._m0 = self._v0 = None  # host copies of Adam's slots waiting for the device
 
     @classmethod
     def from_params(cls, net, params, decay_steps=None):
@@ -82,17 +82,59 @@ class FinalLayerTrainer:
         initializer, drawn from ``seed``.  The optimizer state is reset too."""
         var = self._kernel_var()
         var.assign(_mod.glorot_uniform(seed)(var.shape))
-        self.load_state({"m": np.zeros(var.shape, np.float32), "v": np.zeros(var.shape, np.float32), "t": 0})
+        self.load_state({"m": self._state_view(self._zero_state()), "v": self._state_view(self._zero_state()), "t": 0})
+
+    # the hooks the shared state and Adam code stands on (LastBlockTrainer: the packed block)
+    def _host_weights(self):
+        """the trained weights of the host model as one float32 array"""
+        return np.array(self._kernel_var().numpy(), dtype=np.float32)
+
+    def _zero_state(self):
+        return np.zeros(self._kernel_var().shape, np.float32)
+
+    def _version_key(self):
+        return self._kernel_var().version
+
+    def _state_view(self, a):
+        """one of Adam's slots as ``state`` presents it"""
+        return a.copy()
+
+    def _trained_tail(self):
+        """how many of ``net.variables``, counted from the end, the training kernels take as an argument"""
+        return 1
+
+    def _adam_ranges(self):
+        """(lo, hi, regularised) ranges of the flattened weights Adam runs on"""
+        return ((0, int(np.prod(self._kernel_var().shape)), True),)
+
+    def _write_back(self, host):
+        self.net.Final.kernel.assign(host)
+
+    def _advance_beta_powers(self):
+        self._b1p = np.float32(self._b1p * np.float32(self.beta1))
+        self._b2p = np.float32(self._b2p * np.float32(self.beta2))
+
+    def _reset_beta_powers(self):
+        """the beta powers as AdamOptimizer holds them before step ``t`` + 1 (fp32 products)"""
+        self._b1p = self._b2p = np.float32(1.0)
+        for _ in range(self._t + 1):
+            self._advance_beta_powers()
 
     @property
     def state(self):
         """``{"m", "v"}`` float32 host copies of Adam's slots and ``"t"`` (steps taken)"""
         if self._dev is None:
-            shape = self._kernel_var().shape
-            m = self._m0 if self._m0 is not None else np.zeros(shape, np.float32)
-            v = self._v0 if self._v0 is not None else np.zeros(shape, np.float32)
-            return {"m": m.copy(), "v": v.copy(), "t": self._t}
-        return {"m": self._dev["m"].cpu().numpy(), "v": self._dev["v"].cpu().numpy(), "t": self._t}
+            m = self._m0 if self._m0 is not None else self._zero_state()
+            v = self._v0 if self._v0 is not None else self._zero_state()
+        else:
+            m, v = self._dev["m"].cpu().numpy(), self._dev["v"].cpu().numpy()
+        return {"m": self._state_view(m), "v": self._state_view(v), "t": self._t}
+
+    def _set_state(self, m, v, t):
+        self._t = int(t)
+        self._reset_beta_powers()
+        self._m0, self._v0 = m, v
+        self._dev = None
 
     def load_state(self, state):
         shape = self._kernel_var().shape
@@ -100,14 +142,7 @@ class FinalLayerTrainer:
         v = np.ascontiguousarray(state["v"], dtype=np.float32)
         if m.shape != shape or v.shape != shape:
             raise ValueError("m / v must have shape %s" % (shape,))
-        self._t = int(state["t"])
-        self._b1p = np.float32(1.0)
-        self._b2p = np.float32(1.0)
-        for _ in range(self._t + 1):  # beta powers as AdamOptimizer holds them before step t + 1 (fp32 products)
-            self._b1p = np.float32(self._b1p * np.float32(self.beta1))
-            self._b2p = np.float32(self._b2p * np.float32(self.beta2))
-        self._m0, self._v0 = m, v
-        self._dev = None
+        self._set_state(m, v, state["t"])
 
     def current_learning_rate(self):
         """tf.train.inverse_time_decay(lr, global_step, decay_steps, decay_rate) (not staircase), fp32 as TF computes it;
@@ -120,22 +155,47 @@ class FinalLayerTrainer:
 
     def _device_state(self, device):
         torch = _lib.require_gpu()
-        var = self._kernel_var()
-        if self._dev is None or self._dev["w"].device != device or self._dev["version"] != var.version:
-            shape = var.shape
-            m = self._m0 if self._m0 is not None else (self._dev["m"].cpu().numpy() if self._dev else np.zeros(shape, np.float32))
-            v = self._v0 if self._v0 is not None else (self._dev["v"].cpu().numpy() if self._dev else np.zeros(shape, np.float32))
-            self._dev = {
-                "w": torch.from_numpy(np.array(var.numpy(), dtype=np.float32)).to(device),
-                "m": torch.from_numpy(np.array(m)).to(device),
-                "v": torch.from_numpy(np.array(v)).to(device),
-                "grad": torch.empty(shape, dtype=torch.float32, device=device),
-                "version": var.version,
-            }
+        ver = self._version_key()
+        if self._dev is None or self._dev["w"].device != device or self._dev["version"] != ver:
+            m = self._m0 if self._m0 is not None else (self._dev["m"].cpu().numpy() if self._dev else self._zero_state())
+            v = self._v0 if self._v0 is not None else (self._dev["v"].cpu().numpy() if self._dev else self._zero_state())
+            w = torch.from_numpy(self._host_weights()).to(device)
+            self._dev = {"w": w, "m": torch.from_numpy(np.array(m)).to(device), "v": torch.from_numpy(np.array(v)).to(device),
+                         "grad": torch.empty_like(w), "version": ver}
             self._m0 = self._v0 = None
         return self._dev
 
-    # ---- gradients ---------------------------------------------------------------------------------------------------
+    def _trunk_handle(self):
+        """the net's handle for the current device: reused while every variable BELOW the trained tail is unchanged (the
+        training entries take the trained weights as an argument), so the whole weight set (1.5 MB) is pushed and committed
+        again only when a TRUNK variable changed.  The handle's pushed-versions record keeps the old versions, so the next
+        score / evaluate / call pushes the new weights once."""
+        torch = _lib.require_gpu()
+        net = self.net
+        ent = net._handles.get(torch.cuda.current_device())
+        tail = self._trained_tail()
+        if ent is not None and ent[1] is not None:
+            if tuple(v.version for v in net.variables)[:-tail] == ent[1][:-tail]:
+                return ent[0]
+        return net._sync_handle()
+
+    def _apply(self, dev, grad):
+        lr = self.current_learning_rate()
+        L = _lib.lib()
+        w, m, v, g = (t.view(-1) for t in (dev["w"], dev["m"], dev["v"], grad))
+        for lo, hi, reg in self._adam_ranges():
+            _lib.check(L.ssal_adam_apply(_lib.dev_ptr(w[lo:hi]), _lib.dev_ptr(m[lo:hi]), _lib.dev_ptr(v[lo:hi]),
+                                         _lib.dev_ptr(g[lo:hi]), hi - lo, float(lr), self.beta1, self.beta2, self.epsilon,
+                                         float(self._b1p), float(self._b2p), self.l1 if reg else 0.0,
+                                         self.l2 if reg else 0.0, _lib.stream_ptr()))
+        self._t += 1
+        self._advance_beta_powers()
+        # the host variables are the model's weights of record: score / evaluate / __call__ push them on their next call
+        # (synchronises the stream: 11 KB for the output layer, 12.5 KB for the last block at K = 19)
+        self._write_back(dev["w"].cpu().numpy())
+        dev["version"] = self._version_key()
+
+    # ---- arguments ---------------------------------------------------------------------------------------------------
     def _targets(self, labels, mask, shape, device):
         torch = _lib.require_gpu()
         lab = labels if isinstance(labels, torch.Tensor) else torch.as_tensor(np.asarray(labels))
@@ -147,6 +207,25 @@ class FinalLayerTrainer:
         lab = lab.to(device=device, dtype=torch.uint8).contiguous()
         mk = mk.to(device=device, dtype=torch.float32).contiguous()
         return lab, mk
+
+    _semi_keywords = True  # False: every semi-supervised keyword is refused (LastBlockTrainer, LastStageTrainer)
+
+    @staticmethod
+    def _no_semi(**kw):
+        for name, value in kw.items():
+            if value is not None and value is not False:
+                raise NotImplementedError("%s: the semi-supervised step is implemented for the output layer only "
+                                          "(FinalLayerTrainer)" % name)
+
+    def _semi_call(self, batch, labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels, **raw):
+        """the semi-supervised keywords of a call, before anything else is looked at: refused by the classes that do not take
+        them, else ``_semi``'s verdict for the batch ``batch`` leads"""
+        if not self._semi_keywords:
+            self._no_semi(labelled=labelled, measure=measure, threshold=threshold, confusion=confusion,
+                          return_pseudo_pixels=return_pseudo_pixels, **raw)
+            return None
+        n = int(np.shape(batch)[0]) if len(np.shape(batch)) else 0
+        return self._semi(n, labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels)
 
     def _semi(self, n, labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels):
         """the semi-supervised keywords, judged on the host before any device work: None when the call is today's plain
@@ -172,8 +251,10 @@ class FinalLayerTrainer:
         return labelled, _lib.MEASURES[measure], threshold
 
     def _semi_device(self, semi, n, device, labels, mask, shape):
-        """device forms of the semi-supervised arguments: labelled uint8 [n] (or None), label / mask planes (or None), the
-        pseudo-pixel counts"""
+        """device forms of the targets: labelled uint8 [n] (or None), label / mask planes (None only in a semi call that
+        gives none); a plain call (``semi`` None) needs both planes"""
+        if semi is None:
+            return (None,) + self._targets(labels, mask, shape, device)
         torch = _lib.require_gpu()
         labelled = semi[0]
         if labelled is not None:
@@ -184,6 +265,93 @@ class FinalLayerTrainer:
             lab, mk = self._targets(labels, mask, shape, device)
         return labelled, lab, mk
 
+    @staticmethod
+    def _semi_c_args(semi, labelled_dev, confusion, pseudo_pixels):
+        """what a semi entry takes beyond its plain sibling: (the arguments after the mask, those after the gradient)"""
+        if semi is None:
+            return (), ()
+        torch = _lib.require_gpu()
+        return ((_lib.dev_ptr(labelled_dev), semi[1], semi[2]),
+                (_lib.dev_ptr(confusion, torch.int64, "confusion"), _lib.dev_ptr(pseudo_pixels)))
+
+    # ---- the two C calls: (plain stem, semi stem) of the entries, + "_workspace_bytes" / "_nhwc" ------------------------------
+    _C_FEATURES = ("ssal_final_grad", "ssal_final_grad_semi")
+    _C_IMAGES = ("ssal_enet_train_final", "ssal_enet_train_final_semi")
+    _CHANNELS, _UP = 16, 2  # of the feature map the features entry takes; output pixels per feature pixel and axis
+    _LIMIT = ("kernel's", "kernel's")  # the wording of a plain / a semi call's "beyond the limit" error
+
+    def _features_workspace_bytes(self, query, n, h, w, k, semi, with_raw):
+        """the features entry's workspace query (here the raw features are the caller's: no ``with_raw``)"""
+        return query(n, h, w, k)
+
+    def _grad_call(self, x, x_raw, labels, mask, params_dev, semi, confusion, return_pseudo_pixels, extra=()):
+        """(loss [1] float64, gradient shaped like ``params_dev``, pseudo pixels or None) through the features entry: the plain
+        one, or with ``semi`` the semi-supervised one.  ``x`` / ``x_raw``: the entry's leading device tensors (features[, pooling
+        indices]) of the training / the undistorted frames (``x_raw`` all None: no raw side); ``extra``: the arguments
+        between the loss' knobs and the outputs"""
+        torch = _lib.require_gpu()
+        f = x[0]
+        if f.dim() != 4 or f.shape[-1] != self._CHANNELS:
+            raise ValueError("features must be [N,h,w,%d] (got %s)" % (self._CHANNELS, tuple(f.shape)))
+        n, h, w, _ = f.shape
+        k = int(self.net.classes)
+        lbd, lab, mk = self._semi_device(semi, n, f.device, labels, mask, (n, self._UP * h, self._UP * w))
+        L = _lib.lib()
+        stem = self._C_FEATURES[semi is not None]
+        with torch.cuda.device(f.device):
+            nbytes = self._features_workspace_bytes(getattr(L, stem + "_workspace_bytes"), n, h, w, k, semi is not None,
+                                                    int(x_raw[0] is not None))
+            if nbytes < 0:
+                raise ValueError("feature map %dx%d is beyond the gradient %s limit" % (h, w, self._LIMIT[semi is not None]))
+            ws = torch.empty(int(nbytes), dtype=torch.uint8, device=f.device)
+            loss = torch.empty((1,), dtype=torch.float64, device=f.device)
+            grad = torch.empty_like(params_dev)
+            pp = torch.empty((n,), dtype=torch.int64, device=f.device) if return_pseudo_pixels else None
+            after_mask, after_grad = self._semi_c_args(semi, lbd, confusion, pp)
+            inputs = tuple(x) + (tuple(x_raw) if semi is not None else ())
+            _lib.check(getattr(L, stem + "_nhwc")(
+                *(tuple(_lib.dev_ptr(t) for t in inputs) + (n, h, w, k, _lib.dev_ptr(params_dev), _lib.dev_ptr(lab),
+                  _lib.dev_ptr(mk)) + after_mask + (self.weight, self.label_smoothing) + tuple(extra)
+                  + (_lib.dev_ptr(loss), _lib.dev_ptr(grad)) + after_grad + (_lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))))
+        return loss, grad, pp
+
+    def _step_images(self, images, images_raw, labels, mask, semi, confusion, return_pseudo_pixels, extra=()):
+        """one Adam step through the images entry (the plain one, or with ``semi`` the semi-supervised one): the frozen
+        trunk, the training kernels, Adam.  -> loss before the step[, pseudo pixels]"""
+        torch = _lib.require_gpu()
+        net = self.net
+        x = net._prepare(images, False)
+        n, h, w, _ = x.shape
+        L = _lib.lib()
+        lbd, lab, mk = self._semi_device(semi, n, x.device, labels, mask, (n, h, w))
+        xr = None
+        if semi is not None and images_raw is not None and images_raw is not images:
+            xr = net._prepare(images_raw, False)
+            if tuple(xr.shape) != tuple(x.shape) or xr.dtype != x.dtype or xr.device != x.device:
+                raise ValueError("images_raw must have the shape and dtype of images %s %s (got %s %s)"
+                                 % (tuple(x.shape), x.dtype, tuple(xr.shape), xr.dtype))
+        stem = self._C_IMAGES[semi is not None]
+        with torch.cuda.device(x.device):
+            dev = self._device_state(x.device)
+            handle = self._trunk_handle()
+            raw = () if semi is None else (xr,)
+            nbytes = getattr(L, stem + "_workspace_bytes")(handle, n, h, w, *(int(t is not None) for t in raw))
+            if nbytes < 0:
+                raise ValueError("bad input dims %s" % (tuple(x.shape),))
+            ws = net._workspace(nbytes, x.device)
+            loss = torch.empty((1,), dtype=torch.float64, device=x.device)
+            pp = torch.empty((n,), dtype=torch.int64, device=x.device) if return_pseudo_pixels else None
+            after_mask, after_grad = self._semi_c_args(semi, lbd, confusion, pp)
+            _lib.check(getattr(L, stem + "_nhwc")(
+                *((handle, _lib.dev_ptr(x)) + tuple(_lib.dev_ptr(t) for t in raw) + (int(x.dtype == torch.uint8), n, h, w,
+                  _lib.dev_ptr(lab), _lib.dev_ptr(mk)) + after_mask + (_lib.dev_ptr(dev["w"]), self.weight,
+                  self.label_smoothing) + tuple(extra) + (_lib.dev_ptr(loss), _lib.dev_ptr(dev["grad"])) + after_grad
+                  + (_lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))))
+            net._note_call(ws, (n, h, w), "train")
+            self._apply(dev, dev["grad"])
+        return (loss[0], pp) if return_pseudo_pixels else loss[0]
+
+    # ---- gradients and steps -------------------------------------------------------------------------------------------
     def gradient_features(self, features, labels, mask, kernel=None, labelled=None, measure=None, threshold=None,
                           features_raw=None, confusion=None, return_pseudo_pixels=False):
         """(loss float64 [1], dL/dW [3, 3, K, 16] fp32) on the device for Bottleneck5_1 features [N, h, w, 16] and
@@ -197,93 +365,30 @@ class FinalLayerTrainer:
         undistorted frames, which the pseudo annotation is then computed from.  ``confusion`` (int64 [K, K] device tensor)
         is added the training-pass confusion matrix of the targets trained on against the argmax of the training logits;
         ``return_pseudo_pixels`` appends the int64 [N] count of pseudo-mask-1 pixels per image to the result."""
-        semi = self._semi(int(np.shape(features)[0]) if len(np.shape(features)) else 0, labels, mask, labelled, measure,
-                          threshold, confusion, return_pseudo_pixels)
-        torch = _lib.require_gpu()
+        semi = self._semi_call(features, labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels)
         x = _lib.as_device_f32(features)
         if x.dim() != 4 or x.shape[-1] != 16:
             raise ValueError("features must be [N,h,w,16] (got %s)" % (tuple(x.shape),))
-        n, h, w, _ = x.shape
         k = self.net.classes
         kern = _lib.as_device_f32(self._kernel_var().numpy() if kernel is None else kernel).to(x.device)
         if tuple(kern.shape) != (3, 3, k, 16):
             raise ValueError("kernel must be [3,3,%d,16] (got %s)" % (k, tuple(kern.shape)))
-        L = _lib.lib()
-        if semi is None:
-            lab, mk = self._targets(labels, mask, (n, 2 * h, 2 * w), x.device)
-            with torch.cuda.device(x.device):
-                nbytes = L.ssal_final_grad_workspace_bytes(n, h, w, k)
-                if nbytes < 0:
-                    raise ValueError("feature map %dx%d is beyond the gradient kernel's limit" % (h, w))
-                ws = torch.empty(int(nbytes), dtype=torch.uint8, device=x.device)
-                loss = torch.empty((1,), dtype=torch.float64, device=x.device)
-                grad = torch.empty((3, 3, k, 16), dtype=torch.float32, device=x.device)
-                _lib.check(L.ssal_final_grad_nhwc(_lib.dev_ptr(x), n, h, w, k, _lib.dev_ptr(kern), _lib.dev_ptr(lab),
-                                                  _lib.dev_ptr(mk), self.weight, self.label_smoothing, _lib.dev_ptr(loss),
-                                                  _lib.dev_ptr(grad), _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))
-            return loss, grad
-        lbd, lab, mk = self._semi_device(semi, n, x.device, labels, mask, (n, 2 * h, 2 * w))
         xr = None
-        if features_raw is not None and features_raw is not features:
+        if semi is not None and features_raw is not None and features_raw is not features:
             xr = _lib.as_device_f32(features_raw).to(x.device)
             if tuple(xr.shape) != tuple(x.shape):
                 raise ValueError("features_raw must have the shape of features %s (got %s)" % (tuple(x.shape), tuple(xr.shape)))
-        with torch.cuda.device(x.device):
-            nbytes = L.ssal_final_grad_semi_workspace_bytes(n, h, w, k)
-            if nbytes < 0:
-                raise ValueError("feature map %dx%d is beyond the gradient kernel's limit" % (h, w))
-            ws = torch.empty(int(nbytes), dtype=torch.uint8, device=x.device)
-            loss = torch.empty((1,), dtype=torch.float64, device=x.device)
-            grad = torch.empty((3, 3, k, 16), dtype=torch.float32, device=x.device)
-            pp = torch.empty((n,), dtype=torch.int64, device=x.device) if return_pseudo_pixels else None
-            _lib.check(L.ssal_final_grad_semi_nhwc(
-                _lib.dev_ptr(x), _lib.dev_ptr(xr), n, h, w, k, _lib.dev_ptr(kern), _lib.dev_ptr(lab), _lib.dev_ptr(mk),
-                _lib.dev_ptr(lbd), semi[1], semi[2], self.weight, self.label_smoothing, _lib.dev_ptr(loss),
-                _lib.dev_ptr(grad), _lib.dev_ptr(confusion, torch.int64, "confusion"), _lib.dev_ptr(pp), _lib.dev_ptr(ws),
-                ws.numel(), _lib.stream_ptr()))
+        loss, grad, pp = self._grad_call((x,), (xr,), labels, mask, kern, semi, confusion, return_pseudo_pixels)
         return (loss, grad, pp) if return_pseudo_pixels else (loss, grad)
-
-    def _trunk_handle(self):
-        """the net's handle for the current device.  Only Final.kernel changes between steps, and this entry takes the
-        kernel as an argument: the whole weight set (1.5 MB) is pushed and committed again only when a TRUNK variable
-        changed.  The handle's pushed-versions record keeps the old Final version, so the next score / evaluate / call
-        pushes the new kernel."""
-        torch = _lib.require_gpu()
-        net = self.net
-        ent = net._handles.get(torch.cuda.current_device())
-        if ent is not None and ent[1] is not None:
-            trunk = tuple(v.version for v in net.variables)[:-1]
-            if trunk == ent[1][:-1]:
-                return ent[0]
-        return net._sync_handle()
-
-    def _apply(self, dev, grad):
-        lr = self.current_learning_rate()
-        _lib.check(_lib.lib().ssal_adam_apply(_lib.dev_ptr(dev["w"]), _lib.dev_ptr(dev["m"]), _lib.dev_ptr(dev["v"]),
-                                              _lib.dev_ptr(grad), dev["w"].numel(), float(lr), self.beta1, self.beta2,
-                                              self.epsilon, float(self._b1p), float(self._b2p), self.l1, self.l2,
-                                              _lib.stream_ptr()))
-        self._t += 1
-        self._b1p = np.float32(self._b1p * np.float32(self.beta1))
-        self._b2p = np.float32(self._b2p * np.float32(self.beta2))
-        # the host variable is the model's weight of record: score / evaluate / __call__ push it on their next call
-        host = dev["w"].cpu().numpy()  # (synchronises the stream: 11 KB at K = 19)
-        self.net.Final.kernel.assign(host)
-        dev["version"] = self.net.Final.kernel.version
 
     def step_features(self, features, labels, mask, labelled=None, measure=None, threshold=None, features_raw=None,
                       confusion=None, return_pseudo_pixels=False):
         """one Adam step from cached Bottleneck5_1 features (``ENet.endpoint_outputs[0][1]``); returns the loss (float64
         device scalar) of the kernel BEFORE the step, as ``sess.run([loss, train_op])`` does.  The keywords are those of
         ``gradient_features``; with ``return_pseudo_pixels`` the result is ``(loss, pseudo_pixels)``."""
-        semi = self._semi(int(np.shape(features)[0]) if len(np.shape(features)) else 0, labels, mask, labelled, measure,
-                          threshold, confusion, return_pseudo_pixels)
+        self._semi_call(features, labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels)
         x = _lib.as_device_f32(features)
         dev = self._device_state(x.device)
-        if semi is None:
-            loss, grad = self.gradient_features(x, labels, mask, kernel=dev["w"])
-            self._apply(dev, grad)
-            return loss[0]
         out = self.gradient_features(x, labels, mask, kernel=dev["w"], labelled=labelled, measure=measure,
                                      threshold=threshold, features_raw=features_raw, confusion=confusion,
                                      return_pseudo_pixels=return_pseudo_pixels)
@@ -299,56 +404,8 @@ class FinalLayerTrainer:
         (the result is then ``(loss, pseudo_pixels)``); ``images_raw``: the undistorted frames (``InputStage``'s ``image``
         next to its ``image_dist``), same shape and dtype as ``images`` -- the trunk runs on them too and the pseudo
         annotation comes from their logits, as the reference's ``pseudo_logits`` do (active_learning.py:231)."""
-        semi = self._semi(int(np.shape(images)[0]) if len(np.shape(images)) else 0, labels, mask, labelled, measure,
-                          threshold, confusion, return_pseudo_pixels)
-        torch = _lib.require_gpu()
-        net = self.net
-        x = net._prepare(images, False)
-        n, h, w, _ = x.shape
-        k = net.classes
-        L = _lib.lib()
-        if semi is None:
-            lab, mk = self._targets(labels, mask, (n, h, w), x.device)
-            with torch.cuda.device(x.device):
-                dev = self._device_state(x.device)
-                handle = self._trunk_handle()
-                nbytes = L.ssal_enet_train_final_workspace_bytes(handle, n, h, w)
-                if nbytes < 0:
-                    raise ValueError("bad input dims %s" % (tuple(x.shape),))
-                ws = net._workspace(nbytes, x.device)
-                loss = torch.empty((1,), dtype=torch.float64, device=x.device)
-                _lib.check(L.ssal_enet_train_final_nhwc(handle, _lib.dev_ptr(x), int(x.dtype == torch.uint8), n, h, w,
-                                                        _lib.dev_ptr(lab), _lib.dev_ptr(mk), _lib.dev_ptr(dev["w"]), self.weight,
-                                                        self.label_smoothing, _lib.dev_ptr(loss), _lib.dev_ptr(dev["grad"]),
-                                                        _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))
-                net._note_call(ws, (n, h, w), "train")
-                self._apply(dev, dev["grad"])
-            return loss[0]
-        lbd, lab, mk = self._semi_device(semi, n, x.device, labels, mask, (n, h, w))
-        xr = None
-        if images_raw is not None and images_raw is not images:
-            xr = net._prepare(images_raw, False)
-            if tuple(xr.shape) != tuple(x.shape) or xr.dtype != x.dtype or xr.device != x.device:
-                raise ValueError("images_raw must have the shape and dtype of images %s %s (got %s %s)"
-                                 % (tuple(x.shape), x.dtype, tuple(xr.shape), xr.dtype))
-        with torch.cuda.device(x.device):
-            dev = self._device_state(x.device)
-            handle = self._trunk_handle()
-            nbytes = L.ssal_enet_train_final_semi_workspace_bytes(handle, n, h, w, int(xr is not None))
-            if nbytes < 0:
-                raise ValueError("bad input dims %s" % (tuple(x.shape),))
-            ws = net._workspace(nbytes, x.device)
-            loss = torch.empty((1,), dtype=torch.float64, device=x.device)
-            pp = torch.empty((n,), dtype=torch.int64, device=x.device) if return_pseudo_pixels else None
-            _lib.check(L.ssal_enet_train_final_semi_nhwc(
-                handle, _lib.dev_ptr(x), _lib.dev_ptr(xr), int(x.dtype == torch.uint8), n, h, w, _lib.dev_ptr(lab),
-                _lib.dev_ptr(mk), _lib.dev_ptr(lbd), semi[1], semi[2], _lib.dev_ptr(dev["w"]), self.weight,
-                self.label_smoothing, _lib.dev_ptr(loss), _lib.dev_ptr(dev["grad"]),
-                _lib.dev_ptr(confusion, torch.int64, "confusion"), _lib.dev_ptr(pp), _lib.dev_ptr(ws), ws.numel(),
-                _lib.stream_ptr()))
-            net._note_call(ws, (n, h, w), "train")
-            self._apply(dev, dev["grad"])
-        return (loss[0], pp) if return_pseudo_pixels else loss[0]
+        semi = self._semi_call(images, labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels)
+        return self._step_images(images, images_raw, labels, mask, semi, confusion, return_pseudo_pixels)
 
 
 # ---- the last block: Bottleneck5_1 + Final (DESIGN.md section 17) ---------------------------------------------------------
@@ -390,9 +447,10 @@ class LastBlockTrainer(FinalLayerTrainer):
     ``state`` / ``load_state``: ``{"m": {name: array}, "v": {name: array}, "t": steps}`` keyed by variable name
     (``"Final.kernel"``, ``"Bottleneck5_1.proj_kernel"``, ...)."""
 
-    def __init__(self, net, *args, **kwargs):
-        super().__init__(net, *args, **kwargs)
-        self._m0 = self._v0 = None  # packed host copies waiting for the device
+    _semi_keywords = False  # SemiSupervisedBlockTrainer accepts them
+    _C_FEATURES = ("ssal_train_block_grad", "ssal_train_block_grad_semi")
+    _C_IMAGES = ("ssal_enet_train_block", "ssal_enet_train_block_semi")
+    _LIMIT = ("kernel's", "kernels'")
 
     @classmethod
     def from_params(cls, net, params, decay_steps=None):
@@ -441,97 +499,51 @@ class LastBlockTrainer(FinalLayerTrainer):
         blk = getattr(self.net, _BLOCK)
         return tuple(v.version for v in [self.net.Final.kernel] + list(blk.variables))
 
-    # ---- state -----------------------------------------------------------------------------------------------------------
-    def reinitialize(self, seed=None):
-        """re-draws ``Final.kernel`` only (as ``FinalLayerTrainer.reinitialize``) and resets all optimiser state"""
-        var = self._kernel_var()
-        var.assign(_mod.glorot_uniform(seed)(var.shape))
-        zeros = {n: np.zeros(v.shape, np.float32) for n, v, _, _ in self._named()}
-        self.load_state({"m": zeros, "v": dict(zeros), "t": 0})
+    # ---- FinalLayerTrainer's hooks: the state and Adam run on the packed block ---------------------------------------------
+    def _host_weights(self):
+        return self._pack()
 
-    @property
-    def state(self):
-        if self._dev is None:
-            zero = np.zeros(self._floats(), np.float32)
-            m = self._m0 if self._m0 is not None else zero
-            v = self._v0 if self._v0 is not None else zero
-        else:
-            m, v = self._dev["m"].cpu().numpy(), self._dev["v"].cpu().numpy()
-        return {"m": self._unpack(m), "v": self._unpack(v), "t": self._t}
+    def _version_key(self):
+        return self._versions()
+
+    def _state_view(self, a):
+        return self._unpack(a)
+
+    def _zero_state(self):
+        return np.zeros(self._floats(), np.float32)
+
+    def _features_workspace_bytes(self, query, n, h, w, k, semi, with_raw):
+        """a semi call's workspace holds the packed target plane of the undistorted frames when there are any"""
+        return query(n, h, w, k, with_raw) if semi else query(n, h, w, k)
+
+    def _trained_tail(self):
+        return len(getattr(self.net, _BLOCK).variables) + 1
+
+    def _adam_ranges(self):
+        return _ADAM_RANGES + ((_FINAL_OFFSET, _FINAL_OFFSET + 144 * int(self.net.classes), True),)
+
+    def _write_back(self, host):
+        for name, var, off, _ in self._named():
+            var.assign(host[off:off + int(np.prod(var.shape))].reshape(var.shape))
 
     def load_state(self, state):
         names = set(self.variable_names)
         for key in ("m", "v"):
             if not isinstance(state[key], dict) or set(state[key]) != names:
                 raise ValueError("state[%r] must map exactly the %d variable names to arrays" % (key, len(names)))
-        m, v = self._pack(state["m"]), self._pack(state["v"])
-        self._t = int(state["t"])
-        self._b1p = np.float32(1.0)
-        self._b2p = np.float32(1.0)
-        for _ in range(self._t + 1):
-            self._b1p = np.float32(self._b1p * np.float32(self.beta1))
-            self._b2p = np.float32(self._b2p * np.float32(self.beta2))
-        self._m0, self._v0 = m, v
-        self._dev = None
+        self._set_state(self._pack(state["m"]), self._pack(state["v"]), state["t"])
 
-    def _device_state(self, device):
-        torch = _lib.require_gpu()
-        ver = self._versions()
-        if self._dev is None or self._dev["w"].device != device or self._dev["version"] != ver:
-            zero = np.zeros(self._floats(), np.float32)
-            m = self._m0 if self._m0 is not None else (self._dev["m"].cpu().numpy() if self._dev else zero)
-            v = self._v0 if self._v0 is not None else (self._dev["v"].cpu().numpy() if self._dev else zero)
-            self._dev = {
-                "w": torch.from_numpy(self._pack()).to(device),
-                "m": torch.from_numpy(np.array(m)).to(device),
-                "v": torch.from_numpy(np.array(v)).to(device),
-                "grad": torch.empty(self._floats(), dtype=torch.float32, device=device),
-                "version": ver,
-            }
-            self._m0 = self._v0 = None
-        return self._dev
-
-    # ---- gradients -------------------------------------------------------------------------------------------------------
-    @staticmethod
-    def _no_semi(**kw):
-        for name, value in kw.items():
-            if value is not None and value is not False:
-                raise NotImplementedError("%s: the semi-supervised step is implemented for the output layer only "
-                                          "(FinalLayerTrainer)" % name)
-
-    def _grad_dict(self, grad):
-        return {name: grad[off:off + int(np.prod(var.shape))].view(var.shape) for name, var, off, _ in self._named()}
-
-    def _grad_packed(self, x, labels, mask, params_dev):
-        torch = _lib.require_gpu()
-        if x.dim() != 4 or x.shape[-1] != 16:
-            raise ValueError("features must be [N,h,w,16] (got %s)" % (tuple(x.shape),))
-        n, h, w, _ = x.shape
-        k = int(self.net.classes)
-        lab, mk = self._targets(labels, mask, (n, 2 * h, 2 * w), x.device)
-        L = _lib.lib()
-        with torch.cuda.device(x.device):
-            nbytes = L.ssal_train_block_grad_workspace_bytes(n, h, w, k)
-            if nbytes < 0:
-                raise ValueError("feature map %dx%d is beyond the gradient kernel's limit" % (h, w))
-            ws = torch.empty(int(nbytes), dtype=torch.uint8, device=x.device)
-            loss = torch.empty((1,), dtype=torch.float64, device=x.device)
-            grad = torch.empty(self._floats(), dtype=torch.float32, device=x.device)
-            _lib.check(L.ssal_train_block_grad_nhwc(_lib.dev_ptr(x), n, h, w, k, _lib.dev_ptr(params_dev), _lib.dev_ptr(lab),
-                                                    _lib.dev_ptr(mk), self.weight, self.label_smoothing, _lib.dev_ptr(loss),
-                                                    _lib.dev_ptr(grad), _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))
-        return loss, grad
-
-    def gradient_features(self, features5_0, labels, mask, params=None, **semi):
-        """(loss float64 [1], {name: gradient}) on the device for Bottleneck5_0's output [N, h, w, 16] and labels / mask
-        [N, 2h, 2w].  ``params``: a name -> array mapping that overrides any of the 13 variables (the others, and the
-        moving statistics, are the model's).  No update.  The packed gradient is 0 in the statistics and padding slots."""
-        self._no_semi(**semi)
-        x = _lib.as_device_f32(features5_0)
+    # ---- arguments, judged on the host -----------------------------------------------------------------------------------
+    def _check_params(self, params):
         params = dict(params or {})
         unknown = set(params) - set(self.variable_names)
         if unknown:
             raise ValueError("unknown variables %s (the moving statistics always come from the model)" % sorted(unknown))
+        return params
+
+    def _packed_with(self, params):
+        """the packed block of the host variables with ``params`` (name -> array) laid over it"""
+        params = self._check_params(params)
         packed = self._pack()
         for name, var, off, _ in self._named():
             if name in params:
@@ -540,9 +552,68 @@ class LastBlockTrainer(FinalLayerTrainer):
                 if a.shape != var.shape:
                     raise ValueError("%s must have shape %s (got %s)" % (name, var.shape, a.shape))
                 packed[off:off + a.size] = a.reshape(-1)
-        torch = _lib.require_gpu()
-        loss, grad = self._grad_packed(x, labels, mask, torch.from_numpy(packed).to(x.device))
-        return loss, self._grad_dict(grad)
+        return packed
+
+    def _check_inputs(self, inputs):
+        """the leading arguments of a features call (features[, pooling indices]) after their host-side checks"""
+        return tuple(inputs)
+
+    def _raw_host(self, inputs, raw):
+        """the undistorted frames' side of a features call, judged on the host before any device work: None when there is
+        none (not given, or the very objects of ``inputs``), else its leading arguments after their checks"""
+        if len({r is None for r in raw}) > 1:
+            raise ValueError("features_raw and argmax1_raw are given together or not at all (the undistorted frame's "
+                             "pooling indices are its own)")
+        if raw[0] is None or all(r is i for r, i in zip(raw, inputs)):
+            return None
+        if tuple(np.shape(raw[0])) != tuple(np.shape(inputs[0])):
+            raise ValueError("features_raw must have the shape of the features %s (got %s)"
+                             % (tuple(np.shape(inputs[0])), tuple(np.shape(raw[0]))))
+        return self._check_inputs(raw)
+
+    @staticmethod
+    def _on_device(inputs, device=None):
+        x = _lib.as_device_f32(inputs[0])
+        x = x if device is None else x.to(device)
+        return (x,) + tuple(t.to(device=x.device).contiguous() for t in inputs[1:])
+
+    # ---- gradients and steps ---------------------------------------------------------------------------------------------
+    def _grad_dict(self, grad):
+        return {name: grad[off:off + int(np.prod(var.shape))].view(var.shape) for name, var, off, _ in self._named()}
+
+    def _features_on_device(self, inputs, raw, semi):
+        """(the leading arguments of a features call on the device, those of the undistorted frames or Nones), after the
+        host-side checks of both"""
+        checked = self._check_inputs(inputs)
+        raw = self._raw_host(inputs, raw) if semi is not None else None
+        x = self._on_device(checked)
+        return x, ((None,) * len(x) if raw is None else self._on_device(raw, x[0].device))
+
+    def _gradient(self, inputs, raw, labels, mask, params, semi, confusion, return_pseudo_pixels, extra=()):
+        """``gradient_features`` behind its keywords: (loss [1], {name: gradient}[, pseudo pixels])"""
+        packed = self._packed_with(params)
+        x, xr = self._features_on_device(inputs, raw, semi)
+        params_dev = _lib.require_gpu().from_numpy(packed).to(x[0].device)
+        loss, grad, pp = self._grad_call(x, xr, labels, mask, params_dev, semi, confusion, return_pseudo_pixels, extra)
+        return (loss, self._grad_dict(grad), pp) if return_pseudo_pixels else (loss, self._grad_dict(grad))
+
+    def _step_from_features(self, inputs, raw, labels, mask, semi, confusion, return_pseudo_pixels, extra=()):
+        """``step_features`` behind its keywords: loss before the step[, pseudo pixels]"""
+        x, xr = self._features_on_device(inputs, raw, semi)
+        dev = self._device_state(x[0].device)
+        loss, grad, pp = self._grad_call(x, xr, labels, mask, dev["w"], semi, confusion, return_pseudo_pixels, extra)
+        self._apply(dev, grad)
+        return (loss[0], pp) if return_pseudo_pixels else loss[0]
+
+    def gradient_features(self, features5_0, labels, mask, params=None, labelled=None, measure=None, threshold=None,
+                          features_raw=None, confusion=None, return_pseudo_pixels=False):
+        """(loss float64 [1], {name: gradient}) on the device for Bottleneck5_0's output [N, h, w, 16] and labels / mask
+        [N, 2h, 2w].  ``params``: a name -> array mapping that overrides any of the 13 variables (the others, and the
+        moving statistics, are the model's).  No update.  The packed gradient is 0 in the statistics and padding slots.
+        The keywords after ``params`` are the semi-supervised ones (``SemiSupervisedBlockTrainer``)."""
+        semi = self._semi_call(features5_0, labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels,
+                               features_raw=features_raw)
+        return self._gradient((features5_0,), (features_raw,), labels, mask, params, semi, confusion, return_pseudo_pixels)
 
     def features(self, images):
         """Bottleneck5_0's output [N, H/2, W/2, 16] for ``images`` (a copy): what ``step_features`` and
@@ -559,81 +630,22 @@ class LastBlockTrainer(FinalLayerTrainer):
         shape = (n, h // 2, w // 2, 16)
         return net._ws[off:off + 4 * n * (h // 2) * (w // 2) * 16].view(torch.float32).view(shape).clone()
 
-    def _trained_tail(self):
-        """how many of ``net.variables``, counted from the end, the training kernels take from the packed block"""
-        return len(getattr(self.net, _BLOCK).variables) + 1
-
-    def _adam_ranges(self):
-        """(lo, hi, regularised) float ranges of the packed block Adam runs on"""
-        return _ADAM_RANGES + ((_FINAL_OFFSET, _FINAL_OFFSET + 144 * int(self.net.classes), True),)
-
-    def _trunk_handle(self):
-        """the net's handle for the current device: reused while every variable BELOW Bottleneck5_1 is unchanged (the
-        training kernels take the 13 variables and the block's statistics from the packed device block).  The handle's
-        pushed-versions record keeps the old versions, so the next score / evaluate / call pushes the new weights once."""
-        torch = _lib.require_gpu()
-        net = self.net
-        ent = net._handles.get(torch.cuda.current_device())
-        tail = self._trained_tail()
-        if ent is not None and ent[1] is not None:
-            if tuple(v.version for v in net.variables)[:-tail] == ent[1][:-tail]:
-                return ent[0]
-        return net._sync_handle()
-
-    def _apply(self, dev, grad):
-        lr = self.current_learning_rate()
-        L = _lib.lib()
-        torch = _lib.require_gpu()
-        w, m, v = dev["w"], dev["m"], dev["v"]
-        for lo, hi, reg in self._adam_ranges():
-            _lib.check(L.ssal_adam_apply(_lib.dev_ptr(w[lo:hi]), _lib.dev_ptr(m[lo:hi]), _lib.dev_ptr(v[lo:hi]),
-                                         _lib.dev_ptr(grad[lo:hi]), hi - lo, float(lr), self.beta1, self.beta2, self.epsilon,
-                                         float(self._b1p), float(self._b2p), self.l1 if reg else 0.0,
-                                         self.l2 if reg else 0.0, _lib.stream_ptr()))
-        self._t += 1
-        self._b1p = np.float32(self._b1p * np.float32(self.beta1))
-        self._b2p = np.float32(self._b2p * np.float32(self.beta2))
-        # the host variables are the weights of record (12.5 KB at K = 19; synchronises the stream)
-        host = w.cpu().numpy()
-        for name, var, off, _ in self._named():
-            var.assign(host[off:off + int(np.prod(var.shape))].reshape(var.shape))
-        dev["version"] = self._versions()
-
-    def step_features(self, features5_0, labels, mask, **semi):
+    def step_features(self, features5_0, labels, mask, labelled=None, measure=None, threshold=None, features_raw=None,
+                      confusion=None, return_pseudo_pixels=False):
         """one Adam step from cached Bottleneck5_0 features [N, h, w, 16]; returns the loss (float64 device scalar) BEFORE
         the step, as ``sess.run([loss, train_op])`` does"""
-        self._no_semi(**semi)
-        x = _lib.as_device_f32(features5_0)
-        dev = self._device_state(x.device)
-        loss, grad = self._grad_packed(x, labels, mask, dev["w"])
-        self._apply(dev, grad)
-        return loss[0]
+        semi = self._semi_call(features5_0, labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels,
+                               features_raw=features_raw)
+        return self._step_from_features((features5_0,), (features_raw,), labels, mask, semi, confusion,
+                                        return_pseudo_pixels)
 
-    def step(self, images, labels, mask, **semi):
+    def step(self, images, labels, mask, labelled=None, measure=None, threshold=None, images_raw=None, confusion=None,
+             return_pseudo_pixels=False):
         """one Adam step from images [N, H, W, C] (fp32 or decoded uint8) and labels / mask [N, H, W]: the frozen trunk up
         to Bottleneck5_0, the training kernels, Adam.  Returns the loss (float64 device scalar) before the step."""
-        self._no_semi(**semi)
-        torch = _lib.require_gpu()
-        net = self.net
-        x = net._prepare(images, False)
-        n, h, w, _ = x.shape
-        L = _lib.lib()
-        lab, mk = self._targets(labels, mask, (n, h, w), x.device)
-        with torch.cuda.device(x.device):
-            dev = self._device_state(x.device)
-            handle = self._trunk_handle()
-            nbytes = L.ssal_enet_train_block_workspace_bytes(handle, n, h, w)
-            if nbytes < 0:
-                raise ValueError("bad input dims %s" % (tuple(x.shape),))
-            ws = net._workspace(nbytes, x.device)
-            loss = torch.empty((1,), dtype=torch.float64, device=x.device)
-            _lib.check(L.ssal_enet_train_block_nhwc(handle, _lib.dev_ptr(x), int(x.dtype == torch.uint8), n, h, w,
-                                                    _lib.dev_ptr(lab), _lib.dev_ptr(mk), _lib.dev_ptr(dev["w"]), self.weight,
-                                                    self.label_smoothing, _lib.dev_ptr(loss), _lib.dev_ptr(dev["grad"]),
-                                                    _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))
-            net._note_call(ws, (n, h, w), "train")
-            self._apply(dev, dev["grad"])
-        return loss[0]
+        semi = self._semi_call(images, labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels,
+                               images_raw=images_raw)
+        return self._step_images(images, images_raw, labels, mask, semi, confusion, return_pseudo_pixels)
 
 
 # ---- the last stage: Bottleneck5_0 + Bottleneck5_1 + Final (DESIGN.md section 18) ------------------------------------------
@@ -669,6 +681,11 @@ class LastStageTrainer(LastBlockTrainer):
 
     The inputs are Bottleneck4_2's output [N, h, w, 64] and ``argmax1`` [N, h, w, 16] int64, the pooling indices of
     Bottleneck1_0 in the reference's per-image form ``(y * 2w + x) * 16 + c`` (``features(images)`` returns both)."""
+
+    _C_FEATURES = ("ssal_train_stage_grad", "ssal_train_stage_grad_semi")
+    _C_IMAGES = ("ssal_enet_train_stage", "ssal_enet_train_stage_semi")
+    _CHANNELS, _UP = 64, 4
+    _LIMIT = ("kernels'", "kernels'")
 
     def _stage_offset(self):
         return _FINAL_OFFSET + 144 * int(self.net.classes)
@@ -733,16 +750,16 @@ class LastStageTrainer(LastBlockTrainer):
             self._argmax_ok = (argmax1, argmax1._version) if isinstance(argmax1, torch.Tensor) else None
         return a
 
+    def _check_inputs(self, inputs):
+        return inputs[0], self._check_argmax(np.shape(inputs[0]), inputs[1])
+
     def _check_params(self, params):
-        params = dict(params or {})
-        unknown = set(params) - set(self.variable_names)
+        unknown = set(params or {}) - set(self.variable_names)
         frozen = self.net._layer_names[:self.net._layer_names.index(_STAGE)]
         below = sorted(n for n in unknown if n.split(".")[0] in frozen)
         if below:
             raise NotImplementedError("training below Bottleneck5_0 is not implemented (got %s)" % below)
-        if unknown:
-            raise ValueError("unknown variables %s (the moving statistics always come from the model)" % sorted(unknown))
-        return params
+        return super()._check_params(params)
 
     @staticmethod
     def _check_workgroups(max_workgroups):
@@ -751,47 +768,19 @@ class LastStageTrainer(LastBlockTrainer):
         return int(max_workgroups)
 
     # ---- gradients -------------------------------------------------------------------------------------------------------
-    def _grad_packed(self, x, argmax, labels, mask, params_dev, max_workgroups=0):
-        torch = _lib.require_gpu()
-        n, h, w, _ = x.shape
-        k = int(self.net.classes)
-        lab, mk = self._targets(labels, mask, (n, 4 * h, 4 * w), x.device)
-        am = argmax.to(device=x.device).contiguous()
-        L = _lib.lib()
-        with torch.cuda.device(x.device):
-            nbytes = L.ssal_train_stage_grad_workspace_bytes(n, h, w, k)
-            if nbytes < 0:
-                raise ValueError("feature map %dx%d is beyond the gradient kernels' limit" % (h, w))
-            ws = torch.empty(int(nbytes), dtype=torch.uint8, device=x.device)
-            loss = torch.empty((1,), dtype=torch.float64, device=x.device)
-            grad = torch.empty(self._floats(), dtype=torch.float32, device=x.device)
-            _lib.check(L.ssal_train_stage_grad_nhwc(_lib.dev_ptr(x), _lib.dev_ptr(am), n, h, w, k, _lib.dev_ptr(params_dev),
-                                                    _lib.dev_ptr(lab), _lib.dev_ptr(mk), self.weight, self.label_smoothing,
-                                                    max_workgroups, _lib.dev_ptr(loss), _lib.dev_ptr(grad), _lib.dev_ptr(ws),
-                                                    ws.numel(), _lib.stream_ptr()))
-        return loss, grad
-
-    def gradient_features(self, features4_2, argmax1, labels, mask, params=None, max_workgroups=0, **semi):
+    def gradient_features(self, features4_2, argmax1, labels, mask, params=None, max_workgroups=0, labelled=None,
+                          measure=None, threshold=None, features_raw=None, argmax1_raw=None, confusion=None,
+                          return_pseudo_pixels=False):
         """(loss float64 [1], {name: gradient}) on the device for Bottleneck4_2's output [N, h, w, 64], the pooling indices
         ``argmax1`` [N, h, w, 16] and labels / mask [N, 4h, 4w].  ``params``: a name -> array mapping that overrides any of
         the 26 variables (the others, and the moving statistics, are the model's).  ``max_workgroups``: 0 = the default,
-        min(tiles, 1024); a tuning knob.  No update."""
-        self._no_semi(**semi)
-        params = self._check_params(params)
-        max_workgroups = self._check_workgroups(max_workgroups)
-        am = self._check_argmax(np.shape(features4_2), argmax1)
-        packed = self._pack()
-        for name, var, off, _ in self._named():
-            if name in params:
-                a = params[name]
-                a = np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a, dtype=np.float32)
-                if a.shape != var.shape:
-                    raise ValueError("%s must have shape %s (got %s)" % (name, var.shape, a.shape))
-                packed[off:off + a.size] = a.reshape(-1)
-        x = _lib.as_device_f32(features4_2)
-        torch = _lib.require_gpu()
-        loss, grad = self._grad_packed(x, am, labels, mask, torch.from_numpy(packed).to(x.device), max_workgroups)
-        return loss, self._grad_dict(grad)
+        min(tiles, 1024); a tuning knob.  No update.  The keywords after it are the semi-supervised ones
+        (``SemiSupervisedStageTrainer``)."""
+        semi = self._semi_call(features4_2, labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels,
+                               features_raw=features_raw, argmax1_raw=argmax1_raw)
+        extra = (self._check_workgroups(max_workgroups),)
+        return self._gradient((features4_2, argmax1), (features_raw, argmax1_raw), labels, mask, params, semi, confusion,
+                              return_pseudo_pixels, extra)
 
     def features(self, images):
         """(Bottleneck4_2's output [N, H/4, W/4, 64] (a copy), argmax1 [N, H/4, W/4, 16] int64) for ``images``: what
@@ -809,170 +798,40 @@ class LastStageTrainer(LastBlockTrainer):
         feats = net._ws[off:off + 4 * n * (h // 4) * (w // 4) * 64].view(torch.float32).view(shape).clone()
         return feats, net.pooling_argmax()[0]
 
-    def step_features(self, features4_2, argmax1, labels, mask, max_workgroups=0, **semi):
+    def step_features(self, features4_2, argmax1, labels, mask, max_workgroups=0, labelled=None, measure=None,
+                      threshold=None, features_raw=None, argmax1_raw=None, confusion=None, return_pseudo_pixels=False):
         """one Adam step from cached Bottleneck4_2 features and pooling indices (``features(images)``); returns the loss
         (float64 device scalar) BEFORE the step, as ``sess.run([loss, train_op])`` does"""
-        self._no_semi(**semi)
-        max_workgroups = self._check_workgroups(max_workgroups)
-        am = self._check_argmax(np.shape(features4_2), argmax1)
-        x = _lib.as_device_f32(features4_2)
-        dev = self._device_state(x.device)
-        loss, grad = self._grad_packed(x, am, labels, mask, dev["w"], max_workgroups)
-        self._apply(dev, grad)
-        return loss[0]
+        semi = self._semi_call(features4_2, labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels,
+                               features_raw=features_raw, argmax1_raw=argmax1_raw)
+        extra = (self._check_workgroups(max_workgroups),)
+        return self._step_from_features((features4_2, argmax1), (features_raw, argmax1_raw), labels, mask, semi, confusion,
+                                        return_pseudo_pixels, extra)
 
-    def step(self, images, labels, mask, max_workgroups=0, **semi):
+    def step(self, images, labels, mask, max_workgroups=0, labelled=None, measure=None, threshold=None, images_raw=None,
+             confusion=None, return_pseudo_pixels=False):
         """one Adam step from images [N, H, W, C] (fp32 or decoded uint8) and labels / mask [N, H, W]: the frozen trunk up
         to Bottleneck4_2, the stage's forward and training kernels, Adam.  Returns the loss (float64 device scalar) before
         the step."""
-        self._no_semi(**semi)
-        max_workgroups = self._check_workgroups(max_workgroups)
-        torch = _lib.require_gpu()
-        net = self.net
-        x = net._prepare(images, False)
-        n, h, w, _ = x.shape
-        L = _lib.lib()
-        lab, mk = self._targets(labels, mask, (n, h, w), x.device)
-        with torch.cuda.device(x.device):
-            dev = self._device_state(x.device)
-            handle = self._trunk_handle()
-            nbytes = L.ssal_enet_train_stage_workspace_bytes(handle, n, h, w)
-            if nbytes < 0:
-                raise ValueError("bad input dims %s" % (tuple(x.shape),))
-            ws = net._workspace(nbytes, x.device)
-            loss = torch.empty((1,), dtype=torch.float64, device=x.device)
-            _lib.check(L.ssal_enet_train_stage_nhwc(handle, _lib.dev_ptr(x), int(x.dtype == torch.uint8), n, h, w,
-                                                    _lib.dev_ptr(lab), _lib.dev_ptr(mk), _lib.dev_ptr(dev["w"]), self.weight,
-                                                    self.label_smoothing, max_workgroups, _lib.dev_ptr(loss),
-                                                    _lib.dev_ptr(dev["grad"]), _lib.dev_ptr(ws), ws.numel(),
-                                                    _lib.stream_ptr()))
-            net._note_call(ws, (n, h, w), "train")
-            self._apply(dev, dev["grad"])
-        return loss[0]
+        semi = self._semi_call(images, labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels,
+                               images_raw=images_raw)
+        extra = (self._check_workgroups(max_workgroups),)
+        return self._step_images(images, images_raw, labels, mask, semi, confusion, return_pseudo_pixels, extra)
 
 
 # ---- the semi-supervised step of the two deeper trainers (DESIGN.md section 19) ---------------------------------------------
-class _DeepSemiMixin:
+class _SemiKeywords:
     """The semi-supervised keywords of ``FinalLayerTrainer`` (``labelled``, ``measure``, ``threshold``, ``features_raw`` /
     ``images_raw``, ``confusion``, ``return_pseudo_pixels``; meaning, defaults and validation are its ``_semi`` /
-    ``_semi_device``) on ``LastBlockTrainer`` / ``LastStageTrainer``: the head kernel builds the targets of an unlabelled
-    image from the logits it holds (or reads the packed targets a target-only launch wrote from the undistorted frame),
-    counts the tile's pixels into the confusion matrix and the pseudo pixels per image.  With none of the keywords given
-    a call goes through the parent class's plain entry exactly as before."""
+    ``_semi_device``) are accepted, not refused: the head kernel builds the targets of an unlabelled image from the logits it
+    holds (or reads the packed targets a target-only launch wrote from the undistorted frame), counts the tile's pixels into
+    the confusion matrix and the pseudo pixels per image.  With none of the keywords given a call goes through the plain
+    entry exactly as the class below it in the MRO does."""
 
-    _deep_stage = False  # True: the inputs are Bottleneck4_2's output + argmax1 (LastStageTrainer)
-
-    def _packed_with(self, params):
-        """the packed block of the host variables with ``params`` (name -> array) laid over it"""
-        params = dict(params or {})
-        if self._deep_stage:
-            params = self._check_params(params)
-        else:
-            unknown = set(params) - set(self.variable_names)
-            if unknown:
-                raise ValueError("unknown variables %s (the moving statistics always come from the model)" % sorted(unknown))
-        packed = self._pack()
-        for name, var, off, _ in self._named():
-            if name in params:
-                a = params[name]
-                a = np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a, dtype=np.float32)
-                if a.shape != var.shape:
-                    raise ValueError("%s must have shape %s (got %s)" % (name, var.shape, a.shape))
-                packed[off:off + a.size] = a.reshape(-1)
-        return packed
-
-    @staticmethod
-    def _batch(t):
-        return int(np.shape(t)[0]) if len(np.shape(t)) else 0
-
-    def _raw_host(self, features, features_raw, argmax1=None, argmax1_raw=None):
-        """(raw features or None, checked raw argmax or None), judged on the host before any device work"""
-        if self._deep_stage and (features_raw is None) != (argmax1_raw is None):
-            raise ValueError("features_raw and argmax1_raw are given together or not at all (the undistorted frame's "
-                             "pooling indices are its own)")
-        if features_raw is None or (features_raw is features and (argmax1_raw is None or argmax1_raw is argmax1)):
-            return None, None
-        if tuple(np.shape(features_raw)) != tuple(np.shape(features)):
-            raise ValueError("features_raw must have the shape of the features %s (got %s)"
-                             % (tuple(np.shape(features)), tuple(np.shape(features_raw))))
-        return features_raw, (self._check_argmax(np.shape(features_raw), argmax1_raw) if self._deep_stage else None)
-
-    def _semi_grad_packed(self, x, argmax, xr, argmax_raw, labels, mask, params_dev, semi, confusion, return_pseudo_pixels,
-                          max_workgroups=0):
-        """(loss, packed gradient, pseudo pixels or None) through the features entry of the C ABI"""
-        torch = _lib.require_gpu()
-        c = 64 if self._deep_stage else 16
-        if x.dim() != 4 or x.shape[-1] != c:
-            raise ValueError("features must be [N,h,w,%d] (got %s)" % (c, tuple(x.shape)))
-        n, h, w, _ = x.shape
-        k = int(self.net.classes)
-        up = 4 if self._deep_stage else 2
-        lbd, lab, mk = self._semi_device(semi, n, x.device, labels, mask, (n, up * h, up * w))
-        L = _lib.lib()
-        with torch.cuda.device(x.device):
-            query = L.ssal_train_stage_grad_semi_workspace_bytes if self._deep_stage else L.ssal_train_block_grad_semi_workspace_bytes
-            nbytes = query(n, h, w, k, int(xr is not None))
-            if nbytes < 0:
-                raise ValueError("feature map %dx%d is beyond the gradient kernels' limit" % (h, w))
-            ws = torch.empty(int(nbytes), dtype=torch.uint8, device=x.device)
-            loss = torch.empty((1,), dtype=torch.float64, device=x.device)
-            grad = torch.empty(self._floats(), dtype=torch.float32, device=x.device)
-            pp = torch.empty((n,), dtype=torch.int64, device=x.device) if return_pseudo_pixels else None
-            conf = _lib.dev_ptr(confusion, torch.int64, "confusion")
-            if self._deep_stage:
-                am = argmax.to(device=x.device).contiguous()
-                amr = argmax_raw.to(device=x.device).contiguous() if argmax_raw is not None else None
-                _lib.check(L.ssal_train_stage_grad_semi_nhwc(
-                    _lib.dev_ptr(x), _lib.dev_ptr(am), _lib.dev_ptr(xr), _lib.dev_ptr(amr), n, h, w, k,
-                    _lib.dev_ptr(params_dev), _lib.dev_ptr(lab), _lib.dev_ptr(mk), _lib.dev_ptr(lbd), semi[1], semi[2],
-                    self.weight, self.label_smoothing, max_workgroups, _lib.dev_ptr(loss), _lib.dev_ptr(grad), conf,
-                    _lib.dev_ptr(pp), _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))
-            else:
-                _lib.check(L.ssal_train_block_grad_semi_nhwc(
-                    _lib.dev_ptr(x), _lib.dev_ptr(xr), n, h, w, k, _lib.dev_ptr(params_dev), _lib.dev_ptr(lab),
-                    _lib.dev_ptr(mk), _lib.dev_ptr(lbd), semi[1], semi[2], self.weight, self.label_smoothing,
-                    _lib.dev_ptr(loss), _lib.dev_ptr(grad), conf, _lib.dev_ptr(pp), _lib.dev_ptr(ws), ws.numel(),
-                    _lib.stream_ptr()))
-        return loss, grad, pp
-
-    def _semi_step_images(self, images, labels, mask, semi, images_raw, confusion, return_pseudo_pixels, max_workgroups=0):
-        torch = _lib.require_gpu()
-        net = self.net
-        x = net._prepare(images, False)
-        n, h, w, _ = x.shape
-        L = _lib.lib()
-        lbd, lab, mk = self._semi_device(semi, n, x.device, labels, mask, (n, h, w))
-        xr = None
-        if images_raw is not None and images_raw is not images:
-            xr = net._prepare(images_raw, False)
-            if tuple(xr.shape) != tuple(x.shape) or xr.dtype != x.dtype or xr.device != x.device:
-                raise ValueError("images_raw must have the shape and dtype of images %s %s (got %s %s)"
-                                 % (tuple(x.shape), x.dtype, tuple(xr.shape), xr.dtype))
-        with torch.cuda.device(x.device):
-            dev = self._device_state(x.device)
-            handle = self._trunk_handle()
-            query = L.ssal_enet_train_stage_semi_workspace_bytes if self._deep_stage else L.ssal_enet_train_block_semi_workspace_bytes
-            nbytes = query(handle, n, h, w, int(xr is not None))
-            if nbytes < 0:
-                raise ValueError("bad input dims %s" % (tuple(x.shape),))
-            ws = net._workspace(nbytes, x.device)
-            loss = torch.empty((1,), dtype=torch.float64, device=x.device)
-            pp = torch.empty((n,), dtype=torch.int64, device=x.device) if return_pseudo_pixels else None
-            head = (handle, _lib.dev_ptr(x), _lib.dev_ptr(xr), int(x.dtype == torch.uint8), n, h, w, _lib.dev_ptr(lab),
-                    _lib.dev_ptr(mk), _lib.dev_ptr(lbd), semi[1], semi[2], _lib.dev_ptr(dev["w"]), self.weight,
-                    self.label_smoothing)
-            tail = (_lib.dev_ptr(loss), _lib.dev_ptr(dev["grad"]), _lib.dev_ptr(confusion, torch.int64, "confusion"),
-                    _lib.dev_ptr(pp), _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr())
-            if self._deep_stage:
-                _lib.check(L.ssal_enet_train_stage_semi_nhwc(*(head + (max_workgroups,) + tail)))
-            else:
-                _lib.check(L.ssal_enet_train_block_semi_nhwc(*(head + tail)))
-            net._note_call(ws, (n, h, w), "train")
-            self._apply(dev, dev["grad"])
-        return (loss[0], pp) if return_pseudo_pixels else loss[0]
+    _semi_keywords = True
 
 
-class SemiSupervisedBlockTrainer(_DeepSemiMixin, LastBlockTrainer):
+class SemiSupervisedBlockTrainer(_SemiKeywords, LastBlockTrainer):
     """``LastBlockTrainer`` with the reference's semi-supervised step (active_learning.py:226-275, 339-342) built into its
     head kernel: ``gradient_features``, ``step_features`` and ``step`` accept ``labelled``, ``measure``, ``threshold``,
     ``features_raw`` / ``images_raw``, ``confusion`` and ``return_pseudo_pixels`` with ``FinalLayerTrainer``'s meaning,
@@ -980,96 +839,12 @@ class SemiSupervisedBlockTrainer(_DeepSemiMixin, LastBlockTrainer):
     13 gradients are bit-identical to ``LastBlockTrainer`` on the composed targets.  ``state`` /
     ``load_state`` are interchangeable with ``LastBlockTrainer``'s."""
 
-    def gradient_features(self, features5_0, labels, mask, params=None, labelled=None, measure=None, threshold=None,
-                          features_raw=None, confusion=None, return_pseudo_pixels=False):
-        semi = self._semi(self._batch(features5_0), labels, mask, labelled, measure, threshold, confusion,
-                          return_pseudo_pixels)
-        if semi is None:
-            return super().gradient_features(features5_0, labels, mask, params=params)
-        packed = self._packed_with(params)
-        xr, _ = self._raw_host(features5_0, features_raw)
-        x = _lib.as_device_f32(features5_0)
-        xr = None if xr is None else _lib.as_device_f32(xr).to(x.device)
-        torch = _lib.require_gpu()
-        loss, grad, pp = self._semi_grad_packed(x, None, xr, None, labels, mask, torch.from_numpy(packed).to(x.device),
-                                                semi, confusion, return_pseudo_pixels)
-        return (loss, self._grad_dict(grad), pp) if return_pseudo_pixels else (loss, self._grad_dict(grad))
 
-    def step_features(self, features5_0, labels, mask, labelled=None, measure=None, threshold=None, features_raw=None,
-                      confusion=None, return_pseudo_pixels=False):
-        semi = self._semi(self._batch(features5_0), labels, mask, labelled, measure, threshold, confusion,
-                          return_pseudo_pixels)
-        if semi is None:
-            return super().step_features(features5_0, labels, mask)
-        xr, _ = self._raw_host(features5_0, features_raw)
-        x = _lib.as_device_f32(features5_0)
-        xr = None if xr is None else _lib.as_device_f32(xr).to(x.device)
-        dev = self._device_state(x.device)
-        loss, grad, pp = self._semi_grad_packed(x, None, xr, None, labels, mask, dev["w"], semi, confusion,
-                                                return_pseudo_pixels)
-        self._apply(dev, grad)
-        return (loss[0], pp) if return_pseudo_pixels else loss[0]
-
-    def step(self, images, labels, mask, labelled=None, measure=None, threshold=None, images_raw=None, confusion=None,
-             return_pseudo_pixels=False):
-        semi = self._semi(self._batch(images), labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels)
-        if semi is None:
-            return super().step(images, labels, mask)
-        return self._semi_step_images(images, labels, mask, semi, images_raw, confusion, return_pseudo_pixels)
-
-
-class SemiSupervisedStageTrainer(_DeepSemiMixin, LastStageTrainer):
+class SemiSupervisedStageTrainer(_SemiKeywords, LastStageTrainer):
     """``LastStageTrainer`` with the semi-supervised step built into the head kernel (see ``SemiSupervisedBlockTrainer``);
     the undistorted frame's side of the feature entries is ``features_raw`` [N, h, w, 64] with its own pooling indices
     ``argmax1_raw`` (what ``features(images_raw)`` returns).  Loss and the 26 gradients are bit-identical to
     ``LastStageTrainer`` on the composed targets; ``state`` / ``load_state`` are interchangeable with its."""
-
-    _deep_stage = True
-
-    def gradient_features(self, features4_2, argmax1, labels, mask, params=None, max_workgroups=0, labelled=None,
-                          measure=None, threshold=None, features_raw=None, argmax1_raw=None, confusion=None,
-                          return_pseudo_pixels=False):
-        semi = self._semi(self._batch(features4_2), labels, mask, labelled, measure, threshold, confusion,
-                          return_pseudo_pixels)
-        if semi is None:
-            return super().gradient_features(features4_2, argmax1, labels, mask, params=params,
-                                             max_workgroups=max_workgroups)
-        max_workgroups = self._check_workgroups(max_workgroups)
-        am = self._check_argmax(np.shape(features4_2), argmax1)
-        packed = self._packed_with(params)
-        xr, amr = self._raw_host(features4_2, features_raw, argmax1, argmax1_raw)
-        x = _lib.as_device_f32(features4_2)
-        xr = None if xr is None else _lib.as_device_f32(xr).to(x.device)
-        torch = _lib.require_gpu()
-        loss, grad, pp = self._semi_grad_packed(x, am, xr, amr, labels, mask, torch.from_numpy(packed).to(x.device), semi,
-                                                confusion, return_pseudo_pixels, max_workgroups)
-        return (loss, self._grad_dict(grad), pp) if return_pseudo_pixels else (loss, self._grad_dict(grad))
-
-    def step_features(self, features4_2, argmax1, labels, mask, max_workgroups=0, labelled=None, measure=None,
-                      threshold=None, features_raw=None, argmax1_raw=None, confusion=None, return_pseudo_pixels=False):
-        semi = self._semi(self._batch(features4_2), labels, mask, labelled, measure, threshold, confusion,
-                          return_pseudo_pixels)
-        if semi is None:
-            return super().step_features(features4_2, argmax1, labels, mask, max_workgroups=max_workgroups)
-        max_workgroups = self._check_workgroups(max_workgroups)
-        am = self._check_argmax(np.shape(features4_2), argmax1)
-        xr, amr = self._raw_host(features4_2, features_raw, argmax1, argmax1_raw)
-        x = _lib.as_device_f32(features4_2)
-        xr = None if xr is None else _lib.as_device_f32(xr).to(x.device)
-        dev = self._device_state(x.device)
-        loss, grad, pp = self._semi_grad_packed(x, am, xr, amr, labels, mask, dev["w"], semi, confusion,
-                                                return_pseudo_pixels, max_workgroups)
-        self._apply(dev, grad)
-        return (loss[0], pp) if return_pseudo_pixels else loss[0]
-
-    def step(self, images, labels, mask, max_workgroups=0, labelled=None, measure=None, threshold=None, images_raw=None,
-             confusion=None, return_pseudo_pixels=False):
-        semi = self._semi(self._batch(images), labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels)
-        if semi is None:
-            return super().step(images, labels, mask, max_workgroups=max_workgroups)
-        max_workgroups = self._check_workgroups(max_workgroups)
-        return self._semi_step_images(images, labels, mask, semi, images_raw, confusion, return_pseudo_pixels,
-                                      max_workgroups)
 
 
 __all__ = ["FinalLayerTrainer", "LastBlockTrainer", "LastStageTrainer", "SemiSupervisedBlockTrainer",

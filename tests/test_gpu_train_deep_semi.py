@@ -401,3 +401,82 @@ def test_c_statuses_on_device():
     assert call(ws_bytes=15) == _lib.SSAL_ENOMEM and b"workspace too small" in L.ssal_last_error()
     torch.cuda.synchronize()
     assert pp.tolist() == [256, 256] and bool(torch.isfinite(grad).all())  # the refused calls wrote nothing
+
+
+def test_semi_entries_with_nothing_semi_equal_the_plain_entries():
+    """the six semi C entries called with labelled = confusion = pseudo_pixels = NULL and no raw input give the loss and the
+    gradient of their plain siblings bit for bit: ENet(6), 2 frames of 32 x 48 (feature maps 16 x 24 and 8 x 12: two
+    16 x 16 tiles with a ragged edge on the stage's map), about 10 % of the mask zero"""
+    k, n, h, w = 6, 2, 32, 48
+    L = _lib.lib()
+    net, _ = make_model(k, 3, seed=0)
+    x = syn.synth_frames_device(0, n, h, w, 3)
+    rng = np.random.default_rng(12)
+    labels = torch.as_tensor(rng.integers(0, k, (n, h, w)).astype(np.uint8)).cuda()
+    mask = torch.as_tensor((rng.uniform(size=(n, h, w)) > 0.1).astype(np.float32)).cuda()
+    assert 0.05 <= float((mask == 0).float().mean()) <= 0.15
+    net(x, training=False)
+    f51 = net.endpoint_outputs[0][1].clone()
+    block, stage = LastBlockTrainer(net, 1e-3), LastStageTrainer(net, 1e-3)
+    f50 = block.features(x)
+    f42, am = stage.features(x)
+    assert tuple(f51.shape) == tuple(f50.shape) == (n, 16, 24, 16) and tuple(f42.shape) == (n, 8, 12, 64)
+    kern = torch.as_tensor(net.Final.kernel.numpy()).cuda().contiguous()
+    pb, ps = torch.as_tensor(block._pack()).cuda(), torch.as_tensor(stage._pack()).cuda()
+    handle = net._sync_handle()
+    p, u8 = _lib.dev_ptr, 0
+    semi = (None, 0, 0.5)  # labelled, measure, threshold
+    wl = (1.02, 0.1)  # loss weight, label smoothing
+    # depth -> (gradient floats,
+    #           features side: plain entry, its leading arguments, semi entry, its leading arguments, dims, parameters,
+    #                          max_workgroups or nothing, workspace query, semi workspace query,
+    #           images side: plain entry, semi entry, parameters, max_workgroups or nothing, the two workspace queries)
+    depths = {
+        "final": (kern.numel(),
+                  (L.ssal_final_grad_nhwc, (p(f51),), L.ssal_final_grad_semi_nhwc, (p(f51), None), (n, 16, 24, k), p(kern), (),
+                   L.ssal_final_grad_workspace_bytes, lambda *a: L.ssal_final_grad_semi_workspace_bytes(*a)),
+                  (L.ssal_enet_train_final_nhwc, L.ssal_enet_train_final_semi_nhwc, p(kern), (),
+                   L.ssal_enet_train_final_workspace_bytes, L.ssal_enet_train_final_semi_workspace_bytes)),
+        "block": (pb.numel(),
+                  (L.ssal_train_block_grad_nhwc, (p(f50),), L.ssal_train_block_grad_semi_nhwc, (p(f50), None), (n, 16, 24, k),
+                   p(pb), (), L.ssal_train_block_grad_workspace_bytes,
+                   lambda *a: L.ssal_train_block_grad_semi_workspace_bytes(*a, 0)),
+                  (L.ssal_enet_train_block_nhwc, L.ssal_enet_train_block_semi_nhwc, p(pb), (),
+                   L.ssal_enet_train_block_workspace_bytes, L.ssal_enet_train_block_semi_workspace_bytes)),
+        "stage": (ps.numel(),
+                  (L.ssal_train_stage_grad_nhwc, (p(f42), p(am)), L.ssal_train_stage_grad_semi_nhwc,
+                   (p(f42), p(am), None, None), (n, 8, 12, k), p(ps), (0,), L.ssal_train_stage_grad_workspace_bytes,
+                   lambda *a: L.ssal_train_stage_grad_semi_workspace_bytes(*a, 0)),
+                  (L.ssal_enet_train_stage_nhwc, L.ssal_enet_train_stage_semi_nhwc, p(ps), (0,),
+                   L.ssal_enet_train_stage_workspace_bytes, L.ssal_enet_train_stage_semi_workspace_bytes)),
+    }
+
+    def run(entry, nbytes, args):
+        """args(loss, grad, ws) -> the entry's argument tuple; fresh NaN-filled outputs and workspace per call"""
+        assert nbytes > 0
+        ws = torch.zeros(int(nbytes), dtype=torch.uint8, device="cuda")
+        loss = torch.full((1,), float("nan"), dtype=torch.float64, device="cuda")
+        grad = torch.full((floats,), float("nan"), device="cuda")
+        assert entry(*args(loss, grad, ws)) == _lib.SSAL_OK, L.ssal_last_error()
+        torch.cuda.synchronize()
+        return loss, grad
+
+    for name, (floats, feat, img) in depths.items():
+        plain, head, semi_entry, semi_head, dims, params, extra, query, semi_query = feat
+        tail = lambda loss, grad, ws: (p(ws), ws.numel(), _lib.stream_ptr())
+        l0, g0 = run(plain, query(*dims), lambda loss, grad, ws: head + dims + (params, p(labels), p(mask)) + wl
+                     + extra + (p(loss), p(grad)) + tail(loss, grad, ws))
+        l1, g1 = run(semi_entry, semi_query(*dims), lambda loss, grad, ws: semi_head + dims + (params, p(labels), p(mask))
+                     + semi + wl + extra + (p(loss), p(grad), None, None) + tail(loss, grad, ws))
+        print("%s features: loss %.17g / %.17g" % (name, float(l0.cpu()[0]), float(l1.cpu()[0])))
+        assert bool(torch.isfinite(l0).all()) and bool(torch.isfinite(g0).all())
+        assert torch.equal(l0, l1) and torch.equal(g0, g1), "%s: features entries differ" % name
+        plain, semi_entry, params, extra, query, semi_query = img
+        l2, g2 = run(plain, query(handle, n, h, w), lambda loss, grad, ws: (handle, p(x), u8, n, h, w, p(labels), p(mask),
+                     params) + wl + extra + (p(loss), p(grad)) + tail(loss, grad, ws))
+        l3, g3 = run(semi_entry, semi_query(handle, n, h, w, 0), lambda loss, grad, ws: (handle, p(x), None, u8, n, h, w,
+                     p(labels), p(mask)) + semi + (params,) + wl + extra + (p(loss), p(grad), None, None)
+                     + tail(loss, grad, ws))
+        print("%s images:   loss %.17g / %.17g" % (name, float(l2.cpu()[0]), float(l3.cpu()[0])))
+        assert bool(torch.isfinite(l2).all()) and bool(torch.isfinite(g2).all())
+        assert torch.equal(l2, l3) and torch.equal(g2, g3), "%s: images entries differ" % name

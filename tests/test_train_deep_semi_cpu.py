@@ -76,6 +76,34 @@ def test_workspace_queries_limits_and_with_raw():
         assert q(None, 1, 64, 64, 0) == -1 and q(None, 1, 64, 64, 1) == -1
 
 
+# bytes of the six handle-free queries on the commit before the entries were folded onto shared bodies, in the order
+# final, final semi, block, block semi (with_raw 0, 1), stage, stage semi (with_raw 0, 1)
+PINNED_WORKSPACE_BYTES = {
+    (1, 8, 8, 2): (1552, 9984, 11792, 20224, 20480, 78848, 87040, 88064),
+    (2, 8, 24, 19): (22304, 210944, 57120, 245760, 247296, 397312, 585728, 591872),
+    (3, 40, 24, 32): (110944, 635392, 321888, 846336, 857856, 2812672, 3336960, 3383040),
+}
+
+
+def test_workspace_layout_is_pinned():
+    """the order of the carve calls is the layout: literal byte counts at three shapes, -1 outside the limits"""
+    L = _lib.lib()
+
+    def sizes(n, h, w, k):
+        return (L.ssal_final_grad_workspace_bytes(n, h, w, k), L.ssal_final_grad_semi_workspace_bytes(n, h, w, k),
+                L.ssal_train_block_grad_workspace_bytes(n, h, w, k),
+                L.ssal_train_block_grad_semi_workspace_bytes(n, h, w, k, 0),
+                L.ssal_train_block_grad_semi_workspace_bytes(n, h, w, k, 1),
+                L.ssal_train_stage_grad_workspace_bytes(n, h, w, k),
+                L.ssal_train_stage_grad_semi_workspace_bytes(n, h, w, k, 0),
+                L.ssal_train_stage_grad_semi_workspace_bytes(n, h, w, k, 1))
+
+    for shape, want in PINNED_WORKSPACE_BYTES.items():
+        assert sizes(*shape) == want, shape
+    for shape in ((1, 8, 8, 1), (1, 8, 8, 33), (1, 0, 8, 19)):
+        assert sizes(*shape) == (-1,) * 8, shape
+
+
 def test_statuses_before_any_device_work():
     """bad arguments are judged on the host: the pointers below are never dereferenced"""
     L = _lib.lib()
