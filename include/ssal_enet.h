@@ -564,6 +564,64 @@ int ssal_enet_train_stage_semi_nhwc(ssal_enet *net, const void *x_dev, const voi
                                     int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes,
                                     void *stream);
 
+/* ---- Decoder-tail training: Bottleneck4_2 + Bottleneck5_0 + Bottleneck5_1 + Final (enet_modules.py:526-599; DESIGN.md
+ * section 20) ----
+ * The same gradient one block further down: through Bottleneck4_2, a regular 64-channel bottleneck (1x1 projection 64 -> 16,
+ * 3x3 convolution 16 -> 16, 1x1 expansion 16 -> 64, identity residual), in inference mode as above.  Everything below
+ * Bottleneck4_2 is frozen; no gradient is produced for its input.
+ *
+ * The 39 trained variables and the 18 moving statistics travel in ONE packed fp32 block of
+ * ssal_train_tail_param_floats(classes) = ssal_train_stage_param_floats(classes) + 4840 floats: the stage block above,
+ * unchanged, then Bottleneck4_2's part at float offset T = 3936 + 144 classes (offsets from T, C order inside each tensor):
+ *      0  proj_kernel [64][16]     1024  proj_gamma [16]    1040  proj_beta [16]    1056  proj_alpha [16]
+ *   1072  conv_kernel [3][3][16][16] (HWIO)                 3376  conv_gamma [16]   3392  conv_beta [16]   3408  conv_alpha [16]
+ *   3424  exp_kernel [16][64]      4448  exp_gamma [64]     4512  exp_beta [64]     4576  residual_alpha [64]
+ *   4640  proj_mean [16]           4656  proj_variance [16] 4672  conv_mean [16]    4688  conv_variance [16]
+ *   4704  exp_mean [64]            4768  exp_variance [64]  4832  8 floats of padding
+ * grad_dev has the same layout (0 in the statistics and padding), so Adam's slots can too.
+ *
+ * ssal_train_tail_grad_nhwc: features_dev [n,h,w,64] fp32 = Bottleneck4_1's output; argmax_dev, labels_dev, mask_dev and
+ * max_workgroups as for ssal_train_stage_grad_nhwc.  Bottleneck4_2's output is computed by the forward path's own kernel from
+ * weights folded on the device as ssal_enet_commit folds them, then the stage runs on it, so loss_dev is the forward op's
+ * value on ssal_enet_forward_nhwc's logits.  No float atomics: two calls give the same bits.  The workspace query returns
+ * -1, and the call SSAL_EINVAL, wherever the stage entries do, and beyond the limit of the fused 64-channel bottleneck
+ * kernel the forward runs on (64 h w <= 2^29). */
+int64_t ssal_train_tail_param_floats(int classes);
+int64_t ssal_train_tail_grad_workspace_bytes(int n, int h, int w, int classes);
+int ssal_train_tail_grad_nhwc(const float *features_dev, const int64_t *argmax_dev, int n, int h, int w, int classes,
+                              const float *params_dev, const uint8_t *labels_dev, const float *mask_dev, float weight,
+                              float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev, void *ws_dev,
+                              int64_t ws_bytes, void *stream);
+/* The same from images x_dev [n,h,w,c_in] (fp32, or uint8 with x_is_u8): the committed trunk's launchers up to
+ * Bottleneck4_1 on the caller's stream, then the tail with params_dev (the handle's own Bottleneck4_2 / Bottleneck5_0 /
+ * Bottleneck5_1 / Final weights are not used) and the window codes the trunk's pooling left; labels_dev / mask_dev [n,h,w]. */
+int64_t ssal_enet_train_tail_workspace_bytes(const ssal_enet *net, int n, int h, int w);
+int ssal_enet_train_tail_nhwc(ssal_enet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                              const uint8_t *labels_dev, const float *mask_dev, const float *params_dev, float weight,
+                              float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev, void *ws_dev,
+                              int64_t ws_bytes, void *stream);
+/* Byte offset, into the workspace of ssal_enet_forward_nhwc / ssal_enet_score_nhwc / ssal_enet_train_tail_nhwc, of
+ * Bottleneck4_1's output [n,h/4,w/4,64] (the features_dev of ssal_train_tail_grad_nhwc); valid until the next call.  The
+ * window codes are at ssal_enet_train_stage_code_offset.  -1 for dims the net does not take. */
+int64_t ssal_enet_train_tail_features_offset(const ssal_enet *net, int n, int h, int w);
+/* The semi-supervised forms: arguments, meaning, limits and statuses of ssal_train_stage_grad_semi_nhwc /
+ * ssal_enet_train_stage_semi_nhwc above, one block lower (features_raw_dev = Bottleneck4_1 of the undistorted frames). */
+int64_t ssal_train_tail_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw);
+int ssal_train_tail_grad_semi_nhwc(const float *features_dev, const int64_t *argmax_dev, const float *features_raw_dev,
+                                   const int64_t *argmax_raw_dev, int n, int h, int w, int classes,
+                                   const float *params_dev, const uint8_t *labels_dev, const float *mask_dev,
+                                   const uint8_t *labelled_dev, int measure, float threshold, float weight,
+                                   float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev,
+                                   int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes,
+                                   void *stream);
+int64_t ssal_enet_train_tail_semi_workspace_bytes(const ssal_enet *net, int n, int h, int w, int with_raw);
+int ssal_enet_train_tail_semi_nhwc(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h,
+                                   int w, const uint8_t *labels_dev, const float *mask_dev, const uint8_t *labelled_dev,
+                                   int measure, float threshold, const float *params_dev, float weight,
+                                   float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev,
+                                   int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes,
+                                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif

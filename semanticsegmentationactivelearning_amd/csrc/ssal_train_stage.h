@@ -56,11 +56,13 @@ struct TrainStageWs {
 
 // x4 [N,H,W,64] = Bottleneck4_2's output; argmax int64 [N,H,W,16] (per-image index into [2H,2W,16]) is converted into
 // ws.code first, or, when it is NULL, ws.code already holds the window codes; params / grad: the stage block of
-// train_stage_floats(K) floats; labels uint8 / mask fp32 [N,4H,4W]; loss one double.
+// train_stage_floats(K) floats; labels uint8 / mask fp32 [N,4H,4W]; loss one double.  dx4 (may be NULL) [N,H,W,64]: the
+// stage's input gradient dL/d x4, before the 1 / sum(mask) factor (what the decoder-tail trainer goes on from,
+// ssal_train_tail.h); it changes no bit of loss or grad.
 hipError_t launch_train_stage_grad(const float *x4, const int64_t *argmax, int N, int H, int W, int K, const float *params,
                                    const uint8_t *labels, const float *mask, float weight, float label_smoothing,
                                    int max_workgroups, const TrainStageWs &ws, double *loss, float *grad, hipStream_t s,
-                                   const TrainBlockSemi *semi = nullptr);
+                                   const TrainBlockSemi *semi = nullptr, float *dx4 = nullptr);
 
 // The semi-supervised step with undistorted frames (semi as in ssal_train_block.h, on the [2H, 2W] map): x4_raw [N,H,W,64]
 // and argmax_raw (NULL: ws.code already holds the raw frame's window codes) -> the packed pseudo targets semi.tgt

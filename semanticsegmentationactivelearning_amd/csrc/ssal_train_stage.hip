@@ -118,10 +118,14 @@ __global__ __launch_bounds__(256) void k_ts_fold(const float *__restrict__ P, fl
 //      proj_kernel and res_kernel (thread = input channel x four outputs, over the patch's 64 pixels), conv_kernel (144 threads =
 //      tap x output x half of the inputs), exp_kernel (threads 128 .. 255 = one element each, over the tile's 256 pixels).
 // gamma / beta gradients are produced directly, as in k_tb_block.  part [gridDim.x][TS_TRAINED]: every slot is written.
+// DX (the decoder-tail trainer): the block's INPUT gradient of the patch's pixels -> dx4 [N,H,W,64],
+// written once between D and E: the projection's input gradient sum_k dL/d(proj acc)[k] W_p[ci][k] (BN and PReLU are inside ldpa) plus
+// the residual 1 x 1 convolution's sum_c dL/du_gathered[c] W_res[ci][c].
+template <bool DX>
 __global__ __launch_bounds__(256) void k_ts_block(const float *__restrict__ x4, const uint8_t *__restrict__ code,
                                                   const float *__restrict__ g, int N, int H, int W,
                                                   const float *__restrict__ P, const float *__restrict__ F,
-                                                  float *__restrict__ part)
+                                                  float *__restrict__ part, float *__restrict__ dx4)
 {
     __shared__ __attribute__((aligned(16))) float lwc[9 * 8 * 16];
     __shared__ __attribute__((aligned(16))) float lp[TS_PW * TS_PW * 16];
@@ -348,6 +352,29 @@ __global__ __launch_bounds__(256) void k_ts_block(const float *__restrict__ x4, 
                 if (!valid) reinterpret_cast<float4 *>(ldr)[dqp * 4 + dcg] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             }
             __syncthreads();
+            if constexpr (DX) {
+                // lane = pixel of the patch, wave = 16 input channels with both kernels' rows in scalar registers
+                const int qi = i0 + (lane >> 3), qj = j0 + (lane & 7);
+                const bool inside = qi < H && qj < W;
+                float dv[32];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float4 d = reinterpret_cast<const float4 *>(ldpa)[lane * 4 + q];
+                    const float4 r = reinterpret_cast<const float4 *>(ldr)[lane * 4 + q];
+                    dv[4 * q] = d.x; dv[4 * q + 1] = d.y; dv[4 * q + 2] = d.z; dv[4 * q + 3] = d.w;
+                    dv[16 + 4 * q] = r.x; dv[17 + 4 * q] = r.y; dv[18 + 4 * q] = r.z; dv[19 + 4 * q] = r.w;
+                }
+                float *dxp = dx4 + ((long)n * HW + (long)min(qi, H - 1) * W + min(qj, W - 1)) * 64;
+#pragma unroll 1
+                for (int ci = 16 * wv; ci < 16 * wv + 16; ++ci) {
+                    float v = 0.0f;
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) v = fmaf(dv[k], P[TS_WP + ci * 16 + k], v);
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) v = fmaf(dv[16 + k], P[TS_WR + ci * 16 + k], v);
+                    if (inside) dxp[ci] = v;
+                }
+            }
             // ---- E
             {
                 const int c = tid >> 2, kq = tid & 3;
@@ -442,7 +469,7 @@ __global__ __launch_bounds__(256) void k_ts_finish(const float *__restrict__ par
 hipError_t launch_train_stage_grad(const float *x4, const int64_t *argmax, int N, int H, int W, int K, const float *params,
                                    const uint8_t *labels, const float *mask, float weight, float label_smoothing,
                                    int max_workgroups, const TrainStageWs &ws, double *loss, float *grad, hipStream_t s,
-                                   const TrainBlockSemi *semi)
+                                   const TrainBlockSemi *semi, float *dx4)
 {
     if (N < 1 || K < 2 || K > 32 || !train_stage_fits(H, W)) return hipErrorInvalidValue;
     const int G = train_stage_workgroups(H, W, max_workgroups);
@@ -469,7 +496,8 @@ hipError_t launch_train_stage_grad(const float *x4, const int64_t *argmax, int N
         // input gradient 1152, the contractions 2048 + 1152 + 4 x 128
         ProfScope prof("k_ts_block", 2.0 * qpix * (2048.0 * 1.5625 + 4.0 * 1.13 * (288.0 + 256.0) + 1152.0 + 3712.0),
                        4.0 * qpix * (64.0 * 2 + 4.0 * 16) + qpix * 16 + 4.0 * G * TS_TRAINED, s);
-        hipLaunchKernelGGL(k_ts_block, dim3(G), dim3(256), 0, s, x4, ws.code, ws.dx, N, H, W, P, F, ws.part_s);
+        if (dx4) hipLaunchKernelGGL(k_ts_block<true>, dim3(G), dim3(256), 0, s, x4, ws.code, ws.dx, N, H, W, P, F, ws.part_s, dx4);
+        else     hipLaunchKernelGGL(k_ts_block<false>, dim3(G), dim3(256), 0, s, x4, ws.code, ws.dx, N, H, W, P, F, ws.part_s, dx4);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

@@ -686,6 +686,7 @@ class LastStageTrainer(LastBlockTrainer):
     _C_IMAGES = ("ssal_enet_train_stage", "ssal_enet_train_stage_semi")
     _CHANNELS, _UP = 64, 4
     _LIMIT = ("kernels'", "kernels'")
+    _LOWEST = _STAGE  # the lowest trained block: everything below it is frozen
 
     def _stage_offset(self):
         return _FINAL_OFFSET + 144 * int(self.net.classes)
@@ -755,10 +756,10 @@ class LastStageTrainer(LastBlockTrainer):
 
     def _check_params(self, params):
         unknown = set(params or {}) - set(self.variable_names)
-        frozen = self.net._layer_names[:self.net._layer_names.index(_STAGE)]
+        frozen = self.net._layer_names[:self.net._layer_names.index(self._LOWEST)]
         below = sorted(n for n in unknown if n.split(".")[0] in frozen)
         if below:
-            raise NotImplementedError("training below Bottleneck5_0 is not implemented (got %s)" % below)
+            raise NotImplementedError("training below %s is not implemented (got %s)" % (self._LOWEST, below))
         return super()._check_params(params)
 
     @staticmethod
@@ -819,6 +820,102 @@ class LastStageTrainer(LastBlockTrainer):
         return self._step_images(images, images_raw, labels, mask, semi, confusion, return_pseudo_pixels, extra)
 
 
+# ---- the decoder tail: Bottleneck4_2 + the last stage ------------------------------------------------
+# Bottleneck4_2's part of the packed tail block (include/ssal_enet.h, "Decoder-tail training"), offsets from its start: the
+# layout of a regular 64 -> 16 -> 16 -> 64 bottleneck
+_TAIL = "Bottleneck4_2"
+_TAIL_LAYOUT = (
+    ("proj_kernel", 0, True), ("proj_gamma", 1024, False), ("proj_beta", 1040, False), ("proj_alpha", 1056, True),
+    ("conv_kernel", 1072, True), ("conv_gamma", 3376, False), ("conv_beta", 3392, False), ("conv_alpha", 3408, True),
+    ("exp_kernel", 3424, True), ("exp_gamma", 4448, False), ("exp_beta", 4512, False), ("residual_alpha", 4576, True),
+)
+_TAIL_STATS = (("proj_mean", 4640), ("proj_variance", 4656), ("conv_mean", 4672), ("conv_variance", 4688),
+               ("exp_mean", 4704), ("exp_variance", 4768))
+_TAIL_FLOATS = 4840
+_TAIL_ADAM_RANGES = ((0, 1024, True), (1024, 1056, False), (1056, 3376, True), (3376, 3408, False), (3408, 4448, True),
+                     (4448, 4576, False), (4576, 4640, True))
+
+
+class DecoderTailTrainer(LastStageTrainer):
+    """Adam on the variables of ENet's decoder tail: the 26 of ``LastStageTrainer`` and ``Bottleneck4_2``'s ``proj_kernel``,
+    ``proj_gamma``, ``proj_beta``, ``proj_alpha``, ``conv_kernel``, ``conv_gamma``, ``conv_beta``, ``conv_alpha``,
+    ``exp_kernel``, ``exp_gamma``, ``exp_beta`` and ``residual_alpha`` (4 640 floats): the backward pass through a regular
+    64-channel bottleneck (1 x 1 projection 64 -> 16, 3 x 3 convolution, 1 x 1 expansion 16 -> 64, identity residual).
+
+    The deviation from the reference is ``LastBlockTrainer``'s: everything below Bottleneck4_2 is frozen and runs with
+    ``training=False``; the three trained blocks run in INFERENCE mode (constant moving statistics, never written; no spatial
+    dropout; batch-norm ``y = gamma (x - mean) / sqrt(var + 1e-3) + beta`` with ``gamma`` / ``beta`` trainable).
+
+    Regulariser: the Keras ``l1_l2`` gradient goes, next to ``LastStageTrainer``'s set, to the variables of Bottleneck4_2 the
+    reference attaches a regulariser to in ``Bottleneck`` (the list of Bottleneck5_1): ``proj_kernel``, ``proj_alpha``,
+    ``conv_kernel``, ``conv_alpha``, ``exp_kernel``, ``residual_alpha``; ``gamma`` / ``beta`` get the plain Adam update.
+
+    The inputs are Bottleneck4_1's output [N, h, w, 64] and ``argmax1`` [N, h, w, 16] int64 as ``LastStageTrainer`` takes it
+    (``features(images)`` returns both)."""
+
+    _C_FEATURES = ("ssal_train_tail_grad", "ssal_train_tail_grad_semi")
+    _C_IMAGES = ("ssal_enet_train_tail", "ssal_enet_train_tail_semi")
+    _LOWEST = _TAIL
+
+    def _tail_offset(self):
+        return self._stage_offset() + _STAGE_FLOATS
+
+    def _named(self):
+        """[(name, Variable, float offset, regularised)] of the trained variables: the last stage's 26, then Bottleneck4_2's"""
+        base = super()._named()
+        blk, t0 = getattr(self.net, _TAIL), self._tail_offset()
+        return base + [("%s.%s" % (_TAIL, a), getattr(blk, a), t0 + off, reg) for a, off, reg in _TAIL_LAYOUT]
+
+    def _floats(self):
+        return self._tail_offset() + _TAIL_FLOATS
+
+    def _pack(self, arrays=None):
+        out = super()._pack(arrays)
+        if arrays is None:
+            blk, t0 = getattr(self.net, _TAIL), self._tail_offset()
+            for a, off in _TAIL_STATS:
+                v = getattr(blk, a).numpy()
+                out[t0 + off:t0 + off + v.size] = v
+        return out
+
+    def _versions(self):
+        return super()._versions() + tuple(v.version for v in getattr(self.net, _TAIL).variables)
+
+    def _trained_tail(self):
+        return super()._trained_tail() + len(getattr(self.net, _TAIL).variables)
+
+    def _adam_ranges(self):
+        t0 = self._tail_offset()
+        return super()._adam_ranges() + tuple((t0 + lo, t0 + hi, reg) for lo, hi, reg in _TAIL_ADAM_RANGES)
+
+    def gradient_features(self, features4_1, argmax1, labels, mask, params=None, max_workgroups=0, **semi_keywords):
+        """(loss float64 [1], {name: gradient}) on the device for Bottleneck4_1's output [N, h, w, 64], the pooling indices
+        ``argmax1`` [N, h, w, 16] and labels / mask [N, 4h, 4w]; everything else as ``LastStageTrainer.gradient_features``
+        (``features_raw`` of the semi-supervised form is Bottleneck4_1 of the undistorted frames)."""
+        return super().gradient_features(features4_1, argmax1, labels, mask, params=params, max_workgroups=max_workgroups,
+                                         **semi_keywords)
+
+    def features(self, images):
+        """(Bottleneck4_1's output [N, H/4, W/4, 64] (a copy), argmax1 [N, H/4, W/4, 16] int64) for ``images``: what
+        ``step_features`` and ``gradient_features`` take.  One forward pass of the frozen trunk."""
+        net = self.net
+        x = net._prepare(images, False)
+        n, h, w, _ = x.shape
+        net(x, training=False)
+        off = _lib.lib().ssal_enet_train_tail_features_offset(net._handle, n, h, w)
+        if off < 0:
+            raise ValueError("bad input dims %s" % (tuple(x.shape),))
+        torch = _lib.require_gpu()
+        shape = (n, h // 4, w // 4, 64)
+        feats = net._ws[off:off + 4 * n * (h // 4) * (w // 4) * 64].view(torch.float32).view(shape).clone()
+        return feats, net.pooling_argmax()[0]
+
+    def step_features(self, features4_1, argmax1, labels, mask, max_workgroups=0, **semi_keywords):
+        """one Adam step from cached Bottleneck4_1 features and pooling indices (``features(images)``); returns the loss
+        (float64 device scalar) BEFORE the step"""
+        return super().step_features(features4_1, argmax1, labels, mask, max_workgroups=max_workgroups, **semi_keywords)
+
+
 # ---- the semi-supervised step of the two deeper trainers (DESIGN.md section 19) ---------------------------------------------
 class _SemiKeywords:
     """The semi-supervised keywords of ``FinalLayerTrainer`` (``labelled``, ``measure``, ``threshold``, ``features_raw`` /
@@ -847,5 +944,12 @@ class SemiSupervisedStageTrainer(_SemiKeywords, LastStageTrainer):
     ``LastStageTrainer`` on the composed targets; ``state`` / ``load_state`` are interchangeable with its."""
 
 
-__all__ = ["FinalLayerTrainer", "LastBlockTrainer", "LastStageTrainer", "SemiSupervisedBlockTrainer",
-           "SemiSupervisedStageTrainer"]
+class SemiSupervisedTailTrainer(_SemiKeywords, DecoderTailTrainer):
+    """``DecoderTailTrainer`` with the semi-supervised step built into the head kernel (see ``SemiSupervisedBlockTrainer``);
+    the undistorted frame's side of the feature entries is ``features_raw`` [N, h, w, 64] (Bottleneck4_1) with its own pooling
+    indices ``argmax1_raw``.  Loss and the gradients are bit-identical to ``DecoderTailTrainer`` on the composed targets;
+    ``state`` / ``load_state`` are interchangeable with its."""
+
+
+__all__ = ["FinalLayerTrainer", "LastBlockTrainer", "LastStageTrainer", "DecoderTailTrainer", "SemiSupervisedBlockTrainer",
+           "SemiSupervisedStageTrainer", "SemiSupervisedTailTrainer"]
