@@ -622,6 +622,54 @@ int ssal_enet_train_tail_semi_nhwc(ssal_enet *net, const void *x_dev, const void
                                    int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes,
                                    void *stream);
 
+/* ---- Decoder-tail training, two regular blocks: Bottleneck4_1 + the tail above (enet_modules.py:526-599; DESIGN.md section
+ * 21) ----
+ * The same gradient one more block down: Bottleneck4_2's backward also produces its input gradient, and Bottleneck4_1, a
+ * regular 64-channel bottleneck like it, is trained by a second launch of the same kernel.  Everything below Bottleneck4_1 is
+ * frozen; no gradient is produced for its input.
+ *
+ * The 50 trained variables and the 24 moving statistics travel in ONE packed fp32 block of
+ * ssal_train_tail2_param_floats(classes) = ssal_train_tail_param_floats(classes) + 4840 floats: the tail block above,
+ * unchanged, then Bottleneck4_1's part at float offset T2 = 3936 + 144 classes + 4840, laid out as Bottleneck4_2's part is
+ * (the offsets listed there, from T2).  grad_dev has the same layout.
+ *
+ * The ten entries mirror the tail's one for one: argument order, meaning, statuses, the order of the checks, the -1 /
+ * SSAL_EINVAL limits (h, w are the dims of Bottleneck4_0's output; Bottleneck4_1's and Bottleneck4_2's have the same) and
+ * "every argument is judged before any device work" are theirs.  features_dev / features_raw_dev [n,h,w,64] = Bottleneck4_0's
+ * output; both regular blocks run forward through the forward path's own kernel from weights folded on the device, so
+ * loss_dev is the forward op's value on ssal_enet_forward_nhwc's logits.  No float atomics: two calls give the same bits. */
+int64_t ssal_train_tail2_param_floats(int classes);
+int64_t ssal_train_tail2_grad_workspace_bytes(int n, int h, int w, int classes);
+int ssal_train_tail2_grad_nhwc(const float *features_dev, const int64_t *argmax_dev, int n, int h, int w, int classes,
+                               const float *params_dev, const uint8_t *labels_dev, const float *mask_dev, float weight,
+                               float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev, void *ws_dev,
+                               int64_t ws_bytes, void *stream);
+/* From images: the committed trunk's launchers up to Bottleneck4_0, then the chain with params_dev. */
+int64_t ssal_enet_train_tail2_workspace_bytes(const ssal_enet *net, int n, int h, int w);
+int ssal_enet_train_tail2_nhwc(ssal_enet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                               const uint8_t *labels_dev, const float *mask_dev, const float *params_dev, float weight,
+                               float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev, void *ws_dev,
+                               int64_t ws_bytes, void *stream);
+/* Byte offset, into the workspace of ssal_enet_train_tail2_nhwc / ssal_enet_train_tail2_semi_nhwc, of Bottleneck4_0's output
+ * [n,h/4,w/4,64] (the features_dev of ssal_train_tail2_grad_nhwc) as those calls leave it; valid until the next call.  (A
+ * forward or score call writes Bottleneck4_2's output to the same place.)  -1 for dims the net does not take. */
+int64_t ssal_enet_train_tail2_features_offset(const ssal_enet *net, int n, int h, int w);
+int64_t ssal_train_tail2_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw);
+int ssal_train_tail2_grad_semi_nhwc(const float *features_dev, const int64_t *argmax_dev, const float *features_raw_dev,
+                                    const int64_t *argmax_raw_dev, int n, int h, int w, int classes,
+                                    const float *params_dev, const uint8_t *labels_dev, const float *mask_dev,
+                                    const uint8_t *labelled_dev, int measure, float threshold, float weight,
+                                    float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev,
+                                    int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes,
+                                    void *stream);
+int64_t ssal_enet_train_tail2_semi_workspace_bytes(const ssal_enet *net, int n, int h, int w, int with_raw);
+int ssal_enet_train_tail2_semi_nhwc(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h,
+                                    int w, const uint8_t *labels_dev, const float *mask_dev, const uint8_t *labelled_dev,
+                                    int measure, float threshold, const float *params_dev, float weight,
+                                    float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev,
+                                    int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes,
+                                    void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2336,9 +2336,12 @@ SSAL_API int ssal_enet_train_stage_semi_nhwc(ssal_enet *net, const void *x_dev, 
     return enet_train_stage_entry(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, max_workgroups, a, &semi);
 }
 
-// ---- the decoder tail: Bottleneck4_2 + the last stage ----
-// h, w = the dims of Bottleneck4_1's output; own = the call brings no a4_2 / a5_0 / window-code buffers of its own
-static TrainTailWs train_tail_carve(Bump &b, int64_t n, int h, int w, int classes, bool own)
+// ---- the decoder tail: R regular blocks + the last stage (R = 1: Bottleneck4_2; R = 2: Bottleneck4_1
+// below it, section 21).  One body for both depths; the entries of R = 1 pass no R and run what they ran before. ----
+// h, w = the dims of the lowest trained block's input; own = the call brings no a4_2 / a5_0 / window-code buffers of its own.
+// R = 2 appends Bottleneck4_1's four pieces; an images entry of R = 2 has a4_0 and a4_1 in the forward workspace's two
+// quarter-resolution buffers, so its a4_2 is carved here.
+static TrainTailWs train_tail_carve(Bump &b, int64_t n, int h, int w, int classes, bool own, int R = 1)
 {
     TrainTailWs t;
     t.ts = train_stage_carve(b, n, h, w, classes, own);
@@ -2346,6 +2349,14 @@ static TrainTailWs train_tail_carve(Bump &b, int64_t n, int h, int w, int classe
     t.tfold = b.take<float>(TG_FLOATS);
     t.part_t = b.take<float>((int64_t)train_stage_workgroups(h, w, 0) * TT_TRAINED);
     t.a42 = own ? b.take<float>(n * h * w * 64) : nullptr;
+    t.a41 = t.dx41 = t.tfold2 = t.part_t2 = nullptr;
+    if (R == 2) {
+        t.dx41 = b.take<float>(n * h * w * 64);
+        t.tfold2 = b.take<float>(TG_FLOATS);
+        t.part_t2 = b.take<float>((int64_t)train_stage_workgroups(h, w, 0) * TT_TRAINED);
+        if (own) t.a41 = b.take<float>(n * h * w * 64);
+        else t.a42 = b.take<float>(n * h * w * 64);
+    }
     return t;
 }
 
@@ -2357,34 +2368,35 @@ static int train_tail_check(int n, int h, int w, int classes, int max_workgroups
     return SSAL_OK;
 }
 
-static int64_t train_tail_bytes(int n, int h, int w, int classes, bool own, bool semi, bool with_raw)
+static int64_t train_tail_bytes(int n, int h, int w, int classes, bool own, bool semi, bool with_raw, int R = 1)
 {
     if (!grad_dims_ok(n, h, w, classes, train_tail_fits)) return -1;
     Bump b(nullptr, 0);
-    train_tail_carve(b, n, h, w, classes, own);
+    train_tail_carve(b, n, h, w, classes, own, R);
     train_semi_carve(b, n, 16 * (int64_t)h * w, classes, semi, with_raw);
     return b.off + 256;
 }
 
-static int64_t enet_train_tail_bytes(const ssal_enet *net, int n, int h, int w, bool semi, bool with_raw)
+static int64_t enet_train_tail_bytes(const ssal_enet *net, int n, int h, int w, bool semi, bool with_raw, int R = 1)
 {
     if (!net_dims_ok(net, n, h, w)) return -1;
-    return behind_trunk_bytes(net, n, h, w, train_tail_bytes(n, h / 4, w / 4, net->classes, false, semi, with_raw));
+    return behind_trunk_bytes(net, n, h, w, train_tail_bytes(n, h / 4, w / 4, net->classes, false, semi, with_raw, R));
 }
 
-// b, need, trunk and what x41_raw sets off: as for train_stage_run.  x41 / x41_raw [n,h,w,64]: Bottleneck4_1 of the training /
-// the undistorted frames; an images entry has both in W.s1b, one after the other, and has Bottleneck4_2 written to a42 and
-// Bottleneck5_0 to a5, where the forward leaves them.
+// b, need, trunk and what x41_raw sets off: as for train_stage_run.  x41 / x41_raw [n,h,w,64]: the input of the lowest trained
+// block (Bottleneck4_1's output; R = 2: Bottleneck4_0's) of the training / the undistorted frames; an images entry has both in
+// one buffer of the forward workspace, one after the other, and has Bottleneck4_2 written to a42 (R = 2: Bottleneck4_1 to a42,
+// Bottleneck4_2 to the call's own buffer) and Bottleneck5_0 to a5, where the forward leaves them.
 template <typename Trunk>
 static int train_tail_run(Bump &b, int64_t need, Trunk trunk, const float *x41, const int64_t *argmax, const float *x41_raw,
                           const int64_t *argmax_raw, float *a42, float *a5, uint8_t *code, int n, int h, int w, int classes,
-                          const float *params_dev, int max_workgroups, const CallArgs &a, const SemiArgs *semi)
+                          const float *params_dev, int max_workgroups, const CallArgs &a, const SemiArgs *semi, int R = 1)
 {
-    TrainTailWs t = train_tail_carve(b, n, h, w, classes, a42 == nullptr);
+    TrainTailWs t = train_tail_carve(b, n, h, w, classes, a42 == nullptr, R);
     const TrainSemiWs sw = train_semi_carve(b, n, 16 * (int64_t)h * w, classes, semi != nullptr, semi && semi->with_raw);
     if (int rc = ws_check(need, b, a)) return rc;
     if (a42) {  // an images entry: the three live in the forward workspace
-        t.a42 = a42;
+        (R == 2 ? t.a41 : t.a42) = a42;
         t.ts.a5 = a5;
         t.ts.code = code;
     }
@@ -2393,31 +2405,32 @@ static int train_tail_run(Bump &b, int64_t need, Trunk trunk, const float *x41, 
         if (semi) sa = train_semi_args(*semi, sw, rep, reps);
         if (x41_raw) {
             if (int rc = trunk(true)) return rc;
-            HIP_TRY(launch_train_tail_targets(x41_raw, argmax_raw, n, h, w, classes, params_dev, max_workgroups, t, sa, a.s));
+            HIP_TRY(launch_train_tail_targets(x41_raw, argmax_raw, n, h, w, classes, params_dev, max_workgroups, t, sa, a.s, R));
         }
         if (int rc = trunk(false)) return rc;
         HIP_TRY(launch_train_tail_grad(x41, argmax, n, h, w, classes, params_dev, a.labels, a.mask, a.weight, a.label_smoothing,
-                                       max_workgroups, t, a.loss, a.grad, a.s, semi ? &sa : nullptr));
+                                       max_workgroups, t, a.loss, a.grad, a.s, semi ? &sa : nullptr, R));
         return SSAL_OK;
     });
 }
 
 static int train_tail_grad_entry(const float *features_dev, const int64_t *argmax_dev, const float *features_raw_dev,
                                  const int64_t *argmax_raw_dev, int n, int h, int w, int classes, const float *params_dev,
-                                 int max_workgroups, const CallArgs &a, const SemiArgs *semi)
+                                 int max_workgroups, const CallArgs &a, const SemiArgs *semi, int R = 1)
 {
     if (int rc = train_tail_check(n, h, w, classes, max_workgroups)) return rc;
     if (int rc = args_check(features_dev && argmax_dev && params_dev, a, semi)) return rc;
     if ((features_raw_dev == nullptr) != (argmax_raw_dev == nullptr))
         return fail(SSAL_EINVAL, "features_raw_dev and argmax_raw_dev are given together or not at all");
     Bump b(a.ws, a.ws_bytes);
-    return train_tail_run(b, train_tail_bytes(n, h, w, classes, true, semi != nullptr, features_raw_dev != nullptr), no_trunk,
+    return train_tail_run(b, train_tail_bytes(n, h, w, classes, true, semi != nullptr, features_raw_dev != nullptr, R), no_trunk,
                           features_dev, argmax_dev, features_raw_dev, argmax_raw_dev, nullptr, nullptr, nullptr, n, h, w,
-                          classes, params_dev, max_workgroups, a, semi);
+                          classes, params_dev, max_workgroups, a, semi, R);
 }
 
 static int enet_train_tail_entry(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h, int w,
-                                 const float *params_dev, int max_workgroups, const CallArgs &a, const SemiArgs *semi)
+                                 const float *params_dev, int max_workgroups, const CallArgs &a, const SemiArgs *semi,
+                                 int R = 1)
 {
     int rc = check_dims(net, n, h, w);
     if (rc) return rc;
@@ -2426,13 +2439,15 @@ static int enet_train_tail_entry(ssal_enet *net, const void *x_dev, const void *
     NetWorkspace W;
     Bump b = carve_behind_trunk(net, a, n, h, w, &W);
     // the frozen trunk is Initial .. Bottleneck4_1 (its output lands in W.s1b, the window codes of Bottleneck1_0's pooling
-    // in W.code1); Bottleneck4_2 runs from params_dev into W.s1a and Bottleneck5_0 into W.a0, where the forward leaves them
+    // in W.code1); Bottleneck4_2 runs from params_dev into W.s1a and Bottleneck5_0 into W.a0, where the forward leaves them.
+    // R = 2: the trunk ends one layer earlier, at Bottleneck4_0 in W.s1a, and Bottleneck4_1 runs from params_dev into W.s1b
+    float *x41 = R == 2 ? W.s1a : W.s1b, *next = R == 2 ? W.s1b : W.s1a;
     auto trunk = [&](bool of_raw) {
-        return run_trunk(net, kNumLayers - 4, of_raw ? x_raw_dev : x_dev, x_is_u8, W, n, h, w, a.s);
+        return run_trunk(net, kNumLayers - 3 - R, of_raw ? x_raw_dev : x_dev, x_is_u8, W, n, h, w, a.s);
     };
-    return train_tail_run(b, enet_train_tail_bytes(net, n, h, w, semi != nullptr, x_raw_dev != nullptr), trunk, W.s1b, nullptr,
-                          x_raw_dev && semi->labelled ? W.s1b : nullptr, nullptr, W.s1a, W.a0, W.code1, n, h / 4, w / 4,
-                          net->classes, params_dev, max_workgroups, a, semi);
+    return train_tail_run(b, enet_train_tail_bytes(net, n, h, w, semi != nullptr, x_raw_dev != nullptr, R), trunk, x41, nullptr,
+                          x_raw_dev && semi->labelled ? x41 : nullptr, nullptr, next, W.a0, W.code1, n, h / 4, w / 4,
+                          net->classes, params_dev, max_workgroups, a, semi, R);
 }
 
 SSAL_API int64_t ssal_train_tail_param_floats(int classes)
@@ -2512,4 +2527,85 @@ SSAL_API int ssal_enet_train_tail_semi_nhwc(ssal_enet *net, const void *x_dev, c
     const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
     const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev != nullptr};
     return enet_train_tail_entry(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, max_workgroups, a, &semi);
+}
+
+// ---- decoder-tail training, two regular blocks: Bottleneck4_1 + the tail.  The tail's entries with R = 2.
+SSAL_API int64_t ssal_train_tail2_param_floats(int classes)
+{
+    return classes < 2 || classes > 32 ? -1 : train_tail_floats(classes, 2);
+}
+
+SSAL_API int64_t ssal_train_tail2_grad_workspace_bytes(int n, int h, int w, int classes)
+{
+    return train_tail_bytes(n, h, w, classes, true, false, false, 2);
+}
+
+SSAL_API int ssal_train_tail2_grad_nhwc(const float *features_dev, const int64_t *argmax_dev, int n, int h, int w, int classes,
+                                        const float *params_dev, const uint8_t *labels_dev, const float *mask_dev, float weight,
+                                        float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev,
+                                        void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return train_tail_grad_entry(features_dev, argmax_dev, nullptr, nullptr, n, h, w, classes, params_dev, max_workgroups, a,
+                                 nullptr, 2);
+}
+
+SSAL_API int64_t ssal_enet_train_tail2_workspace_bytes(const ssal_enet *net, int n, int h, int w)
+{
+    return enet_train_tail_bytes(net, n, h, w, false, false, 2);
+}
+
+// byte offset (into the workspace passed to train_tail2) of Bottleneck4_0's output [n,h/4,w/4,64]: where
+// ssal_enet_train_tail2_nhwc and its semi form leave it (a forward / score call writes Bottleneck4_2 over it); valid until
+// the next call.  -1 for dims the net does not take.
+SSAL_API int64_t ssal_enet_train_tail2_features_offset(const ssal_enet *net, int n, int h, int w)
+{
+    if (!net_dims_ok(net, n, h, w)) return -1;
+    NetWorkspace W = carve(net, (void *)256, ((int64_t)1 << 62), n, h, w);
+    return (const char *)W.s1a - (const char *)256;
+}
+
+SSAL_API int ssal_enet_train_tail2_nhwc(ssal_enet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                                        const uint8_t *labels_dev, const float *mask_dev, const float *params_dev,
+                                        float weight, float label_smoothing, int max_workgroups, double *loss_dev,
+                                        float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return enet_train_tail_entry(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, max_workgroups, a, nullptr, 2);
+}
+
+SSAL_API int64_t ssal_train_tail2_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw)
+{
+    return train_tail_bytes(n, h, w, classes, true, true, with_raw != 0, 2);
+}
+
+SSAL_API int ssal_train_tail2_grad_semi_nhwc(const float *features_dev, const int64_t *argmax_dev,
+                                             const float *features_raw_dev, const int64_t *argmax_raw_dev, int n, int h,
+                                             int w, int classes, const float *params_dev, const uint8_t *labels_dev,
+                                             const float *mask_dev, const uint8_t *labelled_dev, int measure,
+                                             float threshold, float weight, float label_smoothing, int max_workgroups,
+                                             double *loss_dev, float *grad_dev, int64_t *confusion_dev,
+                                             int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, features_raw_dev != nullptr};
+    return train_tail_grad_entry(features_dev, argmax_dev, features_raw_dev, argmax_raw_dev, n, h, w, classes, params_dev,
+                                 max_workgroups, a, &semi, 2);
+}
+
+SSAL_API int64_t ssal_enet_train_tail2_semi_workspace_bytes(const ssal_enet *net, int n, int h, int w, int with_raw)
+{
+    return enet_train_tail_bytes(net, n, h, w, true, with_raw != 0, 2);
+}
+
+SSAL_API int ssal_enet_train_tail2_semi_nhwc(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
+                                             int h, int w, const uint8_t *labels_dev, const float *mask_dev,
+                                             const uint8_t *labelled_dev, int measure, float threshold,
+                                             const float *params_dev, float weight, float label_smoothing,
+                                             int max_workgroups, double *loss_dev, float *grad_dev, int64_t *confusion_dev,
+                                             int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev != nullptr};
+    return enet_train_tail_entry(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, max_workgroups, a, &semi, 2);
 }

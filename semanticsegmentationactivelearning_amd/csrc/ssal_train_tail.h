@@ -35,6 +35,9 @@ constexpr int TG_ES = 96, TG_ET = 160, TG_EI = 224;   // expansion
 constexpr int TG_FLOATS = 288;
 
 inline int64_t train_tail_floats(int K) { return train_stage_floats(K) + TT_FLOATS; }
+// R regular blocks above the stage (R = 1: Bottleneck4_2; R = 2: Bottleneck4_1 below it): the tail block
+// is a prefix and every further block's part of TT_FLOATS floats follows it
+inline int64_t train_tail_floats(int K, int R) { return train_stage_floats(K) + (int64_t)R * TT_FLOATS; }
 
 // H, W = the dims of Bottleneck4_1's output (quarter resolution): the stage's limit and that of the fused 64-channel
 // bottleneck kernel the forward runs on
@@ -42,22 +45,27 @@ bool train_tail_fits(int H, int W);
 
 // Workspace of one gradient call: the stage workspace, a42 [N,H,W,64] (Bottleneck4_2's output; NULL when the caller supplies
 // it elsewhere), dx4 [N,H,W,64] (dL/d a4_2 before the 1 / sum(mask) factor), tfold [TG_FLOATS], part_t [G][TT_TRAINED].
+// R = 2 adds the same four for Bottleneck4_1: a41 (its output), dx41 (dL/d a4_1, as dx4), tfold2, part_t2; NULL with R = 1.
 struct TrainTailWs {
     TrainStageWs ts;
     float *a42, *dx4, *tfold, *part_t;
+    float *a41, *dx41, *tfold2, *part_t2;
 };
 
-// x41 [N,H,W,64] = Bottleneck4_1's output; argmax as for launch_train_stage_grad; params / grad: the tail block of
-// train_tail_floats(K) floats; labels uint8 / mask fp32 [N,4H,4W]; loss one double.
-hipError_t launch_train_tail_grad(const float *x41, const int64_t *argmax, int N, int H, int W, int K, const float *params,
+// x [N,H,W,64] = the input of the lowest trained block: Bottleneck4_1's output (R = 1) or Bottleneck4_0's (R = 2); argmax as
+// for launch_train_stage_grad; params / grad: the block of train_tail_floats(K, R) floats; labels uint8 / mask fp32 [N,4H,4W];
+// loss one double.  R = 2: Bottleneck4_1 and 4_2 forward, the stage, k_tt_block<true> on (a4_1, dx4) -> dx41, k_tt_block<false>
+// on (x, dx41), k_tt_finish per block.
+hipError_t launch_train_tail_grad(const float *x, const int64_t *argmax, int N, int H, int W, int K, const float *params,
                                   const uint8_t *labels, const float *mask, float weight, float label_smoothing,
                                   int max_workgroups, const TrainTailWs &ws, double *loss, float *grad, hipStream_t s,
-                                  const TrainBlockSemi *semi = nullptr);
+                                  const TrainBlockSemi *semi = nullptr, int R = 1);
 
 // The semi-supervised step with undistorted frames: Bottleneck4_2 of x41_raw through the scoring path's kernel into ws.a42,
 // then launch_train_stage_targets on it.  Uses ws.a42 and ws.tfold, which launch_train_tail_grad writes again afterwards.
-hipError_t launch_train_tail_targets(const float *x41_raw, const int64_t *argmax_raw, int N, int H, int W, int K,
+// R = 2: x_raw is Bottleneck4_0 of the undistorted frames and Bottleneck4_1 runs first, into ws.a41 (with ws.tfold2).
+hipError_t launch_train_tail_targets(const float *x_raw, const int64_t *argmax_raw, int N, int H, int W, int K,
                                      const float *params, int max_workgroups, const TrainTailWs &ws,
-                                     const TrainBlockSemi &semi, hipStream_t s);
+                                     const TrainBlockSemi &semi, hipStream_t s, int R = 1);
 
 }  // namespace ssal

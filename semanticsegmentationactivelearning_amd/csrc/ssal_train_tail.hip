@@ -6,7 +6,8 @@
 //   (forward)    a4_2 = the library's own Bottleneck4_2 forward, launch_bottleneck_mfma (Cin = 64), on those weights
 //   (stage)      launch_train_stage_grad on a4_2 (ssal_train_stage.hip) with k_ts_block<true>, which also writes dL/d a4_2
 //   k_tt_block   the bottleneck's forward again on the window a tile needs, and its backward: per-workgroup partials of the
-//                12 gradients
+//                12 gradients; <true> also writes the block's input gradient, which makes it a link of a chain: with
+//                R = 2 Bottleneck4_1 below Bottleneck4_2 is a second fold, forward and launch
 //   k_tt_finish  fixed-order compensated fold of the partials, times 1 / sum(mask)
 // Semantics: enet_modules.py:526-599 in inference mode (moving statistics are constants, no dropout); PReLU and its
 // derivative at 0 as in ssal_train_block.hip.  Nothing in the two kernels names the layer: they take the block's part of
@@ -24,6 +25,7 @@ namespace {
 constexpr int TT_Q = 8;    // pixels per tile side (the stage's 8 x 8 patch)
 constexpr int TT_CW = 10;  // convolution window: the tile plus a ring of one
 constexpr int TT_PW = 12;  // projected window: one more ring
+constexpr int TT_UW = 65;  // k_tt_block<true>'s ldu: floats per channel row (64 pixels and one of padding)
 constexpr int TT_CITEMS = TT_CW * TT_CW * 4;  // (pixel of the convolution window, channel quarter)
 // k_tt_block's LDS copy of the per-channel scalars: the folded ones [0, TG_FLOATS) as k_tt_fold lays them out, then
 // proj_alpha, conv_alpha, residual_alpha and the three moving means from the packed block
@@ -91,12 +93,15 @@ __global__ __launch_bounds__(256) void k_tt_fold(const float *__restrict__ P, fl
 //       exp_kernel (thread = input channel x four outputs).
 // The 72 per-channel sums of a thread (its channel quarter is tid & 3 in C2 and D alike) accumulate in registers and are
 // folded over the 64 threads of a quarter in thread order, compensated, at the end.  gamma / beta gradients are produced
-// directly, as in k_tb_block.  No gradient is produced for x: D holds dL/d(proj accumulator) and C2 dL/du of every tile pixel,
-// which is what an input-gradient flag would contract with proj_kernel and add.  part [gridDim.x][TT_TRAINED]: every slot
-// is written.
+// directly, as in k_tb_block.  part [gridDim.x][TT_TRAINED]: every slot is written.
+// DX (a block with another trained block below it): the block's INPUT gradient of the tile's pixels ->
+// dx [N,H,W,64], written once between D and E, before the 1 / sum(mask) factor as g is: dL/du (the identity residual; C2 leaves
+// it in ldu, channel-major with a row of 65 so that neither side meets a bank twice) plus the projection's input gradient
+// sum_k dL/d(proj acc)[k] W_p[ci][k] (BN and PReLU are inside lpa), one fmaf chain that starts at dL/du and takes k = 0 .. 15.
+template <bool DX>
 __global__ __launch_bounds__(256) void k_tt_block(const float *__restrict__ x, const float *__restrict__ g, int N, int H, int W,
                                                   const float *__restrict__ P, const float *__restrict__ F,
-                                                  float *__restrict__ part)
+                                                  float *__restrict__ part, float *__restrict__ dx)
 {
     __shared__ __attribute__((aligned(16))) float lwc[9 * 16 * 16];
     __shared__ __attribute__((aligned(16))) float lwe[16 * 64];
@@ -107,6 +112,7 @@ __global__ __launch_bounds__(256) void k_tt_block(const float *__restrict__ x, c
     __shared__ __attribute__((aligned(16))) float lq[TT_CW * TT_CW * 16];
     __shared__ __attribute__((aligned(16))) float ldc[TT_CW * TT_CW * 16];
     __shared__ __attribute__((aligned(16))) float lde[64 * 64];
+    __shared__ float ldu[DX ? 64 * TT_UW : 1];  // C2 -> DX: dL/du of the tile's pixels, [channel][pixel]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int kq = tid & 3;
@@ -238,6 +244,8 @@ __global__ __launch_bounds__(256) void k_tt_block(const float *__restrict__ x, c
                             el[32 + lc] += d * tt_neg(u);
                         }
                         de[c] = du * lk[TG_ES + co];
+                        if constexpr (DX)
+                            if (own) ldu[co * TT_UW + (pi - 1) * TT_Q + pj - 1] = du;
                     }
                     if (own)
                         reinterpret_cast<float4 *>(lde)[((pi - 1) * TT_Q + pj - 1) * 16 + 4 * kq + c4] = make_float4(de[0], de[1], de[2], de[3]);
@@ -315,6 +323,25 @@ __global__ __launch_bounds__(256) void k_tt_block(const float *__restrict__ x, c
                 reinterpret_cast<float4 *>(lpa)[tid] = make_float4(dap[0], dap[1], dap[2], dap[3]);
             }
             __syncthreads();
+            if constexpr (DX) {
+                // lane = pixel of the tile, wave = 16 input channels with proj_kernel's rows in scalar registers
+                const int qi = i0 + (lane >> 3), qj = j0 + (lane & 7);
+                const bool inside = qi < H && qj < W;
+                float dv[16];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float4 d = reinterpret_cast<const float4 *>(lpa)[lane * 4 + q];
+                    dv[4 * q] = d.x; dv[4 * q + 1] = d.y; dv[4 * q + 2] = d.z; dv[4 * q + 3] = d.w;
+                }
+                float *dxp = dx + ((long)n * HW + (long)min(qi, H - 1) * W + min(qj, W - 1)) * 64;
+#pragma unroll 1
+                for (int ci = 16 * wv; ci < 16 * wv + 16; ++ci) {
+                    float v = ldu[ci * TT_UW + lane];
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) v = fmaf(dv[k], P[TT_WP + ci * 16 + k], v);
+                    if (inside) dxp[ci] = v;
+                }
+            }
             // ---- E
             {
                 const int c = tid >> 2;
@@ -405,43 +432,75 @@ static hipError_t tail_forward(const float *x41, float *a42, int N, int H, int W
                                   F + TG_CS, F + TG_CT, PT + TT_CA, PT + TT_WE, F + TG_ES, F + TG_ET, PT + TT_RA, s);
 }
 
-hipError_t launch_train_tail_grad(const float *x41, const int64_t *argmax, int N, int H, int W, int K, const float *params,
+// one regular block's backward: x = its input, g = dL/d(its output), PT / F = its part of the packed block and its folded
+// form; dx not NULL: its input gradient goes there (k_tt_block<true>)
+static hipError_t tail_block_grad(const float *x, const float *g, int N, int H, int W, int G, const float *PT, const float *F,
+                                  float *part, float *dx, hipStream_t s)
+{
+    const double pix = (double)N * H * W;
+    // per pixel: the projection on a 12 x 12 window for an 8 x 8 tile (1024 FMAs x 2.25), the convolution and the expansion
+    // forward and backward on the 10 x 10 window ((2304 + 2 x 1024) x 1.5625), the convolution's input gradient 2304, the
+    // contractions 1024 + 2304 + 1024; the input gradient another 1024 and its 64 floats
+    ProfScope prof(dx ? "k_tt_block<dx>" : "k_tt_block",
+                   2.0 * pix * (1024.0 * 2.25 + 4352.0 * 1.5625 + 2304.0 + 4352.0 + (dx ? 1024.0 : 0.0)),
+                   4.0 * pix * 64.0 * (dx ? 3 : 2) + 4.0 * G * TT_TRAINED, s);
+    if (dx)
+        hipLaunchKernelGGL(k_tt_block<true>, dim3(G), dim3(256), 0, s, x, g, N, H, W, PT, F, part, dx);
+    else
+        hipLaunchKernelGGL(k_tt_block<false>, dim3(G), dim3(256), 0, s, x, g, N, H, W, PT, F, part, dx);
+    return hipGetLastError();
+}
+
+hipError_t launch_train_tail_grad(const float *x, const int64_t *argmax, int N, int H, int W, int K, const float *params,
                                   const uint8_t *labels, const float *mask, float weight, float label_smoothing,
                                   int max_workgroups, const TrainTailWs &ws, double *loss, float *grad, hipStream_t s,
-                                  const TrainBlockSemi *semi)
+                                  const TrainBlockSemi *semi, int R)
 {
-    if (N < 1 || K < 2 || K > 32 || !train_tail_fits(H, W)) return hipErrorInvalidValue;
+    if (N < 1 || K < 2 || K > 32 || R < 1 || R > 2 || !train_tail_fits(H, W)) return hipErrorInvalidValue;
     const int G = train_stage_workgroups(H, W, max_workgroups);
-    const float *PT = params + train_stage_floats(K);
-    hipError_t e = tail_forward(x41, ws.a42, N, H, W, PT, ws.tfold, s);
+    const float *PT = params + train_stage_floats(K), *PT1 = PT + TT_FLOATS;  // Bottleneck4_2's part, Bottleneck4_1's
+    hipError_t e;
+    const float *x41 = x;
+    if (R == 2) {
+        e = tail_forward(x, ws.a41, N, H, W, PT1, ws.tfold2, s);
+        if (e != hipSuccess) return e;
+        x41 = ws.a41;
+    }
+    e = tail_forward(x41, ws.a42, N, H, W, PT, ws.tfold, s);
     if (e != hipSuccess) return e;
     e = launch_train_stage_grad(ws.a42, argmax, N, H, W, K, params, labels, mask, weight, label_smoothing, max_workgroups, ws.ts,
                                 loss, grad, s, semi, ws.dx4);
     if (e != hipSuccess) return e;
-    const double pix = (double)N * H * W;
-    {
-        // per pixel: the projection on a 12 x 12 window for an 8 x 8 tile (1024 FMAs x 2.25), the convolution and the expansion
-        // forward and backward on the 10 x 10 window ((2304 + 2 x 1024) x 1.5625), the convolution's input gradient 2304, the
-        // contractions 1024 + 2304 + 1024
-        ProfScope prof("k_tt_block", 2.0 * pix * (1024.0 * 2.25 + 4352.0 * 1.5625 + 2304.0 + 4352.0),
-                       4.0 * pix * 64.0 * 2 + 4.0 * G * TT_TRAINED, s);
-        hipLaunchKernelGGL(k_tt_block, dim3(G), dim3(256), 0, s, x41, ws.dx4, N, H, W, PT, ws.tfold, ws.part_t);
+    e = tail_block_grad(x41, ws.dx4, N, H, W, G, PT, ws.tfold, ws.part_t, R == 2 ? ws.dx41 : nullptr, s);
+    if (e != hipSuccess) return e;
+    if (R == 2) {
+        e = tail_block_grad(x, ws.dx41, N, H, W, G, PT1, ws.tfold2, ws.part_t2, nullptr, s);
+        if (e != hipSuccess) return e;
+    }
+    for (int r = 0; r < R; ++r) {
+        ProfScope prof("k_tt_finish", (double)G * TT_TRAINED, 4.0 * G * TT_TRAINED + 16.0 * G, s);
+        hipLaunchKernelGGL(k_tt_finish, dim3((TT_FLOATS + 255) / 256), dim3(256), 0, s, r ? ws.part_t2 : ws.part_t,
+                           ws.ts.tb.lpart, G, grad + train_stage_floats(K) + r * TT_FLOATS);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    ProfScope prof("k_tt_finish", (double)G * TT_TRAINED, 4.0 * G * TT_TRAINED + 16.0 * G, s);
-    hipLaunchKernelGGL(k_tt_finish, dim3((TT_FLOATS + 255) / 256), dim3(256), 0, s, ws.part_t, ws.ts.tb.lpart, G,
-                       grad + train_stage_floats(K));
-    return hipGetLastError();
+    return hipSuccess;
 }
 
-hipError_t launch_train_tail_targets(const float *x41_raw, const int64_t *argmax_raw, int N, int H, int W, int K,
+hipError_t launch_train_tail_targets(const float *x_raw, const int64_t *argmax_raw, int N, int H, int W, int K,
                                      const float *params, int max_workgroups, const TrainTailWs &ws,
-                                     const TrainBlockSemi &semi, hipStream_t s)
+                                     const TrainBlockSemi &semi, hipStream_t s, int R)
 {
-    if (N < 1 || K < 2 || K > 32 || !train_tail_fits(H, W) || !x41_raw) return hipErrorInvalidValue;
+    if (N < 1 || K < 2 || K > 32 || R < 1 || R > 2 || !train_tail_fits(H, W) || !x_raw) return hipErrorInvalidValue;
     if (!semi.labelled) return hipSuccess;  // every image is labelled: no pseudo target is read
-    const hipError_t e = tail_forward(x41_raw, ws.a42, N, H, W, params + train_stage_floats(K), ws.tfold, s);
+    const float *PT = params + train_stage_floats(K);
+    const float *x41_raw = x_raw;
+    if (R == 2) {
+        const hipError_t e1 = tail_forward(x_raw, ws.a41, N, H, W, PT + TT_FLOATS, ws.tfold2, s);
+        if (e1 != hipSuccess) return e1;
+        x41_raw = ws.a41;
+    }
+    const hipError_t e = tail_forward(x41_raw, ws.a42, N, H, W, PT, ws.tfold, s);
     if (e != hipSuccess) return e;
     return launch_train_stage_targets(ws.a42, argmax_raw, N, H, W, K, params, max_workgroups, ws.ts, semi, s);
 }

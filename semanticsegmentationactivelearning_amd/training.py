@@ -916,6 +916,86 @@ class DecoderTailTrainer(LastStageTrainer):
         return super().step_features(features4_1, argmax1, labels, mask, max_workgroups=max_workgroups, **semi_keywords)
 
 
+# ---- the deep tail: Bottleneck4_1 + the decoder tail --------------------------------------------------
+# Bottleneck4_1's part of the packed block follows the tail block and is laid out as Bottleneck4_2's (a regular bottleneck's)
+_DEEP = "Bottleneck4_1"
+
+
+class DeepTailTrainer(DecoderTailTrainer):
+    """Adam on 50 variables: the 38 of ``DecoderTailTrainer``, then ``Bottleneck4_1``'s twelve (``proj_kernel`` ..
+    ``residual_alpha``, 4 640 floats).  Bottleneck4_2's backward also yields its input gradient, and the second regular
+    64-channel bottleneck is a second launch of the same kernel on it: the regular-bottleneck backward as a chain link.
+
+    The deviation from the reference is ``LastBlockTrainer``'s: everything below Bottleneck4_1 is frozen and runs with
+    ``training=False``; the four trained blocks run in INFERENCE mode (constant moving statistics, never written; no spatial
+    dropout; batch-norm ``y = gamma (x - mean) / sqrt(var + 1e-3) + beta`` with ``gamma`` / ``beta`` trainable).
+
+    Regulariser: the Keras ``l1_l2`` gradient goes, next to ``DecoderTailTrainer``'s set, to the variables of Bottleneck4_1
+    the reference attaches a regulariser to in ``Bottleneck``: ``proj_kernel``, ``proj_alpha``, ``conv_kernel``,
+    ``conv_alpha``, ``exp_kernel``, ``residual_alpha``; ``gamma`` / ``beta`` get the plain Adam update.
+
+    The inputs are Bottleneck4_0's output [N, h, w, 64] and ``argmax1`` [N, h, w, 16] int64 as ``LastStageTrainer`` takes it
+    (``features(images)`` returns both)."""
+
+    _C_FEATURES = ("ssal_train_tail2_grad", "ssal_train_tail2_grad_semi")
+    _C_IMAGES = ("ssal_enet_train_tail2", "ssal_enet_train_tail2_semi")
+    _LOWEST = _DEEP
+
+    def _deep_offset(self):
+        return self._tail_offset() + _TAIL_FLOATS
+
+    def _named(self):
+        """[(name, Variable, float offset, regularised)] of the trained variables: the tail's 38, then Bottleneck4_1's"""
+        base = super()._named()
+        blk, t0 = getattr(self.net, _DEEP), self._deep_offset()
+        return base + [("%s.%s" % (_DEEP, a), getattr(blk, a), t0 + off, reg) for a, off, reg in _TAIL_LAYOUT]
+
+    def _floats(self):
+        return self._deep_offset() + _TAIL_FLOATS
+
+    def _pack(self, arrays=None):
+        out = super()._pack(arrays)
+        if arrays is None:
+            blk, t0 = getattr(self.net, _DEEP), self._deep_offset()
+            for a, off in _TAIL_STATS:
+                v = getattr(blk, a).numpy()
+                out[t0 + off:t0 + off + v.size] = v
+        return out
+
+    def _versions(self):
+        return super()._versions() + tuple(v.version for v in getattr(self.net, _DEEP).variables)
+
+    def _trained_tail(self):
+        return super()._trained_tail() + len(getattr(self.net, _DEEP).variables)
+
+    def _adam_ranges(self):
+        t0 = self._deep_offset()
+        return super()._adam_ranges() + tuple((t0 + lo, t0 + hi, reg) for lo, hi, reg in _TAIL_ADAM_RANGES)
+
+    def gradient_features(self, features4_0, argmax1, labels, mask, params=None, max_workgroups=0, **semi_keywords):
+        """(loss float64 [1], {name: gradient}) on the device for Bottleneck4_0's output [N, h, w, 64], the pooling indices
+        ``argmax1`` [N, h, w, 16] and labels / mask [N, 4h, 4w]; everything else as ``LastStageTrainer.gradient_features``
+        (``features_raw`` of the semi-supervised form is Bottleneck4_0 of the undistorted frames)."""
+        return super().gradient_features(features4_0, argmax1, labels, mask, params=params, max_workgroups=max_workgroups,
+                                         **semi_keywords)
+
+    def features(self, images):
+        """(Bottleneck4_0's output [N, H/4, W/4, 64], argmax1 [N, H/4, W/4, 16] int64) for ``images``: what
+        ``step_features`` and ``gradient_features`` take.  One forward pass of the frozen trunk, whose later layers write over
+        Bottleneck4_0's output, and the model's own Bottleneck4_0 on the Bottleneck3_8 endpoint it leaves."""
+        net = self.net
+        x = net._prepare(images, False)
+        net(x, training=False)
+        a38 = net.endpoint_outputs[-1][3].clone()
+        argmax1, argmax2 = net.pooling_argmax()
+        return net.Bottleneck4_0(a38, argmax2, training=False), argmax1
+
+    def step_features(self, features4_0, argmax1, labels, mask, max_workgroups=0, **semi_keywords):
+        """one Adam step from cached Bottleneck4_0 features and pooling indices (``features(images)``); returns the loss
+        (float64 device scalar) BEFORE the step"""
+        return super().step_features(features4_0, argmax1, labels, mask, max_workgroups=max_workgroups, **semi_keywords)
+
+
 # ---- the semi-supervised step of the two deeper trainers (DESIGN.md section 19) ---------------------------------------------
 class _SemiKeywords:
     """The semi-supervised keywords of ``FinalLayerTrainer`` (``labelled``, ``measure``, ``threshold``, ``features_raw`` /
@@ -951,5 +1031,12 @@ class SemiSupervisedTailTrainer(_SemiKeywords, DecoderTailTrainer):
     ``state`` / ``load_state`` are interchangeable with its."""
 
 
+class SemiSupervisedDeepTailTrainer(_SemiKeywords, DeepTailTrainer):
+    """``DeepTailTrainer`` with the semi-supervised step built into the head kernel (see ``SemiSupervisedBlockTrainer``);
+    the undistorted frame's side of the feature entries is ``features_raw`` [N, h, w, 64] (Bottleneck4_0) with its own pooling
+    indices ``argmax1_raw``.  Loss and the gradients are bit-identical to ``DeepTailTrainer`` on the composed targets;
+    ``state`` / ``load_state`` are interchangeable with its."""
+
+
 __all__ = ["FinalLayerTrainer", "LastBlockTrainer", "LastStageTrainer", "DecoderTailTrainer", "SemiSupervisedBlockTrainer",
-           "SemiSupervisedStageTrainer", "SemiSupervisedTailTrainer"]
+           "SemiSupervisedStageTrainer", "SemiSupervisedTailTrainer", "DeepTailTrainer", "SemiSupervisedDeepTailTrainer"]
