@@ -670,6 +670,60 @@ int ssal_enet_train_tail2_semi_nhwc(ssal_enet *net, const void *x_dev, const voi
                                     int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes,
                                     void *stream);
 
+/* ---- Decoder training: Bottleneck4_0 + the two-block tail above (enet_modules.py:1217-1292) ----
+ * The same gradient one more block down, through the 128 -> 64 upsampling block that opens the decoder: the trained part is
+ * exactly ENet's decoder over a frozen encoder.  No gradient is produced for Bottleneck3_8's output.
+ *
+ * The 63 trained variables and the 30 moving statistics travel in ONE packed fp32 block of
+ * ssal_train_decoder_param_floats(classes) = ssal_train_tail2_param_floats(classes) + 18488 floats: the two-block tail block
+ * above, unchanged, then Bottleneck4_0's part at float offset T4 = 3936 + 144 classes + 2 * 4840, laid out in the order of
+ * Bottleneck5_0's part with this block's sizes (offsets from T4): proj_kernel [128][32] 0, proj_gamma / proj_beta /
+ * proj_alpha [32] 4096 / 4128 / 4160, conv_kernel [3][3][16][32] (HW-O-I) 4192, conv_gamma / conv_beta / conv_alpha [16]
+ * 8800 / 8816 / 8832, exp_kernel [16][64] 8848, exp_gamma / exp_beta [64] 9872 / 9936, res_kernel [128][64] 10000,
+ * residual_alpha [64] 18192; trained floats [0, 18256); proj_mean / proj_variance [32] 18256 / 18288, conv_mean /
+ * conv_variance [16] 18320 / 18336, exp_mean / exp_variance [64] 18352 / 18416; 8 floats of padding.  grad_dev has the same
+ * layout.
+ *
+ * The ten entries mirror the tail2 ones one for one: argument order, meaning, statuses, the order of the checks, the -1 /
+ * SSAL_EINVAL limits and "every argument is judged before any device work" are theirs.  h, w of the features entries are the
+ * dims of Bottleneck3_8's output (eighth resolution).  features_dev / features_raw_dev [n,h,w,128] = Bottleneck3_8's output;
+ * argmax2_dev [n,h,w,64] = Bottleneck2_0's pooling indices (per-image index into [2h,2w,64]); argmax1_dev [n,2h,2w,16] =
+ * Bottleneck1_0's, as the tail takes them.  Bottleneck4_0 runs forward through the forward path's own kernel from weights
+ * folded on the device, so loss_dev is the forward op's value on ssal_enet_forward_nhwc's logits.  No float atomics: two calls
+ * give the same bits. */
+int64_t ssal_train_decoder_param_floats(int classes);
+int64_t ssal_train_decoder_grad_workspace_bytes(int n, int h, int w, int classes);
+int ssal_train_decoder_grad_nhwc(const float *features_dev, const int64_t *argmax2_dev, const int64_t *argmax1_dev, int n, int h,
+                                 int w, int classes, const float *params_dev, const uint8_t *labels_dev, const float *mask_dev,
+                                 float weight, float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev,
+                                 void *ws_dev, int64_t ws_bytes, void *stream);
+/* From images: the committed trunk's launchers up to Bottleneck3_8, then the chain with params_dev. */
+int64_t ssal_enet_train_decoder_workspace_bytes(const ssal_enet *net, int n, int h, int w);
+int ssal_enet_train_decoder_nhwc(ssal_enet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                                 const uint8_t *labels_dev, const float *mask_dev, const float *params_dev, float weight,
+                                 float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev, void *ws_dev,
+                                 int64_t ws_bytes, void *stream);
+/* Byte offset, into the workspace of ssal_enet_train_decoder_nhwc / ssal_enet_train_decoder_semi_nhwc, of Bottleneck3_8's
+ * output [n,h/8,w/8,128] (the features_dev of ssal_train_decoder_grad_nhwc) as those calls leave it; valid until the next call.
+ * -1 for dims the net does not take. */
+int64_t ssal_enet_train_decoder_features_offset(const ssal_enet *net, int n, int h, int w);
+int64_t ssal_train_decoder_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw);
+int ssal_train_decoder_grad_semi_nhwc(const float *features_dev, const int64_t *argmax2_dev, const int64_t *argmax1_dev,
+                                      const float *features_raw_dev, const int64_t *argmax2_raw_dev,
+                                      const int64_t *argmax1_raw_dev, int n, int h, int w, int classes,
+                                      const float *params_dev, const uint8_t *labels_dev, const float *mask_dev,
+                                      const uint8_t *labelled_dev, int measure, float threshold, float weight,
+                                      float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev,
+                                      int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes,
+                                      void *stream);
+int64_t ssal_enet_train_decoder_semi_workspace_bytes(const ssal_enet *net, int n, int h, int w, int with_raw);
+int ssal_enet_train_decoder_semi_nhwc(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h,
+                                      int w, const uint8_t *labels_dev, const float *mask_dev, const uint8_t *labelled_dev,
+                                      int measure, float threshold, const float *params_dev, float weight,
+                                      float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev,
+                                      int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes,
+                                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -234,6 +234,20 @@ PROTOTYPES = {
     "ssal_enet_train_tail2_semi_workspace_bytes": (_i64, [_vp, _i, _i, _i, _i]),
     "ssal_enet_train_tail2_semi_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _f, _f, _i, _vp,
                                              _vp, _vp, _vp, _vp, _i64, _vp]),
+    # ---- decoder training: Bottleneck4_0 + the two-block tail ----
+    "ssal_train_decoder_param_floats": (_i64, [_i]),
+    "ssal_train_decoder_grad_workspace_bytes": (_i64, [_i, _i, _i, _i]),
+    "ssal_train_decoder_grad_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _i64,
+                                          _vp]),
+    "ssal_enet_train_decoder_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
+    "ssal_enet_train_decoder_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_enet_train_decoder_features_offset": (_i64, [_vp, _i, _i, _i]),
+    "ssal_train_decoder_grad_semi_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
+    "ssal_train_decoder_grad_semi_nhwc": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _f,
+                                               _f, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_enet_train_decoder_semi_workspace_bytes": (_i64, [_vp, _i, _i, _i, _i]),
+    "ssal_enet_train_decoder_semi_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _f, _f, _i, _vp,
+                                               _vp, _vp, _vp, _vp, _i64, _vp]),
     # ---- measurement aids (include/ssal_enet.h) ----
     "ssal_profile_enable": (_i, [_i]),
     "ssal_profile_collect": (_i, [_c.c_char_p, _i64]),

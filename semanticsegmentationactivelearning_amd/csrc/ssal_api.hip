@@ -10,6 +10,7 @@
 #include "ssal_train_block.h"
 #include "ssal_train_stage.h"
 #include "ssal_train_tail.h"
+#include "ssal_train_decoder.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -2608,4 +2609,198 @@ SSAL_API int ssal_enet_train_tail2_semi_nhwc(ssal_enet *net, const void *x_dev, 
     const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
     const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev != nullptr};
     return enet_train_tail_entry(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, max_workgroups, a, &semi, 2);
+}
+
+// ---- decoder training: Bottleneck4_0 + the two-block tail.  One body, as for the other depths. ----
+// h, w = the dims of Bottleneck3_8's output (eighth resolution); own = the call brings no a4_0 / a4_1 / a5_0 / window-code
+// buffers of its own.  The tail's pieces on the quarter-resolution map first (an images entry's a4_2 is carved there, as section
+// 21 does), then Bottleneck4_0's.
+static TrainDecoderWs train_decoder_carve(Bump &b, int64_t n, int h, int w, int classes, bool own)
+{
+    TrainDecoderWs t;
+    t.tt = train_tail_carve(b, n, 2 * h, 2 * w, classes, own, 2);
+    t.dx40 = b.take<float>(n * 4 * h * w * 64);
+    t.dur = b.take<float>(n * h * w * 64);
+    t.dfold = b.take<float>(DF_FLOATS);
+    t.part_d = b.take<float>((int64_t)train_decoder_workgroups(h, w, 0) * TD_TRAINED);
+    t.bad2 = b.take<int>(1);
+    t.a40 = own ? b.take<float>(n * 4 * h * w * 64) : nullptr;
+    t.code2 = own ? b.take<uint8_t>(n * h * w * 64) : nullptr;
+    return t;
+}
+
+static int train_decoder_check(int n, int h, int w, int classes, int max_workgroups)
+{
+    if (classes < 2 || classes > 32) return fail(SSAL_EINVAL, "classes must be in [2,32] (got %d)", classes);
+    if (n <= 0 || h <= 0 || w <= 0) return fail(SSAL_EINVAL, "bad dims n=%d h=%d w=%d", n, h, w);
+    if (max_workgroups < 0) return fail(SSAL_EINVAL, "max_workgroups must be >= 0 (got %d)", max_workgroups);
+    if (!train_decoder_fits(h, w))
+        return fail(SSAL_EINVAL, "feature map %dx%d is beyond the decoder gradient kernels' limit", h, w);
+    return SSAL_OK;
+}
+
+static int64_t train_decoder_bytes(int n, int h, int w, int classes, bool own, bool semi, bool with_raw)
+{
+    if (!grad_dims_ok(n, h, w, classes, train_decoder_fits)) return -1;
+    Bump b(nullptr, 0);
+    train_decoder_carve(b, n, h, w, classes, own);
+    train_semi_carve(b, n, 64 * (int64_t)h * w, classes, semi, with_raw);
+    return b.off + 256;
+}
+
+static int64_t enet_train_decoder_bytes(const ssal_enet *net, int n, int h, int w, bool semi, bool with_raw)
+{
+    if (!net_dims_ok(net, n, h, w)) return -1;
+    return behind_trunk_bytes(net, n, h, w, train_decoder_bytes(n, h / 8, w / 8, net->classes, false, semi, with_raw));
+}
+
+// b, need, trunk and what x38_raw sets off: as for train_stage_run.  x38 / x38_raw [n,h,w,128]: Bottleneck3_8 of the training /
+// the undistorted frames with their pooling indices; an images entry has both in one buffer of the forward workspace, one after
+// the other, gives no indices (trunk leaves the window codes in code2 / code1) and has Bottleneck4_0 written to a40,
+// Bottleneck4_1 to a41 and Bottleneck5_0 to a5, where the forward leaves them.
+template <typename Trunk>
+static int train_decoder_run(Bump &b, int64_t need, Trunk trunk, const float *x38, const int64_t *argmax2, const int64_t *argmax1,
+                             const float *x38_raw, const int64_t *argmax2_raw, const int64_t *argmax1_raw, float *a40, float *a41,
+                             float *a5, uint8_t *code2, uint8_t *code1, int n, int h, int w, int classes, const float *params_dev,
+                             int max_workgroups, const CallArgs &a, const SemiArgs *semi)
+{
+    TrainDecoderWs t = train_decoder_carve(b, n, h, w, classes, a40 == nullptr);
+    const TrainSemiWs sw = train_semi_carve(b, n, 64 * (int64_t)h * w, classes, semi != nullptr, semi && semi->with_raw);
+    if (int rc = ws_check(need, b, a)) return rc;
+    if (a40) {  // an images entry: the five live in the forward workspace
+        t.a40 = a40;
+        t.code2 = code2;
+        t.tt.a41 = a41;
+        t.tt.ts.a5 = a5;
+        t.tt.ts.code = code1;
+    }
+    return with_confusion(sw.rep, classes, semi ? semi->confusion : nullptr, a.s, [&](unsigned long long *rep, int reps) -> int {
+        TrainBlockSemi sa = {};
+        if (semi) sa = train_semi_args(*semi, sw, rep, reps);
+        if (x38_raw) {
+            if (int rc = trunk(true)) return rc;
+            HIP_TRY(launch_train_decoder_targets(x38_raw, argmax2_raw, argmax1_raw, n, h, w, classes, params_dev, max_workgroups,
+                                                 t, sa, a.s));
+        }
+        if (int rc = trunk(false)) return rc;
+        HIP_TRY(launch_train_decoder_grad(x38, argmax2, argmax1, n, h, w, classes, params_dev, a.labels, a.mask, a.weight,
+                                          a.label_smoothing, max_workgroups, t, a.loss, a.grad, a.s, semi ? &sa : nullptr));
+        return SSAL_OK;
+    });
+}
+
+static int train_decoder_grad_entry(const float *features_dev, const int64_t *argmax2_dev, const int64_t *argmax1_dev,
+                                    const float *features_raw_dev, const int64_t *argmax2_raw_dev,
+                                    const int64_t *argmax1_raw_dev, int n, int h, int w, int classes, const float *params_dev,
+                                    int max_workgroups, const CallArgs &a, const SemiArgs *semi)
+{
+    if (int rc = train_decoder_check(n, h, w, classes, max_workgroups)) return rc;
+    if (int rc = args_check(features_dev && argmax2_dev && argmax1_dev && params_dev, a, semi)) return rc;
+    if ((features_raw_dev == nullptr) != (argmax2_raw_dev == nullptr) || (features_raw_dev == nullptr) != (argmax1_raw_dev == nullptr))
+        return fail(SSAL_EINVAL, "features_raw_dev, argmax2_raw_dev and argmax1_raw_dev are given together or not at all");
+    Bump b(a.ws, a.ws_bytes);
+    return train_decoder_run(b, train_decoder_bytes(n, h, w, classes, true, semi != nullptr, features_raw_dev != nullptr), no_trunk,
+                             features_dev, argmax2_dev, argmax1_dev, features_raw_dev, argmax2_raw_dev, argmax1_raw_dev, nullptr,
+                             nullptr, nullptr, nullptr, nullptr, n, h, w, classes, params_dev, max_workgroups, a, semi);
+}
+
+static int enet_train_decoder_entry(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h, int w,
+                                    const float *params_dev, int max_workgroups, const CallArgs &a, const SemiArgs *semi)
+{
+    int rc = check_dims(net, n, h, w);
+    if (rc) return rc;
+    if ((rc = train_decoder_check(n, h / 8, w / 8, net->classes, max_workgroups))) return rc;
+    if ((rc = args_check(x_dev && params_dev, a, semi))) return rc;
+    NetWorkspace W;
+    Bump b = carve_behind_trunk(net, a, n, h, w, &W);
+    // the frozen trunk is Initial .. Bottleneck3_8 (its output lands in W.s2a, the window codes of Bottleneck2_0's and
+    // Bottleneck1_0's pooling in W.code2 / W.code1); Bottleneck4_0 runs from params_dev into W.s1a, Bottleneck4_1 into W.s1b and
+    // Bottleneck5_0 into W.a0, where the forward leaves them
+    auto trunk = [&](bool of_raw) {
+        return run_trunk(net, kNumLayers - 6, of_raw ? x_raw_dev : x_dev, x_is_u8, W, n, h, w, a.s);
+    };
+    return train_decoder_run(b, enet_train_decoder_bytes(net, n, h, w, semi != nullptr, x_raw_dev != nullptr), trunk, W.s2a,
+                             nullptr, nullptr, x_raw_dev && semi->labelled ? W.s2a : nullptr, nullptr, nullptr, W.s1a, W.s1b, W.a0,
+                             W.code2, W.code1, n, h / 8, w / 8, net->classes, params_dev, max_workgroups, a, semi);
+}
+
+SSAL_API int64_t ssal_train_decoder_param_floats(int classes)
+{
+    return classes < 2 || classes > 32 ? -1 : train_decoder_floats(classes);
+}
+
+SSAL_API int64_t ssal_train_decoder_grad_workspace_bytes(int n, int h, int w, int classes)
+{
+    return train_decoder_bytes(n, h, w, classes, true, false, false);
+}
+
+SSAL_API int ssal_train_decoder_grad_nhwc(const float *features_dev, const int64_t *argmax2_dev, const int64_t *argmax1_dev, int n,
+                                          int h, int w, int classes, const float *params_dev, const uint8_t *labels_dev,
+                                          const float *mask_dev, float weight, float label_smoothing, int max_workgroups,
+                                          double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return train_decoder_grad_entry(features_dev, argmax2_dev, argmax1_dev, nullptr, nullptr, nullptr, n, h, w, classes,
+                                    params_dev, max_workgroups, a, nullptr);
+}
+
+SSAL_API int64_t ssal_enet_train_decoder_workspace_bytes(const ssal_enet *net, int n, int h, int w)
+{
+    return enet_train_decoder_bytes(net, n, h, w, false, false);
+}
+
+// byte offset (into the workspace passed to train_decoder) of Bottleneck3_8's output [n,h/8,w/8,128]: where
+// ssal_enet_train_decoder_nhwc and its semi form leave it (as a forward / score call does); valid until the next call.  -1 for
+// dims the net does not take.
+SSAL_API int64_t ssal_enet_train_decoder_features_offset(const ssal_enet *net, int n, int h, int w)
+{
+    if (!net_dims_ok(net, n, h, w)) return -1;
+    NetWorkspace W = carve(net, (void *)256, ((int64_t)1 << 62), n, h, w);
+    return (const char *)W.s2a - (const char *)256;
+}
+
+SSAL_API int ssal_enet_train_decoder_nhwc(ssal_enet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                                          const uint8_t *labels_dev, const float *mask_dev, const float *params_dev,
+                                          float weight, float label_smoothing, int max_workgroups, double *loss_dev,
+                                          float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return enet_train_decoder_entry(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, max_workgroups, a, nullptr);
+}
+
+SSAL_API int64_t ssal_train_decoder_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw)
+{
+    return train_decoder_bytes(n, h, w, classes, true, true, with_raw != 0);
+}
+
+SSAL_API int ssal_train_decoder_grad_semi_nhwc(const float *features_dev, const int64_t *argmax2_dev, const int64_t *argmax1_dev,
+                                               const float *features_raw_dev, const int64_t *argmax2_raw_dev,
+                                               const int64_t *argmax1_raw_dev, int n, int h, int w, int classes,
+                                               const float *params_dev, const uint8_t *labels_dev, const float *mask_dev,
+                                               const uint8_t *labelled_dev, int measure, float threshold, float weight,
+                                               float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev,
+                                               int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev,
+                                               int64_t ws_bytes, void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, features_raw_dev != nullptr};
+    return train_decoder_grad_entry(features_dev, argmax2_dev, argmax1_dev, features_raw_dev, argmax2_raw_dev, argmax1_raw_dev, n,
+                                    h, w, classes, params_dev, max_workgroups, a, &semi);
+}
+
+SSAL_API int64_t ssal_enet_train_decoder_semi_workspace_bytes(const ssal_enet *net, int n, int h, int w, int with_raw)
+{
+    return enet_train_decoder_bytes(net, n, h, w, true, with_raw != 0);
+}
+
+SSAL_API int ssal_enet_train_decoder_semi_nhwc(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
+                                               int h, int w, const uint8_t *labels_dev, const float *mask_dev,
+                                               const uint8_t *labelled_dev, int measure, float threshold,
+                                               const float *params_dev, float weight, float label_smoothing,
+                                               int max_workgroups, double *loss_dev, float *grad_dev, int64_t *confusion_dev,
+                                               int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev != nullptr};
+    return enet_train_decoder_entry(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, max_workgroups, a, &semi);
 }

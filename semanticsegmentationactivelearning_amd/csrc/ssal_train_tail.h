@@ -55,11 +55,13 @@ struct TrainTailWs {
 // x [N,H,W,64] = the input of the lowest trained block: Bottleneck4_1's output (R = 1) or Bottleneck4_0's (R = 2); argmax as
 // for launch_train_stage_grad; params / grad: the block of train_tail_floats(K, R) floats; labels uint8 / mask fp32 [N,4H,4W];
 // loss one double.  R = 2: Bottleneck4_1 and 4_2 forward, the stage, k_tt_block<true> on (a4_1, dx4) -> dx41, k_tt_block<false>
-// on (x, dx41), k_tt_finish per block.
+// on (x, dx41), k_tt_finish per block.  dx_low (may be NULL) [N,H,W,64]: the lowest block's launch is k_tt_block<true> too and
+// writes its input gradient dL/dx there, before the 1 / sum(mask) factor (what the decoder trainer goes on from,
+// ssal_train_decoder.h); it changes no bit of loss or grad.
 hipError_t launch_train_tail_grad(const float *x, const int64_t *argmax, int N, int H, int W, int K, const float *params,
                                   const uint8_t *labels, const float *mask, float weight, float label_smoothing,
                                   int max_workgroups, const TrainTailWs &ws, double *loss, float *grad, hipStream_t s,
-                                  const TrainBlockSemi *semi = nullptr, int R = 1);
+                                  const TrainBlockSemi *semi = nullptr, int R = 1, float *dx_low = nullptr);
 
 // The semi-supervised step with undistorted frames: Bottleneck4_2 of x41_raw through the scoring path's kernel into ws.a42,
 // then launch_train_stage_targets on it.  Uses ws.a42 and ws.tfold, which launch_train_tail_grad writes again afterwards.

@@ -454,7 +454,7 @@ static hipError_t tail_block_grad(const float *x, const float *g, int N, int H, 
 hipError_t launch_train_tail_grad(const float *x, const int64_t *argmax, int N, int H, int W, int K, const float *params,
                                   const uint8_t *labels, const float *mask, float weight, float label_smoothing,
                                   int max_workgroups, const TrainTailWs &ws, double *loss, float *grad, hipStream_t s,
-                                  const TrainBlockSemi *semi, int R)
+                                  const TrainBlockSemi *semi, int R, float *dx_low)
 {
     if (N < 1 || K < 2 || K > 32 || R < 1 || R > 2 || !train_tail_fits(H, W)) return hipErrorInvalidValue;
     const int G = train_stage_workgroups(H, W, max_workgroups);
@@ -471,10 +471,10 @@ hipError_t launch_train_tail_grad(const float *x, const int64_t *argmax, int N, 
     e = launch_train_stage_grad(ws.a42, argmax, N, H, W, K, params, labels, mask, weight, label_smoothing, max_workgroups, ws.ts,
                                 loss, grad, s, semi, ws.dx4);
     if (e != hipSuccess) return e;
-    e = tail_block_grad(x41, ws.dx4, N, H, W, G, PT, ws.tfold, ws.part_t, R == 2 ? ws.dx41 : nullptr, s);
+    e = tail_block_grad(x41, ws.dx4, N, H, W, G, PT, ws.tfold, ws.part_t, R == 2 ? ws.dx41 : dx_low, s);
     if (e != hipSuccess) return e;
     if (R == 2) {
-        e = tail_block_grad(x, ws.dx41, N, H, W, G, PT1, ws.tfold2, ws.part_t2, nullptr, s);
+        e = tail_block_grad(x, ws.dx41, N, H, W, G, PT1, ws.tfold2, ws.part_t2, dx_low, s);
         if (e != hipSuccess) return e;
     }
     for (int r = 0; r < R; ++r) {

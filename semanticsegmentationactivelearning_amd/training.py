@@ -996,6 +996,163 @@ class DeepTailTrainer(DecoderTailTrainer):
         return super().step_features(features4_0, argmax1, labels, mask, max_workgroups=max_workgroups, **semi_keywords)
 
 
+# ---- the decoder: Bottleneck4_0 + the deep tail --------------------------------------------------------
+# Bottleneck4_0's part of the packed block (include/ssal_enet.h, "Decoder training"), offsets from its start: the order of
+# Bottleneck5_0's part with the sizes of the 128 -> 32 -> 16 -> 64 upsampling block
+_DECODER = "Bottleneck4_0"
+_DECODER_LAYOUT = (
+    ("proj_kernel", 0, True), ("proj_gamma", 4096, False), ("proj_beta", 4128, False), ("proj_alpha", 4160, True),
+    ("conv_kernel", 4192, True), ("conv_gamma", 8800, False), ("conv_beta", 8816, False), ("conv_alpha", 8832, True),
+    ("exp_kernel", 8848, True), ("exp_gamma", 9872, False), ("exp_beta", 9936, False), ("res_kernel", 10000, True),
+    ("residual_alpha", 18192, True),
+)
+_DECODER_STATS = (("proj_mean", 18256), ("proj_variance", 18288), ("conv_mean", 18320), ("conv_variance", 18336),
+                  ("exp_mean", 18352), ("exp_variance", 18416))
+_DECODER_FLOATS = 18488
+_DECODER_ADAM_RANGES = ((0, 4096, True), (4096, 4160, False), (4160, 8800, True), (8800, 8832, False), (8832, 9872, True),
+                        (9872, 10000, False), (10000, 18256, True))
+
+
+class DecoderTrainer(DeepTailTrainer):
+    """Adam on 63 variables: the 50 of ``DeepTailTrainer``, then ``Bottleneck4_0``'s thirteen (``proj_kernel`` ..
+    ``residual_alpha``, 18 256 floats): the backward pass through the 128 -> 64 upsampling block that opens the decoder.  The
+    trained part is exactly ENet's decoder over a frozen encoder.
+
+    The deviation from the reference is ``LastBlockTrainer``'s: everything below Bottleneck4_0 is frozen and runs with
+    ``training=False``; the five trained blocks run in INFERENCE mode (constant moving statistics, never written; no spatial
+    dropout; batch-norm ``y = gamma (x - mean) / sqrt(var + 1e-3) + beta`` with ``gamma`` / ``beta`` trainable).  The unpool's
+    backward is the gather of the gradient at each element's pooling position; no gradient is produced for Bottleneck3_8's
+    output.
+
+    Regulariser: the Keras ``l1_l2`` gradient goes, next to ``DeepTailTrainer``'s set, to the variables of Bottleneck4_0 the
+    reference passes a regulariser to in ``BottleneckUpsample``: ``proj_kernel``, ``proj_alpha``, ``conv_kernel``,
+    ``conv_alpha``, ``exp_kernel``, ``res_kernel``, ``residual_alpha``; ``gamma`` / ``beta`` get the plain Adam update.
+
+    The inputs are Bottleneck3_8's output [N, h, w, 128], ``argmax2`` [N, h, w, 64] int64, the pooling indices of Bottleneck2_0
+    in the reference's per-image form ``(y * 2w + x) * 64 + c`` (``ENet.pooling_argmax()[1]``), and ``argmax1`` [N, 2h, 2w, 16]
+    as ``LastStageTrainer`` takes it (``features(images)`` returns the three)."""
+
+    _C_FEATURES = ("ssal_train_decoder_grad", "ssal_train_decoder_grad_semi")
+    _C_IMAGES = ("ssal_enet_train_decoder", "ssal_enet_train_decoder_semi")
+    _CHANNELS, _UP = 128, 8
+    _LOWEST = _DECODER
+
+    def _decoder_offset(self):
+        return self._deep_offset() + _TAIL_FLOATS
+
+    def _named(self):
+        """[(name, Variable, float offset, regularised)] of the trained variables: the deep tail's 50, then Bottleneck4_0's"""
+        base = super()._named()
+        blk, d0 = getattr(self.net, _DECODER), self._decoder_offset()
+        return base + [("%s.%s" % (_DECODER, a), getattr(blk, a), d0 + off, reg) for a, off, reg in _DECODER_LAYOUT]
+
+    def _floats(self):
+        return self._decoder_offset() + _DECODER_FLOATS
+
+    def _pack(self, arrays=None):
+        out = super()._pack(arrays)
+        if arrays is None:
+            blk, d0 = getattr(self.net, _DECODER), self._decoder_offset()
+            for a, off in _DECODER_STATS:
+                v = getattr(blk, a).numpy()
+                out[d0 + off:d0 + off + v.size] = v
+        return out
+
+    def _versions(self):
+        return super()._versions() + tuple(v.version for v in getattr(self.net, _DECODER).variables)
+
+    def _trained_tail(self):
+        return super()._trained_tail() + len(getattr(self.net, _DECODER).variables)
+
+    def _adam_ranges(self):
+        d0 = self._decoder_offset()
+        return super()._adam_ranges() + tuple((d0 + lo, d0 + hi, reg) for lo, hi, reg in _DECODER_ADAM_RANGES)
+
+    # ---- arguments, judged on the host ---------------------------------------------------------------------------------------
+    def _check_argmax2(self, feature_shape, argmax2):
+        """``argmax2`` as an int64 tensor after the checks ``argmax1`` gets: shape [N, h, w, 64], every index inside its own
+        2 x 2 window and channel.  A torch tensor that passed is remembered, so a cached one is checked once."""
+        import torch
+        a = argmax2 if isinstance(argmax2, torch.Tensor) else torch.as_tensor(np.asarray(argmax2))
+        shape = tuple(feature_shape)
+        if len(shape) != 4 or shape[-1] != 128:
+            raise ValueError("features must be [N,h,w,128] (got %s)" % (shape,))
+        want = shape[:3] + (64,)
+        if tuple(a.shape) != want:
+            raise ValueError("argmax2 must have shape %s (got %s)" % (want, tuple(a.shape)))
+        if a.dtype != torch.int64:
+            if a.dtype.is_floating_point or a.dtype == torch.bool:
+                raise ValueError("argmax2 must be an integer tensor (got %s)" % a.dtype)
+            a = a.to(torch.int64)
+        seen = getattr(self, "_argmax2_ok", None)
+        if not (seen is not None and seen[0] is argmax2 and seen[1] == argmax2._version):
+            _, h, w, _ = want
+            c = torch.arange(64, device=a.device).view(1, 1, 1, 64)
+            i = torch.arange(h, device=a.device).view(1, h, 1, 1)
+            j = torch.arange(w, device=a.device).view(1, 1, w, 1)
+            pix = torch.div(a, 64, rounding_mode="floor")
+            y, x = torch.div(pix, 2 * w, rounding_mode="floor"), pix % (2 * w)
+            ok = (a >= 0) & (a % 64 == c) & (torch.div(y, 2, rounding_mode="floor") == i) & \
+                 (torch.div(x, 2, rounding_mode="floor") == j)
+            if not bool(ok.all()):
+                raise ValueError("argmax2 holds %d indices outside their own 2x2 window / channel" % int((~ok).sum()))
+            self._argmax2_ok = (argmax2, argmax2._version) if isinstance(argmax2, torch.Tensor) else None
+        return a
+
+    def _check_inputs(self, inputs):
+        shape = tuple(np.shape(inputs[0]))
+        a2 = self._check_argmax2(shape, inputs[1])
+        return inputs[0], a2, self._check_argmax((shape[0], 2 * shape[1], 2 * shape[2], 64), inputs[2])
+
+    def _raw_host(self, inputs, raw):
+        if len({r is None for r in raw}) > 1:
+            raise ValueError("features_raw, argmax2_raw and argmax1_raw are given together or not at all (the undistorted "
+                             "frame's pooling indices are its own)")
+        return super()._raw_host(inputs, raw)
+
+    # ---- gradients and steps -------------------------------------------------------------------------------------------------
+    def gradient_features(self, features3_8, argmax2, argmax1, labels, mask, params=None, max_workgroups=0, labelled=None,
+                          measure=None, threshold=None, features_raw=None, argmax2_raw=None, argmax1_raw=None,
+                          confusion=None, return_pseudo_pixels=False):
+        """(loss float64 [1], {name: gradient}) on the device for Bottleneck3_8's output [N, h, w, 128], the pooling indices
+        ``argmax2`` [N, h, w, 64] and ``argmax1`` [N, 2h, 2w, 16], and labels / mask [N, 8h, 8w]; everything else as
+        ``LastStageTrainer.gradient_features`` (``features_raw`` / ``argmax2_raw`` / ``argmax1_raw`` of the semi-supervised
+        form are those of the undistorted frames)."""
+        semi = self._semi_call(features3_8, labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels,
+                               features_raw=features_raw, argmax2_raw=argmax2_raw, argmax1_raw=argmax1_raw)
+        extra = (self._check_workgroups(max_workgroups),)
+        return self._gradient((features3_8, argmax2, argmax1), (features_raw, argmax2_raw, argmax1_raw), labels, mask, params,
+                              semi, confusion, return_pseudo_pixels, extra)
+
+    def features(self, images):
+        """(Bottleneck3_8's output [N, H/8, W/8, 128] (a copy), argmax2 [N, H/8, W/8, 64], argmax1 [N, H/4, W/4, 16], both
+        int64) for ``images``: what ``step_features`` and ``gradient_features`` take.  One forward pass of the frozen encoder;
+        the frozen layers never change, so the result can be cached across steps."""
+        net = self.net
+        x = net._prepare(images, False)
+        n, h, w, _ = x.shape
+        net(x, training=False)
+        off = _lib.lib().ssal_enet_train_decoder_features_offset(net._handle, n, h, w)
+        if off < 0:
+            raise ValueError("bad input dims %s" % (tuple(x.shape),))
+        torch = _lib.require_gpu()
+        shape = (n, h // 8, w // 8, 128)
+        feats = net._ws[off:off + 4 * n * (h // 8) * (w // 8) * 128].view(torch.float32).view(shape).clone()
+        argmax1, argmax2 = net.pooling_argmax()
+        return feats, argmax2, argmax1
+
+    def step_features(self, features3_8, argmax2, argmax1, labels, mask, max_workgroups=0, labelled=None, measure=None,
+                      threshold=None, features_raw=None, argmax2_raw=None, argmax1_raw=None, confusion=None,
+                      return_pseudo_pixels=False):
+        """one Adam step from cached Bottleneck3_8 features and pooling indices (``features(images)``); returns the loss
+        (float64 device scalar) BEFORE the step"""
+        semi = self._semi_call(features3_8, labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels,
+                               features_raw=features_raw, argmax2_raw=argmax2_raw, argmax1_raw=argmax1_raw)
+        extra = (self._check_workgroups(max_workgroups),)
+        return self._step_from_features((features3_8, argmax2, argmax1), (features_raw, argmax2_raw, argmax1_raw), labels, mask,
+                                        semi, confusion, return_pseudo_pixels, extra)
+
+
 # ---- the semi-supervised step of the two deeper trainers (DESIGN.md section 19) ---------------------------------------------
 class _SemiKeywords:
     """The semi-supervised keywords of ``FinalLayerTrainer`` (``labelled``, ``measure``, ``threshold``, ``features_raw`` /
@@ -1038,5 +1195,13 @@ class SemiSupervisedDeepTailTrainer(_SemiKeywords, DeepTailTrainer):
     ``state`` / ``load_state`` are interchangeable with its."""
 
 
+class SemiSupervisedDecoderTrainer(_SemiKeywords, DecoderTrainer):
+    """``DecoderTrainer`` with the semi-supervised step built into the head kernel (see ``SemiSupervisedBlockTrainer``); the
+    undistorted frame's side of the feature entries is ``features_raw`` [N, h, w, 128] (Bottleneck3_8) with its own pooling
+    indices ``argmax2_raw`` and ``argmax1_raw``.  Loss and the gradients are bit-identical to ``DecoderTrainer`` on the composed
+    targets; ``state`` / ``load_state`` are interchangeable with its."""
+
+
 __all__ = ["FinalLayerTrainer", "LastBlockTrainer", "LastStageTrainer", "DecoderTailTrainer", "SemiSupervisedBlockTrainer",
-           "SemiSupervisedStageTrainer", "SemiSupervisedTailTrainer", "DeepTailTrainer", "SemiSupervisedDeepTailTrainer"]
+           "SemiSupervisedStageTrainer", "SemiSupervisedTailTrainer", "DeepTailTrainer", "SemiSupervisedDeepTailTrainer",
+           "DecoderTrainer", "SemiSupervisedDecoderTrainer"]
