@@ -79,6 +79,34 @@ int ssal_icnet_endpoint_info(const ssal_icnet *net, const char *name, int n, int
                              int64_t dims[4]);
 int ssal_icnet_endpoint_valid_after_score(const ssal_icnet *net, const char *name, int h, int w);
 
+/* ---- Output-layer training (the reference's -r/--reinitialize-output-layer slice, active_learning.py:905-909, 461-462,
+ * for ICNet: conv6_cls/Kernel [1,1,128,classes] and conv6_cls/Bias [classes] over a frozen trunk) ----
+ * The head travels PACKED: [128 * classes | classes] floats = the kernel (HWIO, i.e. [c][k]) followed by the bias; head_dev
+ * and grad_dev have that layout.  One call computes, for features sub12_sum [n,h,w,128] (1/8 resolution), labels uint8 and
+ * mask fp32 [n,8h,8w]: lq = conv6_cls(resize_bilinear(sub12_sum, 2x)) by the forward path's own launch, the full-resolution
+ * logits conv6_interp = resize_bilinear(lq, 4x) on the fly, masked_softmax_cross_entropy (tensortools/losses.py:3-74; weight =
+ * loginverse_scaling) -> loss_dev [1] float64, and dL/d(head) -> grad_dev (without the regulariser; ssal_adam_apply of
+ * include/ssal_enet.h adds it and applies the update).  max_workgroups: 0 = min(tiles, 1024), a tuning knob (>= 0).  No
+ * floating-point atomics: two calls give the same bits.  SSAL_EINVAL: classes outside [2,32], n < 1, max_workgroups < 0, a
+ * NULL pointer, a map beyond the kernel's limit (the _workspace_bytes query then returns -1); SSAL_ENOMEM: workspace too small. */
+int64_t ssal_icnet_head_grad_workspace_bytes(int n, int h, int w, int classes);
+int ssal_icnet_head_grad_nhwc(const float *sub12_dev, int n, int h, int w, int classes, const float *head_dev,
+                              const uint8_t *labels_dev, const float *mask_dev, float weight, float label_smoothing,
+                              int max_workgroups, double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes,
+                              void *stream);
+/* the same from frames x_dev [n,h,w,c_in] (fp32, or uint8 when x_is_u8 != 0): the frozen trunk up to sub12_sum on the
+ * caller's stream (the score path's fused launches), then the tail above; labels / mask [n,h,w].  The workspace holds the
+ * network's buffers: after the call the sub12_sum endpoint is the features and conv6_cls the logits of head_dev. */
+int64_t ssal_icnet_train_head_workspace_bytes(const ssal_icnet *net, int n, int h, int w);
+int ssal_icnet_train_head_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                               const uint8_t *labels_dev, const float *mask_dev, const float *head_dev, float weight,
+                               float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev, void *ws_dev,
+                               int64_t ws_bytes, void *stream);
+/* replaces conv6_cls.kernel [128 * classes] / conv6_cls.bias [classes] (host arrays) of a COMMITTED handle in place: only
+ * these two tensors are re-laid-out and uploaded (12 KB), the handle stays committed.  Synchronises the stream; as with
+ * ssal_icnet_commit no call may be in flight on the handle on another stream. */
+int ssal_icnet_update_head(ssal_icnet *net, const float *kernel_host, const float *bias_host, void *stream);
+
 /* Stand-alone fused convolution (the operator every ICNet layer is built from; also the per-block parity hook):
  * y = [relu]( BN(conv2d(x, kernel HWIO, strides s, dilations d, "SAME")) [+ res] ), BN given as mean / variance /
  * gamma / beta (all NULL: no batch-norm; bias_dev optional).  upsample2x != 0 runs the conv on

@@ -165,6 +165,12 @@ PROTOTYPES = {
     "ssal_pyramid_pooling": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i64, _vp]),
     "ssal_upscore_workspace_bytes": (_i64, [_i, _i, _i]),
     "ssal_upscore_logits_nhwc": (_i, [_vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    # ---- output-layer training of ICNet (include/ssal_icnet.h) ----
+    "ssal_icnet_head_grad_workspace_bytes": (_i64, [_i, _i, _i, _i]),
+    "ssal_icnet_head_grad_nhwc": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_icnet_train_head_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
+    "ssal_icnet_train_head_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_icnet_update_head": (_i, [_vp, _vp, _vp, _vp]),
     # ---- PNG decode (include/ssal_enet.h) ----
     "ssal_png_plan": (_i64, [_i64, _vp]),
     "ssal_png_decode_nhwc": (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),

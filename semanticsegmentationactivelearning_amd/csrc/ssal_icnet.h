@@ -32,6 +32,12 @@ struct IgemmArgs {
 #endif
 };
 
+// Position of channel k (0..31) inside a 32-channel chunk row, in LDS and in the re-laid-out kernel: every group of 8
+// is stored as [k0 k2 k4 k6 | k1 k3 k5 k7], so that ONE ds_read_b128 per lane half (h = 0: first quad, h = 1: second)
+// delivers, register by register, exactly the (k = 2s | k = 2s+1) lane-half pairs the MFMA steps s = 0..3 consume in
+// ascending k order -- no register re-pairing (v_permlane32_swap) between the read and the MFMA.
+__host__ __device__ constexpr int igemm_kpos(int k) { return (k & ~7) | ((k & 1) << 2) | ((k & 7) >> 1); }
+
 // kernel [KH][KW][Cin][Cout] (HWIO) -> [KH*KW][Cin/32][CoutP][32], CoutP = Cout rounded up to 32 (zero rows)
 size_t igemm_relayout_floats(int KH, int KW, int Cin, int Cout);
 void igemm_relayout(const float *w_hwio, int KH, int KW, int Cin, int Cout, float *out);

@@ -6,6 +6,7 @@
 #include "ssal_icnet.h"
 #include "ssal_internal.h"
 #include "ssal_prof.h"
+#include "ssal_train_icnet.h"
 
 #include <math.h>
 
@@ -240,8 +241,9 @@ struct Grp {
 // written != NULL: DRY run -- nothing is launched, the names of the activation buffers this schedule would write are
 // collected instead (ssal_icnet_endpoint_valid_after_score: the one place that knows which layer outputs a fused launch
 // swallows is the schedule itself)
+// head = false: the schedule ends at sub12_sum (the output-layer trainer runs conv6_cls on the weights it trains)
 hipError_t run_trunk(const ssal_icnet *net, std::vector<Grp> &grp, bool x_is_u8, int h, int w, bool fused,
-                     std::set<std::string> *written = nullptr)
+                     std::set<std::string> *written = nullptr, bool head = true)
 {
     const bool dry = written != nullptr;
 #define OUT(name) do { if (dry) written->insert(name); } while (0)
@@ -342,7 +344,8 @@ hipError_t run_trunk(const ssal_icnet *net, std::vector<Grp> &grp, bool x_is_u8,
         EACH(launch_conv_first(q.x, x_is_u8, q.n, h, w, net->c_in, 1, c.w, c.scale, c.shift, q.A("conv1_sub1"), q.s));
         EACH(run_conv(net, "conv2_sub1", q.A("conv1_sub1"), q.n, h / 2, w / 2, nullptr, true, false, q.A("conv2_sub1"), q.s));
     }
-    for (const char *nm_ : {"conv3_sub1", "conv3_1_sub2_proj", "sub24_sum", "conv3_sub1_proj", "sub12_sum", "conv6_cls"}) OUT(nm_);
+    for (const char *nm_ : {"conv3_sub1", "conv3_1_sub2_proj", "sub24_sum", "conv3_sub1_proj", "sub12_sum"}) OUT(nm_);
+    if (head) OUT("conv6_cls");
     EACH(run_conv(net, "conv3_sub1", q.A("conv2_sub1"), q.n, h / 4, w / 4, nullptr, true, false, q.A("conv3_sub1"), q.s));
     // ---- cascade feature fusion (section 4): the 2x interpolations are evaluated inside the dilated convs ----
     EACH(run_conv(net, "conv3_1_sub2_proj", q.A("conv3_1"), q.n, h / 16, w / 16, nullptr, false, false,
@@ -354,7 +357,7 @@ hipError_t run_trunk(const ssal_icnet *net, std::vector<Grp> &grp, bool x_is_u8,
     EACH(run_conv(net, "conv_sub2", q.A("sub24_sum"), q.n, h / 16, w / 16, q.A("conv3_sub1_proj"), true, true,
                   q.A("sub12_sum"), q.s));
     // sub12_sum_interp (2x) + conv6_cls (1x1, bias)
-    EACH(run_conv(net, "conv6_cls", q.A("sub12_sum"), q.n, h / 8, w / 8, nullptr, false, true, q.A("conv6_cls"), q.s));
+    if (head) EACH(run_conv(net, "conv6_cls", q.A("sub12_sum"), q.n, h / 8, w / 8, nullptr, false, true, q.A("conv6_cls"), q.s));
 #undef EACH
 #undef OUT
     return hipSuccess;
@@ -682,6 +685,121 @@ SSAL_API int ssal_icnet_endpoint_valid_after_score(const ssal_icnet *net, const 
     std::vector<Grp> none;
     (void)run_trunk(net, none, false, h, w, true, &written);
     return written.count(name) ? 1 : 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// output-layer training (kernels: ssal_train_icnet.hip)
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+// the buffers of one gradient call behind `b`; own_lq: the logits live here (the images entry keeps them in the network's
+// conv6_cls endpoint instead)
+IcnetHeadWs head_carve(Bump &b, int64_t n, int h8, int w8, int classes, bool own_lq)
+{
+    IcnetHeadWs t;
+    t.lq = own_lq ? b.take<float>(n * (2 * (int64_t)h8) * (2 * (int64_t)w8) * classes) : nullptr;
+    t.wt = b.take<float>(icnet_head_ws_floats_wt());
+    const int64_t G = IH_MAX_WG;  // (sized for the default grid: max_workgroups only lowers it)
+    t.part = b.take<float>(G * icnet_head_floats(classes));
+    t.lpart = b.take<double>(2 * G);
+    return t;
+}
+
+int head_check(int n, int h8, int w8, int classes, int max_workgroups)
+{
+    if (n <= 0) return fail(SSAL_EINVAL, "bad dims n=%d h=%d w=%d", n, h8, w8);
+    if (classes < 2 || classes > 32) return fail(SSAL_EINVAL, "classes must be in [2,32] (got %d)", classes);
+    if (max_workgroups < 0) return fail(SSAL_EINVAL, "max_workgroups must be >= 0 (got %d)", max_workgroups);
+    if (!icnet_head_fits(h8, w8) || (double)n * h8 * w8 > 1099511627776.0)
+        return fail(SSAL_EINVAL, "feature map %dx%d (n=%d) is beyond the head gradient kernel's limit", h8, w8, n);
+    return SSAL_OK;
+}
+
+}  // namespace
+
+SSAL_API int64_t ssal_icnet_head_grad_workspace_bytes(int n, int h, int w, int classes)
+{
+    if (n <= 0 || classes < 2 || classes > 32 || !icnet_head_fits(h, w) || (double)n * h * w > 1099511627776.0) return -1;
+    Bump b(nullptr, 0);
+    (void)head_carve(b, n, h, w, classes, true);
+    return b.off + 256;
+}
+
+SSAL_API int ssal_icnet_head_grad_nhwc(const float *sub12_dev, int n, int h, int w, int classes, const float *head_dev,
+                                       const uint8_t *labels_dev, const float *mask_dev, float weight,
+                                       float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev,
+                                       void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    int rc = head_check(n, h, w, classes, max_workgroups);
+    if (rc) return rc;
+    if (!sub12_dev || !head_dev || !labels_dev || !mask_dev || !loss_dev || !grad_dev || !ws_dev)
+        return fail(SSAL_EINVAL, "NULL device pointer");
+    Bump b(ws_dev, ws_bytes);
+    const IcnetHeadWs t = head_carve(b, n, h, w, classes, true);
+    if (!b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
+                           (long long)ssal_icnet_head_grad_workspace_bytes(n, h, w, classes), (long long)ws_bytes);
+    HIP_TRY(launch_icnet_head_grad(sub12_dev, n, h, w, classes, head_dev, labels_dev, mask_dev, weight, label_smoothing,
+                                   max_workgroups, t, loss_dev, grad_dev, (hipStream_t)stream));
+    return SSAL_OK;
+}
+
+SSAL_API int64_t ssal_icnet_train_head_workspace_bytes(const ssal_icnet *net, int n, int h, int w)
+{
+    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 32 || w % 32) return -1;
+    Bump b(nullptr, 0);
+    b.off = carve(net, nullptr, 0, n, h, w).bytes;
+    (void)head_carve(b, n, h / 8, w / 8, net->classes, false);
+    return b.off + 256;
+}
+
+SSAL_API int ssal_icnet_train_head_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                                        const uint8_t *labels_dev, const float *mask_dev, const float *head_dev,
+                                        float weight, float label_smoothing, int max_workgroups, double *loss_dev,
+                                        float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    int rc = check_dims(net, n, h, w);
+    if (rc) return rc;
+    if ((rc = head_check(n, h / 8, w / 8, net->classes, max_workgroups))) return rc;
+    if (!x_dev || !head_dev || !labels_dev || !mask_dev || !loss_dev || !grad_dev || !ws_dev)
+        return fail(SSAL_EINVAL, "NULL device pointer");
+    IcWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
+    Bump b(ws_dev, ws_bytes);
+    b.off = W.bytes;
+    IcnetHeadWs t = head_carve(b, n, h / 8, w / 8, net->classes, false);
+    if (!W.ok || !b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
+                                    (long long)ssal_icnet_train_head_workspace_bytes(net, n, h, w), (long long)ws_bytes);
+    t.lq = W.act.at("conv6_cls");  // the logits of the head being trained are this call's conv6_cls endpoint
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<Grp> one(1);
+    one[0] = {W, x_dev, n, s};
+    HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false));
+    HIP_TRY(launch_icnet_head_grad(W.act.at("sub12_sum"), n, h / 8, w / 8, net->classes, head_dev, labels_dev, mask_dev,
+                                   weight, label_smoothing, max_workgroups, t, loss_dev, grad_dev, s));
+    return SSAL_OK;
+}
+
+SSAL_API int ssal_icnet_update_head(ssal_icnet *net, const float *kernel_host, const float *bias_host, void *stream)
+{
+    if (!net || !kernel_host || !bias_host) return fail(SSAL_EINVAL, "NULL argument");
+    if (!net->committed) return fail(SSAL_ESTATE, "ssal_icnet_commit() has not been called");
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != net->device)
+        return fail(SSAL_ESTATE, "the handle was committed on device %d but the current device is %d (one handle per device)",
+                    net->device, dev);
+    const int K = net->classes;
+    HostTensor &tk = net->tensors[net->index.at("conv6_cls.kernel")], &tb = net->tensors[net->index.at("conv6_cls.bias")];
+    tk.data.assign(kernel_host, kernel_host + 128 * (size_t)K);
+    tb.data.assign(bias_host, bias_host + K);
+    std::vector<float> wt(igemm_relayout_floats(1, 1, 128, K)), sc, sh;
+    igemm_relayout(tk.data.data(), 1, 1, 128, K, wt.data());
+    fold_bn_padded(nullptr, nullptr, nullptr, nullptr, tb.data.data(), K, sc, sh);
+    const ConvDev &c = net->convs.at("conv6_cls");
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemcpyAsync(const_cast<float *>(c.w), wt.data(), wt.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(const_cast<float *>(c.scale), sc.data(), sc.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(const_cast<float *>(c.shift), sh.data(), sh.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));  // the staging vectors die at return
+    return SSAL_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -36,11 +36,7 @@ static inline int cdiv_i(long a, long b) { return (int)((a + b - 1) / b); }
 // that the quad a lane half reads is already the MFMA operand sequence in ascending k order.
 // ------------------------------------------------------------------------------------------------
 constexpr int IG_BM = 128, IG_LDK = 36;
-// Position of channel k (0..31) inside a 32-channel chunk row, in LDS and in the re-laid-out kernel: every group of 8
-// is stored as [k0 k2 k4 k6 | k1 k3 k5 k7], so that ONE ds_read_b128 per lane half (h = 0: first quad, h = 1: second)
-// delivers, register by register, exactly the (k = 2s | k = 2s+1) lane-half pairs the MFMA steps s = 0..3 consume in
-// ascending k order -- no register re-pairing (v_permlane32_swap) between the read and the MFMA.
-__host__ __device__ constexpr int igemm_kpos(int k) { return (k & ~7) | ((k & 1) << 2) | ((k & 7) >> 1); }
+// (igemm_kpos, the position of channel k inside a 32-channel chunk row: ssal_icnet.h)
 constexpr unsigned IG_OOB = 0xFFFFFFFFu;  // a byte offset no tensor reaches: raw buffer loads return 0, stores are dropped
 
 // Addressing: every tensor is reached through a raw buffer resource (base in SGPRs, range = tensor bytes) plus a

@@ -25,9 +25,7 @@ class FinalLayerTrainer:
 
     def __init__(self, net, learning_rate, beta1=0.9, beta2=0.999, epsilon=1e-8, l1=0.0, l2=0.0, loginverse_scaling=0.0,
                  label_smoothing=0.0, learning_rate_decay=0.0, decay_steps=None, measure="entropy", threshold=0.0):
-        from .models.enet.enet import ENet
-        if not isinstance(net, ENet):
-            raise NotImplementedError("output-layer training is implemented for ENet only (got %s)" % type(net).__name__)
+        self._check_model(net)
         if not (2 <= int(net.classes) <= 32):
             raise ValueError("classes must be in [2, 32] (got %d)" % net.classes)
         if learning_rate_decay > 0.0 and not decay_steps:
@@ -47,6 +45,13 @@ class FinalLayerTrainer:
         self._t = 0
         self._reset_beta_powers()  # AdamOptimizer's beta powers (fp32)
         self._m0 = self._v0 = None  # host copies of Adam's slots waiting for the device
+
+    @staticmethod
+    def _check_model(net):
+        """the model class the training kernels are written for (``ICNetHeadTrainer``: ICNet)"""
+        from .models.enet.enet import ENet
+        if not isinstance(net, ENet):
+            raise NotImplementedError("output-layer training is implemented for ENet only (got %s)" % type(net).__name__)
 
     @classmethod
     def from_params(cls, net, params, decay_steps=None):
@@ -1202,6 +1207,201 @@ class SemiSupervisedDecoderTrainer(_SemiKeywords, DecoderTrainer):
     targets; ``state`` / ``load_state`` are interchangeable with its."""
 
 
+# ---- ICNet's output layer: conv6_cls over a frozen trunk (DESIGN.md section 23) ------------------------------------------------
+_HEAD = "conv6_cls"
+_HEAD_NAMES = (_HEAD + ".kernel", _HEAD + ".bias")
+
+
+class ICNetHeadTrainer(FinalLayerTrainer):
+    """Adam on ``net.conv6_cls.kernel`` [1, 1, 128, K] and ``net.conv6_cls.bias`` [K] of an ``ICNet``: the reference's
+    ``-r/--reinitialize-output-layer`` slice (active_learning.py:905-909, 461-462) for the second model -- the only weights
+    whose shape depends on the class count.  The trunk is frozen and runs with ``training=False`` up to ``sub12_sum``
+    [N, H/8, W/8, 128]; the head is the fused 2x bilinear + 1x1 convolution + bias of the forward path (on the weights
+    being trained), the loss is ``masked_softmax_cross_entropy`` on its 4x bilinear up-sampling (``conv6_interp``), which is
+    evaluated inside the gradient kernel.  Hyper-parameters, Adam, the beta powers and the learning-rate decay are
+    ``FinalLayerTrainer``'s; the Keras ``l1_l2`` regulariser goes to the kernel, not to the bias.
+
+    The head travels packed as ``[128 K | K]`` floats (kernel, then bias); ``gradient_features`` returns and ``state`` /
+    ``load_state`` use ``{"conv6_cls.kernel": ..., "conv6_cls.bias": ...}``.  The semi-supervised keywords, ``softmax.multiscale``
+    and ``weight_reg.glorot_scaling`` are refused."""
+
+    _semi_keywords = False
+    _C_FEATURES = ("ssal_icnet_head_grad", None)
+    _C_IMAGES = ("ssal_icnet_train_head", None)
+    _CHANNELS, _UP = 128, 8
+
+    @staticmethod
+    def _check_model(net):
+        from .models.icnet.icnet import ICNet
+        if not isinstance(net, ICNet):
+            raise NotImplementedError("ICNetHeadTrainer trains ICNet's conv6_cls (got %s; ENet: FinalLayerTrainer)"
+                                      % type(net).__name__)
+
+    @classmethod
+    def from_params(cls, net, params, decay_steps=None):
+        hp = params.get("hyperparams", params)
+        if (hp.get("weight_reg", {}) or {}).get("glorot_scaling", False):
+            raise NotImplementedError("weight_reg.glorot_scaling: the per-kernel regulariser scaling is not implemented")
+        return super().from_params(net, params, decay_steps=decay_steps)
+
+    # ---- the packed head ---------------------------------------------------------------------------------------------------
+    def _vars(self):
+        if not self.net.built:
+            raise RuntimeError("build the model (call it once, or .build(input_shape)) before training")
+        layer = getattr(self.net, _HEAD)
+        return layer.kernel, layer.bias
+
+    variable_names = list(_HEAD_NAMES)
+
+    def _split(self):
+        return 128 * int(self.net.classes)
+
+    def _pack(self, arrays=None):
+        out = np.zeros(129 * int(self.net.classes), np.float32)
+        for name, var, lo in zip(_HEAD_NAMES, self._vars(), (0, self._split())):
+            a = var.numpy() if arrays is None else arrays[name]
+            a = np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a, dtype=np.float32)
+            if a.shape != tuple(var.shape):
+                raise ValueError("%s must have shape %s (got %s)" % (name, tuple(var.shape), a.shape))
+            out[lo:lo + a.size] = a.reshape(-1)
+        return out
+
+    def _unpack(self, packed):
+        k, s = int(self.net.classes), self._split()
+        return {_HEAD_NAMES[0]: packed[:s].reshape(1, 1, 128, k), _HEAD_NAMES[1]: packed[s:].reshape(k)}
+
+    # FinalLayerTrainer's hooks
+    def _kernel_var(self):
+        return self._vars()[0]
+
+    def _host_weights(self):
+        return self._pack()
+
+    def _zero_state(self):
+        return np.zeros(129 * int(self.net.classes), np.float32)
+
+    def _version_key(self):
+        return tuple(v.version for v in self._vars())
+
+    def _state_view(self, a):
+        return {n: np.array(v) for n, v in self._unpack(np.asarray(a)).items()}
+
+    def _trained_tail(self):
+        return 2  # conv6_cls is the last layer: kernel and bias close ``net.variables``
+
+    def _adam_ranges(self):
+        s = self._split()
+        return ((0, s, True), (s, s + int(self.net.classes), False))
+
+    def _write_back(self, host):
+        """the host variables take the new head; a handle that held the weights as they were below the head gets exactly
+        these two tensors (``ssal_icnet_update_head``), not the whole weight set"""
+        net, s = self.net, self._split()
+        kern, bias = self._vars()
+        before = tuple(v.version for v in net.variables)
+        kern.assign(host[:s].reshape(kern.shape))
+        bias.assign(host[s:])
+        torch = _lib.require_gpu()
+        device = self._dev["w"].device
+        with net._state_lock:
+            ent = net._handles.get(device.index)
+            if ent is not None and ent[1] is not None and ent[1][:-2] == before[:-2]:
+                k32, b32 = np.ascontiguousarray(host[:s], np.float32), np.ascontiguousarray(host[s:], np.float32)
+                with torch.cuda.device(device):
+                    _lib.check(_lib.lib().ssal_icnet_update_head(ent[0], k32.ctypes.data, b32.ctypes.data, _lib.stream_ptr()))
+                ent[1] = tuple(v.version for v in net.variables)
+
+    def reinitialize(self, seed=None):
+        """``sess.run`` of the output layer's initializers: glorot-uniform kernel drawn from ``seed``, zero bias (the layer's
+        defaults); the optimizer state is reset too"""
+        self._vars()[1].assign(np.zeros(int(self.net.classes), np.float32))
+        super().reinitialize(seed)
+
+    def load_state(self, state):
+        for key in ("m", "v"):
+            if not isinstance(state[key], dict) or set(state[key]) != set(_HEAD_NAMES):
+                raise ValueError("state[%r] must map %s to arrays" % (key, list(_HEAD_NAMES)))
+        self._set_state(self._pack(state["m"]), self._pack(state["v"]), state["t"])
+
+    # ---- arguments, judged on the host before any device work -----------------------------------------------------------------
+    @staticmethod
+    def _refuse_semi(**kw):
+        for name, value in kw.items():
+            if value is not None and value is not False:
+                raise NotImplementedError("%s: the semi-supervised step is not implemented for ICNet's output layer" % name)
+
+    def _check_call(self, batch, up, labels, mask, max_workgroups, channels):
+        if int(max_workgroups) < 0:
+            raise ValueError("max_workgroups must be >= 0 (got %r)" % (max_workgroups,))
+        shape = tuple(np.shape(batch))
+        if len(shape) != 4 or (channels is not None and shape[-1] != channels):
+            raise ValueError("expected a [N,h,w,%s] batch (got %s)" % (channels or "C", shape))
+        dt = str(getattr(batch, "dtype", ""))
+        if channels is not None and not ("float" in dt):
+            raise ValueError("sub12_sum must be a floating-point tensor (got %s)" % (dt or type(batch).__name__))
+        want = (shape[0], up * shape[1], up * shape[2])
+        for name, t in (("labels", labels), ("mask", mask)):
+            if tuple(np.shape(t)) != want:
+                raise ValueError("%s must have shape %s (got %s)" % (name, want, tuple(np.shape(t))))
+        dt = str(getattr(labels, "dtype", ""))
+        if "int" not in dt:
+            raise ValueError("labels must be an integer tensor (got %s)" % (dt or type(labels).__name__))
+        dt = str(getattr(mask, "dtype", ""))
+        if not ("float" in dt or "int" in dt or "bool" in dt):
+            raise ValueError("mask must be a numeric tensor (got %s)" % (dt or type(mask).__name__))
+        return int(max_workgroups)
+
+    def _packed_with(self, params):
+        params = dict(params or {})
+        unknown = set(params) - set(_HEAD_NAMES)
+        if unknown:
+            raise ValueError("unknown variables %s (the head is %s)" % (sorted(unknown), list(_HEAD_NAMES)))
+        packed = self._pack()
+        if params:
+            over = self._pack({n: params.get(n, v) for n, v in self._unpack(packed).items()})
+            packed = over
+        return packed
+
+    # ---- gradients and steps ---------------------------------------------------------------------------------------------
+    def gradient_features(self, sub12_sum, labels, mask, params=None, max_workgroups=0, labelled=None, confusion=None,
+                          return_pseudo_pixels=False):
+        """(loss float64 [1], {"conv6_cls.kernel": [1, 1, 128, K], "conv6_cls.bias": [K]}) on the device for ``sub12_sum``
+        [N, h, w, 128] and labels / mask [N, 8h, 8w].  ``params`` overrides either tensor of the head; ``max_workgroups``: 0 =
+        min(tiles, 1024), a tuning knob.  No update."""
+        self._refuse_semi(labelled=labelled, confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
+        mw = self._check_call(sub12_sum, 8, labels, mask, max_workgroups, 128)
+        packed = self._packed_with(params)
+        x = _lib.as_device_f32(sub12_sum)
+        head = _lib.require_gpu().from_numpy(packed).to(x.device)
+        loss, grad, _ = self._grad_call((x,), (None,), labels, mask, head, None, None, False, (mw,))
+        return loss, self._unpack(grad)
+
+    def features(self, images):
+        """``sub12_sum`` [N, H/8, W/8, 128] for ``images`` (a copy): what ``step_features`` and ``gradient_features`` take.
+        One forward pass of the frozen trunk; it never changes, so the result can be cached across steps."""
+        self.net(images, training=False)
+        return self.net.endpoint("sub12_sum").clone()
+
+    def step_features(self, sub12_sum, labels, mask, max_workgroups=0, labelled=None, confusion=None,
+                      return_pseudo_pixels=False):
+        """one Adam step from cached ``sub12_sum`` features; returns the loss (float64 device scalar) BEFORE the step, as
+        ``sess.run([loss, train_op])`` does"""
+        self._refuse_semi(labelled=labelled, confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
+        mw = self._check_call(sub12_sum, 8, labels, mask, max_workgroups, 128)
+        x = _lib.as_device_f32(sub12_sum)
+        dev = self._device_state(x.device)
+        loss, grad, _ = self._grad_call((x,), (None,), labels, mask, dev["w"], None, None, False, (mw,))
+        self._apply(dev, grad)
+        return loss[0]
+
+    def step(self, images, labels, mask, max_workgroups=0, labelled=None, confusion=None, return_pseudo_pixels=False):
+        """one Adam step from images [N, H, W, C] (fp32 or decoded uint8) and labels / mask [N, H, W]: the frozen trunk up
+        to ``sub12_sum``, the head and its gradient kernel, Adam.  Returns the loss (float64 device scalar) before the step."""
+        self._refuse_semi(labelled=labelled, confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
+        mw = self._check_call(images, 1, labels, mask, max_workgroups, None)
+        return self._step_images(images, None, labels, mask, None, None, False, (mw,))
+
+
 __all__ = ["FinalLayerTrainer", "LastBlockTrainer", "LastStageTrainer", "DecoderTailTrainer", "SemiSupervisedBlockTrainer",
            "SemiSupervisedStageTrainer", "SemiSupervisedTailTrainer", "DeepTailTrainer", "SemiSupervisedDeepTailTrainer",
-           "DecoderTrainer", "SemiSupervisedDecoderTrainer"]
+           "DecoderTrainer", "SemiSupervisedDecoderTrainer", "ICNetHeadTrainer"]
