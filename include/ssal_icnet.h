@@ -102,6 +102,35 @@ int ssal_icnet_train_head_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, 
                                const uint8_t *labels_dev, const float *mask_dev, const float *head_dev, float weight,
                                float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev, void *ws_dev,
                                int64_t ws_bytes, void *stream);
+/* ---- The semi-supervised step of the output-layer trainer (active_learning.py:226-275, 339-342) ----
+ * The two calls above with the targets built inside the gradient kernel; the argument order and every meaning are those of
+ * ssal_final_grad_semi_nhwc / ssal_enet_train_final_semi_nhwc (include/ssal_enet.h).  labelled_dev uint8 [n] (NULL = every
+ * image is labelled): image i with labelled_dev[i] == 0 is trained on its own pseudo annotation -- label = the first maximum
+ * of its full-resolution logits under head_dev, mask = (confidence >= threshold) for `measure` (0 entropy, 1 margin,
+ * 2 confidence; a NaN confidence gives 1) -- and its planes in labels_dev / mask_dev are never read; both may be NULL when
+ * no image is labelled (the caller's contract).  The targets are constants: loss and gradient are those of the plain call on
+ * the composed targets, bit for bit.  sub12_raw_dev / x_raw_dev (may be NULL): the features / frames of the undistorted
+ * images, which the pseudo annotation is then computed from by a target-only launch that leaves one packed byte per loss
+ * pixel; the training side goes through the same buffers afterwards (no second feature or logits slot; the images entry
+ * runs the trunk on x_raw_dev first, and only when labelled_dev is given).  confusion_dev int64 [classes, classes] (may be
+ * NULL) is ADDED the training-pass confusion matrix: (int)mask at [target label][first maximum of the training logits] for
+ * every loss pixel, keys >= classes^2 dropped.  pseudo_pixels_dev int64 [n] (may be NULL) is OVERWRITTEN with the count of
+ * pseudo-mask-1 pixels per image (0 for a labelled image).  Integer atomics only: two calls give the same bits.
+ * with_raw != 0 sizes the workspace for a call with a raw side: one byte per loss pixel more.
+ * Statuses as the plain entries', judged before any device work; an unknown measure: SSAL_ENOTIMPL. */
+int64_t ssal_icnet_head_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw);
+int ssal_icnet_head_grad_semi_nhwc(const float *sub12_dev, const float *sub12_raw_dev, int n, int h, int w, int classes,
+                                   const float *head_dev, const uint8_t *labels_dev, const float *mask_dev,
+                                   const uint8_t *labelled_dev, int measure, float threshold, float weight,
+                                   float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev,
+                                   int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes,
+                                   void *stream);
+int64_t ssal_icnet_train_head_semi_workspace_bytes(const ssal_icnet *net, int n, int h, int w, int with_raw);
+int ssal_icnet_train_head_semi_nhwc(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h,
+                                    int w, const uint8_t *labels_dev, const float *mask_dev, const uint8_t *labelled_dev,
+                                    int measure, float threshold, const float *head_dev, float weight, float label_smoothing,
+                                    int max_workgroups, double *loss_dev, float *grad_dev, int64_t *confusion_dev,
+                                    int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream);
 /* replaces conv6_cls.kernel [128 * classes] / conv6_cls.bias [classes] (host arrays) of a COMMITTED handle in place: only
  * these two tensors are re-laid-out and uploaded (12 KB), the handle stays committed.  Synchronises the stream; as with
  * ssal_icnet_commit no call may be in flight on the handle on another stream. */

@@ -170,6 +170,12 @@ PROTOTYPES = {
     "ssal_icnet_head_grad_nhwc": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _i64, _vp]),
     "ssal_icnet_train_head_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
     "ssal_icnet_train_head_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_icnet_head_grad_semi_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
+    "ssal_icnet_head_grad_semi_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _i, _vp, _vp, _vp,
+                                            _vp, _vp, _i64, _vp]),
+    "ssal_icnet_train_head_semi_workspace_bytes": (_i64, [_vp, _i, _i, _i, _i]),
+    "ssal_icnet_train_head_semi_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _f, _f, _i, _vp,
+                                             _vp, _vp, _vp, _vp, _i64, _vp]),
     "ssal_icnet_update_head": (_i, [_vp, _vp, _vp, _vp]),
     # ---- PNG decode (include/ssal_enet.h) ----
     "ssal_png_plan": (_i64, [_i64, _vp]),

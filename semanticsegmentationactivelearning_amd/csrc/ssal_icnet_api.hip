@@ -2,6 +2,7 @@
 // sequencing of ICNET_SPEC.md.  Host C++ only; no torch types.  gfx950 (MI355X) only.
 #include "../../include/ssal_enet.h"
 #include "../../include/ssal_icnet.h"
+#include "ssal_confusion.h"
 #include "ssal_host.h"
 #include "ssal_icnet.h"
 #include "ssal_internal.h"
@@ -776,6 +777,147 @@ SSAL_API int ssal_icnet_train_head_nhwc(ssal_icnet *net, const void *x_dev, int 
     HIP_TRY(launch_icnet_head_grad(W.act.at("sub12_sum"), n, h / 8, w / 8, net->classes, head_dev, labels_dev, mask_dev,
                                    weight, label_smoothing, max_workgroups, t, loss_dev, grad_dev, s));
     return SSAL_OK;
+}
+
+// ---- the semi-supervised step ----
+namespace {
+
+// what a semi call adds behind the plain pieces: the confusion replicas, then (with_raw) the packed pseudo-target plane of
+// the undistorted frames, one byte per loss pixel
+struct HeadSemiWs {
+    unsigned long long *rep;
+    uint8_t *tgt;
+};
+
+HeadSemiWs head_semi_carve(Bump &b, int64_t n, int h8, int w8, int classes, bool with_raw)
+{
+    HeadSemiWs t;
+    t.rep = b.take<unsigned long long>((int64_t)ssal::kConfMaxReps * ssal::conf_rep_stride(classes * classes));
+    t.tgt = with_raw ? b.take<uint8_t>(n * (8 * (int64_t)h8) * (8 * (int64_t)w8)) : nullptr;
+    return t;
+}
+
+// the arguments of a semi entry as ssal_final_grad_semi_nhwc judges them: the measure, then the pointers (`inputs`: the
+// entry's own features / frames / head, and-ed); the label and mask planes may be NULL when no image is labelled
+int head_semi_check(bool inputs, const uint8_t *labels, const float *mask, const uint8_t *labelled, int measure,
+                    const double *loss, const float *grad, const void *ws)
+{
+    if (measure < 0 || measure > 2) return fail(SSAL_ENOTIMPL, "Uncertainty function not implemented (measure=%d)", measure);
+    if (!labelled && (!labels || !mask))
+        return fail(SSAL_EINVAL, "labels_dev / mask_dev may be NULL only when labelled_dev marks no image as labelled");
+    if (!inputs || !loss || !grad || !ws) return fail(SSAL_EINVAL, "NULL device pointer");
+    return SSAL_OK;
+}
+
+// the training tail of a semi call: the replicas zeroed before and folded into the caller's matrix after the launches
+// (neither is issued without a matrix).  tgt: the plane the target launch wrote, or NULL
+int head_semi_tail(const float *sub12, int n, int h8, int w8, int classes, const float *head_dev, const uint8_t *labels_dev,
+                   const float *mask_dev, const uint8_t *labelled_dev, int measure, float threshold, float weight,
+                   float label_smoothing, int max_workgroups, const IcnetHeadWs &t, const HeadSemiWs &sw, const uint8_t *tgt,
+                   double *loss_dev, float *grad_dev, int64_t *confusion_dev, int64_t *pseudo_pixels_dev, hipStream_t s)
+{
+    const int reps = ssal::knobs().conf_reps;
+    if (confusion_dev) HIP_TRY(hipMemsetAsync(sw.rep, 0, (size_t)reps * ssal::conf_rep_stride(classes * classes) * 8, s));
+    const IcnetHeadSemi sa = {labelled_dev, measure, threshold, tgt, nullptr, confusion_dev ? sw.rep : nullptr, reps,
+                              (unsigned long long *)pseudo_pixels_dev};
+    HIP_TRY(launch_icnet_head_grad(sub12, n, h8, w8, classes, head_dev, labels_dev, mask_dev, weight, label_smoothing,
+                                   max_workgroups, t, loss_dev, grad_dev, s, &sa));
+    if (confusion_dev) HIP_TRY(launch_confusion_fold(sw.rep, reps, classes, confusion_dev, s));
+    return SSAL_OK;
+}
+
+}  // namespace
+
+SSAL_API int64_t ssal_icnet_head_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw)
+{
+    if (n <= 0 || classes < 2 || classes > 32 || !icnet_head_fits(h, w) || (double)n * h * w > 1099511627776.0) return -1;
+    Bump b(nullptr, 0);
+    (void)head_carve(b, n, h, w, classes, true);
+    (void)head_semi_carve(b, n, h, w, classes, with_raw != 0);
+    return b.off + 256;
+}
+
+SSAL_API int ssal_icnet_head_grad_semi_nhwc(const float *sub12_dev, const float *sub12_raw_dev, int n, int h, int w,
+                                            int classes, const float *head_dev, const uint8_t *labels_dev,
+                                            const float *mask_dev, const uint8_t *labelled_dev, int measure,
+                                            float threshold, float weight, float label_smoothing, int max_workgroups,
+                                            double *loss_dev, float *grad_dev, int64_t *confusion_dev,
+                                            int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    int rc = head_check(n, h, w, classes, max_workgroups);
+    if (rc) return rc;
+    if ((rc = head_semi_check(sub12_dev && head_dev, labels_dev, mask_dev, labelled_dev, measure, loss_dev, grad_dev, ws_dev)))
+        return rc;
+    Bump b(ws_dev, ws_bytes);
+    const IcnetHeadWs t = head_carve(b, n, h, w, classes, true);
+    const HeadSemiWs sw = head_semi_carve(b, n, h, w, classes, sub12_raw_dev != nullptr);
+    if (!b.ok)
+        return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
+                    (long long)ssal_icnet_head_grad_semi_workspace_bytes(n, h, w, classes, sub12_raw_dev != nullptr),
+                    (long long)ws_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    // the undistorted frame's features matter only where an image is unlabelled: head on sub12_raw into t.lq, the target
+    // launch; then the training features go through the same t.lq
+    const uint8_t *tgt = nullptr;
+    if (sub12_raw_dev && labelled_dev) {
+        const IcnetHeadSemi sa = {labelled_dev, measure, threshold, nullptr, nullptr, nullptr, 0, nullptr};
+        HIP_TRY(launch_icnet_head_targets(sub12_raw_dev, n, h, w, classes, head_dev, max_workgroups, t, sa, sw.tgt, s));
+        tgt = sw.tgt;
+    }
+    return head_semi_tail(sub12_dev, n, h, w, classes, head_dev, labels_dev, mask_dev, labelled_dev, measure, threshold, weight,
+                          label_smoothing, max_workgroups, t, sw, tgt, loss_dev, grad_dev, confusion_dev, pseudo_pixels_dev, s);
+}
+
+SSAL_API int64_t ssal_icnet_train_head_semi_workspace_bytes(const ssal_icnet *net, int n, int h, int w, int with_raw)
+{
+    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 32 || w % 32) return -1;
+    Bump b(nullptr, 0);
+    b.off = carve(net, nullptr, 0, n, h, w).bytes;
+    (void)head_carve(b, n, h / 8, w / 8, net->classes, false);
+    (void)head_semi_carve(b, n, h / 8, w / 8, net->classes, with_raw != 0);
+    return b.off + 256;
+}
+
+SSAL_API int ssal_icnet_train_head_semi_nhwc(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
+                                             int h, int w, const uint8_t *labels_dev, const float *mask_dev,
+                                             const uint8_t *labelled_dev, int measure, float threshold,
+                                             const float *head_dev, float weight, float label_smoothing, int max_workgroups,
+                                             double *loss_dev, float *grad_dev, int64_t *confusion_dev,
+                                             int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    int rc = check_dims(net, n, h, w);
+    if (rc) return rc;
+    if ((rc = head_check(n, h / 8, w / 8, net->classes, max_workgroups))) return rc;
+    if ((rc = head_semi_check(x_dev && head_dev, labels_dev, mask_dev, labelled_dev, measure, loss_dev, grad_dev, ws_dev)))
+        return rc;
+    IcWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
+    Bump b(ws_dev, ws_bytes);
+    b.off = W.bytes;
+    IcnetHeadWs t = head_carve(b, n, h / 8, w / 8, net->classes, false);
+    const HeadSemiWs sw = head_semi_carve(b, n, h / 8, w / 8, net->classes, x_raw_dev != nullptr);
+    if (!W.ok || !b.ok)
+        return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
+                    (long long)ssal_icnet_train_head_semi_workspace_bytes(net, n, h, w, x_raw_dev != nullptr),
+                    (long long)ws_bytes);
+    t.lq = W.act.at("conv6_cls");
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<Grp> one(1);
+    // the undistorted frames go through the trunk only where an image is unlabelled, and first: the target launch leaves one
+    // byte per loss pixel, so the training frames can go through the same slots afterwards
+    const uint8_t *tgt = nullptr;
+    if (x_raw_dev && labelled_dev) {
+        one[0] = {W, x_raw_dev, n, s};
+        HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false));
+        const IcnetHeadSemi sa = {labelled_dev, measure, threshold, nullptr, nullptr, nullptr, 0, nullptr};
+        HIP_TRY(launch_icnet_head_targets(W.act.at("sub12_sum"), n, h / 8, w / 8, net->classes, head_dev, max_workgroups, t, sa,
+                                          sw.tgt, s));
+        tgt = sw.tgt;
+    }
+    one[0] = {W, x_dev, n, s};
+    HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false));
+    return head_semi_tail(W.act.at("sub12_sum"), n, h / 8, w / 8, net->classes, head_dev, labels_dev, mask_dev, labelled_dev,
+                          measure, threshold, weight, label_smoothing, max_workgroups, t, sw, tgt, loss_dev, grad_dev,
+                          confusion_dev, pseudo_pixels_dev, s);
 }
 
 SSAL_API int ssal_icnet_update_head(ssal_icnet *net, const float *kernel_host, const float *bias_host, void *stream)

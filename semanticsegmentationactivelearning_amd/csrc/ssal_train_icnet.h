@@ -32,10 +32,32 @@ int64_t icnet_head_ws_floats_wt();  // 4 * 32 * 32 + 64
 // conv6_cls/Kernel + Bias (packed head on the device) -> wt / scale / shift as ssal_icnet_commit lays them out
 hipError_t launch_icnet_head_pack(const float *head, int K, float *wt, hipStream_t s);
 
+// The semi-supervised side of a gradient launch; the kernel's argument as it stands.
+struct IcnetHeadSemi {
+    const uint8_t *labelled;    // [N], NULL = all labelled
+    int measure;
+    float threshold;
+    const uint8_t *tgt_in;      // [N, 8 h8, 8 w8] packed pseudo targets of the undistorted frames (label in bits 0..6, mask in
+                                // bit 7; launch_icnet_head_targets wrote them), NULL = from the training logits
+    uint8_t *tgt_out;           // non-NULL: the target-only launch (set by launch_icnet_head_targets alone)
+    unsigned long long *rep;    // confusion replicas [reps][conf_rep_stride(K * K)], zeroed by the caller; NULL = no metrics
+    int reps;
+    unsigned long long *pseudo_pixels;  // [N] (zeroed by the launcher), NULL = not counted
+};
+
 // The whole tail: lq = conv6_cls(resize_2x(sub12_sum)) through launch_igemm (the forward path's own launch, reading the
 // packed head), then the fused loss + gradient kernel and the fold.  loss [1] float64; grad [128 K + K] fp32.
 hipError_t launch_icnet_head_grad(const float *sub12, int N, int h8, int w8, int K, const float *head,
                                   const uint8_t *labels, const float *mask, float weight, float label_smoothing,
-                                  int max_workgroups, const IcnetHeadWs &ws, double *loss, float *grad, hipStream_t s);
+                                  int max_workgroups, const IcnetHeadWs &ws, double *loss, float *grad, hipStream_t s,
+                                  const IcnetHeadSemi *semi = nullptr);
+
+// The target-only launch on the features of the undistorted frames: packs the head, lq = conv6_cls(resize_2x(sub12_raw))
+// into ws.lq, then one packed byte per loss pixel of the unlabelled images -> tgt [N, 8 h8, 8 w8].  Nothing else is
+// written, so the training features can go through the same ws.lq afterwards (launch_icnet_head_grad with semi.tgt_in = tgt,
+// which then does not pack the head again).  semi.labelled NULL: no launch but the pack.
+hipError_t launch_icnet_head_targets(const float *sub12_raw, int N, int h8, int w8, int K, const float *head,
+                                     int max_workgroups, const IcnetHeadWs &ws, const IcnetHeadSemi &semi, uint8_t *tgt,
+                                     hipStream_t s);
 
 }  // namespace ssal

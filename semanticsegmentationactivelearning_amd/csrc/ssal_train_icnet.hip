@@ -8,6 +8,12 @@
 //   k_icnet_head_finish  fixed-order fold of the partials, times 1 / sum(mask); the float64 loss
 // Semantics: ICNET_SPEC.md sections 4 and 6, tensortools/losses.py:3-74, active_learning.py:283-326 (DESIGN.md sections 15
 // and 23).  No floating-point atomics: two runs give the same bits.
+// The semi-supervised step (active_learning.py:226-275, 339-342) is k_icnet_head_grad<K, true>: the
+// targets of an unlabelled image are built from the logits the kernel holds, the training-pass confusion matrix and the
+// pseudo-pixel counts leave through integer atomics.
+#include <type_traits>
+
+#include "ssal_confusion.h"
 #include "ssal_icnet.h"
 #include "ssal_internal.h"
 #include "ssal_prof.h"
@@ -90,12 +96,26 @@ __device__ __forceinline__ float resize_weight(int dst, int src, int size, int f
 //   (4) the contraction: one thread per 4 x 4 (channel, class) block, dKernel[c][k] += sum_s x(s, c) hw(s, k), s row-major,
 //       accumulators in registers across all tiles and images of the workgroup; dBias[k] += sum_s hw(s, k) (the resize
 //       weights of a pixel sum to 1) in the threads of channel block 0.
-template <int K>
+//
+// SEMI: sa.labelled[n] == 0 replaces the label / mask of image n, which are then never read, by the
+// pseudo annotation of active_learning.py:229-275 -- (conf, lab) = pixel_score (ssal_score.h, the code of k_upscore) of the
+// interpolated logits the thread holds, mask = conf < threshold ? 0 : 1 (NaN -> 1).  The targets are constants
+// (tf.stop_gradient, :233): the loss, dL/dlogit, both gathers and the contraction do not change.  With sa.tgt_in the targets
+// of an unlabelled image come from that plane instead (a byte per loss pixel: the label in bits 0..6, the mask in bit 7),
+// which a TARGET-ONLY launch (sa.tgt_out, lq = the head's output on the undistorted frame's features) wrote: phase (1) and
+// the logits of phase (2) for the unlabelled images, nothing else -- no gradient, no partials, no sums.  sa.rep: every loss
+// pixel adds (int)mask at [label][first maximum of the TRAINING logits] of a u32 LDS histogram (ssal_confusion.h), flushed
+// into replica (workgroup % reps) at the end; a loss pixel belongs to exactly one tile.  sa.pseudo_pixels[n] += the image's
+// pixels with pseudo mask 1 (one integer atomic per wave, tile and unlabelled image).
+struct IcnetHeadPlain {};  // SEMI = false: no argument
+
+template <int K, bool SEMI>
 __global__ __launch_bounds__(256) void k_icnet_head_grad(const float *__restrict__ x, const float *__restrict__ lq, int N,
                                                          int h8, int w8, const uint8_t *__restrict__ labels,
                                                          const float *__restrict__ mask, float weight, float on_value,
                                                          float off_value, float *__restrict__ part,
-                                                         double *__restrict__ lpart)
+                                                         double *__restrict__ lpart,
+                                                         std::conditional_t<SEMI, IcnetHeadSemi, IcnetHeadPlain> sa)
 {
     constexpr int K4 = (K + 3) / 4 * 4, KB = K4 / 4;
     constexpr int KLD = K4 % 8 == 0 ? K4 + 4 : K4;  // row stride of the LDS planes: quads of neighbouring rows on other banks
@@ -105,6 +125,7 @@ __global__ __launch_bounds__(256) void k_icnet_head_grad(const float *__restrict
     __shared__ __attribute__((aligned(16))) float lqw[IH_WP * KLD];
     __shared__ __attribute__((aligned(16))) float gw[IH_WP * KLD];
     __shared__ __attribute__((aligned(16))) float big[BIG];
+    __shared__ unsigned hist[SEMI ? K * K : 1];  // (never referenced, so not allocated, without SEMI)
     float *gl = big;                  // (2): dL/dlogit of a band [256][KLD]
     float *xw = big;                  // (3), (4): the sub12_sum window [36][128] ...
     float *hw = big + IH_SP * 128;    // ... and the pull-back [36][KLD]
@@ -122,10 +143,22 @@ __global__ __launch_bounds__(256) void k_icnet_head_grad(const float *__restrict
     double loss = 0.0, msum = 0.0;
     float wc = 1.0f, dwc_cw = 0.0f;  // class weight constants (weight > 1): c_w = e - 1 - weight
     const float cw = kXentEuler - weight;
+    bool tgt_only = false;
+    if constexpr (SEMI) {
+        tgt_only = sa.tgt_out != nullptr;
+        if (sa.rep) hist_zero(hist, K * K);  // (ordered before the first add by the barriers of the first image)
+    }
     for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
         const int i0 = (t / tiles_x) * IH_T, j0 = (t % tiles_x) * IH_T;  // the tile's first pixel of lq
         float bsum[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // tf.reduce_sum(loss, axis=0) in fp32, per loss pixel of the thread
         for (int n = 0; n < N; ++n) {
+            // SEMI: image n is pseudo-annotated (workgroup-uniform)
+            bool pseudo = false;
+            int npseudo = 0;
+            if constexpr (SEMI) {
+                pseudo = sa.labelled && sa.labelled[n] == 0;
+                if (tgt_only && !pseudo) continue;  // a labelled image needs no pseudo targets
+            }
             __syncthreads();  // the previous contraction is done with xw / hw, the previous gather with gw
             for (int e = tid; e < IH_WP * KB; e += 256) {
                 const int wp = e / KB, kb = e % KB;
@@ -160,8 +193,39 @@ __global__ __launch_bounds__(256) void k_icnet_head_grad(const float *__restrict
                         xl[k] = top + (bot - top) * ly;
                     }
                     const long op = ((long)n * Ho + y) * Wo + xo;
-                    const int lab = labels[op];
-                    const float mk = mask[op];
+                    int lab;
+                    float mk;
+                    if constexpr (SEMI) {
+                        if (tgt_only) {
+                            const float conf = pixel_score<K>(xl, sa.measure, 1.0f / __logf((float)K), lab);
+                            sa.tgt_out[op] = (uint8_t)((unsigned)lab | (conf < sa.threshold ? 0u : 0x80u));
+                            continue;
+                        }
+                        if (pseudo) {
+                            if (sa.tgt_in) {
+                                const unsigned tb = sa.tgt_in[op];
+                                lab = (int)(tb & 0x7Fu);
+                                mk = (tb & 0x80u) ? 1.0f : 0.0f;
+                            } else {
+                                mk = pixel_score<K>(xl, sa.measure, 1.0f / __logf((float)K), lab) < sa.threshold ? 0.0f : 1.0f;
+                            }
+                            npseudo += mk != 0.0f;
+                        } else {
+                            lab = labels[op];
+                            mk = mask[op];
+                        }
+                        if (sa.rep) {  // train_pred = tf.math.argmax(train_logits): the first maximum
+                            float pm = xl[0];
+                            int pred = 0;
+#pragma unroll
+                            for (int k = 1; k < K; ++k)
+                                if (xl[k] > pm) { pm = xl[k]; pred = k; }
+                            hist_add_wave(hist, (unsigned)lab * K + (unsigned)pred, (unsigned)(int)mk, K * K);
+                        }
+                    } else {
+                        lab = labels[op];
+                        mk = mask[op];
+                    }
                     const XentPix r = xent_pixel<K>(xl, lab, mk, weight, on_value, off_value);
                     bsum[b] += r.ce;
                     msum += (double)mk;
@@ -186,6 +250,9 @@ __global__ __launch_bounds__(256) void k_icnet_head_grad(const float *__restrict
                 } else {
 #pragma unroll
                     for (int k = 0; k < K4; ++k) gq[k] = 0.0f;
+                }
+                if constexpr (SEMI) {
+                    if (tgt_only) continue;  // (workgroup-uniform: no barrier is skipped by a part of the workgroup)
                 }
                 __syncthreads();
                 if (tid < 3 * IH_TP * KB) {  // the band's pixels read the window rows 2b, 2b + 1, 2b + 2
@@ -214,6 +281,14 @@ __global__ __launch_bounds__(256) void k_icnet_head_grad(const float *__restrict
                     }
                 }
                 __syncthreads();  // gl is free for the next band (or for xw / hw), gw is complete up to this band
+            }
+            if constexpr (SEMI) {
+                if (tgt_only) continue;
+                if (pseudo && sa.pseudo_pixels) {
+#pragma unroll
+                    for (int off = 32; off > 0; off >>= 1) npseudo += __shfl_down(npseudo, off, 64);
+                    if ((tid & 63) == 0 && npseudo) atomicAdd(sa.pseudo_pixels + n, (unsigned long long)npseudo);
+                }
             }
             const int s0 = i0 >> 1, t0 = j0 >> 1;  // the window's first pixel of sub12_sum
             for (int e = tid; e < IH_SP * 32; e += 256) {
@@ -266,6 +341,9 @@ __global__ __launch_bounds__(256) void k_icnet_head_grad(const float *__restrict
 #pragma unroll
         for (int b = 0; b < 4; ++b) loss += (double)bsum[b];  // (0 where the thread's pixel lies outside the map)
     }
+    if constexpr (SEMI) {
+        if (tgt_only) return;
+    }
     float *pw = part + (long)blockIdx.x * (129 * K);
     if (tid < 32 * KB) {
 #pragma unroll
@@ -284,6 +362,12 @@ __global__ __launch_bounds__(256) void k_icnet_head_grad(const float *__restrict
     if (tid == 0) {
         lpart[2 * (long)blockIdx.x] = r0;
         lpart[2 * (long)blockIdx.x + 1] = r1;
+    }
+    if constexpr (SEMI) {
+        if (sa.rep) {
+            __syncthreads();
+            hist_flush(hist, K * K, sa.rep + (long)conf_rep_stride(K * K) * (blockIdx.x % sa.reps));
+        }
     }
 }
 
@@ -314,34 +398,111 @@ __global__ __launch_bounds__(256) void k_icnet_head_finish(const float *__restri
     }
 }
 
-hipError_t launch_icnet_head_grad(const float *sub12, int N, int h8, int w8, int K, const float *head,
-                                  const uint8_t *labels, const float *mask, float weight, float label_smoothing,
-                                  int max_workgroups, const IcnetHeadWs &ws, double *loss, float *grad, hipStream_t s)
+// the K switch of one launch of the template
+#define SSAL_IH_CASES                                                                                                  \
+    SSAL_IH(2) SSAL_IH(3) SSAL_IH(4) SSAL_IH(5) SSAL_IH(6) SSAL_IH(7) SSAL_IH(8) SSAL_IH(9) SSAL_IH(10) SSAL_IH(11)      \
+    SSAL_IH(12) SSAL_IH(13) SSAL_IH(14) SSAL_IH(15) SSAL_IH(16) SSAL_IH(17) SSAL_IH(18) SSAL_IH(19) SSAL_IH(20)         \
+    SSAL_IH(21) SSAL_IH(22) SSAL_IH(23) SSAL_IH(24) SSAL_IH(25) SSAL_IH(26) SSAL_IH(27) SSAL_IH(28) SSAL_IH(29)         \
+    SSAL_IH(30) SSAL_IH(31) SSAL_IH(32)
+
+static bool icnet_head_semi_ok(const IcnetHeadSemi *semi)
 {
-    if (N < 1 || K < 2 || K > 32 || max_workgroups < 0 || !icnet_head_fits(h8, w8)) return hipErrorInvalidValue;
-    const int G = icnet_head_workgroups(h8, w8, max_workgroups);
+    return !semi || (semi->measure >= 0 && semi->measure <= 2 && (!semi->rep || semi->reps >= 1));
+}
+
+// sub12_sum_interp (2x) + conv6_cls (1x1, bias) on the packed head in ws.wt: the launch of the forward path
+// (ssal_icnet_api.hip, run_trunk)
+static hipError_t launch_icnet_head_lq(const float *sub12, int N, int h8, int w8, int K, const IcnetHeadWs &ws, hipStream_t s)
+{
+    return launch_igemm(sub12, N, h8, w8, 128, ws.wt, 1, 1, K, 1, 1, ws.wt + 4096, ws.wt + 4096 + 32, nullptr, false, true,
+                        ws.lq, s);
+}
+
+hipError_t launch_icnet_head_targets(const float *sub12_raw, int N, int h8, int w8, int K, const float *head,
+                                     int max_workgroups, const IcnetHeadWs &ws, const IcnetHeadSemi &semi, uint8_t *tgt,
+                                     hipStream_t s)
+{
+    if (N < 1 || K < 2 || K > 32 || max_workgroups < 0 || !icnet_head_fits(h8, w8) || !icnet_head_semi_ok(&semi) || !tgt ||
+        !sub12_raw)
+        return hipErrorInvalidValue;
     hipError_t e = launch_icnet_head_pack(head, K, ws.wt, s);
     if (e != hipSuccess) return e;
-    // sub12_sum_interp (2x) + conv6_cls (1x1, bias): the launch of the forward path (ssal_icnet_api.hip, run_trunk)
-    e = launch_igemm(sub12, N, h8, w8, 128, ws.wt, 1, 1, K, 1, 1, ws.wt + 4096, ws.wt + 4096 + 32, nullptr, false, true,
-                     ws.lq, s);
+    if (!semi.labelled) return hipSuccess;  // every image is labelled: no pseudo target is read
+    const int G = icnet_head_workgroups(h8, w8, max_workgroups);
+    e = launch_icnet_head_lq(sub12_raw, N, h8, w8, K, ws, s);
+    if (e != hipSuccess) return e;
+    IcnetHeadSemi sa = semi;
+    sa.tgt_in = nullptr;
+    sa.tgt_out = tgt;
+    sa.rep = nullptr;
+    sa.pseudo_pixels = nullptr;
+    const double pix = (double)N * h8 * w8;
+    // the interpolation and the score of every loss pixel (counted for all images), one byte out
+    ProfScope prof("k_icnet_head_targets", 64.0 * pix * 12.0 * K, 4.0 * 4 * pix * K + 64.0 * pix, s);
+#define SSAL_IH(KK)                                                                                                    \
+    case KK:                                                                                                           \
+        hipLaunchKernelGGL((k_icnet_head_grad<KK, true>), dim3(G), dim3(256), 0, s, sub12_raw, ws.lq, N, h8, w8,        \
+                           nullptr, nullptr, 0.0f, 1.0f, 0.0f, ws.part, ws.lpart, sa);                                 \
+        break;
+    switch (K) {
+        SSAL_IH_CASES
+    default:
+        return hipErrorInvalidValue;
+    }
+#undef SSAL_IH
+    return hipGetLastError();
+}
+
+hipError_t launch_icnet_head_grad(const float *sub12, int N, int h8, int w8, int K, const float *head,
+                                  const uint8_t *labels, const float *mask, float weight, float label_smoothing,
+                                  int max_workgroups, const IcnetHeadWs &ws, double *loss, float *grad, hipStream_t s,
+                                  const IcnetHeadSemi *semi)
+{
+    if (N < 1 || K < 2 || K > 32 || max_workgroups < 0 || !icnet_head_fits(h8, w8) || !icnet_head_semi_ok(semi))
+        return hipErrorInvalidValue;
+    const int G = icnet_head_workgroups(h8, w8, max_workgroups);
+    hipError_t e;
+    if (semi && semi->pseudo_pixels) {
+        e = hipMemsetAsync(semi->pseudo_pixels, 0, (size_t)N * sizeof(int64_t), s);
+        if (e != hipSuccess) return e;
+    }
+    if (!(semi && semi->tgt_in)) {  // (the target launch before this one packed the same head into ws.wt)
+        e = launch_icnet_head_pack(head, K, ws.wt, s);
+        if (e != hipSuccess) return e;
+    }
+    e = launch_icnet_head_lq(sub12, N, h8, w8, K, ws, s);
     if (e != hipSuccess) return e;
     const float on_value = 1.0f - label_smoothing, off_value = label_smoothing / ((float)K - 1.0f);
     const double pix = (double)N * h8 * w8;
-    {
+    if (!semi) {
         ProfScope prof("k_icnet_head_grad", 64.0 * pix * 12.0 * K + 2.0 * pix * 128 * K,
                        4.0 * pix * 128 + 4.0 * 4 * pix * K + 64.0 * pix * (1 + 4) + 4.0 * G * 129.0 * K, s);
 #define SSAL_IH(KK)                                                                                                    \
     case KK:                                                                                                           \
-        hipLaunchKernelGGL((k_icnet_head_grad<KK>), dim3(G), dim3(256), 0, s, sub12, ws.lq, N, h8, w8, labels, mask,    \
-                           weight, on_value, off_value, ws.part, ws.lpart);                                            \
+        hipLaunchKernelGGL((k_icnet_head_grad<KK, false>), dim3(G), dim3(256), 0, s, sub12, ws.lq, N, h8, w8, labels,   \
+                           mask, weight, on_value, off_value, ws.part, ws.lpart, IcnetHeadPlain{});                    \
         break;
         switch (K) {
-            SSAL_IH(2) SSAL_IH(3) SSAL_IH(4) SSAL_IH(5) SSAL_IH(6) SSAL_IH(7) SSAL_IH(8) SSAL_IH(9)
-            SSAL_IH(10) SSAL_IH(11) SSAL_IH(12) SSAL_IH(13) SSAL_IH(14) SSAL_IH(15) SSAL_IH(16)
-            SSAL_IH(17) SSAL_IH(18) SSAL_IH(19) SSAL_IH(20) SSAL_IH(21) SSAL_IH(22) SSAL_IH(23)
-            SSAL_IH(24) SSAL_IH(25) SSAL_IH(26) SSAL_IH(27) SSAL_IH(28) SSAL_IH(29) SSAL_IH(30)
-            SSAL_IH(31) SSAL_IH(32)
+            SSAL_IH_CASES
+        default:
+            return hipErrorInvalidValue;
+        }
+#undef SSAL_IH
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    } else {
+        IcnetHeadSemi sa = *semi;
+        sa.tgt_out = nullptr;
+        if (!sa.labelled) sa.tgt_in = nullptr;
+        ProfScope prof("k_icnet_head_grad_semi", 64.0 * pix * 12.0 * K + 2.0 * pix * 128 * K,
+                       4.0 * pix * 128 + 4.0 * 4 * pix * K + 64.0 * pix * (1 + 4) + 4.0 * G * 129.0 * K, s);
+#define SSAL_IH(KK)                                                                                                    \
+    case KK:                                                                                                           \
+        hipLaunchKernelGGL((k_icnet_head_grad<KK, true>), dim3(G), dim3(256), 0, s, sub12, ws.lq, N, h8, w8, labels,    \
+                           mask, weight, on_value, off_value, ws.part, ws.lpart, sa);                                  \
+        break;
+        switch (K) {
+            SSAL_IH_CASES
         default:
             return hipErrorInvalidValue;
         }
@@ -355,5 +516,6 @@ hipError_t launch_icnet_head_grad(const float *sub12, int N, int h8, int w8, int
                        grad);
     return hipGetLastError();
 }
+#undef SSAL_IH_CASES
 
 }  // namespace ssal

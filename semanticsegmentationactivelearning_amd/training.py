@@ -1402,6 +1402,77 @@ class ICNetHeadTrainer(FinalLayerTrainer):
         return self._step_images(images, None, labels, mask, None, None, False, (mw,))
 
 
+# ---- the semi-supervised step of ICNet's output-layer trainer --------------------------------------------
+class SemiSupervisedICNetHeadTrainer(_SemiKeywords, ICNetHeadTrainer):
+    """``ICNetHeadTrainer`` with the reference's semi-supervised step (active_learning.py:226-275, 339-342) built into its
+    gradient kernel: ``gradient_features``, ``step_features`` and ``step`` accept ``labelled``, ``measure``, ``threshold``,
+    ``features_raw`` / ``images_raw``, ``confusion`` and ``return_pseudo_pixels`` with ``FinalLayerTrainer``'s meaning, defaults
+    and validation (the pseudo annotation is that of the full-resolution logits under the head being trained; with a raw
+    side, of the undistorted frames' logits).  Loss, dKernel and dBias are bit-identical to ``ICNetHeadTrainer`` on the
+    composed targets; with none of the keywords a call goes through the plain entry.  ``state`` /
+    ``load_state`` are interchangeable with ``ICNetHeadTrainer``'s."""
+
+    _C_FEATURES = ("ssal_icnet_head_grad", "ssal_icnet_head_grad_semi")
+    _C_IMAGES = ("ssal_icnet_train_head", "ssal_icnet_train_head_semi")
+
+    def _features_workspace_bytes(self, query, n, h, w, k, semi, with_raw):
+        """a semi call's workspace holds the packed target plane of the undistorted frames when there are any"""
+        return query(n, h, w, k, with_raw) if semi else query(n, h, w, k)
+
+    def _check_call(self, batch, up, labels, mask, max_workgroups, channels):
+        """``ICNetHeadTrainer``'s checks; the planes a semi call may leave out (``_semi`` has judged that) are not looked at"""
+        if labels is None or mask is None:
+            shape = tuple(np.shape(batch))
+            stand_in = np.zeros((shape[0], up * shape[1], up * shape[2]), np.uint8) if len(shape) == 4 else None
+            return super()._check_call(batch, up, stand_in, stand_in, max_workgroups, channels)
+        return super()._check_call(batch, up, labels, mask, max_workgroups, channels)
+
+    def _raw_features(self, x, semi, features_raw, features):
+        if semi is None or features_raw is None or features_raw is features:
+            return None
+        xr = _lib.as_device_f32(features_raw).to(x.device)
+        if tuple(xr.shape) != tuple(x.shape):
+            raise ValueError("features_raw must have the shape of sub12_sum %s (got %s)" % (tuple(x.shape), tuple(xr.shape)))
+        return xr
+
+    def gradient_features(self, sub12_sum, labels, mask, params=None, max_workgroups=0, labelled=None, measure=None,
+                          threshold=None, features_raw=None, confusion=None, return_pseudo_pixels=False):
+        """``ICNetHeadTrainer.gradient_features`` with the semi-supervised keywords of ``FinalLayerTrainer.gradient_features``:
+        ``labelled`` [N], ``measure`` / ``threshold`` (defaults: the trainer's), ``features_raw`` (``sub12_sum`` of the
+        undistorted frames), ``confusion`` (int64 [K, K] device tensor, added to), ``return_pseudo_pixels`` (appends the int64
+        [N] counts to the result)."""
+        semi = self._semi_call(sub12_sum, labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels)
+        mw = self._check_call(sub12_sum, 8, labels, mask, max_workgroups, 128)
+        packed = self._packed_with(params)
+        x = _lib.as_device_f32(sub12_sum)
+        xr = self._raw_features(x, semi, features_raw, sub12_sum)
+        head = _lib.require_gpu().from_numpy(packed).to(x.device)
+        loss, grad, pp = self._grad_call((x,), (xr,), labels, mask, head, semi, confusion, return_pseudo_pixels, (mw,))
+        return (loss, self._unpack(grad), pp) if return_pseudo_pixels else (loss, self._unpack(grad))
+
+    def step_features(self, sub12_sum, labels, mask, max_workgroups=0, labelled=None, measure=None, threshold=None,
+                      features_raw=None, confusion=None, return_pseudo_pixels=False):
+        """one Adam step from cached ``sub12_sum`` features; the keywords are those of ``gradient_features``; with
+        ``return_pseudo_pixels`` the result is ``(loss, pseudo_pixels)``"""
+        semi = self._semi_call(sub12_sum, labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels)
+        mw = self._check_call(sub12_sum, 8, labels, mask, max_workgroups, 128)
+        x = _lib.as_device_f32(sub12_sum)
+        xr = self._raw_features(x, semi, features_raw, sub12_sum)
+        dev = self._device_state(x.device)
+        loss, grad, pp = self._grad_call((x,), (xr,), labels, mask, dev["w"], semi, confusion, return_pseudo_pixels, (mw,))
+        self._apply(dev, grad)
+        return (loss[0], pp) if return_pseudo_pixels else loss[0]
+
+    def step(self, images, labels, mask, max_workgroups=0, labelled=None, measure=None, threshold=None, images_raw=None,
+             confusion=None, return_pseudo_pixels=False):
+        """one Adam step from images; ``images_raw``: the undistorted frames (same shape and dtype as ``images``) -- the trunk
+        runs on them first and the pseudo annotation comes from their logits (active_learning.py:231).  The other keywords
+        as in ``gradient_features``; with ``return_pseudo_pixels`` the result is ``(loss, pseudo_pixels)``."""
+        semi = self._semi_call(images, labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels)
+        mw = self._check_call(images, 1, labels, mask, max_workgroups, None)
+        return self._step_images(images, images_raw, labels, mask, semi, confusion, return_pseudo_pixels, (mw,))
+
+
 __all__ = ["FinalLayerTrainer", "LastBlockTrainer", "LastStageTrainer", "DecoderTailTrainer", "SemiSupervisedBlockTrainer",
            "SemiSupervisedStageTrainer", "SemiSupervisedTailTrainer", "DeepTailTrainer", "SemiSupervisedDeepTailTrainer",
-           "DecoderTrainer", "SemiSupervisedDecoderTrainer", "ICNetHeadTrainer"]
+           "DecoderTrainer", "SemiSupervisedDecoderTrainer", "ICNetHeadTrainer", "SemiSupervisedICNetHeadTrainer"]
