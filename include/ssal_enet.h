@@ -265,6 +265,28 @@ int ssal_conv2d_transpose_3x3_s2(const float *x_dev, int n, int h, int w, int ci
 int ssal_resize_bilinear(const float *x_dev, int n, int h, int w, int c, int oh, int ow,
                          float *y_dev, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Prediction (inference.py:95-109): what the test-split program writes per pixel, in one kernel.
+ *
+ * ssal_predict_logits_nhwc: logits_dev [n,h,w,classes] fp32 -> out_dev uint8.  Per output pixel the `classes` values of
+ * tf.image.resize_bilinear(logits, [oh,ow]) (ssal_resize_bilinear's mapping and expression, the same bits) are formed in
+ * registers and their first maximum is taken (the lowest class wins a tie, as the score entries do); the resized logits are
+ * never stored and there is no workspace.  oh == h && ow == w is a plain argmax.
+ *   lut_dev == NULL, lut_channels == 0: out_dev [n,oh,ow] = the train id
+ *   lut_channels == 1: lut_dev = 256 bytes,      out_dev [n,oh,ow]   = lut[id]        (reverse embedding, :101-106)
+ *   lut_channels == 3: lut_dev = 256 x 3 bytes,  out_dev [n,oh,ow,3] = lut[id][0..2]  (colour map, :107-109)
+ * logits_dev needs 4-byte alignment only (16-byte loads are used when classes % 4 == 0 and it is 16-byte aligned; the
+ * result does not depend on it).  SSAL_EINVAL, judged before any device work: a NULL pointer, classes outside [2,32], a
+ * size <= 0, lut_channels outside {0,1,3} or at odds with lut_dev, and more output tiles (32 x 8 pixels) than one launch
+ * takes (n * ceil(oh / 8) * ceil(ow / 32) >= 2^31).
+ *
+ * ssal_label_lut: the table alone on a label plane label_dev uint8 [pixels] (the plane the fused score entries give):
+ * out_dev [pixels] or [pixels][3] as above; lut_channels == 0 copies.  Same statuses. */
+int ssal_predict_logits_nhwc(const float *logits_dev, int n, int h, int w, int classes, int oh, int ow,
+                             const uint8_t *lut_dev, int lut_channels, uint8_t *out_dev, void *stream);
+int ssal_label_lut(const uint8_t *label_dev, int64_t pixels, const uint8_t *lut_dev, int lut_channels,
+                   uint8_t *out_dev, void *stream);
+
 /* Synthetic Cityscapes-shaped frames for benchmarking/tests: frame f of the pool is a
  * pure function of (seed, f); out_dev [count,h,w,c] fp32 = uint8 pixel * (1/255)
  * (tensortools/input.py:289-290 convert_image_dtype).  Host twin: synthetic.synth_frames_u8(). */

@@ -132,6 +132,9 @@ PROTOTYPES = {
     "ssal_conv2d_same": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "ssal_conv2d_transpose_3x3_s2": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     "ssal_resize_bilinear": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    # ---- prediction (include/ssal_enet.h) ----
+    "ssal_predict_logits_nhwc": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "ssal_label_lut": (_i, [_vp, _i64, _vp, _i, _vp, _vp]),
     "ssal_synth_frames_nhwc": (_i, [_c.c_uint64, _i64, _i, _i, _i, _i, _vp, _vp]),
     "ssal_synth_frames_nhwc_u8": (_i, [_c.c_uint64, _i64, _i, _i, _i, _i, _vp, _vp]),
     "ssal_set_kernel_family": (_i, [_i]),

@@ -92,6 +92,15 @@ hipError_t launch_score_logits(const float *logits, int N, int H, int W, int K, 
                                float threshold, double *partial, uint8_t *label, uint8_t *mask,
                                float *conf, hipStream_t s);
 
+// test-split prediction (ssal_predict.hip): bilinear resize of the logits + first maximum + optional id / colour table in one
+// kernel, out uint8 [n,oh,ow] (ch 0 or 1) or [n,oh,ow,3] (ch 3); lut = 256 * ch bytes (NULL at ch 0).  64-bit offsets inside;
+// predict_fits states the one limit (a one-dimensional grid), the launcher returns hipErrorInvalidValue beyond it
+bool predict_fits(int n, int oh, int ow);
+hipError_t launch_resize_argmax(const float *logits, int n, int h, int w, int k, int oh, int ow, const uint8_t *lut, int ch,
+                                uint8_t *out, hipStream_t s);
+// the table alone on a label plane: out [pixels] (ch 0 or 1) or [pixels][3] (ch 3)
+hipError_t launch_label_lut(const uint8_t *label, int64_t pixels, const uint8_t *lut, int ch, uint8_t *out, hipStream_t s);
+
 // masked softmax cross-entropy forward (tensortools/losses.py:3-74); partial: 2 * xent_blocks doubles
 int xent_blocks(int H, int W);
 hipError_t launch_masked_xent(const float *logits, const uint8_t *labels, const float *mask, int N,

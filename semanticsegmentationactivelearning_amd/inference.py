@@ -5,6 +5,10 @@ reference resizes the LOGITS, :96-99; TF-1.13 legacy mapping) -> argmax (first m
 embedding trainId -> dataset id (:101-106) or colour map (:107-109) -> PNG (:110-119).
 Dataset tables (``embedding_reversed``, ``colormap``) are passed in by the caller (the reference's
 ``datasets`` package is out of scope).
+
+Two routes give the same bytes: the composed one (``predict_labels`` + ``reverse_embedding`` / ``colorize``: one
+stand-alone operator per step, the logits in HBM between them) and the fused one (``predict``: resize, argmax and table in
+one kernel, or the fused score kernel's label plane where there is no resize).
 """
 import os
 
@@ -50,25 +54,87 @@ def colorize(pred, colormap):
     return lut[pred.long()]
 
 
+def _table(values, classes, channels, name):
+    """a dataset table as the kernels take it: uint8 [256] (channels 1) or [256, 3], zero-padded on the host"""
+    t = np.asarray(values, dtype=np.uint8)
+    if t.ndim != (1 if channels == 1 else 2) or (channels == 3 and t.shape[1] != 3) or t.shape[0] > 256:
+        raise ValueError("%s must be a table of at most 256 %s (got shape %s)"
+                         % (name, "ids" if channels == 1 else "RGB rows", t.shape))
+    if t.shape[0] < classes:
+        raise ValueError("%s has %d entries, fewer than the network's %d classes" % (name, t.shape[0], classes))
+    full = np.zeros((256,) + t.shape[1:], np.uint8)
+    full[:t.shape[0]] = t
+    return full
+
+
+def predict(net, images, size=None, embedding_reversed=None, colormap=None, arithmetic="f32"):
+    """What ``run_inference`` writes for one batch, on the GPU: uint8 [N,OH,OW] (train ids, or dataset ids through
+    ``embedding_reversed``) or [N,OH,OW,3] (``colormap``).  With ``size`` the logits are resized, reduced to their first
+    maximum and mapped in one kernel (``ssal_predict_logits_nhwc``; the resized logits never reach HBM); without it the label
+    plane comes from the network's fused score kernel (no logits in HBM at all) and ``ssal_label_lut`` applies the table.
+    The bytes are those of ``predict_labels`` + ``reverse_embedding`` / ``colorize``.  ``arithmetic``: as ``ENet.__call__``."""
+    if embedding_reversed is not None and colormap is not None:
+        raise ValueError("give embedding_reversed or colormap, not both")
+    _lib.arithmetic_code(arithmetic)
+    channels = 3 if colormap is not None else 1 if embedding_reversed is not None else 0
+    table = None
+    if channels:
+        table = _table(colormap if channels == 3 else embedding_reversed, net.classes, channels,
+                       "colormap" if channels == 3 else "embedding_reversed")
+    kw = {} if arithmetic == "f32" else {"arithmetic": arithmetic}  # ICNet has the one arithmetic
+    torch = _lib.require_gpu()
+    L = _lib.lib()
+    if size is None:
+        _, extra = net.score(images, "confidence", return_label=True, **kw)
+        label = extra["label"]
+        if not channels:
+            return label
+        src, (n, oh, ow) = label, label.shape
+    else:
+        src = net(images, training=False, **kw)
+        n, h, w, k = src.shape
+        oh, ow = int(size[0]), int(size[1])
+    lut = torch.from_numpy(table).to(src.device) if channels else None
+    out = torch.empty((n, oh, ow, 3) if channels == 3 else (n, oh, ow), dtype=torch.uint8, device=src.device)
+    with torch.cuda.device(src.device):
+        if size is None:
+            _lib.check(L.ssal_label_lut(_lib.dev_ptr(src), n * oh * ow, _lib.dev_ptr(lut), channels, _lib.dev_ptr(out),
+                                        _lib.stream_ptr()))
+        else:
+            _lib.check(L.ssal_predict_logits_nhwc(_lib.dev_ptr(src), n, h, w, k, oh, ow, _lib.dev_ptr(lut), channels,
+                                                  _lib.dev_ptr(out), _lib.stream_ptr()))
+    return out
+
+
 def write_png(path, array):
     from PIL import Image
     Image.fromarray(np.ascontiguousarray(array)).save(path, format="PNG")
 
 
-def run_inference(net, batches, output_dir, embedding_reversed=None, colormap=None, size=None):
+def run_inference(net, batches, output_dir, embedding_reversed=None, colormap=None, size=None, fused=False):
     """``batches`` yields (images NHWC float32, file ids); writes ``<output_dir>/<id>.png`` per example
-    (reference :110-147) and returns the list of written paths."""
+    (reference :110-147) and returns the list of written paths.  ``fused=True`` takes ``predict`` (a colour map wins over
+    an id table, as on the composed route) and downloads each batch into one page-locked buffer kept across batches."""
     os.makedirs(output_dir, exist_ok=True)
     written = []
+    pinned = None
     for images, ids in batches:
-        pred = predict_labels(net, images, size)
-        if colormap is not None:
-            out = colorize(pred, colormap)
-        elif embedding_reversed is not None:
-            out = reverse_embedding(pred, embedding_reversed)
+        if fused:
+            dev_out = predict(net, images, size, None if colormap is not None else embedding_reversed, colormap)
+            if pinned is None or pinned.numel() < dev_out.numel():
+                pinned = _lib.require_gpu().empty(dev_out.numel(), dtype=dev_out.dtype).pin_memory()
+            host = pinned[:dev_out.numel()].view(dev_out.shape)
+            host.copy_(dev_out)  # synchronous: the PNG writer below reads the buffer, the next batch overwrites it
+            out = host.numpy()
         else:
-            out = pred
-        out = out.cpu().numpy()
+            pred = predict_labels(net, images, size)
+            if colormap is not None:
+                out = colorize(pred, colormap)
+            elif embedding_reversed is not None:
+                out = reverse_embedding(pred, embedding_reversed)
+            else:
+                out = pred
+            out = out.cpu().numpy()
         for k, fid in enumerate(ids):
             fid = fid.decode() if isinstance(fid, bytes) else str(fid)
             path = os.path.join(output_dir.rstrip("/"), fid + ".png")
