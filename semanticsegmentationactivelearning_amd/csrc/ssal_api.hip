@@ -1707,11 +1707,12 @@ SSAL_API int ssal_profile_collect(char *json_out, int64_t cap)
 }
 
 // ------------------------------------------------------------------------------------------------
-// Training of ENet's tail over a frozen trunk (include/ssal_enet.h, "Output-layer training" to "Decoder-tail training";
-// DESIGN.md sections 15-20).  Four depths -- the output layer, the last block, the last stage, the decoder tail -- each
-// entered from cached features or from images, plain or semi-supervised.  Every depth has ONE body (final_grad_run,
-// train_block_run, train_stage_run, train_tail_run) that takes the features and an optional SemiArgs; the public entries validate (dims,
-// then semi arguments, then NULL pointers, then the workspace size, all before any launch), carve the workspace and call it.
+// Training of ENet's tail over a frozen trunk (include/ssal_enet.h, "Output-layer training" to "Decoder training";
+// DESIGN.md sections 15-22).  Six depths -- the output layer, the last block, the last stage, the decoder tail, the deep tail,
+// the decoder -- each entered from cached features or from images, plain or semi-supervised.  Every depth has ONE body
+// (final_grad_run, train_block_run, train_stage_run, train_tail_run with R = 1 for the decoder tail and R = 2 for the deep
+// tail, train_decoder_run) that takes the features and an optional SemiArgs; the public entries validate (dims, then semi
+// arguments, then NULL pointers, then the workspace size, all before any launch), carve the workspace and call it.
 // ------------------------------------------------------------------------------------------------
 // what every entry is given besides its inputs and parameters: targets, the loss' knobs, outputs, workspace, stream
 struct CallArgs {

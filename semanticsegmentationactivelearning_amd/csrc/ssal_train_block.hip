@@ -19,6 +19,7 @@
 #include "ssal_prof.h"
 #include "ssal_score.h"
 #include "ssal_train_block.h"
+#include "ssal_train_common.h"
 #include "ssal_xent.h"
 #include <type_traits>
 
@@ -31,21 +32,6 @@ constexpr int TB_GW = TB_T + 1;  // dL/dlogit window: the tile plus one row belo
 constexpr int TB_AW = TB_T + 2;  // Bottleneck5_1 output window: one more row above and column to the left
 constexpr int TB_PW = TB_T + 4;  // projected window
 constexpr int TB_SEG = 86;       // pixels per third of the block contractions (3 x 86 >= 256)
-
-__device__ __forceinline__ float tb_prelu(float v, float a) { return v >= 0.0f ? v : a * v; }
-// d prelu / dv and the factor of d prelu / dalpha (TensorFlow's convention at 0: both 0)
-__device__ __forceinline__ float tb_dprelu(float v, float a) { return v > 0.0f ? 1.0f : (v < 0.0f ? a : 0.0f); }
-__device__ __forceinline__ float tb_neg(float v) { return v < 0.0f ? v : 0.0f; }
-
-// one term of a compensated (Kahan) fp32 sum in a fixed order: the folds over the 256 threads and over the up to 3072
-// partial rows would otherwise be the longest rounding chains of a gradient (the library builds without fast-math and with
-// -ffp-contract=off, so the compensation survives)
-__device__ __forceinline__ void tb_kahan(float &sum, float &comp, float v)
-{
-    const float y = v - comp, t = sum + y;
-    comp = (t - sum) - y;
-    sum = t;
-}
 
 // one pixel of x5 [H,W,16] with clamped coordinates; ok = inside the image
 __device__ __forceinline__ bool tb_load16(const float *__restrict__ x5, int H, int W, int gi, int gj, float (&v)[16])
@@ -82,10 +68,10 @@ __device__ __forceinline__ void tb_phase_p(const float *__restrict__ x5, int H, 
         const bool ok = tb_load16(x5, H, W, i0 - 2 + e / TB_PW, j0 - 2 + e % TB_PW, xv);
         tb_proj(xv, f, acc);
         float4 o;
-        o.x = ok ? tb_prelu(fmaf(acc[0], f[TB_PG + 0], f[TB_PB + 0]), f[TB_PA + 0]) : 0.0f;
-        o.y = ok ? tb_prelu(fmaf(acc[1], f[TB_PG + 1], f[TB_PB + 1]), f[TB_PA + 1]) : 0.0f;
-        o.z = ok ? tb_prelu(fmaf(acc[2], f[TB_PG + 2], f[TB_PB + 2]), f[TB_PA + 2]) : 0.0f;
-        o.w = ok ? tb_prelu(fmaf(acc[3], f[TB_PG + 3], f[TB_PB + 3]), f[TB_PA + 3]) : 0.0f;
+        o.x = ok ? prelu(fmaf(acc[0], f[TB_PG + 0], f[TB_PB + 0]), f[TB_PA + 0]) : 0.0f;
+        o.y = ok ? prelu(fmaf(acc[1], f[TB_PG + 1], f[TB_PB + 1]), f[TB_PA + 1]) : 0.0f;
+        o.z = ok ? prelu(fmaf(acc[2], f[TB_PG + 2], f[TB_PB + 2]), f[TB_PA + 2]) : 0.0f;
+        o.w = ok ? prelu(fmaf(acc[3], f[TB_PG + 3], f[TB_PB + 3]), f[TB_PA + 3]) : 0.0f;
         reinterpret_cast<float4 *>(p1)[e] = o;
     }
 }
@@ -115,7 +101,7 @@ __device__ __forceinline__ void tb_conv_exp(const float *p1, int pi, int pj, con
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         r.yc[k] = fmaf(r.accc[k], f[TB_CG + k], f[TB_CB + k]);
-        r.qv[k] = tb_prelu(r.yc[k], f[TB_CA + k]);
+        r.qv[k] = prelu(r.yc[k], f[TB_CA + k]);
     }
 #pragma unroll
     for (int co = 0; co < 16; ++co) {
@@ -244,7 +230,7 @@ __global__ __launch_bounds__(256) void k_tb_head(const float *__restrict__ x5, i
                 tb_conv_exp(p1, pi, pj, fold, xres, r);
                 float out[16];
 #pragma unroll
-                for (int co = 0; co < 16; ++co) out[co] = ok ? tb_prelu(r.u[co], fold[TB_RA + co]) : 0.0f;
+                for (int co = 0; co < 16; ++co) out[co] = ok ? prelu(r.u[co], fold[TB_RA + co]) : 0.0f;
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
                     reinterpret_cast<float4 *>(tile)[e * 4 + q] = make_float4(out[4 * q], out[4 * q + 1], out[4 * q + 2], out[4 * q + 3]);
@@ -524,11 +510,11 @@ __global__ __launch_bounds__(256) void k_tb_block(const float *__restrict__ x5, 
 #pragma unroll
                 for (int co = 0; co < 16; ++co) {
                     const float d = ok ? dv[co] : 0.0f;
-                    const float du = d * tb_dprelu(r.u[co], fold[TB_RA + co]);
+                    const float du = d * dprelu(r.u[co], fold[TB_RA + co]);
                     if (acc_own) {
                         el[co] += du * ((r.ev[co] - fold[TB_EM + co]) * fold[TB_EV + co]);
                         el[16 + co] += du;
-                        el[32 + co] += d * tb_neg(r.u[co]);
+                        el[32 + co] += d * neg(r.u[co]);
                     }
                     de[co] = du * fold[TB_EG + co];
                 }
@@ -539,11 +525,11 @@ __global__ __launch_bounds__(256) void k_tb_block(const float *__restrict__ x5, 
                 float da[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const float dyc = dq[k] * tb_dprelu(r.yc[k], fold[TB_CA + k]);
+                    const float dyc = dq[k] * dprelu(r.yc[k], fold[TB_CA + k]);
                     if (acc_own) {
                         el[48 + k] += dyc * ((r.accc[k] - fold[TB_CM + k]) * fold[TB_CV + k]);
                         el[52 + k] += dyc;
-                        el[56 + k] += dq[k] * tb_neg(r.yc[k]);
+                        el[56 + k] += dq[k] * neg(r.yc[k]);
                     }
                     da[k] = dyc * fold[TB_CG + k];
                 }
@@ -558,7 +544,7 @@ __global__ __launch_bounds__(256) void k_tb_block(const float *__restrict__ x5, 
                     if constexpr (DX) {  // dL/du of the pixel: lx is free until D writes x into it
 #pragma unroll
                         for (int co = 0; co < 16; ++co)
-                            lx[p * 16 + co] = (ok ? dv[co] : 0.0f) * tb_dprelu(r.u[co], fold[TB_RA + co]);
+                            lx[p * 16 + co] = (ok ? dv[co] : 0.0f) * dprelu(r.u[co], fold[TB_RA + co]);
                     }
                 }
             }
@@ -584,11 +570,11 @@ __global__ __launch_bounds__(256) void k_tb_block(const float *__restrict__ x5, 
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const float yp = fmaf(accp[k], fold[TB_PG + k], fold[TB_PB + k]);
-                    const float dyp = dp[k] * tb_dprelu(yp, fold[TB_PA + k]);
+                    const float dyp = dp[k] * dprelu(yp, fold[TB_PA + k]);
                     if (valid) {
                         el[60 + k] += dyp * ((accp[k] - fold[TB_PM + k]) * fold[TB_PV + k]);
                         el[64 + k] += dyp;
-                        el[68 + k] += dp[k] * tb_neg(yp);
+                        el[68 + k] += dp[k] * neg(yp);
                     }
                     dap[k] = valid ? dyp * fold[TB_PG + k] : 0.0f;
                 }
@@ -664,7 +650,7 @@ __global__ __launch_bounds__(256) void k_tb_block(const float *__restrict__ x5, 
         const int slot = tid < 16 ? tb_elem_slot(ch * 16 + tid) : -1;
         if (slot >= 0) {
             float sum = 0.0f, comp = 0.0f;
-            for (int p = 0; p < 256; ++p) tb_kahan(sum, comp, lx[tid * 256 + p]);
+            for (int p = 0; p < 256; ++p) kahan(sum, comp, lx[tid * 256 + p]);
             row0[slot] = sum;
         }
     }
@@ -693,9 +679,9 @@ __global__ __launch_bounds__(256) void k_tb_finish(const float *__restrict__ par
     if (o >= TB_FINAL + cf) return;
     float acc = 0.0f, comp = 0.0f;
     if (o >= TB_FINAL) {
-        for (int g = 0; g < G; ++g) tb_kahan(acc, comp, part_f[(long)g * cf + (o - TB_FINAL)]);
+        for (int g = 0; g < G; ++g) kahan(acc, comp, part_f[(long)g * cf + (o - TB_FINAL)]);
     } else if (o < TB_TRAINED) {
-        for (long g = 0; g < (long)G * TB_ROWS; ++g) tb_kahan(acc, comp, part_b[g * TB_TRAINED + o]);
+        for (long g = 0; g < (long)G * TB_ROWS; ++g) kahan(acc, comp, part_b[g * TB_TRAINED + o]);
     }
     // the statistics and the padding are 0 whatever the scale is (an all-zero mask makes it inf)
     grad[o] = (o >= TB_TRAINED && o < TB_FINAL) ? 0.0f : acc * scale;

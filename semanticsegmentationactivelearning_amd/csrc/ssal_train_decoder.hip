@@ -8,7 +8,8 @@
 //   k_td_block   Bottleneck4_0's forward again on the window a tile needs, and its backward: per-workgroup partials of twelve
 //                gradients (all but res_kernel), and dL/du gathered through the pooling indices -> dur
 //   k_td_res     res_kernel's gradient: the contraction of the block's input with dur, into the same partial rows
-//   k_td_finish  fixed-order compensated fold of the partials, times 1 / sum(mask)
+//   k_td_finish  (the profile's name of k_train_finish, ssal_train_common.h) fixed-order compensated fold of the partials,
+//                times 1 / sum(mask)
 // Semantics: enet_modules.py:1217-1292 in inference mode (moving statistics are constants, no dropout); PReLU and its
 // derivative at 0 as in ssal_train_block.hip.  The unpool's backward is the gather of dL/du at the position the window code
 // names.  Plain fmaf contractions (fp32 MFMA runs at the vector rate on this part, DESIGN.md section 6, and the fmaf form
@@ -16,6 +17,7 @@
 #include "ssal_internal.h"
 #include "ssal_prof.h"
 #include "ssal_score.h"
+#include "ssal_train_common.h"
 #include "ssal_train_decoder.h"
 
 namespace ssal {
@@ -38,16 +40,6 @@ static_assert(TD_CITEMS % 4 == 0 && 256 % 4 == 0, "the four lanes of a pixel are
 // packed block
 constexpr int LD_PA = DF_WS, LD_CA = LD_PA + 32, LD_RA = LD_CA + 16, LD_PM = LD_RA + 64, LD_CM = LD_PM + 32, LD_EM = LD_CM + 16;
 constexpr int LD_FLOATS = LD_EM + 64;
-
-__device__ __forceinline__ float td_prelu(float v, float a) { return v >= 0.0f ? v : a * v; }
-__device__ __forceinline__ float td_dprelu(float v, float a) { return v > 0.0f ? 1.0f : (v < 0.0f ? a : 0.0f); }
-__device__ __forceinline__ float td_neg(float v) { return v < 0.0f ? v : 0.0f; }
-__device__ __forceinline__ void td_kahan(float &sum, float &comp, float v)
-{
-    const float y = v - comp, t = sum + y;
-    comp = (t - sum) - y;
-    sum = t;
-}
 
 // offset, inside Bottleneck4_0's part of the packed block, of per-channel gradient number r of a thread whose channel
 // quarter is kq (k_td_block's el order: exp_gamma, exp_beta, residual_alpha of the quarter's 16 channels; conv_gamma,
@@ -210,7 +202,7 @@ __global__ __launch_bounds__(256) void k_td_block(const float *__restrict__ x, c
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
                     const int ch = 8 * wv + k;
-                    pv[k] = ok ? td_prelu(fmaf(ap[k], lk[DF_PS + ch], lk[DF_PT + ch]), lk[LD_PA + ch]) : 0.0f;
+                    pv[k] = ok ? prelu(fmaf(ap[k], lk[DF_PS + ch], lk[DF_PT + ch]), lk[LD_PA + ch]) : 0.0f;
                 }
                 reinterpret_cast<float4 *>(lp)[e * 8 + 2 * wv] = make_float4(pv[0], pv[1], pv[2], pv[3]);
                 reinterpret_cast<float4 *>(lp)[e * 8 + 2 * wv + 1] = make_float4(pv[4], pv[5], pv[6], pv[7]);
@@ -262,7 +254,7 @@ __global__ __launch_bounds__(256) void k_td_block(const float *__restrict__ x, c
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int ch = 4 * kq + k;
-                    qv[k] = td_prelu(fmaf(acc[k], lk[DF_CS + ch], lk[DF_CT + ch]), lk[LD_CA + ch]);
+                    qv[k] = prelu(fmaf(acc[k], lk[DF_CS + ch], lk[DF_CT + ch]), lk[LD_CA + ch]);
                 }
                 reinterpret_cast<float4 *>(lca)[it] = make_float4(acc[0], acc[1], acc[2], acc[3]);
                 reinterpret_cast<float4 *>(lq)[it] = make_float4(qv[0], qv[1], qv[2], qv[3]);
@@ -312,11 +304,11 @@ __global__ __launch_bounds__(256) void k_td_block(const float *__restrict__ x, c
                             const bool hit = ((cd >> (8 * c)) & 0xffu) == cls;
                             const float u = fmaf(ev[c], lk[DF_ES + co], lk[DF_ET + co]) + (hit ? rv[c] : 0.0f);
                             const float d = ok ? gv[c] : 0.0f;
-                            const float du = d * td_dprelu(u, lk[LD_RA + co]);
+                            const float du = d * dprelu(u, lk[LD_RA + co]);
                             if (acc_own) {
                                 el[lc] += du * ((ev[c] - lk[LD_EM + co]) * lk[DF_EI + co]);
                                 el[16 + lc] += du;
-                                el[32 + lc] += d * td_neg(u);
+                                el[32 + lc] += d * neg(u);
                                 if (hit) dup[lc] = du;
                             }
                             de[c] = du * lk[DF_ES + co];
@@ -347,11 +339,11 @@ __global__ __launch_bounds__(256) void k_td_block(const float *__restrict__ x, c
                         const int ch = 4 * kq + k;
                         const float dqk = kq == 0 ? dq[k] : (kq == 1 ? dq[4 + k] : (kq == 2 ? dq[8 + k] : dq[12 + k]));
                         const float yc = fmaf(accc[k], lk[DF_CS + ch], lk[DF_CT + ch]);
-                        const float dyc = dqk * td_dprelu(yc, lk[LD_CA + ch]);
+                        const float dyc = dqk * dprelu(yc, lk[LD_CA + ch]);
                         if (acc_own) {
                             el[48 + k] += dyc * ((accc[k] - lk[LD_CM + ch]) * lk[DF_CI + ch]);
                             el[52 + k] += dyc;
-                            el[56 + k] += dqk * td_neg(yc);
+                            el[56 + k] += dqk * neg(yc);
                         }
                         da[k] = dyc * lk[DF_CS + ch];
                     }
@@ -403,11 +395,11 @@ __global__ __launch_bounds__(256) void k_td_block(const float *__restrict__ x, c
                 for (int k = 0; k < 8; ++k) {
                     const int ch = 8 * kq + k;
                     const float yp = fmaf(accp[k], lk[DF_PS + ch], lk[DF_PT + ch]);
-                    const float dyp = dp[k] * td_dprelu(yp, lk[LD_PA + ch]);
+                    const float dyp = dp[k] * dprelu(yp, lk[LD_PA + ch]);
                     if (valid) {
                         el[60 + k] += dyp * ((accp[k] - lk[LD_PM + ch]) * lk[DF_PI + ch]);
                         el[68 + k] += dyp;
-                        el[76 + k] += dp[k] * td_neg(yp);
+                        el[76 + k] += dp[k] * neg(yp);
                     }
                     dap[k] = valid ? dyp * lk[DF_PS + ch] : 0.0f;
                 }
@@ -471,7 +463,7 @@ __global__ __launch_bounds__(256) void k_td_block(const float *__restrict__ x, c
         const int slot = tid < 64 ? td_elem_slot(ch * 16 + (tid >> 2), kq) : -1;
         if (slot >= 0) {
             float sum = 0.0f, comp = 0.0f;
-            for (int j = 0; j < 64; ++j) td_kahan(sum, comp, lde[(tid >> 2) * 256 + 4 * j + kq]);
+            for (int j = 0; j < 64; ++j) kahan(sum, comp, lde[(tid >> 2) * 256 + 4 * j + kq]);
             row[slot] = sum;
         }
     }
@@ -526,26 +518,6 @@ __global__ __launch_bounds__(256) void k_td_res(const float *__restrict__ x, con
     for (int j = 0; j < 32; ++j) row[j] = acc[j];
 }
 
-// grad[o] = (sum over the G partial rows, in row order, compensated fp32) * (float)(1 / (double)(float)sum(mask)), the scale of
-// k_tb_finish from the same Gl per-workgroup mask sums; the moving statistics and the padding get 0.
-__global__ __launch_bounds__(256) void k_td_finish(const float *__restrict__ part, const double *__restrict__ lpart, int G, int Gl,
-                                                   float *__restrict__ grad)
-{
-    __shared__ double red[4];
-    __shared__ float scale;
-    double b = 0.0;
-    for (int i = threadIdx.x; i < Gl; i += 256) b += lpart[2 * (long)i + 1];
-    const double rb = block_sum_256(b, red);
-    if (threadIdx.x == 0) scale = (float)(1.0 / (double)(float)rb);
-    __syncthreads();
-    const int o = blockIdx.x * 256 + threadIdx.x;
-    if (o >= TD_FLOATS) return;
-    float acc = 0.0f, comp = 0.0f;
-    if (o < TD_TRAINED)
-        for (long r = 0; r < G; ++r) td_kahan(acc, comp, part[r * TD_TRAINED + o]);
-    grad[o] = o < TD_TRAINED ? acc * scale : 0.0f;
-}
-
 // Bottleneck4_0's forward as the scoring path runs it, on the block's own weights: PD = its part of the packed block
 static hipError_t decoder_forward(const float *x38, const int64_t *argmax2, int N, int H, int W, const float *PD,
                                   const TrainDecoderWs &ws, hipStream_t s)
@@ -594,10 +566,8 @@ hipError_t launch_train_decoder_grad(const float *x38, const int64_t *argmax2, c
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    ProfScope prof("k_td_finish", (double)G * TD_TRAINED, 4.0 * G * TD_TRAINED + 16.0 * Gl, s);
-    hipLaunchKernelGGL(k_td_finish, dim3((TD_FLOATS + 255) / 256), dim3(256), 0, s, ws.part_d, ws.tt.ts.tb.lpart, G, Gl,
-                       grad + train_tail_floats(K, 2));
-    return hipGetLastError();
+    return launch_train_finish<TD_TRAINED, TD_FLOATS>("k_td_finish", ws.part_d, ws.tt.ts.tb.lpart, G, Gl,
+                                                      grad + train_tail_floats(K, 2), s);
 }
 
 hipError_t launch_train_decoder_targets(const float *x38_raw, const int64_t *argmax2_raw, const int64_t *argmax1_raw, int N,

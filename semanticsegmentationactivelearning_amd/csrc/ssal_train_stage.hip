@@ -7,13 +7,15 @@
 //   (last block) launch_train_block_grad on a5_0 (ssal_train_block.hip) with k_tb_block<true>, which also writes dL/d a5_0
 //   k_ts_block   Bottleneck5_0's forward again on the window a tile needs, and its backward: per-workgroup partials of the
 //                13 gradients
-//   k_ts_finish  fixed-order compensated fold of the partials, times 1 / sum(mask)
+//   k_ts_finish  (the profile's name of k_train_finish, ssal_train_common.h) fixed-order compensated fold of the partials,
+//                times 1 / sum(mask)
 // Semantics: enet_modules.py:1217-1292 in inference mode (moving statistics are constants, no dropout); PReLU and its
 // derivative at 0 as in ssal_train_block.hip.  The unpool's backward is the gather of dL/du at the position the window code
 // names.  No floating-point atomics: two runs give the same bits.
 #include "ssal_internal.h"
 #include "ssal_prof.h"
 #include "ssal_score.h"
+#include "ssal_train_common.h"
 #include "ssal_train_stage.h"
 
 namespace ssal {
@@ -29,16 +31,6 @@ constexpr int TS_RW = 9;   // residual / window-code window (quarter resolution)
 // out, then proj_alpha, conv_alpha, exp_kernel, residual_alpha and the six moving statistics from the packed block
 constexpr int LK_PA = TF_WS, LK_CA = LK_PA + 16, LK_WE = LK_CA + 8, LK_RA = LK_WE + 128, LK_PM = LK_RA + 16;
 constexpr int LK_FLOATS = LK_PM + (TS_FLOATS - 8 - TS_PM);
-
-__device__ __forceinline__ float ts_prelu(float v, float a) { return v >= 0.0f ? v : a * v; }
-__device__ __forceinline__ float ts_dprelu(float v, float a) { return v > 0.0f ? 1.0f : (v < 0.0f ? a : 0.0f); }
-__device__ __forceinline__ float ts_neg(float v) { return v < 0.0f ? v : 0.0f; }
-__device__ __forceinline__ void ts_kahan(float &sum, float &comp, float v)
-{
-    const float y = v - comp, t = sum + y;
-    comp = (t - sum) - y;
-    sum = t;
-}
 
 // offset, inside Bottleneck5_0's part of the stage block, of per-channel gradient number e of k_ts_block
 __device__ __forceinline__ int ts_elem_slot(int e)
@@ -190,7 +182,7 @@ __global__ __launch_bounds__(256) void k_ts_block(const float *__restrict__ x4, 
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int ch = 4 * wv + k;
-                    pv[k] = ok ? ts_prelu(fmaf(ap[k], lk[TF_PS + ch], lk[TF_PT + ch]), lk[LK_PA + ch]) : 0.0f;
+                    pv[k] = ok ? prelu(fmaf(ap[k], lk[TF_PS + ch], lk[TF_PT + ch]), lk[LK_PA + ch]) : 0.0f;
                 }
                 reinterpret_cast<float4 *>(lp)[e * 4 + wv] = make_float4(pv[0], pv[1], pv[2], pv[3]);
                 if (pi >= 1 && pj >= 1) {
@@ -244,7 +236,7 @@ __global__ __launch_bounds__(256) void k_ts_block(const float *__restrict__ x4, 
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
                     yc[k] = fmaf(cacc[k], lk[TF_CS + k], lk[TF_CT + k]);
-                    qv[k] = ts_prelu(yc[k], lk[LK_CA + k]);
+                    qv[k] = prelu(yc[k], lk[LK_CA + k]);
                 }
                 const int rq = (ci_ >> 1) * TS_RW + (cj >> 1);
                 const unsigned cls = (unsigned)((ci_ & 1) * 2 + (cj & 1));
@@ -269,11 +261,11 @@ __global__ __launch_bounds__(256) void k_ts_block(const float *__restrict__ x4, 
                         hit[c] = ((cd >> (8 * c)) & 0xffu) == cls;
                         const float u = fmaf(ev, lk[TF_ES + co], lk[TF_ET + co]) + (hit[c] ? rv[c] : 0.0f);
                         const float d = ok ? gv[c] : 0.0f;
-                        const float du = d * ts_dprelu(u, lk[LK_RA + co]);
+                        const float du = d * dprelu(u, lk[LK_RA + co]);
                         if (acc_own) {
                             el[co] += du * ((ev - lk[LK_PM + TS_EM - TS_PM + co]) * lk[TF_EI + co]);
                             el[16 + co] += du;
-                            el[32 + co] += d * ts_neg(u);
+                            el[32 + co] += d * neg(u);
                         }
                         duv[c] = du;
                         de[co] = du * lk[TF_ES + co];
@@ -292,11 +284,11 @@ __global__ __launch_bounds__(256) void k_ts_block(const float *__restrict__ x4, 
                 float da[8];
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
-                    const float dyc = dq[k] * ts_dprelu(yc[k], lk[LK_CA + k]);
+                    const float dyc = dq[k] * dprelu(yc[k], lk[LK_CA + k]);
                     if (acc_own) {
                         el[48 + k] += dyc * ((cacc[k] - lk[LK_PM + TS_CM - TS_PM + k]) * lk[TF_CI + k]);
                         el[56 + k] += dyc;
-                        el[64 + k] += dq[k] * ts_neg(yc[k]);
+                        el[64 + k] += dq[k] * neg(yc[k]);
                     }
                     da[k] = dyc * lk[TF_CS + k];
                 }
@@ -340,11 +332,11 @@ __global__ __launch_bounds__(256) void k_ts_block(const float *__restrict__ x4, 
                 for (int k = 0; k < 4; ++k) {
                     const int ch = 4 * dcg + k;
                     const float yp = fmaf(accp[k], lk[TF_PS + ch], lk[TF_PT + ch]);
-                    const float dyp = dp[k] * ts_dprelu(yp, lk[LK_PA + ch]);
+                    const float dyp = dp[k] * dprelu(yp, lk[LK_PA + ch]);
                     if (valid) {
                         elp[k] += dyp * ((accp[k] - lk[LK_PM + TS_PM - TS_PM + ch]) * lk[TF_PI + ch]);
                         elp[4 + k] += dyp;
-                        elp[8 + k] += dp[k] * ts_neg(yp);
+                        elp[8 + k] += dp[k] * neg(yp);
                     }
                     dap[k] = valid ? dyp * lk[TF_PS + ch] : 0.0f;
                 }
@@ -440,30 +432,10 @@ __global__ __launch_bounds__(256) void k_ts_block(const float *__restrict__ x4, 
         const int slot = tid < 16 ? ts_elem_slot(ch * 16 + tid) : -1;
         if (slot >= 0) {
             float sum = 0.0f, comp = 0.0f;
-            for (int p = 0; p < 256; ++p) ts_kahan(sum, comp, lde[tid * 256 + p]);
+            for (int p = 0; p < 256; ++p) kahan(sum, comp, lde[tid * 256 + p]);
             row[slot] = sum;
         }
     }
-}
-
-// grad[o] = (sum over the G partial rows, in row order, compensated fp32) * (float)(1 / (double)(float)sum(mask)), the scale of
-// k_tb_finish from the same per-workgroup mask sums; the moving statistics and the padding get 0.
-__global__ __launch_bounds__(256) void k_ts_finish(const float *__restrict__ part, const double *__restrict__ lpart, int G,
-                                                   float *__restrict__ grad)
-{
-    __shared__ double red[4];
-    __shared__ float scale;
-    double b = 0.0;
-    for (int i = threadIdx.x; i < G; i += 256) b += lpart[2 * (long)i + 1];
-    const double rb = block_sum_256(b, red);
-    if (threadIdx.x == 0) scale = (float)(1.0 / (double)(float)rb);
-    __syncthreads();
-    const int o = blockIdx.x * 256 + threadIdx.x;
-    if (o >= TS_FLOATS) return;
-    float acc = 0.0f, comp = 0.0f;
-    if (o < TS_TRAINED)
-        for (long r = 0; r < G; ++r) ts_kahan(acc, comp, part[r * TS_TRAINED + o]);
-    grad[o] = o < TS_TRAINED ? acc * scale : 0.0f;
 }
 
 hipError_t launch_train_stage_grad(const float *x4, const int64_t *argmax, int N, int H, int W, int K, const float *params,
@@ -501,10 +473,7 @@ hipError_t launch_train_stage_grad(const float *x4, const int64_t *argmax, int N
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    ProfScope prof("k_ts_finish", (double)G * TS_TRAINED, 4.0 * G * TS_TRAINED + 16.0 * G, s);
-    hipLaunchKernelGGL(k_ts_finish, dim3((TS_FLOATS + 255) / 256), dim3(256), 0, s, ws.part_s, ws.tb.lpart, G,
-                       grad + train_block_floats(K));
-    return hipGetLastError();
+    return launch_train_finish<TS_TRAINED, TS_FLOATS>("k_ts_finish", ws.part_s, ws.tb.lpart, G, G, grad + train_block_floats(K), s);
 }
 
 // The pseudo targets of the undistorted frames: their window codes and Bottleneck5_0 through the

@@ -8,7 +8,8 @@
 //   k_tt_block   the bottleneck's forward again on the window a tile needs, and its backward: per-workgroup partials of the
 //                12 gradients; <true> also writes the block's input gradient, which makes it a link of a chain: with
 //                R = 2 Bottleneck4_1 below Bottleneck4_2 is a second fold, forward and launch
-//   k_tt_finish  fixed-order compensated fold of the partials, times 1 / sum(mask)
+//   k_tt_finish  (the profile's name of k_train_finish, ssal_train_common.h) fixed-order compensated fold of the partials,
+//                times 1 / sum(mask)
 // Semantics: enet_modules.py:526-599 in inference mode (moving statistics are constants, no dropout); PReLU and its
 // derivative at 0 as in ssal_train_block.hip.  Nothing in the two kernels names the layer: they take the block's part of
 // the packed parameters, its input and its output gradient, so another regular 64-channel bottleneck is another launch.
@@ -16,6 +17,7 @@
 #include "ssal_internal.h"
 #include "ssal_prof.h"
 #include "ssal_score.h"
+#include "ssal_train_common.h"
 #include "ssal_train_tail.h"
 
 namespace ssal {
@@ -31,16 +33,6 @@ constexpr int TT_CITEMS = TT_CW * TT_CW * 4;  // (pixel of the convolution windo
 // proj_alpha, conv_alpha, residual_alpha and the three moving means from the packed block
 constexpr int LT_PA = TG_FLOATS, LT_CA = LT_PA + 16, LT_RA = LT_CA + 16, LT_PM = LT_RA + 64, LT_CM = LT_PM + 16, LT_EM = LT_CM + 16;
 constexpr int LT_FLOATS = LT_EM + 64;
-
-__device__ __forceinline__ float tt_prelu(float v, float a) { return v >= 0.0f ? v : a * v; }
-__device__ __forceinline__ float tt_dprelu(float v, float a) { return v > 0.0f ? 1.0f : (v < 0.0f ? a : 0.0f); }
-__device__ __forceinline__ float tt_neg(float v) { return v < 0.0f ? v : 0.0f; }
-__device__ __forceinline__ void tt_kahan(float &sum, float &comp, float v)
-{
-    const float y = v - comp, t = sum + y;
-    comp = (t - sum) - y;
-    sum = t;
-}
 
 // offset, inside the bottleneck's part of the packed block, of per-channel gradient number r of a thread whose channel
 // quarter is kq (k_tt_block's el order: exp_gamma, exp_beta, residual_alpha of the quarter's 16 channels; conv_gamma,
@@ -159,7 +151,7 @@ __global__ __launch_bounds__(256) void k_tt_block(const float *__restrict__ x, c
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int ch = 4 * wv + k;
-                    pv[k] = ok ? tt_prelu(fmaf(ap[k], lk[TG_PS + ch], lk[TG_PT + ch]), lk[LT_PA + ch]) : 0.0f;
+                    pv[k] = ok ? prelu(fmaf(ap[k], lk[TG_PS + ch], lk[TG_PT + ch]), lk[LT_PA + ch]) : 0.0f;
                 }
                 reinterpret_cast<float4 *>(lp)[e * 4 + wv] = make_float4(pv[0], pv[1], pv[2], pv[3]);
                 if (pi >= 2 && pi < 2 + TT_Q && pj >= 2 && pj < 2 + TT_Q)
@@ -194,7 +186,7 @@ __global__ __launch_bounds__(256) void k_tt_block(const float *__restrict__ x, c
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int ch = 4 * kq + k;
-                    qv[k] = tt_prelu(fmaf(acc[k], lk[TG_CS + ch], lk[TG_CT + ch]), lk[LT_CA + ch]);
+                    qv[k] = prelu(fmaf(acc[k], lk[TG_CS + ch], lk[TG_CT + ch]), lk[LT_CA + ch]);
                 }
                 reinterpret_cast<float4 *>(lca)[it] = make_float4(acc[0], acc[1], acc[2], acc[3]);
                 reinterpret_cast<float4 *>(lq)[it] = make_float4(qv[0], qv[1], qv[2], qv[3]);
@@ -237,11 +229,11 @@ __global__ __launch_bounds__(256) void k_tt_block(const float *__restrict__ x, c
                         const int lc = 4 * c4 + c, co = 16 * kq + lc;
                         const float u = fmaf(ev[c], lk[TG_ES + co], lk[TG_ET + co]) + xv[c];
                         const float d = ok ? gv[c] : 0.0f;
-                        const float du = d * tt_dprelu(u, lk[LT_RA + co]);
+                        const float du = d * dprelu(u, lk[LT_RA + co]);
                         if (acc_own) {
                             el[lc] += du * ((ev[c] - lk[LT_EM + co]) * lk[TG_EI + co]);
                             el[16 + lc] += du;
-                            el[32 + lc] += d * tt_neg(u);
+                            el[32 + lc] += d * neg(u);
                         }
                         de[c] = du * lk[TG_ES + co];
                         if constexpr (DX)
@@ -272,11 +264,11 @@ __global__ __launch_bounds__(256) void k_tt_block(const float *__restrict__ x, c
                     const int ch = 4 * kq + k;
                     const float dqk = kq == 0 ? dq[k] : (kq == 1 ? dq[4 + k] : (kq == 2 ? dq[8 + k] : dq[12 + k]));
                     const float yc = fmaf(accc[k], lk[TG_CS + ch], lk[TG_CT + ch]);
-                    const float dyc = dqk * tt_dprelu(yc, lk[LT_CA + ch]);
+                    const float dyc = dqk * dprelu(yc, lk[LT_CA + ch]);
                     if (acc_own) {
                         el[48 + k] += dyc * ((accc[k] - lk[LT_CM + ch]) * lk[TG_CI + ch]);
                         el[52 + k] += dyc;
-                        el[56 + k] += dqk * tt_neg(yc);
+                        el[56 + k] += dqk * neg(yc);
                     }
                     da[k] = dyc * lk[TG_CS + ch];
                 }
@@ -312,11 +304,11 @@ __global__ __launch_bounds__(256) void k_tt_block(const float *__restrict__ x, c
                 for (int k = 0; k < 4; ++k) {
                     const int ch = 4 * kq + k;
                     const float yp = fmaf(accp[k], lk[TG_PS + ch], lk[TG_PT + ch]);
-                    const float dyp = dp[k] * tt_dprelu(yp, lk[LT_PA + ch]);
+                    const float dyp = dp[k] * dprelu(yp, lk[LT_PA + ch]);
                     if (valid) {
                         el[60 + k] += dyp * ((accp[k] - lk[LT_PM + ch]) * lk[TG_PI + ch]);
                         el[64 + k] += dyp;
-                        el[68 + k] += dp[k] * tt_neg(yp);
+                        el[68 + k] += dp[k] * neg(yp);
                     }
                     dap[k] = valid ? dyp * lk[TG_PS + ch] : 0.0f;
                 }
@@ -396,30 +388,10 @@ __global__ __launch_bounds__(256) void k_tt_block(const float *__restrict__ x, c
         const int slot = tid < 64 ? tt_elem_slot(ch * 16 + (tid >> 2), kq) : -1;
         if (slot >= 0) {
             float sum = 0.0f, comp = 0.0f;
-            for (int j = 0; j < 64; ++j) tt_kahan(sum, comp, lde[(tid >> 2) * 256 + 4 * j + kq]);
+            for (int j = 0; j < 64; ++j) kahan(sum, comp, lde[(tid >> 2) * 256 + 4 * j + kq]);
             row[slot] = sum;
         }
     }
-}
-
-// grad[o] = (sum over the G partial rows, in row order, compensated fp32) * (float)(1 / (double)(float)sum(mask)), the scale of
-// k_tb_finish from the same per-workgroup mask sums; the moving statistics and the padding get 0.
-__global__ __launch_bounds__(256) void k_tt_finish(const float *__restrict__ part, const double *__restrict__ lpart, int G,
-                                                   float *__restrict__ grad)
-{
-    __shared__ double red[4];
-    __shared__ float scale;
-    double b = 0.0;
-    for (int i = threadIdx.x; i < G; i += 256) b += lpart[2 * (long)i + 1];
-    const double rb = block_sum_256(b, red);
-    if (threadIdx.x == 0) scale = (float)(1.0 / (double)(float)rb);
-    __syncthreads();
-    const int o = blockIdx.x * 256 + threadIdx.x;
-    if (o >= TT_FLOATS) return;
-    float acc = 0.0f, comp = 0.0f;
-    if (o < TT_TRAINED)
-        for (long r = 0; r < G; ++r) tt_kahan(acc, comp, part[r * TT_TRAINED + o]);
-    grad[o] = o < TT_TRAINED ? acc * scale : 0.0f;
 }
 
 // the bottleneck's forward as the scoring path runs it, on the block's own weights: PT = its part of the packed block
@@ -478,10 +450,8 @@ hipError_t launch_train_tail_grad(const float *x, const int64_t *argmax, int N, 
         if (e != hipSuccess) return e;
     }
     for (int r = 0; r < R; ++r) {
-        ProfScope prof("k_tt_finish", (double)G * TT_TRAINED, 4.0 * G * TT_TRAINED + 16.0 * G, s);
-        hipLaunchKernelGGL(k_tt_finish, dim3((TT_FLOATS + 255) / 256), dim3(256), 0, s, r ? ws.part_t2 : ws.part_t,
-                           ws.ts.tb.lpart, G, grad + train_stage_floats(K) + r * TT_FLOATS);
-        e = hipGetLastError();
+        e = launch_train_finish<TT_TRAINED, TT_FLOATS>("k_tt_finish", r ? ws.part_t2 : ws.part_t, ws.ts.tb.lpart, G, G,
+                                                       grad + train_stage_floats(K) + r * TT_FLOATS, s);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

@@ -13,6 +13,8 @@ inside it: ``labelled`` marks, per image, whether the caller's annotation or the
 ``confidence >= threshold`` of the logits the kernel already holds) is trained on, ``confusion`` collects the training-pass
 confusion matrix and ``return_pseudo_pixels`` the count of pixels the threshold lets through.
 """
+import collections
+
 import numpy as np
 
 from . import _lib
@@ -413,20 +415,53 @@ class FinalLayerTrainer:
         return self._step_images(images, images_raw, labels, mask, semi, confusion, return_pseudo_pixels)
 
 
+# ---- the packed block of the ENet trainers (DESIGN.md sections 17-22) ------------------------------------------------------
+# The trained blocks travel as one float array, one part per block (include/ssal_enet.h, "Last-block training" .. "Decoder
+# training").  A kind of block is described once: ``layout`` (layer attribute, float offset from the part's start, regularised)
+# of its trained variables, ``stats`` (attribute, offset) of its moving statistics, ``floats`` of the part.  A trainer class
+# states its parts, in packed order, as ``_PARTS``: ((layer name, kind), ...).
+_Kind = collections.namedtuple("_Kind", "layout stats floats")
+_LAST_BLOCK = _Kind(  # Bottleneck5_1's block; Final.kernel closes this part: 144 K more floats at _FINAL_OFFSET
+    (("proj_kernel", 0, True), ("proj_gamma", 64, False), ("proj_beta", 68, False), ("proj_alpha", 72, True),
+     ("conv_kernel", 76, True), ("conv_gamma", 220, False), ("conv_beta", 224, False), ("conv_alpha", 228, True),
+     ("exp_kernel", 232, True), ("exp_gamma", 296, False), ("exp_beta", 312, False), ("residual_alpha", 328, True)),
+    (("proj_mean", 344), ("proj_variance", 348), ("conv_mean", 352), ("conv_variance", 356), ("exp_mean", 360),
+     ("exp_variance", 376)), 400)
+_FINAL_OFFSET = _LAST_BLOCK.floats
+_UPSAMPLE16 = _Kind(  # the 64 -> 16 upsampling block (Bottleneck5_0)
+    (("proj_kernel", 0, True), ("proj_gamma", 1024, False), ("proj_beta", 1040, False), ("proj_alpha", 1056, True),
+     ("conv_kernel", 1072, True), ("conv_gamma", 2224, False), ("conv_beta", 2232, False), ("conv_alpha", 2240, True),
+     ("exp_kernel", 2248, True), ("exp_gamma", 2376, False), ("exp_beta", 2392, False), ("res_kernel", 2408, True),
+     ("residual_alpha", 3432, True)),
+    (("proj_mean", 3448), ("proj_variance", 3464), ("conv_mean", 3480), ("conv_variance", 3488), ("exp_mean", 3496),
+     ("exp_variance", 3512)), 3536)
+_REGULAR64 = _Kind(  # a regular 64 -> 16 -> 16 -> 64 bottleneck (Bottleneck4_2, Bottleneck4_1)
+    (("proj_kernel", 0, True), ("proj_gamma", 1024, False), ("proj_beta", 1040, False), ("proj_alpha", 1056, True),
+     ("conv_kernel", 1072, True), ("conv_gamma", 3376, False), ("conv_beta", 3392, False), ("conv_alpha", 3408, True),
+     ("exp_kernel", 3424, True), ("exp_gamma", 4448, False), ("exp_beta", 4512, False), ("residual_alpha", 4576, True)),
+    (("proj_mean", 4640), ("proj_variance", 4656), ("conv_mean", 4672), ("conv_variance", 4688), ("exp_mean", 4704),
+     ("exp_variance", 4768)), 4840)
+_UPSAMPLE64 = _Kind(  # the 128 -> 32 -> 16 -> 64 upsampling block (Bottleneck4_0): _UPSAMPLE16's order with its sizes
+    (("proj_kernel", 0, True), ("proj_gamma", 4096, False), ("proj_beta", 4128, False), ("proj_alpha", 4160, True),
+     ("conv_kernel", 4192, True), ("conv_gamma", 8800, False), ("conv_beta", 8816, False), ("conv_alpha", 8832, True),
+     ("exp_kernel", 8848, True), ("exp_gamma", 9872, False), ("exp_beta", 9936, False), ("res_kernel", 10000, True),
+     ("residual_alpha", 18192, True)),
+    (("proj_mean", 18256), ("proj_variance", 18288), ("conv_mean", 18320), ("conv_variance", 18336), ("exp_mean", 18352),
+     ("exp_variance", 18416)), 18488)
+
+
+def _merged(ranges):
+    """(lo, hi, regularised) ranges with adjacent ones joined where they touch and carry the same flag: one Adam launch each"""
+    out = []
+    for lo, hi, reg in ranges:
+        if out and out[-1][1] == lo and out[-1][2] == reg:
+            out[-1] = (out[-1][0], hi, reg)
+        else:
+            out.append((lo, hi, reg))
+    return out
+
+
 # ---- the last block: Bottleneck5_1 + Final (DESIGN.md section 17) ---------------------------------------------------------
-# the packed block of include/ssal_enet.h ("Last-block training"): (variable, layer attribute, float offset, regularised)
-_BLOCK = "Bottleneck5_1"
-_BLOCK_LAYOUT = (
-    ("proj_kernel", 0, True), ("proj_gamma", 64, False), ("proj_beta", 68, False), ("proj_alpha", 72, True),
-    ("conv_kernel", 76, True), ("conv_gamma", 220, False), ("conv_beta", 224, False), ("conv_alpha", 228, True),
-    ("exp_kernel", 232, True), ("exp_gamma", 296, False), ("exp_beta", 312, False), ("residual_alpha", 328, True),
-)
-_BLOCK_STATS = (("proj_mean", 344), ("proj_variance", 348), ("conv_mean", 352), ("conv_variance", 356),
-                ("exp_mean", 360), ("exp_variance", 376))
-_FINAL_OFFSET = 400
-# Adam runs on these float ranges of the packed block; True = with the l1_l2 regulariser gradient
-_ADAM_RANGES = ((0, 64, True), (64, 72, False), (72, 220, True), (220, 228, False), (228, 296, True), (296, 328, False),
-                (328, 344, True))
 
 
 class LastBlockTrainer(FinalLayerTrainer):
@@ -465,20 +500,32 @@ class LastBlockTrainer(FinalLayerTrainer):
         return super().from_params(net, params, decay_steps=decay_steps)
 
     # ---- the packed block ------------------------------------------------------------------------------------------------
+    _PARTS = (("Bottleneck5_1", _LAST_BLOCK),)  # lowest block last: everything below it is frozen
+
+    def _parts(self):
+        """[(the layer, its name, its kind, the float offset of its part)] in packed order"""
+        out, start = [], 0
+        for name, kind in self._PARTS:
+            out.append((getattr(self.net, name), name, kind, start))
+            start += kind.floats + (0 if start else 144 * int(self.net.classes))  # (Final.kernel closes the first part)
+        return out
+
+    @staticmethod
+    def _part_named(blk, name, kind, start):
+        return [("%s.%s" % (name, a), getattr(blk, a), start + off, reg) for a, off, reg in kind.layout]
+
     def _named(self):
-        """[(name, Variable, float offset, regularised)] of the 13 trained variables, Final.kernel first"""
+        """[(name, Variable, float offset, regularised)] of the trained variables: Final.kernel, then part by part"""
         if not self.net.built:
             raise RuntimeError("build the model (call it once, or .build(input_shape)) before training")
-        blk = getattr(self.net, _BLOCK)
-        return [("Final.kernel", self.net.Final.kernel, _FINAL_OFFSET, True)] + [
-            ("%s.%s" % (_BLOCK, a), getattr(blk, a), off, reg) for a, off, reg in _BLOCK_LAYOUT]
+        return sum((self._part_named(*p) for p in self._parts()), [("Final.kernel", self.net.Final.kernel, _FINAL_OFFSET, True)])
 
     @property
     def variable_names(self):
         return [n for n, _, _, _ in self._named()]
 
     def _floats(self):
-        return _FINAL_OFFSET + 144 * int(self.net.classes)
+        return 144 * int(self.net.classes) + sum(kind.floats for _, kind in self._PARTS)
 
     def _pack(self, arrays=None):
         """the packed block from the host variables (``arrays`` None; the statistics included) or from a name -> array
@@ -490,10 +537,10 @@ class LastBlockTrainer(FinalLayerTrainer):
                 raise ValueError("%s must have shape %s (got %s)" % (name, var.shape, a.shape))
             out[off:off + a.size] = a.reshape(-1)
         if arrays is None:
-            blk = getattr(self.net, _BLOCK)
-            for a, off in _BLOCK_STATS:
-                v = getattr(blk, a).numpy()
-                out[off:off + v.size] = v
+            for blk, _, kind, start in self._parts():
+                for a, off in kind.stats:
+                    v = getattr(blk, a).numpy()
+                    out[start + off:start + off + v.size] = v
         return out
 
     def _unpack(self, packed):
@@ -501,8 +548,11 @@ class LastBlockTrainer(FinalLayerTrainer):
                 for name, var, off, _ in self._named()}
 
     def _versions(self):
-        blk = getattr(self.net, _BLOCK)
-        return tuple(v.version for v in [self.net.Final.kernel] + list(blk.variables))
+        return tuple(v.version for v in self._trained_variables())
+
+    def _trained_variables(self):
+        """every variable of the trained layers (the moving statistics too), Final.kernel first"""
+        return [self.net.Final.kernel] + [v for blk, _, _, _ in self._parts() for v in blk.variables]
 
     # ---- FinalLayerTrainer's hooks: the state and Adam run on the packed block ---------------------------------------------
     def _host_weights(self):
@@ -522,10 +572,16 @@ class LastBlockTrainer(FinalLayerTrainer):
         return query(n, h, w, k, with_raw) if semi else query(n, h, w, k)
 
     def _trained_tail(self):
-        return len(getattr(self.net, _BLOCK).variables) + 1
+        return len(self._trained_variables())
 
     def _adam_ranges(self):
-        return _ADAM_RANGES + ((_FINAL_OFFSET, _FINAL_OFFSET + 144 * int(self.net.classes), True),)
+        """part by part, each part's variables merged where they touch and share the flag; Final.kernel after the first"""
+        out = []
+        for part in self._parts():
+            out += _merged((off, off + int(np.prod(var.shape)), reg) for _, var, off, reg in self._part_named(*part))
+            if not part[3]:
+                out.append((_FINAL_OFFSET, _FINAL_OFFSET + 144 * int(self.net.classes), True))
+        return tuple(out)
 
     def _write_back(self, host):
         for name, var, off, _ in self._named():
@@ -624,16 +680,21 @@ class LastBlockTrainer(FinalLayerTrainer):
         """Bottleneck5_0's output [N, H/2, W/2, 16] for ``images`` (a copy): what ``step_features`` and
         ``gradient_features`` take.  One forward pass of the frozen trunk; the frozen layers never change, so the result
         can be cached across steps."""
+        return self._workspace_features(images, "ssal_enet_train_block_features_offset", 2, 16)
+
+    def _workspace_features(self, images, offset_entry, down, channels):
+        """[N, H / down, W / down, channels] fp32 (a copy) out of the net's workspace after one forward pass on ``images``;
+        ``offset_entry``: the C query of the slice's byte offset"""
         net = self.net
         x = net._prepare(images, False)
         n, h, w, _ = x.shape
         net(x, training=False)
-        off = _lib.lib().ssal_enet_train_block_features_offset(net._handle, n, h, w)
+        off = getattr(_lib.lib(), offset_entry)(net._handle, n, h, w)
         if off < 0:
             raise ValueError("bad input dims %s" % (tuple(x.shape),))
         torch = _lib.require_gpu()
-        shape = (n, h // 2, w // 2, 16)
-        return net._ws[off:off + 4 * n * (h // 2) * (w // 2) * 16].view(torch.float32).view(shape).clone()
+        shape = (n, h // down, w // down, channels)
+        return net._ws[off:off + 4 * int(np.prod(shape))].view(torch.float32).view(shape).clone()
 
     def step_features(self, features5_0, labels, mask, labelled=None, measure=None, threshold=None, features_raw=None,
                       confusion=None, return_pseudo_pixels=False):
@@ -654,21 +715,6 @@ class LastBlockTrainer(FinalLayerTrainer):
 
 
 # ---- the last stage: Bottleneck5_0 + Bottleneck5_1 + Final ------------------------------------------
-# Bottleneck5_0's part of the packed stage block (include/ssal_enet.h, "Last-stage training"), offsets from its start
-_STAGE = "Bottleneck5_0"
-_STAGE_LAYOUT = (
-    ("proj_kernel", 0, True), ("proj_gamma", 1024, False), ("proj_beta", 1040, False), ("proj_alpha", 1056, True),
-    ("conv_kernel", 1072, True), ("conv_gamma", 2224, False), ("conv_beta", 2232, False), ("conv_alpha", 2240, True),
-    ("exp_kernel", 2248, True), ("exp_gamma", 2376, False), ("exp_beta", 2392, False), ("res_kernel", 2408, True),
-    ("residual_alpha", 3432, True),
-)
-_STAGE_STATS = (("proj_mean", 3448), ("proj_variance", 3464), ("conv_mean", 3480), ("conv_variance", 3488),
-                ("exp_mean", 3496), ("exp_variance", 3512))
-_STAGE_FLOATS = 3536
-_STAGE_ADAM_RANGES = ((0, 1024, True), (1024, 1056, False), (1056, 2224, True), (2224, 2240, False), (2240, 2376, True),
-                      (2376, 2408, False), (2408, 3448, True))
-
-
 class LastStageTrainer(LastBlockTrainer):
     """Adam on the 26 variables of ENet's last decoder stage: the 13 of ``LastBlockTrainer`` and ``Bottleneck5_0``'s
     ``proj_kernel``, ``proj_gamma``, ``proj_beta``, ``proj_alpha``, ``conv_kernel``, ``conv_gamma``, ``conv_beta``,
@@ -691,80 +737,53 @@ class LastStageTrainer(LastBlockTrainer):
     _C_IMAGES = ("ssal_enet_train_stage", "ssal_enet_train_stage_semi")
     _CHANNELS, _UP = 64, 4
     _LIMIT = ("kernels'", "kernels'")
-    _LOWEST = _STAGE  # the lowest trained block: everything below it is frozen
-
-    def _stage_offset(self):
-        return _FINAL_OFFSET + 144 * int(self.net.classes)
-
-    def _named(self):
-        """[(name, Variable, float offset, regularised)] of the 26 trained variables: the last block's, then Bottleneck5_0's"""
-        base = super()._named()
-        blk, s0 = getattr(self.net, _STAGE), self._stage_offset()
-        return base + [("%s.%s" % (_STAGE, a), getattr(blk, a), s0 + off, reg) for a, off, reg in _STAGE_LAYOUT]
-
-    def _floats(self):
-        return self._stage_offset() + _STAGE_FLOATS
-
-    def _pack(self, arrays=None):
-        out = super()._pack(arrays)
-        if arrays is None:
-            blk, s0 = getattr(self.net, _STAGE), self._stage_offset()
-            for a, off in _STAGE_STATS:
-                v = getattr(blk, a).numpy()
-                out[s0 + off:s0 + off + v.size] = v
-        return out
-
-    def _versions(self):
-        return super()._versions() + tuple(v.version for v in getattr(self.net, _STAGE).variables)
-
-    def _trained_tail(self):
-        return super()._trained_tail() + len(getattr(self.net, _STAGE).variables)
-
-    def _adam_ranges(self):
-        s0 = self._stage_offset()
-        return super()._adam_ranges() + tuple((s0 + lo, s0 + hi, reg) for lo, hi, reg in _STAGE_ADAM_RANGES)
+    _PARTS = LastBlockTrainer._PARTS + (("Bottleneck5_0", _UPSAMPLE16),)
 
     # ---- arguments, judged on the host ---------------------------------------------------------------------------------------
-    def _check_argmax(self, feature_shape, argmax1):
-        """``argmax1`` as an int64 tensor (on whatever device it lives) after the checks: shape [N, h, w, 16], every index
-        inside its own 2 x 2 window and channel.  A torch tensor that passed is remembered, so a cached one is checked once."""
+    def _check_argmax(self, name, feature_channels, index_channels, feature_shape, argmax):
+        """the pooling indices ``argmax`` (``name`` in the messages: "argmax1" / "argmax2") as an int64 tensor (on whatever
+        device it lives) after the checks: shape [N, h, w, index_channels] next to features [N, h, w, feature_channels], every
+        index inside its own 2 x 2 window and channel.  A torch tensor that passed is remembered under its name, so a cached
+        one is checked once."""
         import torch
-        a = argmax1 if isinstance(argmax1, torch.Tensor) else torch.as_tensor(np.asarray(argmax1))
-        shape = tuple(feature_shape)
-        if len(shape) != 4 or shape[-1] != 64:
-            raise ValueError("features must be [N,h,w,64] (got %s)" % (shape,))
-        want = shape[:3] + (16,)
+        a = argmax if isinstance(argmax, torch.Tensor) else torch.as_tensor(np.asarray(argmax))
+        shape, ch = tuple(feature_shape), index_channels
+        if len(shape) != 4 or shape[-1] != feature_channels:
+            raise ValueError("features must be [N,h,w,%d] (got %s)" % (feature_channels, shape))
+        want = shape[:3] + (ch,)
         if tuple(a.shape) != want:
-            raise ValueError("argmax1 must have shape %s (got %s)" % (want, tuple(a.shape)))
+            raise ValueError("%s must have shape %s (got %s)" % (name, want, tuple(a.shape)))
         if a.dtype != torch.int64:
             if a.dtype.is_floating_point or a.dtype == torch.bool:
-                raise ValueError("argmax1 must be an integer tensor (got %s)" % a.dtype)
+                raise ValueError("%s must be an integer tensor (got %s)" % (name, a.dtype))
             a = a.to(torch.int64)
-        seen = getattr(self, "_argmax_ok", None)  # (the caller's tensor itself, its version): kept alive, so never confused
-        if not (seen is not None and seen[0] is argmax1 and seen[1] == argmax1._version):
+        # name -> (the caller's tensor itself, its version): kept alive, so never confused
+        memo = vars(self).setdefault("_argmax_ok", {})
+        seen = memo.get(name)
+        if not (seen is not None and seen[0] is argmax and seen[1] == argmax._version):
             _, h, w, _ = want
-            c = torch.arange(16, device=a.device).view(1, 1, 1, 16)
+            c = torch.arange(ch, device=a.device).view(1, 1, 1, ch)
             i = torch.arange(h, device=a.device).view(1, h, 1, 1)
             j = torch.arange(w, device=a.device).view(1, 1, w, 1)
-            pix = torch.div(a, 16, rounding_mode="floor")
+            pix = torch.div(a, ch, rounding_mode="floor")
             y, x = torch.div(pix, 2 * w, rounding_mode="floor"), pix % (2 * w)
-            ok = (a >= 0) & (a % 16 == c) & (torch.div(y, 2, rounding_mode="floor") == i) & \
+            ok = (a >= 0) & (a % ch == c) & (torch.div(y, 2, rounding_mode="floor") == i) & \
                  (torch.div(x, 2, rounding_mode="floor") == j)
             if not bool(ok.all()):
-                raise ValueError("argmax1 holds %d indices outside their own 2x2 window / channel"
-                                 % int((~ok).sum()))
-            self._argmax_ok = (argmax1, argmax1._version) if isinstance(argmax1, torch.Tensor) else None
+                raise ValueError("%s holds %d indices outside their own 2x2 window / channel" % (name, int((~ok).sum())))
+            memo[name] = (argmax, argmax._version) if isinstance(argmax, torch.Tensor) else None
         return a
 
     def _check_inputs(self, inputs):
-        return inputs[0], self._check_argmax(np.shape(inputs[0]), inputs[1])
+        return inputs[0], self._check_argmax("argmax1", 64, 16, np.shape(inputs[0]), inputs[1])
 
     def _check_params(self, params):
         unknown = set(params or {}) - set(self.variable_names)
-        frozen = self.net._layer_names[:self.net._layer_names.index(self._LOWEST)]
+        lowest = self._PARTS[-1][0]
+        frozen = self.net._layer_names[:self.net._layer_names.index(lowest)]
         below = sorted(n for n in unknown if n.split(".")[0] in frozen)
         if below:
-            raise NotImplementedError("training below %s is not implemented (got %s)" % (self._LOWEST, below))
+            raise NotImplementedError("training below %s is not implemented (got %s)" % (lowest, below))
         return super()._check_params(params)
 
     @staticmethod
@@ -792,17 +811,7 @@ class LastStageTrainer(LastBlockTrainer):
         """(Bottleneck4_2's output [N, H/4, W/4, 64] (a copy), argmax1 [N, H/4, W/4, 16] int64) for ``images``: what
         ``step_features`` and ``gradient_features`` take.  One forward pass of the frozen trunk; the frozen layers never
         change, so the result can be cached across steps."""
-        net = self.net
-        x = net._prepare(images, False)
-        n, h, w, _ = x.shape
-        net(x, training=False)
-        off = _lib.lib().ssal_enet_train_stage_features_offset(net._handle, n, h, w)
-        if off < 0:
-            raise ValueError("bad input dims %s" % (tuple(x.shape),))
-        torch = _lib.require_gpu()
-        shape = (n, h // 4, w // 4, 64)
-        feats = net._ws[off:off + 4 * n * (h // 4) * (w // 4) * 64].view(torch.float32).view(shape).clone()
-        return feats, net.pooling_argmax()[0]
+        return self._workspace_features(images, "ssal_enet_train_stage_features_offset", 4, 64), self.net.pooling_argmax()[0]
 
     def step_features(self, features4_2, argmax1, labels, mask, max_workgroups=0, labelled=None, measure=None,
                       threshold=None, features_raw=None, argmax1_raw=None, confusion=None, return_pseudo_pixels=False):
@@ -826,21 +835,6 @@ class LastStageTrainer(LastBlockTrainer):
 
 
 # ---- the decoder tail: Bottleneck4_2 + the last stage ------------------------------------------------
-# Bottleneck4_2's part of the packed tail block (include/ssal_enet.h, "Decoder-tail training"), offsets from its start: the
-# layout of a regular 64 -> 16 -> 16 -> 64 bottleneck
-_TAIL = "Bottleneck4_2"
-_TAIL_LAYOUT = (
-    ("proj_kernel", 0, True), ("proj_gamma", 1024, False), ("proj_beta", 1040, False), ("proj_alpha", 1056, True),
-    ("conv_kernel", 1072, True), ("conv_gamma", 3376, False), ("conv_beta", 3392, False), ("conv_alpha", 3408, True),
-    ("exp_kernel", 3424, True), ("exp_gamma", 4448, False), ("exp_beta", 4512, False), ("residual_alpha", 4576, True),
-)
-_TAIL_STATS = (("proj_mean", 4640), ("proj_variance", 4656), ("conv_mean", 4672), ("conv_variance", 4688),
-               ("exp_mean", 4704), ("exp_variance", 4768))
-_TAIL_FLOATS = 4840
-_TAIL_ADAM_RANGES = ((0, 1024, True), (1024, 1056, False), (1056, 3376, True), (3376, 3408, False), (3408, 4448, True),
-                     (4448, 4576, False), (4576, 4640, True))
-
-
 class DecoderTailTrainer(LastStageTrainer):
     """Adam on the variables of ENet's decoder tail: the 26 of ``LastStageTrainer`` and ``Bottleneck4_2``'s ``proj_kernel``,
     ``proj_gamma``, ``proj_beta``, ``proj_alpha``, ``conv_kernel``, ``conv_gamma``, ``conv_beta``, ``conv_alpha``,
@@ -860,38 +854,7 @@ class DecoderTailTrainer(LastStageTrainer):
 
     _C_FEATURES = ("ssal_train_tail_grad", "ssal_train_tail_grad_semi")
     _C_IMAGES = ("ssal_enet_train_tail", "ssal_enet_train_tail_semi")
-    _LOWEST = _TAIL
-
-    def _tail_offset(self):
-        return self._stage_offset() + _STAGE_FLOATS
-
-    def _named(self):
-        """[(name, Variable, float offset, regularised)] of the trained variables: the last stage's 26, then Bottleneck4_2's"""
-        base = super()._named()
-        blk, t0 = getattr(self.net, _TAIL), self._tail_offset()
-        return base + [("%s.%s" % (_TAIL, a), getattr(blk, a), t0 + off, reg) for a, off, reg in _TAIL_LAYOUT]
-
-    def _floats(self):
-        return self._tail_offset() + _TAIL_FLOATS
-
-    def _pack(self, arrays=None):
-        out = super()._pack(arrays)
-        if arrays is None:
-            blk, t0 = getattr(self.net, _TAIL), self._tail_offset()
-            for a, off in _TAIL_STATS:
-                v = getattr(blk, a).numpy()
-                out[t0 + off:t0 + off + v.size] = v
-        return out
-
-    def _versions(self):
-        return super()._versions() + tuple(v.version for v in getattr(self.net, _TAIL).variables)
-
-    def _trained_tail(self):
-        return super()._trained_tail() + len(getattr(self.net, _TAIL).variables)
-
-    def _adam_ranges(self):
-        t0 = self._tail_offset()
-        return super()._adam_ranges() + tuple((t0 + lo, t0 + hi, reg) for lo, hi, reg in _TAIL_ADAM_RANGES)
+    _PARTS = LastStageTrainer._PARTS + (("Bottleneck4_2", _REGULAR64),)
 
     def gradient_features(self, features4_1, argmax1, labels, mask, params=None, max_workgroups=0, **semi_keywords):
         """(loss float64 [1], {name: gradient}) on the device for Bottleneck4_1's output [N, h, w, 64], the pooling indices
@@ -903,17 +866,7 @@ class DecoderTailTrainer(LastStageTrainer):
     def features(self, images):
         """(Bottleneck4_1's output [N, H/4, W/4, 64] (a copy), argmax1 [N, H/4, W/4, 16] int64) for ``images``: what
         ``step_features`` and ``gradient_features`` take.  One forward pass of the frozen trunk."""
-        net = self.net
-        x = net._prepare(images, False)
-        n, h, w, _ = x.shape
-        net(x, training=False)
-        off = _lib.lib().ssal_enet_train_tail_features_offset(net._handle, n, h, w)
-        if off < 0:
-            raise ValueError("bad input dims %s" % (tuple(x.shape),))
-        torch = _lib.require_gpu()
-        shape = (n, h // 4, w // 4, 64)
-        feats = net._ws[off:off + 4 * n * (h // 4) * (w // 4) * 64].view(torch.float32).view(shape).clone()
-        return feats, net.pooling_argmax()[0]
+        return self._workspace_features(images, "ssal_enet_train_tail_features_offset", 4, 64), self.net.pooling_argmax()[0]
 
     def step_features(self, features4_1, argmax1, labels, mask, max_workgroups=0, **semi_keywords):
         """one Adam step from cached Bottleneck4_1 features and pooling indices (``features(images)``); returns the loss
@@ -922,10 +875,6 @@ class DecoderTailTrainer(LastStageTrainer):
 
 
 # ---- the deep tail: Bottleneck4_1 + the decoder tail --------------------------------------------------
-# Bottleneck4_1's part of the packed block follows the tail block and is laid out as Bottleneck4_2's (a regular bottleneck's)
-_DEEP = "Bottleneck4_1"
-
-
 class DeepTailTrainer(DecoderTailTrainer):
     """Adam on 50 variables: the 38 of ``DecoderTailTrainer``, then ``Bottleneck4_1``'s twelve (``proj_kernel`` ..
     ``residual_alpha``, 4 640 floats).  Bottleneck4_2's backward also yields its input gradient, and the second regular
@@ -944,38 +893,7 @@ class DeepTailTrainer(DecoderTailTrainer):
 
     _C_FEATURES = ("ssal_train_tail2_grad", "ssal_train_tail2_grad_semi")
     _C_IMAGES = ("ssal_enet_train_tail2", "ssal_enet_train_tail2_semi")
-    _LOWEST = _DEEP
-
-    def _deep_offset(self):
-        return self._tail_offset() + _TAIL_FLOATS
-
-    def _named(self):
-        """[(name, Variable, float offset, regularised)] of the trained variables: the tail's 38, then Bottleneck4_1's"""
-        base = super()._named()
-        blk, t0 = getattr(self.net, _DEEP), self._deep_offset()
-        return base + [("%s.%s" % (_DEEP, a), getattr(blk, a), t0 + off, reg) for a, off, reg in _TAIL_LAYOUT]
-
-    def _floats(self):
-        return self._deep_offset() + _TAIL_FLOATS
-
-    def _pack(self, arrays=None):
-        out = super()._pack(arrays)
-        if arrays is None:
-            blk, t0 = getattr(self.net, _DEEP), self._deep_offset()
-            for a, off in _TAIL_STATS:
-                v = getattr(blk, a).numpy()
-                out[t0 + off:t0 + off + v.size] = v
-        return out
-
-    def _versions(self):
-        return super()._versions() + tuple(v.version for v in getattr(self.net, _DEEP).variables)
-
-    def _trained_tail(self):
-        return super()._trained_tail() + len(getattr(self.net, _DEEP).variables)
-
-    def _adam_ranges(self):
-        t0 = self._deep_offset()
-        return super()._adam_ranges() + tuple((t0 + lo, t0 + hi, reg) for lo, hi, reg in _TAIL_ADAM_RANGES)
+    _PARTS = DecoderTailTrainer._PARTS + (("Bottleneck4_1", _REGULAR64),)
 
     def gradient_features(self, features4_0, argmax1, labels, mask, params=None, max_workgroups=0, **semi_keywords):
         """(loss float64 [1], {name: gradient}) on the device for Bottleneck4_0's output [N, h, w, 64], the pooling indices
@@ -1002,22 +920,6 @@ class DeepTailTrainer(DecoderTailTrainer):
 
 
 # ---- the decoder: Bottleneck4_0 + the deep tail --------------------------------------------------------
-# Bottleneck4_0's part of the packed block (include/ssal_enet.h, "Decoder training"), offsets from its start: the order of
-# Bottleneck5_0's part with the sizes of the 128 -> 32 -> 16 -> 64 upsampling block
-_DECODER = "Bottleneck4_0"
-_DECODER_LAYOUT = (
-    ("proj_kernel", 0, True), ("proj_gamma", 4096, False), ("proj_beta", 4128, False), ("proj_alpha", 4160, True),
-    ("conv_kernel", 4192, True), ("conv_gamma", 8800, False), ("conv_beta", 8816, False), ("conv_alpha", 8832, True),
-    ("exp_kernel", 8848, True), ("exp_gamma", 9872, False), ("exp_beta", 9936, False), ("res_kernel", 10000, True),
-    ("residual_alpha", 18192, True),
-)
-_DECODER_STATS = (("proj_mean", 18256), ("proj_variance", 18288), ("conv_mean", 18320), ("conv_variance", 18336),
-                  ("exp_mean", 18352), ("exp_variance", 18416))
-_DECODER_FLOATS = 18488
-_DECODER_ADAM_RANGES = ((0, 4096, True), (4096, 4160, False), (4160, 8800, True), (8800, 8832, False), (8832, 9872, True),
-                        (9872, 10000, False), (10000, 18256, True))
-
-
 class DecoderTrainer(DeepTailTrainer):
     """Adam on 63 variables: the 50 of ``DeepTailTrainer``, then ``Bottleneck4_0``'s thirteen (``proj_kernel`` ..
     ``residual_alpha``, 18 256 floats): the backward pass through the 128 -> 64 upsampling block that opens the decoder.  The
@@ -1040,74 +942,13 @@ class DecoderTrainer(DeepTailTrainer):
     _C_FEATURES = ("ssal_train_decoder_grad", "ssal_train_decoder_grad_semi")
     _C_IMAGES = ("ssal_enet_train_decoder", "ssal_enet_train_decoder_semi")
     _CHANNELS, _UP = 128, 8
-    _LOWEST = _DECODER
-
-    def _decoder_offset(self):
-        return self._deep_offset() + _TAIL_FLOATS
-
-    def _named(self):
-        """[(name, Variable, float offset, regularised)] of the trained variables: the deep tail's 50, then Bottleneck4_0's"""
-        base = super()._named()
-        blk, d0 = getattr(self.net, _DECODER), self._decoder_offset()
-        return base + [("%s.%s" % (_DECODER, a), getattr(blk, a), d0 + off, reg) for a, off, reg in _DECODER_LAYOUT]
-
-    def _floats(self):
-        return self._decoder_offset() + _DECODER_FLOATS
-
-    def _pack(self, arrays=None):
-        out = super()._pack(arrays)
-        if arrays is None:
-            blk, d0 = getattr(self.net, _DECODER), self._decoder_offset()
-            for a, off in _DECODER_STATS:
-                v = getattr(blk, a).numpy()
-                out[d0 + off:d0 + off + v.size] = v
-        return out
-
-    def _versions(self):
-        return super()._versions() + tuple(v.version for v in getattr(self.net, _DECODER).variables)
-
-    def _trained_tail(self):
-        return super()._trained_tail() + len(getattr(self.net, _DECODER).variables)
-
-    def _adam_ranges(self):
-        d0 = self._decoder_offset()
-        return super()._adam_ranges() + tuple((d0 + lo, d0 + hi, reg) for lo, hi, reg in _DECODER_ADAM_RANGES)
+    _PARTS = DeepTailTrainer._PARTS + (("Bottleneck4_0", _UPSAMPLE64),)
 
     # ---- arguments, judged on the host ---------------------------------------------------------------------------------------
-    def _check_argmax2(self, feature_shape, argmax2):
-        """``argmax2`` as an int64 tensor after the checks ``argmax1`` gets: shape [N, h, w, 64], every index inside its own
-        2 x 2 window and channel.  A torch tensor that passed is remembered, so a cached one is checked once."""
-        import torch
-        a = argmax2 if isinstance(argmax2, torch.Tensor) else torch.as_tensor(np.asarray(argmax2))
-        shape = tuple(feature_shape)
-        if len(shape) != 4 or shape[-1] != 128:
-            raise ValueError("features must be [N,h,w,128] (got %s)" % (shape,))
-        want = shape[:3] + (64,)
-        if tuple(a.shape) != want:
-            raise ValueError("argmax2 must have shape %s (got %s)" % (want, tuple(a.shape)))
-        if a.dtype != torch.int64:
-            if a.dtype.is_floating_point or a.dtype == torch.bool:
-                raise ValueError("argmax2 must be an integer tensor (got %s)" % a.dtype)
-            a = a.to(torch.int64)
-        seen = getattr(self, "_argmax2_ok", None)
-        if not (seen is not None and seen[0] is argmax2 and seen[1] == argmax2._version):
-            _, h, w, _ = want
-            c = torch.arange(64, device=a.device).view(1, 1, 1, 64)
-            i = torch.arange(h, device=a.device).view(1, h, 1, 1)
-            j = torch.arange(w, device=a.device).view(1, 1, w, 1)
-            pix = torch.div(a, 64, rounding_mode="floor")
-            y, x = torch.div(pix, 2 * w, rounding_mode="floor"), pix % (2 * w)
-            ok = (a >= 0) & (a % 64 == c) & (torch.div(y, 2, rounding_mode="floor") == i) & \
-                 (torch.div(x, 2, rounding_mode="floor") == j)
-            if not bool(ok.all()):
-                raise ValueError("argmax2 holds %d indices outside their own 2x2 window / channel" % int((~ok).sum()))
-            self._argmax2_ok = (argmax2, argmax2._version) if isinstance(argmax2, torch.Tensor) else None
-        return a
-
     def _check_inputs(self, inputs):
         shape = tuple(np.shape(inputs[0]))
-        a2 = self._check_argmax2(shape, inputs[1])
-        return inputs[0], a2, self._check_argmax((shape[0], 2 * shape[1], 2 * shape[2], 64), inputs[2])
+        a2 = self._check_argmax("argmax2", 128, 64, shape, inputs[1])
+        return inputs[0], a2, self._check_argmax("argmax1", 64, 16, (shape[0], 2 * shape[1], 2 * shape[2], 64), inputs[2])
 
     def _raw_host(self, inputs, raw):
         if len({r is None for r in raw}) > 1:
@@ -1133,17 +974,8 @@ class DecoderTrainer(DeepTailTrainer):
         """(Bottleneck3_8's output [N, H/8, W/8, 128] (a copy), argmax2 [N, H/8, W/8, 64], argmax1 [N, H/4, W/4, 16], both
         int64) for ``images``: what ``step_features`` and ``gradient_features`` take.  One forward pass of the frozen encoder;
         the frozen layers never change, so the result can be cached across steps."""
-        net = self.net
-        x = net._prepare(images, False)
-        n, h, w, _ = x.shape
-        net(x, training=False)
-        off = _lib.lib().ssal_enet_train_decoder_features_offset(net._handle, n, h, w)
-        if off < 0:
-            raise ValueError("bad input dims %s" % (tuple(x.shape),))
-        torch = _lib.require_gpu()
-        shape = (n, h // 8, w // 8, 128)
-        feats = net._ws[off:off + 4 * n * (h // 8) * (w // 8) * 128].view(torch.float32).view(shape).clone()
-        argmax1, argmax2 = net.pooling_argmax()
+        feats = self._workspace_features(images, "ssal_enet_train_decoder_features_offset", 8, 128)
+        argmax1, argmax2 = self.net.pooling_argmax()
         return feats, argmax2, argmax1
 
     def step_features(self, features3_8, argmax2, argmax1, labels, mask, max_workgroups=0, labelled=None, measure=None,

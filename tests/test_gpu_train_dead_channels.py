@@ -1,7 +1,7 @@
-"""Dead channels on the MI355X: the derivative of PReLU at exactly 0 in the four kernel files' own copies of the rule
-(tb_dprelu, ts_dprelu, tt_dprelu, td_dprelu).  A trained network's dead channels -- batch-norm gamma = beta = 0 -- put +0 into
+"""Dead channels on the MI355X: the derivative of PReLU at exactly 0 as the four training kernel files use it (dprelu of
+csrc/ssal_train_common.h, inlined into each block kernel).  A trained network's dead channels -- batch-norm gamma = beta = 0 -- put +0 into
 their PReLU at every pixel; the reference's PReLU, relu(x) - alpha relu(-x), has derivative 0 there, so every gradient entry that
-belongs to such a channel is exactly 0.0.  A copy that said ``v >= 0 ? 1 : a`` would push a spurious d beta into Adam.  The
+belongs to such a channel is exactly 0.0.  A rule that said ``v >= 0 ? 1 : a`` would push a spurious d beta into Adam.  The
 float64 oracle's half is test_train_dead_channels_cpu.py; the data is class_count_cases.dead_decoder_case (K = 19, a3_8
 1 x 3 x 9, projection channel 1 and convolution channel 2 dead in all five trained blocks, the moving statistics random).
 

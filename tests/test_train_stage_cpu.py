@@ -190,7 +190,7 @@ def test_bad_argmax_raises_before_any_device_work():
     x = np.zeros((1, 4, 6, 64), np.float32)
     lab, mk = np.zeros((1, 16, 24), np.uint8), np.ones((1, 16, 24), np.float32)
     good = lso.random_argmax(np.random.default_rng(0), 1, 4, 6)
-    assert tr._check_argmax(x.shape, good).shape == (1, 4, 6, 16)
+    assert tr._check_argmax("argmax1", 64, 16, x.shape, good).shape == (1, 4, 6, 16)
     bad = {}
     bad["shape"] = good[:, :, :, :8]
     bad["other window"] = good.copy()

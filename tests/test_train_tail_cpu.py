@@ -93,7 +93,7 @@ def test_names_layout_and_pack_round_trip():
         assert re.search(r"\b%d  %s \[" % (off, a), sec), (a, off)
     for name, var, off, _ in tr._named()[26:]:
         assert off == t0 + HEADER_OFFSETS[name.split(".")[1]], name
-    assert dict(training._TAIL_STATS) == {a: o for a, o in HEADER_OFFSETS.items() if a.endswith(("mean", "variance"))}
+    assert dict(training._REGULAR64.stats) == {a: o for a, o in HEADER_OFFSETS.items() if a.endswith(("mean", "variance"))}
     used = np.zeros(tr._floats(), np.int32)
     for name, var, off, _ in tr._named():
         used[off:off + int(np.prod(var.shape))] += 1
