@@ -64,6 +64,20 @@ int ssal_icnet_score_regions_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u
                                   uint8_t *label_dev, uint8_t *mask_dev, float *conf_dev, void *ws_dev, int64_t ws_bytes,
                                   void *stream);
 
+/* Evaluation pass (the validation epoch of active_learning.py:277-282 with tensortools/metrics.py:226-257):
+ * ssal_enet_evaluate_nhwc_arith's contract (include/ssal_enet.h) for the ICNet handle, fp32 arithmetic.  The trunk is the
+ * one ssal_icnet_score_nhwc runs (same schedule, fused launches and knobs); the last launch evaluates conv6_interp, takes
+ * the first maximum of the full-resolution logits (the byte ssal_icnet_score_nhwc writes to label_dev) and counts it against
+ * labels_dev uint8 [n,h,w]: mask_dev[p] (uint8 [n,h,w]; NULL = weight 1) is ADDED to confusion_dev[label][prediction]
+ * (int64 [classes, classes]); labels >= classes are dropped.  No softmax, no score, no per-pixel plane leaves the kernel.
+ * labels_dev / mask_dev 4-byte aligned (four pixels per load).  Integer atomics only: the result does not depend on the
+ * launch order.  SSAL_EINVAL: bad dims, a NULL pointer (mask_dev aside), a misaligned plane; SSAL_ENOMEM: workspace smaller
+ * than ssal_icnet_eval_workspace_bytes (which returns -1 for bad dims or an uncommitted handle). */
+int64_t ssal_icnet_eval_workspace_bytes(const ssal_icnet *net, int n, int h, int w);
+int ssal_icnet_evaluate_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                             const uint8_t *labels_dev, const uint8_t *mask_dev, int64_t *confusion_dev, void *ws_dev,
+                             int64_t ws_bytes, void *stream);
+
 /* Named intermediate tensors of the LAST forward/score call on a workspace (every ICNET_SPEC layer output that is
  * materialised keeps its own buffer): byte offset into the workspace and NHWC dims.  SSAL_EINVAL for a name that
  * is not materialised (the 2x interpolations are evaluated inside the consuming convolution).  Every endpoint is valid

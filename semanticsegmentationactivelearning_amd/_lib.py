@@ -157,6 +157,8 @@ PROTOTYPES = {
     "ssal_icnet_score_nhwc_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "ssal_icnet_regions_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
     "ssal_icnet_score_regions_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_icnet_eval_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
+    "ssal_icnet_evaluate_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
     "ssal_icnet_num_endpoints": (_i, [_vp]),
     "ssal_icnet_endpoint_name": (_i, [_vp, _i, _c.POINTER(_c.c_char_p)]),
     "ssal_icnet_endpoint_info": (_i, [_vp, _c.c_char_p, _i, _i, _i, _c.POINTER(_i64), _c.POINTER(_i64)]),

@@ -262,8 +262,8 @@ def evaluate(net, batches, num_classes, group=None, prefetch=2, arithmetic="f32"
     """The validation / test pass of the reference loop (active_learning.py:277-282 ``val_net`` + ``val_pred``, the
     ``Metrics`` update :390-427, read back at :616-630 and :655-680): ``batches`` yields ``(image, label, mask, ...)``
     as ``InputStage``'s evaluation path produces them (centre crop, ``generate_mask``); extra items are ignored.  Each
-    batch is counted on the device by ``net.evaluate`` (ENet: fused into the Final kernel; ICNet: label plane + the
-    confusion op) into one int64 K x K accumulator; host batches are copied ``prefetch`` batches ahead on a side stream
+    batch is counted on the device by ``net.evaluate`` (ENet: fused into the Final kernel; ICNet: into the up-sampling
+    kernel) into one int64 K x K accumulator; host batches are copied ``prefetch`` batches ahead on a side stream
     (``prefetch_to_device``).  With a process group (every rank evaluates its own shard) the K x K matrices are summed
     with exactly ONE all-reduce.  Returns ``tensortools.metrics.create_metrics`` of the total (``MeanIoU`` decides the
     reference's early stopping)."""

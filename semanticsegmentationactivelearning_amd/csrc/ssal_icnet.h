@@ -83,5 +83,10 @@ hipError_t launch_ppm(const float *x, int N, int H, int W, int C, float *scratch
 int upscore_blocks(int H, int W);
 hipError_t launch_upscore(const float *lq, int N, int H, int W, int K, int measure, float threshold, double *partial,
                           uint8_t *label, uint8_t *mask, float *conf, hipStream_t s);
+// the evaluation form (ssal_icnet_eval.hip): conv6_interp + argmax (k_upscore's label) counted against gt_label / gt_mask
+// uint8 [N,4H,4W] (gt_mask NULL = weight 1; both 4-byte aligned) into the zeroed confusion replicas rep [reps] of
+// ssal_confusion.h; launch_confusion_fold folds them.  No output plane, no partials.
+hipError_t launch_upeval(const float *lq, int N, int H, int W, int K, const uint8_t *gt_label, const uint8_t *gt_mask,
+                         unsigned long long *rep, int reps, hipStream_t s);
 
 }  // namespace ssal

@@ -380,19 +380,11 @@ int forward_any(ssal_icnet *net, const void *x_dev, bool u8, int n, int h, int w
     return SSAL_OK;
 }
 
-int score_any(ssal_icnet *net, const void *x_dev, bool u8, int n, int h, int w, int measure, float threshold,
-              double *scores_dev, uint8_t *label_dev, uint8_t *mask_dev, float *conf_dev, void *ws_dev,
-              int64_t ws_bytes, void *stream)
+// The fused trunk of a score-type call (ranking: score_any; validation: eval_any) up to conv6_cls, then tail(chain, first
+// image of the chain) on every chain's stream, then the join: one schedule, one set of knobs for both passes.
+template <class Tail>
+int run_scored(ssal_icnet *net, const void *x_dev, bool u8, int n, int h, int w, const IcWorkspace &W, hipStream_t s, Tail tail)
 {
-    int rc = check_dims(net, n, h, w);
-    if (rc) return rc;
-    if (measure < 0 || measure > 2) return fail(SSAL_ENOTIMPL, "Uncertainty function not implemented (measure=%d)", measure);
-    if (!x_dev || !scores_dev || !ws_dev) return fail(SSAL_EINVAL, "NULL device pointer");
-    if (((uintptr_t)label_dev | (uintptr_t)mask_dev) & 3 || ((uintptr_t)conf_dev & 15))
-        return fail(SSAL_EINVAL, "label_dev / mask_dev must be 4-byte aligned and conf_dev 16-byte aligned");
-    IcWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
-    if (!W.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)W.bytes, (long long)ws_bytes);
-    hipStream_t s = (hipStream_t)stream;
     // image-group schedule (same knob and same reasoning as ENet's run_net, ssal_api.hip): the batch runs as G chains of
     // ~n / G images on library-owned side streams, forked from / joined into the caller's stream with events
     int G = ssal::knobs().ic_groups;  // ICNet's own chain count (default 1; ENet: img_groups)
@@ -421,15 +413,71 @@ int score_any(ssal_icnet *net, const void *x_dev, bool u8, int n, int h, int w, 
     const hipError_t trunk_rc = run_trunk(net, grp, u8, h, w, true);
     set_launch_concurrency(1);
     HIP_TRY(trunk_rc);
-    for (int g = 0; g < G; ++g) {
-        const Grp &q = grp[g];
-        const int64_t i0 = first[g];
-        HIP_TRY(launch_upscore(q.A("conv6_cls"), q.n, h / 4, w / 4, net->classes, measure, threshold, q.W.partial,
-                               label_dev ? label_dev + i0 * px : nullptr, mask_dev ? mask_dev + i0 * px : nullptr,
-                               conf_dev ? conf_dev + i0 * px : nullptr, q.s));
-    }
+    for (int g = 0; g < G; ++g) HIP_TRY(tail(grp[g], first[g]));
     HIP_TRY(cs.end());
+    return SSAL_OK;
+}
+
+int score_any(ssal_icnet *net, const void *x_dev, bool u8, int n, int h, int w, int measure, float threshold,
+              double *scores_dev, uint8_t *label_dev, uint8_t *mask_dev, float *conf_dev, void *ws_dev,
+              int64_t ws_bytes, void *stream)
+{
+    int rc = check_dims(net, n, h, w);
+    if (rc) return rc;
+    if (measure < 0 || measure > 2) return fail(SSAL_ENOTIMPL, "Uncertainty function not implemented (measure=%d)", measure);
+    if (!x_dev || !scores_dev || !ws_dev) return fail(SSAL_EINVAL, "NULL device pointer");
+    if (((uintptr_t)label_dev | (uintptr_t)mask_dev) & 3 || ((uintptr_t)conf_dev & 15))
+        return fail(SSAL_EINVAL, "label_dev / mask_dev must be 4-byte aligned and conf_dev 16-byte aligned");
+    IcWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
+    if (!W.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)W.bytes, (long long)ws_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t px = (int64_t)h * w;
+    if ((rc = run_scored(net, x_dev, u8, n, h, w, W, s, [&](const Grp &q, int64_t i0) {
+            return launch_upscore(q.A("conv6_cls"), q.n, h / 4, w / 4, net->classes, measure, threshold, q.W.partial,
+                                  label_dev ? label_dev + i0 * px : nullptr, mask_dev ? mask_dev + i0 * px : nullptr,
+                                  conf_dev ? conf_dev + i0 * px : nullptr, q.s);
+        })))
+        return rc;
     HIP_TRY(launch_reduce_mean(W.partial, n, upscore_blocks(h / 4, w / 4), (double)h * (double)w, scores_dev, s));
+    return SSAL_OK;
+}
+
+// ---- evaluation pass: the score path's trunk, then conv6_interp + argmax + confusion matrix in one launch (k_upeval) ----
+int64_t conf_replica_bytes(int classes) { return (int64_t)ssal::kConfMaxReps * ssal::conf_rep_stride(classes * classes) * 8; }
+
+int64_t eval_workspace_bytes(const ssal_icnet *net, int n, int h, int w)
+{
+    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 32 || w % 32) return -1;
+    if (net->classes < 2 || net->classes > ssal::kConfMaxClasses) return -1;
+    const IcWorkspace W = carve(net, nullptr, 0, n, h, w);
+    return (W.bytes + 255) / 256 * 256 + conf_replica_bytes(net->classes) + 256;
+}
+
+int eval_any(ssal_icnet *net, const void *x_dev, bool u8, int n, int h, int w, const uint8_t *labels_dev,
+             const uint8_t *mask_dev, int64_t *confusion_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    int rc = check_dims(net, n, h, w);
+    if (rc) return rc;
+    const int K = net->classes;
+    if (K < 2 || K > ssal::kConfMaxClasses) return fail(SSAL_EINVAL, "classes must be in [2,32] (got %d)", K);
+    if (!x_dev || !labels_dev || !confusion_dev || !ws_dev) return fail(SSAL_EINVAL, "NULL device pointer");
+    if (((uintptr_t)labels_dev | (uintptr_t)mask_dev) & 3)
+        return fail(SSAL_EINVAL, "labels_dev / mask_dev must be 4-byte aligned");
+    const int64_t need = eval_workspace_bytes(net, n, h, w);
+    IcWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
+    if (!W.ok || ws_bytes < need)
+        return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need, (long long)ws_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    const int reps = ssal::knobs().conf_reps;
+    unsigned long long *rep = (unsigned long long *)((char *)ws_dev + (W.bytes + 255) / 256 * 256);
+    HIP_TRY(hipMemsetAsync(rep, 0, (size_t)reps * ssal::conf_rep_stride(K * K) * 8, s));  // before the chains fork from s
+    const int64_t px = (int64_t)h * w;
+    if ((rc = run_scored(net, x_dev, u8, n, h, w, W, s, [&](const Grp &q, int64_t i0) {
+            return launch_upeval(q.A("conv6_cls"), q.n, h / 4, w / 4, K, labels_dev + i0 * px,
+                                 mask_dev ? mask_dev + i0 * px : nullptr, rep, reps, q.s);
+        })))
+        return rc;
+    HIP_TRY(launch_confusion_fold(rep, reps, K, confusion_dev, s));
     return SSAL_OK;
 }
 
@@ -643,6 +691,19 @@ SSAL_API int ssal_icnet_score_regions_nhwc(ssal_icnet *net, const void *x_dev, i
         return rc;
     HIP_TRY(launch_region_means_plane(plane, n, h, w, rh, rw, region_scores_dev, (hipStream_t)stream));
     return SSAL_OK;
+}
+
+// ---- evaluation pass (eval_any above): ssal_enet_evaluate_nhwc_arith's contract for the ICNet handle ----
+SSAL_API int64_t ssal_icnet_eval_workspace_bytes(const ssal_icnet *net, int n, int h, int w)
+{
+    return eval_workspace_bytes(net, n, h, w);
+}
+
+SSAL_API int ssal_icnet_evaluate_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                                      const uint8_t *labels_dev, const uint8_t *mask_dev, int64_t *confusion_dev,
+                                      void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    return eval_any(net, x_dev, x_is_u8 != 0, n, h, w, labels_dev, mask_dev, confusion_dev, ws_dev, ws_bytes, stream);
 }
 
 SSAL_API int ssal_icnet_num_endpoints(const ssal_icnet *net) { return net ? (int)net->acts.size() : 0; }

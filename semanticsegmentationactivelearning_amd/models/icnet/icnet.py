@@ -10,6 +10,8 @@ in the hand-written HIP kernels of libssal_hip.so through the C ABI (``include/s
 """
 import ctypes
 
+import numpy as np
+
 from ... import _lib
 from ..enet import enet_modules as mod
 
@@ -264,11 +266,64 @@ class ICNet(_lib.DeviceState):
 
     # ---- validation pass (active_learning.py:277-282 + tensortools.metrics.Metrics :390-427) ----------------------------
     def evaluate(self, inputs, labels, mask=None, confusion=None):
-        """forward(training=False) + argmax + masked confusion matrix: ``ENet.evaluate``'s contract (int64 [K, K] device
-        tensor, row = label, column = prediction; ADDED into ``confusion`` when given).  Two steps: ``score(...,
-        return_label=True)`` writes the argmax plane (uint8, 1 B / pixel), then the device op
-        ``tensortools.metrics.confusion_mat`` counts it.  (A tail fused into the up-sampling score kernel, as ENet's is
-        into its Final kernel, is not implemented: DESIGN.md §12.)"""
+        """forward(training=False) + argmax + masked confusion matrix in one pass: ``ENet.evaluate``'s contract (int64
+        [K, K] device tensor, row = label, column = prediction; ADDED into ``confusion`` when given; a mask value is the
+        pixel's weight; labels >= K are dropped).  The up-sampling kernel counts the argmax of the full-resolution logits
+        itself (``ssal_icnet_evaluate_nhwc``): no label plane, no softmax, no second launch."""
+        from ...tensortools import metrics as _metrics
+        self._check_evaluate_shapes(inputs, labels, mask, confusion)  # host only: raised before any device work
+        torch = _lib.require_gpu()
+        x = self._prepare(inputs, False)
+        n, h, w, _ = x.shape
+        lab = _metrics._as_u8(labels, x.device, "labels")
+        msk = _metrics._as_u8(mask, x.device, "mask") if mask is not None else None
+        for name, t in (("labels", lab), ("mask", msk)):
+            if t is not None and tuple(t.shape) != (n, h, w):
+                raise ValueError("%s must have shape %s (got %s)" % (name, (n, h, w), tuple(t.shape)))
+        k = self.classes
+        if confusion is None:
+            confusion = torch.zeros((k, k), dtype=torch.int64, device=x.device)
+        elif (confusion.dtype != torch.int64 or tuple(confusion.shape) != (k, k) or confusion.device != x.device
+              or not confusion.is_contiguous()):
+            raise ValueError("confusion must be a contiguous int64 [%d, %d] tensor on %s" % (k, k, x.device))
+        L = _lib.lib()
+        with torch.cuda.device(x.device):
+            handle = self._sync_handle()
+            nbytes = L.ssal_icnet_eval_workspace_bytes(handle, n, h, w)
+            if nbytes < 0:
+                raise ValueError("bad input dims %s" % (tuple(x.shape),))
+            ws = self._workspace(nbytes, x.device)
+            _lib.check(L.ssal_icnet_evaluate_nhwc(
+                handle, _lib.dev_ptr(x), int(x.dtype == torch.uint8), n, h, w, _lib.dev_ptr(lab), _lib.dev_ptr(msk),
+                _lib.dev_ptr(confusion), _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))
+            self._note_call(ws, (n, h, w), "score")
+        return confusion
+
+    def _check_evaluate_shapes(self, inputs, labels, mask, confusion):
+        """the refusals of ``evaluate`` that shapes and dtypes alone decide (the messages of ``_prepare`` and of the checks
+        that follow it), judged on the host so that a bad call never reaches the device"""
+        def shape_of(t):
+            return tuple(t.shape) if hasattr(t, "shape") else np.shape(t)
+
+        shp = shape_of(inputs)
+        if len(shp) != 4:
+            raise ValueError("inputs must be NHWC rank-4 (got shape %s)" % (shp,))
+        if self.built and shp[-1] != self._c_in:
+            raise ValueError("model was built for %d input channels, got %d" % (self._c_in, shp[-1]))
+        if shp[1] % 32 or shp[2] % 32:
+            raise ValueError("ICNet needs H and W divisible by 32 (got %dx%d)" % (shp[1], shp[2]))
+        for name, t in (("labels", labels), ("mask", mask)):
+            if t is not None and shape_of(t) != shp[:3]:
+                raise ValueError("%s must have shape %s (got %s)" % (name, shp[:3], shape_of(t)))
+        if confusion is not None:
+            k = self.classes
+            if str(getattr(confusion, "dtype", None)) != "torch.int64" or shape_of(confusion) != (k, k):
+                raise ValueError("confusion must be a contiguous int64 [%d, %d] tensor on the input's device" % (k, k))
+
+    def _evaluate_composed(self, inputs, labels, mask=None, confusion=None):
+        """``evaluate`` in two steps, the route it took before the fused kernel: ``score(..., return_label=True)`` writes
+        the argmax plane (uint8, 1 B / pixel), then ``tensortools.metrics.confusion_mat`` counts it.  Kept as the reference
+        of the tests and of tools/icnet_eval_bench.py."""
         from ...tensortools import metrics as _metrics
         _, extra = self.score(inputs, measure="confidence", return_label=True)
         pred = extra["label"]
