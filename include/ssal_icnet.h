@@ -150,6 +150,37 @@ int ssal_icnet_train_head_semi_nhwc(ssal_icnet *net, const void *x_dev, const vo
  * ssal_icnet_commit no call may be in flight on the handle on another stream. */
 int ssal_icnet_update_head(ssal_icnet *net, const float *kernel_host, const float *bias_host, void *stream);
 
+/* ---- Training of the last fusion stage: sub12_sum = relu(BN(conv_sub2(resize_bilinear(sub24_sum,
+ * 2x))) + BN(conv3_sub1_proj(conv3_sub1))) and conv6_cls over a trunk frozen below them ----
+ * The eight trained variables travel PACKED, in this order: conv_sub2.kernel [3,3,128,128] | .gamma [128] | .beta [128] |
+ * conv3_sub1_proj.kernel [1,1,64,128] | .gamma [128] | .beta [128] | conv6_cls.kernel [1,1,128,classes] | .bias [classes]
+ * (156160 + 129 * classes floats); params_dev and grad_dev have that layout.  Batch-norm is inference-mode: stats_dev
+ * [4 * 128] = conv_sub2 mean | variance | conv3_sub1_proj mean | variance stay frozen, scale = gamma / sqrtf(variance + 1e-3f)
+ * and shift = fmaf(-mean, scale, beta) are folded on the device as ssal_icnet_commit folds them.  One call computes, for
+ * sub24_sum [n,h,w,128] (1/16 resolution), conv3_sub1 [n,2h,2w,64], labels uint8 and mask fp32 [n,16h,16w]: sub12_sum and lq
+ * by the forward path's own launches on params_dev, the loss of ssal_icnet_head_grad_nhwc -> loss_dev [1] float64, and the
+ * gradient of all eight variables -> grad_dev (without the regulariser).  Nothing below the block gets a gradient.  The
+ * conv6_cls part of grad_dev and the loss are the bits ssal_icnet_head_grad_nhwc gives on the same sub12_sum.  max_workgroups:
+ * 0 = the default grids, a tuning knob (>= 0).  No floating-point atomics: two calls give the same bits.  Statuses as
+ * ssal_icnet_head_grad_nhwc's (the _workspace_bytes query returns -1 for a map beyond the kernels' limit). */
+int64_t ssal_icnet_fusion_grad_workspace_bytes(int n, int h, int w, int classes);
+int ssal_icnet_fusion_grad_nhwc(const float *sub24_dev, const float *conv3_sub1_dev, int n, int h, int w, int classes,
+                                const float *params_dev, const uint8_t *labels_dev, const float *mask_dev, float weight,
+                                float label_smoothing, const float *stats_dev, int max_workgroups, double *loss_dev,
+                                float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream);
+/* the same from frames x_dev [n,h,w,c_in] (fp32, or uint8 when x_is_u8 != 0): the frozen trunk up to sub24_sum and
+ * conv3_sub1 on the caller's stream (the score path's fused launches), then the tail above; labels / mask [n,h,w].  After the
+ * call the conv3_sub1_proj, sub12_sum and conv6_cls endpoints are those of params_dev. */
+int64_t ssal_icnet_train_fusion_workspace_bytes(const ssal_icnet *net, int n, int h, int w);
+int ssal_icnet_train_fusion_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                                 const uint8_t *labels_dev, const float *mask_dev, const float *params_dev, float weight,
+                                 float label_smoothing, const float *stats_dev, int max_workgroups, double *loss_dev,
+                                 float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream);
+/* replaces the eight trained variables (params_host: the packed vector, a host array) of a COMMITTED handle in place: only
+ * conv_sub2, conv3_sub1_proj and conv6_cls are re-laid-out, folded with the handle's moving statistics and uploaded (0.7 MB),
+ * the handle stays committed.  Synchronises the stream; as with ssal_icnet_commit no call may be in flight on the handle. */
+int ssal_icnet_update_fusion(ssal_icnet *net, const float *params_host, void *stream);
+
 /* Stand-alone fused convolution (the operator every ICNet layer is built from; also the per-block parity hook):
  * y = [relu]( BN(conv2d(x, kernel HWIO, strides s, dilations d, "SAME")) [+ res] ), BN given as mean / variance /
  * gamma / beta (all NULL: no batch-norm; bias_dev optional).  upsample2x != 0 runs the conv on

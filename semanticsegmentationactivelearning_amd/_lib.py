@@ -182,6 +182,12 @@ PROTOTYPES = {
     "ssal_icnet_train_head_semi_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _f, _f, _i, _vp,
                                              _vp, _vp, _vp, _vp, _i64, _vp]),
     "ssal_icnet_update_head": (_i, [_vp, _vp, _vp, _vp]),
+    # ---- training of ICNet's last fusion stage (include/ssal_icnet.h) ----
+    "ssal_icnet_fusion_grad_workspace_bytes": (_i64, [_i, _i, _i, _i]),
+    "ssal_icnet_fusion_grad_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_icnet_train_fusion_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
+    "ssal_icnet_train_fusion_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_icnet_update_fusion": (_i, [_vp, _vp, _vp]),
     # ---- PNG decode (include/ssal_enet.h) ----
     "ssal_png_plan": (_i64, [_i64, _vp]),
     "ssal_png_decode_nhwc": (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),

@@ -8,6 +8,7 @@
 #include "ssal_internal.h"
 #include "ssal_prof.h"
 #include "ssal_train_icnet.h"
+#include "ssal_train_icnet_fusion.h"
 
 #include <math.h>
 
@@ -243,8 +244,9 @@ struct Grp {
 // collected instead (ssal_icnet_endpoint_valid_after_score: the one place that knows which layer outputs a fused launch
 // swallows is the schedule itself)
 // head = false: the schedule ends at sub12_sum (the output-layer trainer runs conv6_cls on the weights it trains)
+// fusion = false (with head = false): it ends at sub24_sum and conv3_sub1 (the fusion trainer runs the last fusion block too)
 hipError_t run_trunk(const ssal_icnet *net, std::vector<Grp> &grp, bool x_is_u8, int h, int w, bool fused,
-                     std::set<std::string> *written = nullptr, bool head = true)
+                     std::set<std::string> *written = nullptr, bool head = true, bool fusion = true)
 {
     const bool dry = written != nullptr;
 #define OUT(name) do { if (dry) written->insert(name); } while (0)
@@ -345,7 +347,8 @@ hipError_t run_trunk(const ssal_icnet *net, std::vector<Grp> &grp, bool x_is_u8,
         EACH(launch_conv_first(q.x, x_is_u8, q.n, h, w, net->c_in, 1, c.w, c.scale, c.shift, q.A("conv1_sub1"), q.s));
         EACH(run_conv(net, "conv2_sub1", q.A("conv1_sub1"), q.n, h / 2, w / 2, nullptr, true, false, q.A("conv2_sub1"), q.s));
     }
-    for (const char *nm_ : {"conv3_sub1", "conv3_1_sub2_proj", "sub24_sum", "conv3_sub1_proj", "sub12_sum"}) OUT(nm_);
+    for (const char *nm_ : {"conv3_sub1", "conv3_1_sub2_proj", "sub24_sum"}) OUT(nm_);
+    if (fusion) for (const char *nm_ : {"conv3_sub1_proj", "sub12_sum"}) OUT(nm_);
     if (head) OUT("conv6_cls");
     EACH(run_conv(net, "conv3_sub1", q.A("conv2_sub1"), q.n, h / 4, w / 4, nullptr, true, false, q.A("conv3_sub1"), q.s));
     // ---- cascade feature fusion (section 4): the 2x interpolations are evaluated inside the dilated convs ----
@@ -353,10 +356,12 @@ hipError_t run_trunk(const ssal_icnet *net, std::vector<Grp> &grp, bool x_is_u8,
                   q.A("conv3_1_sub2_proj"), q.s));
     EACH(run_conv(net, "conv_sub4", q.A("conv5_4_k1"), q.n, h / 32, w / 32, q.A("conv3_1_sub2_proj"), true, true,
                   q.A("sub24_sum"), q.s));
-    EACH(run_conv(net, "conv3_sub1_proj", q.A("conv3_sub1"), q.n, h / 8, w / 8, nullptr, false, false,
-                  q.A("conv3_sub1_proj"), q.s));
-    EACH(run_conv(net, "conv_sub2", q.A("sub24_sum"), q.n, h / 16, w / 16, q.A("conv3_sub1_proj"), true, true,
-                  q.A("sub12_sum"), q.s));
+    if (fusion) {
+        EACH(run_conv(net, "conv3_sub1_proj", q.A("conv3_sub1"), q.n, h / 8, w / 8, nullptr, false, false,
+                      q.A("conv3_sub1_proj"), q.s));
+        EACH(run_conv(net, "conv_sub2", q.A("sub24_sum"), q.n, h / 16, w / 16, q.A("conv3_sub1_proj"), true, true,
+                      q.A("sub12_sum"), q.s));
+    }
     // sub12_sum_interp (2x) + conv6_cls (1x1, bias)
     if (head) EACH(run_conv(net, "conv6_cls", q.A("sub12_sum"), q.n, h / 8, w / 8, nullptr, false, true, q.A("conv6_cls"), q.s));
 #undef EACH
@@ -1002,6 +1007,160 @@ SSAL_API int ssal_icnet_update_head(ssal_icnet *net, const float *kernel_host, c
     HIP_TRY(hipMemcpyAsync(const_cast<float *>(c.scale), sc.data(), sc.size() * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(const_cast<float *>(c.shift), sh.data(), sh.size() * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));  // the staging vectors die at return
+    return SSAL_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// training of the last fusion stage (kernels: ssal_train_icnet_fusion.hip)
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+// the buffers of one gradient call behind `b`; own_acts: proj / sub12_sum / lq live here (the images entry keeps them in the
+// network's conv3_sub1_proj / sub12_sum / conv6_cls endpoints instead)
+IcnetFusionWs fusion_carve(Bump &b, int64_t n, int h16, int w16, int classes, bool own_acts)
+{
+    IcnetFusionWs t;
+    const int h8 = 2 * h16, w8 = 2 * w16;
+    const int64_t act = n * h8 * (int64_t)w8 * 128;
+    t.wt_a = b.take<float>(FU_GA);
+    t.wt_b = b.take<float>(64 * 128);
+    t.rows = b.take<float>(512);
+    t.proj = own_acts ? b.take<float>(act) : nullptr;
+    t.sub12 = own_acts ? b.take<float>(act) : nullptr;
+    t.g = b.take<float>(act);
+    t.hw = b.take<float>(n * icnet_head_tiles(h8, w8) * 36 * classes);
+    t.part = b.take<float>((int64_t)FU_MAX_WG * FU_PART);  // (sized for the default grid: max_workgroups only lowers it)
+    t.fold = b.take<float>(FU_PART + 64);
+    t.head = head_carve(b, n, h8, w8, classes, own_acts);
+    return t;
+}
+
+bool fusion_dims_ok(int n, int h16, int w16, int classes)
+{
+    return n > 0 && classes >= 2 && classes <= 32 && icnet_fusion_fits(h16, w16) && (double)n * h16 * w16 <= 274877906944.0;
+}
+
+int fusion_check(int n, int h16, int w16, int classes, int max_workgroups)
+{
+    if (n <= 0) return fail(SSAL_EINVAL, "bad dims n=%d h=%d w=%d", n, h16, w16);
+    if (classes < 2 || classes > 32) return fail(SSAL_EINVAL, "classes must be in [2,32] (got %d)", classes);
+    if (max_workgroups < 0) return fail(SSAL_EINVAL, "max_workgroups must be >= 0 (got %d)", max_workgroups);
+    if (!fusion_dims_ok(n, h16, w16, classes))
+        return fail(SSAL_EINVAL, "feature map %dx%d (n=%d) is beyond the fusion gradient kernels' limit", h16, w16, n);
+    return SSAL_OK;
+}
+
+}  // namespace
+
+SSAL_API int64_t ssal_icnet_fusion_grad_workspace_bytes(int n, int h, int w, int classes)
+{
+    if (!fusion_dims_ok(n, h, w, classes)) return -1;
+    Bump b(nullptr, 0);
+    (void)fusion_carve(b, n, h, w, classes, true);
+    return b.off + 256;
+}
+
+SSAL_API int ssal_icnet_fusion_grad_nhwc(const float *sub24_dev, const float *conv3_sub1_dev, int n, int h, int w, int classes,
+                                         const float *params_dev, const uint8_t *labels_dev, const float *mask_dev,
+                                         float weight, float label_smoothing, const float *stats_dev, int max_workgroups,
+                                         double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    int rc = fusion_check(n, h, w, classes, max_workgroups);
+    if (rc) return rc;
+    if (!sub24_dev || !conv3_sub1_dev || !params_dev || !stats_dev || !labels_dev || !mask_dev || !loss_dev || !grad_dev ||
+        !ws_dev)
+        return fail(SSAL_EINVAL, "NULL device pointer");
+    Bump b(ws_dev, ws_bytes);
+    const IcnetFusionWs t = fusion_carve(b, n, h, w, classes, true);
+    if (!b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
+                           (long long)ssal_icnet_fusion_grad_workspace_bytes(n, h, w, classes), (long long)ws_bytes);
+    HIP_TRY(launch_icnet_fusion_grad(sub24_dev, conv3_sub1_dev, n, h, w, classes, params_dev, stats_dev, labels_dev, mask_dev,
+                                     weight, label_smoothing, max_workgroups, t, loss_dev, grad_dev, (hipStream_t)stream));
+    return SSAL_OK;
+}
+
+SSAL_API int64_t ssal_icnet_train_fusion_workspace_bytes(const ssal_icnet *net, int n, int h, int w)
+{
+    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 32 || w % 32) return -1;
+    Bump b(nullptr, 0);
+    b.off = carve(net, nullptr, 0, n, h, w).bytes;
+    (void)fusion_carve(b, n, h / 16, w / 16, net->classes, false);
+    return b.off + 256;
+}
+
+SSAL_API int ssal_icnet_train_fusion_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                                          const uint8_t *labels_dev, const float *mask_dev, const float *params_dev,
+                                          float weight, float label_smoothing, const float *stats_dev, int max_workgroups,
+                                          double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    int rc = check_dims(net, n, h, w);
+    if (rc) return rc;
+    if ((rc = fusion_check(n, h / 16, w / 16, net->classes, max_workgroups))) return rc;
+    if (!x_dev || !params_dev || !stats_dev || !labels_dev || !mask_dev || !loss_dev || !grad_dev || !ws_dev)
+        return fail(SSAL_EINVAL, "NULL device pointer");
+    IcWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
+    Bump b(ws_dev, ws_bytes);
+    b.off = W.bytes;
+    IcnetFusionWs t = fusion_carve(b, n, h / 16, w / 16, net->classes, false);
+    if (!W.ok || !b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
+                                    (long long)ssal_icnet_train_fusion_workspace_bytes(net, n, h, w), (long long)ws_bytes);
+    // the block and the head being trained write this call's conv3_sub1_proj, sub12_sum and conv6_cls endpoints
+    t.proj = W.act.at("conv3_sub1_proj");
+    t.sub12 = W.act.at("sub12_sum");
+    t.head.lq = W.act.at("conv6_cls");
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<Grp> one(1);
+    one[0] = {W, x_dev, n, s};
+    HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false, false));
+    HIP_TRY(launch_icnet_fusion_grad(W.act.at("sub24_sum"), W.act.at("conv3_sub1"), n, h / 16, w / 16, net->classes, params_dev,
+                                     stats_dev, labels_dev, mask_dev, weight, label_smoothing, max_workgroups, t, loss_dev,
+                                     grad_dev, s));
+    return SSAL_OK;
+}
+
+SSAL_API int ssal_icnet_update_fusion(ssal_icnet *net, const float *params_host, void *stream)
+{
+    if (!net || !params_host) return fail(SSAL_EINVAL, "NULL argument");
+    if (!net->committed) return fail(SSAL_ESTATE, "ssal_icnet_commit() has not been called");
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != net->device)
+        return fail(SSAL_ESTATE, "the handle was committed on device %d but the current device is %d (one handle per device)",
+                    net->device, dev);
+    const int K = net->classes;
+    auto put = [&](const std::string &name, int off, size_t count) {
+        net->tensors[net->index.at(name)].data.assign(params_host + off, params_host + off + count);
+    };
+    put("conv_sub2.kernel", FU_KA, FU_GA);
+    put("conv_sub2.gamma", FU_GA, 128);
+    put("conv_sub2.beta", FU_BA, 128);
+    put("conv3_sub1_proj.kernel", FU_KB, 64 * 128);
+    put("conv3_sub1_proj.gamma", FU_GB, 128);
+    put("conv3_sub1_proj.beta", FU_BB, 128);
+    put("conv6_cls.kernel", FU_HEAD, 128 * (size_t)K);
+    put("conv6_cls.bias", FU_HEAD + 128 * K, K);
+    hipStream_t s = (hipStream_t)stream;
+    // the staging vectors live until the synchronisation below
+    std::vector<std::vector<float>> keep;
+    for (const ConvSpec &sp : net->specs) {
+        if (sp.name != "conv_sub2" && sp.name != "conv3_sub1_proj" && sp.name != "conv6_cls") continue;
+        std::vector<float> wt(igemm_relayout_floats(sp.k, sp.k, sp.cin, sp.cout)), sc, sh;
+        igemm_relayout(T(net, sp.name + ".kernel").data(), sp.k, sp.k, sp.cin, sp.cout, wt.data());
+        if (sp.bn)
+            fold_bn_padded(T(net, sp.name + ".mean").data(), T(net, sp.name + ".variance").data(),
+                           T(net, sp.name + ".gamma").data(), T(net, sp.name + ".beta").data(), nullptr, sp.cout, sc, sh);
+        else
+            fold_bn_padded(nullptr, nullptr, nullptr, nullptr, T(net, sp.name + ".bias").data(), sp.cout, sc, sh);
+        const ConvDev &c = net->convs.at(sp.name);
+        const float *dst[3] = {c.w, c.scale, c.shift};
+        keep.push_back(std::move(wt));
+        keep.push_back(std::move(sc));
+        keep.push_back(std::move(sh));
+        for (int i = 0; i < 3; ++i) {
+            const std::vector<float> &src = keep[keep.size() - 3 + i];
+            HIP_TRY(hipMemcpyAsync(const_cast<float *>(dst[i]), src.data(), src.size() * 4, hipMemcpyHostToDevice, s));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(s));
     return SSAL_OK;
 }
 

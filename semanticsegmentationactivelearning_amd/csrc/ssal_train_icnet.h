@@ -28,6 +28,7 @@ struct IcnetHeadWs {
     double *lpart;   // [G][2]
 };
 int64_t icnet_head_ws_floats_wt();  // 4 * 32 * 32 + 64
+int64_t icnet_head_tiles(int h8, int w8);  // tiles of the gradient kernel per image
 
 // conv6_cls/Kernel + Bias (packed head on the device) -> wt / scale / shift as ssal_icnet_commit lays them out
 hipError_t launch_icnet_head_pack(const float *head, int K, float *wt, hipStream_t s);
@@ -47,10 +48,12 @@ struct IcnetHeadSemi {
 
 // The whole tail: lq = conv6_cls(resize_2x(sub12_sum)) through launch_igemm (the forward path's own launch, reading the
 // packed head), then the fused loss + gradient kernel and the fold.  loss [1] float64; grad [128 K + K] fp32.
+// hw_out (never with semi; NULL = not written): [N][icnet_head_tiles][36][K], every tile's pull-back of dL/dlq onto its
+// 6 x 6 window of sub12_sum (first pixel (4 ty, 4 tx)), un-normalised; a window pixel two tiles share holds each one's part.
 hipError_t launch_icnet_head_grad(const float *sub12, int N, int h8, int w8, int K, const float *head,
                                   const uint8_t *labels, const float *mask, float weight, float label_smoothing,
                                   int max_workgroups, const IcnetHeadWs &ws, double *loss, float *grad, hipStream_t s,
-                                  const IcnetHeadSemi *semi = nullptr);
+                                  const IcnetHeadSemi *semi = nullptr, float *hw_out = nullptr);
 
 // The target-only launch on the features of the undistorted frames: packs the head, lq = conv6_cls(resize_2x(sub12_raw))
 // into ws.lq, then one packed byte per loss pixel of the unlabelled images -> tgt [N, 8 h8, 8 w8].  Nothing else is

@@ -44,6 +44,8 @@ int icnet_head_workgroups(int h8, int w8, int max_workgroups)
 
 int64_t icnet_head_ws_floats_wt() { return 4 * 32 * 32 + 64; }
 
+int64_t icnet_head_tiles(int h8, int w8) { return (int64_t)((2 * h8 + IH_T - 1) / IH_T) * ((2 * w8 + IH_T - 1) / IH_T); }
+
 // wt [128 / 32][32][32] as igemm_relayout writes a 1 x 1 x 128 x K kernel (rows co >= K zero), scale (1 / 0), shift (bias / 0)
 __global__ __launch_bounds__(256) void k_icnet_head_pack(const float *__restrict__ head, int K, float *__restrict__ wt)
 {
@@ -108,15 +110,21 @@ __device__ __forceinline__ float resize_weight(int dst, int src, int size, int f
 // into replica (workgroup % reps) at the end; a loss pixel belongs to exactly one tile.  sa.pseudo_pixels[n] += the image's
 // pixels with pseudo mask 1 (one integer atomic per wave, tile and unlabelled image).
 struct IcnetHeadPlain {};  // SEMI = false: no argument
+// HWOUT (never with SEMI): every tile also leaves its pull-back window hw [36][K] as it stands --
+// partial sums where the window overlaps a neighbouring tile's -- at hw[(n tiles + tile) 36 K], for the fusion trainer's
+// gather into dL/dsub12_sum.  Nothing else changes: loss, dKernel and dBias are the bits of the plain instantiation.
+struct IcnetHeadHw { float *hw; };
 
-template <int K, bool SEMI>
+template <int K, bool SEMI, bool HWOUT = false>
 __global__ __launch_bounds__(256) void k_icnet_head_grad(const float *__restrict__ x, const float *__restrict__ lq, int N,
                                                          int h8, int w8, const uint8_t *__restrict__ labels,
                                                          const float *__restrict__ mask, float weight, float on_value,
                                                          float off_value, float *__restrict__ part,
                                                          double *__restrict__ lpart,
-                                                         std::conditional_t<SEMI, IcnetHeadSemi, IcnetHeadPlain> sa)
+                                                         std::conditional_t<SEMI, IcnetHeadSemi,
+                                                                            std::conditional_t<HWOUT, IcnetHeadHw, IcnetHeadPlain>> sa)
 {
+    static_assert(!(SEMI && HWOUT), "the window output belongs to the plain step");
     constexpr int K4 = (K + 3) / 4 * 4, KB = K4 / 4;
     constexpr int KLD = K4 % 8 == 0 ? K4 + 4 : K4;  // row stride of the LDS planes: quads of neighbouring rows on other banks
     constexpr int BIG = 256 * KLD > IH_SP * (128 + KLD) ? 256 * KLD : IH_SP * (128 + KLD);
@@ -321,6 +329,10 @@ __global__ __launch_bounds__(256) void k_icnet_head_grad(const float *__restrict
                 *reinterpret_cast<float4 *>(hw + p * KLD + 4 * kb) = a;
             }
             __syncthreads();
+            if constexpr (HWOUT) {
+                float *dst = sa.hw + ((long)n * tiles + t) * (IH_SP * K);
+                for (int e = tid; e < IH_SP * K; e += 256) dst[e] = hw[(e / K) * KLD + e % K];
+            }
             if (tid < 32 * KB) {
                 const float4 *f4 = reinterpret_cast<const float4 *>(xw) + cb;
                 const float *hp = hw + 4 * kbc;
@@ -456,8 +468,9 @@ hipError_t launch_icnet_head_targets(const float *sub12_raw, int N, int h8, int 
 hipError_t launch_icnet_head_grad(const float *sub12, int N, int h8, int w8, int K, const float *head,
                                   const uint8_t *labels, const float *mask, float weight, float label_smoothing,
                                   int max_workgroups, const IcnetHeadWs &ws, double *loss, float *grad, hipStream_t s,
-                                  const IcnetHeadSemi *semi)
+                                  const IcnetHeadSemi *semi, float *hw_out)
 {
+    if (semi && hw_out) return hipErrorInvalidValue;
     if (N < 1 || K < 2 || K > 32 || max_workgroups < 0 || !icnet_head_fits(h8, w8) || !icnet_head_semi_ok(semi))
         return hipErrorInvalidValue;
     const int G = icnet_head_workgroups(h8, w8, max_workgroups);
@@ -474,7 +487,24 @@ hipError_t launch_icnet_head_grad(const float *sub12, int N, int h8, int w8, int
     if (e != hipSuccess) return e;
     const float on_value = 1.0f - label_smoothing, off_value = label_smoothing / ((float)K - 1.0f);
     const double pix = (double)N * h8 * w8;
-    if (!semi) {
+    if (hw_out) {
+        ProfScope prof("k_icnet_head_grad_hw", 64.0 * pix * 12.0 * K + 2.0 * pix * 128 * K,
+                       4.0 * pix * 128 + 4.0 * 4 * pix * K + 64.0 * pix * (1 + 4) + 4.0 * G * 129.0 * K +
+                           4.0 * N * icnet_head_tiles(h8, w8) * IH_SP * K, s);
+#define SSAL_IH(KK)                                                                                                    \
+    case KK:                                                                                                           \
+        hipLaunchKernelGGL((k_icnet_head_grad<KK, false, true>), dim3(G), dim3(256), 0, s, sub12, ws.lq, N, h8, w8,     \
+                           labels, mask, weight, on_value, off_value, ws.part, ws.lpart, IcnetHeadHw{hw_out});         \
+        break;
+        switch (K) {
+            SSAL_IH_CASES
+        default:
+            return hipErrorInvalidValue;
+        }
+#undef SSAL_IH
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    } else if (!semi) {
         ProfScope prof("k_icnet_head_grad", 64.0 * pix * 12.0 * K + 2.0 * pix * 128 * K,
                        4.0 * pix * 128 + 4.0 * 4 * pix * K + 64.0 * pix * (1 + 4) + 4.0 * G * 129.0 * K, s);
 #define SSAL_IH(KK)                                                                                                    \

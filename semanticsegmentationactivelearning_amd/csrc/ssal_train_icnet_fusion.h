@@ -1,0 +1,49 @@
+// ssal_train_icnet_fusion.h -- training of ICNet's last cascade-feature-fusion block together with the output layer over a
+// frozen trunk: sub12_sum = relu(BN(conv_sub2(resize_2x(sub24_sum))) + BN(conv3_sub1_proj(conv3_sub1))), conv6_cls
+// (ssal_train_icnet_fusion.hip).  gfx950 (MI355X / CDNA4) only.  All tensors fp32 NHWC.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "ssal_train_icnet.h"
+
+namespace ssal {
+
+// The packed vector everything here takes and gives (float offsets):
+//   conv_sub2.kernel [3,3,128,128] | .gamma [128] | .beta [128] | conv3_sub1_proj.kernel [1,1,64,128] | .gamma | .beta |
+//   conv6_cls.kernel [1,1,128,K] | conv6_cls.bias [K]
+constexpr int FU_KA = 0, FU_GA = 9 * 128 * 128, FU_BA = FU_GA + 128, FU_KB = FU_BA + 128, FU_GB = FU_KB + 64 * 128,
+              FU_BB = FU_GB + 128, FU_HEAD = FU_BB + 128;
+inline int64_t icnet_fusion_floats(int K) { return FU_HEAD + icnet_head_floats(K); }
+// the frozen moving statistics travel next to it: conv_sub2 mean | variance | conv3_sub1_proj mean | variance
+constexpr int FU_STATS = 4 * 128;
+
+// Geometry: sub24_sum [N, h16, w16, 128], conv3_sub1 [N, h8, w8, 64] with h8 = 2 h16, w8 = 2 w16; the loss is taken on
+// [N, 8 h8, 8 w8].  The weight-gradient kernel walks tiles of FU_TH x FU_TW pixels of sub12_sum.
+constexpr int FU_TH = 4, FU_TW = 8;
+constexpr int FU_TAPS = 10;                      // the nine dilated taps, then the 1 x 1 branch (+ the row of ones: dBeta)
+constexpr int FU_PART = FU_TAPS * 128 * 128;     // floats of one split-K partial: [tap][ci][co]
+constexpr int FU_MAX_WG = 96;                    // split-K groups the finish kernel folds (x FU_TAPS workgroups)
+bool icnet_fusion_fits(int h16, int w16);
+int icnet_fusion_workgroups(int n, int h16, int w16, int max_workgroups);
+
+struct IcnetFusionWs {
+    float *wt_a;    // conv_sub2's kernel in igemm_relayout's layout [9][4][128][32]
+    float *wt_b;    // conv3_sub1_proj's [1][2][128][32]
+    float *rows;    // scale_a | shift_a | scale_b | shift_b (128 each)
+    float *proj;    // [N, h8, w8, 128]   BN(conv3_sub1_proj(conv3_sub1))
+    float *sub12;   // [N, h8, w8, 128]
+    float *g;       // [N, h8, w8, 128]   un-normalised dL/dsub12_sum behind the ReLU
+    float *hw;      // [N][icnet_head_tiles][36][K]
+    float *part;    // [G][FU_PART]
+    float *fold;    // [FU_PART] the folded partials, then the scale 1 / sum(mask)
+    IcnetHeadWs head;
+};
+
+// loss [1] float64; grad [icnet_fusion_floats(K)] fp32 in the packed order
+hipError_t launch_icnet_fusion_grad(const float *sub24, const float *c3, int N, int h16, int w16, int K, const float *params,
+                                    const float *stats, const uint8_t *labels, const float *mask, float weight,
+                                    float label_smoothing, int max_workgroups, const IcnetFusionWs &ws, double *loss,
+                                    float *grad, hipStream_t s);
+
+}  // namespace ssal

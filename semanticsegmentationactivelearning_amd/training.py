@@ -1305,6 +1305,208 @@ class SemiSupervisedICNetHeadTrainer(_SemiKeywords, ICNetHeadTrainer):
         return self._step_images(images, images_raw, labels, mask, semi, confusion, return_pseudo_pixels, (mw,))
 
 
+# ---- ICNet's last fusion stage: conv_sub2 + conv3_sub1_proj + conv6_cls over a frozen trunk -------------
+# (layer, attribute, regularised) of the packed vector, in packed order
+_FUSION_VARS = (("conv_sub2", "kernel", True), ("conv_sub2", "gamma", False), ("conv_sub2", "beta", False),
+                ("conv3_sub1_proj", "kernel", True), ("conv3_sub1_proj", "gamma", False), ("conv3_sub1_proj", "beta", False),
+                (_HEAD, "kernel", True), (_HEAD, "bias", False))
+_FUSION_NAMES = tuple("%s.%s" % (layer, attr) for layer, attr, _ in _FUSION_VARS)
+_FUSION_STATS = (("conv_sub2", "mean"), ("conv_sub2", "variance"), ("conv3_sub1_proj", "mean"), ("conv3_sub1_proj", "variance"))
+
+
+class ICNetFusionTrainer(ICNetHeadTrainer):
+    """Adam on ICNet's last cascade-feature-fusion block and its output layer: ``sub12_sum = relu(BN(conv_sub2(resize_2x(
+    sub24_sum))) + BN(conv3_sub1_proj(conv3_sub1)))`` (ICNET_SPEC section 4) and ``conv6_cls``, over a trunk frozen below
+    them (``training=False`` up to ``sub24_sum`` [N, H/16, W/16, 128] and ``conv3_sub1`` [N, H/8, W/8, 64]; nothing below
+    the block gets a gradient).  Batch-norm is inference-mode: ``gamma`` and ``beta`` are trained, the moving mean and
+    variance stay frozen.  Hyper-parameters, ``from_params``, Adam, the beta powers and the learning-rate decay are the
+    parent's; the Keras ``l1_l2`` regulariser goes to the three kernels only.
+
+    The eight variables travel as one packed float32 vector in the order of ``variable_names``; ``gradient_features``
+    returns and ``state`` / ``load_state`` use a dict keyed by those names.  The semi-supervised keywords,
+    ``softmax.multiscale`` and ``weight_reg.glorot_scaling`` are refused."""
+
+    _semi_keywords = False
+    _C_FEATURES = ("ssal_icnet_fusion_grad", None)
+    _C_IMAGES = ("ssal_icnet_train_fusion", None)
+    _CHANNELS, _UP = 128, 16
+    _LIMIT = ("kernels'", "kernels'")
+    variable_names = list(_FUSION_NAMES)
+
+    # ---- the packed vector ---------------------------------------------------------------------------------------------------
+    def _vars(self):
+        if not self.net.built:
+            raise RuntimeError("build the model (call it once, or .build(input_shape)) before training")
+        return tuple(getattr(getattr(self.net, layer), attr) for layer, attr, _ in _FUSION_VARS)
+
+    def _offsets(self):
+        """(lo, hi) of every variable in the packed vector"""
+        out, lo = [], 0
+        for var in self._vars():
+            size = int(np.prod(var.shape))
+            out.append((lo, lo + size))
+            lo += size
+        return out
+
+    def _floats(self):
+        return self._offsets()[-1][1]
+
+    def _pack(self, arrays=None):
+        out = np.zeros(self._floats(), np.float32)
+        for name, var, (lo, hi) in zip(_FUSION_NAMES, self._vars(), self._offsets()):
+            a = var.numpy() if arrays is None else arrays[name]
+            a = np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a, dtype=np.float32)
+            if a.shape != tuple(var.shape):
+                raise ValueError("%s must have shape %s (got %s)" % (name, tuple(var.shape), a.shape))
+            out[lo:hi] = a.reshape(-1)
+        return out
+
+    def _unpack(self, packed):
+        return {name: packed[lo:hi].reshape(tuple(var.shape))
+                for name, var, (lo, hi) in zip(_FUSION_NAMES, self._vars(), self._offsets())}
+
+    def _kernel_var(self):
+        return getattr(self.net, _HEAD).kernel  # what ``reinitialize`` re-draws
+
+    def _zero_state(self):
+        return np.zeros(self._floats(), np.float32)
+
+    def _adam_ranges(self):
+        return tuple((lo, hi, reg) for (lo, hi), (_, _, reg) in zip(self._offsets(), _FUSION_VARS))
+
+    def _stats(self, device):
+        """the frozen moving statistics [4 * 128] on the device (pushed again only when one of them changed)"""
+        torch = _lib.require_gpu()
+        stat_vars = [getattr(getattr(self.net, layer), attr) for layer, attr in _FUSION_STATS]
+        key = (device, tuple(v.version for v in stat_vars))
+        if getattr(self, "_stats_dev", None) is None or self._stats_dev[0] != key:
+            host = np.concatenate([np.asarray(v.numpy(), np.float32).reshape(-1) for v in stat_vars])
+            self._stats_dev = (key, torch.from_numpy(host).to(device))
+        return self._stats_dev[1]
+
+    # ---- the handle: the trained variables are not a tail of ``net.variables`` ---------------------------------------------------
+    def _frozen_versions(self, versions):
+        """of a ``net.variables``-ordered version tuple, the entries of the variables that are NOT trained"""
+        trained = {id(v) for v in self._vars()}
+        return tuple(ver for var, ver in zip(self.net.variables, versions) if id(var) not in trained)
+
+    def _handle_reusable(self, ent, versions):
+        """a handle entry ``[handle, pushed versions]`` holds every frozen variable as ``versions`` has it"""
+        return (ent is not None and ent[1] is not None and len(ent[1]) == len(versions)
+                and self._frozen_versions(ent[1]) == self._frozen_versions(versions))
+
+    def _trunk_handle(self):
+        torch = _lib.require_gpu()
+        net = self.net
+        ent = net._handles.get(torch.cuda.current_device())
+        if self._handle_reusable(ent, tuple(v.version for v in net.variables)):
+            return ent[0]
+        return net._sync_handle()
+
+    def _write_back(self, host):
+        """the host variables take the new weights; a handle that held the frozen variables as they were gets exactly the
+        three trained layers (``ssal_icnet_update_fusion``), not the whole weight set"""
+        net = self.net
+        before = tuple(v.version for v in net.variables)
+        for var, (lo, hi) in zip(self._vars(), self._offsets()):
+            var.assign(host[lo:hi].reshape(var.shape))
+        torch = _lib.require_gpu()
+        device = self._dev["w"].device
+        with net._state_lock:
+            ent = net._handles.get(device.index)
+            if self._handle_reusable(ent, before):
+                p32 = np.ascontiguousarray(host, np.float32)
+                with torch.cuda.device(device):
+                    _lib.check(_lib.lib().ssal_icnet_update_fusion(ent[0], p32.ctypes.data, _lib.stream_ptr()))
+                ent[1] = tuple(v.version for v in net.variables)
+
+    def reinitialize(self, seed=None):
+        """``sess.run`` of the output layer's initializers, as the parent does (glorot-uniform ``conv6_cls`` kernel drawn
+        from ``seed``, zero bias; the fusion block keeps its weights); all eight Adam slots are reset"""
+        getattr(self.net, _HEAD).bias.assign(np.zeros(int(self.net.classes), np.float32))
+        FinalLayerTrainer.reinitialize(self, seed)
+
+    def load_state(self, state):
+        for key in ("m", "v"):
+            if not isinstance(state[key], dict) or set(state[key]) != set(_FUSION_NAMES):
+                raise ValueError("state[%r] must map %s to arrays" % (key, list(_FUSION_NAMES)))
+        self._set_state(self._pack(state["m"]), self._pack(state["v"]), state["t"])
+
+    # ---- arguments, judged on the host before any device work -----------------------------------------------------------------
+    @staticmethod
+    def _refuse_semi(**kw):
+        for name, value in kw.items():
+            if value is not None and value is not False:
+                raise NotImplementedError("%s: the semi-supervised step is not implemented for ICNet's fusion trainer" % name)
+
+    def _check_features(self, sub24_sum, conv3_sub1, labels, mask, max_workgroups):
+        mw = self._check_call(sub24_sum, 16, labels, mask, max_workgroups, 128)
+        s24, s3 = tuple(np.shape(sub24_sum)), tuple(np.shape(conv3_sub1))
+        if s3 != (s24[0], 2 * s24[1], 2 * s24[2], 64):
+            raise ValueError("conv3_sub1 must be [N,2h,2w,64] = %s for sub24_sum %s (got %s)"
+                             % ((s24[0], 2 * s24[1], 2 * s24[2], 64), s24, s3))
+        dt = str(getattr(conv3_sub1, "dtype", ""))
+        if "float" not in dt:
+            raise ValueError("conv3_sub1 must be a floating-point tensor (got %s)" % (dt or type(conv3_sub1).__name__))
+        return mw
+
+    def _packed_with(self, params):
+        params = dict(params or {})
+        unknown = set(params) - set(_FUSION_NAMES)
+        if unknown:
+            raise ValueError("unknown variables %s (the trained variables are %s)" % (sorted(unknown), list(_FUSION_NAMES)))
+        packed = self._pack()
+        if params:
+            packed = self._pack({n: params.get(n, v) for n, v in self._unpack(packed).items()})
+        return packed
+
+    # ---- gradients and steps ---------------------------------------------------------------------------------------------
+    def gradient_features(self, sub24_sum, conv3_sub1, labels, mask, params=None, max_workgroups=0, labelled=None,
+                          confusion=None, return_pseudo_pixels=False):
+        """(loss float64 [1], {name: gradient} for ``variable_names``) on the device for ``sub24_sum`` [N, h, w, 128],
+        ``conv3_sub1`` [N, 2h, 2w, 64] and labels / mask [N, 16h, 16w].  ``params`` overrides any of the eight tensors;
+        ``max_workgroups``: 0 = the default grids, a tuning knob.  No update."""
+        self._refuse_semi(labelled=labelled, confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
+        mw = self._check_features(sub24_sum, conv3_sub1, labels, mask, max_workgroups)
+        packed = self._packed_with(params)
+        x = _lib.as_device_f32(sub24_sum)
+        c3 = _lib.as_device_f32(conv3_sub1).to(x.device)
+        vec = _lib.require_gpu().from_numpy(packed).to(x.device)
+        loss, grad, _ = self._grad_call((x, c3), (None,), labels, mask, vec, None, None, False,
+                                        (_lib.dev_ptr(self._stats(x.device)), mw))
+        return loss, self._unpack(grad)
+
+    def features(self, images):
+        """``(sub24_sum [N, H/16, W/16, 128], conv3_sub1 [N, H/8, W/8, 64])`` for ``images`` (copies): what ``step_features``
+        and ``gradient_features`` take.  One forward pass of the frozen trunk; the result can be cached across steps."""
+        self.net(images, training=False)
+        return self.net.endpoint("sub24_sum").clone(), self.net.endpoint("conv3_sub1").clone()
+
+    def step_features(self, sub24_sum, conv3_sub1, labels, mask, max_workgroups=0, labelled=None, confusion=None,
+                      return_pseudo_pixels=False):
+        """one Adam step from cached features; returns the loss (float64 device scalar) BEFORE the step"""
+        self._refuse_semi(labelled=labelled, confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
+        mw = self._check_features(sub24_sum, conv3_sub1, labels, mask, max_workgroups)
+        x = _lib.as_device_f32(sub24_sum)
+        c3 = _lib.as_device_f32(conv3_sub1).to(x.device)
+        dev = self._device_state(x.device)
+        loss, grad, _ = self._grad_call((x, c3), (None,), labels, mask, dev["w"], None, None, False,
+                                        (_lib.dev_ptr(self._stats(x.device)), mw))
+        self._apply(dev, grad)
+        return loss[0]
+
+    def step(self, images, labels, mask, max_workgroups=0, labelled=None, confusion=None, return_pseudo_pixels=False):
+        """one Adam step from images [N, H, W, C] (fp32 or decoded uint8) and labels / mask [N, H, W]: the frozen trunk up
+        to ``sub24_sum`` and ``conv3_sub1``, the block and the head on the weights being trained, their gradient kernels,
+        Adam.  Returns the loss (float64 device scalar) before the step."""
+        self._refuse_semi(labelled=labelled, confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
+        mw = self._check_call(images, 1, labels, mask, max_workgroups, None)
+        torch = _lib.require_gpu()
+        device = images.device if getattr(images, "is_cuda", False) else torch.device("cuda", torch.cuda.current_device())
+        return self._step_images(images, None, labels, mask, None, None, False, (_lib.dev_ptr(self._stats(device)), mw))
+
+
 __all__ = ["FinalLayerTrainer", "LastBlockTrainer", "LastStageTrainer", "DecoderTailTrainer", "SemiSupervisedBlockTrainer",
            "SemiSupervisedStageTrainer", "SemiSupervisedTailTrainer", "DeepTailTrainer", "SemiSupervisedDeepTailTrainer",
-           "DecoderTrainer", "SemiSupervisedDecoderTrainer", "ICNetHeadTrainer", "SemiSupervisedICNetHeadTrainer"]
+           "DecoderTrainer", "SemiSupervisedDecoderTrainer", "ICNetHeadTrainer", "SemiSupervisedICNetHeadTrainer",
+           "ICNetFusionTrainer"]
