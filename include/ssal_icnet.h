@@ -181,6 +181,34 @@ int ssal_icnet_train_fusion_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8
  * the handle stays committed.  Synchronises the stream; as with ssal_icnet_commit no call may be in flight on the handle. */
 int ssal_icnet_update_fusion(ssal_icnet *net, const float *params_host, void *stream);
 
+/* ---- Training of the whole cascade head: sub24_sum = relu(BN(conv_sub4(resize_bilinear(conv5_4_k1,
+ * 2x))) + BN(conv3_1_sub2_proj(conv3_1))), then the last fusion stage and conv6_cls as above, over the three frozen branches ----
+ * The fourteen trained variables travel PACKED, in this order: conv_sub4.kernel [3,3,256,128] | .gamma [128] | .beta [128] |
+ * conv3_1_sub2_proj.kernel [1,1,256,128] | .gamma [128] | .beta [128] | the eight of the fusion entries in their order
+ * (328192 + 156160 + 129 * classes floats); params_dev and grad_dev have that layout.  stats_dev [8 * 128] = conv_sub4 mean |
+ * variance | conv3_1_sub2_proj mean | variance | the four rows of the fusion entries; batch-norm as there.  One call computes,
+ * for conv5_4_k1 [n,h,w,256] (1/32 resolution), conv3_1 [n,2h,2w,256], conv3_sub1 [n,4h,4w,64], labels uint8 and mask fp32
+ * [n,32h,32w]: sub24_sum, sub12_sum and lq by the forward path's own launches on params_dev, the loss -> loss_dev [1] float64,
+ * and the gradient of all fourteen variables -> grad_dev (without the regulariser).  Nothing below the three inputs gets a
+ * gradient.  The loss and the last eight gradients are the bits ssal_icnet_fusion_grad_nhwc gives on the same sub24_sum.
+ * max_workgroups, determinism and statuses as ssal_icnet_fusion_grad_nhwc's. */
+int64_t ssal_icnet_cascade_grad_workspace_bytes(int n, int h, int w, int classes);
+int ssal_icnet_cascade_grad_nhwc(const float *conv5_4_k1_dev, const float *conv3_1_dev, const float *conv3_sub1_dev, int n,
+                                 int h, int w, int classes, const float *params_dev, const uint8_t *labels_dev,
+                                 const float *mask_dev, float weight, float label_smoothing, const float *stats_dev,
+                                 int max_workgroups, double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes,
+                                 void *stream);
+/* the same from frames x_dev [n,h,w,c_in] (fp32, or uint8 when x_is_u8 != 0): the frozen trunk until conv5_4_k1, conv3_1 and
+ * conv3_sub1 are written, then the tail above; labels / mask [n,h,w].  After the call the endpoints from conv3_1_sub2_proj on
+ * are those of params_dev. */
+int64_t ssal_icnet_train_cascade_workspace_bytes(const ssal_icnet *net, int n, int h, int w);
+int ssal_icnet_train_cascade_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                                  const uint8_t *labels_dev, const float *mask_dev, const float *params_dev, float weight,
+                                  float label_smoothing, const float *stats_dev, int max_workgroups, double *loss_dev,
+                                  float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream);
+/* ssal_icnet_update_fusion for the fourteen variables: only the five trained layers are re-laid-out, folded and uploaded */
+int ssal_icnet_update_cascade(ssal_icnet *net, const float *params_host, void *stream);
+
 /* Stand-alone fused convolution (the operator every ICNet layer is built from; also the per-block parity hook):
  * y = [relu]( BN(conv2d(x, kernel HWIO, strides s, dilations d, "SAME")) [+ res] ), BN given as mean / variance /
  * gamma / beta (all NULL: no batch-norm; bias_dev optional).  upsample2x != 0 runs the conv on

@@ -188,6 +188,13 @@ PROTOTYPES = {
     "ssal_icnet_train_fusion_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
     "ssal_icnet_train_fusion_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
     "ssal_icnet_update_fusion": (_i, [_vp, _vp, _vp]),
+    # ---- training of ICNet's whole cascade head (include/ssal_icnet.h) ----
+    "ssal_icnet_cascade_grad_workspace_bytes": (_i64, [_i, _i, _i, _i]),
+    "ssal_icnet_cascade_grad_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64,
+                                          _vp]),
+    "ssal_icnet_train_cascade_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
+    "ssal_icnet_train_cascade_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_icnet_update_cascade": (_i, [_vp, _vp, _vp]),
     # ---- PNG decode (include/ssal_enet.h) ----
     "ssal_png_plan": (_i64, [_i64, _vp]),
     "ssal_png_decode_nhwc": (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),

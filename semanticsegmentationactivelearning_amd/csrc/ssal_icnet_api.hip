@@ -8,6 +8,7 @@
 #include "ssal_internal.h"
 #include "ssal_prof.h"
 #include "ssal_train_icnet.h"
+#include "ssal_train_icnet_cascade.h"
 #include "ssal_train_icnet_fusion.h"
 
 #include <math.h>
@@ -245,8 +246,10 @@ struct Grp {
 // swallows is the schedule itself)
 // head = false: the schedule ends at sub12_sum (the output-layer trainer runs conv6_cls on the weights it trains)
 // fusion = false (with head = false): it ends at sub24_sum and conv3_sub1 (the fusion trainer runs the last fusion block too)
+// cascade = false (with fusion = false): it ends once conv5_4_k1, conv3_1 and conv3_sub1 are written (the cascade trainer runs
+// both fusion blocks; every fused launch above writes those three: none of them is swallowed)
 hipError_t run_trunk(const ssal_icnet *net, std::vector<Grp> &grp, bool x_is_u8, int h, int w, bool fused,
-                     std::set<std::string> *written = nullptr, bool head = true, bool fusion = true)
+                     std::set<std::string> *written = nullptr, bool head = true, bool fusion = true, bool cascade = true)
 {
     const bool dry = written != nullptr;
 #define OUT(name) do { if (dry) written->insert(name); } while (0)
@@ -347,15 +350,18 @@ hipError_t run_trunk(const ssal_icnet *net, std::vector<Grp> &grp, bool x_is_u8,
         EACH(launch_conv_first(q.x, x_is_u8, q.n, h, w, net->c_in, 1, c.w, c.scale, c.shift, q.A("conv1_sub1"), q.s));
         EACH(run_conv(net, "conv2_sub1", q.A("conv1_sub1"), q.n, h / 2, w / 2, nullptr, true, false, q.A("conv2_sub1"), q.s));
     }
-    for (const char *nm_ : {"conv3_sub1", "conv3_1_sub2_proj", "sub24_sum"}) OUT(nm_);
+    OUT("conv3_sub1");
+    if (cascade) for (const char *nm_ : {"conv3_1_sub2_proj", "sub24_sum"}) OUT(nm_);
     if (fusion) for (const char *nm_ : {"conv3_sub1_proj", "sub12_sum"}) OUT(nm_);
     if (head) OUT("conv6_cls");
     EACH(run_conv(net, "conv3_sub1", q.A("conv2_sub1"), q.n, h / 4, w / 4, nullptr, true, false, q.A("conv3_sub1"), q.s));
     // ---- cascade feature fusion (section 4): the 2x interpolations are evaluated inside the dilated convs ----
-    EACH(run_conv(net, "conv3_1_sub2_proj", q.A("conv3_1"), q.n, h / 16, w / 16, nullptr, false, false,
-                  q.A("conv3_1_sub2_proj"), q.s));
-    EACH(run_conv(net, "conv_sub4", q.A("conv5_4_k1"), q.n, h / 32, w / 32, q.A("conv3_1_sub2_proj"), true, true,
-                  q.A("sub24_sum"), q.s));
+    if (cascade) {
+        EACH(run_conv(net, "conv3_1_sub2_proj", q.A("conv3_1"), q.n, h / 16, w / 16, nullptr, false, false,
+                      q.A("conv3_1_sub2_proj"), q.s));
+        EACH(run_conv(net, "conv_sub4", q.A("conv5_4_k1"), q.n, h / 32, w / 32, q.A("conv3_1_sub2_proj"), true, true,
+                      q.A("sub24_sum"), q.s));
+    }
     if (fusion) {
         EACH(run_conv(net, "conv3_sub1_proj", q.A("conv3_sub1"), q.n, h / 8, w / 8, nullptr, false, false,
                       q.A("conv3_sub1_proj"), q.s));
@@ -1118,31 +1124,41 @@ SSAL_API int ssal_icnet_train_fusion_nhwc(ssal_icnet *net, const void *x_dev, in
     return SSAL_OK;
 }
 
-SSAL_API int ssal_icnet_update_fusion(ssal_icnet *net, const float *params_host, void *stream)
+namespace {
+
+// the fusion trainer's eight variables at params_host + base -> the handle's host tensors, then the named layers re-laid-out,
+// folded with the handle's moving statistics and uploaded; `more`: further (tensor, offset, count) in front of them
+struct PackedTensor {
+    const char *name;
+    int64_t off, count;
+};
+
+int update_packed(ssal_icnet *net, const float *params_host, const std::vector<PackedTensor> &more, int64_t base,
+                  const std::set<std::string> &layers, void *stream)
 {
-    if (!net || !params_host) return fail(SSAL_EINVAL, "NULL argument");
     if (!net->committed) return fail(SSAL_ESTATE, "ssal_icnet_commit() has not been called");
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess || dev != net->device)
         return fail(SSAL_ESTATE, "the handle was committed on device %d but the current device is %d (one handle per device)",
                     net->device, dev);
     const int K = net->classes;
-    auto put = [&](const std::string &name, int off, size_t count) {
+    auto put = [&](const std::string &name, int64_t off, size_t count) {
         net->tensors[net->index.at(name)].data.assign(params_host + off, params_host + off + count);
     };
-    put("conv_sub2.kernel", FU_KA, FU_GA);
-    put("conv_sub2.gamma", FU_GA, 128);
-    put("conv_sub2.beta", FU_BA, 128);
-    put("conv3_sub1_proj.kernel", FU_KB, 64 * 128);
-    put("conv3_sub1_proj.gamma", FU_GB, 128);
-    put("conv3_sub1_proj.beta", FU_BB, 128);
-    put("conv6_cls.kernel", FU_HEAD, 128 * (size_t)K);
-    put("conv6_cls.bias", FU_HEAD + 128 * K, K);
+    for (const PackedTensor &t : more) put(t.name, t.off, (size_t)t.count);
+    put("conv_sub2.kernel", base + FU_KA, FU_GA);
+    put("conv_sub2.gamma", base + FU_GA, 128);
+    put("conv_sub2.beta", base + FU_BA, 128);
+    put("conv3_sub1_proj.kernel", base + FU_KB, 64 * 128);
+    put("conv3_sub1_proj.gamma", base + FU_GB, 128);
+    put("conv3_sub1_proj.beta", base + FU_BB, 128);
+    put("conv6_cls.kernel", base + FU_HEAD, 128 * (size_t)K);
+    put("conv6_cls.bias", base + FU_HEAD + 128 * K, K);
     hipStream_t s = (hipStream_t)stream;
     // the staging vectors live until the synchronisation below
     std::vector<std::vector<float>> keep;
     for (const ConvSpec &sp : net->specs) {
-        if (sp.name != "conv_sub2" && sp.name != "conv3_sub1_proj" && sp.name != "conv6_cls") continue;
+        if (!layers.count(sp.name)) continue;
         std::vector<float> wt(igemm_relayout_floats(sp.k, sp.k, sp.cin, sp.cout)), sc, sh;
         igemm_relayout(T(net, sp.name + ".kernel").data(), sp.k, sp.k, sp.cin, sp.cout, wt.data());
         if (sp.bn)
@@ -1162,6 +1178,136 @@ SSAL_API int ssal_icnet_update_fusion(ssal_icnet *net, const float *params_host,
     }
     HIP_TRY(hipStreamSynchronize(s));
     return SSAL_OK;
+}
+
+}  // namespace
+
+SSAL_API int ssal_icnet_update_fusion(ssal_icnet *net, const float *params_host, void *stream)
+{
+    if (!net || !params_host) return fail(SSAL_EINVAL, "NULL argument");
+    return update_packed(net, params_host, {}, 0, {"conv_sub2", "conv3_sub1_proj", "conv6_cls"}, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// training of the whole cascade head (kernels: ssal_train_icnet_cascade.hip)
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+// the buffers of one gradient call behind `b`; own_acts: the block's projection / sub24_sum and the fusion stage's activations
+// live here (the images entry keeps them in the network's endpoints instead)
+IcnetCascadeWs cascade_carve(Bump &b, int64_t n, int h32, int w32, int classes, bool own_acts)
+{
+    IcnetCascadeWs t;
+    const int h16 = 2 * h32, w16 = 2 * w32;
+    const int64_t act = n * h16 * (int64_t)w16 * 128;
+    t.wt_c = b.take<float>(CA_GC);
+    t.wt_d = b.take<float>(256 * 128);
+    t.rows = b.take<float>(512);
+    t.proj = own_acts ? b.take<float>(act) : nullptr;
+    t.sub24 = own_acts ? b.take<float>(act) : nullptr;
+    t.du = b.take<float>(4 * act);
+    t.g24 = b.take<float>(act);
+    t.part = b.take<float>((int64_t)CA_MAX_WG * CA_PART);  // (sized for the default grid: max_workgroups only lowers it)
+    t.fold = b.take<float>(CA_PART);
+    t.fusion = fusion_carve(b, n, h16, w16, classes, own_acts);
+    return t;
+}
+
+bool cascade_dims_ok(int n, int h32, int w32, int classes)
+{
+    return icnet_cascade_fits(h32, w32) && fusion_dims_ok(n, 2 * h32, 2 * w32, classes);
+}
+
+int cascade_check(int n, int h32, int w32, int classes, int max_workgroups)
+{
+    if (n <= 0) return fail(SSAL_EINVAL, "bad dims n=%d h=%d w=%d", n, h32, w32);
+    if (classes < 2 || classes > 32) return fail(SSAL_EINVAL, "classes must be in [2,32] (got %d)", classes);
+    if (max_workgroups < 0) return fail(SSAL_EINVAL, "max_workgroups must be >= 0 (got %d)", max_workgroups);
+    if (!cascade_dims_ok(n, h32, w32, classes))
+        return fail(SSAL_EINVAL, "feature map %dx%d (n=%d) is beyond the cascade gradient kernels' limit", h32, w32, n);
+    return SSAL_OK;
+}
+
+}  // namespace
+
+SSAL_API int64_t ssal_icnet_cascade_grad_workspace_bytes(int n, int h, int w, int classes)
+{
+    if (n <= 0 || !cascade_dims_ok(n, h, w, classes)) return -1;
+    Bump b(nullptr, 0);
+    (void)cascade_carve(b, n, h, w, classes, true);
+    return b.off + 256;
+}
+
+SSAL_API int ssal_icnet_cascade_grad_nhwc(const float *conv5_4_k1_dev, const float *conv3_1_dev, const float *conv3_sub1_dev,
+                                          int n, int h, int w, int classes, const float *params_dev,
+                                          const uint8_t *labels_dev, const float *mask_dev, float weight,
+                                          float label_smoothing, const float *stats_dev, int max_workgroups, double *loss_dev,
+                                          float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    int rc = cascade_check(n, h, w, classes, max_workgroups);
+    if (rc) return rc;
+    if (!conv5_4_k1_dev || !conv3_1_dev || !conv3_sub1_dev || !params_dev || !stats_dev || !labels_dev || !mask_dev ||
+        !loss_dev || !grad_dev || !ws_dev)
+        return fail(SSAL_EINVAL, "NULL device pointer");
+    Bump b(ws_dev, ws_bytes);
+    const IcnetCascadeWs t = cascade_carve(b, n, h, w, classes, true);
+    if (!b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
+                           (long long)ssal_icnet_cascade_grad_workspace_bytes(n, h, w, classes), (long long)ws_bytes);
+    HIP_TRY(launch_icnet_cascade_grad(conv5_4_k1_dev, conv3_1_dev, conv3_sub1_dev, n, h, w, classes, params_dev, stats_dev,
+                                      labels_dev, mask_dev, weight, label_smoothing, max_workgroups, t, loss_dev, grad_dev,
+                                      (hipStream_t)stream));
+    return SSAL_OK;
+}
+
+SSAL_API int64_t ssal_icnet_train_cascade_workspace_bytes(const ssal_icnet *net, int n, int h, int w)
+{
+    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 32 || w % 32) return -1;
+    Bump b(nullptr, 0);
+    b.off = carve(net, nullptr, 0, n, h, w).bytes;
+    (void)cascade_carve(b, n, h / 32, w / 32, net->classes, false);
+    return b.off + 256;
+}
+
+SSAL_API int ssal_icnet_train_cascade_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                                           const uint8_t *labels_dev, const float *mask_dev, const float *params_dev,
+                                           float weight, float label_smoothing, const float *stats_dev, int max_workgroups,
+                                           double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    int rc = check_dims(net, n, h, w);
+    if (rc) return rc;
+    if ((rc = cascade_check(n, h / 32, w / 32, net->classes, max_workgroups))) return rc;
+    if (!x_dev || !params_dev || !stats_dev || !labels_dev || !mask_dev || !loss_dev || !grad_dev || !ws_dev)
+        return fail(SSAL_EINVAL, "NULL device pointer");
+    IcWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
+    Bump b(ws_dev, ws_bytes);
+    b.off = W.bytes;
+    IcnetCascadeWs t = cascade_carve(b, n, h / 32, w / 32, net->classes, false);
+    if (!W.ok || !b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
+                                    (long long)ssal_icnet_train_cascade_workspace_bytes(net, n, h, w), (long long)ws_bytes);
+    // both blocks and the head being trained write this call's endpoints from conv3_1_sub2_proj on
+    t.proj = W.act.at("conv3_1_sub2_proj");
+    t.sub24 = W.act.at("sub24_sum");
+    t.fusion.proj = W.act.at("conv3_sub1_proj");
+    t.fusion.sub12 = W.act.at("sub12_sum");
+    t.fusion.head.lq = W.act.at("conv6_cls");
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<Grp> one(1);
+    one[0] = {W, x_dev, n, s};
+    HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false, false, false));
+    HIP_TRY(launch_icnet_cascade_grad(W.act.at("conv5_4_k1"), W.act.at("conv3_1"), W.act.at("conv3_sub1"), n, h / 32, w / 32,
+                                      net->classes, params_dev, stats_dev, labels_dev, mask_dev, weight, label_smoothing,
+                                      max_workgroups, t, loss_dev, grad_dev, s));
+    return SSAL_OK;
+}
+
+SSAL_API int ssal_icnet_update_cascade(ssal_icnet *net, const float *params_host, void *stream)
+{
+    if (!net || !params_host) return fail(SSAL_EINVAL, "NULL argument");
+    return update_packed(net, params_host,
+                         {{"conv_sub4.kernel", CA_KC, CA_GC}, {"conv_sub4.gamma", CA_GC, 128}, {"conv_sub4.beta", CA_BC, 128},
+                          {"conv3_1_sub2_proj.kernel", CA_KD, 256 * 128}, {"conv3_1_sub2_proj.gamma", CA_GD, 128},
+                          {"conv3_1_sub2_proj.beta", CA_BD, 128}},
+                         CA_FUSION, {"conv_sub4", "conv3_1_sub2_proj", "conv_sub2", "conv3_sub1_proj", "conv6_cls"}, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -27,6 +27,14 @@ constexpr int FU_MAX_WG = 96;                    // split-K groups the finish ke
 bool icnet_fusion_fits(int h16, int w16);
 int icnet_fusion_workgroups(int n, int h16, int w16, int max_workgroups);
 
+// The weight-gradient kernel at 256 input channels (the other fusion block): src [N, hs, ws, 256] is
+// interpolated 2x on the fly, side [N, 2 hs, 2 ws, 256] is the 1 x 1 branch's input, g [N, 2 hs, 2 ws, 128].  Grid
+// (G, CA_TAPS, 2): the third index picks the input-channel half; the row of ones (sum_p g) is an eleventh tap.
+// part [G][CA_TAPS][256][128] ([G][tap][half][128][128]; tap 10 has its first half only, whose row 0 is sum_p g).
+constexpr int CA_TAPS = 11;
+hipError_t launch_icnet_fusion_wgrad256(const float *src, const float *side, const float *g, int N, int hs, int ws, int G,
+                                        float *part, hipStream_t s);
+
 struct IcnetFusionWs {
     float *wt_a;    // conv_sub2's kernel in igemm_relayout's layout [9][4][128][32]
     float *wt_b;    // conv3_sub1_proj's [1][2][128][32]

@@ -129,6 +129,10 @@ __global__ __launch_bounds__(256) void k_icnet_fusion_g(const float *__restrict_
 //   tap 9: A[p][ci] = conv3_sub1[p, ci] for ci < 64, 1 for ci = 64 (that row of D is sum_p g = dBeta), 0 beyond;
 //   16 steps of two pixels each: lane (r = lane & 31, h = lane >> 5) feeds A[2 s + h][32 w + r] and B[2 s + h][32 j + r].
 // part [G][FU_TAPS][128][128].
+// CIN = 256 (the other fusion block, section 29): grid (G, CA_TAPS, 2), blockIdx.z picks the half of the input channels a
+// workgroup owns; tap 9 is the 1 x 1 branch on all 256 channels of its input, tap 10 (half 0 only) the row of ones in
+// row 0.  part [G][CA_TAPS][2][128][128].  CIN = 128 compiles to the kernel it was before the parameter.
+template <int CIN>
 __global__ __launch_bounds__(256) void k_icnet_fusion_wgrad(const float *__restrict__ s24, const float *__restrict__ c3,
                                                             const float *__restrict__ g, int N, int h16, int w16,
                                                             float *__restrict__ part)
@@ -138,6 +142,9 @@ __global__ __launch_bounds__(256) void k_icnet_fusion_wgrad(const float *__restr
     __shared__ __attribute__((aligned(16))) float win[FU_WR * FU_WC * 128];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
     const int tap = blockIdx.y;
+    constexpr int TAPS = CIN == 128 ? FU_TAPS : CA_TAPS;
+    const int half = CIN == 128 ? 0 : (int)blockIdx.z, cb = 128 * half;
+    if (CIN != 128 && tap == 10 && half) return;
     const int h8 = 2 * h16, w8 = 2 * w16;
     const int tx = (w8 + FU_TW - 1) / FU_TW, ty = (h8 + FU_TH - 1) / FU_TH;
     const long per_image = (long)tx * ty, tiles = (long)N * per_image;
@@ -165,7 +172,7 @@ __global__ __launch_bounds__(256) void k_icnet_fusion_wgrad(const float *__restr
                 const int wp = e >> 5, q = e & 31;
                 const int sr = min(sr0 + wp / FU_WC, h16 - 1), sc = min(sc0 + wp % FU_WC, w16 - 1);
                 float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                if (sr >= 0 && sc >= 0) v = reinterpret_cast<const float4 *>(s24 + ((n * h16 + sr) * w16 + sc) * 128)[q];
+                if (sr >= 0 && sc >= 0) v = reinterpret_cast<const float4 *>(s24 + ((n * h16 + sr) * w16 + sc) * CIN + cb)[q];
                 *reinterpret_cast<float4 *>(win + wp * 128 + 4 * q) = v;
             }
             __syncthreads();
@@ -194,8 +201,14 @@ __global__ __launch_bounds__(256) void k_icnet_fusion_wgrad(const float *__restr
                 const int y = y0 + (p >> 3), xx = x0 + (p & 7);
                 float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                 if (y < h8 && xx < w8) {
-                    if (q < 16) v = reinterpret_cast<const float4 *>(c3 + ((n * h8 + y) * w8 + xx) * 64)[q];
-                    else if (q == 16) v.x = 1.0f;
+                    if (CIN == 128) {
+                        if (q < 16) v = reinterpret_cast<const float4 *>(c3 + ((n * h8 + y) * w8 + xx) * 64)[q];
+                        else if (q == 16) v.x = 1.0f;
+                    } else if (tap == 9) {
+                        v = reinterpret_cast<const float4 *>(c3 + ((n * h8 + y) * w8 + xx) * CIN + cb)[q];
+                    } else if (q == 0) {
+                        v.x = 1.0f;
+                    }
                 }
                 *reinterpret_cast<float4 *>(As + p * FU_LD + 4 * q) = v;
             }
@@ -209,7 +222,7 @@ __global__ __launch_bounds__(256) void k_icnet_fusion_wgrad(const float *__restr
             for (int j = 0; j < 4; ++j) acc[j] = mfma32(a, bp[32 * j], acc[j]);
         }
     }
-    float *pw = part + ((long)blockIdx.x * FU_TAPS + tap) * (128 * 128);
+    float *pw = part + (((long)blockIdx.x * TAPS + tap) * (CIN / 128) + half) * (128 * 128);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -317,7 +330,7 @@ hipError_t launch_icnet_fusion_grad(const float *sub24, const float *c3, int N, 
     {
         ProfScope prof("k_icnet_fusion_wgrad", 2.0 * pix * (9 * 128 + 64) * 128,
                        4.0 * (FU_TAPS * pix * 128 + pix * (32 + 64)) + 4.0 * G * FU_PART, s);
-        hipLaunchKernelGGL(k_icnet_fusion_wgrad, dim3(G, FU_TAPS), dim3(256), 0, s, sub24, c3, ws.g, N, h16, w16, ws.part);
+        hipLaunchKernelGGL(k_icnet_fusion_wgrad<128>, dim3(G, FU_TAPS), dim3(256), 0, s, sub24, c3, ws.g, N, h16, w16, ws.part);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     {
@@ -328,6 +341,17 @@ hipError_t launch_icnet_fusion_grad(const float *sub24, const float *c3, int N, 
     }
     ProfScope prof("k_icnet_fusion_gamma", 2.0 * (FU_GA + 64 * 128), 8.0 * FU_PART, s);
     hipLaunchKernelGGL(k_icnet_fusion_gamma, dim3(2), dim3(128), 0, s, ws.fold, params, stats, grad);
+    return hipGetLastError();
+}
+
+hipError_t launch_icnet_fusion_wgrad256(const float *src, const float *side, const float *g, int N, int hs, int ws, int G,
+                                        float *part, hipStream_t s)
+{
+    if (N < 1 || G < 1 || G > 0xffff || !icnet_fusion_fits(hs, ws)) return hipErrorInvalidValue;
+    const double pix = 4.0 * N * hs * ws;
+    ProfScope prof("k_icnet_fusion_wgrad<256>", 2.0 * pix * (10 * 256 + 1) * 128,
+                   4.0 * (2.0 * CA_TAPS * pix * 128 + pix * (9 * 64 + 256)) + 4.0 * G * (CA_TAPS * 256 * 128), s);
+    hipLaunchKernelGGL(k_icnet_fusion_wgrad<256>, dim3(G, CA_TAPS, 2), dim3(256), 0, s, src, side, g, N, hs, ws, part);
     return hipGetLastError();
 }
 

@@ -1331,13 +1331,14 @@ class ICNetFusionTrainer(ICNetHeadTrainer):
     _C_IMAGES = ("ssal_icnet_train_fusion", None)
     _CHANNELS, _UP = 128, 16
     _LIMIT = ("kernels'", "kernels'")
+    _VARS, _STATS, _C_UPDATE = _FUSION_VARS, _FUSION_STATS, "ssal_icnet_update_fusion"  # what a subclass widens
     variable_names = list(_FUSION_NAMES)
 
     # ---- the packed vector ---------------------------------------------------------------------------------------------------
     def _vars(self):
         if not self.net.built:
             raise RuntimeError("build the model (call it once, or .build(input_shape)) before training")
-        return tuple(getattr(getattr(self.net, layer), attr) for layer, attr, _ in _FUSION_VARS)
+        return tuple(getattr(getattr(self.net, layer), attr) for layer, attr, _ in self._VARS)
 
     def _offsets(self):
         """(lo, hi) of every variable in the packed vector"""
@@ -1353,7 +1354,7 @@ class ICNetFusionTrainer(ICNetHeadTrainer):
 
     def _pack(self, arrays=None):
         out = np.zeros(self._floats(), np.float32)
-        for name, var, (lo, hi) in zip(_FUSION_NAMES, self._vars(), self._offsets()):
+        for name, var, (lo, hi) in zip(self.variable_names, self._vars(), self._offsets()):
             a = var.numpy() if arrays is None else arrays[name]
             a = np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a, dtype=np.float32)
             if a.shape != tuple(var.shape):
@@ -1363,7 +1364,7 @@ class ICNetFusionTrainer(ICNetHeadTrainer):
 
     def _unpack(self, packed):
         return {name: packed[lo:hi].reshape(tuple(var.shape))
-                for name, var, (lo, hi) in zip(_FUSION_NAMES, self._vars(), self._offsets())}
+                for name, var, (lo, hi) in zip(self.variable_names, self._vars(), self._offsets())}
 
     def _kernel_var(self):
         return getattr(self.net, _HEAD).kernel  # what ``reinitialize`` re-draws
@@ -1372,12 +1373,12 @@ class ICNetFusionTrainer(ICNetHeadTrainer):
         return np.zeros(self._floats(), np.float32)
 
     def _adam_ranges(self):
-        return tuple((lo, hi, reg) for (lo, hi), (_, _, reg) in zip(self._offsets(), _FUSION_VARS))
+        return tuple((lo, hi, reg) for (lo, hi), (_, _, reg) in zip(self._offsets(), self._VARS))
 
     def _stats(self, device):
-        """the frozen moving statistics [4 * 128] on the device (pushed again only when one of them changed)"""
+        """the frozen moving statistics [len(_STATS) * 128] on the device (pushed again only when one of them changed)"""
         torch = _lib.require_gpu()
-        stat_vars = [getattr(getattr(self.net, layer), attr) for layer, attr in _FUSION_STATS]
+        stat_vars = [getattr(getattr(self.net, layer), attr) for layer, attr in self._STATS]
         key = (device, tuple(v.version for v in stat_vars))
         if getattr(self, "_stats_dev", None) is None or self._stats_dev[0] != key:
             host = np.concatenate([np.asarray(v.numpy(), np.float32).reshape(-1) for v in stat_vars])
@@ -1405,7 +1406,7 @@ class ICNetFusionTrainer(ICNetHeadTrainer):
 
     def _write_back(self, host):
         """the host variables take the new weights; a handle that held the frozen variables as they were gets exactly the
-        three trained layers (``ssal_icnet_update_fusion``), not the whole weight set"""
+        trained layers (``ssal_icnet_update_fusion`` / ``_cascade``), not the whole weight set"""
         net = self.net
         before = tuple(v.version for v in net.variables)
         for var, (lo, hi) in zip(self._vars(), self._offsets()):
@@ -1417,7 +1418,7 @@ class ICNetFusionTrainer(ICNetHeadTrainer):
             if self._handle_reusable(ent, before):
                 p32 = np.ascontiguousarray(host, np.float32)
                 with torch.cuda.device(device):
-                    _lib.check(_lib.lib().ssal_icnet_update_fusion(ent[0], p32.ctypes.data, _lib.stream_ptr()))
+                    _lib.check(getattr(_lib.lib(), self._C_UPDATE)(ent[0], p32.ctypes.data, _lib.stream_ptr()))
                 ent[1] = tuple(v.version for v in net.variables)
 
     def reinitialize(self, seed=None):
@@ -1428,8 +1429,8 @@ class ICNetFusionTrainer(ICNetHeadTrainer):
 
     def load_state(self, state):
         for key in ("m", "v"):
-            if not isinstance(state[key], dict) or set(state[key]) != set(_FUSION_NAMES):
-                raise ValueError("state[%r] must map %s to arrays" % (key, list(_FUSION_NAMES)))
+            if not isinstance(state[key], dict) or set(state[key]) != set(self.variable_names):
+                raise ValueError("state[%r] must map %s to arrays" % (key, self.variable_names))
         self._set_state(self._pack(state["m"]), self._pack(state["v"]), state["t"])
 
     # ---- arguments, judged on the host before any device work -----------------------------------------------------------------
@@ -1452,9 +1453,9 @@ class ICNetFusionTrainer(ICNetHeadTrainer):
 
     def _packed_with(self, params):
         params = dict(params or {})
-        unknown = set(params) - set(_FUSION_NAMES)
+        unknown = set(params) - set(self.variable_names)
         if unknown:
-            raise ValueError("unknown variables %s (the trained variables are %s)" % (sorted(unknown), list(_FUSION_NAMES)))
+            raise ValueError("unknown variables %s (the trained variables are %s)" % (sorted(unknown), self.variable_names))
         packed = self._pack()
         if params:
             packed = self._pack({n: params.get(n, v) for n, v in self._unpack(packed).items()})
@@ -1506,7 +1507,85 @@ class ICNetFusionTrainer(ICNetHeadTrainer):
         return self._step_images(images, None, labels, mask, None, None, False, (_lib.dev_ptr(self._stats(device)), mw))
 
 
+# ---- ICNet's whole cascade head: both fusion blocks + conv6_cls over the three frozen branches -----------
+_CASCADE_VARS = (("conv_sub4", "kernel", True), ("conv_sub4", "gamma", False), ("conv_sub4", "beta", False),
+                 ("conv3_1_sub2_proj", "kernel", True), ("conv3_1_sub2_proj", "gamma", False),
+                 ("conv3_1_sub2_proj", "beta", False)) + _FUSION_VARS
+_CASCADE_STATS = (("conv_sub4", "mean"), ("conv_sub4", "variance"), ("conv3_1_sub2_proj", "mean"),
+                  ("conv3_1_sub2_proj", "variance")) + _FUSION_STATS
+
+
+class ICNetCascadeTrainer(ICNetFusionTrainer):
+    """Adam on ICNet's cascade head -- everything ICNET_SPEC section 4 defines: ``sub24_sum = relu(BN(conv_sub4(resize_2x(
+    conv5_4_k1))) + BN(conv3_1_sub2_proj(conv3_1)))``, the last fusion block of ``ICNetFusionTrainer`` and ``conv6_cls`` --
+    over the three frozen branches (``training=False`` up to ``conv5_4_k1`` [N, H/32, W/32, 256], ``conv3_1`` [N, H/16, W/16,
+    256] and ``conv3_sub1`` [N, H/8, W/8, 64]; nothing below them gets a gradient).  Batch-norm, hyper-parameters, Adam and the
+    refusals are the parent's; the ``l1_l2`` regulariser goes to the five kernels only.
+
+    The fourteen variables travel as one packed float32 vector in the order of ``variable_names``: the new block's six, then the
+    parent's eight in the parent's order."""
+
+    _C_FEATURES = ("ssal_icnet_cascade_grad", None)
+    _C_IMAGES = ("ssal_icnet_train_cascade", None)
+    _CHANNELS, _UP = 256, 32
+    _VARS, _STATS, _C_UPDATE = _CASCADE_VARS, _CASCADE_STATS, "ssal_icnet_update_cascade"
+    variable_names = ["%s.%s" % (layer, attr) for layer, attr, _ in _CASCADE_VARS]
+
+    @staticmethod
+    def _refuse_semi(**kw):
+        for name, value in kw.items():
+            if value is not None and value is not False:
+                raise NotImplementedError("%s: the semi-supervised step is not implemented for ICNet's cascade trainer" % name)
+
+    def _check_features(self, conv5_4_k1, conv3_1, conv3_sub1, labels, mask, max_workgroups):
+        mw = self._check_call(conv5_4_k1, 32, labels, mask, max_workgroups, 256)
+        n, h, w, _ = tuple(np.shape(conv5_4_k1))
+        for name, t, want in (("conv3_1", conv3_1, (n, 2 * h, 2 * w, 256)), ("conv3_sub1", conv3_sub1, (n, 4 * h, 4 * w, 64))):
+            if tuple(np.shape(t)) != want:
+                raise ValueError("%s must be %s for conv5_4_k1 %s (got %s)" % (name, want, (n, h, w, 256), tuple(np.shape(t))))
+            dt = str(getattr(t, "dtype", ""))
+            if "float" not in dt:
+                raise ValueError("%s must be a floating-point tensor (got %s)" % (name, dt or type(t).__name__))
+        return mw
+
+    def _feature_call(self, conv5_4_k1, conv3_1, conv3_sub1, labels, mask, packed, mw):
+        """-> (loss, packed gradient, device state); ``packed`` None: on the weights of the device state"""
+        x = _lib.as_device_f32(conv5_4_k1)
+        rest = tuple(_lib.as_device_f32(t).to(x.device) for t in (conv3_1, conv3_sub1))
+        dev = self._device_state(x.device) if packed is None else None
+        vec = dev["w"] if packed is None else _lib.require_gpu().from_numpy(packed).to(x.device)
+        loss, grad, _ = self._grad_call((x,) + rest, (None,), labels, mask, vec, None, None, False,
+                                        (_lib.dev_ptr(self._stats(x.device)), mw))
+        return loss, grad, dev
+
+    def gradient_features(self, conv5_4_k1, conv3_1, conv3_sub1, labels, mask, params=None, max_workgroups=0, labelled=None,
+                          confusion=None, return_pseudo_pixels=False):
+        """(loss float64 [1], {name: gradient} for ``variable_names``) on the device for ``conv5_4_k1`` [N, h, w, 256],
+        ``conv3_1`` [N, 2h, 2w, 256], ``conv3_sub1`` [N, 4h, 4w, 64] and labels / mask [N, 32h, 32w].  ``params`` overrides
+        any of the fourteen tensors; ``max_workgroups``: 0 = the default grids, a tuning knob.  No update."""
+        self._refuse_semi(labelled=labelled, confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
+        mw = self._check_features(conv5_4_k1, conv3_1, conv3_sub1, labels, mask, max_workgroups)
+        packed = self._packed_with(params)
+        loss, grad, _ = self._feature_call(conv5_4_k1, conv3_1, conv3_sub1, labels, mask, packed, mw)
+        return loss, self._unpack(grad)
+
+    def features(self, images):
+        """``(conv5_4_k1 [N, H/32, W/32, 256], conv3_1 [N, H/16, W/16, 256], conv3_sub1 [N, H/8, W/8, 64])`` for ``images``
+        (copies): what ``step_features`` and ``gradient_features`` take.  One forward pass of the frozen branches."""
+        self.net(images, training=False)
+        return tuple(self.net.endpoint(name).clone() for name in ("conv5_4_k1", "conv3_1", "conv3_sub1"))
+
+    def step_features(self, conv5_4_k1, conv3_1, conv3_sub1, labels, mask, max_workgroups=0, labelled=None, confusion=None,
+                      return_pseudo_pixels=False):
+        """one Adam step from cached features; returns the loss (float64 device scalar) BEFORE the step"""
+        self._refuse_semi(labelled=labelled, confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
+        mw = self._check_features(conv5_4_k1, conv3_1, conv3_sub1, labels, mask, max_workgroups)
+        loss, grad, dev = self._feature_call(conv5_4_k1, conv3_1, conv3_sub1, labels, mask, None, mw)
+        self._apply(dev, grad)
+        return loss[0]
+
+
 __all__ = ["FinalLayerTrainer", "LastBlockTrainer", "LastStageTrainer", "DecoderTailTrainer", "SemiSupervisedBlockTrainer",
            "SemiSupervisedStageTrainer", "SemiSupervisedTailTrainer", "DeepTailTrainer", "SemiSupervisedDeepTailTrainer",
            "DecoderTrainer", "SemiSupervisedDecoderTrainer", "ICNetHeadTrainer", "SemiSupervisedICNetHeadTrainer",
-           "ICNetFusionTrainer"]
+           "ICNetFusionTrainer", "ICNetCascadeTrainer"]
