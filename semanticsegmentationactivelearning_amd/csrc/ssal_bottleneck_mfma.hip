@@ -871,6 +871,287 @@ __global__ __launch_bounds__(256, 3) void k_bottleneck_mfma_asym16x(BnkArgs a)
 }
 
 // =================================================================================================
+// The 128-channel blocks on EIGHT-wave workgroups (knob bnk_w8): 512 threads on the 8 x 32 tile of k_bottleneck_mfma<32>,
+// two workgroups per CU = four waves per SIMD -- k_bottleneck_o4's occupancy and per-wave work (one 32-pixel M-tile per
+// wave behind the projection, <= 128 VGPRs) without its 8 x 16 tiles: the projection halo stays 1.33x and the 16 KB
+// kernel area is filled once per 256 pixels.  The kernel area holds the projection kernel during phase A and the
+// expansion kernel behind it, as in k_bottleneck_o4; the convolution kernels stream from L1 in the quad layout.
+//
+// Phase A runs on 16-pixel HALF-tiles with v_mfma_f32_16x16x4_f32 (two 16-channel N halves per half-tile): the 340
+// halo'd pixels are 22 half-tiles = three rounds over eight waves with 22 of the 24 slots busy, where 32-pixel M-tiles
+// would take two full rounds with 11 of 16.  Like 32x32x2 the instruction is a k-ordered fmaf chain (ssal_mfma.h), so
+// the projected values are the same bits.
+// =================================================================================================
+constexpr int W8_THREADS = 512;
+constexpr long W8_MAX_ELEMS = 1L << 28;  // floats per image the eight-wave kernels take (launch_bottleneck_mfma)
+
+// projection kernel -> LDS as 16x16x4 B operands: float4 ((u, n), lane (i, g)), element e = Wp[16 u + 4 e + g][16 n + i]
+// (u = 0..7 groups of four MFMA steps, n = N half): one conflict-free ds_read_b128 per four MFMAs
+__device__ __forceinline__ void w8_fill_proj(const BnkArgs &a, float *WL)
+{
+#pragma unroll
+    for (int it = 0; it < C * F / W8_THREADS; ++it) {
+        const int e = (int)threadIdx.x + W8_THREADS * it, k = e >> 5, co = e & 31;
+        WL[((((k >> 4) * 2 + (co >> 4)) * 64 + (k & 3) * 16 + (co & 15)) << 2) + ((k >> 2) & 3)] = a.wp[e];
+    }
+}
+
+// requests the 8 activation fragments of half-tile ht (lane (i, g): pixel 16 ht + i of the row-major halo'd tile, channels
+// 16 u + 4 g .. + 3) and returns the validity of its 16 pixels (0: nothing requested, the half-tile is all padding)
+template <int HWP, int HALO, int NPIX>
+__device__ __forceinline__ unsigned w8_request(const BnkArgs &a, const float *ximg, const TileId &t, int ht, int lane,
+                                               float4 (&X)[8])
+{
+    const int i = lane & 15, g = lane >> 4;
+    const int q = ht * 16 + i;
+    const int hr = q / HWP, hc = q - hr * HWP;
+    const int pr = t.ty0 - HALO + hr, pc = t.tx0 - HALO + hc;
+    const bool valid = (q < NPIX) && (pr >= 0) && (pr < t.Hp) && (pc >= 0) && (pc < t.Wp);
+    const unsigned vm = (unsigned)__ballot(valid) & 0xffffu;  // validity is per pixel: every lane quarter carries the same bits
+    if (vm == 0u) return 0u;
+    const float *xp = valid ? ximg + ((long)(t.py + pr * a.dil) * a.W + (t.px + pc * a.dil)) * C : ximg;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) X[u] = *reinterpret_cast<const float4 *>(xp + 16 * u + 4 * g);
+    return vm;
+}
+
+// projects half-tile ht: D[pixel 4 g + r][co 16 n + i] -> BN + PReLU, exact zeros outside the image -> P rows 16 ht ..
+template <int NPIX>
+__device__ __forceinline__ void w8_project(const float *WL, float *P, int ht, unsigned vm, const float4 (&X)[8], int lane,
+                                           const float (&bs)[2], const float (&bt)[2], const float (&ba)[2])
+{
+    const int i = lane & 15, g = lane >> 4;
+    const int kp = kperm(i);  // kperm(16 + i) = 16 + kperm(i)
+    if (vm == 0u) {  // wave-uniform
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int qi = ht * 16 + 4 * g + r;
+            if (qi < NPIX) { P[qi * PSTR + kp] = 0.0f; P[qi * PSTR + 16 + kp] = 0.0f; }
+        }
+        return;
+    }
+    f32x4 acc0 = {0}, acc1 = {0};
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        asm volatile("" ::: "memory");  // keep the reads here: hoisted they would pin 64 registers
+        const float4 w0 = *reinterpret_cast<const float4 *>(WL + (((2 * u) * 64 + lane) << 2));
+        const float4 w1 = *reinterpret_cast<const float4 *>(WL + (((2 * u + 1) * 64 + lane) << 2));
+        float r0 = X[u].x, r1 = X[u].y, r2 = X[u].z, r3 = X[u].w;
+        transpose4(r0, r1, r2, r3);  // reg e of quarter g: channel 16 u + 4 e + g = k index g of step 4 u + e
+        acc0 = mfma16(r0, w0.x, acc0); acc1 = mfma16(r0, w1.x, acc1);
+        acc0 = mfma16(r1, w0.y, acc0); acc1 = mfma16(r1, w1.y, acc1);
+        acc0 = mfma16(r2, w0.z, acc0); acc1 = mfma16(r2, w1.z, acc1);
+        acc0 = mfma16(r3, w0.w, acc0); acc1 = mfma16(r3, w1.w, acc1);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int qi = ht * 16 + 4 * g + r;
+        const bool ok = (vm >> (4 * g + r)) & 1u;
+        const float v0 = ok ? prelu1(fmaf(acc0[r], bs[0], bt[0]), ba[0]) : 0.0f;
+        const float v1 = ok ? prelu1(fmaf(acc1[r], bs[1], bt[1]), ba[1]) : 0.0f;
+        if (qi < NPIX) { P[qi * PSTR + kp] = v0; P[qi * PSTR + 16 + kp] = v1; }
+    }
+}
+
+// phase A of both eight-wave kernels: wave w projects half-tiles w, w + 8, ...  The fragments of a wave's first half-tile are
+// requested before the kernel fill and the barrier, those of half-tile r + 1 before the MFMAs of half-tile r (two buffers).
+template <int HWP, int HALO, int NPIX>
+__device__ __forceinline__ void w8_proj_to_lds(const BnkArgs &a, const float *ximg, const TileId &t, float *P, float *WL,
+                                               int wave, int lane)
+{
+    constexpr int NR = ((NPIX + 15) / 16 + 7) / 8;  // rounds; a half-tile past the last one requests and writes nothing
+    float4 XA[8], XB[8];
+    unsigned vA = w8_request<HWP, HALO, NPIX>(a, ximg, t, wave, lane, XA), vB = 0u;
+    w8_fill_proj(a, WL);
+    const int i = lane & 15;
+    const float bs[2] = {a.ps[i], a.ps[16 + i]}, bt[2] = {a.pt[i], a.pt[16 + i]}, ba[2] = {a.pa[i], a.pa[16 + i]};
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < NR; r += 2) {
+        if (r + 1 < NR) vB = w8_request<HWP, HALO, NPIX>(a, ximg, t, wave + 8 * (r + 1), lane, XB);
+        __builtin_amdgcn_sched_barrier(0);
+        w8_project<NPIX>(WL, P, wave + 8 * r, vA, XA, lane, bs, bt, ba);
+        __builtin_amdgcn_sched_barrier(0);
+        if (r + 2 < NR) vA = w8_request<HWP, HALO, NPIX>(a, ximg, t, wave + 8 * (r + 2), lane, XA);
+        __builtin_amdgcn_sched_barrier(0);
+        if (r + 1 < NR) w8_project<NPIX>(WL, P, wave + 8 * (r + 1), vB, XB, lane, bs, bt, ba);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// last phase of both eight-wave kernels, k_bottleneck_o4's register plan on an 8 x 32 tile: wave w convolves M-tile w (tile
+// row w) of the LDS tensor S, then expansion (kernel in WL, quad layout) + BN + residual + PReLU as D[pixel][co] with
+// 128-byte row stores through range-checked raw buffer instructions; the residual is re-read one N-tile ahead and every
+// load of a stage is issued before that stage's stores.  SYNC: WL was written by this workgroup's threads after the last
+// barrier (regular block) -- one more barrier between the convolution and the expansion.
+template <int KH, int KW, int SW, bool SYNC>
+__device__ __forceinline__ void w8_conv_exp_store(const BnkArgs &a, const float *ximg, float *yimg, const float *S,
+                                                  const float *wconv, const float *WL, const TileId &t, int wave, int lane)
+{
+    constexpr int TW = 32;
+    const int j = lane & 31, h = lane >> 5, d = a.dil;
+    const int mt = wave;
+    constexpr unsigned kOOB = 0x80000000u;
+    const unsigned img_bytes = (unsigned)(a.H * a.W * C) * 4u;
+    const rsrc_t xrs = make_rsrc(ximg, img_bytes), yrs = make_rsrc(yimg, img_bytes);
+    const rsrc_t esrs = make_rsrc(a.es, C * 4), etrs = make_rsrc(a.et, C * 4), rars = make_rsrc(a.ra, C * 4);
+    unsigned boff[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int ti = mt * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+        const int rr = ti / TW, cc = ti - rr * TW;
+        const int pr = t.ty0 + rr, pc = t.tx0 + cc;
+        const bool ok = (pr < t.Hp) && (pc < t.Wp);
+        boff[i] = ok ? (unsigned)((((t.py + pr * d) * a.W + (t.px + pc * d)) * C + j) * 4) : kOOB;
+    }
+    float rxA[16], rxB[16];
+    auto fetch_rx = [&](int nt, float (&rx)[16]) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) rx[i] = bload(xrs, boff[i], nt * 128);
+    };
+    fetch_rx(0, rxA);  // the first residual rows travel while the convolution runs
+    float qv[16];
+    conv_tile_q<TW, KH, KW, SW, BnkArgs, 0, true>(a, S, wconv, mt, j, h, qv);
+    fetch_rx(1, rxB);
+    if (SYNC) __syncthreads();  // the expansion kernel is in WL
+    float sA, tA, aA, sB, tB, aB;
+    auto fetch_bn = [&](int nt, float &s1, float &t1, float &al) {
+        s1 = bload(esrs, j * 4, nt * 128); t1 = bload(etrs, j * 4, nt * 128); al = bload(rars, j * 4, nt * 128);
+    };
+    auto chain_step = [&](int nt, int s4, f32x16 e) {  // four MFMAs: steps 4 s4 .. 4 s4 + 3 of N-tile nt
+        asm volatile("" ::: "memory");
+        const float4 w = *reinterpret_cast<const float4 *>(WL + (((nt * 4 + s4) * 64 + lane) << 2));
+        e = mfma32(qv[ord(4 * s4 + 0)], w.x, e);
+        e = mfma32(qv[ord(4 * s4 + 1)], w.y, e);
+        e = mfma32(qv[ord(4 * s4 + 2)], w.z, e);
+        e = mfma32(qv[ord(4 * s4 + 3)], w.w, e);
+        return e;
+    };
+    auto put = [&](int nt, int i, float v) {
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), yrs, boff[i], nt * 128, 0);
+    };
+    fetch_bn(0, sA, tA, aA);
+    fetch_bn(1, sB, tB, aB);
+    f32x16 e0 = {0}, e1 = {0};
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) e0 = chain_step(0, s4, e0);
+    // stage 1: chain of N-tile 1  ||  epilogue of N-tile 0
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) {
+        e1 = chain_step(1, s4, e1);
+#pragma unroll
+        for (int i = 4 * s4; i < 4 * s4 + 4; ++i) put(0, i, prelu1(fmaf(e0[i], sA, tA) + rxA[i], aA));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    fetch_rx(2, rxA);
+    fetch_bn(2, sA, tA, aA);
+    e0 = (f32x16){0};
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) {
+        e0 = chain_step(2, s4, e0);
+#pragma unroll
+        for (int i = 4 * s4; i < 4 * s4 + 4; ++i) put(1, i, prelu1(fmaf(e1[i], sB, tB) + rxB[i], aB));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    fetch_rx(3, rxB);
+    fetch_bn(3, sB, tB, aB);
+    e1 = (f32x16){0};
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) {
+        e1 = chain_step(3, s4, e1);
+#pragma unroll
+        for (int i = 4 * s4; i < 4 * s4 + 4; ++i) put(2, i, prelu1(fmaf(e0[i], sA, tA) + rxA[i], aA));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) put(3, i, prelu1(fmaf(e1[i], sB, tB) + rxB[i], aB));
+}
+
+// regular / dilated 3x3 block: P = 10 x 34 rows (46.2 KB) + 16 KB kernel area = 62.6 KB, two workgroups per CU
+constexpr int W8_PROWS = 10 * 34;
+__global__ __launch_bounds__(W8_THREADS, 2) void k_bottleneck_w8(BnkArgs a)
+{
+    constexpr int TW = 32, HWP = TW + 2;
+    __shared__ float P[W8_PROWS * PSTR];
+    __shared__ __attribute__((aligned(16))) float WL[C * F];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const TileId t = decode_tile<TW>(a);
+    if (t.empty) return;  // whole workgroup: no barrier has been reached yet
+    const float *ximg = a.x + (long)t.n * a.H * a.W * C;
+    float *yimg = a.y + (long)t.n * a.H * a.W * C;
+    w8_proj_to_lds<HWP, 1, W8_PROWS>(a, ximg, t, P, WL, wave, lane);
+    // the expansion kernel is already in the order phase B reads it (quad layout): two float4 per thread, requested before
+    // the barrier and written over the projection kernel behind it
+    const float4 *weq = reinterpret_cast<const float4 *>(a.wq + quad::we(9));
+    const float4 wex0 = weq[threadIdx.x], wex1 = weq[threadIdx.x + W8_THREADS];
+    __syncthreads();  // P complete, the projection kernel no longer needed
+    reinterpret_cast<float4 *>(WL)[threadIdx.x] = wex0;
+    reinterpret_cast<float4 *>(WL)[threadIdx.x + W8_THREADS] = wex1;
+    w8_conv_exp_store<3, 3, HWP, true>(a, ximg, yimg, P, a.wq + quad::WC, WL, t, wave, lane);
+}
+
+// one quarter of a (5,1) M-tile on 16x16x4: result pixels u0 .. u0 + 15 of the row-major 8 x 36 grid, channels 16 n ..
+// + 15, taps and channels in ascending order; reg r of lane (i, g) = D[pixel u0 + 4 g + r][co 16 n + i]
+__device__ __forceinline__ f32x4 w8_conv5x1_quarter(const BnkArgs &a, const float *P, int u0, int n, int lane)
+{
+    constexpr int HWP = 36;
+    const int i = lane & 15, g = lane >> 4;
+    const rsrc_t wrs = make_rsrc(a.wc, 5 * F * F * 4);
+    const unsigned lo = (unsigned)(g * F + 16 * n + i) * 4u;  // W0[kh][ci = 4 s + g][co = 16 n + i]
+    const int pos = ((g & 1) << 2) + (g >> 1);  // place of channel 8 G + g inside a permuted row; channel 8 G + 4 + g: + 2
+    f32x4 acc = {0};
+#pragma unroll
+    for (int kh = 0; kh < 5; ++kh) {
+        const float *pq = P + (u0 + i + kh * HWP) * PSTR + pos;
+#pragma unroll
+        for (int s = 0; s < 8; ++s)
+            acc = mfma16(pq[8 * (s >> 1) + 2 * (s & 1)], bload(wrs, lo, kh * (F * F * 4) + s * (4 * F * 4)), acc);
+    }
+    return acc;
+}
+
+// asymmetric block: P = 12 x 36 projected rows (58.8 KB) + 16 KB kernel area = 75.1 KB, two workgroups per CU.  The (5,1)
+// pass over the 8 x 36 region is nine M-tiles: wave w takes M-tile w, and the ninth is split into four 16-pixel x 16-channel
+// quarters for waves 0..3.  As in k_bottleneck_mfma_asym16x the results wait in accumulators behind a barrier and are
+// written over P's rows 0..287; then (1,5) + expansion, one M-tile per wave.
+constexpr int W8_PROWS_ASYM = 12 * 36;
+__global__ __launch_bounds__(W8_THREADS, 2) void k_bottleneck_asym_w8(BnkArgs a)
+{
+    constexpr int TW = 32, HWP = TW + 4;
+    __shared__ float P[W8_PROWS_ASYM * PSTR];
+    __shared__ __attribute__((aligned(16))) float WL[C * F];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j = lane & 31, h = lane >> 5;
+    const TileId t = decode_tile<TW>(a);
+    if (t.empty) return;
+    const float *ximg = a.x + (long)t.n * a.H * a.W * C;
+    float *yimg = a.y + (long)t.n * a.H * a.W * C;
+    w8_proj_to_lds<HWP, 2, W8_PROWS_ASYM>(a, ximg, t, P, WL, wave, lane);
+    const float4 *weq = reinterpret_cast<const float4 *>(a.wq + quad::we(10));
+    const float4 wex0 = weq[threadIdx.x], wex1 = weq[threadIdx.x + W8_THREADS];
+    __syncthreads();  // P complete, the projection kernel no longer needed
+    reinterpret_cast<float4 *>(WL)[threadIdx.x] = wex0;
+    reinterpret_cast<float4 *>(WL)[threadIdx.x + W8_THREADS] = wex1;
+    const f32x16 r0 = conv5x1_tile<TW>(a, P, wave * 32, j, h);
+    f32x4 r1 = {0};
+    if (wave < 4) r1 = w8_conv5x1_quarter(a, P, 256 + 16 * (wave >> 1), wave & 1, lane);  // wave-uniform
+    __syncthreads();  // nobody reads the projected rows any more
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int ri = (i & 3) + 8 * (i >> 2) + 4 * h;
+        P[(wave * 32 + ri) * PSTR + kperm(j)] = r0[i];
+    }
+    if (wave < 4) {
+        const int i16 = lane & 15, g = lane >> 4;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            P[(256 + 16 * (wave >> 1) + 4 * g + r) * PSTR + 16 * (wave & 1) + kperm(i16)] = r1[r];
+    }
+    __syncthreads();  // R complete (result pixel (r, c') in row r * HWP + c'), and the expansion kernel is in WL
+    w8_conv_exp_store<1, 5, HWP, false>(a, ximg, yimg, P, a.wq + quad::WC + 5 * F * F, WL, t, wave, lane);
+}
+
+// =================================================================================================
 // Downsample bottleneck, C = 64 -> 128 (Bottleneck2_0; enet_modules.py:868-938) in one launch:
 //   main:     2x2/s2 proj (64 -> 32) + BN + PReLU -> 3x3 conv (32 -> 32) + BN + PReLU -> 1x1 exp
 //             (32 -> 128) + BN
@@ -1447,6 +1728,7 @@ Knobs &knobs()
         Knobs q;
         q.bnk_tw = 0;
         q.bnk_o4 = 2;
+        q.bnk_w8 = BNK_W8_DEFAULT;
         q.bnk_xcd = 1;
         q.asym_tw16 = ASYM_TW16_DEFAULT;
         q.bnk_qepi = BNK_QEPI_DEFAULT;
@@ -1631,8 +1913,15 @@ hipError_t launch_bottleneck_mfma(const float *x, float *y, int N, int H, int W,
     // 8x16 tiles at four workgroups per CU (k_bottleneck_o4): bnk_o4 = 1 everywhere (experiment), 2 = only where the phase
     // sub-image is at most 16 pixels wide, i.e. where 8x16 tiles are used anyway (the dilation-16 layers at 128 x 256)
     const bool o4 = !asym && Cin == C && (kn.bnk_o4 == 1 || (kn.bnk_o4 == 2 && Wp <= 16));
-    const bool asym16x = asym && kn.asym_tw16 != 0;  // 8 x 16 tiles, three workgroups per CU, R written over P
-    const bool wide = Wp > 16 && kn.bnk_tw != 16 && !o4 && !asym16x;
+    // eight-wave workgroups on 8x32 tiles (bnk_w8: 1 = the regular block at dilations 1..8, 2 (default) = also the asymmetric
+    // one) wherever the 8x32 kernels of the four-wave family would run; every other shape keeps the four-wave kernels
+    // Images above W8_MAX_ELEMS (half the 2^29-element guard of this family) keep the four-wave kernels: the eight-wave kernels
+    // were measured at the ranking shape only, and inside this limit every byte offset they form stays below 2^30.
+    const bool w8_shape = Wp > 16 && kn.bnk_tw != 16 && wq != nullptr && (long)H * W * C <= W8_MAX_ELEMS;
+    const bool w8 = !asym && !o4 && dil <= 8 && kn.bnk_w8 >= 1 && w8_shape;
+    const bool asym_w8 = asym && kn.bnk_w8 >= 2 && w8_shape;
+    const bool asym16x = asym && kn.asym_tw16 != 0 && !asym_w8;  // 8 x 16 tiles, three workgroups per CU, R written over P
+    const bool wide = (Wp > 16 && kn.bnk_tw != 16 && !o4 && !asym16x) || w8 || asym_w8;
     const int TW = wide ? 32 : 16;
     a.tiles_y = (Hp + a.TH - 1) / a.TH;
     a.tiles_x = (Wp + TW - 1) / TW;
@@ -1646,11 +1935,16 @@ hipError_t launch_bottleneck_mfma(const float *x, float *y, int N, int H, int W,
     const double f = Cin / 4.0;
     const double taps = asym ? 10.0 : 9.0;
     // one profile row per kernel symbol, as rocprofv3 lists them
-    ProfScope prof(asym16x ? "k_bottleneck_mfma_asym16x" : asym ? (wide ? "k_bottleneck_mfma_asym<32>" : "k_bottleneck_mfma_asym<16>")
+    ProfScope prof(asym_w8 ? "k_bottleneck_asym_w8" : w8 ? "k_bottleneck_w8" : asym16x ? "k_bottleneck_mfma_asym16x" : asym ? (wide ? "k_bottleneck_mfma_asym<32>" : "k_bottleneck_mfma_asym<16>")
                         : o4 ? "k_bottleneck_o4" : (wide ? "k_bottleneck_mfma<32>" : "k_bottleneck_mfma<16>"),
                    2.0 * pix * (Cin * f + taps * f * f + f * Cin),
                    4.0 * (2.0 * pix * Cin + Cin * f * 2.0 + taps * f * f), s);
-    if (asym16x) {
+    if (w8 || asym_w8) a.trace = nullptr;  // the trace buffer is laid out for four waves per workgroup
+    if (asym_w8) {
+        hipLaunchKernelGGL(k_bottleneck_asym_w8, dim3((unsigned)launch_grid), dim3(W8_THREADS), 0, s, a);
+    } else if (w8) {
+        hipLaunchKernelGGL(k_bottleneck_w8, dim3((unsigned)launch_grid), dim3(W8_THREADS), 0, s, a);
+    } else if (asym16x) {
         hipLaunchKernelGGL(k_bottleneck_mfma_asym16x, dim3((unsigned)launch_grid), dim3(256), 0, s, a);
     } else if (asym) {
         if (wide)

@@ -193,11 +193,12 @@ hipError_t launch_upsample_mfma(const float *x, float *y, const uint8_t *code, i
 // ssal_debug_set_knob for A/B runs and for the tests that compare the variants bit for bit: every setting of the
 // product build produces identical results.  Work-skipping "ablate" and the SSAL_* environment reads exist only in
 // -DSSAL_MEASURE builds).
-constexpr int IC_FRONT_DEFAULT = 3, IC_DUAL_DEFAULT = 1, ASYM_TW16_DEFAULT = 1, IG_SB_DEFAULT = 3, IC_GROUPS_DEFAULT = 1, BNK_QEPI_DEFAULT = 2;
+constexpr int IC_FRONT_DEFAULT = 3, IC_DUAL_DEFAULT = 1, ASYM_TW16_DEFAULT = 1, IG_SB_DEFAULT = 3, IC_GROUPS_DEFAULT = 1, BNK_QEPI_DEFAULT = 2, BNK_W8_DEFAULT = 2;
 constexpr int CONF_REPS_DEFAULT = 8;
 struct Knobs {
     int bnk_tw;      // 16 = force 8x16 tiles in the 128-channel bottleneck kernels
     int bnk_o4;      // k_bottleneck_o4 (8x16 tiles, four workgroups per CU): 2 (default) = where the phase sub-image is <= 16 wide, 1 = everywhere, 0 = never
+    int bnk_w8;      // eight-wave (512-thread) workgroups on 8x32 tiles, two workgroups per CU: 1 = k_bottleneck_w8 for the regular block (dilation <= 8) where k_bottleneck_mfma<32> would run, 2 (default) = also k_bottleneck_asym_w8 for the asymmetric block, 0 = the four-wave kernels (profiles/r22_ab_eight_wave_workgroups.txt); images above 2^28 elements always run the four-wave kernels
     int bnk_xcd;     // 1 = XCD-aware tile order in the 128-channel bottleneck kernels
     int bnk_qepi;    // k_bottleneck_mfma<32> epilogue: 2 (default) = D[co][pixel], 16-byte residual loads, whole-row 16-byte stores through quad_transpose4; 1 = the same without the transpose; 0 = D[pixel][co] with 4-byte accesses (rounds 1-4)
     int asym_tw16;   // asymmetric 128-channel block: 1 = k_bottleneck_mfma_asym16x (8x16 tiles, 3 workgroups per CU, (5,1) result written over the projected rows), 0 = the 8x32 / two-halves kernel
