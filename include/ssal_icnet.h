@@ -209,6 +209,50 @@ int ssal_icnet_train_cascade_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u
 /* ssal_icnet_update_fusion for the fourteen variables: only the five trained layers are re-laid-out, folded and uploaded */
 int ssal_icnet_update_cascade(ssal_icnet *net, const float *params_host, void *stream);
 
+/* ---- The semi-supervised step of the fusion and the cascade trainer (active_learning.py:226-275, 339-342; DESIGN.md
+ * section 30) ----
+ * The four gradient calls above with the targets built inside the head's gradient kernel: labelled_dev, measure, threshold,
+ * confusion_dev and pseudo_pixels_dev mean what they mean in ssal_icnet_head_grad_semi_nhwc, and sit where they sit there
+ * (after the mask; after the gradient).  The targets are constants: the loss and all 8 / 14 gradients are those of the plain
+ * call on the composed targets, bit for bit.  The raw feature pointers (the features of the undistorted frames; shapes as
+ * their counterparts) come directly after the training ones, all or none; x_raw_dev likewise after x_dev.  With a raw side
+ * and labelled_dev given, the trained blocks and the head run on the raw features first, through the same workspace slots,
+ * and a target-only launch leaves one packed byte per loss pixel; the training side follows (the images entries run the
+ * trunk twice, up to the trainer's stop).  with_raw != 0 sizes the workspace for that byte plane: n * 16h * 16w (fusion
+ * features entry), n * 32h * 32w (cascade features entry), n * h * w (images entries) bytes more.  Statuses as the plain
+ * entries', judged before any device work; raw pointers given in part: SSAL_EINVAL; an unknown measure: SSAL_ENOTIMPL. */
+int64_t ssal_icnet_fusion_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw);
+int ssal_icnet_fusion_grad_semi_nhwc(const float *sub24_dev, const float *conv3_sub1_dev, const float *sub24_raw_dev,
+                                     const float *conv3_sub1_raw_dev, int n, int h, int w, int classes,
+                                     const float *params_dev, const uint8_t *labels_dev, const float *mask_dev,
+                                     const uint8_t *labelled_dev, int measure, float threshold, float weight,
+                                     float label_smoothing, const float *stats_dev, int max_workgroups, double *loss_dev,
+                                     float *grad_dev, int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev,
+                                     int64_t ws_bytes, void *stream);
+int64_t ssal_icnet_train_fusion_semi_workspace_bytes(const ssal_icnet *net, int n, int h, int w, int with_raw);
+int ssal_icnet_train_fusion_semi_nhwc(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h,
+                                      int w, const uint8_t *labels_dev, const float *mask_dev, const uint8_t *labelled_dev,
+                                      int measure, float threshold, const float *params_dev, float weight,
+                                      float label_smoothing, const float *stats_dev, int max_workgroups, double *loss_dev,
+                                      float *grad_dev, int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev,
+                                      int64_t ws_bytes, void *stream);
+int64_t ssal_icnet_cascade_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw);
+int ssal_icnet_cascade_grad_semi_nhwc(const float *conv5_4_k1_dev, const float *conv3_1_dev, const float *conv3_sub1_dev,
+                                      const float *conv5_4_k1_raw_dev, const float *conv3_1_raw_dev,
+                                      const float *conv3_sub1_raw_dev, int n, int h, int w, int classes,
+                                      const float *params_dev, const uint8_t *labels_dev, const float *mask_dev,
+                                      const uint8_t *labelled_dev, int measure, float threshold, float weight,
+                                      float label_smoothing, const float *stats_dev, int max_workgroups, double *loss_dev,
+                                      float *grad_dev, int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev,
+                                      int64_t ws_bytes, void *stream);
+int64_t ssal_icnet_train_cascade_semi_workspace_bytes(const ssal_icnet *net, int n, int h, int w, int with_raw);
+int ssal_icnet_train_cascade_semi_nhwc(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h,
+                                       int w, const uint8_t *labels_dev, const float *mask_dev, const uint8_t *labelled_dev,
+                                       int measure, float threshold, const float *params_dev, float weight,
+                                       float label_smoothing, const float *stats_dev, int max_workgroups, double *loss_dev,
+                                       float *grad_dev, int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev,
+                                       int64_t ws_bytes, void *stream);
+
 /* Stand-alone fused convolution (the operator every ICNet layer is built from; also the per-block parity hook):
  * y = [relu]( BN(conv2d(x, kernel HWIO, strides s, dilations d, "SAME")) [+ res] ), BN given as mean / variance /
  * gamma / beta (all NULL: no batch-norm; bias_dev optional).  upsample2x != 0 runs the conv on

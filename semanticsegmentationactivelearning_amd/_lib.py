@@ -195,6 +195,19 @@ PROTOTYPES = {
     "ssal_icnet_train_cascade_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
     "ssal_icnet_train_cascade_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
     "ssal_icnet_update_cascade": (_i, [_vp, _vp, _vp]),
+    # ---- the semi-supervised step of the two (include/ssal_icnet.h) ----
+    "ssal_icnet_fusion_grad_semi_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
+    "ssal_icnet_fusion_grad_semi_nhwc": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _vp, _i,
+                                              _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_icnet_train_fusion_semi_workspace_bytes": (_i64, [_vp, _i, _i, _i, _i]),
+    "ssal_icnet_train_fusion_semi_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _f, _f, _vp, _i, _vp,
+                                               _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_icnet_cascade_grad_semi_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
+    "ssal_icnet_cascade_grad_semi_nhwc": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _f,
+                                               _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_icnet_train_cascade_semi_workspace_bytes": (_i64, [_vp, _i, _i, _i, _i]),
+    "ssal_icnet_train_cascade_semi_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _f, _f, _vp, _i, _vp,
+                                                _vp, _vp, _vp, _vp, _i64, _vp]),
     # ---- PNG decode (include/ssal_enet.h) ----
     "ssal_png_plan": (_i64, [_i64, _vp]),
     "ssal_png_decode_nhwc": (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),

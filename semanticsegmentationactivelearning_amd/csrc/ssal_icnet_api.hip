@@ -1311,6 +1311,253 @@ SSAL_API int ssal_icnet_update_cascade(ssal_icnet *net, const float *params_host
 }
 
 // ------------------------------------------------------------------------------------------------
+// the semi-supervised step of the fusion and the cascade trainer: the plain entries' buffers, then
+// head_semi_carve's (the confusion replicas; with a raw side one packed target byte per loss pixel)
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+// the training tail of a semi call, as head_semi_tail: `grad` launches the gradient with the kernel's semi argument
+template <typename Launch>
+int deep_semi_tail(const HeadSemiWs &sw, int classes, const uint8_t *labelled_dev, int measure, float threshold,
+                   const uint8_t *tgt, int64_t *confusion_dev, int64_t *pseudo_pixels_dev, hipStream_t s, Launch grad)
+{
+    const int reps = ssal::knobs().conf_reps;
+    if (confusion_dev) HIP_TRY(hipMemsetAsync(sw.rep, 0, (size_t)reps * ssal::conf_rep_stride(classes * classes) * 8, s));
+    const IcnetHeadSemi sa = {labelled_dev, measure, threshold, tgt, nullptr, confusion_dev ? sw.rep : nullptr, reps,
+                              (unsigned long long *)pseudo_pixels_dev};
+    HIP_TRY(grad(&sa));
+    if (confusion_dev) HIP_TRY(launch_confusion_fold(sw.rep, reps, classes, confusion_dev, s));
+    return SSAL_OK;
+}
+
+// the raw pointers of a features entry come all or none
+int raw_all_or_none(int given, int of)
+{
+    if (given != 0 && given != of) return fail(SSAL_EINVAL, "the raw feature pointers must be given together (%d of %d)", given, of);
+    return SSAL_OK;
+}
+
+}  // namespace
+
+SSAL_API int64_t ssal_icnet_fusion_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw)
+{
+    if (!fusion_dims_ok(n, h, w, classes)) return -1;
+    Bump b(nullptr, 0);
+    (void)fusion_carve(b, n, h, w, classes, true);
+    (void)head_semi_carve(b, n, 2 * h, 2 * w, classes, with_raw != 0);
+    return b.off + 256;
+}
+
+SSAL_API int ssal_icnet_fusion_grad_semi_nhwc(const float *sub24_dev, const float *conv3_sub1_dev, const float *sub24_raw_dev,
+                                              const float *conv3_sub1_raw_dev, int n, int h, int w, int classes,
+                                              const float *params_dev, const uint8_t *labels_dev, const float *mask_dev,
+                                              const uint8_t *labelled_dev, int measure, float threshold, float weight,
+                                              float label_smoothing, const float *stats_dev, int max_workgroups,
+                                              double *loss_dev, float *grad_dev, int64_t *confusion_dev,
+                                              int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    int rc = fusion_check(n, h, w, classes, max_workgroups);
+    if (rc) return rc;
+    if ((rc = head_semi_check(sub24_dev && conv3_sub1_dev && params_dev && stats_dev, labels_dev, mask_dev, labelled_dev,
+                              measure, loss_dev, grad_dev, ws_dev)))
+        return rc;
+    const bool raw = sub24_raw_dev != nullptr;
+    if ((rc = raw_all_or_none((sub24_raw_dev != nullptr) + (conv3_sub1_raw_dev != nullptr), 2))) return rc;
+    Bump b(ws_dev, ws_bytes);
+    const IcnetFusionWs t = fusion_carve(b, n, h, w, classes, true);
+    const HeadSemiWs sw = head_semi_carve(b, n, 2 * h, 2 * w, classes, raw);
+    if (!b.ok)
+        return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
+                    (long long)ssal_icnet_fusion_grad_semi_workspace_bytes(n, h, w, classes, raw), (long long)ws_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    // the undistorted frame's features matter only where an image is unlabelled: the block and the head on them into t's
+    // slots, the target launch; then the training features go through the same slots
+    const uint8_t *tgt = nullptr;
+    if (raw && labelled_dev) {
+        const IcnetHeadSemi sa = {labelled_dev, measure, threshold, nullptr, nullptr, nullptr, 0, nullptr};
+        HIP_TRY(launch_icnet_fusion_targets(sub24_raw_dev, conv3_sub1_raw_dev, n, h, w, classes, params_dev, stats_dev,
+                                            max_workgroups, t, sa, sw.tgt, s));
+        tgt = sw.tgt;
+    }
+    return deep_semi_tail(sw, classes, labelled_dev, measure, threshold, tgt, confusion_dev, pseudo_pixels_dev, s,
+                          [&](const IcnetHeadSemi *sa) {
+                              return launch_icnet_fusion_grad(sub24_dev, conv3_sub1_dev, n, h, w, classes, params_dev, stats_dev,
+                                                              labels_dev, mask_dev, weight, label_smoothing, max_workgroups, t,
+                                                              loss_dev, grad_dev, s, sa);
+                          });
+}
+
+SSAL_API int64_t ssal_icnet_train_fusion_semi_workspace_bytes(const ssal_icnet *net, int n, int h, int w, int with_raw)
+{
+    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 32 || w % 32) return -1;
+    Bump b(nullptr, 0);
+    b.off = carve(net, nullptr, 0, n, h, w).bytes;
+    (void)fusion_carve(b, n, h / 16, w / 16, net->classes, false);
+    (void)head_semi_carve(b, n, h / 8, w / 8, net->classes, with_raw != 0);
+    return b.off + 256;
+}
+
+SSAL_API int ssal_icnet_train_fusion_semi_nhwc(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
+                                               int h, int w, const uint8_t *labels_dev, const float *mask_dev,
+                                               const uint8_t *labelled_dev, int measure, float threshold,
+                                               const float *params_dev, float weight, float label_smoothing,
+                                               const float *stats_dev, int max_workgroups, double *loss_dev, float *grad_dev,
+                                               int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev,
+                                               int64_t ws_bytes, void *stream)
+{
+    int rc = check_dims(net, n, h, w);
+    if (rc) return rc;
+    if ((rc = fusion_check(n, h / 16, w / 16, net->classes, max_workgroups))) return rc;
+    if ((rc = head_semi_check(x_dev && params_dev && stats_dev, labels_dev, mask_dev, labelled_dev, measure, loss_dev, grad_dev,
+                              ws_dev)))
+        return rc;
+    IcWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
+    Bump b(ws_dev, ws_bytes);
+    b.off = W.bytes;
+    IcnetFusionWs t = fusion_carve(b, n, h / 16, w / 16, net->classes, false);
+    const HeadSemiWs sw = head_semi_carve(b, n, h / 8, w / 8, net->classes, x_raw_dev != nullptr);
+    if (!W.ok || !b.ok)
+        return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
+                    (long long)ssal_icnet_train_fusion_semi_workspace_bytes(net, n, h, w, x_raw_dev != nullptr),
+                    (long long)ws_bytes);
+    t.proj = W.act.at("conv3_sub1_proj");
+    t.sub12 = W.act.at("sub12_sum");
+    t.head.lq = W.act.at("conv6_cls");
+    const int K = net->classes;
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<Grp> one(1);
+    // the undistorted frames go through the trunk only where an image is unlabelled, and first: the target launch leaves one
+    // byte per loss pixel, so the training frames can go through the same slots afterwards
+    const uint8_t *tgt = nullptr;
+    if (x_raw_dev && labelled_dev) {
+        one[0] = {W, x_raw_dev, n, s};
+        HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false, false));
+        const IcnetHeadSemi sa = {labelled_dev, measure, threshold, nullptr, nullptr, nullptr, 0, nullptr};
+        HIP_TRY(launch_icnet_fusion_targets(W.act.at("sub24_sum"), W.act.at("conv3_sub1"), n, h / 16, w / 16, K, params_dev,
+                                            stats_dev, max_workgroups, t, sa, sw.tgt, s));
+        tgt = sw.tgt;
+    }
+    one[0] = {W, x_dev, n, s};
+    HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false, false));
+    return deep_semi_tail(sw, K, labelled_dev, measure, threshold, tgt, confusion_dev, pseudo_pixels_dev, s,
+                          [&](const IcnetHeadSemi *sa) {
+                              return launch_icnet_fusion_grad(W.act.at("sub24_sum"), W.act.at("conv3_sub1"), n, h / 16, w / 16, K,
+                                                              params_dev, stats_dev, labels_dev, mask_dev, weight,
+                                                              label_smoothing, max_workgroups, t, loss_dev, grad_dev, s, sa);
+                          });
+}
+
+SSAL_API int64_t ssal_icnet_cascade_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw)
+{
+    if (n <= 0 || !cascade_dims_ok(n, h, w, classes)) return -1;
+    Bump b(nullptr, 0);
+    (void)cascade_carve(b, n, h, w, classes, true);
+    (void)head_semi_carve(b, n, 4 * h, 4 * w, classes, with_raw != 0);
+    return b.off + 256;
+}
+
+SSAL_API int ssal_icnet_cascade_grad_semi_nhwc(const float *conv5_4_k1_dev, const float *conv3_1_dev,
+                                               const float *conv3_sub1_dev, const float *conv5_4_k1_raw_dev,
+                                               const float *conv3_1_raw_dev, const float *conv3_sub1_raw_dev, int n, int h,
+                                               int w, int classes, const float *params_dev, const uint8_t *labels_dev,
+                                               const float *mask_dev, const uint8_t *labelled_dev, int measure,
+                                               float threshold, float weight, float label_smoothing, const float *stats_dev,
+                                               int max_workgroups, double *loss_dev, float *grad_dev, int64_t *confusion_dev,
+                                               int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    int rc = cascade_check(n, h, w, classes, max_workgroups);
+    if (rc) return rc;
+    if ((rc = head_semi_check(conv5_4_k1_dev && conv3_1_dev && conv3_sub1_dev && params_dev && stats_dev, labels_dev, mask_dev,
+                              labelled_dev, measure, loss_dev, grad_dev, ws_dev)))
+        return rc;
+    const bool raw = conv5_4_k1_raw_dev != nullptr;
+    if ((rc = raw_all_or_none((conv5_4_k1_raw_dev != nullptr) + (conv3_1_raw_dev != nullptr) + (conv3_sub1_raw_dev != nullptr),
+                              3)))
+        return rc;
+    Bump b(ws_dev, ws_bytes);
+    const IcnetCascadeWs t = cascade_carve(b, n, h, w, classes, true);
+    const HeadSemiWs sw = head_semi_carve(b, n, 4 * h, 4 * w, classes, raw);
+    if (!b.ok)
+        return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
+                    (long long)ssal_icnet_cascade_grad_semi_workspace_bytes(n, h, w, classes, raw), (long long)ws_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    const uint8_t *tgt = nullptr;
+    if (raw && labelled_dev) {  // both blocks and the head on the undistorted frame's features first, through t's slots
+        const IcnetHeadSemi sa = {labelled_dev, measure, threshold, nullptr, nullptr, nullptr, 0, nullptr};
+        HIP_TRY(launch_icnet_cascade_targets(conv5_4_k1_raw_dev, conv3_1_raw_dev, conv3_sub1_raw_dev, n, h, w, classes,
+                                             params_dev, stats_dev, max_workgroups, t, sa, sw.tgt, s));
+        tgt = sw.tgt;
+    }
+    return deep_semi_tail(sw, classes, labelled_dev, measure, threshold, tgt, confusion_dev, pseudo_pixels_dev, s,
+                          [&](const IcnetHeadSemi *sa) {
+                              return launch_icnet_cascade_grad(conv5_4_k1_dev, conv3_1_dev, conv3_sub1_dev, n, h, w, classes,
+                                                               params_dev, stats_dev, labels_dev, mask_dev, weight,
+                                                               label_smoothing, max_workgroups, t, loss_dev, grad_dev, s, sa);
+                          });
+}
+
+SSAL_API int64_t ssal_icnet_train_cascade_semi_workspace_bytes(const ssal_icnet *net, int n, int h, int w, int with_raw)
+{
+    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 32 || w % 32) return -1;
+    Bump b(nullptr, 0);
+    b.off = carve(net, nullptr, 0, n, h, w).bytes;
+    (void)cascade_carve(b, n, h / 32, w / 32, net->classes, false);
+    (void)head_semi_carve(b, n, h / 8, w / 8, net->classes, with_raw != 0);
+    return b.off + 256;
+}
+
+SSAL_API int ssal_icnet_train_cascade_semi_nhwc(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
+                                                int h, int w, const uint8_t *labels_dev, const float *mask_dev,
+                                                const uint8_t *labelled_dev, int measure, float threshold,
+                                                const float *params_dev, float weight, float label_smoothing,
+                                                const float *stats_dev, int max_workgroups, double *loss_dev, float *grad_dev,
+                                                int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev,
+                                                int64_t ws_bytes, void *stream)
+{
+    int rc = check_dims(net, n, h, w);
+    if (rc) return rc;
+    if ((rc = cascade_check(n, h / 32, w / 32, net->classes, max_workgroups))) return rc;
+    if ((rc = head_semi_check(x_dev && params_dev && stats_dev, labels_dev, mask_dev, labelled_dev, measure, loss_dev, grad_dev,
+                              ws_dev)))
+        return rc;
+    IcWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
+    Bump b(ws_dev, ws_bytes);
+    b.off = W.bytes;
+    IcnetCascadeWs t = cascade_carve(b, n, h / 32, w / 32, net->classes, false);
+    const HeadSemiWs sw = head_semi_carve(b, n, h / 8, w / 8, net->classes, x_raw_dev != nullptr);
+    if (!W.ok || !b.ok)
+        return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
+                    (long long)ssal_icnet_train_cascade_semi_workspace_bytes(net, n, h, w, x_raw_dev != nullptr),
+                    (long long)ws_bytes);
+    t.proj = W.act.at("conv3_1_sub2_proj");
+    t.sub24 = W.act.at("sub24_sum");
+    t.fusion.proj = W.act.at("conv3_sub1_proj");
+    t.fusion.sub12 = W.act.at("sub12_sum");
+    t.fusion.head.lq = W.act.at("conv6_cls");
+    const int K = net->classes;
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<Grp> one(1);
+    const uint8_t *tgt = nullptr;
+    if (x_raw_dev && labelled_dev) {  // the undistorted frames first, through the same slots (see the fusion entry)
+        one[0] = {W, x_raw_dev, n, s};
+        HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false, false, false));
+        const IcnetHeadSemi sa = {labelled_dev, measure, threshold, nullptr, nullptr, nullptr, 0, nullptr};
+        HIP_TRY(launch_icnet_cascade_targets(W.act.at("conv5_4_k1"), W.act.at("conv3_1"), W.act.at("conv3_sub1"), n, h / 32,
+                                             w / 32, K, params_dev, stats_dev, max_workgroups, t, sa, sw.tgt, s));
+        tgt = sw.tgt;
+    }
+    one[0] = {W, x_dev, n, s};
+    HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false, false, false));
+    return deep_semi_tail(sw, K, labelled_dev, measure, threshold, tgt, confusion_dev, pseudo_pixels_dev, s,
+                          [&](const IcnetHeadSemi *sa) {
+                              return launch_icnet_cascade_grad(W.act.at("conv5_4_k1"), W.act.at("conv3_1"),
+                                                               W.act.at("conv3_sub1"), n, h / 32, w / 32, K, params_dev,
+                                                               stats_dev, labels_dev, mask_dev, weight, label_smoothing,
+                                                               max_workgroups, t, loss_dev, grad_dev, s, sa);
+                          });
+}
+
+// ------------------------------------------------------------------------------------------------
 // stand-alone operators
 // ------------------------------------------------------------------------------------------------
 SSAL_API int64_t ssal_conv_bn_workspace_bytes(int kh, int kw, int cin, int cout)

@@ -48,8 +48,9 @@ struct IcnetHeadSemi {
 
 // The whole tail: lq = conv6_cls(resize_2x(sub12_sum)) through launch_igemm (the forward path's own launch, reading the
 // packed head), then the fused loss + gradient kernel and the fold.  loss [1] float64; grad [128 K + K] fp32.
-// hw_out (never with semi; NULL = not written): [N][icnet_head_tiles][36][K], every tile's pull-back of dL/dlq onto its
-// 6 x 6 window of sub12_sum (first pixel (4 ty, 4 tx)), un-normalised; a window pixel two tiles share holds each one's part.
+// hw_out (NULL = not written; with semi: DESIGN.md section 30): [N][icnet_head_tiles][36][K], every tile's pull-back of dL/dlq
+// onto its 6 x 6 window of sub12_sum (first pixel (4 ty, 4 tx)), un-normalised; a window pixel two tiles share holds each
+// one's part.
 hipError_t launch_icnet_head_grad(const float *sub12, int N, int h8, int w8, int K, const float *head,
                                   const uint8_t *labels, const float *mask, float weight, float label_smoothing,
                                   int max_workgroups, const IcnetHeadWs &ws, double *loss, float *grad, hipStream_t s,

@@ -10,7 +10,8 @@
 // and 23).  No floating-point atomics: two runs give the same bits.
 // The semi-supervised step (active_learning.py:226-275, 339-342) is k_icnet_head_grad<K, true>: the
 // targets of an unlabelled image are built from the logits the kernel holds, the training-pass confusion matrix and the
-// pseudo-pixel counts leave through integer atomics.
+// pseudo-pixel counts leave through integer atomics.  k_icnet_head_grad<K, true, true> is that step with the pull-back
+// windows of the fusion and the cascade trainer.
 #include <type_traits>
 
 #include "ssal_confusion.h"
@@ -110,21 +111,24 @@ __device__ __forceinline__ float resize_weight(int dst, int src, int size, int f
 // into replica (workgroup % reps) at the end; a loss pixel belongs to exactly one tile.  sa.pseudo_pixels[n] += the image's
 // pixels with pseudo mask 1 (one integer atomic per wave, tile and unlabelled image).
 struct IcnetHeadPlain {};  // SEMI = false: no argument
-// HWOUT (never with SEMI): every tile also leaves its pull-back window hw [36][K] as it stands --
-// partial sums where the window overlaps a neighbouring tile's -- at hw[(n tiles + tile) 36 K], for the fusion trainer's
-// gather into dL/dsub12_sum.  Nothing else changes: loss, dKernel and dBias are the bits of the plain instantiation.
+// HWOUT: every tile also leaves its pull-back window hw [36][K] as it stands -- partial sums where
+// the window overlaps a neighbouring tile's -- at hw[(n tiles + tile) 36 K], for the fusion trainer's gather into
+// dL/dsub12_sum.  Nothing else changes: loss, dKernel and dBias are the bits of the plain instantiation.
 struct IcnetHeadHw { float *hw; };
+// SEMI and HWOUT: the semi-supervised step of the fusion and the cascade trainer.  The targets are
+// constants, so the window is the plain one's on the composed targets; a target-only launch never takes this form.
+struct IcnetHeadSemiHw : IcnetHeadSemi { float *hw; };
+template <bool SEMI, bool HWOUT>
+using IcnetHeadArg = std::conditional_t<SEMI, std::conditional_t<HWOUT, IcnetHeadSemiHw, IcnetHeadSemi>,
+                                        std::conditional_t<HWOUT, IcnetHeadHw, IcnetHeadPlain>>;
 
 template <int K, bool SEMI, bool HWOUT = false>
 __global__ __launch_bounds__(256) void k_icnet_head_grad(const float *__restrict__ x, const float *__restrict__ lq, int N,
                                                          int h8, int w8, const uint8_t *__restrict__ labels,
                                                          const float *__restrict__ mask, float weight, float on_value,
                                                          float off_value, float *__restrict__ part,
-                                                         double *__restrict__ lpart,
-                                                         std::conditional_t<SEMI, IcnetHeadSemi,
-                                                                            std::conditional_t<HWOUT, IcnetHeadHw, IcnetHeadPlain>> sa)
+                                                         double *__restrict__ lpart, IcnetHeadArg<SEMI, HWOUT> sa)
 {
-    static_assert(!(SEMI && HWOUT), "the window output belongs to the plain step");
     constexpr int K4 = (K + 3) / 4 * 4, KB = K4 / 4;
     constexpr int KLD = K4 % 8 == 0 ? K4 + 4 : K4;  // row stride of the LDS planes: quads of neighbouring rows on other banks
     constexpr int BIG = 256 * KLD > IH_SP * (128 + KLD) ? 256 * KLD : IH_SP * (128 + KLD);
@@ -470,7 +474,6 @@ hipError_t launch_icnet_head_grad(const float *sub12, int N, int h8, int w8, int
                                   int max_workgroups, const IcnetHeadWs &ws, double *loss, float *grad, hipStream_t s,
                                   const IcnetHeadSemi *semi, float *hw_out)
 {
-    if (semi && hw_out) return hipErrorInvalidValue;
     if (N < 1 || K < 2 || K > 32 || max_workgroups < 0 || !icnet_head_fits(h8, w8) || !icnet_head_semi_ok(semi))
         return hipErrorInvalidValue;
     const int G = icnet_head_workgroups(h8, w8, max_workgroups);
@@ -487,7 +490,7 @@ hipError_t launch_icnet_head_grad(const float *sub12, int N, int h8, int w8, int
     if (e != hipSuccess) return e;
     const float on_value = 1.0f - label_smoothing, off_value = label_smoothing / ((float)K - 1.0f);
     const double pix = (double)N * h8 * w8;
-    if (hw_out) {
+    if (hw_out && !semi) {
         ProfScope prof("k_icnet_head_grad_hw", 64.0 * pix * 12.0 * K + 2.0 * pix * 128 * K,
                        4.0 * pix * 128 + 4.0 * 4 * pix * K + 64.0 * pix * (1 + 4) + 4.0 * G * 129.0 * K +
                            4.0 * N * icnet_head_tiles(h8, w8) * IH_SP * K, s);
@@ -511,6 +514,28 @@ hipError_t launch_icnet_head_grad(const float *sub12, int N, int h8, int w8, int
     case KK:                                                                                                           \
         hipLaunchKernelGGL((k_icnet_head_grad<KK, false>), dim3(G), dim3(256), 0, s, sub12, ws.lq, N, h8, w8, labels,   \
                            mask, weight, on_value, off_value, ws.part, ws.lpart, IcnetHeadPlain{});                    \
+        break;
+        switch (K) {
+            SSAL_IH_CASES
+        default:
+            return hipErrorInvalidValue;
+        }
+#undef SSAL_IH
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    } else if (hw_out) {
+        IcnetHeadSemiHw sa;
+        static_cast<IcnetHeadSemi &>(sa) = *semi;
+        sa.tgt_out = nullptr;
+        if (!sa.labelled) sa.tgt_in = nullptr;
+        sa.hw = hw_out;
+        ProfScope prof("k_icnet_head_grad_semi_hw", 64.0 * pix * 12.0 * K + 2.0 * pix * 128 * K,
+                       4.0 * pix * 128 + 4.0 * 4 * pix * K + 64.0 * pix * (1 + 4) + 4.0 * G * 129.0 * K +
+                           4.0 * N * icnet_head_tiles(h8, w8) * IH_SP * K, s);
+#define SSAL_IH(KK)                                                                                                    \
+    case KK:                                                                                                           \
+        hipLaunchKernelGGL((k_icnet_head_grad<KK, true, true>), dim3(G), dim3(256), 0, s, sub12, ws.lq, N, h8, w8,      \
+                           labels, mask, weight, on_value, off_value, ws.part, ws.lpart, sa);                          \
         break;
         switch (K) {
             SSAL_IH_CASES

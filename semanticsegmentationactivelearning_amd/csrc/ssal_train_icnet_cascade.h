@@ -41,10 +41,18 @@ struct IcnetCascadeWs {
     IcnetFusionWs fusion;
 };
 
-// loss [1] float64; grad [icnet_cascade_floats(K)] fp32 in the packed order
+// loss [1] float64; grad [icnet_cascade_floats(K)] fp32 in the packed order.  semi (NULL = the plain
+// step, launch for launch): handed on to launch_icnet_fusion_grad
 hipError_t launch_icnet_cascade_grad(const float *c54, const float *c31, const float *c3, int N, int h32, int w32, int K,
                                      const float *params, const float *stats, const uint8_t *labels, const float *mask,
                                      float weight, float label_smoothing, int max_workgroups, const IcnetCascadeWs &ws,
-                                     double *loss, float *grad, hipStream_t s);
+                                     double *loss, float *grad, hipStream_t s, const IcnetHeadSemi *semi = nullptr);
+
+// The target phase on the features of the undistorted frames: the pack and this block's two forward launches on them into
+// ws.proj / ws.sub24, then launch_icnet_fusion_targets on that sub24_sum -> tgt [N, 32 h32, 32 w32].  The training features go
+// through the same slots afterwards (launch_icnet_cascade_grad with semi.tgt_in = tgt).
+hipError_t launch_icnet_cascade_targets(const float *c54_raw, const float *c31_raw, const float *c3_raw, int N, int h32,
+                                        int w32, int K, const float *params, const float *stats, int max_workgroups,
+                                        const IcnetCascadeWs &ws, const IcnetHeadSemi &semi, uint8_t *tgt, hipStream_t s);
 
 }  // namespace ssal

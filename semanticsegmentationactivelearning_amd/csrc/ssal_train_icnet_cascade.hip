@@ -218,14 +218,12 @@ __global__ __launch_bounds__(128) void k_icnet_cascade_gamma(const float *__rest
     grad[(b ? CA_GD : CA_GC) + co] = ((sum - stats[2 * b * 128 + co] * rbeta) * rstd) * scale;
 }
 
-hipError_t launch_icnet_cascade_grad(const float *c54, const float *c31, const float *c3, int N, int h32, int w32, int K,
-                                     const float *params, const float *stats, const uint8_t *labels, const float *mask,
-                                     float weight, float label_smoothing, int max_workgroups, const IcnetCascadeWs &ws,
-                                     double *loss, float *grad, hipStream_t s)
+// the pack, then the forward path's own launches (ssal_icnet_api.hip, run_trunk) on the weights being trained:
+// ws.proj = BN(conv3_1_sub2_proj(c31)), ws.sub24 = sub24_sum
+static hipError_t cascade_forward(const float *c54, const float *c31, int N, int h32, int w32, const float *params,
+                                  const float *stats, const IcnetCascadeWs &ws, hipStream_t s)
 {
-    if (N < 1 || K < 2 || K > 32 || max_workgroups < 0 || !icnet_cascade_fits(h32, w32)) return hipErrorInvalidValue;
-    const int h16 = 2 * h32, w16 = 2 * w32, h8 = 2 * h16, w8 = 2 * w16;
-    const double pix8 = (double)N * h8 * w8, pix16 = (double)N * h16 * w16;
+    const int h16 = 2 * h32, w16 = 2 * w32;
     hipError_t e;
     {
         ProfScope prof("k_icnet_cascade_pack", 0.0, 8.0 * CA_FUSION, s);
@@ -233,15 +231,40 @@ hipError_t launch_icnet_cascade_grad(const float *c54, const float *c31, const f
                            ws.wt_c, ws.wt_d, ws.rows);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    // the forward path's own launches (ssal_icnet_api.hip, run_trunk) on the weights being trained
     e = launch_igemm(c31, N, h16, w16, 256, ws.wt_d, 1, 1, 128, 1, 1, ws.rows + 256, ws.rows + 384, nullptr, false, false,
                      ws.proj, s);
     if (e != hipSuccess) return e;
-    e = launch_igemm(c54, N, h32, w32, 256, ws.wt_c, 3, 3, 128, 1, 2, ws.rows, ws.rows + 128, ws.proj, true, true, ws.sub24, s);
+    return launch_igemm(c54, N, h32, w32, 256, ws.wt_c, 3, 3, 128, 1, 2, ws.rows, ws.rows + 128, ws.proj, true, true, ws.sub24,
+                        s);
+}
+
+hipError_t launch_icnet_cascade_targets(const float *c54_raw, const float *c31_raw, const float *c3_raw, int N, int h32,
+                                        int w32, int K, const float *params, const float *stats, int max_workgroups,
+                                        const IcnetCascadeWs &ws, const IcnetHeadSemi &semi, uint8_t *tgt, hipStream_t s)
+{
+    if (N < 1 || K < 2 || K > 32 || max_workgroups < 0 || !icnet_cascade_fits(h32, w32) || !c54_raw || !c31_raw)
+        return hipErrorInvalidValue;
+    if (semi.labelled) {  // (every image labelled: no pseudo target is read)
+        const hipError_t e = cascade_forward(c54_raw, c31_raw, N, h32, w32, params, stats, ws, s);
+        if (e != hipSuccess) return e;
+    }
+    return launch_icnet_fusion_targets(ws.sub24, c3_raw, N, 2 * h32, 2 * w32, K, params + CA_FUSION, stats + 4 * 128,
+                                       max_workgroups, ws.fusion, semi, tgt, s);
+}
+
+hipError_t launch_icnet_cascade_grad(const float *c54, const float *c31, const float *c3, int N, int h32, int w32, int K,
+                                     const float *params, const float *stats, const uint8_t *labels, const float *mask,
+                                     float weight, float label_smoothing, int max_workgroups, const IcnetCascadeWs &ws,
+                                     double *loss, float *grad, hipStream_t s, const IcnetHeadSemi *semi)
+{
+    if (N < 1 || K < 2 || K > 32 || max_workgroups < 0 || !icnet_cascade_fits(h32, w32)) return hipErrorInvalidValue;
+    const int h16 = 2 * h32, w16 = 2 * w32, h8 = 2 * h16, w8 = 2 * w16;
+    const double pix8 = (double)N * h8 * w8, pix16 = (double)N * h16 * w16;
+    hipError_t e = cascade_forward(c54, c31, N, h32, w32, params, stats, ws, s);
     if (e != hipSuccess) return e;
     // section 28 as it stands: sub12_sum, the head, the loss, its eight gradients, and g behind sub12_sum's ReLU
     e = launch_icnet_fusion_grad(ws.sub24, c3, N, h16, w16, K, params + CA_FUSION, stats + 4 * 128, labels, mask, weight,
-                                 label_smoothing, max_workgroups, ws.fusion, loss, grad + CA_FUSION, s);
+                                 label_smoothing, max_workgroups, ws.fusion, loss, grad + CA_FUSION, s, semi);
     if (e != hipSuccess) return e;
     {
         long G = dx_tiles(N, h8, w8);

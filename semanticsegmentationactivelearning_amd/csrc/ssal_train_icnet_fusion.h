@@ -48,10 +48,20 @@ struct IcnetFusionWs {
     IcnetHeadWs head;
 };
 
-// loss [1] float64; grad [icnet_fusion_floats(K)] fp32 in the packed order
+// loss [1] float64; grad [icnet_fusion_floats(K)] fp32 in the packed order.  semi (NULL = the plain
+// step, launch for launch): handed to the head launch, which then builds the targets, counts the confusion replicas and the
+// pseudo pixels; everything behind dL/dlogit is the plain step's.
 hipError_t launch_icnet_fusion_grad(const float *sub24, const float *c3, int N, int h16, int w16, int K, const float *params,
                                     const float *stats, const uint8_t *labels, const float *mask, float weight,
                                     float label_smoothing, int max_workgroups, const IcnetFusionWs &ws, double *loss,
-                                    float *grad, hipStream_t s);
+                                    float *grad, hipStream_t s, const IcnetHeadSemi *semi = nullptr);
+
+// The target phase on the features of the undistorted frames: the pack, the block's two forward launches on them into
+// ws.proj / ws.sub12, then launch_icnet_head_targets on that sub12_sum -> tgt [N, 16 h16, 16 w16], one packed byte per loss
+// pixel of the unlabelled images.  The training features go through the same slots afterwards (launch_icnet_fusion_grad with
+// semi.tgt_in = tgt).  semi.labelled NULL: no launch but the head's pack.
+hipError_t launch_icnet_fusion_targets(const float *sub24_raw, const float *c3_raw, int N, int h16, int w16, int K,
+                                       const float *params, const float *stats, int max_workgroups, const IcnetFusionWs &ws,
+                                       const IcnetHeadSemi &semi, uint8_t *tgt, hipStream_t s);
 
 }  // namespace ssal

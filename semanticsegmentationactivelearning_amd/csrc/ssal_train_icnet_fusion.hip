@@ -292,14 +292,12 @@ __global__ __launch_bounds__(128) void k_icnet_fusion_gamma(const float *__restr
     grad[(b ? FU_GB : FU_GA) + co] = ((sum - stats[2 * b * 128 + co] * rbeta) * rstd) * scale;
 }
 
-hipError_t launch_icnet_fusion_grad(const float *sub24, const float *c3, int N, int h16, int w16, int K, const float *params,
-                                    const float *stats, const uint8_t *labels, const float *mask, float weight,
-                                    float label_smoothing, int max_workgroups, const IcnetFusionWs &ws, double *loss,
-                                    float *grad, hipStream_t s)
+// the pack, then the forward path's own launches (ssal_icnet_api.hip, run_trunk) on the weights being trained:
+// ws.proj = BN(conv3_sub1_proj(c3)), ws.sub12 = sub12_sum
+static hipError_t fusion_forward(const float *sub24, const float *c3, int N, int h16, int w16, const float *params,
+                                 const float *stats, const IcnetFusionWs &ws, hipStream_t s)
 {
-    if (N < 1 || K < 2 || K > 32 || max_workgroups < 0 || !icnet_fusion_fits(h16, w16)) return hipErrorInvalidValue;
     const int h8 = 2 * h16, w8 = 2 * w16;
-    const double pix = (double)N * h8 * w8;
     hipError_t e;
     {
         ProfScope prof("k_icnet_fusion_pack", 0.0, 8.0 * FU_HEAD, s);
@@ -307,16 +305,39 @@ hipError_t launch_icnet_fusion_grad(const float *sub24, const float *c3, int N, 
                            ws.wt_a, ws.wt_b, ws.rows);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    // the forward path's own launches (ssal_icnet_api.hip, run_trunk) on the weights being trained
     e = launch_igemm(c3, N, h8, w8, 64, ws.wt_b, 1, 1, 128, 1, 1, ws.rows + 256, ws.rows + 384, nullptr, false, false,
                      ws.proj, s);
     if (e != hipSuccess) return e;
-    e = launch_igemm(sub24, N, h16, w16, 128, ws.wt_a, 3, 3, 128, 1, 2, ws.rows, ws.rows + 128, ws.proj, true, true, ws.sub12,
-                     s);
+    return launch_igemm(sub24, N, h16, w16, 128, ws.wt_a, 3, 3, 128, 1, 2, ws.rows, ws.rows + 128, ws.proj, true, true,
+                        ws.sub12, s);
+}
+
+hipError_t launch_icnet_fusion_targets(const float *sub24_raw, const float *c3_raw, int N, int h16, int w16, int K,
+                                       const float *params, const float *stats, int max_workgroups, const IcnetFusionWs &ws,
+                                       const IcnetHeadSemi &semi, uint8_t *tgt, hipStream_t s)
+{
+    if (N < 1 || K < 2 || K > 32 || max_workgroups < 0 || !icnet_fusion_fits(h16, w16) || !sub24_raw || !c3_raw)
+        return hipErrorInvalidValue;
+    if (semi.labelled) {  // (every image labelled: no pseudo target is read, the head launcher below only packs)
+        const hipError_t e = fusion_forward(sub24_raw, c3_raw, N, h16, w16, params, stats, ws, s);
+        if (e != hipSuccess) return e;
+    }
+    return launch_icnet_head_targets(ws.sub12, N, 2 * h16, 2 * w16, K, params + FU_HEAD, max_workgroups, ws.head, semi, tgt, s);
+}
+
+hipError_t launch_icnet_fusion_grad(const float *sub24, const float *c3, int N, int h16, int w16, int K, const float *params,
+                                    const float *stats, const uint8_t *labels, const float *mask, float weight,
+                                    float label_smoothing, int max_workgroups, const IcnetFusionWs &ws, double *loss,
+                                    float *grad, hipStream_t s, const IcnetHeadSemi *semi)
+{
+    if (N < 1 || K < 2 || K > 32 || max_workgroups < 0 || !icnet_fusion_fits(h16, w16)) return hipErrorInvalidValue;
+    const int h8 = 2 * h16, w8 = 2 * w16;
+    const double pix = (double)N * h8 * w8;
+    hipError_t e = fusion_forward(sub24, c3, N, h16, w16, params, stats, ws, s);
     if (e != hipSuccess) return e;
     // head, loss, dL/d(head) into the packed gradient's tail, the per-tile pull-back windows
     e = launch_icnet_head_grad(ws.sub12, N, h8, w8, K, params + FU_HEAD, labels, mask, weight, label_smoothing,
-                               max_workgroups, ws.head, loss, grad + FU_HEAD, s, nullptr, ws.hw);
+                               max_workgroups, ws.head, loss, grad + FU_HEAD, s, semi, ws.hw);
     if (e != hipSuccess) return e;
     {
         ProfScope prof("k_icnet_fusion_g", 2.0 * pix * 128 * K, 4.0 * pix * (256 + 2.25 * K), s);

@@ -1585,7 +1585,135 @@ class ICNetCascadeTrainer(ICNetFusionTrainer):
         return loss[0]
 
 
+# ---- the semi-supervised step of ICNet's fusion and cascade trainers --------------------------------------
+class SemiSupervisedICNetFusionTrainer(_SemiKeywords, ICNetFusionTrainer):
+    """``ICNetFusionTrainer`` with the reference's semi-supervised step (active_learning.py:226-275, 339-342) built into the
+    head's gradient kernel: ``gradient_features``, ``step_features`` and ``step`` accept ``labelled``, ``measure``,
+    ``threshold``, ``features_raw`` / ``images_raw``, ``confusion`` and ``return_pseudo_pixels`` with ``FinalLayerTrainer``'s
+    meaning, defaults and validation (the pseudo annotation is that of the full-resolution logits under the variables being
+    trained; with a raw side, of the undistorted frames' logits under them).  ``features_raw`` is the tuple ``features()``
+    returns for the undistorted frames, given whole or not at all.  Loss and the eight gradients are bit-identical to
+    ``ICNetFusionTrainer`` on the composed targets; with none of the keywords a call goes through the
+    plain entry.  ``state`` / ``load_state`` are interchangeable with ``ICNetFusionTrainer``'s."""
+
+    _C_FEATURES = ("ssal_icnet_fusion_grad", "ssal_icnet_fusion_grad_semi")
+    _C_IMAGES = ("ssal_icnet_train_fusion", "ssal_icnet_train_fusion_semi")
+    _FEATURE_NAMES = ("sub24_sum", "conv3_sub1")
+
+    def _features_workspace_bytes(self, query, n, h, w, k, semi, with_raw):
+        """a semi call's workspace holds the packed target plane of the undistorted frames when there are any"""
+        return query(n, h, w, k, with_raw) if semi else query(n, h, w, k)
+
+    def _check_call(self, batch, up, labels, mask, max_workgroups, channels):
+        """``ICNetHeadTrainer``'s checks; the planes a semi call may leave out (``_semi`` has judged that) are not looked at"""
+        if labels is None or mask is None:
+            shape = tuple(np.shape(batch))
+            labels = mask = np.zeros((shape[0], up * shape[1], up * shape[2]), np.uint8) if len(shape) == 4 else None
+        return ICNetHeadTrainer._check_call(self, batch, up, labels, mask, max_workgroups, channels)
+
+    def _check_raw(self, feats, features_raw):
+        """``features_raw`` as given -> its members (None: no raw side), judged on the host"""
+        if features_raw is None:
+            return None
+        names = self._FEATURE_NAMES
+        if not isinstance(features_raw, (tuple, list)) or len(features_raw) != len(names) or any(t is None for t in features_raw):
+            raise ValueError("features_raw must be the %d tensors features() returns, (%s), given whole or not at all"
+                             % (len(names), ", ".join(names)))
+        for name, t, f in zip(names, features_raw, feats):
+            if tuple(np.shape(t)) != tuple(np.shape(f)):
+                raise ValueError("features_raw: %s must have the shape of its counterpart %s (got %s)"
+                                 % (name, tuple(np.shape(f)), tuple(np.shape(t))))
+        return tuple(features_raw)
+
+    def _semi_feature_call(self, feats, labels, mask, params, step, max_workgroups, labelled, measure, threshold, features_raw,
+                           confusion, return_pseudo_pixels):
+        """the features entry on ``feats``: -> (loss [1], packed gradient, pseudo pixels or None, device state or None);
+        ``step``: on the weights of the device state, else on the host variables overridden by ``params``"""
+        semi = self._semi_call(feats[0], labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels)
+        mw = self._check_features(*feats, labels, mask, max_workgroups)
+        raw = self._check_raw(feats, features_raw)
+        packed = None if step else self._packed_with(params)
+        x = _lib.as_device_f32(feats[0])
+        xs = (x,) + tuple(_lib.as_device_f32(t).to(x.device) for t in feats[1:])
+        xr = (None,) * len(xs)
+        if semi is not None and raw is not None and any(r is not f for r, f in zip(raw, feats)):
+            xr = tuple(_lib.as_device_f32(t).to(x.device) for t in raw)
+        dev = self._device_state(x.device) if step else None
+        vec = dev["w"] if step else _lib.require_gpu().from_numpy(packed).to(x.device)
+        loss, grad, pp = self._grad_call(xs, xr, labels, mask, vec, semi, confusion, return_pseudo_pixels,
+                                         (_lib.dev_ptr(self._stats(x.device)), mw))
+        return loss, grad, pp, dev
+
+    def gradient_features(self, sub24_sum, conv3_sub1, labels, mask, params=None, max_workgroups=0, labelled=None,
+                          measure=None, threshold=None, features_raw=None, confusion=None, return_pseudo_pixels=False):
+        """``ICNetFusionTrainer.gradient_features`` with the semi-supervised keywords of
+        ``FinalLayerTrainer.gradient_features``: ``labelled`` [N], ``measure`` / ``threshold`` (defaults: the trainer's),
+        ``features_raw`` (``features(images_raw)``: both tensors), ``confusion`` (int64 [K, K] device tensor, added to),
+        ``return_pseudo_pixels`` (appends the int64 [N] counts to the result)."""
+        loss, grad, pp, _ = self._semi_feature_call((sub24_sum, conv3_sub1), labels, mask, params, False, max_workgroups,
+                                                    labelled, measure, threshold, features_raw, confusion, return_pseudo_pixels)
+        return (loss, self._unpack(grad), pp) if return_pseudo_pixels else (loss, self._unpack(grad))
+
+    def step_features(self, sub24_sum, conv3_sub1, labels, mask, max_workgroups=0, labelled=None, measure=None, threshold=None,
+                      features_raw=None, confusion=None, return_pseudo_pixels=False):
+        """one Adam step from cached features; the keywords are those of ``gradient_features``; with
+        ``return_pseudo_pixels`` the result is ``(loss, pseudo_pixels)``"""
+        loss, grad, pp, dev = self._semi_feature_call((sub24_sum, conv3_sub1), labels, mask, None, True, max_workgroups,
+                                                      labelled, measure, threshold, features_raw, confusion,
+                                                      return_pseudo_pixels)
+        self._apply(dev, grad)
+        return (loss[0], pp) if return_pseudo_pixels else loss[0]
+
+    def step(self, images, labels, mask, max_workgroups=0, labelled=None, measure=None, threshold=None, images_raw=None,
+             confusion=None, return_pseudo_pixels=False):
+        """one Adam step from images; ``images_raw``: the undistorted frames (same shape and dtype as ``images``) -- the trunk,
+        the trained blocks and the head run on them first and the pseudo annotation comes from their logits
+        (active_learning.py:231).  The other keywords as in ``gradient_features``; with ``return_pseudo_pixels`` the result
+        is ``(loss, pseudo_pixels)``."""
+        semi = self._semi_call(images, labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels)
+        mw = self._check_call(images, 1, labels, mask, max_workgroups, None)
+        torch = _lib.require_gpu()
+        device = images.device if getattr(images, "is_cuda", False) else torch.device("cuda", torch.cuda.current_device())
+        return self._step_images(images, images_raw, labels, mask, semi, confusion, return_pseudo_pixels,
+                                 (_lib.dev_ptr(self._stats(device)), mw))
+
+
+class SemiSupervisedICNetCascadeTrainer(_SemiKeywords, ICNetCascadeTrainer):
+    """``ICNetCascadeTrainer`` with the semi-supervised step built into the head's gradient kernel (see
+    ``SemiSupervisedICNetFusionTrainer``); ``features_raw`` is the three tensors ``features(images_raw)`` returns.  Loss and
+    the fourteen gradients are bit-identical to ``ICNetCascadeTrainer`` on the composed targets; ``state`` / ``load_state``
+    are interchangeable with its."""
+
+    _C_FEATURES = ("ssal_icnet_cascade_grad", "ssal_icnet_cascade_grad_semi")
+    _C_IMAGES = ("ssal_icnet_train_cascade", "ssal_icnet_train_cascade_semi")
+    _FEATURE_NAMES = ("conv5_4_k1", "conv3_1", "conv3_sub1")
+    # the fusion form's helpers name no class of their own: they serve this one as they stand
+    _features_workspace_bytes = SemiSupervisedICNetFusionTrainer._features_workspace_bytes
+    _check_call = SemiSupervisedICNetFusionTrainer._check_call
+    _check_raw = SemiSupervisedICNetFusionTrainer._check_raw
+    _semi_feature_call = SemiSupervisedICNetFusionTrainer._semi_feature_call
+    step = SemiSupervisedICNetFusionTrainer.step
+
+    def gradient_features(self, conv5_4_k1, conv3_1, conv3_sub1, labels, mask, params=None, max_workgroups=0, labelled=None,
+                          measure=None, threshold=None, features_raw=None, confusion=None, return_pseudo_pixels=False):
+        """``ICNetCascadeTrainer.gradient_features`` with the keywords of ``SemiSupervisedICNetFusionTrainer``'s"""
+        loss, grad, pp, _ = self._semi_feature_call((conv5_4_k1, conv3_1, conv3_sub1), labels, mask, params, False,
+                                                    max_workgroups, labelled, measure, threshold, features_raw, confusion,
+                                                    return_pseudo_pixels)
+        return (loss, self._unpack(grad), pp) if return_pseudo_pixels else (loss, self._unpack(grad))
+
+    def step_features(self, conv5_4_k1, conv3_1, conv3_sub1, labels, mask, max_workgroups=0, labelled=None, measure=None,
+                      threshold=None, features_raw=None, confusion=None, return_pseudo_pixels=False):
+        """one Adam step from cached features; the keywords are those of ``gradient_features``"""
+        loss, grad, pp, dev = self._semi_feature_call((conv5_4_k1, conv3_1, conv3_sub1), labels, mask, None, True,
+                                                      max_workgroups, labelled, measure, threshold, features_raw, confusion,
+                                                      return_pseudo_pixels)
+        self._apply(dev, grad)
+        return (loss[0], pp) if return_pseudo_pixels else loss[0]
+
+
 __all__ = ["FinalLayerTrainer", "LastBlockTrainer", "LastStageTrainer", "DecoderTailTrainer", "SemiSupervisedBlockTrainer",
            "SemiSupervisedStageTrainer", "SemiSupervisedTailTrainer", "DeepTailTrainer", "SemiSupervisedDeepTailTrainer",
            "DecoderTrainer", "SemiSupervisedDecoderTrainer", "ICNetHeadTrainer", "SemiSupervisedICNetHeadTrainer",
-           "ICNetFusionTrainer", "ICNetCascadeTrainer"]
+           "ICNetFusionTrainer", "ICNetCascadeTrainer", "SemiSupervisedICNetFusionTrainer",
+           "SemiSupervisedICNetCascadeTrainer"]
