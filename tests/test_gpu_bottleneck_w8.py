@@ -2,7 +2,11 @@
 bits of today's kernels (bnk_w8 = 0) and of the C oracle: single layers through ssal_enet_run_layer at one exact tile, ragged
 in both axes, interior tiles with neighbours on all sides and narrower than a tile -- for a dilated layer the same shapes
 times the dilation, so that its phase sub-images are a single tile, ragged, and (17 x 31) smaller than a tile with a halo
-ring of SAME-padding zeros -- at N = 1 and N = 3; then the whole network's scores under every setting of the knob."""
+ring of SAME-padding zeros -- at N = 1 and N = 3; then the whole network's scores under every setting of the knob.
+Every dilated shape here is a multiple of the dilation, so all its phases are the same size; the unequal-phase geometries
+(phases a row or column short of the grid's, empty tiles, phases <= 16 wide under the 32-wide tile, H < dilation, both sides
+of the Wp = 16 / 17 dispatch boundary) are in tests/test_gpu_bottleneck_phases.py, their case table in
+tests/bottleneck_phase_cases.py (checked without a GPU by tests/test_bottleneck_phase_cases_cpu.py)."""
 import numpy as np
 import pytest
 import torch
