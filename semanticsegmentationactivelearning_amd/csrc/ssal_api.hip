@@ -7,6 +7,7 @@
 #include "ssal_bottleneck_args.h"
 #include "ssal_bf16x3.h"
 #include "ssal_confusion.h"
+#include "ssal_train_host.h"
 #include "ssal_train_block.h"
 #include "ssal_train_stage.h"
 #include "ssal_train_tail.h"
@@ -1714,29 +1715,9 @@ SSAL_API int ssal_profile_collect(char *json_out, int64_t cap)
 // (final_grad_run, train_block_run, train_stage_run, train_tail_run with R = 1 for the decoder tail and R = 2 for the deep
 // tail, train_decoder_run) that takes the features and an optional SemiArgs; the public entries validate (dims, then semi
 // arguments, then NULL pointers, then the workspace size, all before any launch), carve the workspace and call it.
+// CallArgs, SemiArgs, args_check, ws_check, no_trunk and with_confusion are ssal_train_host.h's: ICNet's entries share them.
 // ------------------------------------------------------------------------------------------------
-// what every entry is given besides its inputs and parameters: targets, the loss' knobs, outputs, workspace, stream
-struct CallArgs {
-    const uint8_t *labels;
-    const float *mask;
-    float weight, label_smoothing;
-    double *loss;
-    float *grad;
-    void *ws;
-    int64_t ws_bytes;
-    hipStream_t s;
-};
-
-// the semi-supervised side of a call as the public entries take it (DESIGN.md sections 16 and 19); NULL = the plain step
-struct SemiArgs {
-    const uint8_t *labelled;
-    int measure;
-    float threshold;
-    int64_t *confusion, *pseudo_pixels;
-    bool with_raw;
-};
-
-// ---- the steps the entries share ----
+// ---- the steps ENet's entries share ----
 static bool net_dims_ok(const ssal_enet *net, int n, int h, int w)
 {
     return net && net->committed && n > 0 && h > 0 && w > 0 && h % 8 == 0 && w % 8 == 0;
@@ -1755,27 +1736,6 @@ static int final_grad_check(int n, int h, int w, int classes)
     if (!final_grad_fits(h, w))
         return fail(SSAL_EINVAL, "feature map %dx%d is beyond the output-layer gradient kernel's limit", h, w);
     return SSAL_OK;
-}
-
-// the semi arguments, then the pointers (`inputs`: the entry's own features / frames / parameters, and-ed); a semi call's
-// label and mask planes may be NULL when no image is labelled
-static int args_check(bool inputs, const CallArgs &a, const SemiArgs *semi)
-{
-    if (semi && (semi->measure < 0 || semi->measure > 2))
-        return fail(SSAL_ENOTIMPL, "Uncertainty function not implemented (measure=%d)", semi->measure);
-    if (semi && !semi->labelled && (!a.labels || !a.mask))
-        return fail(SSAL_EINVAL, "labels_dev / mask_dev may be NULL only when labelled_dev marks no image as labelled");
-    if (!inputs || !a.loss || !a.grad || !a.ws || (!semi && (!a.labels || !a.mask)))
-        return fail(SSAL_EINVAL, "NULL device pointer");
-    return SSAL_OK;
-}
-
-// judged once the call's pieces are carved from b (pointer arithmetic only), before anything is launched
-static int ws_check(int64_t need, const Bump &b, const CallArgs &a)
-{
-    if (a.ws_bytes < need) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld", (long long)need,
-                                       (long long)a.ws_bytes);
-    return b.ok ? SSAL_OK : fail(SSAL_ENOMEM, "workspace too small: need %lld bytes", (long long)need);
 }
 
 // carves the forward workspace into W and returns a Bump positioned behind it (not ok when W is not)
@@ -1799,21 +1759,6 @@ static int run_trunk(const ssal_enet *net, int upto, const void *x_dev, int x_is
                      hipStream_t s)
 {
     for (int li = 0; li < upto; ++li) HIP_TRY(run_layer_idx(net, li, x_dev, x_is_u8 != 0, W, n, h, w, s));
-    return SSAL_OK;
-}
-
-// a features entry has its features already: nothing to run where an images entry runs the trunk
-static int no_trunk(bool) { return SSAL_OK; }
-
-// launches(rep, reps) with the confusion replicas zeroed before and folded into the caller's matrix after it; without a
-// matrix (a plain call, or a semi call that asks for none) rep is NULL and neither the memset nor the fold is issued
-template <typename Launches>
-static int with_confusion(unsigned long long *rep, int classes, int64_t *confusion_dev, hipStream_t s, Launches launches)
-{
-    const int reps = ssal::knobs().conf_reps;
-    if (confusion_dev) HIP_TRY(hipMemsetAsync(rep, 0, (size_t)reps * ssal::conf_rep_stride(classes * classes) * 8, s));
-    if (int rc = launches(confusion_dev ? rep : nullptr, reps)) return rc;
-    if (confusion_dev) HIP_TRY(launch_confusion_fold(rep, reps, classes, confusion_dev, s));
     return SSAL_OK;
 }
 

@@ -7,6 +7,7 @@
 #include "ssal_icnet.h"
 #include "ssal_internal.h"
 #include "ssal_prof.h"
+#include "ssal_train_host.h"
 #include "ssal_train_icnet.h"
 #include "ssal_train_icnet_cascade.h"
 #include "ssal_train_icnet_fusion.h"
@@ -761,16 +762,91 @@ SSAL_API int ssal_icnet_endpoint_valid_after_score(const ssal_icnet *net, const 
 }
 
 // ------------------------------------------------------------------------------------------------
-// output-layer training (kernels: ssal_train_icnet.hip)
+// Training of ICNet's tail over a frozen trunk (include/ssal_icnet.h; DESIGN.md sections 23, 25 and 28-30).  Three depths --
+// the output layer (head), the last fusion stage, the whole cascade head -- each entered from cached features or from images,
+// plain or semi-supervised.  Every depth has ONE carve function, ONE byte count (the queries and the entries' workspace check
+// both read it) and ONE body (head_run, fusion_run, cascade_run) that takes the features, the features of the undistorted
+// frames and an optional SemiArgs; its features wrapper (*_grad_entry) and its images wrapper (*_train_entry) validate (dims,
+// then semi arguments, then NULL pointers, then raw all-or-none, then the workspace size, all before any launch), carve and
+// call it.  The public entries pack their arguments and call a wrapper.  The shared steps are ssal_train_host.h's, as for ENet.
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-// the buffers of one gradient call behind `b`; own_lq: the logits live here (the images entry keeps them in the network's
+// ---- the steps the entries share ----
+bool net_dims_ok(const ssal_icnet *net, int n, int h, int w)
+{
+    return net && net->committed && n > 0 && h > 0 && w > 0 && h % 32 == 0 && w % 32 == 0;
+}
+
+int64_t trunk_bytes(const ssal_icnet *net, int n, int h, int w) { return carve(net, nullptr, 0, n, h, w).bytes; }
+
+// carves the forward workspace into W and returns a Bump positioned behind it (not ok when W is not)
+Bump carve_behind_trunk(const ssal_icnet *net, const CallArgs &a, int n, int h, int w, IcWorkspace *W)
+{
+    *W = carve(net, a.ws, a.ws_bytes, n, h, w);
+    Bump b(a.ws, a.ws_bytes);
+    b.off = W->bytes;
+    b.ok = W->ok;
+    return b;
+}
+
+// the frozen trunk of an images entry, on the undistorted (of_raw) or the training frames, through the same slots of W.  It
+// ends in front of the layers being trained (run_trunk: head = false; fusion / cascade as the depth says)
+auto frozen_trunk(const ssal_icnet *net, const IcWorkspace &W, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
+                  int h, int w, hipStream_t s, bool fusion, bool cascade)
+{
+    return [=, &W](bool of_raw) -> int {
+        std::vector<Grp> one(1);
+        one[0] = {W, of_raw ? x_raw_dev : x_dev, n, s};
+        HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false, fusion, cascade));
+        return SSAL_OK;
+    };
+}
+
+// the raw pointers of a features entry come all or none
+int raw_all_or_none(int given, int of)
+{
+    if (given != 0 && given != of) return fail(SSAL_EINVAL, "the raw feature pointers must be given together (%d of %d)", given, of);
+    return SSAL_OK;
+}
+
+// what a semi call adds behind the plain pieces (DESIGN.md sections 25 and 30): the confusion replicas, then (with_raw) the
+// packed pseudo-target plane of the undistorted frames, one byte per loss pixel.  Plain: nothing.
+struct SemiWs {
+    unsigned long long *rep;
+    uint8_t *tgt;
+};
+
+SemiWs semi_carve(Bump &b, int64_t n, int h8, int w8, int classes, bool semi, bool with_raw)
+{
+    SemiWs t;
+    t.rep = semi ? b.take<unsigned long long>((int64_t)ssal::kConfMaxReps * ssal::conf_rep_stride(classes * classes)) : nullptr;
+    t.tgt = semi && with_raw ? b.take<uint8_t>(n * (8 * (int64_t)h8) * (8 * (int64_t)w8)) : nullptr;
+    return t;
+}
+
+// the launchers' form of a semi call (ssal_train_icnet.h): of the target launch, which only reads the rule ...
+IcnetHeadSemi semi_of_targets(const SemiArgs &semi)
+{
+    return {semi.labelled, semi.measure, semi.threshold, nullptr, nullptr, nullptr, 0, nullptr};
+}
+
+// ... and of the gradient launch (tgt: the plane the target launch wrote, or NULL = targets from the training logits)
+IcnetHeadSemi semi_of_grad(const SemiArgs &semi, const uint8_t *tgt, unsigned long long *rep, int reps)
+{
+    return {semi.labelled, semi.measure, semi.threshold, tgt, nullptr, rep, reps, (unsigned long long *)semi.pseudo_pixels};
+}
+
+// the undistorted frames' features matter only where an image is unlabelled
+bool wants_targets(const void *raw, const SemiArgs *semi) { return raw && semi && semi->labelled; }
+
+// ---- the output layer (DESIGN.md sections 23 and 25; kernels: ssal_train_icnet.hip) ----
+// the buffers of one gradient call behind `b`; own_acts: the logits live here (the images entry keeps them in the network's
 // conv6_cls endpoint instead)
-IcnetHeadWs head_carve(Bump &b, int64_t n, int h8, int w8, int classes, bool own_lq)
+IcnetHeadWs head_carve(Bump &b, int64_t n, int h8, int w8, int classes, bool own_acts)
 {
     IcnetHeadWs t;
-    t.lq = own_lq ? b.take<float>(n * (2 * (int64_t)h8) * (2 * (int64_t)w8) * classes) : nullptr;
+    t.lq = own_acts ? b.take<float>(n * (2 * (int64_t)h8) * (2 * (int64_t)w8) * classes) : nullptr;
     t.wt = b.take<float>(icnet_head_ws_floats_wt());
     const int64_t G = IH_MAX_WG;  // (sized for the default grid: max_workgroups only lowers it)
     t.part = b.take<float>(G * icnet_head_floats(classes));
@@ -778,249 +854,82 @@ IcnetHeadWs head_carve(Bump &b, int64_t n, int h8, int w8, int classes, bool own
     return t;
 }
 
+// front: the bytes ahead of the call's own pieces (an images entry: the forward workspace)
+int64_t head_bytes(int64_t front, int n, int h8, int w8, int classes, bool own_acts, bool semi, bool with_raw)
+{
+    Bump b(nullptr, 0);
+    b.off = front;
+    (void)head_carve(b, n, h8, w8, classes, own_acts);
+    (void)semi_carve(b, n, h8, w8, classes, semi, with_raw);
+    return b.off + 256;
+}
+
+// the images entry: the logits of the head being trained are this call's conv6_cls endpoint
+void head_bind(IcnetHeadWs &t, const IcWorkspace &W) { t.lq = W.act.at("conv6_cls"); }
+
+bool head_fits(int n, int h8, int w8) { return icnet_head_fits(h8, w8) && (double)n * h8 * w8 <= 1099511627776.0; }
+
 int head_check(int n, int h8, int w8, int classes, int max_workgroups)
 {
-    if (n <= 0) return fail(SSAL_EINVAL, "bad dims n=%d h=%d w=%d", n, h8, w8);
-    if (classes < 2 || classes > 32) return fail(SSAL_EINVAL, "classes must be in [2,32] (got %d)", classes);
-    if (max_workgroups < 0) return fail(SSAL_EINVAL, "max_workgroups must be >= 0 (got %d)", max_workgroups);
-    if (!icnet_head_fits(h8, w8) || (double)n * h8 * w8 > 1099511627776.0)
-        return fail(SSAL_EINVAL, "feature map %dx%d (n=%d) is beyond the head gradient kernel's limit", h8, w8, n);
-    return SSAL_OK;
+    return capped_dims_check(n, h8, w8, classes, max_workgroups, head_fits(n, h8, w8), "head gradient kernel's");
 }
 
-}  // namespace
-
-SSAL_API int64_t ssal_icnet_head_grad_workspace_bytes(int n, int h, int w, int classes)
+// sub12 / sub12_raw [n,h8,w8,128]: sub12_sum of the training / the undistorted frames, which trunk(raw) brings about (an images
+// entry: one after the other in the same endpoint) or the caller has.  The target launch leaves one byte per loss pixel, so the
+// training features can go through the same t.lq afterwards.
+template <typename Trunk>
+int head_run(Trunk trunk, const float *sub12, const float *sub12_raw, int n, int h8, int w8, int classes, const float *head_dev,
+             int max_workgroups, const CallArgs &a, const SemiArgs *semi, const IcnetHeadWs &t, const SemiWs &sw)
 {
-    if (n <= 0 || classes < 2 || classes > 32 || !icnet_head_fits(h, w) || (double)n * h * w > 1099511627776.0) return -1;
-    Bump b(nullptr, 0);
-    (void)head_carve(b, n, h, w, classes, true);
-    return b.off + 256;
+    const uint8_t *tgt = nullptr;
+    if (wants_targets(sub12_raw, semi)) {
+        if (int rc = trunk(true)) return rc;
+        HIP_TRY(launch_icnet_head_targets(sub12_raw, n, h8, w8, classes, head_dev, max_workgroups, t, semi_of_targets(*semi),
+                                          sw.tgt, a.s));
+        tgt = sw.tgt;
+    }
+    if (int rc = trunk(false)) return rc;
+    return with_confusion(sw.rep, classes, semi ? semi->confusion : nullptr, a.s, [&](unsigned long long *rep, int reps) -> int {
+        IcnetHeadSemi sa = {};
+        if (semi) sa = semi_of_grad(*semi, tgt, rep, reps);
+        HIP_TRY(launch_icnet_head_grad(sub12, n, h8, w8, classes, head_dev, a.labels, a.mask, a.weight, a.label_smoothing,
+                                       max_workgroups, t, a.loss, a.grad, a.s, semi ? &sa : nullptr));
+        return SSAL_OK;
+    });
 }
 
-SSAL_API int ssal_icnet_head_grad_nhwc(const float *sub12_dev, int n, int h, int w, int classes, const float *head_dev,
-                                       const uint8_t *labels_dev, const float *mask_dev, float weight,
-                                       float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev,
-                                       void *ws_dev, int64_t ws_bytes, void *stream)
+int head_grad_entry(const float *sub12_dev, const float *sub12_raw_dev, int n, int h, int w, int classes, const float *head_dev,
+                    int max_workgroups, const CallArgs &a, const SemiArgs *semi)
 {
-    int rc = head_check(n, h, w, classes, max_workgroups);
-    if (rc) return rc;
-    if (!sub12_dev || !head_dev || !labels_dev || !mask_dev || !loss_dev || !grad_dev || !ws_dev)
-        return fail(SSAL_EINVAL, "NULL device pointer");
-    Bump b(ws_dev, ws_bytes);
+    if (int rc = head_check(n, h, w, classes, max_workgroups)) return rc;
+    if (int rc = args_check(sub12_dev && head_dev, a, semi)) return rc;
+    Bump b(a.ws, a.ws_bytes);
     const IcnetHeadWs t = head_carve(b, n, h, w, classes, true);
-    if (!b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
-                           (long long)ssal_icnet_head_grad_workspace_bytes(n, h, w, classes), (long long)ws_bytes);
-    HIP_TRY(launch_icnet_head_grad(sub12_dev, n, h, w, classes, head_dev, labels_dev, mask_dev, weight, label_smoothing,
-                                   max_workgroups, t, loss_dev, grad_dev, (hipStream_t)stream));
-    return SSAL_OK;
+    const SemiWs sw = semi_carve(b, n, h, w, classes, semi != nullptr, sub12_raw_dev != nullptr);
+    if (int rc = ws_check(head_bytes(0, n, h, w, classes, true, semi != nullptr, sub12_raw_dev != nullptr), b, a)) return rc;
+    return head_run(no_trunk, sub12_dev, sub12_raw_dev, n, h, w, classes, head_dev, max_workgroups, a, semi, t, sw);
 }
 
-SSAL_API int64_t ssal_icnet_train_head_workspace_bytes(const ssal_icnet *net, int n, int h, int w)
-{
-    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 32 || w % 32) return -1;
-    Bump b(nullptr, 0);
-    b.off = carve(net, nullptr, 0, n, h, w).bytes;
-    (void)head_carve(b, n, h / 8, w / 8, net->classes, false);
-    return b.off + 256;
-}
-
-SSAL_API int ssal_icnet_train_head_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
-                                        const uint8_t *labels_dev, const float *mask_dev, const float *head_dev,
-                                        float weight, float label_smoothing, int max_workgroups, double *loss_dev,
-                                        float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+int head_train_entry(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h, int w,
+                     const float *head_dev, int max_workgroups, const CallArgs &a, const SemiArgs *semi)
 {
     int rc = check_dims(net, n, h, w);
     if (rc) return rc;
-    if ((rc = head_check(n, h / 8, w / 8, net->classes, max_workgroups))) return rc;
-    if (!x_dev || !head_dev || !labels_dev || !mask_dev || !loss_dev || !grad_dev || !ws_dev)
-        return fail(SSAL_EINVAL, "NULL device pointer");
-    IcWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
-    Bump b(ws_dev, ws_bytes);
-    b.off = W.bytes;
-    IcnetHeadWs t = head_carve(b, n, h / 8, w / 8, net->classes, false);
-    if (!W.ok || !b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
-                                    (long long)ssal_icnet_train_head_workspace_bytes(net, n, h, w), (long long)ws_bytes);
-    t.lq = W.act.at("conv6_cls");  // the logits of the head being trained are this call's conv6_cls endpoint
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<Grp> one(1);
-    one[0] = {W, x_dev, n, s};
-    HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false));
-    HIP_TRY(launch_icnet_head_grad(W.act.at("sub12_sum"), n, h / 8, w / 8, net->classes, head_dev, labels_dev, mask_dev,
-                                   weight, label_smoothing, max_workgroups, t, loss_dev, grad_dev, s));
-    return SSAL_OK;
+    const int K = net->classes, h8 = h / 8, w8 = w / 8;
+    if ((rc = head_check(n, h8, w8, K, max_workgroups))) return rc;
+    if ((rc = args_check(x_dev && head_dev, a, semi))) return rc;
+    IcWorkspace W;
+    Bump b = carve_behind_trunk(net, a, n, h, w, &W);
+    IcnetHeadWs t = head_carve(b, n, h8, w8, K, false);
+    const SemiWs sw = semi_carve(b, n, h8, w8, K, semi != nullptr, x_raw_dev != nullptr);
+    if ((rc = ws_check(head_bytes(W.bytes, n, h8, w8, K, false, semi != nullptr, x_raw_dev != nullptr), b, a))) return rc;
+    head_bind(t, W);
+    const float *sub12 = W.act.at("sub12_sum");
+    return head_run(frozen_trunk(net, W, x_dev, x_raw_dev, x_is_u8, n, h, w, a.s, true, true), sub12,
+                    x_raw_dev ? sub12 : nullptr, n, h8, w8, K, head_dev, max_workgroups, a, semi, t, sw);
 }
 
-// ---- the semi-supervised step ----
-namespace {
-
-// what a semi call adds behind the plain pieces: the confusion replicas, then (with_raw) the packed pseudo-target plane of
-// the undistorted frames, one byte per loss pixel
-struct HeadSemiWs {
-    unsigned long long *rep;
-    uint8_t *tgt;
-};
-
-HeadSemiWs head_semi_carve(Bump &b, int64_t n, int h8, int w8, int classes, bool with_raw)
-{
-    HeadSemiWs t;
-    t.rep = b.take<unsigned long long>((int64_t)ssal::kConfMaxReps * ssal::conf_rep_stride(classes * classes));
-    t.tgt = with_raw ? b.take<uint8_t>(n * (8 * (int64_t)h8) * (8 * (int64_t)w8)) : nullptr;
-    return t;
-}
-
-// the arguments of a semi entry as ssal_final_grad_semi_nhwc judges them: the measure, then the pointers (`inputs`: the
-// entry's own features / frames / head, and-ed); the label and mask planes may be NULL when no image is labelled
-int head_semi_check(bool inputs, const uint8_t *labels, const float *mask, const uint8_t *labelled, int measure,
-                    const double *loss, const float *grad, const void *ws)
-{
-    if (measure < 0 || measure > 2) return fail(SSAL_ENOTIMPL, "Uncertainty function not implemented (measure=%d)", measure);
-    if (!labelled && (!labels || !mask))
-        return fail(SSAL_EINVAL, "labels_dev / mask_dev may be NULL only when labelled_dev marks no image as labelled");
-    if (!inputs || !loss || !grad || !ws) return fail(SSAL_EINVAL, "NULL device pointer");
-    return SSAL_OK;
-}
-
-// the training tail of a semi call: the replicas zeroed before and folded into the caller's matrix after the launches
-// (neither is issued without a matrix).  tgt: the plane the target launch wrote, or NULL
-int head_semi_tail(const float *sub12, int n, int h8, int w8, int classes, const float *head_dev, const uint8_t *labels_dev,
-                   const float *mask_dev, const uint8_t *labelled_dev, int measure, float threshold, float weight,
-                   float label_smoothing, int max_workgroups, const IcnetHeadWs &t, const HeadSemiWs &sw, const uint8_t *tgt,
-                   double *loss_dev, float *grad_dev, int64_t *confusion_dev, int64_t *pseudo_pixels_dev, hipStream_t s)
-{
-    const int reps = ssal::knobs().conf_reps;
-    if (confusion_dev) HIP_TRY(hipMemsetAsync(sw.rep, 0, (size_t)reps * ssal::conf_rep_stride(classes * classes) * 8, s));
-    const IcnetHeadSemi sa = {labelled_dev, measure, threshold, tgt, nullptr, confusion_dev ? sw.rep : nullptr, reps,
-                              (unsigned long long *)pseudo_pixels_dev};
-    HIP_TRY(launch_icnet_head_grad(sub12, n, h8, w8, classes, head_dev, labels_dev, mask_dev, weight, label_smoothing,
-                                   max_workgroups, t, loss_dev, grad_dev, s, &sa));
-    if (confusion_dev) HIP_TRY(launch_confusion_fold(sw.rep, reps, classes, confusion_dev, s));
-    return SSAL_OK;
-}
-
-}  // namespace
-
-SSAL_API int64_t ssal_icnet_head_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw)
-{
-    if (n <= 0 || classes < 2 || classes > 32 || !icnet_head_fits(h, w) || (double)n * h * w > 1099511627776.0) return -1;
-    Bump b(nullptr, 0);
-    (void)head_carve(b, n, h, w, classes, true);
-    (void)head_semi_carve(b, n, h, w, classes, with_raw != 0);
-    return b.off + 256;
-}
-
-SSAL_API int ssal_icnet_head_grad_semi_nhwc(const float *sub12_dev, const float *sub12_raw_dev, int n, int h, int w,
-                                            int classes, const float *head_dev, const uint8_t *labels_dev,
-                                            const float *mask_dev, const uint8_t *labelled_dev, int measure,
-                                            float threshold, float weight, float label_smoothing, int max_workgroups,
-                                            double *loss_dev, float *grad_dev, int64_t *confusion_dev,
-                                            int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
-{
-    int rc = head_check(n, h, w, classes, max_workgroups);
-    if (rc) return rc;
-    if ((rc = head_semi_check(sub12_dev && head_dev, labels_dev, mask_dev, labelled_dev, measure, loss_dev, grad_dev, ws_dev)))
-        return rc;
-    Bump b(ws_dev, ws_bytes);
-    const IcnetHeadWs t = head_carve(b, n, h, w, classes, true);
-    const HeadSemiWs sw = head_semi_carve(b, n, h, w, classes, sub12_raw_dev != nullptr);
-    if (!b.ok)
-        return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
-                    (long long)ssal_icnet_head_grad_semi_workspace_bytes(n, h, w, classes, sub12_raw_dev != nullptr),
-                    (long long)ws_bytes);
-    hipStream_t s = (hipStream_t)stream;
-    // the undistorted frame's features matter only where an image is unlabelled: head on sub12_raw into t.lq, the target
-    // launch; then the training features go through the same t.lq
-    const uint8_t *tgt = nullptr;
-    if (sub12_raw_dev && labelled_dev) {
-        const IcnetHeadSemi sa = {labelled_dev, measure, threshold, nullptr, nullptr, nullptr, 0, nullptr};
-        HIP_TRY(launch_icnet_head_targets(sub12_raw_dev, n, h, w, classes, head_dev, max_workgroups, t, sa, sw.tgt, s));
-        tgt = sw.tgt;
-    }
-    return head_semi_tail(sub12_dev, n, h, w, classes, head_dev, labels_dev, mask_dev, labelled_dev, measure, threshold, weight,
-                          label_smoothing, max_workgroups, t, sw, tgt, loss_dev, grad_dev, confusion_dev, pseudo_pixels_dev, s);
-}
-
-SSAL_API int64_t ssal_icnet_train_head_semi_workspace_bytes(const ssal_icnet *net, int n, int h, int w, int with_raw)
-{
-    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 32 || w % 32) return -1;
-    Bump b(nullptr, 0);
-    b.off = carve(net, nullptr, 0, n, h, w).bytes;
-    (void)head_carve(b, n, h / 8, w / 8, net->classes, false);
-    (void)head_semi_carve(b, n, h / 8, w / 8, net->classes, with_raw != 0);
-    return b.off + 256;
-}
-
-SSAL_API int ssal_icnet_train_head_semi_nhwc(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
-                                             int h, int w, const uint8_t *labels_dev, const float *mask_dev,
-                                             const uint8_t *labelled_dev, int measure, float threshold,
-                                             const float *head_dev, float weight, float label_smoothing, int max_workgroups,
-                                             double *loss_dev, float *grad_dev, int64_t *confusion_dev,
-                                             int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
-{
-    int rc = check_dims(net, n, h, w);
-    if (rc) return rc;
-    if ((rc = head_check(n, h / 8, w / 8, net->classes, max_workgroups))) return rc;
-    if ((rc = head_semi_check(x_dev && head_dev, labels_dev, mask_dev, labelled_dev, measure, loss_dev, grad_dev, ws_dev)))
-        return rc;
-    IcWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
-    Bump b(ws_dev, ws_bytes);
-    b.off = W.bytes;
-    IcnetHeadWs t = head_carve(b, n, h / 8, w / 8, net->classes, false);
-    const HeadSemiWs sw = head_semi_carve(b, n, h / 8, w / 8, net->classes, x_raw_dev != nullptr);
-    if (!W.ok || !b.ok)
-        return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
-                    (long long)ssal_icnet_train_head_semi_workspace_bytes(net, n, h, w, x_raw_dev != nullptr),
-                    (long long)ws_bytes);
-    t.lq = W.act.at("conv6_cls");
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<Grp> one(1);
-    // the undistorted frames go through the trunk only where an image is unlabelled, and first: the target launch leaves one
-    // byte per loss pixel, so the training frames can go through the same slots afterwards
-    const uint8_t *tgt = nullptr;
-    if (x_raw_dev && labelled_dev) {
-        one[0] = {W, x_raw_dev, n, s};
-        HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false));
-        const IcnetHeadSemi sa = {labelled_dev, measure, threshold, nullptr, nullptr, nullptr, 0, nullptr};
-        HIP_TRY(launch_icnet_head_targets(W.act.at("sub12_sum"), n, h / 8, w / 8, net->classes, head_dev, max_workgroups, t, sa,
-                                          sw.tgt, s));
-        tgt = sw.tgt;
-    }
-    one[0] = {W, x_dev, n, s};
-    HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false));
-    return head_semi_tail(W.act.at("sub12_sum"), n, h / 8, w / 8, net->classes, head_dev, labels_dev, mask_dev, labelled_dev,
-                          measure, threshold, weight, label_smoothing, max_workgroups, t, sw, tgt, loss_dev, grad_dev,
-                          confusion_dev, pseudo_pixels_dev, s);
-}
-
-SSAL_API int ssal_icnet_update_head(ssal_icnet *net, const float *kernel_host, const float *bias_host, void *stream)
-{
-    if (!net || !kernel_host || !bias_host) return fail(SSAL_EINVAL, "NULL argument");
-    if (!net->committed) return fail(SSAL_ESTATE, "ssal_icnet_commit() has not been called");
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != net->device)
-        return fail(SSAL_ESTATE, "the handle was committed on device %d but the current device is %d (one handle per device)",
-                    net->device, dev);
-    const int K = net->classes;
-    HostTensor &tk = net->tensors[net->index.at("conv6_cls.kernel")], &tb = net->tensors[net->index.at("conv6_cls.bias")];
-    tk.data.assign(kernel_host, kernel_host + 128 * (size_t)K);
-    tb.data.assign(bias_host, bias_host + K);
-    std::vector<float> wt(igemm_relayout_floats(1, 1, 128, K)), sc, sh;
-    igemm_relayout(tk.data.data(), 1, 1, 128, K, wt.data());
-    fold_bn_padded(nullptr, nullptr, nullptr, nullptr, tb.data.data(), K, sc, sh);
-    const ConvDev &c = net->convs.at("conv6_cls");
-    hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(hipMemcpyAsync(const_cast<float *>(c.w), wt.data(), wt.size() * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(const_cast<float *>(c.scale), sc.data(), sc.size() * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(const_cast<float *>(c.shift), sh.data(), sh.size() * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));  // the staging vectors die at return
-    return SSAL_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// training of the last fusion stage (kernels: ssal_train_icnet_fusion.hip)
-// ------------------------------------------------------------------------------------------------
-namespace {
-
+// ---- the last fusion stage (DESIGN.md sections 28 and 30; kernels: ssal_train_icnet_fusion.hip) ----
 // the buffers of one gradient call behind `b`; own_acts: proj / sub12_sum / lq live here (the images entry keeps them in the
 // network's conv3_sub1_proj / sub12_sum / conv6_cls endpoints instead)
 IcnetFusionWs fusion_carve(Bump &b, int64_t n, int h16, int w16, int classes, bool own_acts)
@@ -1041,119 +950,220 @@ IcnetFusionWs fusion_carve(Bump &b, int64_t n, int h16, int w16, int classes, bo
     return t;
 }
 
-bool fusion_dims_ok(int n, int h16, int w16, int classes)
+int64_t fusion_bytes(int64_t front, int n, int h16, int w16, int classes, bool own_acts, bool semi, bool with_raw)
 {
-    return n > 0 && classes >= 2 && classes <= 32 && icnet_fusion_fits(h16, w16) && (double)n * h16 * w16 <= 274877906944.0;
+    Bump b(nullptr, 0);
+    b.off = front;
+    (void)fusion_carve(b, n, h16, w16, classes, own_acts);
+    (void)semi_carve(b, n, 2 * h16, 2 * w16, classes, semi, with_raw);
+    return b.off + 256;
 }
+
+// the images entry: the block and the head being trained write this call's conv3_sub1_proj, sub12_sum and conv6_cls endpoints
+void fusion_bind(IcnetFusionWs &t, const IcWorkspace &W)
+{
+    t.proj = W.act.at("conv3_sub1_proj");
+    t.sub12 = W.act.at("sub12_sum");
+    head_bind(t.head, W);
+}
+
+bool fusion_fits(int n, int h16, int w16) { return icnet_fusion_fits(h16, w16) && (double)n * h16 * w16 <= 274877906944.0; }
 
 int fusion_check(int n, int h16, int w16, int classes, int max_workgroups)
 {
-    if (n <= 0) return fail(SSAL_EINVAL, "bad dims n=%d h=%d w=%d", n, h16, w16);
-    if (classes < 2 || classes > 32) return fail(SSAL_EINVAL, "classes must be in [2,32] (got %d)", classes);
-    if (max_workgroups < 0) return fail(SSAL_EINVAL, "max_workgroups must be >= 0 (got %d)", max_workgroups);
-    if (!fusion_dims_ok(n, h16, w16, classes))
-        return fail(SSAL_EINVAL, "feature map %dx%d (n=%d) is beyond the fusion gradient kernels' limit", h16, w16, n);
-    return SSAL_OK;
+    return capped_dims_check(n, h16, w16, classes, max_workgroups, fusion_fits(n, h16, w16), "fusion gradient kernels'");
 }
 
-}  // namespace
-
-SSAL_API int64_t ssal_icnet_fusion_grad_workspace_bytes(int n, int h, int w, int classes)
+// sub24 [n,h16,w16,128] / c3 [n,2 h16,2 w16,64]: sub24_sum and conv3_sub1 of the training frames, *_raw: of the undistorted
+// frames (both or neither); trunk as for head_run.  The target launch runs the block and the head on the raw features into t's
+// slots; then the training features go through the same slots.
+template <typename Trunk>
+int fusion_run(Trunk trunk, const float *sub24, const float *c3, const float *sub24_raw, const float *c3_raw, int n, int h16,
+               int w16, int classes, const float *params_dev, const float *stats_dev, int max_workgroups, const CallArgs &a,
+               const SemiArgs *semi, const IcnetFusionWs &t, const SemiWs &sw)
 {
-    if (!fusion_dims_ok(n, h, w, classes)) return -1;
-    Bump b(nullptr, 0);
-    (void)fusion_carve(b, n, h, w, classes, true);
-    return b.off + 256;
+    const uint8_t *tgt = nullptr;
+    if (wants_targets(sub24_raw, semi)) {
+        if (int rc = trunk(true)) return rc;
+        HIP_TRY(launch_icnet_fusion_targets(sub24_raw, c3_raw, n, h16, w16, classes, params_dev, stats_dev, max_workgroups, t,
+                                            semi_of_targets(*semi), sw.tgt, a.s));
+        tgt = sw.tgt;
+    }
+    if (int rc = trunk(false)) return rc;
+    return with_confusion(sw.rep, classes, semi ? semi->confusion : nullptr, a.s, [&](unsigned long long *rep, int reps) -> int {
+        IcnetHeadSemi sa = {};
+        if (semi) sa = semi_of_grad(*semi, tgt, rep, reps);
+        HIP_TRY(launch_icnet_fusion_grad(sub24, c3, n, h16, w16, classes, params_dev, stats_dev, a.labels, a.mask, a.weight,
+                                         a.label_smoothing, max_workgroups, t, a.loss, a.grad, a.s, semi ? &sa : nullptr));
+        return SSAL_OK;
+    });
 }
 
-SSAL_API int ssal_icnet_fusion_grad_nhwc(const float *sub24_dev, const float *conv3_sub1_dev, int n, int h, int w, int classes,
-                                         const float *params_dev, const uint8_t *labels_dev, const float *mask_dev,
-                                         float weight, float label_smoothing, const float *stats_dev, int max_workgroups,
-                                         double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+int fusion_grad_entry(const float *sub24_dev, const float *conv3_sub1_dev, const float *sub24_raw_dev,
+                      const float *conv3_sub1_raw_dev, int n, int h, int w, int classes, const float *params_dev,
+                      const float *stats_dev, int max_workgroups, const CallArgs &a, const SemiArgs *semi)
 {
-    int rc = fusion_check(n, h, w, classes, max_workgroups);
-    if (rc) return rc;
-    if (!sub24_dev || !conv3_sub1_dev || !params_dev || !stats_dev || !labels_dev || !mask_dev || !loss_dev || !grad_dev ||
-        !ws_dev)
-        return fail(SSAL_EINVAL, "NULL device pointer");
-    Bump b(ws_dev, ws_bytes);
+    if (int rc = fusion_check(n, h, w, classes, max_workgroups)) return rc;
+    if (int rc = args_check(sub24_dev && conv3_sub1_dev && params_dev && stats_dev, a, semi)) return rc;
+    const bool raw = sub24_raw_dev != nullptr;
+    if (int rc = raw_all_or_none((sub24_raw_dev != nullptr) + (conv3_sub1_raw_dev != nullptr), 2)) return rc;
+    Bump b(a.ws, a.ws_bytes);
     const IcnetFusionWs t = fusion_carve(b, n, h, w, classes, true);
-    if (!b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
-                           (long long)ssal_icnet_fusion_grad_workspace_bytes(n, h, w, classes), (long long)ws_bytes);
-    HIP_TRY(launch_icnet_fusion_grad(sub24_dev, conv3_sub1_dev, n, h, w, classes, params_dev, stats_dev, labels_dev, mask_dev,
-                                     weight, label_smoothing, max_workgroups, t, loss_dev, grad_dev, (hipStream_t)stream));
-    return SSAL_OK;
+    const SemiWs sw = semi_carve(b, n, 2 * h, 2 * w, classes, semi != nullptr, raw);
+    if (int rc = ws_check(fusion_bytes(0, n, h, w, classes, true, semi != nullptr, raw), b, a)) return rc;
+    return fusion_run(no_trunk, sub24_dev, conv3_sub1_dev, sub24_raw_dev, conv3_sub1_raw_dev, n, h, w, classes, params_dev,
+                      stats_dev, max_workgroups, a, semi, t, sw);
 }
 
-SSAL_API int64_t ssal_icnet_train_fusion_workspace_bytes(const ssal_icnet *net, int n, int h, int w)
-{
-    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 32 || w % 32) return -1;
-    Bump b(nullptr, 0);
-    b.off = carve(net, nullptr, 0, n, h, w).bytes;
-    (void)fusion_carve(b, n, h / 16, w / 16, net->classes, false);
-    return b.off + 256;
-}
-
-SSAL_API int ssal_icnet_train_fusion_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
-                                          const uint8_t *labels_dev, const float *mask_dev, const float *params_dev,
-                                          float weight, float label_smoothing, const float *stats_dev, int max_workgroups,
-                                          double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+int fusion_train_entry(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h, int w,
+                       const float *params_dev, const float *stats_dev, int max_workgroups, const CallArgs &a,
+                       const SemiArgs *semi)
 {
     int rc = check_dims(net, n, h, w);
     if (rc) return rc;
-    if ((rc = fusion_check(n, h / 16, w / 16, net->classes, max_workgroups))) return rc;
-    if (!x_dev || !params_dev || !stats_dev || !labels_dev || !mask_dev || !loss_dev || !grad_dev || !ws_dev)
-        return fail(SSAL_EINVAL, "NULL device pointer");
-    IcWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
-    Bump b(ws_dev, ws_bytes);
-    b.off = W.bytes;
-    IcnetFusionWs t = fusion_carve(b, n, h / 16, w / 16, net->classes, false);
-    if (!W.ok || !b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
-                                    (long long)ssal_icnet_train_fusion_workspace_bytes(net, n, h, w), (long long)ws_bytes);
-    // the block and the head being trained write this call's conv3_sub1_proj, sub12_sum and conv6_cls endpoints
-    t.proj = W.act.at("conv3_sub1_proj");
-    t.sub12 = W.act.at("sub12_sum");
-    t.head.lq = W.act.at("conv6_cls");
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<Grp> one(1);
-    one[0] = {W, x_dev, n, s};
-    HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false, false));
-    HIP_TRY(launch_icnet_fusion_grad(W.act.at("sub24_sum"), W.act.at("conv3_sub1"), n, h / 16, w / 16, net->classes, params_dev,
-                                     stats_dev, labels_dev, mask_dev, weight, label_smoothing, max_workgroups, t, loss_dev,
-                                     grad_dev, s));
-    return SSAL_OK;
+    const int K = net->classes, h16 = h / 16, w16 = w / 16;
+    const bool raw = x_raw_dev != nullptr;
+    if ((rc = fusion_check(n, h16, w16, K, max_workgroups))) return rc;
+    if ((rc = args_check(x_dev && params_dev && stats_dev, a, semi))) return rc;
+    IcWorkspace W;
+    Bump b = carve_behind_trunk(net, a, n, h, w, &W);
+    IcnetFusionWs t = fusion_carve(b, n, h16, w16, K, false);
+    const SemiWs sw = semi_carve(b, n, h / 8, w / 8, K, semi != nullptr, raw);
+    if ((rc = ws_check(fusion_bytes(W.bytes, n, h16, w16, K, false, semi != nullptr, raw), b, a))) return rc;
+    fusion_bind(t, W);
+    const float *sub24 = W.act.at("sub24_sum"), *c3 = W.act.at("conv3_sub1");
+    return fusion_run(frozen_trunk(net, W, x_dev, x_raw_dev, x_is_u8, n, h, w, a.s, false, true), sub24, c3,
+                      raw ? sub24 : nullptr, raw ? c3 : nullptr, n, h16, w16, K, params_dev, stats_dev, max_workgroups, a, semi, t,
+                      sw);
 }
 
-namespace {
+// ---- the whole cascade head (DESIGN.md sections 29 and 30; kernels: ssal_train_icnet_cascade.hip) ----
+// the buffers of one gradient call behind `b`; own_acts: the block's projection / sub24_sum and the fusion stage's activations
+// live here (the images entry keeps them in the network's endpoints instead)
+IcnetCascadeWs cascade_carve(Bump &b, int64_t n, int h32, int w32, int classes, bool own_acts)
+{
+    IcnetCascadeWs t;
+    const int h16 = 2 * h32, w16 = 2 * w32;
+    const int64_t act = n * h16 * (int64_t)w16 * 128;
+    t.wt_c = b.take<float>(CA_GC);
+    t.wt_d = b.take<float>(256 * 128);
+    t.rows = b.take<float>(512);
+    t.proj = own_acts ? b.take<float>(act) : nullptr;
+    t.sub24 = own_acts ? b.take<float>(act) : nullptr;
+    t.du = b.take<float>(4 * act);
+    t.g24 = b.take<float>(act);
+    t.part = b.take<float>((int64_t)CA_MAX_WG * CA_PART);  // (sized for the default grid: max_workgroups only lowers it)
+    t.fold = b.take<float>(CA_PART);
+    t.fusion = fusion_carve(b, n, h16, w16, classes, own_acts);
+    return t;
+}
 
-// the fusion trainer's eight variables at params_host + base -> the handle's host tensors, then the named layers re-laid-out,
-// folded with the handle's moving statistics and uploaded; `more`: further (tensor, offset, count) in front of them
-struct PackedTensor {
+int64_t cascade_bytes(int64_t front, int n, int h32, int w32, int classes, bool own_acts, bool semi, bool with_raw)
+{
+    Bump b(nullptr, 0);
+    b.off = front;
+    (void)cascade_carve(b, n, h32, w32, classes, own_acts);
+    (void)semi_carve(b, n, 4 * h32, 4 * w32, classes, semi, with_raw);
+    return b.off + 256;
+}
+
+// the images entry: both blocks and the head being trained write this call's endpoints from conv3_1_sub2_proj on
+void cascade_bind(IcnetCascadeWs &t, const IcWorkspace &W)
+{
+    t.proj = W.act.at("conv3_1_sub2_proj");
+    t.sub24 = W.act.at("sub24_sum");
+    fusion_bind(t.fusion, W);
+}
+
+bool cascade_fits(int n, int h32, int w32) { return icnet_cascade_fits(h32, w32) && fusion_fits(n, 2 * h32, 2 * w32); }
+
+int cascade_check(int n, int h32, int w32, int classes, int max_workgroups)
+{
+    return capped_dims_check(n, h32, w32, classes, max_workgroups, cascade_fits(n, h32, w32), "cascade gradient kernels'");
+}
+
+// c54 [n,h32,w32,256] / c31 [n,2 h32,2 w32,256] / c3 [n,4 h32,4 w32,64]: conv5_4_k1, conv3_1 and conv3_sub1 of the training
+// frames, *_raw: of the undistorted frames (all or none); trunk and the slots as for fusion_run, with both blocks.
+template <typename Trunk>
+int cascade_run(Trunk trunk, const float *c54, const float *c31, const float *c3, const float *c54_raw, const float *c31_raw,
+                const float *c3_raw, int n, int h32, int w32, int classes, const float *params_dev, const float *stats_dev,
+                int max_workgroups, const CallArgs &a, const SemiArgs *semi, const IcnetCascadeWs &t, const SemiWs &sw)
+{
+    const uint8_t *tgt = nullptr;
+    if (wants_targets(c54_raw, semi)) {
+        if (int rc = trunk(true)) return rc;
+        HIP_TRY(launch_icnet_cascade_targets(c54_raw, c31_raw, c3_raw, n, h32, w32, classes, params_dev, stats_dev,
+                                             max_workgroups, t, semi_of_targets(*semi), sw.tgt, a.s));
+        tgt = sw.tgt;
+    }
+    if (int rc = trunk(false)) return rc;
+    return with_confusion(sw.rep, classes, semi ? semi->confusion : nullptr, a.s, [&](unsigned long long *rep, int reps) -> int {
+        IcnetHeadSemi sa = {};
+        if (semi) sa = semi_of_grad(*semi, tgt, rep, reps);
+        HIP_TRY(launch_icnet_cascade_grad(c54, c31, c3, n, h32, w32, classes, params_dev, stats_dev, a.labels, a.mask, a.weight,
+                                          a.label_smoothing, max_workgroups, t, a.loss, a.grad, a.s, semi ? &sa : nullptr));
+        return SSAL_OK;
+    });
+}
+
+int cascade_grad_entry(const float *conv5_4_k1_dev, const float *conv3_1_dev, const float *conv3_sub1_dev,
+                       const float *conv5_4_k1_raw_dev, const float *conv3_1_raw_dev, const float *conv3_sub1_raw_dev, int n,
+                       int h, int w, int classes, const float *params_dev, const float *stats_dev, int max_workgroups,
+                       const CallArgs &a, const SemiArgs *semi)
+{
+    if (int rc = cascade_check(n, h, w, classes, max_workgroups)) return rc;
+    if (int rc = args_check(conv5_4_k1_dev && conv3_1_dev && conv3_sub1_dev && params_dev && stats_dev, a, semi)) return rc;
+    const bool raw = conv5_4_k1_raw_dev != nullptr;
+    if (int rc = raw_all_or_none((conv5_4_k1_raw_dev != nullptr) + (conv3_1_raw_dev != nullptr) + (conv3_sub1_raw_dev != nullptr),
+                                 3))
+        return rc;
+    Bump b(a.ws, a.ws_bytes);
+    const IcnetCascadeWs t = cascade_carve(b, n, h, w, classes, true);
+    const SemiWs sw = semi_carve(b, n, 4 * h, 4 * w, classes, semi != nullptr, raw);
+    if (int rc = ws_check(cascade_bytes(0, n, h, w, classes, true, semi != nullptr, raw), b, a)) return rc;
+    return cascade_run(no_trunk, conv5_4_k1_dev, conv3_1_dev, conv3_sub1_dev, conv5_4_k1_raw_dev, conv3_1_raw_dev,
+                       conv3_sub1_raw_dev, n, h, w, classes, params_dev, stats_dev, max_workgroups, a, semi, t, sw);
+}
+
+int cascade_train_entry(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h, int w,
+                        const float *params_dev, const float *stats_dev, int max_workgroups, const CallArgs &a,
+                        const SemiArgs *semi)
+{
+    int rc = check_dims(net, n, h, w);
+    if (rc) return rc;
+    const int K = net->classes, h32 = h / 32, w32 = w / 32;
+    const bool raw = x_raw_dev != nullptr;
+    if ((rc = cascade_check(n, h32, w32, K, max_workgroups))) return rc;
+    if ((rc = args_check(x_dev && params_dev && stats_dev, a, semi))) return rc;
+    IcWorkspace W;
+    Bump b = carve_behind_trunk(net, a, n, h, w, &W);
+    IcnetCascadeWs t = cascade_carve(b, n, h32, w32, K, false);
+    const SemiWs sw = semi_carve(b, n, h / 8, w / 8, K, semi != nullptr, raw);
+    if ((rc = ws_check(cascade_bytes(W.bytes, n, h32, w32, K, false, semi != nullptr, raw), b, a))) return rc;
+    cascade_bind(t, W);
+    const float *c54 = W.act.at("conv5_4_k1"), *c31 = W.act.at("conv3_1"), *c3 = W.act.at("conv3_sub1");
+    return cascade_run(frozen_trunk(net, W, x_dev, x_raw_dev, x_is_u8, n, h, w, a.s, false, false), c54, c31, c3,
+                       raw ? c54 : nullptr, raw ? c31 : nullptr, raw ? c3 : nullptr, n, h32, w32, K, params_dev, stats_dev,
+                       max_workgroups, a, semi, t, sw);
+}
+
+// ---- the trained variables back into the handle ----
+// Each (tensor, host pointer, count) goes into the handle's host tensors; then the named layers are re-laid-out, folded with
+// the handle's moving statistics and uploaded.
+struct HostUpdate {
     const char *name;
-    int64_t off, count;
+    const float *host;
+    int64_t count;
 };
 
-int update_packed(ssal_icnet *net, const float *params_host, const std::vector<PackedTensor> &more, int64_t base,
-                  const std::set<std::string> &layers, void *stream)
+int update_packed(ssal_icnet *net, const std::vector<HostUpdate> &tensors, const std::set<std::string> &layers, void *stream)
 {
     if (!net->committed) return fail(SSAL_ESTATE, "ssal_icnet_commit() has not been called");
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess || dev != net->device)
         return fail(SSAL_ESTATE, "the handle was committed on device %d but the current device is %d (one handle per device)",
                     net->device, dev);
-    const int K = net->classes;
-    auto put = [&](const std::string &name, int64_t off, size_t count) {
-        net->tensors[net->index.at(name)].data.assign(params_host + off, params_host + off + count);
-    };
-    for (const PackedTensor &t : more) put(t.name, t.off, (size_t)t.count);
-    put("conv_sub2.kernel", base + FU_KA, FU_GA);
-    put("conv_sub2.gamma", base + FU_GA, 128);
-    put("conv_sub2.beta", base + FU_BA, 128);
-    put("conv3_sub1_proj.kernel", base + FU_KB, 64 * 128);
-    put("conv3_sub1_proj.gamma", base + FU_GB, 128);
-    put("conv3_sub1_proj.beta", base + FU_BB, 128);
-    put("conv6_cls.kernel", base + FU_HEAD, 128 * (size_t)K);
-    put("conv6_cls.bias", base + FU_HEAD + 128 * K, K);
+    for (const HostUpdate &t : tensors) net->tensors[net->index.at(t.name)].data.assign(t.host, t.host + t.count);
     hipStream_t s = (hipStream_t)stream;
     // the staging vectors live until the synchronisation below
     std::vector<std::vector<float>> keep;
@@ -1180,172 +1190,131 @@ int update_packed(ssal_icnet *net, const float *params_host, const std::vector<P
     return SSAL_OK;
 }
 
-}  // namespace
-
-SSAL_API int ssal_icnet_update_fusion(ssal_icnet *net, const float *params_host, void *stream)
+// the packed head (ssal_train_icnet.h) / the fusion trainer's packed vector (ssal_train_icnet_fusion.h) at p
+std::vector<HostUpdate> head_tensors(const float *kernel, const float *bias, int K)
 {
-    if (!net || !params_host) return fail(SSAL_EINVAL, "NULL argument");
-    return update_packed(net, params_host, {}, 0, {"conv_sub2", "conv3_sub1_proj", "conv6_cls"}, stream);
+    return {{"conv6_cls.kernel", kernel, 128 * (int64_t)K}, {"conv6_cls.bias", bias, K}};
 }
 
-// ------------------------------------------------------------------------------------------------
-// training of the whole cascade head (kernels: ssal_train_icnet_cascade.hip)
-// ------------------------------------------------------------------------------------------------
-namespace {
-
-// the buffers of one gradient call behind `b`; own_acts: the block's projection / sub24_sum and the fusion stage's activations
-// live here (the images entry keeps them in the network's endpoints instead)
-IcnetCascadeWs cascade_carve(Bump &b, int64_t n, int h32, int w32, int classes, bool own_acts)
+std::vector<HostUpdate> fusion_tensors(const float *p, int K)
 {
-    IcnetCascadeWs t;
-    const int h16 = 2 * h32, w16 = 2 * w32;
-    const int64_t act = n * h16 * (int64_t)w16 * 128;
-    t.wt_c = b.take<float>(CA_GC);
-    t.wt_d = b.take<float>(256 * 128);
-    t.rows = b.take<float>(512);
-    t.proj = own_acts ? b.take<float>(act) : nullptr;
-    t.sub24 = own_acts ? b.take<float>(act) : nullptr;
-    t.du = b.take<float>(4 * act);
-    t.g24 = b.take<float>(act);
-    t.part = b.take<float>((int64_t)CA_MAX_WG * CA_PART);  // (sized for the default grid: max_workgroups only lowers it)
-    t.fold = b.take<float>(CA_PART);
-    t.fusion = fusion_carve(b, n, h16, w16, classes, own_acts);
+    std::vector<HostUpdate> t = {{"conv_sub2.kernel", p + FU_KA, FU_GA},
+                                 {"conv_sub2.gamma", p + FU_GA, 128},
+                                 {"conv_sub2.beta", p + FU_BA, 128},
+                                 {"conv3_sub1_proj.kernel", p + FU_KB, 64 * 128},
+                                 {"conv3_sub1_proj.gamma", p + FU_GB, 128},
+                                 {"conv3_sub1_proj.beta", p + FU_BB, 128}};
+    for (const HostUpdate &u : head_tensors(p + FU_HEAD, p + FU_HEAD + 128 * K, K)) t.push_back(u);
     return t;
 }
 
-bool cascade_dims_ok(int n, int h32, int w32, int classes)
-{
-    return icnet_cascade_fits(h32, w32) && fusion_dims_ok(n, 2 * h32, 2 * w32, classes);
-}
-
-int cascade_check(int n, int h32, int w32, int classes, int max_workgroups)
-{
-    if (n <= 0) return fail(SSAL_EINVAL, "bad dims n=%d h=%d w=%d", n, h32, w32);
-    if (classes < 2 || classes > 32) return fail(SSAL_EINVAL, "classes must be in [2,32] (got %d)", classes);
-    if (max_workgroups < 0) return fail(SSAL_EINVAL, "max_workgroups must be >= 0 (got %d)", max_workgroups);
-    if (!cascade_dims_ok(n, h32, w32, classes))
-        return fail(SSAL_EINVAL, "feature map %dx%d (n=%d) is beyond the cascade gradient kernels' limit", h32, w32, n);
-    return SSAL_OK;
-}
-
 }  // namespace
 
-SSAL_API int64_t ssal_icnet_cascade_grad_workspace_bytes(int n, int h, int w, int classes)
+// ---- the output layer ----
+SSAL_API int64_t ssal_icnet_head_grad_workspace_bytes(int n, int h, int w, int classes)
 {
-    if (n <= 0 || !cascade_dims_ok(n, h, w, classes)) return -1;
-    Bump b(nullptr, 0);
-    (void)cascade_carve(b, n, h, w, classes, true);
-    return b.off + 256;
+    return capped_dims_ok(n, classes, head_fits(n, h, w)) ? head_bytes(0, n, h, w, classes, true, false, false) : -1;
 }
 
-SSAL_API int ssal_icnet_cascade_grad_nhwc(const float *conv5_4_k1_dev, const float *conv3_1_dev, const float *conv3_sub1_dev,
-                                          int n, int h, int w, int classes, const float *params_dev,
-                                          const uint8_t *labels_dev, const float *mask_dev, float weight,
-                                          float label_smoothing, const float *stats_dev, int max_workgroups, double *loss_dev,
-                                          float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+SSAL_API int ssal_icnet_head_grad_nhwc(const float *sub12_dev, int n, int h, int w, int classes, const float *head_dev,
+                                       const uint8_t *labels_dev, const float *mask_dev, float weight,
+                                       float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev,
+                                       void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    int rc = cascade_check(n, h, w, classes, max_workgroups);
-    if (rc) return rc;
-    if (!conv5_4_k1_dev || !conv3_1_dev || !conv3_sub1_dev || !params_dev || !stats_dev || !labels_dev || !mask_dev ||
-        !loss_dev || !grad_dev || !ws_dev)
-        return fail(SSAL_EINVAL, "NULL device pointer");
-    Bump b(ws_dev, ws_bytes);
-    const IcnetCascadeWs t = cascade_carve(b, n, h, w, classes, true);
-    if (!b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
-                           (long long)ssal_icnet_cascade_grad_workspace_bytes(n, h, w, classes), (long long)ws_bytes);
-    HIP_TRY(launch_icnet_cascade_grad(conv5_4_k1_dev, conv3_1_dev, conv3_sub1_dev, n, h, w, classes, params_dev, stats_dev,
-                                      labels_dev, mask_dev, weight, label_smoothing, max_workgroups, t, loss_dev, grad_dev,
-                                      (hipStream_t)stream));
-    return SSAL_OK;
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return head_grad_entry(sub12_dev, nullptr, n, h, w, classes, head_dev, max_workgroups, a, nullptr);
 }
 
-SSAL_API int64_t ssal_icnet_train_cascade_workspace_bytes(const ssal_icnet *net, int n, int h, int w)
+SSAL_API int64_t ssal_icnet_train_head_workspace_bytes(const ssal_icnet *net, int n, int h, int w)
 {
-    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 32 || w % 32) return -1;
-    Bump b(nullptr, 0);
-    b.off = carve(net, nullptr, 0, n, h, w).bytes;
-    (void)cascade_carve(b, n, h / 32, w / 32, net->classes, false);
-    return b.off + 256;
+    if (!net_dims_ok(net, n, h, w)) return -1;
+    return head_bytes(trunk_bytes(net, n, h, w), n, h / 8, w / 8, net->classes, false, false, false);
 }
 
-SSAL_API int ssal_icnet_train_cascade_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
-                                           const uint8_t *labels_dev, const float *mask_dev, const float *params_dev,
-                                           float weight, float label_smoothing, const float *stats_dev, int max_workgroups,
-                                           double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+SSAL_API int ssal_icnet_train_head_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                                        const uint8_t *labels_dev, const float *mask_dev, const float *head_dev,
+                                        float weight, float label_smoothing, int max_workgroups, double *loss_dev,
+                                        float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    int rc = check_dims(net, n, h, w);
-    if (rc) return rc;
-    if ((rc = cascade_check(n, h / 32, w / 32, net->classes, max_workgroups))) return rc;
-    if (!x_dev || !params_dev || !stats_dev || !labels_dev || !mask_dev || !loss_dev || !grad_dev || !ws_dev)
-        return fail(SSAL_EINVAL, "NULL device pointer");
-    IcWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
-    Bump b(ws_dev, ws_bytes);
-    b.off = W.bytes;
-    IcnetCascadeWs t = cascade_carve(b, n, h / 32, w / 32, net->classes, false);
-    if (!W.ok || !b.ok) return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
-                                    (long long)ssal_icnet_train_cascade_workspace_bytes(net, n, h, w), (long long)ws_bytes);
-    // both blocks and the head being trained write this call's endpoints from conv3_1_sub2_proj on
-    t.proj = W.act.at("conv3_1_sub2_proj");
-    t.sub24 = W.act.at("sub24_sum");
-    t.fusion.proj = W.act.at("conv3_sub1_proj");
-    t.fusion.sub12 = W.act.at("sub12_sum");
-    t.fusion.head.lq = W.act.at("conv6_cls");
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<Grp> one(1);
-    one[0] = {W, x_dev, n, s};
-    HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false, false, false));
-    HIP_TRY(launch_icnet_cascade_grad(W.act.at("conv5_4_k1"), W.act.at("conv3_1"), W.act.at("conv3_sub1"), n, h / 32, w / 32,
-                                      net->classes, params_dev, stats_dev, labels_dev, mask_dev, weight, label_smoothing,
-                                      max_workgroups, t, loss_dev, grad_dev, s));
-    return SSAL_OK;
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return head_train_entry(net, x_dev, nullptr, x_is_u8, n, h, w, head_dev, max_workgroups, a, nullptr);
 }
 
-SSAL_API int ssal_icnet_update_cascade(ssal_icnet *net, const float *params_host, void *stream)
+SSAL_API int64_t ssal_icnet_head_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw)
 {
-    if (!net || !params_host) return fail(SSAL_EINVAL, "NULL argument");
-    return update_packed(net, params_host,
-                         {{"conv_sub4.kernel", CA_KC, CA_GC}, {"conv_sub4.gamma", CA_GC, 128}, {"conv_sub4.beta", CA_BC, 128},
-                          {"conv3_1_sub2_proj.kernel", CA_KD, 256 * 128}, {"conv3_1_sub2_proj.gamma", CA_GD, 128},
-                          {"conv3_1_sub2_proj.beta", CA_BD, 128}},
-                         CA_FUSION, {"conv_sub4", "conv3_1_sub2_proj", "conv_sub2", "conv3_sub1_proj", "conv6_cls"}, stream);
+    return capped_dims_ok(n, classes, head_fits(n, h, w)) ? head_bytes(0, n, h, w, classes, true, true, with_raw != 0) : -1;
 }
 
-// ------------------------------------------------------------------------------------------------
-// the semi-supervised step of the fusion and the cascade trainer: the plain entries' buffers, then
-// head_semi_carve's (the confusion replicas; with a raw side one packed target byte per loss pixel)
-// ------------------------------------------------------------------------------------------------
-namespace {
-
-// the training tail of a semi call, as head_semi_tail: `grad` launches the gradient with the kernel's semi argument
-template <typename Launch>
-int deep_semi_tail(const HeadSemiWs &sw, int classes, const uint8_t *labelled_dev, int measure, float threshold,
-                   const uint8_t *tgt, int64_t *confusion_dev, int64_t *pseudo_pixels_dev, hipStream_t s, Launch grad)
+SSAL_API int ssal_icnet_head_grad_semi_nhwc(const float *sub12_dev, const float *sub12_raw_dev, int n, int h, int w,
+                                            int classes, const float *head_dev, const uint8_t *labels_dev,
+                                            const float *mask_dev, const uint8_t *labelled_dev, int measure,
+                                            float threshold, float weight, float label_smoothing, int max_workgroups,
+                                            double *loss_dev, float *grad_dev, int64_t *confusion_dev,
+                                            int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    const int reps = ssal::knobs().conf_reps;
-    if (confusion_dev) HIP_TRY(hipMemsetAsync(sw.rep, 0, (size_t)reps * ssal::conf_rep_stride(classes * classes) * 8, s));
-    const IcnetHeadSemi sa = {labelled_dev, measure, threshold, tgt, nullptr, confusion_dev ? sw.rep : nullptr, reps,
-                              (unsigned long long *)pseudo_pixels_dev};
-    HIP_TRY(grad(&sa));
-    if (confusion_dev) HIP_TRY(launch_confusion_fold(sw.rep, reps, classes, confusion_dev, s));
-    return SSAL_OK;
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, sub12_raw_dev != nullptr};
+    return head_grad_entry(sub12_dev, sub12_raw_dev, n, h, w, classes, head_dev, max_workgroups, a, &semi);
 }
 
-// the raw pointers of a features entry come all or none
-int raw_all_or_none(int given, int of)
+SSAL_API int64_t ssal_icnet_train_head_semi_workspace_bytes(const ssal_icnet *net, int n, int h, int w, int with_raw)
 {
-    if (given != 0 && given != of) return fail(SSAL_EINVAL, "the raw feature pointers must be given together (%d of %d)", given, of);
-    return SSAL_OK;
+    if (!net_dims_ok(net, n, h, w)) return -1;
+    return head_bytes(trunk_bytes(net, n, h, w), n, h / 8, w / 8, net->classes, false, true, with_raw != 0);
 }
 
-}  // namespace
+SSAL_API int ssal_icnet_train_head_semi_nhwc(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
+                                             int h, int w, const uint8_t *labels_dev, const float *mask_dev,
+                                             const uint8_t *labelled_dev, int measure, float threshold,
+                                             const float *head_dev, float weight, float label_smoothing, int max_workgroups,
+                                             double *loss_dev, float *grad_dev, int64_t *confusion_dev,
+                                             int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev != nullptr};
+    return head_train_entry(net, x_dev, x_raw_dev, x_is_u8, n, h, w, head_dev, max_workgroups, a, &semi);
+}
+
+SSAL_API int ssal_icnet_update_head(ssal_icnet *net, const float *kernel_host, const float *bias_host, void *stream)
+{
+    if (!net || !kernel_host || !bias_host) return fail(SSAL_EINVAL, "NULL argument");
+    return update_packed(net, head_tensors(kernel_host, bias_host, net->classes), {"conv6_cls"}, stream);
+}
+
+// ---- the last fusion stage ----
+SSAL_API int64_t ssal_icnet_fusion_grad_workspace_bytes(int n, int h, int w, int classes)
+{
+    return capped_dims_ok(n, classes, fusion_fits(n, h, w)) ? fusion_bytes(0, n, h, w, classes, true, false, false) : -1;
+}
+
+SSAL_API int ssal_icnet_fusion_grad_nhwc(const float *sub24_dev, const float *conv3_sub1_dev, int n, int h, int w, int classes,
+                                         const float *params_dev, const uint8_t *labels_dev, const float *mask_dev,
+                                         float weight, float label_smoothing, const float *stats_dev, int max_workgroups,
+                                         double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return fusion_grad_entry(sub24_dev, conv3_sub1_dev, nullptr, nullptr, n, h, w, classes, params_dev, stats_dev, max_workgroups,
+                             a, nullptr);
+}
+
+SSAL_API int64_t ssal_icnet_train_fusion_workspace_bytes(const ssal_icnet *net, int n, int h, int w)
+{
+    if (!net_dims_ok(net, n, h, w)) return -1;
+    return fusion_bytes(trunk_bytes(net, n, h, w), n, h / 16, w / 16, net->classes, false, false, false);
+}
+
+SSAL_API int ssal_icnet_train_fusion_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                                          const uint8_t *labels_dev, const float *mask_dev, const float *params_dev,
+                                          float weight, float label_smoothing, const float *stats_dev, int max_workgroups,
+                                          double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return fusion_train_entry(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, stats_dev, max_workgroups, a, nullptr);
+}
 
 SSAL_API int64_t ssal_icnet_fusion_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw)
 {
-    if (!fusion_dims_ok(n, h, w, classes)) return -1;
-    Bump b(nullptr, 0);
-    (void)fusion_carve(b, n, h, w, classes, true);
-    (void)head_semi_carve(b, n, 2 * h, 2 * w, classes, with_raw != 0);
-    return b.off + 256;
+    return capped_dims_ok(n, classes, fusion_fits(n, h, w)) ? fusion_bytes(0, n, h, w, classes, true, true, with_raw != 0) : -1;
 }
 
 SSAL_API int ssal_icnet_fusion_grad_semi_nhwc(const float *sub24_dev, const float *conv3_sub1_dev, const float *sub24_raw_dev,
@@ -1356,45 +1325,16 @@ SSAL_API int ssal_icnet_fusion_grad_semi_nhwc(const float *sub24_dev, const floa
                                               double *loss_dev, float *grad_dev, int64_t *confusion_dev,
                                               int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    int rc = fusion_check(n, h, w, classes, max_workgroups);
-    if (rc) return rc;
-    if ((rc = head_semi_check(sub24_dev && conv3_sub1_dev && params_dev && stats_dev, labels_dev, mask_dev, labelled_dev,
-                              measure, loss_dev, grad_dev, ws_dev)))
-        return rc;
-    const bool raw = sub24_raw_dev != nullptr;
-    if ((rc = raw_all_or_none((sub24_raw_dev != nullptr) + (conv3_sub1_raw_dev != nullptr), 2))) return rc;
-    Bump b(ws_dev, ws_bytes);
-    const IcnetFusionWs t = fusion_carve(b, n, h, w, classes, true);
-    const HeadSemiWs sw = head_semi_carve(b, n, 2 * h, 2 * w, classes, raw);
-    if (!b.ok)
-        return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
-                    (long long)ssal_icnet_fusion_grad_semi_workspace_bytes(n, h, w, classes, raw), (long long)ws_bytes);
-    hipStream_t s = (hipStream_t)stream;
-    // the undistorted frame's features matter only where an image is unlabelled: the block and the head on them into t's
-    // slots, the target launch; then the training features go through the same slots
-    const uint8_t *tgt = nullptr;
-    if (raw && labelled_dev) {
-        const IcnetHeadSemi sa = {labelled_dev, measure, threshold, nullptr, nullptr, nullptr, 0, nullptr};
-        HIP_TRY(launch_icnet_fusion_targets(sub24_raw_dev, conv3_sub1_raw_dev, n, h, w, classes, params_dev, stats_dev,
-                                            max_workgroups, t, sa, sw.tgt, s));
-        tgt = sw.tgt;
-    }
-    return deep_semi_tail(sw, classes, labelled_dev, measure, threshold, tgt, confusion_dev, pseudo_pixels_dev, s,
-                          [&](const IcnetHeadSemi *sa) {
-                              return launch_icnet_fusion_grad(sub24_dev, conv3_sub1_dev, n, h, w, classes, params_dev, stats_dev,
-                                                              labels_dev, mask_dev, weight, label_smoothing, max_workgroups, t,
-                                                              loss_dev, grad_dev, s, sa);
-                          });
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, sub24_raw_dev != nullptr};
+    return fusion_grad_entry(sub24_dev, conv3_sub1_dev, sub24_raw_dev, conv3_sub1_raw_dev, n, h, w, classes, params_dev, stats_dev,
+                             max_workgroups, a, &semi);
 }
 
 SSAL_API int64_t ssal_icnet_train_fusion_semi_workspace_bytes(const ssal_icnet *net, int n, int h, int w, int with_raw)
 {
-    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 32 || w % 32) return -1;
-    Bump b(nullptr, 0);
-    b.off = carve(net, nullptr, 0, n, h, w).bytes;
-    (void)fusion_carve(b, n, h / 16, w / 16, net->classes, false);
-    (void)head_semi_carve(b, n, h / 8, w / 8, net->classes, with_raw != 0);
-    return b.off + 256;
+    if (!net_dims_ok(net, n, h, w)) return -1;
+    return fusion_bytes(trunk_bytes(net, n, h, w), n, h / 16, w / 16, net->classes, false, true, with_raw != 0);
 }
 
 SSAL_API int ssal_icnet_train_fusion_semi_nhwc(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
@@ -1405,55 +1345,52 @@ SSAL_API int ssal_icnet_train_fusion_semi_nhwc(ssal_icnet *net, const void *x_de
                                                int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev,
                                                int64_t ws_bytes, void *stream)
 {
-    int rc = check_dims(net, n, h, w);
-    if (rc) return rc;
-    if ((rc = fusion_check(n, h / 16, w / 16, net->classes, max_workgroups))) return rc;
-    if ((rc = head_semi_check(x_dev && params_dev && stats_dev, labels_dev, mask_dev, labelled_dev, measure, loss_dev, grad_dev,
-                              ws_dev)))
-        return rc;
-    IcWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
-    Bump b(ws_dev, ws_bytes);
-    b.off = W.bytes;
-    IcnetFusionWs t = fusion_carve(b, n, h / 16, w / 16, net->classes, false);
-    const HeadSemiWs sw = head_semi_carve(b, n, h / 8, w / 8, net->classes, x_raw_dev != nullptr);
-    if (!W.ok || !b.ok)
-        return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
-                    (long long)ssal_icnet_train_fusion_semi_workspace_bytes(net, n, h, w, x_raw_dev != nullptr),
-                    (long long)ws_bytes);
-    t.proj = W.act.at("conv3_sub1_proj");
-    t.sub12 = W.act.at("sub12_sum");
-    t.head.lq = W.act.at("conv6_cls");
-    const int K = net->classes;
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<Grp> one(1);
-    // the undistorted frames go through the trunk only where an image is unlabelled, and first: the target launch leaves one
-    // byte per loss pixel, so the training frames can go through the same slots afterwards
-    const uint8_t *tgt = nullptr;
-    if (x_raw_dev && labelled_dev) {
-        one[0] = {W, x_raw_dev, n, s};
-        HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false, false));
-        const IcnetHeadSemi sa = {labelled_dev, measure, threshold, nullptr, nullptr, nullptr, 0, nullptr};
-        HIP_TRY(launch_icnet_fusion_targets(W.act.at("sub24_sum"), W.act.at("conv3_sub1"), n, h / 16, w / 16, K, params_dev,
-                                            stats_dev, max_workgroups, t, sa, sw.tgt, s));
-        tgt = sw.tgt;
-    }
-    one[0] = {W, x_dev, n, s};
-    HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false, false));
-    return deep_semi_tail(sw, K, labelled_dev, measure, threshold, tgt, confusion_dev, pseudo_pixels_dev, s,
-                          [&](const IcnetHeadSemi *sa) {
-                              return launch_icnet_fusion_grad(W.act.at("sub24_sum"), W.act.at("conv3_sub1"), n, h / 16, w / 16, K,
-                                                              params_dev, stats_dev, labels_dev, mask_dev, weight,
-                                                              label_smoothing, max_workgroups, t, loss_dev, grad_dev, s, sa);
-                          });
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev != nullptr};
+    return fusion_train_entry(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, stats_dev, max_workgroups, a, &semi);
+}
+
+SSAL_API int ssal_icnet_update_fusion(ssal_icnet *net, const float *params_host, void *stream)
+{
+    if (!net || !params_host) return fail(SSAL_EINVAL, "NULL argument");
+    return update_packed(net, fusion_tensors(params_host, net->classes), {"conv_sub2", "conv3_sub1_proj", "conv6_cls"}, stream);
+}
+
+// ---- the whole cascade head ----
+SSAL_API int64_t ssal_icnet_cascade_grad_workspace_bytes(int n, int h, int w, int classes)
+{
+    return capped_dims_ok(n, classes, cascade_fits(n, h, w)) ? cascade_bytes(0, n, h, w, classes, true, false, false) : -1;
+}
+
+SSAL_API int ssal_icnet_cascade_grad_nhwc(const float *conv5_4_k1_dev, const float *conv3_1_dev, const float *conv3_sub1_dev,
+                                          int n, int h, int w, int classes, const float *params_dev,
+                                          const uint8_t *labels_dev, const float *mask_dev, float weight,
+                                          float label_smoothing, const float *stats_dev, int max_workgroups, double *loss_dev,
+                                          float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return cascade_grad_entry(conv5_4_k1_dev, conv3_1_dev, conv3_sub1_dev, nullptr, nullptr, nullptr, n, h, w, classes, params_dev,
+                              stats_dev, max_workgroups, a, nullptr);
+}
+
+SSAL_API int64_t ssal_icnet_train_cascade_workspace_bytes(const ssal_icnet *net, int n, int h, int w)
+{
+    if (!net_dims_ok(net, n, h, w)) return -1;
+    return cascade_bytes(trunk_bytes(net, n, h, w), n, h / 32, w / 32, net->classes, false, false, false);
+}
+
+SSAL_API int ssal_icnet_train_cascade_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                                           const uint8_t *labels_dev, const float *mask_dev, const float *params_dev,
+                                           float weight, float label_smoothing, const float *stats_dev, int max_workgroups,
+                                           double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return cascade_train_entry(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, stats_dev, max_workgroups, a, nullptr);
 }
 
 SSAL_API int64_t ssal_icnet_cascade_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw)
 {
-    if (n <= 0 || !cascade_dims_ok(n, h, w, classes)) return -1;
-    Bump b(nullptr, 0);
-    (void)cascade_carve(b, n, h, w, classes, true);
-    (void)head_semi_carve(b, n, 4 * h, 4 * w, classes, with_raw != 0);
-    return b.off + 256;
+    return capped_dims_ok(n, classes, cascade_fits(n, h, w)) ? cascade_bytes(0, n, h, w, classes, true, true, with_raw != 0) : -1;
 }
 
 SSAL_API int ssal_icnet_cascade_grad_semi_nhwc(const float *conv5_4_k1_dev, const float *conv3_1_dev,
@@ -1465,45 +1402,16 @@ SSAL_API int ssal_icnet_cascade_grad_semi_nhwc(const float *conv5_4_k1_dev, cons
                                                int max_workgroups, double *loss_dev, float *grad_dev, int64_t *confusion_dev,
                                                int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    int rc = cascade_check(n, h, w, classes, max_workgroups);
-    if (rc) return rc;
-    if ((rc = head_semi_check(conv5_4_k1_dev && conv3_1_dev && conv3_sub1_dev && params_dev && stats_dev, labels_dev, mask_dev,
-                              labelled_dev, measure, loss_dev, grad_dev, ws_dev)))
-        return rc;
-    const bool raw = conv5_4_k1_raw_dev != nullptr;
-    if ((rc = raw_all_or_none((conv5_4_k1_raw_dev != nullptr) + (conv3_1_raw_dev != nullptr) + (conv3_sub1_raw_dev != nullptr),
-                              3)))
-        return rc;
-    Bump b(ws_dev, ws_bytes);
-    const IcnetCascadeWs t = cascade_carve(b, n, h, w, classes, true);
-    const HeadSemiWs sw = head_semi_carve(b, n, 4 * h, 4 * w, classes, raw);
-    if (!b.ok)
-        return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
-                    (long long)ssal_icnet_cascade_grad_semi_workspace_bytes(n, h, w, classes, raw), (long long)ws_bytes);
-    hipStream_t s = (hipStream_t)stream;
-    const uint8_t *tgt = nullptr;
-    if (raw && labelled_dev) {  // both blocks and the head on the undistorted frame's features first, through t's slots
-        const IcnetHeadSemi sa = {labelled_dev, measure, threshold, nullptr, nullptr, nullptr, 0, nullptr};
-        HIP_TRY(launch_icnet_cascade_targets(conv5_4_k1_raw_dev, conv3_1_raw_dev, conv3_sub1_raw_dev, n, h, w, classes,
-                                             params_dev, stats_dev, max_workgroups, t, sa, sw.tgt, s));
-        tgt = sw.tgt;
-    }
-    return deep_semi_tail(sw, classes, labelled_dev, measure, threshold, tgt, confusion_dev, pseudo_pixels_dev, s,
-                          [&](const IcnetHeadSemi *sa) {
-                              return launch_icnet_cascade_grad(conv5_4_k1_dev, conv3_1_dev, conv3_sub1_dev, n, h, w, classes,
-                                                               params_dev, stats_dev, labels_dev, mask_dev, weight,
-                                                               label_smoothing, max_workgroups, t, loss_dev, grad_dev, s, sa);
-                          });
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, conv5_4_k1_raw_dev != nullptr};
+    return cascade_grad_entry(conv5_4_k1_dev, conv3_1_dev, conv3_sub1_dev, conv5_4_k1_raw_dev, conv3_1_raw_dev, conv3_sub1_raw_dev,
+                              n, h, w, classes, params_dev, stats_dev, max_workgroups, a, &semi);
 }
 
 SSAL_API int64_t ssal_icnet_train_cascade_semi_workspace_bytes(const ssal_icnet *net, int n, int h, int w, int with_raw)
 {
-    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 32 || w % 32) return -1;
-    Bump b(nullptr, 0);
-    b.off = carve(net, nullptr, 0, n, h, w).bytes;
-    (void)cascade_carve(b, n, h / 32, w / 32, net->classes, false);
-    (void)head_semi_carve(b, n, h / 8, w / 8, net->classes, with_raw != 0);
-    return b.off + 256;
+    if (!net_dims_ok(net, n, h, w)) return -1;
+    return cascade_bytes(trunk_bytes(net, n, h, w), n, h / 32, w / 32, net->classes, false, true, with_raw != 0);
 }
 
 SSAL_API int ssal_icnet_train_cascade_semi_nhwc(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
@@ -1514,47 +1422,22 @@ SSAL_API int ssal_icnet_train_cascade_semi_nhwc(ssal_icnet *net, const void *x_d
                                                 int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev,
                                                 int64_t ws_bytes, void *stream)
 {
-    int rc = check_dims(net, n, h, w);
-    if (rc) return rc;
-    if ((rc = cascade_check(n, h / 32, w / 32, net->classes, max_workgroups))) return rc;
-    if ((rc = head_semi_check(x_dev && params_dev && stats_dev, labels_dev, mask_dev, labelled_dev, measure, loss_dev, grad_dev,
-                              ws_dev)))
-        return rc;
-    IcWorkspace W = carve(net, ws_dev, ws_bytes, n, h, w);
-    Bump b(ws_dev, ws_bytes);
-    b.off = W.bytes;
-    IcnetCascadeWs t = cascade_carve(b, n, h / 32, w / 32, net->classes, false);
-    const HeadSemiWs sw = head_semi_carve(b, n, h / 8, w / 8, net->classes, x_raw_dev != nullptr);
-    if (!W.ok || !b.ok)
-        return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes, got %lld",
-                    (long long)ssal_icnet_train_cascade_semi_workspace_bytes(net, n, h, w, x_raw_dev != nullptr),
-                    (long long)ws_bytes);
-    t.proj = W.act.at("conv3_1_sub2_proj");
-    t.sub24 = W.act.at("sub24_sum");
-    t.fusion.proj = W.act.at("conv3_sub1_proj");
-    t.fusion.sub12 = W.act.at("sub12_sum");
-    t.fusion.head.lq = W.act.at("conv6_cls");
-    const int K = net->classes;
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<Grp> one(1);
-    const uint8_t *tgt = nullptr;
-    if (x_raw_dev && labelled_dev) {  // the undistorted frames first, through the same slots (see the fusion entry)
-        one[0] = {W, x_raw_dev, n, s};
-        HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false, false, false));
-        const IcnetHeadSemi sa = {labelled_dev, measure, threshold, nullptr, nullptr, nullptr, 0, nullptr};
-        HIP_TRY(launch_icnet_cascade_targets(W.act.at("conv5_4_k1"), W.act.at("conv3_1"), W.act.at("conv3_sub1"), n, h / 32,
-                                             w / 32, K, params_dev, stats_dev, max_workgroups, t, sa, sw.tgt, s));
-        tgt = sw.tgt;
-    }
-    one[0] = {W, x_dev, n, s};
-    HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false, false, false));
-    return deep_semi_tail(sw, K, labelled_dev, measure, threshold, tgt, confusion_dev, pseudo_pixels_dev, s,
-                          [&](const IcnetHeadSemi *sa) {
-                              return launch_icnet_cascade_grad(W.act.at("conv5_4_k1"), W.act.at("conv3_1"),
-                                                               W.act.at("conv3_sub1"), n, h / 32, w / 32, K, params_dev,
-                                                               stats_dev, labels_dev, mask_dev, weight, label_smoothing,
-                                                               max_workgroups, t, loss_dev, grad_dev, s, sa);
-                          });
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev != nullptr};
+    return cascade_train_entry(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, stats_dev, max_workgroups, a, &semi);
+}
+
+SSAL_API int ssal_icnet_update_cascade(ssal_icnet *net, const float *params_host, void *stream)
+{
+    if (!net || !params_host) return fail(SSAL_EINVAL, "NULL argument");
+    std::vector<HostUpdate> t = {{"conv_sub4.kernel", params_host + CA_KC, CA_GC},
+                                 {"conv_sub4.gamma", params_host + CA_GC, 128},
+                                 {"conv_sub4.beta", params_host + CA_BC, 128},
+                                 {"conv3_1_sub2_proj.kernel", params_host + CA_KD, 256 * 128},
+                                 {"conv3_1_sub2_proj.gamma", params_host + CA_GD, 128},
+                                 {"conv3_1_sub2_proj.beta", params_host + CA_BD, 128}};
+    for (const HostUpdate &u : fusion_tensors(params_host + CA_FUSION, net->classes)) t.push_back(u);
+    return update_packed(net, t, {"conv_sub4", "conv3_1_sub2_proj", "conv_sub2", "conv3_sub1_proj", "conv6_cls"}, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1156,13 +1156,24 @@ class ICNetHeadTrainer(FinalLayerTrainer):
         self._set_state(self._pack(state["m"]), self._pack(state["v"]), state["t"])
 
     # ---- arguments, judged on the host before any device work -----------------------------------------------------------------
-    @staticmethod
-    def _refuse_semi(**kw):
+    _SEMI_NOUN = "ICNet's output layer"  # what the refusal of a semi-supervised keyword calls the class
+    _FEATURE_NAMES = ("sub12_sum",)      # the endpoints the features entry takes, in its order
+
+    def _no_semi(self, **kw):
+        """``_semi_call``'s refusal for the three plain ICNet trainers"""
         for name, value in kw.items():
             if value is not None and value is not False:
-                raise NotImplementedError("%s: the semi-supervised step is not implemented for ICNet's output layer" % name)
+                raise NotImplementedError("%s: the semi-supervised step is not implemented for %s" % (name, self._SEMI_NOUN))
+
+    def _features_workspace_bytes(self, query, n, h, w, k, semi, with_raw):
+        """a semi call's workspace holds the packed target plane of the undistorted frames when there are any"""
+        return query(n, h, w, k, with_raw) if semi else query(n, h, w, k)
 
     def _check_call(self, batch, up, labels, mask, max_workgroups, channels):
+        if self._semi_keywords and (labels is None or mask is None):
+            # the planes a semi call may leave out (``_semi`` has judged that) are not looked at
+            shape = tuple(np.shape(batch))
+            labels = mask = np.zeros((shape[0], up * shape[1], up * shape[2]), np.uint8) if len(shape) == 4 else None
         if int(max_workgroups) < 0:
             raise ValueError("max_workgroups must be >= 0 (got %r)" % (max_workgroups,))
         shape = tuple(np.shape(batch))
@@ -1194,19 +1205,73 @@ class ICNetHeadTrainer(FinalLayerTrainer):
             packed = over
         return packed
 
-    # ---- gradients and steps ---------------------------------------------------------------------------------------------
+    def _check_features(self, sub12_sum, labels, mask, max_workgroups):
+        return self._check_call(sub12_sum, 8, labels, mask, max_workgroups, 128)
+
+    def _check_raw(self, feats, features_raw, semi):
+        """``features_raw`` as given -> its members (None: no raw side), judged on the host: the tuple ``features()`` returns"""
+        if features_raw is None:
+            return None
+        names = self._FEATURE_NAMES
+        if not isinstance(features_raw, (tuple, list)) or len(features_raw) != len(names) or any(t is None for t in features_raw):
+            raise ValueError("features_raw must be the %d tensors features() returns, (%s), given whole or not at all"
+                             % (len(names), ", ".join(names)))
+        for name, t, f in zip(names, features_raw, feats):
+            if tuple(np.shape(t)) != tuple(np.shape(f)):
+                raise ValueError("features_raw: %s must have the shape of its counterpart %s (got %s)"
+                                 % (name, tuple(np.shape(f)), tuple(np.shape(t))))
+        return tuple(features_raw)
+
+    def _extra_c_args(self, batch):
+        """the entries' arguments between the loss' knobs and ``max_workgroups``, for a call on ``batch``'s device: none here"""
+        return ()
+
+    # ---- gradients and steps: one path for the three depths, plain and semi-supervised ----------------------------------------
+    def _feature_call(self, feats, labels, mask, params, step, max_workgroups, labelled=None, measure=None, threshold=None,
+                      features_raw=None, confusion=None, return_pseudo_pixels=False):
+        """the features entry on the tuple ``feats``: -> (loss [1], packed gradient, pseudo pixels or None, device state or
+        None); ``step``: on the weights of the device state, else on the host variables overridden by ``params``.  A plain
+        class refuses the semi-supervised keywords here (``_no_semi``); everything is judged before any device work."""
+        semi = self._semi_call(feats[0], labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels)
+        mw = self._check_features(*feats, labels, mask, max_workgroups)
+        raw = self._check_raw(feats, features_raw, semi)
+        packed = None if step else self._packed_with(params)
+        x = _lib.as_device_f32(feats[0])
+        xs = (x,) + tuple(_lib.as_device_f32(t).to(x.device) for t in feats[1:])
+        xr = (None,) * len(xs)
+        if semi is not None and raw is not None and any(r is not f for r, f in zip(raw, feats)):
+            xr = tuple(_lib.as_device_f32(t).to(x.device) for t in raw)
+        dev = self._device_state(x.device) if step else None
+        vec = dev["w"] if step else _lib.require_gpu().from_numpy(packed).to(x.device)
+        loss, grad, pp = self._grad_call(xs, xr, labels, mask, vec, semi, confusion, return_pseudo_pixels,
+                                         self._extra_c_args(x) + (mw,))
+        return loss, grad, pp, dev
+
+    def _gradient_from(self, feats, labels, mask, params, max_workgroups, return_pseudo_pixels=False, **semi_kw):
+        loss, grad, pp, _ = self._feature_call(feats, labels, mask, params, False, max_workgroups,
+                                               return_pseudo_pixels=return_pseudo_pixels, **semi_kw)
+        return (loss, self._unpack(grad), pp) if return_pseudo_pixels else (loss, self._unpack(grad))
+
+    def _step_from(self, feats, labels, mask, max_workgroups, return_pseudo_pixels=False, **semi_kw):
+        loss, grad, pp, dev = self._feature_call(feats, labels, mask, None, True, max_workgroups,
+                                                 return_pseudo_pixels=return_pseudo_pixels, **semi_kw)
+        self._apply(dev, grad)
+        return (loss[0], pp) if return_pseudo_pixels else loss[0]
+
+    def _step_from_images(self, images, labels, mask, max_workgroups, labelled=None, measure=None, threshold=None,
+                          images_raw=None, confusion=None, return_pseudo_pixels=False):
+        semi = self._semi_call(images, labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels)
+        mw = self._check_call(images, 1, labels, mask, max_workgroups, None)
+        return self._step_images(images, images_raw, labels, mask, semi, confusion, return_pseudo_pixels,
+                                 self._extra_c_args(images) + (mw,))
+
     def gradient_features(self, sub12_sum, labels, mask, params=None, max_workgroups=0, labelled=None, confusion=None,
                           return_pseudo_pixels=False):
         """(loss float64 [1], {"conv6_cls.kernel": [1, 1, 128, K], "conv6_cls.bias": [K]}) on the device for ``sub12_sum``
         [N, h, w, 128] and labels / mask [N, 8h, 8w].  ``params`` overrides either tensor of the head; ``max_workgroups``: 0 =
         min(tiles, 1024), a tuning knob.  No update."""
-        self._refuse_semi(labelled=labelled, confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
-        mw = self._check_call(sub12_sum, 8, labels, mask, max_workgroups, 128)
-        packed = self._packed_with(params)
-        x = _lib.as_device_f32(sub12_sum)
-        head = _lib.require_gpu().from_numpy(packed).to(x.device)
-        loss, grad, _ = self._grad_call((x,), (None,), labels, mask, head, None, None, False, (mw,))
-        return loss, self._unpack(grad)
+        return self._gradient_from((sub12_sum,), labels, mask, params, max_workgroups, labelled=labelled, confusion=confusion,
+                                   return_pseudo_pixels=return_pseudo_pixels)
 
     def features(self, images):
         """``sub12_sum`` [N, H/8, W/8, 128] for ``images`` (a copy): what ``step_features`` and ``gradient_features`` take.
@@ -1218,20 +1283,14 @@ class ICNetHeadTrainer(FinalLayerTrainer):
                       return_pseudo_pixels=False):
         """one Adam step from cached ``sub12_sum`` features; returns the loss (float64 device scalar) BEFORE the step, as
         ``sess.run([loss, train_op])`` does"""
-        self._refuse_semi(labelled=labelled, confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
-        mw = self._check_call(sub12_sum, 8, labels, mask, max_workgroups, 128)
-        x = _lib.as_device_f32(sub12_sum)
-        dev = self._device_state(x.device)
-        loss, grad, _ = self._grad_call((x,), (None,), labels, mask, dev["w"], None, None, False, (mw,))
-        self._apply(dev, grad)
-        return loss[0]
+        return self._step_from((sub12_sum,), labels, mask, max_workgroups, labelled=labelled, confusion=confusion,
+                               return_pseudo_pixels=return_pseudo_pixels)
 
     def step(self, images, labels, mask, max_workgroups=0, labelled=None, confusion=None, return_pseudo_pixels=False):
         """one Adam step from images [N, H, W, C] (fp32 or decoded uint8) and labels / mask [N, H, W]: the frozen trunk up
         to ``sub12_sum``, the head and its gradient kernel, Adam.  Returns the loss (float64 device scalar) before the step."""
-        self._refuse_semi(labelled=labelled, confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
-        mw = self._check_call(images, 1, labels, mask, max_workgroups, None)
-        return self._step_images(images, None, labels, mask, None, None, False, (mw,))
+        return self._step_from_images(images, labels, mask, max_workgroups, labelled=labelled, confusion=confusion,
+                                      return_pseudo_pixels=return_pseudo_pixels)
 
 
 # ---- the semi-supervised step of ICNet's output-layer trainer (DESIGN.md section 25) --------------------------------------------
@@ -1247,25 +1306,14 @@ class SemiSupervisedICNetHeadTrainer(_SemiKeywords, ICNetHeadTrainer):
     _C_FEATURES = ("ssal_icnet_head_grad", "ssal_icnet_head_grad_semi")
     _C_IMAGES = ("ssal_icnet_train_head", "ssal_icnet_train_head_semi")
 
-    def _features_workspace_bytes(self, query, n, h, w, k, semi, with_raw):
-        """a semi call's workspace holds the packed target plane of the undistorted frames when there are any"""
-        return query(n, h, w, k, with_raw) if semi else query(n, h, w, k)
-
-    def _check_call(self, batch, up, labels, mask, max_workgroups, channels):
-        """``ICNetHeadTrainer``'s checks; the planes a semi call may leave out (``_semi`` has judged that) are not looked at"""
-        if labels is None or mask is None:
-            shape = tuple(np.shape(batch))
-            stand_in = np.zeros((shape[0], up * shape[1], up * shape[2]), np.uint8) if len(shape) == 4 else None
-            return super()._check_call(batch, up, stand_in, stand_in, max_workgroups, channels)
-        return super()._check_call(batch, up, labels, mask, max_workgroups, channels)
-
-    def _raw_features(self, x, semi, features_raw, features):
-        if semi is None or features_raw is None or features_raw is features:
+    def _check_raw(self, feats, features_raw, semi):
+        """the head's raw side is one tensor, looked at only in a call that is semi-supervised"""
+        if semi is None or features_raw is None:
             return None
-        xr = _lib.as_device_f32(features_raw).to(x.device)
-        if tuple(xr.shape) != tuple(x.shape):
-            raise ValueError("features_raw must have the shape of sub12_sum %s (got %s)" % (tuple(x.shape), tuple(xr.shape)))
-        return xr
+        if tuple(np.shape(features_raw)) != tuple(np.shape(feats[0])):
+            raise ValueError("features_raw must have the shape of sub12_sum %s (got %s)"
+                             % (tuple(np.shape(feats[0])), tuple(np.shape(features_raw))))
+        return (features_raw,)
 
     def gradient_features(self, sub12_sum, labels, mask, params=None, max_workgroups=0, labelled=None, measure=None,
                           threshold=None, features_raw=None, confusion=None, return_pseudo_pixels=False):
@@ -1273,36 +1321,26 @@ class SemiSupervisedICNetHeadTrainer(_SemiKeywords, ICNetHeadTrainer):
         ``labelled`` [N], ``measure`` / ``threshold`` (defaults: the trainer's), ``features_raw`` (``sub12_sum`` of the
         undistorted frames), ``confusion`` (int64 [K, K] device tensor, added to), ``return_pseudo_pixels`` (appends the int64
         [N] counts to the result)."""
-        semi = self._semi_call(sub12_sum, labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels)
-        mw = self._check_call(sub12_sum, 8, labels, mask, max_workgroups, 128)
-        packed = self._packed_with(params)
-        x = _lib.as_device_f32(sub12_sum)
-        xr = self._raw_features(x, semi, features_raw, sub12_sum)
-        head = _lib.require_gpu().from_numpy(packed).to(x.device)
-        loss, grad, pp = self._grad_call((x,), (xr,), labels, mask, head, semi, confusion, return_pseudo_pixels, (mw,))
-        return (loss, self._unpack(grad), pp) if return_pseudo_pixels else (loss, self._unpack(grad))
+        return self._gradient_from((sub12_sum,), labels, mask, params, max_workgroups, labelled=labelled, measure=measure,
+                                   threshold=threshold, features_raw=features_raw, confusion=confusion,
+                                   return_pseudo_pixels=return_pseudo_pixels)
 
     def step_features(self, sub12_sum, labels, mask, max_workgroups=0, labelled=None, measure=None, threshold=None,
                       features_raw=None, confusion=None, return_pseudo_pixels=False):
         """one Adam step from cached ``sub12_sum`` features; the keywords are those of ``gradient_features``; with
         ``return_pseudo_pixels`` the result is ``(loss, pseudo_pixels)``"""
-        semi = self._semi_call(sub12_sum, labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels)
-        mw = self._check_call(sub12_sum, 8, labels, mask, max_workgroups, 128)
-        x = _lib.as_device_f32(sub12_sum)
-        xr = self._raw_features(x, semi, features_raw, sub12_sum)
-        dev = self._device_state(x.device)
-        loss, grad, pp = self._grad_call((x,), (xr,), labels, mask, dev["w"], semi, confusion, return_pseudo_pixels, (mw,))
-        self._apply(dev, grad)
-        return (loss[0], pp) if return_pseudo_pixels else loss[0]
+        return self._step_from((sub12_sum,), labels, mask, max_workgroups, labelled=labelled, measure=measure,
+                               threshold=threshold, features_raw=features_raw, confusion=confusion,
+                               return_pseudo_pixels=return_pseudo_pixels)
 
     def step(self, images, labels, mask, max_workgroups=0, labelled=None, measure=None, threshold=None, images_raw=None,
              confusion=None, return_pseudo_pixels=False):
         """one Adam step from images; ``images_raw``: the undistorted frames (same shape and dtype as ``images``) -- the trunk
         runs on them first and the pseudo annotation comes from their logits (active_learning.py:231).  The other keywords
         as in ``gradient_features``; with ``return_pseudo_pixels`` the result is ``(loss, pseudo_pixels)``."""
-        semi = self._semi_call(images, labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels)
-        mw = self._check_call(images, 1, labels, mask, max_workgroups, None)
-        return self._step_images(images, images_raw, labels, mask, semi, confusion, return_pseudo_pixels, (mw,))
+        return self._step_from_images(images, labels, mask, max_workgroups, labelled=labelled, measure=measure,
+                                      threshold=threshold, images_raw=images_raw, confusion=confusion,
+                                      return_pseudo_pixels=return_pseudo_pixels)
 
 
 # ---- ICNet's last fusion stage: conv_sub2 + conv3_sub1_proj + conv6_cls over a frozen trunk (DESIGN.md section 28) -------------
@@ -1434,11 +1472,8 @@ class ICNetFusionTrainer(ICNetHeadTrainer):
         self._set_state(self._pack(state["m"]), self._pack(state["v"]), state["t"])
 
     # ---- arguments, judged on the host before any device work -----------------------------------------------------------------
-    @staticmethod
-    def _refuse_semi(**kw):
-        for name, value in kw.items():
-            if value is not None and value is not False:
-                raise NotImplementedError("%s: the semi-supervised step is not implemented for ICNet's fusion trainer" % name)
+    _SEMI_NOUN = "ICNet's fusion trainer"
+    _FEATURE_NAMES = ("sub24_sum", "conv3_sub1")
 
     def _check_features(self, sub24_sum, conv3_sub1, labels, mask, max_workgroups):
         mw = self._check_call(sub24_sum, 16, labels, mask, max_workgroups, 128)
@@ -1461,21 +1496,20 @@ class ICNetFusionTrainer(ICNetHeadTrainer):
             packed = self._pack({n: params.get(n, v) for n, v in self._unpack(packed).items()})
         return packed
 
+    def _extra_c_args(self, batch):
+        """the frozen moving statistics, on ``batch``'s device (a host batch: the current device)"""
+        torch = _lib.require_gpu()
+        device = batch.device if getattr(batch, "is_cuda", False) else torch.device("cuda", torch.cuda.current_device())
+        return (_lib.dev_ptr(self._stats(device)),)
+
     # ---- gradients and steps ---------------------------------------------------------------------------------------------
     def gradient_features(self, sub24_sum, conv3_sub1, labels, mask, params=None, max_workgroups=0, labelled=None,
                           confusion=None, return_pseudo_pixels=False):
         """(loss float64 [1], {name: gradient} for ``variable_names``) on the device for ``sub24_sum`` [N, h, w, 128],
         ``conv3_sub1`` [N, 2h, 2w, 64] and labels / mask [N, 16h, 16w].  ``params`` overrides any of the eight tensors;
         ``max_workgroups``: 0 = the default grids, a tuning knob.  No update."""
-        self._refuse_semi(labelled=labelled, confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
-        mw = self._check_features(sub24_sum, conv3_sub1, labels, mask, max_workgroups)
-        packed = self._packed_with(params)
-        x = _lib.as_device_f32(sub24_sum)
-        c3 = _lib.as_device_f32(conv3_sub1).to(x.device)
-        vec = _lib.require_gpu().from_numpy(packed).to(x.device)
-        loss, grad, _ = self._grad_call((x, c3), (None,), labels, mask, vec, None, None, False,
-                                        (_lib.dev_ptr(self._stats(x.device)), mw))
-        return loss, self._unpack(grad)
+        return self._gradient_from((sub24_sum, conv3_sub1), labels, mask, params, max_workgroups, labelled=labelled,
+                                   confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
 
     def features(self, images):
         """``(sub24_sum [N, H/16, W/16, 128], conv3_sub1 [N, H/8, W/8, 64])`` for ``images`` (copies): what ``step_features``
@@ -1486,25 +1520,15 @@ class ICNetFusionTrainer(ICNetHeadTrainer):
     def step_features(self, sub24_sum, conv3_sub1, labels, mask, max_workgroups=0, labelled=None, confusion=None,
                       return_pseudo_pixels=False):
         """one Adam step from cached features; returns the loss (float64 device scalar) BEFORE the step"""
-        self._refuse_semi(labelled=labelled, confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
-        mw = self._check_features(sub24_sum, conv3_sub1, labels, mask, max_workgroups)
-        x = _lib.as_device_f32(sub24_sum)
-        c3 = _lib.as_device_f32(conv3_sub1).to(x.device)
-        dev = self._device_state(x.device)
-        loss, grad, _ = self._grad_call((x, c3), (None,), labels, mask, dev["w"], None, None, False,
-                                        (_lib.dev_ptr(self._stats(x.device)), mw))
-        self._apply(dev, grad)
-        return loss[0]
+        return self._step_from((sub24_sum, conv3_sub1), labels, mask, max_workgroups, labelled=labelled, confusion=confusion,
+                               return_pseudo_pixels=return_pseudo_pixels)
 
     def step(self, images, labels, mask, max_workgroups=0, labelled=None, confusion=None, return_pseudo_pixels=False):
         """one Adam step from images [N, H, W, C] (fp32 or decoded uint8) and labels / mask [N, H, W]: the frozen trunk up
         to ``sub24_sum`` and ``conv3_sub1``, the block and the head on the weights being trained, their gradient kernels,
         Adam.  Returns the loss (float64 device scalar) before the step."""
-        self._refuse_semi(labelled=labelled, confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
-        mw = self._check_call(images, 1, labels, mask, max_workgroups, None)
-        torch = _lib.require_gpu()
-        device = images.device if getattr(images, "is_cuda", False) else torch.device("cuda", torch.cuda.current_device())
-        return self._step_images(images, None, labels, mask, None, None, False, (_lib.dev_ptr(self._stats(device)), mw))
+        return self._step_from_images(images, labels, mask, max_workgroups, labelled=labelled, confusion=confusion,
+                                      return_pseudo_pixels=return_pseudo_pixels)
 
 
 # ---- ICNet's whole cascade head: both fusion blocks + conv6_cls over the three frozen branches (DESIGN.md section 29) -----------
@@ -1531,11 +1555,8 @@ class ICNetCascadeTrainer(ICNetFusionTrainer):
     _VARS, _STATS, _C_UPDATE = _CASCADE_VARS, _CASCADE_STATS, "ssal_icnet_update_cascade"
     variable_names = ["%s.%s" % (layer, attr) for layer, attr, _ in _CASCADE_VARS]
 
-    @staticmethod
-    def _refuse_semi(**kw):
-        for name, value in kw.items():
-            if value is not None and value is not False:
-                raise NotImplementedError("%s: the semi-supervised step is not implemented for ICNet's cascade trainer" % name)
+    _SEMI_NOUN = "ICNet's cascade trainer"
+    _FEATURE_NAMES = ("conv5_4_k1", "conv3_1", "conv3_sub1")
 
     def _check_features(self, conv5_4_k1, conv3_1, conv3_sub1, labels, mask, max_workgroups):
         mw = self._check_call(conv5_4_k1, 32, labels, mask, max_workgroups, 256)
@@ -1548,26 +1569,13 @@ class ICNetCascadeTrainer(ICNetFusionTrainer):
                 raise ValueError("%s must be a floating-point tensor (got %s)" % (name, dt or type(t).__name__))
         return mw
 
-    def _feature_call(self, conv5_4_k1, conv3_1, conv3_sub1, labels, mask, packed, mw):
-        """-> (loss, packed gradient, device state); ``packed`` None: on the weights of the device state"""
-        x = _lib.as_device_f32(conv5_4_k1)
-        rest = tuple(_lib.as_device_f32(t).to(x.device) for t in (conv3_1, conv3_sub1))
-        dev = self._device_state(x.device) if packed is None else None
-        vec = dev["w"] if packed is None else _lib.require_gpu().from_numpy(packed).to(x.device)
-        loss, grad, _ = self._grad_call((x,) + rest, (None,), labels, mask, vec, None, None, False,
-                                        (_lib.dev_ptr(self._stats(x.device)), mw))
-        return loss, grad, dev
-
     def gradient_features(self, conv5_4_k1, conv3_1, conv3_sub1, labels, mask, params=None, max_workgroups=0, labelled=None,
                           confusion=None, return_pseudo_pixels=False):
         """(loss float64 [1], {name: gradient} for ``variable_names``) on the device for ``conv5_4_k1`` [N, h, w, 256],
         ``conv3_1`` [N, 2h, 2w, 256], ``conv3_sub1`` [N, 4h, 4w, 64] and labels / mask [N, 32h, 32w].  ``params`` overrides
         any of the fourteen tensors; ``max_workgroups``: 0 = the default grids, a tuning knob.  No update."""
-        self._refuse_semi(labelled=labelled, confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
-        mw = self._check_features(conv5_4_k1, conv3_1, conv3_sub1, labels, mask, max_workgroups)
-        packed = self._packed_with(params)
-        loss, grad, _ = self._feature_call(conv5_4_k1, conv3_1, conv3_sub1, labels, mask, packed, mw)
-        return loss, self._unpack(grad)
+        return self._gradient_from((conv5_4_k1, conv3_1, conv3_sub1), labels, mask, params, max_workgroups, labelled=labelled,
+                                   confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
 
     def features(self, images):
         """``(conv5_4_k1 [N, H/32, W/32, 256], conv3_1 [N, H/16, W/16, 256], conv3_sub1 [N, H/8, W/8, 64])`` for ``images``
@@ -1578,11 +1586,8 @@ class ICNetCascadeTrainer(ICNetFusionTrainer):
     def step_features(self, conv5_4_k1, conv3_1, conv3_sub1, labels, mask, max_workgroups=0, labelled=None, confusion=None,
                       return_pseudo_pixels=False):
         """one Adam step from cached features; returns the loss (float64 device scalar) BEFORE the step"""
-        self._refuse_semi(labelled=labelled, confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
-        mw = self._check_features(conv5_4_k1, conv3_1, conv3_sub1, labels, mask, max_workgroups)
-        loss, grad, dev = self._feature_call(conv5_4_k1, conv3_1, conv3_sub1, labels, mask, None, mw)
-        self._apply(dev, grad)
-        return loss[0]
+        return self._step_from((conv5_4_k1, conv3_1, conv3_sub1), labels, mask, max_workgroups, labelled=labelled,
+                               confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
 
 
 # ---- the semi-supervised step of ICNet's fusion and cascade trainers (DESIGN.md section 30) --------------------------------------
@@ -1598,51 +1603,6 @@ class SemiSupervisedICNetFusionTrainer(_SemiKeywords, ICNetFusionTrainer):
 
     _C_FEATURES = ("ssal_icnet_fusion_grad", "ssal_icnet_fusion_grad_semi")
     _C_IMAGES = ("ssal_icnet_train_fusion", "ssal_icnet_train_fusion_semi")
-    _FEATURE_NAMES = ("sub24_sum", "conv3_sub1")
-
-    def _features_workspace_bytes(self, query, n, h, w, k, semi, with_raw):
-        """a semi call's workspace holds the packed target plane of the undistorted frames when there are any"""
-        return query(n, h, w, k, with_raw) if semi else query(n, h, w, k)
-
-    def _check_call(self, batch, up, labels, mask, max_workgroups, channels):
-        """``ICNetHeadTrainer``'s checks; the planes a semi call may leave out (``_semi`` has judged that) are not looked at"""
-        if labels is None or mask is None:
-            shape = tuple(np.shape(batch))
-            labels = mask = np.zeros((shape[0], up * shape[1], up * shape[2]), np.uint8) if len(shape) == 4 else None
-        return ICNetHeadTrainer._check_call(self, batch, up, labels, mask, max_workgroups, channels)
-
-    def _check_raw(self, feats, features_raw):
-        """``features_raw`` as given -> its members (None: no raw side), judged on the host"""
-        if features_raw is None:
-            return None
-        names = self._FEATURE_NAMES
-        if not isinstance(features_raw, (tuple, list)) or len(features_raw) != len(names) or any(t is None for t in features_raw):
-            raise ValueError("features_raw must be the %d tensors features() returns, (%s), given whole or not at all"
-                             % (len(names), ", ".join(names)))
-        for name, t, f in zip(names, features_raw, feats):
-            if tuple(np.shape(t)) != tuple(np.shape(f)):
-                raise ValueError("features_raw: %s must have the shape of its counterpart %s (got %s)"
-                                 % (name, tuple(np.shape(f)), tuple(np.shape(t))))
-        return tuple(features_raw)
-
-    def _semi_feature_call(self, feats, labels, mask, params, step, max_workgroups, labelled, measure, threshold, features_raw,
-                           confusion, return_pseudo_pixels):
-        """the features entry on ``feats``: -> (loss [1], packed gradient, pseudo pixels or None, device state or None);
-        ``step``: on the weights of the device state, else on the host variables overridden by ``params``"""
-        semi = self._semi_call(feats[0], labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels)
-        mw = self._check_features(*feats, labels, mask, max_workgroups)
-        raw = self._check_raw(feats, features_raw)
-        packed = None if step else self._packed_with(params)
-        x = _lib.as_device_f32(feats[0])
-        xs = (x,) + tuple(_lib.as_device_f32(t).to(x.device) for t in feats[1:])
-        xr = (None,) * len(xs)
-        if semi is not None and raw is not None and any(r is not f for r, f in zip(raw, feats)):
-            xr = tuple(_lib.as_device_f32(t).to(x.device) for t in raw)
-        dev = self._device_state(x.device) if step else None
-        vec = dev["w"] if step else _lib.require_gpu().from_numpy(packed).to(x.device)
-        loss, grad, pp = self._grad_call(xs, xr, labels, mask, vec, semi, confusion, return_pseudo_pixels,
-                                         (_lib.dev_ptr(self._stats(x.device)), mw))
-        return loss, grad, pp, dev
 
     def gradient_features(self, sub24_sum, conv3_sub1, labels, mask, params=None, max_workgroups=0, labelled=None,
                           measure=None, threshold=None, features_raw=None, confusion=None, return_pseudo_pixels=False):
@@ -1650,19 +1610,17 @@ class SemiSupervisedICNetFusionTrainer(_SemiKeywords, ICNetFusionTrainer):
         ``FinalLayerTrainer.gradient_features``: ``labelled`` [N], ``measure`` / ``threshold`` (defaults: the trainer's),
         ``features_raw`` (``features(images_raw)``: both tensors), ``confusion`` (int64 [K, K] device tensor, added to),
         ``return_pseudo_pixels`` (appends the int64 [N] counts to the result)."""
-        loss, grad, pp, _ = self._semi_feature_call((sub24_sum, conv3_sub1), labels, mask, params, False, max_workgroups,
-                                                    labelled, measure, threshold, features_raw, confusion, return_pseudo_pixels)
-        return (loss, self._unpack(grad), pp) if return_pseudo_pixels else (loss, self._unpack(grad))
+        return self._gradient_from((sub24_sum, conv3_sub1), labels, mask, params, max_workgroups, labelled=labelled,
+                                   measure=measure, threshold=threshold, features_raw=features_raw, confusion=confusion,
+                                   return_pseudo_pixels=return_pseudo_pixels)
 
     def step_features(self, sub24_sum, conv3_sub1, labels, mask, max_workgroups=0, labelled=None, measure=None, threshold=None,
                       features_raw=None, confusion=None, return_pseudo_pixels=False):
         """one Adam step from cached features; the keywords are those of ``gradient_features``; with
         ``return_pseudo_pixels`` the result is ``(loss, pseudo_pixels)``"""
-        loss, grad, pp, dev = self._semi_feature_call((sub24_sum, conv3_sub1), labels, mask, None, True, max_workgroups,
-                                                      labelled, measure, threshold, features_raw, confusion,
-                                                      return_pseudo_pixels)
-        self._apply(dev, grad)
-        return (loss[0], pp) if return_pseudo_pixels else loss[0]
+        return self._step_from((sub24_sum, conv3_sub1), labels, mask, max_workgroups, labelled=labelled, measure=measure,
+                               threshold=threshold, features_raw=features_raw, confusion=confusion,
+                               return_pseudo_pixels=return_pseudo_pixels)
 
     def step(self, images, labels, mask, max_workgroups=0, labelled=None, measure=None, threshold=None, images_raw=None,
              confusion=None, return_pseudo_pixels=False):
@@ -1670,12 +1628,9 @@ class SemiSupervisedICNetFusionTrainer(_SemiKeywords, ICNetFusionTrainer):
         the trained blocks and the head run on them first and the pseudo annotation comes from their logits
         (active_learning.py:231).  The other keywords as in ``gradient_features``; with ``return_pseudo_pixels`` the result
         is ``(loss, pseudo_pixels)``."""
-        semi = self._semi_call(images, labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels)
-        mw = self._check_call(images, 1, labels, mask, max_workgroups, None)
-        torch = _lib.require_gpu()
-        device = images.device if getattr(images, "is_cuda", False) else torch.device("cuda", torch.cuda.current_device())
-        return self._step_images(images, images_raw, labels, mask, semi, confusion, return_pseudo_pixels,
-                                 (_lib.dev_ptr(self._stats(device)), mw))
+        return self._step_from_images(images, labels, mask, max_workgroups, labelled=labelled, measure=measure,
+                                      threshold=threshold, images_raw=images_raw, confusion=confusion,
+                                      return_pseudo_pixels=return_pseudo_pixels)
 
 
 class SemiSupervisedICNetCascadeTrainer(_SemiKeywords, ICNetCascadeTrainer):
@@ -1686,30 +1641,27 @@ class SemiSupervisedICNetCascadeTrainer(_SemiKeywords, ICNetCascadeTrainer):
 
     _C_FEATURES = ("ssal_icnet_cascade_grad", "ssal_icnet_cascade_grad_semi")
     _C_IMAGES = ("ssal_icnet_train_cascade", "ssal_icnet_train_cascade_semi")
-    _FEATURE_NAMES = ("conv5_4_k1", "conv3_1", "conv3_sub1")
-    # the fusion form's helpers name no class of their own: they serve this one as they stand
-    _features_workspace_bytes = SemiSupervisedICNetFusionTrainer._features_workspace_bytes
-    _check_call = SemiSupervisedICNetFusionTrainer._check_call
-    _check_raw = SemiSupervisedICNetFusionTrainer._check_raw
-    _semi_feature_call = SemiSupervisedICNetFusionTrainer._semi_feature_call
-    step = SemiSupervisedICNetFusionTrainer.step
 
     def gradient_features(self, conv5_4_k1, conv3_1, conv3_sub1, labels, mask, params=None, max_workgroups=0, labelled=None,
                           measure=None, threshold=None, features_raw=None, confusion=None, return_pseudo_pixels=False):
         """``ICNetCascadeTrainer.gradient_features`` with the keywords of ``SemiSupervisedICNetFusionTrainer``'s"""
-        loss, grad, pp, _ = self._semi_feature_call((conv5_4_k1, conv3_1, conv3_sub1), labels, mask, params, False,
-                                                    max_workgroups, labelled, measure, threshold, features_raw, confusion,
-                                                    return_pseudo_pixels)
-        return (loss, self._unpack(grad), pp) if return_pseudo_pixels else (loss, self._unpack(grad))
+        return self._gradient_from((conv5_4_k1, conv3_1, conv3_sub1), labels, mask, params, max_workgroups, labelled=labelled,
+                                   measure=measure, threshold=threshold, features_raw=features_raw, confusion=confusion,
+                                   return_pseudo_pixels=return_pseudo_pixels)
 
     def step_features(self, conv5_4_k1, conv3_1, conv3_sub1, labels, mask, max_workgroups=0, labelled=None, measure=None,
                       threshold=None, features_raw=None, confusion=None, return_pseudo_pixels=False):
         """one Adam step from cached features; the keywords are those of ``gradient_features``"""
-        loss, grad, pp, dev = self._semi_feature_call((conv5_4_k1, conv3_1, conv3_sub1), labels, mask, None, True,
-                                                      max_workgroups, labelled, measure, threshold, features_raw, confusion,
-                                                      return_pseudo_pixels)
-        self._apply(dev, grad)
-        return (loss[0], pp) if return_pseudo_pixels else loss[0]
+        return self._step_from((conv5_4_k1, conv3_1, conv3_sub1), labels, mask, max_workgroups, labelled=labelled,
+                               measure=measure, threshold=threshold, features_raw=features_raw, confusion=confusion,
+                               return_pseudo_pixels=return_pseudo_pixels)
+
+    def step(self, images, labels, mask, max_workgroups=0, labelled=None, measure=None, threshold=None, images_raw=None,
+             confusion=None, return_pseudo_pixels=False):
+        """``SemiSupervisedICNetFusionTrainer.step`` for the cascade head"""
+        return self._step_from_images(images, labels, mask, max_workgroups, labelled=labelled, measure=measure,
+                                      threshold=threshold, images_raw=images_raw, confusion=confusion,
+                                      return_pseudo_pixels=return_pseudo_pixels)
 
 
 __all__ = ["FinalLayerTrainer", "LastBlockTrainer", "LastStageTrainer", "DecoderTailTrainer", "SemiSupervisedBlockTrainer",
