@@ -253,6 +253,38 @@ int ssal_icnet_train_cascade_semi_nhwc(ssal_icnet *net, const void *x_dev, const
                                        float *grad_dev, int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev,
                                        int64_t ws_bytes, void *stream);
 
+/* ---- Training of the high-resolution branch down to the image: conv1_sub1, conv2_sub1, conv3_sub1
+ * (3 x 3, stride 2, TF SAME, batch-norm, ReLU; c_in -> 32 -> 32 -> 64), then the cascade head as above, over the two frozen
+ * backbone branches ----
+ * The 23 trained variables travel PACKED, in this order: conv1_sub1.kernel [3,3,c_in,32] | .gamma [32] | .beta [32] |
+ * conv2_sub1.kernel [3,3,32,32] | .gamma [32] | .beta [32] | conv3_sub1.kernel [3,3,32,64] | .gamma [64] | .beta [64] | the
+ * fourteen of the cascade entries in their order (288 c_in + 27904 floats, then theirs); params_dev and grad_dev have that
+ * layout.  c_in is 3 or 4.  stats_dev is UNPADDED, every row at its layer's own width: conv1_sub1 mean [32] | variance [32] |
+ * conv2_sub1 mean [32] | variance [32] | conv3_sub1 mean [64] | variance [64] | the eight rows of 128 of the cascade entries
+ * (256 + 1024 floats); batch-norm as there.  One call computes, for conv5_4_k1 [n,h,w,256] (1/32 resolution), conv3_1
+ * [n,2h,2w,256], the frames x_dev [n,32h,32w,c_in] (fp32, or uint8 when x_is_u8 != 0: float(u8) * float32(1/255)), labels uint8
+ * and mask fp32 [n,32h,32w]: the branch, sub24_sum, sub12_sum and lq by the forward path's own launches on params_dev, the loss
+ * -> loss_dev [1] float64, and the gradient of all 23 variables -> grad_dev (without the regulariser).  The frames and the two
+ * backbone features get no gradient.  The loss and the last fourteen gradients are the bits ssal_icnet_cascade_grad_nhwc gives
+ * on the same conv3_sub1.  max_workgroups, determinism and statuses as ssal_icnet_fusion_grad_nhwc's; the _workspace_bytes
+ * query returns -1 beyond the cascade entries' limit or at n * 32h * 32w >= 2^27 frame pixels (the forward path's limit). */
+int64_t ssal_icnet_highres_grad_workspace_bytes(int n, int h, int w, int classes);
+int ssal_icnet_highres_grad_nhwc(const float *conv5_4_k1_dev, const float *conv3_1_dev, const void *x_dev, int n, int h, int w,
+                                 int classes, const float *params_dev, const uint8_t *labels_dev, const float *mask_dev,
+                                 float weight, float label_smoothing, const float *stats_dev, int x_is_u8, int c_in,
+                                 int max_workgroups, double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes,
+                                 void *stream);
+/* the same from the frames alone ([n,h,w,c_in] of the handle): the two frozen backbone branches until conv5_4_k1 and conv3_1 are
+ * written, then the branch and the tail above; labels / mask [n,h,w].  After the call the endpoints conv1_sub1, conv2_sub1,
+ * conv3_sub1 and those from conv3_1_sub2_proj on are those of params_dev. */
+int64_t ssal_icnet_train_highres_workspace_bytes(const ssal_icnet *net, int n, int h, int w);
+int ssal_icnet_train_highres_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                                  const uint8_t *labels_dev, const float *mask_dev, const float *params_dev, float weight,
+                                  float label_smoothing, const float *stats_dev, int max_workgroups, double *loss_dev,
+                                  float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream);
+/* ssal_icnet_update_fusion for the 23 variables: only the eight trained layers are re-laid-out, folded and uploaded */
+int ssal_icnet_update_highres(ssal_icnet *net, const float *params_host, void *stream);
+
 /* Stand-alone fused convolution (the operator every ICNet layer is built from; also the per-block parity hook):
  * y = [relu]( BN(conv2d(x, kernel HWIO, strides s, dilations d, "SAME")) [+ res] ), BN given as mean / variance /
  * gamma / beta (all NULL: no batch-norm; bias_dev optional).  upsample2x != 0 runs the conv on

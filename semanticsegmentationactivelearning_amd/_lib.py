@@ -208,6 +208,13 @@ PROTOTYPES = {
     "ssal_icnet_train_cascade_semi_workspace_bytes": (_i64, [_vp, _i, _i, _i, _i]),
     "ssal_icnet_train_cascade_semi_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _f, _f, _vp, _i, _vp,
                                                 _vp, _vp, _vp, _vp, _i64, _vp]),
+    # ---- training of ICNet's high-resolution branch down to the image (include/ssal_icnet.h) ----
+    "ssal_icnet_highres_grad_workspace_bytes": (_i64, [_i, _i, _i, _i]),
+    "ssal_icnet_highres_grad_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _i, _i, _vp, _vp, _vp,
+                                          _i64, _vp]),
+    "ssal_icnet_train_highres_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
+    "ssal_icnet_train_highres_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_icnet_update_highres": (_i, [_vp, _vp, _vp]),
     # ---- PNG decode (include/ssal_enet.h) ----
     "ssal_png_plan": (_i64, [_i64, _vp]),
     "ssal_png_decode_nhwc": (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),

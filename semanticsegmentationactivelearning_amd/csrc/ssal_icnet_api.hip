@@ -11,6 +11,7 @@
 #include "ssal_train_icnet.h"
 #include "ssal_train_icnet_cascade.h"
 #include "ssal_train_icnet_fusion.h"
+#include "ssal_train_icnet_highres.h"
 
 #include <math.h>
 
@@ -249,8 +250,11 @@ struct Grp {
 // fusion = false (with head = false): it ends at sub24_sum and conv3_sub1 (the fusion trainer runs the last fusion block too)
 // cascade = false (with fusion = false): it ends once conv5_4_k1, conv3_1 and conv3_sub1 are written (the cascade trainer runs
 // both fusion blocks; every fused launch above writes those three: none of them is swallowed)
+// highres = false (with cascade = false): the high-resolution branch is left out too -- only the two backbone branches run
+// (the high-resolution trainer runs conv1_sub1 .. conv3_sub1 on the weights it trains)
 hipError_t run_trunk(const ssal_icnet *net, std::vector<Grp> &grp, bool x_is_u8, int h, int w, bool fused,
-                     std::set<std::string> *written = nullptr, bool head = true, bool fusion = true, bool cascade = true)
+                     std::set<std::string> *written = nullptr, bool head = true, bool fusion = true, bool cascade = true,
+                     bool highres = true)
 {
     const bool dry = written != nullptr;
 #define OUT(name) do { if (dry) written->insert(name); } while (0)
@@ -339,6 +343,7 @@ hipError_t run_trunk(const ssal_icnet *net, std::vector<Grp> &grp, bool x_is_u8,
     EACH(launch_ppm(q.A(cur), q.n, ch, cw, 1024, q.W.pooled, q.A("conv5_3_sum"), q.s));
     EACH(run_conv(net, "conv5_4_k1", q.A("conv5_3_sum"), q.n, ch, cw, nullptr, true, false, q.A("conv5_4_k1"), q.s));
     // ---- high-resolution branch (section 3) ----
+    if (!highres) return hipSuccess;
     if ((front & 1) && front2_supported(h, w, net->c_in, 1, 2)) {
         const ConvDev &c = net->convs.at("conv1_sub1"), &c2 = net->convs.at("conv2_sub1");
         OUT("conv2_sub1");
@@ -1147,6 +1152,106 @@ int cascade_train_entry(ssal_icnet *net, const void *x_dev, const void *x_raw_de
                        max_workgroups, a, semi, t, sw);
 }
 
+// ---- the high-resolution branch down to the image (kernels: ssal_train_icnet_highres.hip) ----
+// the buffers of one gradient call behind `b`; own_acts: a_1, a_2, conv3_sub1 and the cascade head's activations live here (the
+// images entry keeps them in the network's conv1_sub1 / conv2_sub1 / conv3_sub1 / ... endpoints instead)
+IcnetHighresWs highres_carve(Bump &b, int64_t n, int h32, int w32, int classes, bool own_acts)
+{
+    IcnetHighresWs t;
+    const int64_t px8 = n * (4 * (int64_t)h32) * (4 * (int64_t)w32);
+    t.wt2 = b.take<float>(9 * 32 * 32);
+    t.wt3 = b.take<float>(9 * 32 * 64);
+    t.rows = b.take<float>(256);
+    t.a1 = own_acts ? b.take<float>(16 * px8 * 32) : nullptr;
+    t.a2 = own_acts ? b.take<float>(4 * px8 * 32) : nullptr;
+    t.f3 = own_acts ? b.take<float>(px8 * 64) : nullptr;
+    t.gz3 = b.take<float>(px8 * 64);
+    t.gz2 = b.take<float>(4 * px8 * 32);
+    t.gz1 = b.take<float>(16 * px8 * 32);
+    t.part = b.take<float>((int64_t)HR_MAX_WG * HR_PART);  // (sized for the default grid: max_workgroups only lowers it)
+    t.fold = b.take<float>(HR_PART);
+    t.cascade = cascade_carve(b, n, h32, w32, classes, own_acts);
+    return t;
+}
+
+int64_t highres_bytes(int64_t front, int n, int h32, int w32, int classes, bool own_acts)
+{
+    Bump b(nullptr, 0);
+    b.off = front;
+    (void)highres_carve(b, n, h32, w32, classes, own_acts);
+    return b.off + 256;
+}
+
+// the images entry: the branch, both blocks and the head being trained write this call's endpoints
+void highres_bind(IcnetHighresWs &t, const IcWorkspace &W)
+{
+    t.a1 = W.act.at("conv1_sub1");
+    t.a2 = W.act.at("conv2_sub1");
+    t.f3 = W.act.at("conv3_sub1");
+    cascade_bind(t.cascade, W);
+}
+
+bool highres_fits(int n, int h32, int w32) { return icnet_highres_fits(n, h32, w32) && cascade_fits(n, h32, w32); }
+
+int highres_check(int n, int h32, int w32, int classes, int c_in, int max_workgroups)
+{
+    if (int rc = capped_dims_check(n, h32, w32, classes, max_workgroups, n <= 0 || highres_fits(n, h32, w32),
+                                   "high-resolution gradient kernels'"))
+        return rc;
+    if (c_in != 3 && c_in != 4) return fail(SSAL_EINVAL, "the high-resolution trainer takes 3 or 4 input channels (got %d)", c_in);
+    return SSAL_OK;
+}
+
+// c54 [n,h32,w32,256] / c31 [n,2 h32,2 w32,256]: conv5_4_k1 and conv3_1 of the training frames x [n,32 h32,32 w32,c_in], which
+// trunk(false) brings about (an images entry) or the caller has
+template <typename Trunk>
+int highres_run(Trunk trunk, const float *c54, const float *c31, const void *x, bool x_is_u8, int c_in, int n, int h32, int w32,
+                int classes, const float *params_dev, const float *stats_dev, int max_workgroups, const CallArgs &a,
+                const IcnetHighresWs &t)
+{
+    if (int rc = trunk(false)) return rc;
+    HIP_TRY(launch_icnet_highres_grad(c54, c31, x, x_is_u8, c_in, n, h32, w32, classes, params_dev, stats_dev, a.labels, a.mask,
+                                      a.weight, a.label_smoothing, max_workgroups, t, a.loss, a.grad, a.s));
+    return SSAL_OK;
+}
+
+int highres_grad_entry(const float *conv5_4_k1_dev, const float *conv3_1_dev, const void *x_dev, int x_is_u8, int c_in, int n,
+                       int h, int w, int classes, const float *params_dev, const float *stats_dev, int max_workgroups,
+                       const CallArgs &a)
+{
+    if (int rc = highres_check(n, h, w, classes, c_in, max_workgroups)) return rc;
+    if (int rc = args_check(conv5_4_k1_dev && conv3_1_dev && x_dev && params_dev && stats_dev, a, nullptr)) return rc;
+    Bump b(a.ws, a.ws_bytes);
+    const IcnetHighresWs t = highres_carve(b, n, h, w, classes, true);
+    if (int rc = ws_check(highres_bytes(0, n, h, w, classes, true), b, a)) return rc;
+    return highres_run(no_trunk, conv5_4_k1_dev, conv3_1_dev, x_dev, x_is_u8 != 0, c_in, n, h, w, classes, params_dev, stats_dev,
+                       max_workgroups, a, t);
+}
+
+int highres_train_entry(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w, const float *params_dev,
+                        const float *stats_dev, int max_workgroups, const CallArgs &a)
+{
+    int rc = check_dims(net, n, h, w);
+    if (rc) return rc;
+    const int K = net->classes, h32 = h / 32, w32 = w / 32;
+    if ((rc = highres_check(n, h32, w32, K, net->c_in, max_workgroups))) return rc;
+    if ((rc = args_check(x_dev && params_dev && stats_dev, a, nullptr))) return rc;
+    IcWorkspace W;
+    Bump b = carve_behind_trunk(net, a, n, h, w, &W);
+    IcnetHighresWs t = highres_carve(b, n, h32, w32, K, false);
+    if ((rc = ws_check(highres_bytes(W.bytes, n, h32, w32, K, false), b, a))) return rc;
+    highres_bind(t, W);
+    hipStream_t s = a.s;
+    auto backbone = [=, &W](bool) -> int {  // the two frozen branches only: run_trunk's stop in front of conv1_sub1
+        std::vector<Grp> one(1);
+        one[0] = {W, x_dev, n, s};
+        HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false, false, false, false));
+        return SSAL_OK;
+    };
+    return highres_run(backbone, W.act.at("conv5_4_k1"), W.act.at("conv3_1"), x_dev, x_is_u8 != 0, net->c_in, n, h32, w32, K,
+                       params_dev, stats_dev, max_workgroups, a, t);
+}
+
 // ---- the trained variables back into the handle ----
 // Each (tensor, host pointer, count) goes into the handle's host tensors; then the named layers are re-laid-out, folded with
 // the handle's moving statistics and uploaded.
@@ -1169,8 +1274,13 @@ int update_packed(ssal_icnet *net, const std::vector<HostUpdate> &tensors, const
     std::vector<std::vector<float>> keep;
     for (const ConvSpec &sp : net->specs) {
         if (!layers.count(sp.name)) continue;
-        std::vector<float> wt(igemm_relayout_floats(sp.k, sp.k, sp.cin, sp.cout)), sc, sh;
-        igemm_relayout(T(net, sp.name + ".kernel").data(), sp.k, sp.k, sp.cin, sp.cout, wt.data());
+        std::vector<float> wt, sc, sh;
+        if (sp.cin % 32 == 0) {
+            wt.resize(igemm_relayout_floats(sp.k, sp.k, sp.cin, sp.cout));
+            igemm_relayout(T(net, sp.name + ".kernel").data(), sp.k, sp.k, sp.cin, sp.cout, wt.data());
+        } else {
+            wt = T(net, sp.name + ".kernel");  // a branch's first convolution keeps HWIO, as ssal_icnet_commit stages it
+        }
         if (sp.bn)
             fold_bn_padded(T(net, sp.name + ".mean").data(), T(net, sp.name + ".variance").data(),
                            T(net, sp.name + ".gamma").data(), T(net, sp.name + ".beta").data(), nullptr, sp.cout, sc, sh);
@@ -1438,6 +1548,65 @@ SSAL_API int ssal_icnet_update_cascade(ssal_icnet *net, const float *params_host
                                  {"conv3_1_sub2_proj.beta", params_host + CA_BD, 128}};
     for (const HostUpdate &u : fusion_tensors(params_host + CA_FUSION, net->classes)) t.push_back(u);
     return update_packed(net, t, {"conv_sub4", "conv3_1_sub2_proj", "conv_sub2", "conv3_sub1_proj", "conv6_cls"}, stream);
+}
+
+// ---- the high-resolution branch down to the image ----
+SSAL_API int64_t ssal_icnet_highres_grad_workspace_bytes(int n, int h, int w, int classes)
+{
+    return capped_dims_ok(n, classes, highres_fits(n, h, w)) ? highres_bytes(0, n, h, w, classes, true) : -1;
+}
+
+SSAL_API int ssal_icnet_highres_grad_nhwc(const float *conv5_4_k1_dev, const float *conv3_1_dev, const void *x_dev, int n, int h,
+                                          int w, int classes, const float *params_dev, const uint8_t *labels_dev,
+                                          const float *mask_dev, float weight, float label_smoothing, const float *stats_dev,
+                                          int x_is_u8, int c_in, int max_workgroups, double *loss_dev, float *grad_dev,
+                                          void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return highres_grad_entry(conv5_4_k1_dev, conv3_1_dev, x_dev, x_is_u8, c_in, n, h, w, classes, params_dev, stats_dev,
+                              max_workgroups, a);
+}
+
+SSAL_API int64_t ssal_icnet_train_highres_workspace_bytes(const ssal_icnet *net, int n, int h, int w)
+{
+    if (!net_dims_ok(net, n, h, w) || !highres_fits(n, h / 32, w / 32)) return -1;
+    return highres_bytes(trunk_bytes(net, n, h, w), n, h / 32, w / 32, net->classes, false);
+}
+
+SSAL_API int ssal_icnet_train_highres_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                                           const uint8_t *labels_dev, const float *mask_dev, const float *params_dev,
+                                           float weight, float label_smoothing, const float *stats_dev, int max_workgroups,
+                                           double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return highres_train_entry(net, x_dev, x_is_u8, n, h, w, params_dev, stats_dev, max_workgroups, a);
+}
+
+SSAL_API int ssal_icnet_update_highres(ssal_icnet *net, const float *params_host, void *stream)
+{
+    if (!net || !params_host) return fail(SSAL_EINVAL, "NULL argument");
+    if (net->c_in != 3 && net->c_in != 4)
+        return fail(SSAL_EINVAL, "the high-resolution trainer takes 3 or 4 input channels (got %d)", net->c_in);
+    const IcnetHighresOff o = icnet_highres_offsets(net->c_in);
+    const float *p = params_host, *c = params_host + o.cascade;
+    std::vector<HostUpdate> t = {{"conv1_sub1.kernel", p + o.k1, o.g1},
+                                 {"conv1_sub1.gamma", p + o.g1, 32},
+                                 {"conv1_sub1.beta", p + o.b1, 32},
+                                 {"conv2_sub1.kernel", p + o.k2, 9 * 32 * 32},
+                                 {"conv2_sub1.gamma", p + o.g2, 32},
+                                 {"conv2_sub1.beta", p + o.b2, 32},
+                                 {"conv3_sub1.kernel", p + o.k3, 9 * 32 * 64},
+                                 {"conv3_sub1.gamma", p + o.g3, 64},
+                                 {"conv3_sub1.beta", p + o.b3, 64},
+                                 {"conv_sub4.kernel", c + CA_KC, CA_GC},
+                                 {"conv_sub4.gamma", c + CA_GC, 128},
+                                 {"conv_sub4.beta", c + CA_BC, 128},
+                                 {"conv3_1_sub2_proj.kernel", c + CA_KD, 256 * 128},
+                                 {"conv3_1_sub2_proj.gamma", c + CA_GD, 128},
+                                 {"conv3_1_sub2_proj.beta", c + CA_BD, 128}};
+    for (const HostUpdate &u : fusion_tensors(c + CA_FUSION, net->classes)) t.push_back(u);
+    return update_packed(net, t, {"conv1_sub1", "conv2_sub1", "conv3_sub1", "conv_sub4", "conv3_1_sub2_proj", "conv_sub2",
+                                  "conv3_sub1_proj", "conv6_cls"}, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1414,7 +1414,7 @@ class ICNetFusionTrainer(ICNetHeadTrainer):
         return tuple((lo, hi, reg) for (lo, hi), (_, _, reg) in zip(self._offsets(), self._VARS))
 
     def _stats(self, device):
-        """the frozen moving statistics [len(_STATS) * 128] on the device (pushed again only when one of them changed)"""
+        """the frozen moving statistics, ``_STATS``' rows concatenated unpadded at their own widths, on the device (pushed again only when one of them changed)"""
         torch = _lib.require_gpu()
         stat_vars = [getattr(getattr(self.net, layer), attr) for layer, attr in self._STATS]
         key = (device, tuple(v.version for v in stat_vars))
@@ -1590,6 +1590,102 @@ class ICNetCascadeTrainer(ICNetFusionTrainer):
                                confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
 
 
+# ---- ICNet's high-resolution branch down to the image, with the cascade head ----------------------------
+_HIGHRES_LAYERS = ("conv1_sub1", "conv2_sub1", "conv3_sub1")
+_HIGHRES_VARS = tuple((layer, attr, attr == "kernel") for layer in _HIGHRES_LAYERS
+                      for attr in ("kernel", "gamma", "beta")) + _CASCADE_VARS
+# rows of mixed widths (32, 32, 32, 32, 64, 64, then the cascade trainer's eight of 128), concatenated unpadded
+_HIGHRES_STATS = tuple((layer, attr) for layer in _HIGHRES_LAYERS for attr in ("mean", "variance")) + _CASCADE_STATS
+
+
+class ICNetHighResTrainer(ICNetCascadeTrainer):
+    """Adam on ICNet's high-resolution branch (ICNET_SPEC section 3) and the cascade head above it: ``conv1_sub1``,
+    ``conv2_sub1`` and ``conv3_sub1`` -- three 3 x 3 stride-2 convolutions + batch-norm + ReLU, ``C_in -> 32 -> 32 -> 64`` on
+    the full-resolution frame -- then everything ``ICNetCascadeTrainer`` trains.  The two backbone branches stay frozen
+    (``training=False`` up to ``conv5_4_k1`` [N, H/32, W/32, 256] and ``conv3_1`` [N, H/16, W/16, 256]) and can be cached
+    across steps; the backward pass ends at the frame, which gets no gradient.  Batch-norm, hyper-parameters, Adam and the
+    refusals are the parent's; the ``l1_l2`` regulariser goes to the eight kernels only.  ``C_in`` is 3 or 4.
+
+    The 23 variables travel as one packed float32 vector in the order of ``variable_names``: the branch's nine, then the
+    parent's fourteen in the parent's order."""
+
+    _C_FEATURES = ("ssal_icnet_highres_grad", None)
+    _C_IMAGES = ("ssal_icnet_train_highres", None)
+    _CHANNELS, _UP = 256, 32
+    _VARS, _STATS, _C_UPDATE = _HIGHRES_VARS, _HIGHRES_STATS, "ssal_icnet_update_highres"
+    variable_names = ["%s.%s" % (layer, attr) for layer, attr, _ in _HIGHRES_VARS]
+
+    _SEMI_NOUN = "ICNet's high-resolution trainer"
+    _FEATURE_NAMES = ("conv5_4_k1", "conv3_1")
+
+    def _check_features(self, conv5_4_k1, conv3_1, images, labels, mask, max_workgroups):
+        mw = self._check_call(conv5_4_k1, 32, labels, mask, max_workgroups, 256)
+        n, h, w, _ = tuple(np.shape(conv5_4_k1))
+        if tuple(np.shape(conv3_1)) != (n, 2 * h, 2 * w, 256):
+            raise ValueError("conv3_1 must be %s for conv5_4_k1 %s (got %s)"
+                             % ((n, 2 * h, 2 * w, 256), (n, h, w, 256), tuple(np.shape(conv3_1))))
+        dt = str(getattr(conv3_1, "dtype", ""))
+        if "float" not in dt:
+            raise ValueError("conv3_1 must be a floating-point tensor (got %s)" % (dt or type(conv3_1).__name__))
+        self._vars()  # (the model is built)
+        c_in = int(self.net._c_in)
+        if c_in not in (3, 4):
+            raise ValueError("the high-resolution trainer takes 3 or 4 input channels (the model has %d)" % c_in)
+        if tuple(np.shape(images)) != (n, 32 * h, 32 * w, c_in):
+            raise ValueError("images must be %s for conv5_4_k1 %s (got %s)"
+                             % ((n, 32 * h, 32 * w, c_in), (n, h, w, 256), tuple(np.shape(images))))
+        dt = str(getattr(images, "dtype", ""))
+        if not ("float" in dt or "uint8" in dt):
+            raise ValueError("images must be a floating-point or uint8 tensor (got %s)" % (dt or type(images).__name__))
+        return mw
+
+    def _feature_call(self, feats, labels, mask, params, step, max_workgroups, labelled=None, measure=None, threshold=None,
+                      features_raw=None, confusion=None, return_pseudo_pixels=False):
+        """the parent's, with the frames as the third input: they stay uint8 when they are (the entry converts them as the
+        forward path does) and the entry is told their type and channel count"""
+        self._semi_call(feats[0], labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels,
+                        features_raw=features_raw)
+        mw = self._check_features(*feats, labels, mask, max_workgroups)
+        packed = None if step else self._packed_with(params)
+        torch = _lib.require_gpu()
+        x = _lib.as_device_f32(feats[0])
+        xs = (x, _lib.as_device_f32(feats[1]).to(x.device), _lib.as_device_image(feats[2]).to(x.device))
+        dev = self._device_state(x.device) if step else None
+        vec = dev["w"] if step else torch.from_numpy(packed).to(x.device)
+        extra = self._extra_c_args(x) + (int(xs[2].dtype == torch.uint8), int(self.net._c_in), mw)
+        loss, grad, pp = self._grad_call(xs, (None,) * 3, labels, mask, vec, None, confusion, return_pseudo_pixels, extra)
+        return loss, grad, pp, dev
+
+    def gradient_features(self, conv5_4_k1, conv3_1, images, labels, mask, params=None, max_workgroups=0, labelled=None,
+                          confusion=None, return_pseudo_pixels=False):
+        """(loss float64 [1], {name: gradient} for ``variable_names``) on the device for ``conv5_4_k1`` [N, h, w, 256],
+        ``conv3_1`` [N, 2h, 2w, 256], ``images`` [N, 32h, 32w, C_in] (fp32 or decoded uint8) and labels / mask [N, 32h, 32w].
+        ``params`` overrides any of the 23 tensors; ``max_workgroups``: 0 = the default grids, a tuning knob.  No update."""
+        return self._gradient_from((conv5_4_k1, conv3_1, images), labels, mask, params, max_workgroups, labelled=labelled,
+                                   confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
+
+    def features(self, images):
+        """``(conv5_4_k1 [N, H/32, W/32, 256], conv3_1 [N, H/16, W/16, 256])`` for ``images`` (copies): what ``step_features``
+        and ``gradient_features`` take next to the frames.  One forward pass; the two backbone branches are frozen, so the
+        result can be cached across steps."""
+        self.net(images, training=False)
+        return tuple(self.net.endpoint(name).clone() for name in ("conv5_4_k1", "conv3_1"))
+
+    def step_features(self, conv5_4_k1, conv3_1, images, labels, mask, max_workgroups=0, labelled=None, confusion=None,
+                      return_pseudo_pixels=False):
+        """one Adam step from cached backbone features and the frames; returns the loss (float64 device scalar) BEFORE the
+        step"""
+        return self._step_from((conv5_4_k1, conv3_1, images), labels, mask, max_workgroups, labelled=labelled,
+                               confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
+
+    def step(self, images, labels, mask, max_workgroups=0, labelled=None, confusion=None, return_pseudo_pixels=False):
+        """one Adam step from images [N, H, W, C_in] (fp32 or decoded uint8) and labels / mask [N, H, W]: the two frozen
+        backbone branches, then the high-resolution branch, both fusion blocks and the head on the weights being trained,
+        their gradient kernels down to the frame, Adam.  Returns the loss (float64 device scalar) before the step."""
+        return self._step_from_images(images, labels, mask, max_workgroups, labelled=labelled, confusion=confusion,
+                                      return_pseudo_pixels=return_pseudo_pixels)
+
+
 # ---- the semi-supervised step of ICNet's fusion and cascade trainers (DESIGN.md section 30) --------------------------------------
 class SemiSupervisedICNetFusionTrainer(_SemiKeywords, ICNetFusionTrainer):
     """``ICNetFusionTrainer`` with the reference's semi-supervised step (active_learning.py:226-275, 339-342) built into the
@@ -1668,4 +1764,4 @@ __all__ = ["FinalLayerTrainer", "LastBlockTrainer", "LastStageTrainer", "Decoder
            "SemiSupervisedStageTrainer", "SemiSupervisedTailTrainer", "DeepTailTrainer", "SemiSupervisedDeepTailTrainer",
            "DecoderTrainer", "SemiSupervisedDecoderTrainer", "ICNetHeadTrainer", "SemiSupervisedICNetHeadTrainer",
            "ICNetFusionTrainer", "ICNetCascadeTrainer", "SemiSupervisedICNetFusionTrainer",
-           "SemiSupervisedICNetCascadeTrainer"]
+           "SemiSupervisedICNetCascadeTrainer", "ICNetHighResTrainer"]
