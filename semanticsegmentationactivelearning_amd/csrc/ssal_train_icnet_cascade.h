@@ -10,11 +10,12 @@
 
 namespace ssal {
 
-// The packed vector everything here takes and gives (float offsets):
+// The packed vector everything here takes and gives (float offsets; FusionBlock<256>, ssal_train_icnet_common.h):
 //   conv_sub4.kernel [3,3,256,128] | .gamma [128] | .beta [128] | conv3_1_sub2_proj.kernel [1,1,256,128] | .gamma | .beta |
 //   the fusion trainer's packed vector (ssal_train_icnet_fusion.h)
-constexpr int CA_KC = 0, CA_GC = 9 * 256 * 128, CA_BC = CA_GC + 128, CA_KD = CA_BC + 128, CA_GD = CA_KD + 256 * 128,
-              CA_BD = CA_GD + 128, CA_FUSION = CA_BD + 128;
+using CaBlock = FusionBlock<256>;
+constexpr int CA_KC = CaBlock::KA, CA_GC = CaBlock::GA, CA_BC = CaBlock::BA, CA_KD = CaBlock::KB, CA_GD = CaBlock::GB,
+              CA_BD = CaBlock::BB, CA_FUSION = CaBlock::END;
 inline int64_t icnet_cascade_floats(int K) { return CA_FUSION + icnet_fusion_floats(K); }
 // the frozen moving statistics: conv_sub4 mean | variance | conv3_1_sub2_proj mean | variance | the fusion trainer's four
 constexpr int CA_STATS = 4 * 128 + FU_STATS;
@@ -23,10 +24,9 @@ constexpr int CA_STATS = 4 * 128 + FU_STATS;
 // taken on [N, 32 h32, 32 w32].  k_icnet_cascade_dx walks tiles of CA_DX_TH x CA_DX_TW pixels of du (1/8 resolution).
 constexpr int CA_DX_TH = 8, CA_DX_TW = 16;
 constexpr int CA_DX_MAX_WG = 2048;                  // workgroups of the data-gradient launch (tiles are strided over them)
-constexpr int CA_PART = CA_TAPS * 256 * 128;        // floats of one split-K partial: [tap][ci][co]
-constexpr int CA_MAX_WG = 64;                       // split-K groups the finish kernel folds (x CA_TAPS x 2 workgroups)
+constexpr int CA_PART = CaBlock::PART;              // floats of one split-K partial: [tap][ci][co]
+constexpr int CA_MAX_WG = CaBlock::MAX_WG;          // split-K groups the finish kernel folds (x CA_TAPS x 2 workgroups)
 bool icnet_cascade_fits(int h32, int w32);
-int icnet_cascade_workgroups(int n, int h32, int w32, int max_workgroups);
 
 struct IcnetCascadeWs {
     float *wt_c;    // conv_sub4's kernel in igemm_relayout's layout [9][8][128][32]

@@ -1,13 +1,15 @@
 // ssal_train_icnet_cascade.hip -- training of ICNet's whole cascade head (both fusion blocks and conv6_cls) over frozen
 // branches, gfx950.  Behind the forward path's own launches on the weights being trained and the
 // fusion trainer's gradient (ssal_train_icnet_fusion.hip, which leaves g = dL/dsub12_sum behind its ReLU):
-//   k_icnet_cascade_pack    the packed vector -> conv_sub4 / conv3_1_sub2_proj in launch_igemm's layout, folded batch-norm rows
+//   k_icnet_block_pack<256> (ssal_train_icnet_common.h; the profile's k_icnet_cascade_pack) the packed vector -> conv_sub4 /
+//                           conv3_1_sub2_proj in launch_igemm's layout, folded batch-norm rows
 //   k_icnet_cascade_dx      the data gradient through conv_sub2 as an implicit GEMM on the fp32 matrix cores:
 //                           du[p, ci] = sum_tap sum_co K_a[tap, ci, co] (s_a[co] g[p - 2 (tap - 1), co])
 //   k_icnet_cascade_g24     the adjoint of the legacy 2x resize in gather form and the ReLU mask: du -> dL/dsub24_sum
 //   k_icnet_fusion_wgrad<256>  (ssal_train_icnet_fusion.hip) the weight gradients of the block, split-K
-//   k_icnet_cascade_finish  fixed-order fold of the partials, the batch-norm scale, 1 / sum(mask)
-//   k_icnet_cascade_gamma   dGamma contracted from the folded weight gradient
+//   k_icnet_block_finish<256, false>  (common; k_icnet_cascade_finish) fixed-order fold of the partials, the batch-norm scale,
+//                           the 1 / sum(mask) the fusion trainer's finish left behind
+//   k_icnet_block_gamma<256>  (common; k_icnet_cascade_gamma) dGamma contracted from the folded weight gradient
 // No floating-point atomics, no inline assembly, 64-bit offsets: two runs give the same bits.
 #include "ssal_icnet.h"
 #include "ssal_internal.h"
@@ -26,39 +28,6 @@ bool icnet_cascade_fits(int h32, int w32)
 {
     if (h32 < 1 || w32 < 1 || h32 > (1 << 25) || w32 > (1 << 25)) return false;  // 2 h32 <= 2^26: icnet_fusion_fits' limit
     return icnet_fusion_fits(2 * h32, 2 * w32);  // every grid here is strided over 64-bit tile counts: no limit of its own
-}
-
-int icnet_cascade_workgroups(int n, int h32, int w32, int max_workgroups)
-{
-    long g = (long)n * ((2 * h32 + FU_TH - 1) / FU_TH) * ((2 * w32 + FU_TW - 1) / FU_TW);
-    if (g > CA_MAX_WG) g = CA_MAX_WG;
-    if (max_workgroups > 0 && g > max_workgroups) g = max_workgroups;
-    return (int)g;
-}
-
-static long dx_tiles(int n, int h8, int w8)
-{
-    return (long)n * ((h8 + CA_DX_TH - 1) / CA_DX_TH) * ((w8 + CA_DX_TW - 1) / CA_DX_TW);
-}
-
-// stats: mean_c | var_c | mean_d | var_d.  As k_icnet_fusion_pack, at 256 input channels.
-__global__ __launch_bounds__(256) void k_icnet_cascade_pack(const float *__restrict__ P, const float *__restrict__ stats,
-                                                            float *__restrict__ wt_c, float *__restrict__ wt_d,
-                                                            float *__restrict__ rows)
-{
-    const int o = blockIdx.x * 256 + threadIdx.x;
-    if (o < CA_GC) {
-        const int tap = o >> 15, ci = (o >> 7) & 255, co = o & 127;
-        wt_c[((tap * 8 + (ci >> 5)) * 128 + co) * 32 + igemm_kpos(ci & 31)] = P[CA_KC + o];
-    } else if (o < CA_GC + 256 * 128) {
-        const int e = o - CA_GC, ci = e >> 7, co = e & 127;
-        wt_d[((ci >> 5) * 128 + co) * 32 + igemm_kpos(ci & 31)] = P[CA_KD + e];
-    } else if (o < CA_GC + 256 * 128 + 256) {
-        const int e = o - CA_GC - 256 * 128, b = e >> 7, c = e & 127;
-        const float sg = P[(b ? CA_GD : CA_GC) + c] / sqrtf(stats[(2 * b + 1) * 128 + c] + 1e-3f);
-        rows[256 * b + c] = sg;
-        rows[256 * b + 128 + c] = fmaf(-stats[2 * b * 128 + c], sg, P[(b ? CA_BD : CA_BC) + c]);
-    }
 }
 
 // du[p, ci] = sum_co sum_tap K[tap, ci, co] gs[p - 2 (kh - 1, kw - 1), co], gs = s[co] g, zero outside the map: the transposed
@@ -170,54 +139,6 @@ __global__ __launch_bounds__(256) void k_icnet_cascade_g24(const float *__restri
     }
 }
 
-// raw[o] = sum over split-K groups b = 0 .. G - 1 of part[b][o], fp32, in that order -> fold[o] ([tap][ci 256][co]); dK_c =
-// (raw scale) s_c[co], dK_d = (raw scale) s_d[co], dBeta_c = dBeta_d = raw[10][0][co] scale; scale: the one
-// k_icnet_fusion_finish took from the head kernel's lpart
-__global__ __launch_bounds__(256) void k_icnet_cascade_finish(const float *__restrict__ part, int G,
-                                                              const float *__restrict__ scale_p, const float *__restrict__ rows,
-                                                              float *__restrict__ fold, float *__restrict__ grad)
-{
-    const int o = blockIdx.x * 256 + threadIdx.x;
-    const int tap = o >> 15, ci = (o >> 7) & 255, co = o & 127;
-    if (o >= CA_PART || (tap == 10 && ci != 0)) return;  // (of tap 10 only the row of ones is a gradient)
-    const float scale = scale_p[0];
-    float acc = 0.0f;
-    for (int gi = 0; gi < G; ++gi) acc += part[(long)gi * CA_PART + o];
-    fold[o] = acc;
-    if (tap < 9) {
-        grad[CA_KC + o] = (acc * scale) * rows[co];
-    } else if (tap == 9) {
-        grad[CA_KD + ci * 128 + co] = (acc * scale) * rows[256 + co];
-    } else {
-        grad[CA_BC + co] = acc * scale;
-        grad[CA_BD + co] = acc * scale;
-    }
-}
-
-// k_icnet_fusion_gamma at 256 input channels.  grid 2 (branch c, d) x 128 threads (co)
-__global__ __launch_bounds__(128) void k_icnet_cascade_gamma(const float *__restrict__ fold, const float *__restrict__ scale_p,
-                                                             const float *__restrict__ P, const float *__restrict__ stats,
-                                                             float *__restrict__ grad)
-{
-    const int co = threadIdx.x, b = blockIdx.x;
-    const float rbeta = fold[10 * 256 * 128 + co], scale = scale_p[0];
-    float sum = 0.0f;
-    if (b == 0) {
-        for (int tap = 0; tap < 9; ++tap) {
-            float a = 0.0f;
-            for (int ci = 0; ci < 256; ++ci) {
-                const int o = (tap * 256 + ci) * 128 + co;
-                a = fmaf(P[CA_KC + o], fold[o], a);
-            }
-            sum += a;
-        }
-    } else {
-        for (int ci = 0; ci < 256; ++ci) sum = fmaf(P[CA_KD + ci * 128 + co], fold[(9 * 256 + ci) * 128 + co], sum);
-    }
-    const float rstd = 1.0f / sqrtf(stats[(2 * b + 1) * 128 + co] + 1e-3f);
-    grad[(b ? CA_GD : CA_GC) + co] = ((sum - stats[2 * b * 128 + co] * rbeta) * rstd) * scale;
-}
-
 // the pack, then the forward path's own launches (ssal_icnet_api.hip, run_trunk) on the weights being trained:
 // ws.proj = BN(conv3_1_sub2_proj(c31)), ws.sub24 = sub24_sum
 static hipError_t cascade_forward(const float *c54, const float *c31, int N, int h32, int w32, const float *params,
@@ -227,8 +148,8 @@ static hipError_t cascade_forward(const float *c54, const float *c31, int N, int
     hipError_t e;
     {
         ProfScope prof("k_icnet_cascade_pack", 0.0, 8.0 * CA_FUSION, s);
-        hipLaunchKernelGGL(k_icnet_cascade_pack, dim3((CA_GC + 256 * 128 + 256 + 255) / 256), dim3(256), 0, s, params, stats,
-                           ws.wt_c, ws.wt_d, ws.rows);
+        hipLaunchKernelGGL(k_icnet_block_pack<256>, dim3(icnet_cdiv(CA_GC + 256 * 128 + 256, 256)), dim3(256), 0, s, params,
+                           stats, ws.wt_c, ws.wt_d, ws.rows);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     e = launch_igemm(c31, N, h16, w16, 256, ws.wt_d, 1, 1, 128, 1, 1, ws.rows + 256, ws.rows + 384, nullptr, false, false,
@@ -267,34 +188,30 @@ hipError_t launch_icnet_cascade_grad(const float *c54, const float *c31, const f
                                  label_smoothing, max_workgroups, ws.fusion, loss, grad + CA_FUSION, s, semi);
     if (e != hipSuccess) return e;
     {
-        long G = dx_tiles(N, h8, w8);
-        if (G > CA_DX_MAX_WG) G = CA_DX_MAX_WG;
-        if (max_workgroups > 0 && G > max_workgroups) G = max_workgroups;
-        ProfScope prof("k_icnet_cascade_dx", 2.0 * pix8 * 9 * 128 * 128,
-                       8.0 * pix8 * 128 + 4.0 * (double)dx_tiles(N, h8, w8) * 9 * 128 * 128, s);
-        hipLaunchKernelGGL(k_icnet_cascade_dx, dim3((unsigned)G), dim3(256), 0, s, ws.fusion.g, params + CA_FUSION + FU_KA,
-                           ws.fusion.rows, N, h8, w8, ws.du);
+        const long tiles = (long)N * icnet_cdiv(h8, CA_DX_TH) * icnet_cdiv(w8, CA_DX_TW);
+        ProfScope prof("k_icnet_cascade_dx", 2.0 * pix8 * 9 * 128 * 128, 8.0 * pix8 * 128 + 4.0 * (double)tiles * 9 * 128 * 128,
+                       s);
+        hipLaunchKernelGGL(k_icnet_cascade_dx, dim3(icnet_grid(tiles, CA_DX_MAX_WG, max_workgroups)), dim3(256), 0, s,
+                           ws.fusion.g, params + CA_FUSION + FU_KA, ws.fusion.rows, N, h8, w8, ws.du);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     {
-        long B = ((long)N * h16 * w16 * 32 + 255) / 256;
-        if (B > 65536) B = 65536;
-        if (max_workgroups > 0 && B > max_workgroups) B = max_workgroups;
+        const int B = icnet_grid(icnet_cdiv((long)N * h16 * w16 * 32, 256), 65536, max_workgroups);
         ProfScope prof("k_icnet_cascade_g24", 18.0 * pix16 * 128, 4.0 * (pix8 + 2.0 * pix16) * 128, s);
-        hipLaunchKernelGGL(k_icnet_cascade_g24, dim3((unsigned)B), dim3(256), 0, s, ws.du, ws.sub24, N, h16, w16, ws.g24);
+        hipLaunchKernelGGL(k_icnet_cascade_g24, dim3(B), dim3(256), 0, s, ws.du, ws.sub24, N, h16, w16, ws.g24);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    const int G = icnet_cascade_workgroups(N, h32, w32, max_workgroups);
+    const int G = icnet_block_workgroups<256>(N, h32, w32, max_workgroups);
     if ((e = launch_icnet_fusion_wgrad256(c54, c31, ws.g24, N, h32, w32, G, ws.part, s)) != hipSuccess) return e;
-    const float *scale = ws.fusion.fold + FU_PART;
+    float *scale = ws.fusion.fold + FU_PART;  // 1 / sum(mask), as the fusion trainer's finish left it
     {
         ProfScope prof("k_icnet_cascade_finish", (double)G * CA_PART, 4.0 * (G + 2.0) * CA_PART, s);
-        hipLaunchKernelGGL(k_icnet_cascade_finish, dim3((CA_PART + 255) / 256), dim3(256), 0, s, ws.part, G, scale, ws.rows,
-                           ws.fold, grad);
+        hipLaunchKernelGGL((k_icnet_block_finish<256, false>), dim3(icnet_cdiv(CA_PART, 256)), dim3(256), 0, s, ws.part, G,
+                           nullptr, 0, scale, ws.rows, ws.fold, grad);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     ProfScope prof("k_icnet_cascade_gamma", 2.0 * (CA_GC + 256 * 128), 8.0 * CA_PART, s);
-    hipLaunchKernelGGL(k_icnet_cascade_gamma, dim3(2), dim3(128), 0, s, ws.fold, scale, params, stats, grad);
+    hipLaunchKernelGGL(k_icnet_block_gamma<256>, dim3(2), dim3(128), 0, s, ws.fold, scale, params, stats, grad);
     return hipGetLastError();
 }
 

@@ -6,14 +6,16 @@
 #include <stdint.h>
 
 #include "ssal_train_icnet.h"
+#include "ssal_train_icnet_common.h"
 
 namespace ssal {
 
-// The packed vector everything here takes and gives (float offsets):
+// The packed vector everything here takes and gives (float offsets; FusionBlock<128>, ssal_train_icnet_common.h):
 //   conv_sub2.kernel [3,3,128,128] | .gamma [128] | .beta [128] | conv3_sub1_proj.kernel [1,1,64,128] | .gamma | .beta |
 //   conv6_cls.kernel [1,1,128,K] | conv6_cls.bias [K]
-constexpr int FU_KA = 0, FU_GA = 9 * 128 * 128, FU_BA = FU_GA + 128, FU_KB = FU_BA + 128, FU_GB = FU_KB + 64 * 128,
-              FU_BB = FU_GB + 128, FU_HEAD = FU_BB + 128;
+using FuBlock = FusionBlock<128>;
+constexpr int FU_KA = FuBlock::KA, FU_GA = FuBlock::GA, FU_BA = FuBlock::BA, FU_KB = FuBlock::KB, FU_GB = FuBlock::GB,
+              FU_BB = FuBlock::BB, FU_HEAD = FuBlock::END;
 inline int64_t icnet_fusion_floats(int K) { return FU_HEAD + icnet_head_floats(K); }
 // the frozen moving statistics travel next to it: conv_sub2 mean | variance | conv3_sub1_proj mean | variance
 constexpr int FU_STATS = 4 * 128;
@@ -21,17 +23,22 @@ constexpr int FU_STATS = 4 * 128;
 // Geometry: sub24_sum [N, h16, w16, 128], conv3_sub1 [N, h8, w8, 64] with h8 = 2 h16, w8 = 2 w16; the loss is taken on
 // [N, 8 h8, 8 w8].  The weight-gradient kernel walks tiles of FU_TH x FU_TW pixels of sub12_sum.
 constexpr int FU_TH = 4, FU_TW = 8;
-constexpr int FU_TAPS = 10;                      // the nine dilated taps, then the 1 x 1 branch (+ the row of ones: dBeta)
-constexpr int FU_PART = FU_TAPS * 128 * 128;     // floats of one split-K partial: [tap][ci][co]
-constexpr int FU_MAX_WG = 96;                    // split-K groups the finish kernel folds (x FU_TAPS workgroups)
+constexpr int FU_TAPS = FuBlock::TAPS;           // the nine dilated taps, then the 1 x 1 branch (+ the row of ones: dBeta)
+constexpr int FU_PART = FuBlock::PART;           // floats of one split-K partial: [tap][ci][co]
+constexpr int FU_MAX_WG = FuBlock::MAX_WG;       // split-K groups the finish kernel folds (x FU_TAPS workgroups)
 bool icnet_fusion_fits(int h16, int w16);
-int icnet_fusion_workgroups(int n, int h16, int w16, int max_workgroups);
+// split-K groups of a fusion block's weight gradient on a low-resolution input [n, h, w]: its FU_TH x FU_TW tiles of the output
+template <int CIN>
+inline int icnet_block_workgroups(int n, int h, int w, int max_workgroups)
+{
+    return icnet_grid((long)n * icnet_cdiv(2 * h, FU_TH) * icnet_cdiv(2 * w, FU_TW), FusionBlock<CIN>::MAX_WG, max_workgroups);
+}
 
 // The weight-gradient kernel at 256 input channels (the other fusion block): src [N, hs, ws, 256] is
 // interpolated 2x on the fly, side [N, 2 hs, 2 ws, 256] is the 1 x 1 branch's input, g [N, 2 hs, 2 ws, 128].  Grid
 // (G, CA_TAPS, 2): the third index picks the input-channel half; the row of ones (sum_p g) is an eleventh tap.
 // part [G][CA_TAPS][256][128] ([G][tap][half][128][128]; tap 10 has its first half only, whose row 0 is sum_p g).
-constexpr int CA_TAPS = 11;
+constexpr int CA_TAPS = FusionBlock<256>::TAPS;
 hipError_t launch_icnet_fusion_wgrad256(const float *src, const float *side, const float *g, int N, int hs, int ws, int G,
                                         float *part, hipStream_t s);
 

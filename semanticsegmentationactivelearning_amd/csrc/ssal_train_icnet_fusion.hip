@@ -1,16 +1,18 @@
 // ssal_train_icnet_fusion.hip -- training of ICNet's last fusion stage and its output layer over a frozen trunk, gfx950
 // (DESIGN.md section 28):
-//   k_icnet_fusion_pack    the packed vector -> conv_sub2 / conv3_sub1_proj in launch_igemm's layout with their folded
-//                          batch-norm rows, so that the FORWARD path's own launches compute sub12_sum from the weights being
-//                          trained (the head: k_icnet_head_pack, the loss and dL/d(head): k_icnet_head_grad<K, false, true>)
+//   k_icnet_block_pack<128>  (ssal_train_icnet_common.h; the profile's k_icnet_fusion_pack) the packed vector -> conv_sub2 /
+//                          conv3_sub1_proj in launch_igemm's layout with their folded batch-norm rows, so that the FORWARD
+//                          path's own launches compute sub12_sum from the weights being trained (the head:
+//                          k_icnet_head_pack, the loss and dL/d(head): k_icnet_head_grad<K, false, true>)
 //   k_icnet_fusion_g       g = relu'(sub12_sum) (hw Wcls^T): the head kernel's per-tile pull-back windows gathered in a fixed
 //                          order into the complete per-pixel plane
 //   k_icnet_fusion_wgrad   the weight-gradient implicit GEMM on the fp32 matrix cores: sum_p u[p + tap, ci] g[p, co] for the
 //                          nine dilated taps (u = resize_2x(sub24_sum), interpolated from a staged window, never written),
 //                          sum_p conv3_sub1[p, ci] g[p, co] and sum_p g[p, co] as a tenth tap; split-K over workgroups
-//   k_icnet_fusion_finish  fixed-order fold of the partials, the batch-norm scale, 1 / sum(mask)
-//   k_icnet_fusion_gamma   dGamma = (sum K dKraw - mean dBeta) / sqrt(var + eps): sum_p g acc re-associated, so the pre-BN
-//                          accumulators are never formed
+//   k_icnet_block_finish<128, true>  (common; k_icnet_fusion_finish) fixed-order fold of the partials, the batch-norm scale,
+//                          1 / sum(mask)
+//   k_icnet_block_gamma<128>  (common; k_icnet_fusion_gamma) dGamma = (sum K dKraw - mean dBeta) / sqrt(var + eps): sum_p g acc
+//                          re-associated, so the pre-BN accumulators are never formed
 // No floating-point atomics, no inline assembly, 64-bit offsets: two runs give the same bits.
 #include "ssal_icnet.h"
 #include "ssal_internal.h"
@@ -29,40 +31,6 @@ bool icnet_fusion_fits(int h16, int w16)
 {
     if (h16 < 1 || w16 < 1 || h16 > (1 << 26) || w16 > (1 << 26)) return false;  // 2 h16 <= 2^27: icnet_head_fits' limit
     return icnet_head_fits(2 * h16, 2 * w16);  // its 4 x 4 tiles of sub12_sum outnumber the 4 x 8 ones here
-}
-
-static long fusion_tiles(int n, int h16, int w16)
-{
-    return (long)n * ((2 * h16 + FU_TH - 1) / FU_TH) * ((2 * w16 + FU_TW - 1) / FU_TW);
-}
-
-int icnet_fusion_workgroups(int n, int h16, int w16, int max_workgroups)
-{
-    long g = fusion_tiles(n, h16, w16);
-    if (g > FU_MAX_WG) g = FU_MAX_WG;
-    if (max_workgroups > 0 && g > max_workgroups) g = max_workgroups;
-    return (int)g;
-}
-
-// stats: mean_a | var_a | mean_b | var_b.  s = gamma / sqrtf(var + 1e-3f), t = fmaf(-mean, s, beta) as fold_bn_padded
-// (sqrtf and '/' are correctly rounded under HIP's default -fhip-fp32-correctly-rounded-divide-sqrt)
-__global__ __launch_bounds__(256) void k_icnet_fusion_pack(const float *__restrict__ P, const float *__restrict__ stats,
-                                                           float *__restrict__ wt_a, float *__restrict__ wt_b,
-                                                           float *__restrict__ rows)
-{
-    const int o = blockIdx.x * 256 + threadIdx.x;
-    if (o < FU_GA) {
-        const int tap = o >> 14, ci = (o >> 7) & 127, co = o & 127;
-        wt_a[((tap * 4 + (ci >> 5)) * 128 + co) * 32 + igemm_kpos(ci & 31)] = P[FU_KA + o];
-    } else if (o < FU_GA + 64 * 128) {
-        const int e = o - FU_GA, ci = e >> 7, co = e & 127;
-        wt_b[(((ci >> 5)) * 128 + co) * 32 + igemm_kpos(ci & 31)] = P[FU_KB + e];
-    } else if (o < FU_GA + 64 * 128 + 256) {
-        const int e = o - FU_GA - 64 * 128, b = e >> 7, c = e & 127;
-        const float sg = P[(b ? FU_GB : FU_GA) + c] / sqrtf(stats[(2 * b + 1) * 128 + c] + 1e-3f);
-        rows[256 * b + c] = sg;
-        rows[256 * b + 128 + c] = fmaf(-stats[2 * b * 128 + c], sg, P[(b ? FU_BB : FU_BA) + c]);
-    }
 }
 
 // hwp [N][tiles][36][K]: tile (ty, tx) of k_icnet_head_grad holds the pull-back of its own loss pixels onto the window of
@@ -142,7 +110,7 @@ __global__ __launch_bounds__(256) void k_icnet_fusion_wgrad(const float *__restr
     __shared__ __attribute__((aligned(16))) float win[FU_WR * FU_WC * 128];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
     const int tap = blockIdx.y;
-    constexpr int TAPS = CIN == 128 ? FU_TAPS : CA_TAPS;
+    constexpr int TAPS = FusionBlock<CIN>::TAPS;
     const int half = CIN == 128 ? 0 : (int)blockIdx.z, cb = 128 * half;
     if (CIN != 128 && tap == 10 && half) return;
     const int h8 = 2 * h16, w8 = 2 * w16;
@@ -232,66 +200,6 @@ __global__ __launch_bounds__(256) void k_icnet_fusion_wgrad(const float *__restr
         }
 }
 
-// raw[o] = sum over split-K groups b = 0 .. G - 1 of part[b][o], fp32, in that order -> fold[o]; the gradients that are a
-// scaled copy of it: dK_a = (raw scale) s_a[co], dK_b = (raw scale) s_b[co], dBeta_a = dBeta_b = raw[9][64][co] scale, scale =
-// (float)(1 / (double)(float)sum(mask)) from the head kernel's lpart as k_icnet_head_finish takes it (-> fold[FU_PART])
-__global__ __launch_bounds__(256) void k_icnet_fusion_finish(const float *__restrict__ part, int G,
-                                                             const double *__restrict__ lpart, int Gh,
-                                                             const float *__restrict__ rows, float *__restrict__ fold,
-                                                             float *__restrict__ grad)
-{
-    __shared__ double red[4];
-    __shared__ float scale_s;
-    double b = 0.0;
-    for (int i = threadIdx.x; i < Gh; i += 256) b += lpart[2 * (long)i + 1];
-    const double rb = block_sum_256(b, red);
-    if (threadIdx.x == 0) {
-        scale_s = (float)(1.0 / (double)(float)rb);
-        if (blockIdx.x == 0) fold[FU_PART] = scale_s;
-    }
-    __syncthreads();
-    const float scale = scale_s;
-    const int o = blockIdx.x * 256 + threadIdx.x;
-    if (o >= FU_PART) return;
-    float acc = 0.0f;
-    for (int gi = 0; gi < G; ++gi) acc += part[(long)gi * FU_PART + o];
-    fold[o] = acc;
-    const int tap = o >> 14, ci = (o >> 7) & 127, co = o & 127;
-    if (tap < 9) {
-        grad[FU_KA + o] = (acc * scale) * rows[co];
-    } else if (ci < 64) {
-        grad[FU_KB + ci * 128 + co] = (acc * scale) * rows[256 + co];
-    } else if (ci == 64) {
-        grad[FU_BA + co] = acc * scale;
-        grad[FU_BB + co] = acc * scale;
-    }
-}
-
-// dGamma[co] = sum_p g[p, co] (acc[p, co] - mean) / sqrt(var + 1e-3) with acc = sum K u re-associated over the pixels:
-// ((sum_tap (sum_ci K[tap, ci, co] raw[tap, ci, co], ci ascending, fmaf), taps ascending) - mean raw_beta) rstd scale.
-// grid 2 (branch a, b) x 128 threads (co)
-__global__ __launch_bounds__(128) void k_icnet_fusion_gamma(const float *__restrict__ fold, const float *__restrict__ P,
-                                                            const float *__restrict__ stats, float *__restrict__ grad)
-{
-    const int co = threadIdx.x, b = blockIdx.x;
-    const float rbeta = fold[(9 * 128 + 64) * 128 + co], scale = fold[FU_PART];
-    float sum = 0.0f;
-    if (b == 0) {
-        for (int tap = 0; tap < 9; ++tap) {
-            float a = 0.0f;
-            for (int ci = 0; ci < 128; ++ci) {
-                const int o = (tap * 128 + ci) * 128 + co;
-                a = fmaf(P[FU_KA + o], fold[o], a);
-            }
-            sum += a;
-        }
-    } else {
-        for (int ci = 0; ci < 64; ++ci) sum = fmaf(P[FU_KB + ci * 128 + co], fold[(9 * 128 + ci) * 128 + co], sum);
-    }
-    const float rstd = 1.0f / sqrtf(stats[(2 * b + 1) * 128 + co] + 1e-3f);
-    grad[(b ? FU_GB : FU_GA) + co] = ((sum - stats[2 * b * 128 + co] * rbeta) * rstd) * scale;
-}
-
 // the pack, then the forward path's own launches (ssal_icnet_api.hip, run_trunk) on the weights being trained:
 // ws.proj = BN(conv3_sub1_proj(c3)), ws.sub12 = sub12_sum
 static hipError_t fusion_forward(const float *sub24, const float *c3, int N, int h16, int w16, const float *params,
@@ -301,8 +209,8 @@ static hipError_t fusion_forward(const float *sub24, const float *c3, int N, int
     hipError_t e;
     {
         ProfScope prof("k_icnet_fusion_pack", 0.0, 8.0 * FU_HEAD, s);
-        hipLaunchKernelGGL(k_icnet_fusion_pack, dim3((FU_GA + 64 * 128 + 256 + 255) / 256), dim3(256), 0, s, params, stats,
-                           ws.wt_a, ws.wt_b, ws.rows);
+        hipLaunchKernelGGL(k_icnet_block_pack<128>, dim3(icnet_cdiv(FU_GA + 64 * 128 + 256, 256)), dim3(256), 0, s, params,
+                           stats, ws.wt_a, ws.wt_b, ws.rows);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     e = launch_igemm(c3, N, h8, w8, 64, ws.wt_b, 1, 1, 128, 1, 1, ws.rows + 256, ws.rows + 384, nullptr, false, false,
@@ -341,13 +249,13 @@ hipError_t launch_icnet_fusion_grad(const float *sub24, const float *c3, int N, 
     if (e != hipSuccess) return e;
     {
         ProfScope prof("k_icnet_fusion_g", 2.0 * pix * 128 * K, 4.0 * pix * (256 + 2.25 * K), s);
-        const long blocks = ((long)N * h8 * w8 + 63) / 64;
+        const long blocks = icnet_cdiv((long)N * h8 * w8, 64);
         if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
         hipLaunchKernelGGL(k_icnet_fusion_g, dim3((unsigned)blocks), dim3(256), 0, s, ws.hw, ws.sub12, params + FU_HEAD, N, h8,
                            w8, K, ws.g);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    const int G = icnet_fusion_workgroups(N, h16, w16, max_workgroups);
+    const int G = icnet_block_workgroups<128>(N, h16, w16, max_workgroups);
     {
         ProfScope prof("k_icnet_fusion_wgrad", 2.0 * pix * (9 * 128 + 64) * 128,
                        4.0 * (FU_TAPS * pix * 128 + pix * (32 + 64)) + 4.0 * G * FU_PART, s);
@@ -356,12 +264,13 @@ hipError_t launch_icnet_fusion_grad(const float *sub24, const float *c3, int N, 
     }
     {
         ProfScope prof("k_icnet_fusion_finish", (double)G * FU_PART, 4.0 * (G + 2.0) * FU_PART, s);
-        hipLaunchKernelGGL(k_icnet_fusion_finish, dim3((FU_PART + 255) / 256), dim3(256), 0, s, ws.part, G, ws.head.lpart,
-                           icnet_head_workgroups(h8, w8, max_workgroups), ws.rows, ws.fold, grad);
+        hipLaunchKernelGGL((k_icnet_block_finish<128, true>), dim3(icnet_cdiv(FU_PART, 256)), dim3(256), 0, s, ws.part, G,
+                           ws.head.lpart, icnet_head_workgroups(h8, w8, max_workgroups), ws.fold + FU_PART, ws.rows, ws.fold,
+                           grad);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     ProfScope prof("k_icnet_fusion_gamma", 2.0 * (FU_GA + 64 * 128), 8.0 * FU_PART, s);
-    hipLaunchKernelGGL(k_icnet_fusion_gamma, dim3(2), dim3(128), 0, s, ws.fold, params, stats, grad);
+    hipLaunchKernelGGL(k_icnet_block_gamma<128>, dim3(2), dim3(128), 0, s, ws.fold, ws.fold + FU_PART, params, stats, grad);
     return hipGetLastError();
 }
 

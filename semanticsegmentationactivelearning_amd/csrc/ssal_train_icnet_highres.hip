@@ -13,6 +13,8 @@
 //                            and of the frame, and a 32 x 32 MFMA tile would be 3/32 or 4/32 full
 //   k_icnet_highres_finish   fixed-order fold of the partials, the batch-norm scale, 1 / sum(mask); dBeta
 //   k_icnet_highres_gamma    dGamma contracted from the folded weight gradient (section 28's re-association)
+// The last two are the one-layer forms of the fusion blocks' finish and gamma; the batch-norm row fold, the relayout index, the
+// gamma loop and the grid arithmetic are ssal_train_icnet_common.h's.
 // Every gz is un-normalised and WITHOUT its layer's batch-norm scale: the weight gradient wants it so (s_l is applied once,
 // by the finish kernel), and a data-gradient kernel forms gs_l = s_l gz_l, rounded once, while it stages its window.
 // No floating-point atomics, no inline assembly, 64-bit offsets, grids strided over the tiles: two runs give the same bits.
@@ -30,18 +32,9 @@ bool icnet_highres_fits(int n, int h32, int w32)
     return (double)n * h32 * w32 < 131072.0;  // n (32 h32) (32 w32) < 2^27: check_dims' limit (ssal_icnet_api.hip)
 }
 
-static long cdiv_l(long a, long b) { return (a + b - 1) / b; }
-
-static unsigned capped_grid(long tiles, int cap, int max_workgroups)
-{
-    long g = tiles < cap ? tiles : cap;
-    if (max_workgroups > 0 && g > max_workgroups) g = max_workgroups;
-    return (unsigned)(g < 1 ? 1 : g);
-}
-
 // P: the packed vector; o2 / o3: where conv2_sub1.kernel / conv3_sub1.kernel start; the gammas and betas follow their kernels
 // (ssal_train_icnet_highres.h).  stats: mean_1 | var_1 | mean_2 | var_2 (32 each) | mean_3 | var_3 (64 each).
-// s = gamma / sqrtf(var + 1e-3f), t = fmaf(-mean, s, beta) as fold_bn_padded.
+// rows: icnet_bn_row's s | t of each layer.
 __global__ __launch_bounds__(256) void k_icnet_highres_pack(const float *__restrict__ P, IcnetHighresOff off,
                                                             const float *__restrict__ stats, float *__restrict__ wt2,
                                                             float *__restrict__ wt3, float *__restrict__ rows)
@@ -49,19 +42,17 @@ __global__ __launch_bounds__(256) void k_icnet_highres_pack(const float *__restr
     const int o = blockIdx.x * 256 + threadIdx.x;
     if (o < 9 * 32 * 32) {
         const int tap = o >> 10, ci = (o >> 5) & 31, co = o & 31;
-        wt2[(tap * 32 + co) * 32 + igemm_kpos(ci)] = P[off.k2 + o];
+        wt2[igemm_wt_index(tap, ci, co, 1, 32)] = P[off.k2 + o];
     } else if (o < 9 * 32 * 32 + 9 * 32 * 64) {
         const int e = o - 9 * 32 * 32, tap = e >> 11, ci = (e >> 6) & 31, co = e & 63;
-        wt3[(tap * 64 + co) * 32 + igemm_kpos(ci)] = P[off.k3 + e];
+        wt3[igemm_wt_index(tap, ci, co, 1, 64)] = P[off.k3 + e];
     } else if (o < 9 * 32 * 32 + 9 * 32 * 64 + 128) {
         const int e = o - 9 * 32 * 32 - 9 * 32 * 64;
         int c, go, bo, mo, vo, so, w;
         if (e < 32) { c = e; go = off.g1; bo = off.b1; mo = 0; vo = 32; so = 0; w = 32; }
         else if (e < 64) { c = e - 32; go = off.g2; bo = off.b2; mo = 64; vo = 96; so = 64; w = 32; }
         else { c = e - 64; go = off.g3; bo = off.b3; mo = 128; vo = 192; so = 128; w = 64; }
-        const float sg = P[go + c] / sqrtf(stats[vo + c] + 1e-3f);
-        rows[so + c] = sg;
-        rows[so + w + c] = fmaf(-stats[mo + c], sg, P[bo + c]);
+        icnet_bn_row(P[go + c], P[bo + c], stats[mo + c], stats[vo + c], rows + so + c, rows + so + w + c);
     }
 }
 
@@ -326,9 +317,9 @@ __global__ __launch_bounds__(256) void k_icnet_highres_wgrad1(const TX *__restri
     }
 }
 
-// raw[o] = sum over split-K groups b = 0 .. G - 1 of part[b][o], fp32, in that order -> fold[o] ([rows + 1][CO]); dK = (raw
-// scale) s[co] for the first `rows` rows, dBeta = raw[rows][co] scale; scale: the one k_icnet_fusion_finish took from the head
-// kernel's lpart
+// The one-layer form of k_icnet_block_finish (ssal_train_icnet_common.h) at run-time widths: raw[o] = sum over split-K groups
+// b = 0 .. G - 1 of part[b][o], fp32, in that order -> fold[o] ([rows + 1][CO]); dK = (raw scale) s[co] for the first `rows`
+// rows, dBeta = raw[rows][co] scale; scale: the one the fusion trainer's finish took from the head kernel's lpart
 __global__ __launch_bounds__(256) void k_icnet_highres_finish(const float *__restrict__ part, int G, int rows, int CO,
                                                               const float *__restrict__ scale_p, const float *__restrict__ sl,
                                                               float *__restrict__ fold, float *__restrict__ gK,
@@ -345,8 +336,7 @@ __global__ __launch_bounds__(256) void k_icnet_highres_finish(const float *__res
     else gB[co] = acc * scale;
 }
 
-// dGamma[co] = ((sum_tap (sum_ci K[tap, ci, co] raw[tap, ci, co], ci ascending, fmaf), taps ascending) - mean raw_beta) rstd scale
-// (k_icnet_fusion_gamma's re-association of sum_p gz (z - mean)).  One workgroup of 64 threads (co).
+// The one-layer form of k_icnet_block_gamma: its 3 x 3 branch at run-time widths.  One workgroup of 64 threads (co).
 __global__ __launch_bounds__(64) void k_icnet_highres_gamma(const float *__restrict__ fold, const float *__restrict__ scale_p,
                                                             const float *__restrict__ K, const float *__restrict__ mean,
                                                             const float *__restrict__ var, int CI, int CO,
@@ -354,17 +344,7 @@ __global__ __launch_bounds__(64) void k_icnet_highres_gamma(const float *__restr
 {
     const int co = threadIdx.x;
     if (co >= CO) return;
-    float sum = 0.0f;
-    for (int tap = 0; tap < 9; ++tap) {
-        float a = 0.0f;
-        for (int ci = 0; ci < CI; ++ci) {
-            const int o = (tap * CI + ci) * CO + co;
-            a = fmaf(K[o], fold[o], a);
-        }
-        sum += a;
-    }
-    const float rbeta = fold[9 * CI * CO + co], rstd = 1.0f / sqrtf(var[co] + 1e-3f);
-    gG[co] = ((sum - mean[co] * rbeta) * rstd) * scale_p[0];
+    gG[co] = icnet_dgamma(icnet_gamma_3x3(K, fold, CI, CO, co), mean[co], var[co], fold[9 * CI * CO + co], scale_p[0]);
 }
 
 // finish + gamma of one layer whose partials lie in ws.part
@@ -375,8 +355,8 @@ static hipError_t highres_fold(int G, int CI, int CO, const float *scale, const 
     hipError_t e;
     {
         ProfScope prof("k_icnet_highres_finish", (double)G * total, 4.0 * (G + 2.0) * total, s);
-        hipLaunchKernelGGL(k_icnet_highres_finish, dim3((total + 255) / 256), dim3(256), 0, s, ws.part, G, 9 * CI, CO, scale, sl,
-                           ws.fold, gK, gB);
+        hipLaunchKernelGGL(k_icnet_highres_finish, dim3(icnet_cdiv(total, 256)), dim3(256), 0, s, ws.part, G, 9 * CI, CO, scale,
+                           sl, ws.fold, gK, gB);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     ProfScope prof("k_icnet_highres_gamma", 2.0 * 9 * CI * CO, 8.0 * total, s);
@@ -400,7 +380,7 @@ hipError_t launch_icnet_highres_grad(const float *c54, const float *c31, const v
     // ---- forward: the pack, then run_trunk's launches of the branch on the weights being trained ----
     {
         ProfScope prof("k_icnet_highres_pack", 0.0, 8.0 * (9 * 32 * 96 + 128), s);
-        hipLaunchKernelGGL(k_icnet_highres_pack, dim3((9 * 32 * 96 + 128 + 255) / 256), dim3(256), 0, s, params, off, stats,
+        hipLaunchKernelGGL(k_icnet_highres_pack, dim3(icnet_cdiv(9 * 32 * 96 + 128, 256)), dim3(256), 0, s, params, off, stats,
                            ws.wt2, ws.wt3, ws.rows);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
@@ -416,16 +396,17 @@ hipError_t launch_icnet_highres_grad(const float *c54, const float *c31, const v
     const float *scale = ws.cascade.fusion.fold + FU_PART;
     // ---- backward ----
     {
-        const long tiles = cdiv_l((long)N * h8 * w8, 64);
+        const long tiles = icnet_cdiv((long)N * h8 * w8, 64);
         ProfScope prof("k_icnet_highres_dproj", 2.0 * pix8 * 128 * 64, 4.0 * pix8 * (128 + 64 + 64), s);
-        hipLaunchKernelGGL(k_icnet_highres_dproj, dim3(capped_grid(tiles, HR_DX_MAX_WG, max_workgroups)), dim3(256), 0, s,
+        hipLaunchKernelGGL(k_icnet_highres_dproj, dim3(icnet_grid(tiles, HR_DX_MAX_WG, max_workgroups)), dim3(256), 0, s,
                            ws.cascade.fusion.g, params + off.cascade + CA_FUSION + FU_KB, ws.cascade.fusion.rows + 256, ws.f3,
                            (long)N * h8 * w8, ws.gz3);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    const long wt3 = (long)N * cdiv_l(h8, HW_TH) * cdiv_l(w8, HW_TW), wt2 = (long)N * cdiv_l(h4, HW_TH) * cdiv_l(w4, HW_TW);
+    const long wt3 = (long)N * icnet_cdiv(h8, HW_TH) * icnet_cdiv(w8, HW_TW);
+    const long wt2 = (long)N * icnet_cdiv(h4, HW_TH) * icnet_cdiv(w4, HW_TW);
     {
-        const int G = (int)capped_grid(wt3, HR_MAX_WG, max_workgroups);
+        const int G = icnet_grid(wt3, HR_MAX_WG, max_workgroups);
         {
             ProfScope prof("k_icnet_highres_wgrad<64>", 2.0 * pix8 * 289 * 64, 4.0 * pix8 * (3 * 64 + 3 * 4 * 32) + 4.0 * G * 289 * 64,
                            s);
@@ -437,14 +418,14 @@ hipError_t launch_icnet_highres_grad(const float *c54, const float *c31, const v
         if (e != hipSuccess) return e;
     }
     {
-        const long tiles = (long)N * cdiv_l(h8, HX_TH) * cdiv_l(w8, HX_TW);
+        const long tiles = (long)N * icnet_cdiv(h8, HX_TH) * icnet_cdiv(w8, HX_TW);
         ProfScope prof("k_icnet_highres_dx<64>", 2.0 * pix8 * 9 * 64 * 32, 4.0 * (pix8 * 64 + 2.0 * pix4 * 32), s);
-        hipLaunchKernelGGL(k_icnet_highres_dx<64>, dim3(capped_grid(tiles, HR_DX_MAX_WG, max_workgroups)), dim3(256), 0, s,
+        hipLaunchKernelGGL(k_icnet_highres_dx<64>, dim3(icnet_grid(tiles, HR_DX_MAX_WG, max_workgroups)), dim3(256), 0, s,
                            ws.gz3, params + off.k3, s3, ws.a2, N, h8, w8, ws.gz2);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     {
-        const int G = (int)capped_grid(wt2, HR_MAX_WG, max_workgroups);
+        const int G = icnet_grid(wt2, HR_MAX_WG, max_workgroups);
         {
             ProfScope prof("k_icnet_highres_wgrad<32>", 2.0 * pix4 * 289 * 32, 4.0 * pix4 * (3 * 32 + 3 * 4 * 32) + 4.0 * G * 289 * 32,
                            s);
@@ -456,13 +437,13 @@ hipError_t launch_icnet_highres_grad(const float *c54, const float *c31, const v
         if (e != hipSuccess) return e;
     }
     {
-        const long tiles = (long)N * cdiv_l(h4, HX_TH) * cdiv_l(w4, HX_TW);
+        const long tiles = (long)N * icnet_cdiv(h4, HX_TH) * icnet_cdiv(w4, HX_TW);
         ProfScope prof("k_icnet_highres_dx<32>", 2.0 * pix4 * 9 * 32 * 32, 4.0 * (pix4 * 32 + 2.0 * pix2 * 32), s);
-        hipLaunchKernelGGL(k_icnet_highres_dx<32>, dim3(capped_grid(tiles, HR_DX_MAX_WG, max_workgroups)), dim3(256), 0, s,
+        hipLaunchKernelGGL(k_icnet_highres_dx<32>, dim3(icnet_grid(tiles, HR_DX_MAX_WG, max_workgroups)), dim3(256), 0, s,
                            ws.gz2, params + off.k2, s2, ws.a1, N, h4, w4, ws.gz1);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    const int G = (int)capped_grid(cdiv_l((long)N * h2 * w2, 256), HR_MAX_WG, max_workgroups);
+    const int G = icnet_grid(icnet_cdiv((long)N * h2 * w2, 256), HR_MAX_WG, max_workgroups);
     {
         ProfScope prof("k_icnet_highres_wgrad1", 2.0 * pix2 * (9 * c_in + 1) * 32,
                        4.0 * pix2 * 32 + (double)N * H * W * c_in * (x_is_u8 ? 1.0 : 4.0) + 4.0 * G * (9 * c_in + 1) * 32, s);
