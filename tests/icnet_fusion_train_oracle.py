@@ -79,9 +79,11 @@ def _tensors(s24, c3, packed, grad=True):
     return (torch.as_tensor(np.asarray(s24, dtype=np.float64)), torch.as_tensor(np.asarray(c3, dtype=np.float64)), W)
 
 
-def loss_and_grad(s24, c3, packed, stats, labels, mask, weight, label_smoothing, sub12_32=None, logits32=None):
+def loss_and_grad(s24, c3, packed, stats, labels, mask, weight, label_smoothing, sub12_32=None, logits32=None, wmask=None):
     """float64 (loss, packed gradient).  With ``sub12_32`` / ``logits32`` the ReLU and the loss are evaluated at those (fp32)
-    values -- the point the GPU evaluates -- and differentiated through the float64 chain."""
+    values -- the point the GPU evaluates -- and differentiated through the float64 chain.  ``wmask`` [N, 2h, 2w, 1]: a weight
+    per pixel of sub12_sum on g = dL/dsub12_sum inside the contraction of the block's six parameter gradients only (0: the
+    pixel is left out of the split-K sum, 2: counted twice) -- the deliberately wrong sums of the grid tests."""
     k = classes_of(packed)
     on, off, w32, c_w = fto.xent_constants(k, weight, label_smoothing)
     s = fto.mask_scale(mask)
@@ -91,6 +93,8 @@ def loss_and_grad(s24, c3, packed, stats, labels, mask, weight, label_smoothing,
     acc_b = x3 @ W[NAMES[3]].reshape(64, 128)
     sa, sb = W[NAMES[1]] / torch.sqrt(va + EPS), W[NAMES[4]] / torch.sqrt(vb + EPS)
     pre = acc_a * sa + (W[NAMES[2]] - ma * sa) + acc_b * sb + (W[NAMES[5]] - mb * sb)
+    if wmask is not None:  # (the block's inputs are constants here: only the parameters see pre's gradient)
+        pre = pre.detach() + torch.as_tensor(np.asarray(wmask, dtype=np.float64)) * (pre - pre.detach())
     if sub12_32 is not None:
         # the value is the fp32 one wherever the unit is alive there, and the unit is dead exactly where fp32 says so
         s32 = torch.as_tensor(np.asarray(sub12_32, dtype=np.float64))

@@ -88,9 +88,11 @@ def _drop_last(a):
     return out
 
 
-def _branch(x, W, bn, at32=(None, None, None), variant=None):
+def _branch(x, W, bn, at32=(None, None, None), variant=None, wmask=None):
     """a_1, a_2, a_3 (float64 torch); ``at32``: the fp32 activations the ReLUs are pinned to.  ``variant``: one of the
-    deliberately wrong backward passes of the discrimination test (the forward values stay right but for "pad")"""
+    deliberately wrong backward passes of the discrimination test (the forward values stay right but for "pad").
+    ``wmask``: {layer index 0..2: [N, Ho, Wo, 1]}, a weight per pixel on gz_l inside the contraction of that layer's kernel,
+    gamma and beta gradients only (0: left out of the split-K sum, 2: counted twice); the data gradient keeps every pixel"""
     acts, a = [], x
     for l, (layer, (mean, var)) in enumerate(zip(LAYERS, bn)):
         kern, gamma, beta = (W["%s.%s" % (layer, s)] for s in ("kernel", "gamma", "beta"))
@@ -103,6 +105,11 @@ def _branch(x, W, bn, at32=(None, None, None), variant=None):
             zk = conv_s2(a.detach(), kern)
             za = conv_s2(a, kern.detach())
             pre = zk * s + (beta - mean * s) + (za - za.detach())
+        if wmask is not None and l in wmask:
+            pw = conv_s2(a.detach(), kern) * s + (beta - mean * s)
+            sd = s.detach()
+            pre = (conv_s2(a, kern.detach()) * sd + (beta.detach() - mean * sd)
+                   + torch.as_tensor(np.asarray(wmask[l], dtype=np.float64)) * (pw - pw.detach()))
         act = ico._pinned_relu(pre, at32[l])
         if variant == "no_mask2" and l == 1:  # a_2's ReLU mask omitted from da_2
             act = pre + (act - pre).detach()
@@ -152,14 +159,14 @@ def _cascade_loss(x54, x31, a3, W, cstats, labels, mask, k, weight, label_smooth
     return fto.pixel_loss(lg, y, mk, w32, c_w, True).sum() * s
 
 
-def loss_and_grad(c54, c31, x, packed, stats, labels, mask, k, weight, label_smoothing, at32=None, variant=None):
+def loss_and_grad(c54, c31, x, packed, stats, labels, mask, k, weight, label_smoothing, at32=None, variant=None, wmask=None):
     """float64 (loss, packed gradient).  ``at32`` = (a_1, a_2, F3, sub24_sum, sub12_sum, logits) in fp32: every ReLU and the loss
     are evaluated at those values -- the point the GPU evaluates."""
     c_in = int(np.shape(x)[-1])
     at32 = (None,) * 6 if at32 is None else at32
     x54, x31, xx, W = _tensors(c54, c31, x, packed, k, c_in)
     bn, cstats = split_stats(stats)
-    a3 = _branch(xx, W, bn, at32[:3], variant)[2]
+    a3 = _branch(xx, W, bn, at32[:3], variant, wmask)[2]
     loss = _cascade_loss(x54, x31, a3, W, cstats, labels, mask, k, weight, label_smoothing, *at32[3:])
     loss.backward()
     return float(loss.detach()), pack({n: W[n].grad.numpy() for n in NAMES})

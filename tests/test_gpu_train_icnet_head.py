@@ -70,13 +70,9 @@ SHAPES = [((1, 1, 1), 0),   # lq 2 x 2: every +1 tap is clamped
 CASES = [(s, mw, k, wl) for s, mw in SHAPES for k in (2, 19, 32) for wl in ((0.0, 0.0), (1.02, 0.1))]
 
 
-@pytest.mark.parametrize("shape,mw,k,wl", CASES)
-def test_gradient_loss_and_determinism(shape, mw, k, wl):
-    """|g - g64| <= kappa 2^-24 C_j for every entry of dKernel and dBias; the loss bit-identical to the forward op on the
-    forward path's logits; two calls give the same bits"""
-    n, h, w = shape
-    weight, ls = wl
-    x, head, labels, mask = _case(1000 + CASES.index((shape, mw, k, wl)), n, h, w, k)
+def _check_gradient(k, x, head, labels, mask, weight, ls, mw):
+    n, h, w, _ = x.shape
+    shape = (n, h, w)
     tr = ICNetHeadTrainer(_shared_net(k), 1e-3, loginverse_scaling=weight, label_smoothing=ls)
     xd = torch.as_tensor(x).cuda()
     loss, gd = tr.gradient_features(xd, labels, mask, params=_params(head, k), max_workgroups=mw)
@@ -102,6 +98,16 @@ def test_gradient_loss_and_determinism(shape, mw, k, wl):
     assert not bad.any(), "%d of %d entries beyond kappa 2^-24 C (first at %d)" % (int(bad.sum()), bad.size,
                                                                                    int(np.argwhere(bad)[0]))
     assert abs(float(loss[0]) - loss64) <= 1e-5 * abs(loss64)
+    return gd
+
+
+@pytest.mark.parametrize("shape,mw,k,wl", CASES)
+def test_gradient_loss_and_determinism(shape, mw, k, wl):
+    """|g - g64| <= kappa 2^-24 C_j for every entry of dKernel and dBias; the loss bit-identical to the forward op on the
+    forward path's logits; two calls give the same bits"""
+    n, h, w = shape
+    x, head, labels, mask = _case(1000 + CASES.index((shape, mw, k, wl)), n, h, w, k)
+    _check_gradient(k, x, head, labels, mask, wl[0], wl[1], mw)
 
 
 def test_adam_three_steps_bit_identical_to_float32_restatement():
