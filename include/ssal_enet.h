@@ -53,7 +53,14 @@ extern "C" {
  *                      is O(2^-24) relative per product).  Same accuracy class as fp32, a different summation: logits differ
  *                      from the default mode by <= ~1e-5, per-pixel confidences by <= 1e-4 (north_star's tolerance), per-image
  *                      scores by <= 1e-6; the max-pool + argmax of both pooling blocks is evaluated in exact fp32 (inside
- *                      Bottleneck2_0's split-operand kernel too), so the pooling indices are bit-identical.  No reference counterpart (the reference computes in fp32 on TensorFlow). */
+ *                      Bottleneck2_0's split-operand kernel too), so the pooling indices are bit-identical.  No reference counterpart (the reference computes in fp32 on TensorFlow).
+ *                      ICNet (include/ssal_icnet.h, the *_arith entries): every convolution the exact path gives to the plain
+ *                      implicit-GEMM kernel k_igemm<NT, 0> -- the 1x1 reduce / increase / projection convolutions, the 3x3
+ *                      convolutions on 64, 128 and 256 channels, conv5_4_k1, conv2_sub1, conv3_sub1, conv3_sub1_proj and
+ *                      conv3_1_sub2_proj: 54 of the 64 convolutions of a forward call -- runs on k_igemm_bf16x3<NT>, and
+ *                      conv2_2 / conv2_3 of a score call on k_bottleneck_bf16x3; the first convolutions, k_conv3x3_c32, both
+ *                      up-sampling forms, the dual (projection-shortcut) launches, the conv6_cls head, pooling and the score
+ *                      kernel stay exact. */
 #define SSAL_ARITH_F32     0
 #define SSAL_ARITH_BF16X3  1
 

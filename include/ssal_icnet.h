@@ -311,6 +311,40 @@ int ssal_upscore_logits_nhwc(const float *lq_dev, int n, int h, int w, int class
                              double *scores_dev, uint8_t *label_dev, uint8_t *mask_dev, float *conf_dev,
                              void *ws_dev, int64_t ws_bytes, void *stream);
 
+/* ---- Opt-in arithmetic (SSAL_ARITH_* of include/ssal_enet.h) ----
+ * arithmetic == SSAL_ARITH_F32 is exactly the entry without the suffix: same launches, same bits.  SSAL_ARITH_BF16X3 runs
+ * every convolution that the exact path gives to the plain implicit-GEMM kernel (k_igemm<NT, 0>) on the split-operand kernel
+ * k_igemm_bf16x3<NT> (csrc/ssal_icnet_bf16x3.hip) and, in the score entry, conv2_2 / conv2_3 on ENet's bf16x3 regular-block
+ * kernel; the first convolutions, k_conv3x3_c32, both up-sampling forms, the projection-shortcut (dual) launches, the
+ * conv6_cls head, pooling and the score kernel stay exact.  Not bit-identical to the default mode.  An unknown mode is
+ * SSAL_EINVAL, judged before any device work.  x_dev is float32 (x_is_u8 == 0) or the decoded uint8 frame.  Workspaces are
+ * those of the plain entries. */
+int ssal_icnet_forward_nhwc_arith(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w, int arithmetic,
+                                  float *logits_dev, void *ws_dev, int64_t ws_bytes, void *stream);
+int ssal_icnet_score_nhwc_arith(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w, int measure,
+                                float threshold, int arithmetic, double *scores_dev, uint8_t *label_dev, uint8_t *mask_dev,
+                                float *conf_dev, void *ws_dev, int64_t ws_bytes, void *stream);
+/* ssal_conv_bn_act with an arithmetic mode: the per-operator test hook of k_igemm_bf16x3.  The workspace of the bf16x3 mode
+ * also holds the pre-split kernel (1.5x the fp32 kernel's bytes, output channels padded to 32). */
+int64_t ssal_conv_bn_workspace_bytes_arith(int kh, int kw, int cin, int cout, int arithmetic);
+int ssal_conv_bn_act_arith(const float *x_dev, int n, int h, int w, int cin, const float *kernel_host, int kh, int kw,
+                           int cout, int stride, int dilation, const float *mean_host, const float *var_host,
+                           const float *gamma_host, const float *beta_host, const float *bias_host, const float *res_dev,
+                           int relu, int upsample2x, float *y_dev, void *ws_dev, int64_t ws_bytes, void *stream,
+                           int arithmetic);
+/* Dry query (no device, no launch; cf. ssal_debug_layer_dispatch): which kernel and which column-tile width NT the
+ * convolution launcher picks for x [n,h,w,cin] (up2 != 0: the conv runs on the 2x up-sampled tensor), with the knobs and the
+ * launch concurrency of the calling thread as they are now.  nt_out: 1, 2 or 4 for the implicit-GEMM kernels, 0 otherwise.
+ * SSAL_EINVAL: a shape no kernel takes, an unknown mode, a NULL output. */
+#define SSAL_ICNET_KERNEL_IGEMM             0  /* k_igemm<NT, 0> (either LDS-buffer count) */
+#define SSAL_ICNET_KERNEL_IGEMM_UP2         1  /* k_igemm<NT, 1 | 2> */
+#define SSAL_ICNET_KERNEL_CONV1X1_UP2_C128  2  /* k_conv1x1_up2_c128 */
+#define SSAL_ICNET_KERNEL_CONV3X3_C32       3  /* k_conv3x3_c32 */
+#define SSAL_ICNET_KERNEL_IGEMM_BF16X3      4  /* k_igemm_bf16x3<NT> */
+#define SSAL_ICNET_KERNEL_CONV_FIRST        5  /* k_conv_first (cin 1, 3 or 4) */
+int ssal_icnet_debug_conv_dispatch(int n, int h, int w, int cin, int cout, int kh, int kw, int stride, int dil, int up2,
+                                   int has_res, int arithmetic, int *kernel_out, int *nt_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,6 +155,8 @@ PROTOTYPES = {
     "ssal_icnet_forward_nhwc_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i64, _vp]),
     "ssal_icnet_score_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "ssal_icnet_score_nhwc_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_icnet_forward_nhwc_arith": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i64, _vp]),
+    "ssal_icnet_score_nhwc_arith": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "ssal_icnet_regions_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
     "ssal_icnet_score_regions_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "ssal_icnet_eval_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
@@ -166,6 +168,10 @@ PROTOTYPES = {
     "ssal_conv_bn_workspace_bytes": (_i64, [_i, _i, _i, _i]),
     "ssal_conv_bn_act": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i,
                               _vp, _vp, _i64, _vp]),
+    "ssal_conv_bn_workspace_bytes_arith": (_i64, [_i, _i, _i, _i, _i]),
+    "ssal_conv_bn_act_arith": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i,
+                                    _vp, _vp, _i64, _vp, _i]),
+    "ssal_icnet_debug_conv_dispatch": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _c.POINTER(_i), _c.POINTER(_i)]),
     "ssal_max_pool_3x3_s2": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "ssal_pyramid_pooling": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i64, _vp]),
     "ssal_upscore_workspace_bytes": (_i64, [_i, _i, _i]),
@@ -574,6 +580,21 @@ def get_knobs():
 
 LAYER_KINDS = {"initial": 0, "regular": 1, "down": 2, "up": 3}           # SSAL_LAYER_*
 DISPATCH_NAMES = {0: "generic", 1: "fused", 2: "fused_bf16x3"}        # SSAL_DISPATCH_*
+
+
+# include/ssal_icnet.h SSAL_ICNET_KERNEL_*
+ICNET_CONV_KERNELS = ("k_igemm", "k_igemm_up2", "k_conv1x1_up2_c128", "k_conv3x3_c32", "k_igemm_bf16x3", "k_conv_first")
+
+
+def icnet_conv_dispatch(n, h, w, cin, cout, k, stride=1, dilation=1, upsample2x=False, residual=False, arithmetic="f32"):
+    """host-only: ``(kernel name, NT)`` the ICNet convolution launcher picks for x [n, h, w, cin] and a k x k kernel
+    (include/ssal_icnet.h: ssal_icnet_debug_conv_dispatch; NT = 0 for kernels without a column-tile width).  Needs no GPU."""
+    kh, kw = (k, k) if isinstance(k, int) else k
+    kern, nt = _c.c_int(-1), _c.c_int(-1)
+    check(lib().ssal_icnet_debug_conv_dispatch(int(n), int(h), int(w), int(cin), int(cout), int(kh), int(kw), int(stride),
+                                               int(dilation), int(bool(upsample2x)), int(bool(residual)),
+                                               arithmetic_code(arithmetic), _c.byref(kern), _c.byref(nt)))
+    return ICNET_CONV_KERNELS[kern.value], nt.value
 
 
 def layer_dispatch(kind, cin, cout, f, asym, h, w, arithmetic="f32"):

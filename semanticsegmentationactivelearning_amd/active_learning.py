@@ -209,11 +209,14 @@ def pad_to_length(index, score, length):
 
 
 def _check_arithmetic(net_call, arithmetic):
-    """ValueError, before any GPU work, for an unknown mode or a non-default one the model's call does not take (ICNet has
-    no opt-in arithmetic: its score / evaluate take no ``arithmetic`` argument)"""
+    """ValueError, before any GPU work, for an unknown mode or a non-default one the model's call does not take in these
+    loops (ICNet: ``evaluate`` / ``score_regions`` take no ``arithmetic`` argument, and ``ICNet.score``'s opt-in mode is offered
+    on direct calls and ``inference.predict`` only -- ``ICNet.loop_arithmetics``)"""
     import inspect
     _lib.arithmetic_code(arithmetic)
-    if arithmetic != "f32" and "arithmetic" not in inspect.signature(net_call).parameters:
+    offered = getattr(net_call.__self__, "loop_arithmetics", None)
+    if arithmetic != "f32" and ("arithmetic" not in inspect.signature(net_call).parameters
+                                or (offered is not None and arithmetic not in offered)):
         raise ValueError("arithmetic=%r: %s has no such mode (only 'f32')" % (arithmetic, type(net_call.__self__).__name__))
 
 

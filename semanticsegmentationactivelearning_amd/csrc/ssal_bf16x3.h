@@ -1,5 +1,6 @@
-// ssal_bf16x3.h -- kernel packing of the opt-in SSAL_ARITH_BF16X3 mode (ssal_bottleneck_bf16x3.hip), shared by the commit
-// step (host: ssal_api.hip) and the kernels.  A layer's three kernels are pre-split into bf16 triples (w = w1 + w2 + w3
+// ssal_bf16x3.h -- kernel packing of the opt-in SSAL_ARITH_BF16X3 mode (ssal_bottleneck_bf16x3.hip, ssal_icnet_bf16x3.hip),
+// shared by the commit steps (host: ssal_api.hip, ssal_icnet_api.hip) and the kernels, and (device builds only, at the end)
+// the mode's activation split and six-product step.  A layer's three kernels are pre-split into bf16 triples (w = w1 + w2 + w3
 // exactly, by truncation) and laid out per K = 16 chunk in MFMA operand order: 16-byte UNITS, [chunk][term][lane], where
 // operand lane (j = lane & 31, h = lane >> 5) of a v_mfma_f32_32x32x16_bf16 holds k = 8 h + i, i = 0..7, of row / column j.
 //   chunks 0 .. 7                      projection   Wp[ci = 16 c + 8 h + i][co = j]
@@ -7,6 +8,9 @@
 //                                      (asymmetric block: taps 0..4 = the (5,1) kernel, 5..9 = the (1,5) kernel)
 //   then 8 chunks                      expansion    We[ci = 16 c + 8 h + i][co = 32 nt + j], chunk = 2 nt + c
 #pragma once
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+#endif
 #include <stdint.h>
 #include <string.h>
 
@@ -120,6 +124,79 @@ inline std::vector<float> pack_up_layer(const float *wp, const float *wr, const 
     for (int nt = 0; nt < 2; ++nt) pack_chunk(out, [&](int h, int i, int j) { return we[(8 * h + i) * 64 + 32 * nt + j]; });
     return out;
 }
+
+// One convolution of ICNet's implicit GEMM (ssal_icnet_bf16x3.hip: k_igemm_bf16x3): kernel [KH*KW][Cin][Cout] (HWIO) ->
+// [tap][Cin/16][CoutP/32] chunks, chunk (tap, c, nt) = W[tap][ci = 16 c + 8 h + i][co = 32 nt + j]; output channels are
+// zero-padded to CoutP = Cout rounded up to 32 (the split of 0 is (0, 0, 0)).  1.5x the bytes of the fp32 kernel.
+inline size_t igemm_units(int KH, int KW, int Cin, int Cout)
+{
+    return (size_t)KH * KW * (Cin / 16) * ((Cout + 31) / 32) * CHUNK_UNITS;
+}
+inline std::vector<float> pack_igemm(const float *w, int KH, int KW, int Cin, int Cout)
+{
+    std::vector<float> out;
+    out.reserve(igemm_units(KH, KW, Cin, Cout) * 4);
+    const int nb32 = (Cout + 31) / 32;
+    for (int tap = 0; tap < KH * KW; ++tap)
+        for (int c = 0; c < Cin / 16; ++c)
+            for (int nt = 0; nt < nb32; ++nt)
+                pack_chunk(out, [&](int h, int i, int j) {
+                    const int co = 32 * nt + j;
+                    return co < Cout ? w[((size_t)tap * Cin + 16 * c + 8 * h + i) * Cout + co] : 0.0f;
+                });
+    return out;
+}
+
+#ifdef __HIPCC__
+// ---- device side: the activation split and the six-product step, shared by every kernel of the mode ----
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float acc16 __attribute__((ext_vector_type(16)));  // == ssal::f32x16 (ssal_mfma.h)
+
+struct Split3 {
+    uint4 t1, t2, t3;  // 8 values each: the leading bf16, the bf16 of the remainder, the bf16 of what remains after that
+};
+
+__device__ __forceinline__ unsigned pack_hi(unsigned lo, unsigned hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302u); }
+
+// x = h1 + h2 + h3 exactly; h1, h2 are fp32 values with 16 zero low bits, h3 fits 8 significant bits (its low 16 bits are 0)
+__device__ __forceinline__ void split1(float x, unsigned &h1, unsigned &h2, unsigned &h3)
+{
+    h1 = __float_as_uint(x) & 0xffff0000u;
+    const float r1 = x - __uint_as_float(h1);
+    h2 = __float_as_uint(r1) & 0xffff0000u;
+    const float r2 = r1 - __uint_as_float(h2);
+    h3 = __float_as_uint(r2);
+}
+
+__device__ __forceinline__ Split3 split_pack8(const float (&v)[8])
+{
+    unsigned a[8], b[8], c[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) split1(v[k], a[k], b[k], c[k]);
+    Split3 s;
+    s.t1 = make_uint4(pack_hi(a[0], a[1]), pack_hi(a[2], a[3]), pack_hi(a[4], a[5]), pack_hi(a[6], a[7]));
+    s.t2 = make_uint4(pack_hi(b[0], b[1]), pack_hi(b[2], b[3]), pack_hi(b[4], b[5]), pack_hi(b[6], b[7]));
+    s.t3 = make_uint4(pack_hi(c[0], c[1]), pack_hi(c[2], c[3]), pack_hi(c[4], c[5]), pack_hi(c[6], c[7]));
+    return s;
+}
+
+__device__ __forceinline__ acc16 mfma_bf(uint4 a, uint4 b, acc16 c)
+{
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+
+// one K = 16 step: the six leading cross products, small terms first
+__device__ __forceinline__ acc16 mfma6(const Split3 &a, const Split3 &b, acc16 c)
+{
+    c = mfma_bf(a.t3, b.t1, c);
+    c = mfma_bf(a.t2, b.t2, c);
+    c = mfma_bf(a.t1, b.t3, c);
+    c = mfma_bf(a.t2, b.t1, c);
+    c = mfma_bf(a.t1, b.t2, c);
+    c = mfma_bf(a.t1, b.t1, c);
+    return c;
+}
+#endif  // __HIPCC__
 
 }  // namespace bf16x3
 }  // namespace ssal

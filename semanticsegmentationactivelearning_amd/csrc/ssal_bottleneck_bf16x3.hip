@@ -39,52 +39,13 @@ constexpr int F = 32, C = 128;
 constexpr int TW = 16, TH = 8;
 constexpr int PS = 208;  // bytes per P slot: 3 terms x 32 bf16 = 192 B, padded to 208 (16-byte aligned rows, 52-dword pitch)
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-struct Split3 {
-    uint4 t1, t2, t3;  // 8 values each: the leading bf16, the bf16 of the remainder, the bf16 of what remains after that
-};
-
-__device__ __forceinline__ unsigned pack_hi(unsigned lo, unsigned hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302u); }
-
-// x = h1 + h2 + h3 exactly; h1, h2 are fp32 values with 16 zero low bits, h3 fits 8 significant bits (its low 16 bits are 0)
-__device__ __forceinline__ void split1(float x, unsigned &h1, unsigned &h2, unsigned &h3)
-{
-    h1 = __float_as_uint(x) & 0xffff0000u;
-    const float r1 = x - __uint_as_float(h1);
-    h2 = __float_as_uint(r1) & 0xffff0000u;
-    const float r2 = r1 - __uint_as_float(h2);
-    h3 = __float_as_uint(r2);
-}
-
-__device__ __forceinline__ Split3 split_pack8(const float (&v)[8])
-{
-    unsigned a[8], b[8], c[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) split1(v[k], a[k], b[k], c[k]);
-    Split3 s;
-    s.t1 = make_uint4(pack_hi(a[0], a[1]), pack_hi(a[2], a[3]), pack_hi(a[4], a[5]), pack_hi(a[6], a[7]));
-    s.t2 = make_uint4(pack_hi(b[0], b[1]), pack_hi(b[2], b[3]), pack_hi(b[4], b[5]), pack_hi(b[6], b[7]));
-    s.t3 = make_uint4(pack_hi(c[0], c[1]), pack_hi(c[2], c[3]), pack_hi(c[4], c[5]), pack_hi(c[6], c[7]));
-    return s;
-}
-
-__device__ __forceinline__ f32x16 mfma_bf(uint4 a, uint4 b, f32x16 c)
-{
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-// one K = 16 step: the six leading cross products, small terms first
-__device__ __forceinline__ f32x16 mfma6(const Split3 &a, const Split3 &b, f32x16 c)
-{
-    c = mfma_bf(a.t3, b.t1, c);
-    c = mfma_bf(a.t2, b.t2, c);
-    c = mfma_bf(a.t1, b.t3, c);
-    c = mfma_bf(a.t2, b.t1, c);
-    c = mfma_bf(a.t1, b.t2, c);
-    c = mfma_bf(a.t1, b.t1, c);
-    return c;
-}
+// the activation split (split1, split_pack8) and the six-product step (mfma6): ssal_bf16x3.h, shared with ICNet's kernel
+using bf16x3::Split3;
+using bf16x3::pack_hi;
+using bf16x3::split1;
+using bf16x3::split_pack8;
+using bf16x3::mfma_bf;
+using bf16x3::mfma6;
 
 // packed kernel chunk `unit` (16-byte units, bf16x3::CHUNK_UNITS per chunk): [term][lane]
 __device__ __forceinline__ Split3 load_w(const rsrc_t &rs, int unit_off, int lane)

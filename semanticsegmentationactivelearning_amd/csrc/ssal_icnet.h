@@ -48,9 +48,21 @@ bool igemm_supported(int Cin, int Cout, int KH, int KW);
 hipError_t launch_igemm_dual(const float *x, int N, int H, int W, int Cin, const float *wt, int Cout, const float *scale,
                              const float *shift, const float *xs, int Cin_s, int stride_s, const float *wt_s,
                              const float *scale_s, const float *shift_s, bool relu, float *y, hipStream_t s);
+// arithmetic (SSAL_ARITH_* of include/ssal_enet.h; 0 = exact fp32): in the bf16x3 mode a convolution that the exact path
+// gives to the plain k_igemm<NT, 0> runs on k_igemm_bf16x3<NT> (ssal_icnet_bf16x3.hip) and reads wt_bf16x3 = the kernel as
+// bf16x3::pack_igemm lays it out; every other form stays exact and reads wt
 hipError_t launch_igemm(const float *x, int N, int H, int W, int Cin, const float *wt, int KH, int KW, int Cout,
                         int stride, int dil, const float *scale, const float *shift, const float *res, bool relu,
-                        bool up2, float *y, hipStream_t s);
+                        bool up2, float *y, hipStream_t s, int arithmetic = 0, const void *wt_bf16x3 = nullptr);
+// the launcher's choice without a launch (values = SSAL_ICNET_KERNEL_* of include/ssal_icnet.h); nt = 0 where no NT exists
+enum IgemmKernel { IGK_IGEMM = 0, IGK_IGEMM_UP2 = 1, IGK_CONV1X1_UP2_C128 = 2, IGK_CONV3X3_C32 = 3, IGK_IGEMM_BF16X3 = 4 };
+struct IgemmPlan {
+    int kernel, nt;
+};
+hipError_t igemm_plan(int N, int H, int W, int Cin, int KH, int KW, int Cout, int stride, int dil, bool has_res, bool up2,
+                      int arithmetic, IgemmPlan *plan);
+// k_igemm_bf16x3<NT> on launch_igemm's arguments (tile counts filled in for NT); packed: bf16x3::pack_igemm
+hipError_t launch_igemm_bf16x3(const IgemmArgs &a, int NT, const void *packed, int grid, hipStream_t s);
 
 // first convolution of a branch: 3x3 / stride 2 / SAME on a 1-, 3- or 4-channel image -> 32 channels, BN, ReLU.
 // sub = 1: plain;  sub = 2: the conv runs on resize_bilinear(x, H/2, W/2) (ICNET_SPEC data_sub2), which at the exact

@@ -2,6 +2,8 @@
 // sequencing of ICNET_SPEC.md.  Host C++ only; no torch types.  gfx950 (MI355X) only.
 #include "../../include/ssal_enet.h"
 #include "../../include/ssal_icnet.h"
+#include "ssal_bf16x3.h"
+#include "ssal_bottleneck_args.h"
 #include "ssal_confusion.h"
 #include "ssal_host.h"
 #include "ssal_icnet.h"
@@ -86,6 +88,8 @@ struct ConvDev {
     const float *shift = nullptr;  // [CoutP]
     const float *w_hwio = nullptr; // plain HWIO copy: only the layers of the blocks in fused_bneck() (else NULL)
     const float *wq = nullptr;     // on the *_1x1_reduce layer of a fused_bneck() block: its three kernels in quad layout (bnk_quad_layout)
+    const float *w3 = nullptr;     // cin % 32 == 0: the kernel pre-split for k_igemm_bf16x3 (bf16x3::pack_igemm), next to w
+    const float *pk3 = nullptr;    // on the *_1x1_reduce layer of a fused_bneck() block: bf16x3::pack_layer of its three kernels
 };
 
 // identity-shortcut bottlenecks with ENet's stage-2 shape (128 -> 32 -> 3x3 -> 128 on the 1/8-resolution map): the score
@@ -222,11 +226,11 @@ int check_dims(const ssal_icnet *net, int n, int h, int w)
 
 // conv -> BN -> [+res] -> [relu] on the matrix cores
 hipError_t run_conv(const ssal_icnet *net, const std::string &name, const float *x, int n, int h, int w,
-                    const float *res, bool relu, bool up2, float *y, hipStream_t s)
+                    const float *res, bool relu, bool up2, float *y, hipStream_t s, int arith = SSAL_ARITH_F32)
 {
     const ConvDev &c = net->convs.at(name);
     return launch_igemm(x, n, h, w, c.spec.cin, c.w, c.spec.k, c.spec.k, c.spec.cout, c.spec.stride, c.spec.dil,
-                        c.scale, c.shift, res, relu, up2, y, s);
+                        c.scale, c.shift, res, relu, up2, y, s, arith, c.w3);
 }
 
 // runs everything up to the 1/4-resolution class logits (ICNET_SPEC conv6_cls)
@@ -252,9 +256,11 @@ struct Grp {
 // both fusion blocks; every fused launch above writes those three: none of them is swallowed)
 // highres = false (with cascade = false): the high-resolution branch is left out too -- only the two backbone branches run
 // (the high-resolution trainer runs conv1_sub1 .. conv3_sub1 on the weights it trains)
+// arith: SSAL_ARITH_BF16X3 hands the mode to every run_conv (launch_igemm keeps what has no split kernel exact) and runs the
+// fused blocks on ENet's bf16x3 regular-block kernel; the training, evaluate and regions entries pass the default
 hipError_t run_trunk(const ssal_icnet *net, std::vector<Grp> &grp, bool x_is_u8, int h, int w, bool fused,
                      std::set<std::string> *written = nullptr, bool head = true, bool fusion = true, bool cascade = true,
-                     bool highres = true)
+                     bool highres = true, int arith = SSAL_ARITH_F32)
 {
     const bool dry = written != nullptr;
 #define OUT(name) do { if (dry) written->insert(name); } while (0)
@@ -278,11 +284,11 @@ hipError_t run_trunk(const ssal_icnet *net, std::vector<Grp> &grp, bool x_is_u8,
         OUT("conv1_1_3x3_s2");
         OUT("conv1_2_3x3");
         EACH(launch_conv_first(q.x, x_is_u8, q.n, h, w, net->c_in, 2, c.w, c.scale, c.shift, q.A("conv1_1_3x3_s2"), q.s));
-        EACH(run_conv(net, "conv1_2_3x3", q.A("conv1_1_3x3_s2"), q.n, h / 4, w / 4, nullptr, true, false, q.A("conv1_2_3x3"), q.s));
+        EACH(run_conv(net, "conv1_2_3x3", q.A("conv1_1_3x3_s2"), q.n, h / 4, w / 4, nullptr, true, false, q.A("conv1_2_3x3"), q.s, arith));
     }
     OUT("conv1_3_3x3");
     OUT("pool1_3x3_s2");
-    EACH(run_conv(net, "conv1_3_3x3", q.A("conv1_2_3x3"), q.n, h / 4, w / 4, nullptr, true, false, q.A("conv1_3_3x3"), q.s));
+    EACH(run_conv(net, "conv1_3_3x3", q.A("conv1_2_3x3"), q.n, h / 4, w / 4, nullptr, true, false, q.A("conv1_3_3x3"), q.s, arith));
     EACH(launch_maxpool3x3_s2(q.A("conv1_3_3x3"), q.n, h / 4, w / 4, 64, q.A("pool1_3x3_s2"), q.s));
     std::string cur = "pool1_3x3_s2";
     int ch = h / 8, cw = w / 8;
@@ -306,6 +312,21 @@ hipError_t run_trunk(const ssal_icnet *net, std::vector<Grp> &grp, bool x_is_u8,
             const ConvDev &r = net->convs.at(nm + "_1x1_reduce"), &c3 = net->convs.at(nm + "_3x3"),
                           &inc = net->convs.at(nm + "_1x1_increase");
             OUT(nm);
+            if (arith == SSAL_ARITH_BF16X3 && r.pk3 && bottleneck_bf16x3_fits(ch, cw)) {  // opt-in: NOT bit-identical
+                BnkArgs ba;
+                memset(&ba, 0, sizeof(ba));
+                ba.wp = r.w_hwio; ba.ps = r.scale; ba.pt = r.shift; ba.pa = net->zeros128;
+                ba.wc = c3.w_hwio; ba.cs = c3.scale; ba.ct = c3.shift; ba.ca = net->zeros128;
+                ba.we = inc.w_hwio; ba.es = inc.scale; ba.et = inc.shift; ba.ra = net->zeros128;
+                ba.H = ch; ba.W = cw; ba.dil = b.dil;
+                for (Grp & q : grp) {
+                    if (dry) break;
+                    ba.x = q.A(cur); ba.y = q.A(nm); ba.N = q.n;
+                    HIP_RET(launch_bottleneck_bf16x3(ba, r.pk3, q.s));
+                }
+                cur = nm;
+                continue;
+            }
             EACH(launch_bottleneck_mfma(q.A(cur), q.A(nm), q.n, ch, cw, b.cin, b.dil, r.w_hwio, r.scale, r.shift,
                                         net->zeros128, c3.w_hwio, nullptr, c3.scale, c3.shift, net->zeros128, inc.w_hwio,
                                         inc.scale, inc.shift, net->zeros128, q.s, r.wq));
@@ -318,20 +339,20 @@ hipError_t run_trunk(const ssal_icnet *net, std::vector<Grp> &grp, bool x_is_u8,
         const bool dual = b.proj && fused && ssal::mfma_family() && ssal::knobs().ic_dual;
         if (b.proj && !dual) {
             OUT(nm + "_1x1_proj");
-            EACH(run_conv(net, nm + "_1x1_proj", q.A(cur), q.n, ch, cw, nullptr, false, false, q.A(nm + "_1x1_proj"), q.s));
+            EACH(run_conv(net, nm + "_1x1_proj", q.A(cur), q.n, ch, cw, nullptr, false, false, q.A(nm + "_1x1_proj"), q.s, arith));
             shortcut = nm + "_1x1_proj";
         }
         OUT(nm + "_1x1_reduce");
         OUT(nm + "_3x3");
         OUT(nm);
-        EACH(run_conv(net, nm + "_1x1_reduce", q.A(cur), q.n, ch, cw, nullptr, true, false, q.A(nm + "_1x1_reduce"), q.s));
-        EACH(run_conv(net, nm + "_3x3", q.A(nm + "_1x1_reduce"), q.n, oh, ow, nullptr, true, false, q.A(nm + "_3x3"), q.s));
+        EACH(run_conv(net, nm + "_1x1_reduce", q.A(cur), q.n, ch, cw, nullptr, true, false, q.A(nm + "_1x1_reduce"), q.s, arith));
+        EACH(run_conv(net, nm + "_3x3", q.A(nm + "_1x1_reduce"), q.n, oh, ow, nullptr, true, false, q.A(nm + "_3x3"), q.s, arith));
         if (dual) {
             const ConvDev &ci_ = net->convs.at(nm + "_1x1_increase"), &cp = net->convs.at(nm + "_1x1_proj");
             EACH(launch_igemm_dual(q.A(nm + "_3x3"), q.n, oh, ow, ci_.spec.cin, ci_.w, ci_.spec.cout, ci_.scale, ci_.shift,
                                    q.A(cur), cp.spec.cin, b.stride, cp.w, cp.scale, cp.shift, true, q.A(nm), q.s));
         } else {
-            EACH(run_conv(net, nm + "_1x1_increase", q.A(nm + "_3x3"), q.n, oh, ow, q.A(shortcut), true, false, q.A(nm), q.s));
+            EACH(run_conv(net, nm + "_1x1_increase", q.A(nm + "_3x3"), q.n, oh, ow, q.A(shortcut), true, false, q.A(nm), q.s, arith));
         }
         cur = nm;
         ch = oh;
@@ -341,7 +362,7 @@ hipError_t run_trunk(const ssal_icnet *net, std::vector<Grp> &grp, bool x_is_u8,
     OUT("conv5_3_sum");
     OUT("conv5_4_k1");
     EACH(launch_ppm(q.A(cur), q.n, ch, cw, 1024, q.W.pooled, q.A("conv5_3_sum"), q.s));
-    EACH(run_conv(net, "conv5_4_k1", q.A("conv5_3_sum"), q.n, ch, cw, nullptr, true, false, q.A("conv5_4_k1"), q.s));
+    EACH(run_conv(net, "conv5_4_k1", q.A("conv5_3_sum"), q.n, ch, cw, nullptr, true, false, q.A("conv5_4_k1"), q.s, arith));
     // ---- high-resolution branch (section 3) ----
     if (!highres) return hipSuccess;
     if ((front & 1) && front2_supported(h, w, net->c_in, 1, 2)) {
@@ -354,35 +375,35 @@ hipError_t run_trunk(const ssal_icnet *net, std::vector<Grp> &grp, bool x_is_u8,
         OUT("conv1_sub1");
         OUT("conv2_sub1");
         EACH(launch_conv_first(q.x, x_is_u8, q.n, h, w, net->c_in, 1, c.w, c.scale, c.shift, q.A("conv1_sub1"), q.s));
-        EACH(run_conv(net, "conv2_sub1", q.A("conv1_sub1"), q.n, h / 2, w / 2, nullptr, true, false, q.A("conv2_sub1"), q.s));
+        EACH(run_conv(net, "conv2_sub1", q.A("conv1_sub1"), q.n, h / 2, w / 2, nullptr, true, false, q.A("conv2_sub1"), q.s, arith));
     }
     OUT("conv3_sub1");
     if (cascade) for (const char *nm_ : {"conv3_1_sub2_proj", "sub24_sum"}) OUT(nm_);
     if (fusion) for (const char *nm_ : {"conv3_sub1_proj", "sub12_sum"}) OUT(nm_);
     if (head) OUT("conv6_cls");
-    EACH(run_conv(net, "conv3_sub1", q.A("conv2_sub1"), q.n, h / 4, w / 4, nullptr, true, false, q.A("conv3_sub1"), q.s));
+    EACH(run_conv(net, "conv3_sub1", q.A("conv2_sub1"), q.n, h / 4, w / 4, nullptr, true, false, q.A("conv3_sub1"), q.s, arith));
     // ---- cascade feature fusion (section 4): the 2x interpolations are evaluated inside the dilated convs ----
     if (cascade) {
         EACH(run_conv(net, "conv3_1_sub2_proj", q.A("conv3_1"), q.n, h / 16, w / 16, nullptr, false, false,
-                      q.A("conv3_1_sub2_proj"), q.s));
+                      q.A("conv3_1_sub2_proj"), q.s, arith));
         EACH(run_conv(net, "conv_sub4", q.A("conv5_4_k1"), q.n, h / 32, w / 32, q.A("conv3_1_sub2_proj"), true, true,
-                      q.A("sub24_sum"), q.s));
+                      q.A("sub24_sum"), q.s, arith));
     }
     if (fusion) {
         EACH(run_conv(net, "conv3_sub1_proj", q.A("conv3_sub1"), q.n, h / 8, w / 8, nullptr, false, false,
-                      q.A("conv3_sub1_proj"), q.s));
+                      q.A("conv3_sub1_proj"), q.s, arith));
         EACH(run_conv(net, "conv_sub2", q.A("sub24_sum"), q.n, h / 16, w / 16, q.A("conv3_sub1_proj"), true, true,
-                      q.A("sub12_sum"), q.s));
+                      q.A("sub12_sum"), q.s, arith));
     }
     // sub12_sum_interp (2x) + conv6_cls (1x1, bias)
-    if (head) EACH(run_conv(net, "conv6_cls", q.A("sub12_sum"), q.n, h / 8, w / 8, nullptr, false, true, q.A("conv6_cls"), q.s));
+    if (head) EACH(run_conv(net, "conv6_cls", q.A("sub12_sum"), q.n, h / 8, w / 8, nullptr, false, true, q.A("conv6_cls"), q.s, arith));
 #undef EACH
 #undef OUT
     return hipSuccess;
 }
 
 int forward_any(ssal_icnet *net, const void *x_dev, bool u8, int n, int h, int w, float *logits_dev, void *ws_dev,
-                int64_t ws_bytes, void *stream)
+                int64_t ws_bytes, void *stream, int arith = SSAL_ARITH_F32)
 {
     int rc = check_dims(net, n, h, w);
     if (rc) return rc;
@@ -392,7 +413,7 @@ int forward_any(ssal_icnet *net, const void *x_dev, bool u8, int n, int h, int w
     hipStream_t s = (hipStream_t)stream;
     std::vector<Grp> one(1);
     one[0] = {W, x_dev, n, s};
-    HIP_TRY(run_trunk(net, one, u8, h, w, false));
+    HIP_TRY(run_trunk(net, one, u8, h, w, false, nullptr, true, true, true, true, arith));
     HIP_TRY(launch_resize_bilinear(W.act.at("conv6_cls"), n, h / 4, w / 4, net->classes, h, w, logits_dev, s));
     return SSAL_OK;
 }
@@ -400,7 +421,8 @@ int forward_any(ssal_icnet *net, const void *x_dev, bool u8, int n, int h, int w
 // The fused trunk of a score-type call (ranking: score_any; validation: eval_any) up to conv6_cls, then tail(chain, first
 // image of the chain) on every chain's stream, then the join: one schedule, one set of knobs for both passes.
 template <class Tail>
-int run_scored(ssal_icnet *net, const void *x_dev, bool u8, int n, int h, int w, const IcWorkspace &W, hipStream_t s, Tail tail)
+int run_scored(ssal_icnet *net, const void *x_dev, bool u8, int n, int h, int w, const IcWorkspace &W, hipStream_t s, Tail tail,
+               int arith = SSAL_ARITH_F32)
 {
     // image-group schedule (same knob and same reasoning as ENet's run_net, ssal_api.hip): the batch runs as G chains of
     // ~n / G images on library-owned side streams, forked from / joined into the caller's stream with events
@@ -427,7 +449,7 @@ int run_scored(ssal_icnet *net, const void *x_dev, bool u8, int n, int h, int w,
         if (G > 1) q.s = cs.side[g];
     }
     set_launch_concurrency(G);
-    const hipError_t trunk_rc = run_trunk(net, grp, u8, h, w, true);
+    const hipError_t trunk_rc = run_trunk(net, grp, u8, h, w, true, nullptr, true, true, true, true, arith);
     set_launch_concurrency(1);
     HIP_TRY(trunk_rc);
     for (int g = 0; g < G; ++g) HIP_TRY(tail(grp[g], first[g]));
@@ -437,7 +459,7 @@ int run_scored(ssal_icnet *net, const void *x_dev, bool u8, int n, int h, int w,
 
 int score_any(ssal_icnet *net, const void *x_dev, bool u8, int n, int h, int w, int measure, float threshold,
               double *scores_dev, uint8_t *label_dev, uint8_t *mask_dev, float *conf_dev, void *ws_dev,
-              int64_t ws_bytes, void *stream)
+              int64_t ws_bytes, void *stream, int arith = SSAL_ARITH_F32)
 {
     int rc = check_dims(net, n, h, w);
     if (rc) return rc;
@@ -453,7 +475,7 @@ int score_any(ssal_icnet *net, const void *x_dev, bool u8, int n, int h, int w, 
             return launch_upscore(q.A("conv6_cls"), q.n, h / 4, w / 4, net->classes, measure, threshold, q.W.partial,
                                   label_dev ? label_dev + i0 * px : nullptr, mask_dev ? mask_dev + i0 * px : nullptr,
                                   conf_dev ? conf_dev + i0 * px : nullptr, q.s);
-        })))
+        }, arith)))
         return rc;
     HIP_TRY(launch_reduce_mean(W.partial, n, upscore_blocks(h / 4, w / 4), (double)h * (double)w, scores_dev, s));
     return SSAL_OK;
@@ -573,7 +595,7 @@ SSAL_API int ssal_icnet_commit(ssal_icnet *net, void *stream)
     for (const auto &t : net->tensors)
         if (!t.set) return fail(SSAL_ESTATE, "tensor '%s' has not been set", t.name.c_str());
     ArenaBuilder ab;
-    struct Off { size_t w, s, t, hwio, wq; };
+    struct Off { size_t w, s, t, hwio, wq, w3, pk3; };
     std::map<std::string, Off> offs;
     std::vector<float> s, t, wt;
     std::map<std::string, bool> wants_hwio;
@@ -585,9 +607,14 @@ SSAL_API int ssal_icnet_commit(ssal_icnet *net, void *stream)
         Off o;
         o.hwio = (size_t)-1;
         o.wq = (size_t)-1;
+        o.w3 = (size_t)-1;
+        o.pk3 = (size_t)-1;
         for (int i = 0; i < kNumBnecks; ++i)
             if (fused_bneck(kBnecks[i]) && sp.name == std::string(kBnecks[i].name) + "_1x1_reduce") {
                 const std::string b = kBnecks[i].name;
+                if (bottleneck_bf16x3_supported(kBnecks[i].cin, kBnecks[i].mid))  // the opt-in arithmetic mode (104 KB per block)
+                    o.pk3 = ab.push(bf16x3::pack_layer(T(net, b + "_1x1_reduce.kernel").data(), T(net, b + "_3x3.kernel").data(),
+                                                       nullptr, 9, T(net, b + "_1x1_increase.kernel").data()));
                 o.wq = ab.push(bnk_quad_layout(T(net, b + "_1x1_reduce.kernel").data(), T(net, b + "_3x3.kernel").data(), nullptr, 9,
                                                T(net, b + "_1x1_increase.kernel").data()));
             }
@@ -597,6 +624,8 @@ SSAL_API int ssal_icnet_commit(ssal_icnet *net, void *stream)
             wt.resize(igemm_relayout_floats(sp.k, sp.k, sp.cin, sp.cout));
             igemm_relayout(k.data(), sp.k, sp.k, sp.cin, sp.cout, wt.data());
             o.w = ab.push(wt);
+            // the opt-in arithmetic mode: the same kernel pre-split into bf16 triples, 1.5x the bytes, next to the fp32 layout
+            o.w3 = ab.push(bf16x3::pack_igemm(k.data(), sp.k, sp.k, sp.cin, sp.cout));
         } else {
             o.w = ab.push(k);
         }
@@ -633,6 +662,8 @@ SSAL_API int ssal_icnet_commit(ssal_icnet *net, void *stream)
         d.shift = net->arena + o.t;
         d.w_hwio = o.hwio == (size_t)-1 ? nullptr : net->arena + o.hwio;
         d.wq = o.wq == (size_t)-1 ? nullptr : net->arena + o.wq;
+        d.w3 = o.w3 == (size_t)-1 ? nullptr : net->arena + o.w3;
+        d.pk3 = o.pk3 == (size_t)-1 ? nullptr : net->arena + o.pk3;
         net->convs[sp.name] = d;
     }
     net->zeros128 = net->arena + zeros_off;
@@ -673,6 +704,23 @@ SSAL_API int ssal_icnet_score_nhwc_u8(ssal_icnet *net, const uint8_t *x_dev, int
 {
     return score_any(net, x_dev, true, n, h, w, measure, threshold, scores_dev, label_dev, mask_dev, conf_dev, ws_dev,
                      ws_bytes, stream);
+}
+
+// ---- opt-in arithmetic (include/ssal_icnet.h): SSAL_ARITH_F32 is the plain entry ----
+SSAL_API int ssal_icnet_forward_nhwc_arith(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w, int arithmetic,
+                                           float *logits_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    if (arithmetic != SSAL_ARITH_F32 && arithmetic != SSAL_ARITH_BF16X3) return fail(SSAL_EINVAL, "unknown arithmetic mode %d", arithmetic);
+    return forward_any(net, x_dev, x_is_u8 != 0, n, h, w, logits_dev, ws_dev, ws_bytes, stream, arithmetic);
+}
+
+SSAL_API int ssal_icnet_score_nhwc_arith(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w, int measure,
+                                         float threshold, int arithmetic, double *scores_dev, uint8_t *label_dev,
+                                         uint8_t *mask_dev, float *conf_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    if (arithmetic != SSAL_ARITH_F32 && arithmetic != SSAL_ARITH_BF16X3) return fail(SSAL_EINVAL, "unknown arithmetic mode %d", arithmetic);
+    return score_any(net, x_dev, x_is_u8 != 0, n, h, w, measure, threshold, scores_dev, label_dev, mask_dev, conf_dev, ws_dev,
+                     ws_bytes, stream, arithmetic);
 }
 
 // ---- region-level acquisition through the confidence plane (a fused tail inside k_upscore is not built: its partials
@@ -1278,6 +1326,10 @@ int update_packed(ssal_icnet *net, const std::vector<HostUpdate> &tensors, const
         if (sp.cin % 32 == 0) {
             wt.resize(igemm_relayout_floats(sp.k, sp.k, sp.cin, sp.cout));
             igemm_relayout(T(net, sp.name + ".kernel").data(), sp.k, sp.k, sp.cin, sp.cout, wt.data());
+            // the pre-split copy of the opt-in arithmetic mode follows the kernel it was made from
+            keep.push_back(bf16x3::pack_igemm(T(net, sp.name + ".kernel").data(), sp.k, sp.k, sp.cin, sp.cout));
+            HIP_TRY(hipMemcpyAsync(const_cast<float *>(net->convs.at(sp.name).w3), keep.back().data(), keep.back().size() * 4,
+                                   hipMemcpyHostToDevice, s));
         } else {
             wt = T(net, sp.name + ".kernel");  // a branch's first convolution keeps HWIO, as ssal_icnet_commit stages it
         }
@@ -1612,18 +1664,23 @@ SSAL_API int ssal_icnet_update_highres(ssal_icnet *net, const float *params_host
 // ------------------------------------------------------------------------------------------------
 // stand-alone operators
 // ------------------------------------------------------------------------------------------------
-SSAL_API int64_t ssal_conv_bn_workspace_bytes(int kh, int kw, int cin, int cout)
+namespace {
+
+// the split kernel of the opt-in mode sits behind the buffers of the exact call (256-byte aligned), on the matrix-core path only
+bool conv_bn_splits(int cin, int arithmetic) { return arithmetic == SSAL_ARITH_BF16X3 && cin % 32 == 0; }
+
+int64_t conv_bn_bytes(int kh, int kw, int cin, int cout, int arithmetic)
 {
-    if (kh <= 0 || kw <= 0 || cin <= 0 || cout <= 0) return -1;
     const int64_t wfl = cin % 32 == 0 ? (int64_t)igemm_relayout_floats(kh, kw, cin, cout) : (int64_t)kh * kw * cin * cout;
-    return (wfl + 2 * ((cout + 31) / 32 * 32)) * 4 + 1024;
+    const int64_t base = (wfl + 2 * ((cout + 31) / 32 * 32)) * 4 + 1024;
+    if (!conv_bn_splits(cin, arithmetic)) return base;
+    return base + (int64_t)bf16x3::igemm_units(kh, kw, cin, cout) * 16 + 256;
 }
 
-SSAL_API int ssal_conv_bn_act(const float *x_dev, int n, int h, int w, int cin, const float *kernel_host, int kh,
-                              int kw, int cout, int stride, int dilation, const float *mean_host,
-                              const float *var_host, const float *gamma_host, const float *beta_host,
-                              const float *bias_host, const float *res_dev, int relu, int upsample2x, float *y_dev,
-                              void *ws_dev, int64_t ws_bytes, void *stream)
+int conv_bn_act_any(const float *x_dev, int n, int h, int w, int cin, const float *kernel_host, int kh, int kw, int cout,
+                    int stride, int dilation, const float *mean_host, const float *var_host, const float *gamma_host,
+                    const float *beta_host, const float *bias_host, const float *res_dev, int relu, int upsample2x,
+                    float *y_dev, void *ws_dev, int64_t ws_bytes, void *stream, int arithmetic)
 {
     if (!x_dev || !kernel_host || !y_dev || !ws_dev) return fail(SSAL_EINVAL, "NULL pointer");
     if (n <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0 || stride < 1 || dilation < 1)
@@ -1631,8 +1688,8 @@ SSAL_API int ssal_conv_bn_act(const float *x_dev, int n, int h, int w, int cin, 
     const bool bn = mean_host || var_host || gamma_host || beta_host;
     if (bn && !(mean_host && var_host && gamma_host && beta_host))
         return fail(SSAL_EINVAL, "batch-norm needs all of mean / variance / gamma / beta");
-    if (ws_bytes < ssal_conv_bn_workspace_bytes(kh, kw, cin, cout))
-        return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes", (long long)ssal_conv_bn_workspace_bytes(kh, kw, cin, cout));
+    if (ws_bytes < conv_bn_bytes(kh, kw, cin, cout, arithmetic))
+        return fail(SSAL_ENOMEM, "workspace too small: need %lld bytes", (long long)conv_bn_bytes(kh, kw, cin, cout, arithmetic));
     const bool first = cin % 32 != 0;
     if (first && !((cin == 1 || cin == 3 || cin == 4) && kh == 3 && kw == 3 && stride == 2 && dilation == 1 &&
                    cout == 32 && relu && !res_dev && !upsample2x))
@@ -1654,11 +1711,76 @@ SSAL_API int ssal_conv_bn_act(const float *x_dev, int n, int h, int w, int cin, 
     HIP_TRY(hipMemcpyAsync(wd, wt.data(), wt.size() * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(sd, sc.data(), sc.size() * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(td, sh.data(), sh.size() * 4, hipMemcpyHostToDevice, s));
+    std::vector<float> w3;
+    float *w3d = nullptr;
+    if (!first && conv_bn_splits(cin, arithmetic)) {
+        w3 = bf16x3::pack_igemm(kernel_host, kh, kw, cin, cout);
+        b.off = (b.off + 255) / 256 * 256;
+        w3d = b.take<float>((int64_t)w3.size());
+        HIP_TRY(hipMemcpyAsync(w3d, w3.data(), w3.size() * 4, hipMemcpyHostToDevice, s));
+    }
     HIP_TRY(hipStreamSynchronize(s));  // the staging vectors die at return
     if (first) HIP_TRY(launch_conv_first(x_dev, false, n, h, w, cin, 1, wd, sd, td, y_dev, s));
     else
         HIP_TRY(launch_igemm(x_dev, n, h, w, cin, wd, kh, kw, cout, stride, dilation, sd, td, res_dev, relu != 0,
-                             upsample2x != 0, y_dev, s));
+                             upsample2x != 0, y_dev, s, arithmetic, w3d));
+    return SSAL_OK;
+}
+
+}  // namespace
+
+SSAL_API int64_t ssal_conv_bn_workspace_bytes(int kh, int kw, int cin, int cout)
+{
+    if (kh <= 0 || kw <= 0 || cin <= 0 || cout <= 0) return -1;
+    return conv_bn_bytes(kh, kw, cin, cout, SSAL_ARITH_F32);
+}
+
+SSAL_API int64_t ssal_conv_bn_workspace_bytes_arith(int kh, int kw, int cin, int cout, int arithmetic)
+{
+    if (kh <= 0 || kw <= 0 || cin <= 0 || cout <= 0) return -1;
+    if (arithmetic != SSAL_ARITH_F32 && arithmetic != SSAL_ARITH_BF16X3) return -1;
+    return conv_bn_bytes(kh, kw, cin, cout, arithmetic);
+}
+
+SSAL_API int ssal_conv_bn_act(const float *x_dev, int n, int h, int w, int cin, const float *kernel_host, int kh,
+                              int kw, int cout, int stride, int dilation, const float *mean_host,
+                              const float *var_host, const float *gamma_host, const float *beta_host,
+                              const float *bias_host, const float *res_dev, int relu, int upsample2x, float *y_dev,
+                              void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    return conv_bn_act_any(x_dev, n, h, w, cin, kernel_host, kh, kw, cout, stride, dilation, mean_host, var_host, gamma_host,
+                           beta_host, bias_host, res_dev, relu, upsample2x, y_dev, ws_dev, ws_bytes, stream, SSAL_ARITH_F32);
+}
+
+SSAL_API int ssal_conv_bn_act_arith(const float *x_dev, int n, int h, int w, int cin, const float *kernel_host, int kh,
+                                    int kw, int cout, int stride, int dilation, const float *mean_host,
+                                    const float *var_host, const float *gamma_host, const float *beta_host,
+                                    const float *bias_host, const float *res_dev, int relu, int upsample2x, float *y_dev,
+                                    void *ws_dev, int64_t ws_bytes, void *stream, int arithmetic)
+{
+    if (arithmetic != SSAL_ARITH_F32 && arithmetic != SSAL_ARITH_BF16X3) return fail(SSAL_EINVAL, "unknown arithmetic mode %d", arithmetic);
+    return conv_bn_act_any(x_dev, n, h, w, cin, kernel_host, kh, kw, cout, stride, dilation, mean_host, var_host, gamma_host,
+                           beta_host, bias_host, res_dev, relu, upsample2x, y_dev, ws_dev, ws_bytes, stream, arithmetic);
+}
+
+SSAL_API int ssal_icnet_debug_conv_dispatch(int n, int h, int w, int cin, int cout, int kh, int kw, int stride, int dil, int up2,
+                                            int has_res, int arithmetic, int *kernel_out, int *nt_out)
+{
+    if (!kernel_out || !nt_out) return fail(SSAL_EINVAL, "NULL output");
+    if (arithmetic != SSAL_ARITH_F32 && arithmetic != SSAL_ARITH_BF16X3) return fail(SSAL_EINVAL, "unknown arithmetic mode %d", arithmetic);
+    if (n <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0 || stride < 1 || dil < 1) return fail(SSAL_EINVAL, "bad dims");
+    if (cin % 32 != 0) {  // ssal_conv_bn_act's first-layer path
+        if (!((cin == 1 || cin == 3 || cin == 4) && kh == 3 && kw == 3 && stride == 2 && dil == 1 && cout == 32 && !has_res && !up2))
+            return fail(SSAL_EINVAL, "unsupported convolution");
+        *kernel_out = SSAL_ICNET_KERNEL_CONV_FIRST;
+        *nt_out = 0;
+        return SSAL_OK;
+    }
+    IgemmPlan plan;
+    if (igemm_plan(n, h, w, cin, kh, kw, cout, stride, dil, has_res != 0, up2 != 0, arithmetic, &plan) != hipSuccess)
+        return fail(SSAL_EINVAL, "no kernel takes this convolution (kernel size, or a tensor beyond the 32-bit offset limits)");
+    *kernel_out = plan.kernel;
+    *nt_out = plan.nt;
     return SSAL_OK;
 }
 

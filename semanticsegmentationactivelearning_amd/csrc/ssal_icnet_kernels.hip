@@ -11,6 +11,7 @@
 // Bit-exactness contract (same as the ENet kernels): every conv output element is ONE fp32 fmaf chain over
 // (kh, kw, ci) ascending -- the fp32 MFMA is exactly such a chain over its k index -- so results equal the parity
 // oracle bit for bit.  Out-of-image taps contribute fmaf(0, w, acc) == acc.
+#include "../../include/ssal_enet.h"
 #include "ssal_icnet.h"
 #include "ssal_internal.h"
 #include "ssal_mfma.h"
@@ -698,19 +699,13 @@ bool igemm_supported(int Cin, int Cout, int KH, int KW)
     return Cin > 0 && Cin % 32 == 0 && Cout > 0 && KH >= 1 && KW >= 1 && KH <= 7 && KW <= 7;
 }
 
-hipError_t launch_igemm(const float *x, int N, int H, int W, int Cin, const float *wt, int KH, int KW, int Cout,
-                        int stride, int dil, const float *scale, const float *shift, const float *res, bool relu,
-                        bool up2, float *y, hipStream_t s)
+// TF "SAME" geometry of one launch_igemm call (H, W: dims of the tensor in memory; up2: the conv sees 2H x 2W)
+static void igemm_geometry(IgemmArgs &a, int N, int H, int W, int Cin, int KH, int KW, int Cout, int stride, int dil, bool up2)
 {
-    if (!igemm_supported(Cin, Cout, KH, KW) || stride < 1 || dil < 1) return hipErrorInvalidValue;
-    IgemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = x; a.wt = wt; a.y = y; a.scale = scale; a.shift = shift; a.res = res;
     a.N = N; a.Cin = Cin; a.Cout = Cout; a.CoutP = (Cout + 31) / 32 * 32;
     a.H = up2 ? 2 * H : H;  // H, W: dims of the tensor the conv SEES
     a.W = up2 ? 2 * W : W;
     a.KH = KH; a.KW = KW; a.stride = stride; a.dil = dil;
-    a.relu = relu ? 1 : 0;
     a.up2 = up2 ? 1 : 0;
     // TF "SAME": out = ceil(in/stride); pad_total = max((out-1)*stride + (k-1)*dil + 1 - in, 0); before = total/2
     a.Ho = (a.H + stride - 1) / stride;
@@ -720,37 +715,24 @@ hipError_t launch_igemm(const float *x, int N, int H, int W, int Cin, const floa
     a.pad_t = th / 2;
     a.pad_l = tw / 2;
     a.M = (long)N * a.Ho * a.Wo;
-    if (KH == 1 && KW == 1 && Cin == 128 && Cout <= 32 && stride == 1 && up2 && !res &&
-        (long)4 * H * W * Cout * 4 < (1L << 31) && (long)H * W * 512 < (1L << 31)) {  // 32-bit offsets inside one image
-        ClsUpArgs q;
-        q.x = x; q.wt = wt; q.scale = scale; q.shift = shift; q.y = y;
-        q.N = N; q.Hs = H; q.Ws = W; q.Cout = Cout; q.relu = relu ? 1 : 0;
-        q.tiles_x = cdiv_i(2 * W, HT_W); q.tiles_y = cdiv_i(2 * H, HT_H);
-        const long grid = (long)N * q.tiles_x * q.tiles_y;
-        if (grid < (1L << 31)) {
-            ProfScope prof("k_conv1x1_up2_c128", 2.0 * (double)a.M * Cin * Cout,
-                           4.0 * ((double)N * H * W * Cin + (double)a.M * Cout + (double)Cin * Cout), s);
-            const long slots = 768 / launch_concurrency();  // persistent: three workgroups per CU over the chains that run side by side
-            hipLaunchKernelGGL(k_conv1x1_up2_c128, dim3((unsigned)(grid < slots ? grid : slots)), dim3(256), 0, s, q);
-            return hipGetLastError();
-        }
+}
+
+// The ONE place that decides which kernel a convolution runs on (launch_igemm switches on its answer; the dry query
+// ssal_icnet_debug_conv_dispatch reports it).  a: igemm_geometry's output; fills the tile counts of the generic kernels.
+static hipError_t igemm_choose(IgemmArgs &a, int N, int H, int W, bool has_res, bool up2, int arithmetic, IgemmPlan *plan)
+{
+    const int Cin = a.Cin, Cout = a.Cout, KH = a.KH, KW = a.KW, stride = a.stride, dil = a.dil;
+    plan->nt = 0;
+    if (KH == 1 && KW == 1 && Cin == 128 && Cout <= 32 && stride == 1 && up2 && !has_res &&
+        (long)4 * H * W * Cout * 4 < (1L << 31) && (long)H * W * 512 < (1L << 31) &&  // 32-bit offsets inside one image
+        (long)N * cdiv_i(2 * W, HT_W) * cdiv_i(2 * H, HT_H) < (1L << 31)) {
+        plan->kernel = IGK_CONV1X1_UP2_C128;
+        return hipSuccess;
     }
-    if (KH == 3 && KW == 3 && Cin == 32 && stride == 1 && dil == 1 && !up2 && (long)H * W * (Cout > 32 ? Cout : 32) * 4 < (1L << 31)) {
-        HaloArgs q;
-        q.x = x; q.wt = wt; q.scale = scale; q.shift = shift; q.res = res; q.y = y;
-        q.N = N; q.H = H; q.W = W; q.Cout = Cout; q.CoutP = a.CoutP; q.relu = relu ? 1 : 0;
-        q.tiles_x = cdiv_i(W, HT_W); q.tiles_y = cdiv_i(H, HT_H); q.tiles_n = a.CoutP / 32;
-        const long ntiles = (long)N * q.tiles_x * q.tiles_y * q.tiles_n;
-        // persistent workgroups: two per CU (67 KB of LDS each), a multiple of the column-tile count
-        long grid = (512 / launch_concurrency()) / q.tiles_n * q.tiles_n;
-        if (grid < q.tiles_n) grid = q.tiles_n;
-        if (grid > ntiles) grid = ntiles;
-        if (ntiles < (1L << 31)) {
-            ProfScope prof("k_conv3x3_c32", 2.0 * (double)a.M * 9 * Cin * Cout,
-                           4.0 * ((double)N * H * W * Cin + (double)a.M * Cout * (res ? 2.0 : 1.0) + 9.0 * Cin * Cout), s);
-            hipLaunchKernelGGL(k_conv3x3_c32, dim3((unsigned)grid), dim3(256), 0, s, q);
-            return hipGetLastError();
-        }
+    if (KH == 3 && KW == 3 && Cin == 32 && stride == 1 && dil == 1 && !up2 && (long)H * W * (Cout > 32 ? Cout : 32) * 4 < (1L << 31) &&
+        (long)N * cdiv_i(W, HT_W) * cdiv_i(H, HT_H) * (a.CoutP / 32) < (1L << 31)) {
+        plan->kernel = IGK_CONV3X3_C32;
+        return hipSuccess;
     }
     // 32-bit byte offsets inside the kernel: every tensor of one launch must stay below 4 GiB (split the batch); the
     // margin covers the per-chunk scalar offset (< 4 * Cin <= 8 KiB) that is added to a row offset by the hardware
@@ -764,12 +746,75 @@ hipError_t launch_igemm(const float *x, int N, int H, int W, int Cin, const floa
     a.tiles_n = nb32 / NT;
     a.ntiles = a.tiles_m * a.tiles_n;
     a.xcd_chunk = (a.ntiles + 7) / 8;
+    plan->nt = NT;
+    // the opt-in split-operand mode has a kernel for the plain form only; every other form stays exact
+    plan->kernel = up2 ? IGK_IGEMM_UP2 : (arithmetic == SSAL_ARITH_BF16X3 ? IGK_IGEMM_BF16X3 : IGK_IGEMM);
+    return hipSuccess;
+}
+
+hipError_t igemm_plan(int N, int H, int W, int Cin, int KH, int KW, int Cout, int stride, int dil, bool has_res, bool up2,
+                      int arithmetic, IgemmPlan *plan)
+{
+    if (!igemm_supported(Cin, Cout, KH, KW) || stride < 1 || dil < 1 || N < 1 || H < 1 || W < 1) return hipErrorInvalidValue;
+    IgemmArgs a;
+    memset(&a, 0, sizeof(a));
+    igemm_geometry(a, N, H, W, Cin, KH, KW, Cout, stride, dil, up2);
+    return igemm_choose(a, N, H, W, has_res, up2, arithmetic, plan);
+}
+
+hipError_t launch_igemm(const float *x, int N, int H, int W, int Cin, const float *wt, int KH, int KW, int Cout,
+                        int stride, int dil, const float *scale, const float *shift, const float *res, bool relu,
+                        bool up2, float *y, hipStream_t s, int arithmetic, const void *wt_bf16x3)
+{
+    if (!igemm_supported(Cin, Cout, KH, KW) || stride < 1 || dil < 1) return hipErrorInvalidValue;
+    IgemmArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.wt = wt; a.y = y; a.scale = scale; a.shift = shift; a.res = res;
+    a.relu = relu ? 1 : 0;
+    igemm_geometry(a, N, H, W, Cin, KH, KW, Cout, stride, dil, up2);
+    IgemmPlan plan;
+    const hipError_t prc = igemm_choose(a, N, H, W, res != nullptr, up2, arithmetic, &plan);
+    if (prc != hipSuccess) return prc;
+    if (plan.kernel == IGK_CONV1X1_UP2_C128) {
+        ClsUpArgs q;
+        q.x = x; q.wt = wt; q.scale = scale; q.shift = shift; q.y = y;
+        q.N = N; q.Hs = H; q.Ws = W; q.Cout = Cout; q.relu = relu ? 1 : 0;
+        q.tiles_x = cdiv_i(2 * W, HT_W); q.tiles_y = cdiv_i(2 * H, HT_H);
+        const long grid = (long)N * q.tiles_x * q.tiles_y;
+        ProfScope prof("k_conv1x1_up2_c128", 2.0 * (double)a.M * Cin * Cout,
+                       4.0 * ((double)N * H * W * Cin + (double)a.M * Cout + (double)Cin * Cout), s);
+        const long slots = 768 / launch_concurrency();  // persistent: three workgroups per CU over the chains that run side by side
+        hipLaunchKernelGGL(k_conv1x1_up2_c128, dim3((unsigned)(grid < slots ? grid : slots)), dim3(256), 0, s, q);
+        return hipGetLastError();
+    }
+    if (plan.kernel == IGK_CONV3X3_C32) {
+        HaloArgs q;
+        q.x = x; q.wt = wt; q.scale = scale; q.shift = shift; q.res = res; q.y = y;
+        q.N = N; q.H = H; q.W = W; q.Cout = Cout; q.CoutP = a.CoutP; q.relu = relu ? 1 : 0;
+        q.tiles_x = cdiv_i(W, HT_W); q.tiles_y = cdiv_i(H, HT_H); q.tiles_n = a.CoutP / 32;
+        const long ntiles = (long)N * q.tiles_x * q.tiles_y * q.tiles_n;
+        // persistent workgroups: two per CU (67 KB of LDS each), a multiple of the column-tile count
+        long grid = (512 / launch_concurrency()) / q.tiles_n * q.tiles_n;
+        if (grid < q.tiles_n) grid = q.tiles_n;
+        if (grid > ntiles) grid = ntiles;
+        ProfScope prof("k_conv3x3_c32", 2.0 * (double)a.M * 9 * Cin * Cout,
+                       4.0 * ((double)N * H * W * Cin + (double)a.M * Cout * (res ? 2.0 : 1.0) + 9.0 * Cin * Cout), s);
+        hipLaunchKernelGGL(k_conv3x3_c32, dim3((unsigned)grid), dim3(256), 0, s, q);
+        return hipGetLastError();
+    }
+    const int NT = plan.nt;
     const int grid = a.xcd_chunk * 8;
+    const double flops = 2.0 * (double)a.M * KH * KW * Cin * Cout;
+    if (plan.kernel == IGK_IGEMM_BF16X3) {
+        // the packed kernel holds three bf16 terms per element: 6 bytes instead of 4
+        const double bytes = 4.0 * ((double)N * H * W * Cin + (double)a.M * Cout * (res ? 2.0 : 1.0)) + 6.0 * (double)KH * KW * Cin * a.CoutP;
+        ProfScope prof(NT == 4 ? "k_igemm_bf16x3<4>" : NT == 2 ? "k_igemm_bf16x3<2>" : "k_igemm_bf16x3<1>", flops, bytes, s);
+        return launch_igemm_bf16x3(a, NT, wt_bf16x3, grid, s);
+    }
     a.trace = (g_trace_buf && (long)grid * 4 * 16 * 8 <= g_trace_bytes) ? g_trace_buf : nullptr;
 #ifdef SSAL_MEASURE
     a.ablate = knobs().ablate;
 #endif
-    const double flops = 2.0 * (double)a.M * KH * KW * Cin * Cout;
     const double bytes = 4.0 * ((double)N * H * W * Cin + (double)a.M * Cout * (res ? 2.0 : 1.0) +
                                 (double)KH * KW * Cin * Cout);
     // one profile row per kernel SYMBOL (rocprofv3 lists k_igemm<NT, false> and k_igemm<NT, true> separately)

@@ -72,7 +72,7 @@ def predict(net, images, size=None, embedding_reversed=None, colormap=None, arit
     ``embedding_reversed``) or [N,OH,OW,3] (``colormap``).  With ``size`` the logits are resized, reduced to their first
     maximum and mapped in one kernel (``ssal_predict_logits_nhwc``; the resized logits never reach HBM); without it the label
     plane comes from the network's fused score kernel (no logits in HBM at all) and ``ssal_label_lut`` applies the table.
-    The bytes are those of ``predict_labels`` + ``reverse_embedding`` / ``colorize``.  ``arithmetic``: as ``ENet.__call__``."""
+    The bytes are those of ``predict_labels`` + ``reverse_embedding`` / ``colorize``.  ``arithmetic``: as ``ENet.__call__`` / ``ICNet.__call__``."""
     if embedding_reversed is not None and colormap is not None:
         raise ValueError("give embedding_reversed or colormap, not both")
     _lib.arithmetic_code(arithmetic)
@@ -81,17 +81,16 @@ def predict(net, images, size=None, embedding_reversed=None, colormap=None, arit
     if channels:
         table = _table(colormap if channels == 3 else embedding_reversed, net.classes, channels,
                        "colormap" if channels == 3 else "embedding_reversed")
-    kw = {} if arithmetic == "f32" else {"arithmetic": arithmetic}  # ICNet has the one arithmetic
     torch = _lib.require_gpu()
     L = _lib.lib()
     if size is None:
-        _, extra = net.score(images, "confidence", return_label=True, **kw)
+        _, extra = net.score(images, "confidence", return_label=True, arithmetic=arithmetic)
         label = extra["label"]
         if not channels:
             return label
         src, (n, oh, ow) = label, label.shape
     else:
-        src = net(images, training=False, **kw)
+        src = net(images, training=False, arithmetic=arithmetic)
         n, h, w, k = src.shape
         oh, ow = int(size[0]), int(size[1])
     lut = torch.from_numpy(table).to(src.device) if channels else None

@@ -101,6 +101,10 @@ class ICNet(_lib.DeviceState):
     (the paper the reference's empty ``models/icnet/icnet.py:3`` cites; architecture pinned in ICNET_SPEC.md)
     """
 
+    # the modes active_learning's ranking / evaluation loops accept for this model: ``score(arithmetic="bf16x3")`` exists, but
+    # the loops keep ICNet on the exact path until evaluate / score_regions have the mode too (one arithmetic per campaign)
+    loop_arithmetics = ("f32",)
+
     def __init__(self, classes, kernel_initializer=None, weight_regularization=None, name="ICNet"):
         self.classes = int(classes)
         self.name = name
@@ -185,7 +189,11 @@ class ICNet(_lib.DeviceState):
         return x
 
     # ---- forward ---------------------------------------------------------------------------
-    def __call__(self, inputs, training=False):
+    def __call__(self, inputs, training=False, arithmetic="f32"):
+        """``arithmetic``: "f32" (default; exact fp32, bit-identical to the parity oracle) or the OPT-IN "bf16x3"
+        (include/ssal_enet.h SSAL_ARITH_BF16X3: split-operand bf16 MFMAs in every convolution the plain implicit-GEMM kernel
+        runs; same accuracy class, NOT bit-identical -- DESIGN.md section 35)."""
+        arith = _lib.arithmetic_code(arithmetic)
         torch = _lib.require_gpu() if not training else None
         x = self._prepare(inputs, training)
         n, h, w, _ = x.shape
@@ -194,9 +202,13 @@ class ICNet(_lib.DeviceState):
             handle = self._sync_handle()
             ws = self._workspace(L.ssal_icnet_workspace_bytes(handle, n, h, w), x.device)
             logits = torch.empty((n, h, w, self.classes), dtype=torch.float32, device=x.device)
-            fwd = L.ssal_icnet_forward_nhwc_u8 if x.dtype == torch.uint8 else L.ssal_icnet_forward_nhwc
-            _lib.check(fwd(handle, _lib.dev_ptr(x), n, h, w, _lib.dev_ptr(logits), _lib.dev_ptr(ws), ws.numel(),
-                           _lib.stream_ptr()))
+            if arith:
+                _lib.check(L.ssal_icnet_forward_nhwc_arith(handle, _lib.dev_ptr(x), int(x.dtype == torch.uint8), n, h, w, arith,
+                                                           _lib.dev_ptr(logits), _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))
+            else:
+                fwd = L.ssal_icnet_forward_nhwc_u8 if x.dtype == torch.uint8 else L.ssal_icnet_forward_nhwc
+                _lib.check(fwd(handle, _lib.dev_ptr(x), n, h, w, _lib.dev_ptr(logits), _lib.dev_ptr(ws), ws.numel(),
+                               _lib.stream_ptr()))
             self._note_call(ws, (n, h, w), "forward")
         self.outputs = [logits]  # eager: keep only the most recent call
         return logits
@@ -204,12 +216,14 @@ class ICNet(_lib.DeviceState):
     call = __call__
 
     def score(self, inputs, measure="margin", threshold=0.0, return_label=False, return_mask=False,
-              return_confidence=False, out=None):
+              return_confidence=False, out=None, arithmetic="f32"):
         """forward(training=False) + softmax + acquisition measure + float64 per-image mean; the 4x bilinear
         up-sampling of the 1/4-resolution class scores happens inside the score kernel (the full-resolution
-        logits never reach HBM).  Returns scores [N] float64 (device), optionally the per-pixel maps."""
+        logits never reach HBM).  Returns scores [N] float64 (device), optionally the per-pixel maps.
+        ``arithmetic="bf16x3"`` is the opt-in split-operand mode (see ``__call__``); the default "f32" is exact."""
         if measure not in _lib.MEASURES:
             raise NotImplementedError("Uncertainty function not implemented.")
+        arith = _lib.arithmetic_code(arithmetic)
         torch = _lib.require_gpu()
         x = self._prepare(inputs, False)
         n, h, w, _ = x.shape
@@ -221,10 +235,16 @@ class ICNet(_lib.DeviceState):
             label = torch.empty((n, h, w), dtype=torch.uint8, device=x.device) if return_label else None
             mask = torch.empty((n, h, w), dtype=torch.uint8, device=x.device) if return_mask else None
             conf = torch.empty((n, h, w), dtype=torch.float32, device=x.device) if return_confidence else None
-            fn = L.ssal_icnet_score_nhwc_u8 if x.dtype == torch.uint8 else L.ssal_icnet_score_nhwc
-            _lib.check(fn(handle, _lib.dev_ptr(x), n, h, w, _lib.MEASURES[measure], float(threshold),
-                          _lib.dev_ptr(scores, torch.float64, "scores"), _lib.dev_ptr(label), _lib.dev_ptr(mask),
-                          _lib.dev_ptr(conf), _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))
+            if arith:
+                _lib.check(L.ssal_icnet_score_nhwc_arith(
+                    handle, _lib.dev_ptr(x), int(x.dtype == torch.uint8), n, h, w, _lib.MEASURES[measure], float(threshold),
+                    arith, _lib.dev_ptr(scores, torch.float64, "scores"), _lib.dev_ptr(label), _lib.dev_ptr(mask),
+                    _lib.dev_ptr(conf), _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))
+            else:
+                fn = L.ssal_icnet_score_nhwc_u8 if x.dtype == torch.uint8 else L.ssal_icnet_score_nhwc
+                _lib.check(fn(handle, _lib.dev_ptr(x), n, h, w, _lib.MEASURES[measure], float(threshold),
+                              _lib.dev_ptr(scores, torch.float64, "scores"), _lib.dev_ptr(label), _lib.dev_ptr(mask),
+                              _lib.dev_ptr(conf), _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))
             self._note_call(ws, (n, h, w), "score")
         if return_label or return_mask or return_confidence:
             return scores, {"label": label, "mask": mask, "confidence": conf}

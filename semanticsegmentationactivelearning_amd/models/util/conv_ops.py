@@ -18,11 +18,15 @@ def _hp(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
-def conv_bn_act(x, kernel, stride=1, dilation=1, bn=None, bias=None, residual=None, relu=True, upsample2x=False):
+def conv_bn_act(x, kernel, stride=1, dilation=1, bn=None, bias=None, residual=None, relu=True, upsample2x=False,
+                arithmetic=None):
     """``[relu]( BN(conv2d(x, kernel HWIO, strides, dilations, "SAME")) [+ residual] )`` in ONE launch on the fp32
     matrix cores (``cin % 32 == 0``), or the 3x3 / stride-2 first-layer kernel (``cin`` in 1, 3, 4 -> 32 channels).
     ``bn`` = (mean, variance, gamma, beta) numpy vectors or None; ``upsample2x`` runs the convolution on
-    ``tf.image.resize_bilinear(x, 2x)`` evaluated on the fly (cascade feature fusion, ICNET_SPEC section 4)."""
+    ``tf.image.resize_bilinear(x, 2x)`` evaluated on the fly (cascade feature fusion, ICNET_SPEC section 4).
+    ``arithmetic``: None (default) is ``ssal_conv_bn_act``; "f32" / "bf16x3" go through ``ssal_conv_bn_act_arith`` ("f32":
+    the same launch, the same bits; "bf16x3": the opt-in split-operand kernel where the launcher has one, as ``ICNet.score``)."""
+    arith = None if arithmetic is None else _lib.arithmetic_code(arithmetic)
     torch = _lib.require_gpu()
     x = _lib.as_device_f32(x)
     k = _host(kernel)
@@ -43,13 +47,14 @@ def conv_bn_act(x, kernel, stride=1, dilation=1, bn=None, bias=None, residual=No
             raise ValueError("residual must have shape %s (got %s)" % ((n, oh, ow, cout), tuple(res.shape)))
     L = _lib.lib()
     with torch.cuda.device(x.device):
-        nbytes = L.ssal_conv_bn_workspace_bytes(kh, kw, cin, cout)
+        nbytes = (L.ssal_conv_bn_workspace_bytes(kh, kw, cin, cout) if arith is None
+                  else L.ssal_conv_bn_workspace_bytes_arith(kh, kw, cin, cout, arith))
         ws = torch.empty(int(nbytes), dtype=torch.uint8, device=x.device)
         y = torch.empty((n, oh, ow, cout), dtype=torch.float32, device=x.device)
-        _lib.check(L.ssal_conv_bn_act(_lib.dev_ptr(x), n, h, w, cin, _hp(k), kh, kw, cout, int(stride), int(dilation),
-                                      _hp(m), _hp(v), _hp(g), _hp(b), _hp(bias), _lib.dev_ptr(res), 1 if relu else 0,
-                                      1 if upsample2x else 0, _lib.dev_ptr(y), _lib.dev_ptr(ws), ws.numel(),
-                                      _lib.stream_ptr()))
+        args = (_lib.dev_ptr(x), n, h, w, cin, _hp(k), kh, kw, cout, int(stride), int(dilation), _hp(m), _hp(v), _hp(g), _hp(b),
+                _hp(bias), _lib.dev_ptr(res), 1 if relu else 0, 1 if upsample2x else 0, _lib.dev_ptr(y), _lib.dev_ptr(ws),
+                ws.numel(), _lib.stream_ptr())
+        _lib.check(L.ssal_conv_bn_act(*args) if arith is None else L.ssal_conv_bn_act_arith(*(args + (arith,))))
     return y
 
 
