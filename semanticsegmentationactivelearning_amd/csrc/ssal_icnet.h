@@ -69,6 +69,9 @@ hipError_t launch_igemm_bf16x3(const IgemmArgs &a, int NT, const void *packed, i
 // factor 2 of the legacy mapping is x[2y][2x] bit for bit.  x may be the decoded uint8 frame (x * f32(1/255)).
 hipError_t launch_conv_first(const void *x, bool x_is_u8, int N, int H, int W, int Cin, int sub, const float *w,
                              const float *scale, const float *shift, float *y, hipStream_t s);
+// the shapes launch_conv_first takes (one workgroup per 8 x 32 output tile; the kernel indexes in 64 bits): what the
+// launcher, the stand-alone operator and the dry query ssal_icnet_debug_conv_dispatch all ask
+bool conv_first_fits(int N, int H, int W, int sub);
 
 // the first TWO convolutions of a branch in one launch (ssal_icnet_front.hip): launch_conv_first(x, ..., sub, w1, s1, t1)
 // followed by the 3x3 / stride `stride2` (1 or 2) / SAME convolution 32 -> 32 + BN + ReLU whose kernel is w2_igemm

@@ -1696,6 +1696,12 @@ int conv_bn_act_any(const float *x_dev, int n, int h, int w, int cin, const floa
         return fail(SSAL_EINVAL, "unsupported convolution: cin %% 32 == 0, or the 3x3 / stride-2 / 32-channel first layer "
                                  "on 1, 3 or 4 channels");
     if (!first && !igemm_supported(cin, cout, kh, kw)) return fail(SSAL_EINVAL, "unsupported kernel size %dx%d", kh, kw);
+    // a shape no launcher takes is an argument error, reported before anything is staged or launched (the launchers' own
+    // refusal would surface as a HIP failure); the same answer as ssal_icnet_debug_conv_dispatch
+    IgemmPlan plan;
+    if (first ? !conv_first_fits(n, h, w, 1)
+              : igemm_plan(n, h, w, cin, kh, kw, cout, stride, dilation, res_dev != nullptr, upsample2x != 0, arithmetic, &plan) != hipSuccess)
+        return fail(SSAL_EINVAL, "no kernel takes this convolution (kernel size, or a tensor beyond the 32-bit offset limits)");
     hipStream_t s = (hipStream_t)stream;
     std::vector<float> sc, sh, wt;
     fold_bn_padded(mean_host, var_host, gamma_host, beta_host, bias_host, cout, sc, sh);
@@ -1772,6 +1778,8 @@ SSAL_API int ssal_icnet_debug_conv_dispatch(int n, int h, int w, int cin, int co
     if (cin % 32 != 0) {  // ssal_conv_bn_act's first-layer path
         if (!((cin == 1 || cin == 3 || cin == 4) && kh == 3 && kw == 3 && stride == 2 && dil == 1 && cout == 32 && !has_res && !up2))
             return fail(SSAL_EINVAL, "unsupported convolution");
+        if (!conv_first_fits(n, h, w, 1))
+            return fail(SSAL_EINVAL, "no kernel takes this convolution (kernel size, or a tensor beyond the 32-bit offset limits)");
         *kernel_out = SSAL_ICNET_KERNEL_CONV_FIRST;
         *nt_out = 0;
         return SSAL_OK;

@@ -972,16 +972,22 @@ __global__ __launch_bounds__(256) void k_conv_first(const TX *__restrict__ x, co
     }
 }
 
+bool conv_first_fits(int N, int H, int W, int sub)
+{
+    if ((sub != 1 && sub != 2) || N < 1 || H < sub || W < sub) return false;
+    const int Ho = (H / sub + 1) / 2, Wo = (W / sub + 1) / 2;
+    return (long)N * cdiv_i(Wo, CF_TW) * cdiv_i(Ho, CF_TH) < (1L << 31);  // the grid: one workgroup per tile
+}
+
 hipError_t launch_conv_first(const void *x, bool x_is_u8, int N, int H, int W, int Cin, int sub, const float *w,
                              const float *scale, const float *shift, float *y, hipStream_t s)
 {
-    if (sub != 1 && sub != 2) return hipErrorInvalidValue;
+    if (!conv_first_fits(N, H, W, sub)) return hipErrorInvalidValue;
     const int Hc = H / sub, Wc = W / sub;
     const int Ho = (Hc + 1) / 2, Wo = (Wc + 1) / 2;
     const long total = (long)N * Ho * Wo;
     const int tiles_x = cdiv_i(Wo, CF_TW), tiles_y = cdiv_i(Ho, CF_TH);
     const long grid = (long)N * tiles_x * tiles_y;
-    if (grid >= (1L << 31)) return hipErrorInvalidValue;
     ProfScope prof("k_conv_first", 2.0 * (double)total * 9 * Cin * 32,
                    (double)N * H * W * Cin * (x_is_u8 ? 1.0 : 4.0) / sub + 4.0 * (double)total * 32, s);
 #define SSAL_CF(C)                                                                                                   \
