@@ -285,6 +285,32 @@ int ssal_icnet_train_highres_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u
 /* ssal_icnet_update_fusion for the 23 variables: only the eight trained layers are re-laid-out, folded and uploaded */
 int ssal_icnet_update_highres(ssal_icnet *net, const float *params_host, void *stream);
 
+/* ---- The semi-supervised step of the high-resolution trainer ----
+ * ssal_icnet_highres_grad_nhwc / ssal_icnet_train_highres_nhwc with the semi-supervised step of the cascade entries above
+ * (ssal_icnet_cascade_grad_semi_nhwc: labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, their meaning,
+ * determinism and statuses).  The raw side is conv5_4_k1_raw_dev, conv3_1_raw_dev and the undistorted frames x_raw_dev (the dtype
+ * of x_dev), all three or none (else SSAL_EINVAL); with it the pseudo annotation of an unlabelled image comes from the logits of
+ * the undistorted frames under params_dev: the branch (conv1_sub1 + conv2_sub1 as one launch where the forward path's fused
+ * front applies -- knob "ic_front" bit 0 -- with the same bits as the separate launches), both fusion blocks and the head run on
+ * them first, through the same workspace slots as the training frames after them.  The loss and the 23 gradients are the bits
+ * the plain entries give on the composed targets.  The workspace is the plain entries' plus what the cascade semi entries add
+ * to theirs at the same n, h, w, classes; the queries return -1 wherever the plain ones do. */
+int64_t ssal_icnet_highres_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw);
+int ssal_icnet_highres_grad_semi_nhwc(const float *conv5_4_k1_dev, const float *conv3_1_dev, const void *x_dev,
+                                      const float *conv5_4_k1_raw_dev, const float *conv3_1_raw_dev, const void *x_raw_dev,
+                                      int n, int h, int w, int classes, const float *params_dev, const uint8_t *labels_dev,
+                                      const float *mask_dev, const uint8_t *labelled_dev, int measure, float threshold,
+                                      float weight, float label_smoothing, const float *stats_dev, int x_is_u8, int c_in,
+                                      int max_workgroups, double *loss_dev, float *grad_dev, int64_t *confusion_dev,
+                                      int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream);
+int64_t ssal_icnet_train_highres_semi_workspace_bytes(const ssal_icnet *net, int n, int h, int w, int with_raw);
+int ssal_icnet_train_highres_semi_nhwc(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h,
+                                       int w, const uint8_t *labels_dev, const float *mask_dev, const uint8_t *labelled_dev,
+                                       int measure, float threshold, const float *params_dev, float weight,
+                                       float label_smoothing, const float *stats_dev, int max_workgroups, double *loss_dev,
+                                       float *grad_dev, int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev,
+                                       int64_t ws_bytes, void *stream);
+
 /* Stand-alone fused convolution (the operator every ICNet layer is built from; also the per-block parity hook):
  * y = [relu]( BN(conv2d(x, kernel HWIO, strides s, dilations d, "SAME")) [+ res] ), BN given as mean / variance /
  * gamma / beta (all NULL: no batch-norm; bias_dev optional).  upsample2x != 0 runs the conv on
@@ -344,6 +370,10 @@ int ssal_conv_bn_act_arith(const float *x_dev, int n, int h, int w, int cin, con
 #define SSAL_ICNET_KERNEL_CONV_FIRST        5  /* k_conv_first (cin 1, 3 or 4) */
 int ssal_icnet_debug_conv_dispatch(int n, int h, int w, int cin, int cout, int kh, int kw, int stride, int dil, int up2,
                                    int has_res, int arithmetic, int *kernel_out, int *nt_out);
+/* Host-only, no device is touched: which route the raw side of the semi-supervised high-resolution entries (above) takes for
+ * conv1_sub1 + conv2_sub1 on n frames of 32h x 32w x c_in under the current knobs -- *fused_out = 1: one launch (k_front2),
+ * 0: the two separate launches.  The statuses of the entries' dims check (SSAL_EINVAL beyond their limit or at c_in not 3 / 4). */
+int ssal_icnet_debug_highres_raw_route(int c_in, int n, int h, int w, int *fused_out);
 
 #ifdef __cplusplus
 }

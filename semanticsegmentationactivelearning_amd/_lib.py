@@ -221,6 +221,14 @@ PROTOTYPES = {
     "ssal_icnet_train_highres_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
     "ssal_icnet_train_highres_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
     "ssal_icnet_update_highres": (_i, [_vp, _vp, _vp]),
+    # ---- its semi-supervised step ----
+    "ssal_icnet_highres_grad_semi_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
+    "ssal_icnet_highres_grad_semi_nhwc": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _f,
+                                               _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_icnet_train_highres_semi_workspace_bytes": (_i64, [_vp, _i, _i, _i, _i]),
+    "ssal_icnet_train_highres_semi_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _f, _f, _vp, _i, _vp,
+                                                _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_icnet_debug_highres_raw_route": (_i, [_i, _i, _i, _i, _c.POINTER(_i)]),
     # ---- PNG decode (include/ssal_enet.h) ----
     "ssal_png_plan": (_i64, [_i64, _vp]),
     "ssal_png_decode_nhwc": (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
@@ -595,6 +603,15 @@ def icnet_conv_dispatch(n, h, w, cin, cout, k, stride=1, dilation=1, upsample2x=
                                                int(dilation), int(bool(upsample2x)), int(bool(residual)),
                                                arithmetic_code(arithmetic), _c.byref(kern), _c.byref(nt)))
     return ICNET_CONV_KERNELS[kern.value], nt.value
+
+
+def icnet_highres_raw_route(c_in, n, h32, w32):
+    """host-only: "fused" (conv1_sub1 + conv2_sub1 as one k_front2 launch) or "unfused" -- the route the raw side of the
+    semi-supervised high-resolution trainer takes for n frames of 32 h32 x 32 w32 x c_in under the current knobs
+    (include/ssal_icnet.h: ssal_icnet_debug_highres_raw_route).  Needs no GPU."""
+    out = _c.c_int(-1)
+    check(lib().ssal_icnet_debug_highres_raw_route(int(c_in), int(n), int(h32), int(w32), _c.byref(out)))
+    return "fused" if out.value else "unfused"
 
 
 def layer_dispatch(kind, cin, cout, f, asym, h, w, arithmetic="f32"):

@@ -1222,11 +1222,12 @@ IcnetHighresWs highres_carve(Bump &b, int64_t n, int h32, int w32, int classes, 
     return t;
 }
 
-int64_t highres_bytes(int64_t front, int n, int h32, int w32, int classes, bool own_acts)
+int64_t highres_bytes(int64_t front, int n, int h32, int w32, int classes, bool own_acts, bool semi, bool with_raw)
 {
     Bump b(nullptr, 0);
     b.off = front;
     (void)highres_carve(b, n, h32, w32, classes, own_acts);
+    (void)semi_carve(b, n, 4 * h32, 4 * w32, classes, semi, with_raw);
     return b.off + 256;
 }
 
@@ -1250,54 +1251,78 @@ int highres_check(int n, int h32, int w32, int classes, int c_in, int max_workgr
     return SSAL_OK;
 }
 
-// c54 [n,h32,w32,256] / c31 [n,2 h32,2 w32,256]: conv5_4_k1 and conv3_1 of the training frames x [n,32 h32,32 w32,c_in], which
-// trunk(false) brings about (an images entry) or the caller has
+// c54 [n,h32,w32,256] / c31 [n,2 h32,2 w32,256]: conv5_4_k1 and conv3_1 of the training frames x [n,32 h32,32 w32,c_in], *_raw:
+// of the undistorted frames x_raw (all or none); trunk and the slots as for cascade_run, with the branch
 template <typename Trunk>
-int highres_run(Trunk trunk, const float *c54, const float *c31, const void *x, bool x_is_u8, int c_in, int n, int h32, int w32,
-                int classes, const float *params_dev, const float *stats_dev, int max_workgroups, const CallArgs &a,
-                const IcnetHighresWs &t)
+int highres_run(Trunk trunk, const float *c54, const float *c31, const void *x, const float *c54_raw, const float *c31_raw,
+                const void *x_raw, bool x_is_u8, int c_in, int n, int h32, int w32, int classes, const float *params_dev,
+                const float *stats_dev, int max_workgroups, const CallArgs &a, const SemiArgs *semi, const IcnetHighresWs &t,
+                const SemiWs &sw)
 {
+    const uint8_t *tgt = nullptr;
+    if (wants_targets(c54_raw, semi)) {
+        if (int rc = trunk(true)) return rc;
+        HIP_TRY(launch_icnet_highres_targets(c54_raw, c31_raw, x_raw, x_is_u8, c_in, n, h32, w32, classes, params_dev, stats_dev,
+                                             max_workgroups, t, semi_of_targets(*semi), sw.tgt, a.s));
+        tgt = sw.tgt;
+    }
     if (int rc = trunk(false)) return rc;
-    HIP_TRY(launch_icnet_highres_grad(c54, c31, x, x_is_u8, c_in, n, h32, w32, classes, params_dev, stats_dev, a.labels, a.mask,
-                                      a.weight, a.label_smoothing, max_workgroups, t, a.loss, a.grad, a.s));
-    return SSAL_OK;
+    return with_confusion(sw.rep, classes, semi ? semi->confusion : nullptr, a.s, [&](unsigned long long *rep, int reps) -> int {
+        IcnetHeadSemi sa = {};
+        if (semi) sa = semi_of_grad(*semi, tgt, rep, reps);
+        HIP_TRY(launch_icnet_highres_grad(c54, c31, x, x_is_u8, c_in, n, h32, w32, classes, params_dev, stats_dev, a.labels,
+                                          a.mask, a.weight, a.label_smoothing, max_workgroups, t, a.loss, a.grad, a.s,
+                                          semi ? &sa : nullptr));
+        return SSAL_OK;
+    });
 }
 
-int highres_grad_entry(const float *conv5_4_k1_dev, const float *conv3_1_dev, const void *x_dev, int x_is_u8, int c_in, int n,
-                       int h, int w, int classes, const float *params_dev, const float *stats_dev, int max_workgroups,
-                       const CallArgs &a)
+int highres_grad_entry(const float *conv5_4_k1_dev, const float *conv3_1_dev, const void *x_dev, const float *conv5_4_k1_raw_dev,
+                       const float *conv3_1_raw_dev, const void *x_raw_dev, int x_is_u8, int c_in, int n, int h, int w,
+                       int classes, const float *params_dev, const float *stats_dev, int max_workgroups, const CallArgs &a,
+                       const SemiArgs *semi)
 {
     if (int rc = highres_check(n, h, w, classes, c_in, max_workgroups)) return rc;
-    if (int rc = args_check(conv5_4_k1_dev && conv3_1_dev && x_dev && params_dev && stats_dev, a, nullptr)) return rc;
+    if (int rc = args_check(conv5_4_k1_dev && conv3_1_dev && x_dev && params_dev && stats_dev, a, semi)) return rc;
+    const bool raw = conv5_4_k1_raw_dev != nullptr;
+    if (int rc = raw_all_or_none((conv5_4_k1_raw_dev != nullptr) + (conv3_1_raw_dev != nullptr) + (x_raw_dev != nullptr), 3))
+        return rc;
     Bump b(a.ws, a.ws_bytes);
     const IcnetHighresWs t = highres_carve(b, n, h, w, classes, true);
-    if (int rc = ws_check(highres_bytes(0, n, h, w, classes, true), b, a)) return rc;
-    return highres_run(no_trunk, conv5_4_k1_dev, conv3_1_dev, x_dev, x_is_u8 != 0, c_in, n, h, w, classes, params_dev, stats_dev,
-                       max_workgroups, a, t);
+    const SemiWs sw = semi_carve(b, n, 4 * h, 4 * w, classes, semi != nullptr, raw);
+    if (int rc = ws_check(highres_bytes(0, n, h, w, classes, true, semi != nullptr, raw), b, a)) return rc;
+    return highres_run(no_trunk, conv5_4_k1_dev, conv3_1_dev, x_dev, conv5_4_k1_raw_dev, conv3_1_raw_dev, x_raw_dev,
+                       x_is_u8 != 0, c_in, n, h, w, classes, params_dev, stats_dev, max_workgroups, a, semi, t, sw);
 }
 
-int highres_train_entry(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w, const float *params_dev,
-                        const float *stats_dev, int max_workgroups, const CallArgs &a)
+int highres_train_entry(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h, int w,
+                        const float *params_dev, const float *stats_dev, int max_workgroups, const CallArgs &a,
+                        const SemiArgs *semi)
 {
     int rc = check_dims(net, n, h, w);
     if (rc) return rc;
     const int K = net->classes, h32 = h / 32, w32 = w / 32;
+    const bool raw = x_raw_dev != nullptr;
     if ((rc = highres_check(n, h32, w32, K, net->c_in, max_workgroups))) return rc;
-    if ((rc = args_check(x_dev && params_dev && stats_dev, a, nullptr))) return rc;
+    if ((rc = args_check(x_dev && params_dev && stats_dev, a, semi))) return rc;
     IcWorkspace W;
     Bump b = carve_behind_trunk(net, a, n, h, w, &W);
     IcnetHighresWs t = highres_carve(b, n, h32, w32, K, false);
-    if ((rc = ws_check(highres_bytes(W.bytes, n, h32, w32, K, false), b, a))) return rc;
+    const SemiWs sw = semi_carve(b, n, h / 8, w / 8, K, semi != nullptr, raw);
+    if ((rc = ws_check(highres_bytes(W.bytes, n, h32, w32, K, false, semi != nullptr, raw), b, a))) return rc;
     highres_bind(t, W);
     hipStream_t s = a.s;
-    auto backbone = [=, &W](bool) -> int {  // the two frozen branches only: run_trunk's stop in front of conv1_sub1
+    // the two frozen branches only (run_trunk's stop in front of conv1_sub1), on the undistorted or the training frames, through
+    // the same endpoints
+    auto backbone = [=, &W](bool of_raw) -> int {
         std::vector<Grp> one(1);
-        one[0] = {W, x_dev, n, s};
+        one[0] = {W, of_raw ? x_raw_dev : x_dev, n, s};
         HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false, false, false, false));
         return SSAL_OK;
     };
-    return highres_run(backbone, W.act.at("conv5_4_k1"), W.act.at("conv3_1"), x_dev, x_is_u8 != 0, net->c_in, n, h32, w32, K,
-                       params_dev, stats_dev, max_workgroups, a, t);
+    const float *c54 = W.act.at("conv5_4_k1"), *c31 = W.act.at("conv3_1");
+    return highres_run(backbone, c54, c31, x_dev, raw ? c54 : nullptr, raw ? c31 : nullptr, x_raw_dev, x_is_u8 != 0, net->c_in, n,
+                       h32, w32, K, params_dev, stats_dev, max_workgroups, a, semi, t, sw);
 }
 
 // ---- the trained variables back into the handle ----
@@ -1605,7 +1630,7 @@ SSAL_API int ssal_icnet_update_cascade(ssal_icnet *net, const float *params_host
 // ---- the high-resolution branch down to the image ----
 SSAL_API int64_t ssal_icnet_highres_grad_workspace_bytes(int n, int h, int w, int classes)
 {
-    return capped_dims_ok(n, classes, highres_fits(n, h, w)) ? highres_bytes(0, n, h, w, classes, true) : -1;
+    return capped_dims_ok(n, classes, highres_fits(n, h, w)) ? highres_bytes(0, n, h, w, classes, true, false, false) : -1;
 }
 
 SSAL_API int ssal_icnet_highres_grad_nhwc(const float *conv5_4_k1_dev, const float *conv3_1_dev, const void *x_dev, int n, int h,
@@ -1615,14 +1640,14 @@ SSAL_API int ssal_icnet_highres_grad_nhwc(const float *conv5_4_k1_dev, const flo
                                           void *ws_dev, int64_t ws_bytes, void *stream)
 {
     const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    return highres_grad_entry(conv5_4_k1_dev, conv3_1_dev, x_dev, x_is_u8, c_in, n, h, w, classes, params_dev, stats_dev,
-                              max_workgroups, a);
+    return highres_grad_entry(conv5_4_k1_dev, conv3_1_dev, x_dev, nullptr, nullptr, nullptr, x_is_u8, c_in, n, h, w, classes,
+                              params_dev, stats_dev, max_workgroups, a, nullptr);
 }
 
 SSAL_API int64_t ssal_icnet_train_highres_workspace_bytes(const ssal_icnet *net, int n, int h, int w)
 {
     if (!net_dims_ok(net, n, h, w) || !highres_fits(n, h / 32, w / 32)) return -1;
-    return highres_bytes(trunk_bytes(net, n, h, w), n, h / 32, w / 32, net->classes, false);
+    return highres_bytes(trunk_bytes(net, n, h, w), n, h / 32, w / 32, net->classes, false, false, false);
 }
 
 SSAL_API int ssal_icnet_train_highres_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
@@ -1631,7 +1656,46 @@ SSAL_API int ssal_icnet_train_highres_nhwc(ssal_icnet *net, const void *x_dev, i
                                            double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
     const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    return highres_train_entry(net, x_dev, x_is_u8, n, h, w, params_dev, stats_dev, max_workgroups, a);
+    return highres_train_entry(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, stats_dev, max_workgroups, a, nullptr);
+}
+
+SSAL_API int64_t ssal_icnet_highres_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw)
+{
+    return capped_dims_ok(n, classes, highres_fits(n, h, w)) ? highres_bytes(0, n, h, w, classes, true, true, with_raw != 0) : -1;
+}
+
+SSAL_API int ssal_icnet_highres_grad_semi_nhwc(const float *conv5_4_k1_dev, const float *conv3_1_dev, const void *x_dev,
+                                               const float *conv5_4_k1_raw_dev, const float *conv3_1_raw_dev,
+                                               const void *x_raw_dev, int n, int h, int w, int classes, const float *params_dev,
+                                               const uint8_t *labels_dev, const float *mask_dev, const uint8_t *labelled_dev,
+                                               int measure, float threshold, float weight, float label_smoothing,
+                                               const float *stats_dev, int x_is_u8, int c_in, int max_workgroups,
+                                               double *loss_dev, float *grad_dev, int64_t *confusion_dev,
+                                               int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, conv5_4_k1_raw_dev != nullptr};
+    return highres_grad_entry(conv5_4_k1_dev, conv3_1_dev, x_dev, conv5_4_k1_raw_dev, conv3_1_raw_dev, x_raw_dev, x_is_u8, c_in, n,
+                              h, w, classes, params_dev, stats_dev, max_workgroups, a, &semi);
+}
+
+SSAL_API int64_t ssal_icnet_train_highres_semi_workspace_bytes(const ssal_icnet *net, int n, int h, int w, int with_raw)
+{
+    if (!net_dims_ok(net, n, h, w) || !highres_fits(n, h / 32, w / 32)) return -1;
+    return highres_bytes(trunk_bytes(net, n, h, w), n, h / 32, w / 32, net->classes, false, true, with_raw != 0);
+}
+
+SSAL_API int ssal_icnet_train_highres_semi_nhwc(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
+                                                int h, int w, const uint8_t *labels_dev, const float *mask_dev,
+                                                const uint8_t *labelled_dev, int measure, float threshold,
+                                                const float *params_dev, float weight, float label_smoothing,
+                                                const float *stats_dev, int max_workgroups, double *loss_dev, float *grad_dev,
+                                                int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev,
+                                                int64_t ws_bytes, void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev != nullptr};
+    return highres_train_entry(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, stats_dev, max_workgroups, a, &semi);
 }
 
 SSAL_API int ssal_icnet_update_highres(ssal_icnet *net, const float *params_host, void *stream)
@@ -1789,6 +1853,14 @@ SSAL_API int ssal_icnet_debug_conv_dispatch(int n, int h, int w, int cin, int co
         return fail(SSAL_EINVAL, "no kernel takes this convolution (kernel size, or a tensor beyond the 32-bit offset limits)");
     *kernel_out = plan.kernel;
     *nt_out = plan.nt;
+    return SSAL_OK;
+}
+
+SSAL_API int ssal_icnet_debug_highres_raw_route(int c_in, int n, int h, int w, int *fused_out)
+{
+    if (!fused_out) return fail(SSAL_EINVAL, "NULL output");
+    if (int rc = highres_check(n, h, w, 2, c_in, 0)) return rc;
+    *fused_out = icnet_highres_raw_fused(c_in, n, h, w, ssal::knobs().ic_front, ssal::mfma_family()) ? 1 : 0;
     return SSAL_OK;
 }
 

@@ -63,10 +63,27 @@ struct IcnetHighresWs {
     IcnetCascadeWs cascade;
 };
 
-// loss [1] float64; grad [icnet_highres_floats(c_in, K)] fp32 in the packed order.  x: the frame, fp32 or uint8.
+// loss [1] float64; grad [icnet_highres_floats(c_in, K)] fp32 in the packed order.  x: the frame, fp32 or uint8.  semi
+// (NULL = the plain step, launch for launch): handed on to launch_icnet_cascade_grad
 hipError_t launch_icnet_highres_grad(const float *c54, const float *c31, const void *x, bool x_is_u8, int c_in, int N, int h32,
                                      int w32, int K, const float *params, const float *stats, const uint8_t *labels,
                                      const float *mask, float weight, float label_smoothing, int max_workgroups,
-                                     const IcnetHighresWs &ws, double *loss, float *grad, hipStream_t s);
+                                     const IcnetHighresWs &ws, double *loss, float *grad, hipStream_t s,
+                                     const IcnetHeadSemi *semi = nullptr);
+
+// The target phase on the undistorted frames x_raw and their backbone features: the pack, the branch on x_raw under the weights
+// being trained -> conv3_sub1_raw in ws.f3, then launch_icnet_cascade_targets on it -> tgt [N, 32 h32, 32 w32].  Nobody reads
+// the raw a_1 again, so conv1_sub1 + conv2_sub1 run as ONE launch (launch_front2, bit-identical to the two) into ws.a2 wherever
+// icnet_highres_raw_fused says so, else as the training side's launches into ws.a1 / ws.a2.  The training frames go through
+// the same slots afterwards (launch_icnet_highres_grad with semi.tgt_in = tgt).
+hipError_t launch_icnet_highres_targets(const float *c54_raw, const float *c31_raw, const void *x_raw, bool x_is_u8, int c_in,
+                                        int N, int h32, int w32, int K, const float *params, const float *stats,
+                                        int max_workgroups, const IcnetHighresWs &ws, const IcnetHeadSemi &semi, uint8_t *tgt,
+                                        hipStream_t s);
+// the raw side's route: launch_front2's own guards (front2_supported; one frame of c_in floats below 2^31 bytes; fewer than
+// 2^31 tiles of 8 x 16) on the matrix-core family, under bit 0 of the knob "ic_front".  icnet_highres_fits is the tighter
+// bound (N H W < 2^27 with c_in <= 4 keeps H W c_in 4 below 2^29), so only the knob ever sends an admitted shape to the
+// unfused route; the guards are restated all the same, so that no launch_front2 refusal can become an error of the step.
+bool icnet_highres_raw_fused(int c_in, int N, int h32, int w32, int ic_front, bool mfma);
 
 }  // namespace ssal

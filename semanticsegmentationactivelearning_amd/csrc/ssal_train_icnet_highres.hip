@@ -364,34 +364,79 @@ static hipError_t highres_fold(int G, int CI, int CO, const float *scale, const 
     return hipGetLastError();
 }
 
-hipError_t launch_icnet_highres_grad(const float *c54, const float *c31, const void *x, bool x_is_u8, int c_in, int N, int h32,
-                                     int w32, int K, const float *params, const float *stats, const uint8_t *labels,
-                                     const float *mask, float weight, float label_smoothing, int max_workgroups,
-                                     const IcnetHighresWs &ws, double *loss, float *grad, hipStream_t s)
+// the raw side's route (ssal_train_icnet_highres.h)
+bool icnet_highres_raw_fused(int c_in, int N, int h32, int w32, int ic_front, bool mfma)
 {
-    if (N < 1 || K < 2 || K > 32 || max_workgroups < 0 || (c_in != 3 && c_in != 4) || !icnet_highres_fits(N, h32, w32))
-        return hipErrorInvalidValue;
+    if (!mfma || !(ic_front & 1) || N < 1 || h32 < 1 || w32 < 1) return false;
+    const long H = 32L * h32, W = 32L * w32;
+    if (H * W * c_in * 4 >= (1L << 31)) return false;
+    if ((long)N * icnet_cdiv(H / 4, 8) * icnet_cdiv(W / 4, 16) >= (1L << 31)) return false;
+    return front2_supported((int)H, (int)W, c_in, 1, 2);
+}
+
+// the pack, then run_trunk's launches of the branch (ssal_icnet_api.hip) on the weights being trained: ws.f3 = conv3_sub1(x).
+// fused: conv1_sub1 + conv2_sub1 as one launch into ws.a2 -- ws.a1 is not written (the raw side: nobody reads it again); else
+// the separate launches, which leave a_1 in ws.a1 and a_2 in ws.a2 for the backward pass
+static hipError_t highres_forward(const void *x, bool x_is_u8, int c_in, int N, int h32, int w32, const float *params,
+                                  const float *stats, const IcnetHighresWs &ws, bool fused, hipStream_t s)
+{
     const IcnetHighresOff off = icnet_highres_offsets(c_in);
-    const int H = 32 * h32, W = 32 * w32, h2 = H / 2, w2 = W / 2, h4 = H / 4, w4 = W / 4, h8 = H / 8, w8 = W / 8;
-    const double pix2 = (double)N * h2 * w2, pix4 = (double)N * h4 * w4, pix8 = (double)N * h8 * w8;
+    const int H = 32 * h32, W = 32 * w32, h2 = H / 2, w2 = W / 2, h4 = H / 4, w4 = W / 4;
     const float *s1 = ws.rows, *t1 = ws.rows + 32, *s2 = ws.rows + 64, *t2 = ws.rows + 96, *s3 = ws.rows + 128,
                 *t3 = ws.rows + 192;
     hipError_t e;
-    // ---- forward: the pack, then run_trunk's launches of the branch on the weights being trained ----
     {
         ProfScope prof("k_icnet_highres_pack", 0.0, 8.0 * (9 * 32 * 96 + 128), s);
         hipLaunchKernelGGL(k_icnet_highres_pack, dim3(icnet_cdiv(9 * 32 * 96 + 128, 256)), dim3(256), 0, s, params, off, stats,
                            ws.wt2, ws.wt3, ws.rows);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    if ((e = launch_conv_first(x, x_is_u8, N, H, W, c_in, 1, params + off.k1, s1, t1, ws.a1, s)) != hipSuccess) return e;
-    if ((e = launch_igemm(ws.a1, N, h2, w2, 32, ws.wt2, 3, 3, 32, 2, 1, s2, t2, nullptr, true, false, ws.a2, s)) != hipSuccess)
-        return e;
-    if ((e = launch_igemm(ws.a2, N, h4, w4, 32, ws.wt3, 3, 3, 64, 2, 1, s3, t3, nullptr, true, false, ws.f3, s)) != hipSuccess)
-        return e;
+    if (fused) {
+        e = launch_front2(x, x_is_u8, N, H, W, c_in, 1, params + off.k1, s1, t1, ws.wt2, s2, t2, 2, ws.a2, s);
+        if (e != hipSuccess) return e;
+    } else {
+        if ((e = launch_conv_first(x, x_is_u8, N, H, W, c_in, 1, params + off.k1, s1, t1, ws.a1, s)) != hipSuccess) return e;
+        e = launch_igemm(ws.a1, N, h2, w2, 32, ws.wt2, 3, 3, 32, 2, 1, s2, t2, nullptr, true, false, ws.a2, s);
+        if (e != hipSuccess) return e;
+    }
+    return launch_igemm(ws.a2, N, h4, w4, 32, ws.wt3, 3, 3, 64, 2, 1, s3, t3, nullptr, true, false, ws.f3, s);
+}
+
+hipError_t launch_icnet_highres_targets(const float *c54_raw, const float *c31_raw, const void *x_raw, bool x_is_u8, int c_in,
+                                        int N, int h32, int w32, int K, const float *params, const float *stats,
+                                        int max_workgroups, const IcnetHighresWs &ws, const IcnetHeadSemi &semi, uint8_t *tgt,
+                                        hipStream_t s)
+{
+    if (N < 1 || K < 2 || K > 32 || max_workgroups < 0 || (c_in != 3 && c_in != 4) || !icnet_highres_fits(N, h32, w32) ||
+        !c54_raw || !c31_raw || !x_raw)
+        return hipErrorInvalidValue;
+    const IcnetHighresOff off = icnet_highres_offsets(c_in);
+    if (semi.labelled) {  // (every image labelled: no pseudo target is read)
+        const bool fused = icnet_highres_raw_fused(c_in, N, h32, w32, knobs().ic_front, mfma_family());
+        const hipError_t e = highres_forward(x_raw, x_is_u8, c_in, N, h32, w32, params, stats, ws, fused, s);
+        if (e != hipSuccess) return e;
+    }
+    return launch_icnet_cascade_targets(c54_raw, c31_raw, ws.f3, N, h32, w32, K, params + off.cascade, stats + HR_STATS_OWN,
+                                        max_workgroups, ws.cascade, semi, tgt, s);
+}
+
+hipError_t launch_icnet_highres_grad(const float *c54, const float *c31, const void *x, bool x_is_u8, int c_in, int N, int h32,
+                                     int w32, int K, const float *params, const float *stats, const uint8_t *labels,
+                                     const float *mask, float weight, float label_smoothing, int max_workgroups,
+                                     const IcnetHighresWs &ws, double *loss, float *grad, hipStream_t s, const IcnetHeadSemi *semi)
+{
+    if (N < 1 || K < 2 || K > 32 || max_workgroups < 0 || (c_in != 3 && c_in != 4) || !icnet_highres_fits(N, h32, w32))
+        return hipErrorInvalidValue;
+    const IcnetHighresOff off = icnet_highres_offsets(c_in);
+    const int H = 32 * h32, W = 32 * w32, h2 = H / 2, w2 = W / 2, h4 = H / 4, w4 = W / 4, h8 = H / 8, w8 = W / 8;
+    const double pix2 = (double)N * h2 * w2, pix4 = (double)N * h4 * w4, pix8 = (double)N * h8 * w8;
+    const float *s1 = ws.rows, *s2 = ws.rows + 64, *s3 = ws.rows + 128;
+    // ---- forward: the pack, then run_trunk's launches of the branch on the weights being trained; a_1 is kept ----
+    hipError_t e = highres_forward(x, x_is_u8, c_in, N, h32, w32, params, stats, ws, false, s);
+    if (e != hipSuccess) return e;
     // section 29 as it stands: both fusion blocks, the head, the loss, its fourteen gradients, g behind sub12_sum's ReLU
     e = launch_icnet_cascade_grad(c54, c31, ws.f3, N, h32, w32, K, params + off.cascade, stats + HR_STATS_OWN, labels, mask,
-                                  weight, label_smoothing, max_workgroups, ws.cascade, loss, grad + off.cascade, s);
+                                  weight, label_smoothing, max_workgroups, ws.cascade, loss, grad + off.cascade, s, semi);
     if (e != hipSuccess) return e;
     const float *scale = ws.cascade.fusion.fold + FU_PART;
     // ---- backward ----

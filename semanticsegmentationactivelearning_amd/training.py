@@ -1643,18 +1643,46 @@ class ICNetHighResTrainer(ICNetCascadeTrainer):
                       features_raw=None, confusion=None, return_pseudo_pixels=False):
         """the parent's, with the frames as the third input: they stay uint8 when they are (the entry converts them as the
         forward path does) and the entry is told their type and channel count"""
-        self._semi_call(feats[0], labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels,
-                        features_raw=features_raw)
+        semi = self._semi_call(feats[0], labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels,
+                               features_raw=features_raw)
         mw = self._check_features(*feats, labels, mask, max_workgroups)
+        raw = self._check_raw(feats, features_raw, semi)
         packed = None if step else self._packed_with(params)
         torch = _lib.require_gpu()
         x = _lib.as_device_f32(feats[0])
         xs = (x, _lib.as_device_f32(feats[1]).to(x.device), _lib.as_device_image(feats[2]).to(x.device))
+        xr = (None,) * 3
+        if semi is not None and raw is not None and any(r is not f for r, f in zip(raw, feats)):
+            xr = (_lib.as_device_f32(raw[0]).to(x.device), _lib.as_device_f32(raw[1]).to(x.device),
+                  _lib.as_device_image(raw[2]).to(x.device))
+            if xr[2].dtype != xs[2].dtype:
+                raise ValueError("features_raw: images_raw must have the dtype of images %s (got %s)" % (xs[2].dtype, xr[2].dtype))
         dev = self._device_state(x.device) if step else None
         vec = dev["w"] if step else torch.from_numpy(packed).to(x.device)
         extra = self._extra_c_args(x) + (int(xs[2].dtype == torch.uint8), int(self.net._c_in), mw)
-        loss, grad, pp = self._grad_call(xs, (None,) * 3, labels, mask, vec, None, confusion, return_pseudo_pixels, extra)
+        loss, grad, pp = self._grad_call(xs, xr, labels, mask, vec, semi, confusion, return_pseudo_pixels, extra)
         return loss, grad, pp, dev
+
+    def _check_raw(self, feats, features_raw, semi):
+        """the parent's on the triple ``(conv5_4_k1_raw, conv3_1_raw, images_raw)``: the frame is this trainer's third feature
+        input, so the raw frames come with the raw features; each member is shaped and typed like its counterpart"""
+        names = self._FEATURE_NAMES + ("images",)
+        if features_raw is None:
+            return None
+        if not isinstance(features_raw, (tuple, list)) or len(features_raw) != 3 or any(t is None for t in features_raw):
+            raise ValueError("features_raw must be the triple (conv5_4_k1_raw, conv3_1_raw, images_raw): features(images_raw) "
+                             "and the raw frames, given whole or not at all")
+        for name, t, f in zip(names, features_raw, feats):
+            if tuple(np.shape(t)) != tuple(np.shape(f)):
+                raise ValueError("features_raw: %s must have the shape of its counterpart %s (got %s)"
+                                 % (name, tuple(np.shape(f)), tuple(np.shape(t))))
+        dt, want = str(getattr(features_raw[2], "dtype", "")), str(getattr(feats[2], "dtype", ""))
+        if ("uint8" in dt) != ("uint8" in want) or not ("float" in dt or "uint8" in dt):
+            raise ValueError("features_raw: images_raw must have the dtype of images %s (got %s)" % (want, dt or "none"))
+        for name, t in zip(names[:2], features_raw[:2]):
+            if "float" not in str(getattr(t, "dtype", "")):
+                raise ValueError("features_raw: %s must be a floating-point tensor" % name)
+        return tuple(features_raw)
 
     def gradient_features(self, conv5_4_k1, conv3_1, images, labels, mask, params=None, max_workgroups=0, labelled=None,
                           confusion=None, return_pseudo_pixels=False):
@@ -1760,8 +1788,46 @@ class SemiSupervisedICNetCascadeTrainer(_SemiKeywords, ICNetCascadeTrainer):
                                       return_pseudo_pixels=return_pseudo_pixels)
 
 
+# ---- the semi-supervised step of ICNet's high-resolution trainer -----------------------------------------
+class SemiSupervisedICNetHighResTrainer(_SemiKeywords, ICNetHighResTrainer):
+    """``ICNetHighResTrainer`` with the semi-supervised step built into the head's gradient kernel (see
+    ``SemiSupervisedICNetFusionTrainer``).  ``features_raw`` is the triple ``(conv5_4_k1_raw, conv3_1_raw, images_raw)``:
+    ``features(images_raw)`` plus the undistorted frames themselves, because the frame is this trainer's third feature input;
+    it is given whole or not at all, each member shaped and typed like its counterpart (the raw frames stay uint8 when they
+    are).  With a raw side the branch, both fusion blocks and the head run on the undistorted frames first, under the variables
+    being trained.  Loss and the 23 gradients are bit-identical to ``ICNetHighResTrainer`` on the composed targets (DESIGN.md
+    section 37); with none of the keywords a call goes through the plain entry.  ``state`` / ``load_state`` are interchangeable
+    with ``ICNetHighResTrainer``'s."""
+
+    _C_FEATURES = ("ssal_icnet_highres_grad", "ssal_icnet_highres_grad_semi")
+    _C_IMAGES = ("ssal_icnet_train_highres", "ssal_icnet_train_highres_semi")
+
+    def gradient_features(self, conv5_4_k1, conv3_1, images, labels, mask, params=None, max_workgroups=0, labelled=None,
+                          measure=None, threshold=None, features_raw=None, confusion=None, return_pseudo_pixels=False):
+        """``ICNetHighResTrainer.gradient_features`` with the keywords of ``SemiSupervisedICNetFusionTrainer``'s;
+        ``features_raw``: ``(conv5_4_k1_raw, conv3_1_raw, images_raw)``"""
+        return self._gradient_from((conv5_4_k1, conv3_1, images), labels, mask, params, max_workgroups, labelled=labelled,
+                                   measure=measure, threshold=threshold, features_raw=features_raw, confusion=confusion,
+                                   return_pseudo_pixels=return_pseudo_pixels)
+
+    def step_features(self, conv5_4_k1, conv3_1, images, labels, mask, max_workgroups=0, labelled=None, measure=None,
+                      threshold=None, features_raw=None, confusion=None, return_pseudo_pixels=False):
+        """one Adam step from cached backbone features and the frames; the keywords are those of ``gradient_features``"""
+        return self._step_from((conv5_4_k1, conv3_1, images), labels, mask, max_workgroups, labelled=labelled,
+                               measure=measure, threshold=threshold, features_raw=features_raw, confusion=confusion,
+                               return_pseudo_pixels=return_pseudo_pixels)
+
+    def step(self, images, labels, mask, max_workgroups=0, labelled=None, measure=None, threshold=None, images_raw=None,
+             confusion=None, return_pseudo_pixels=False):
+        """``SemiSupervisedICNetFusionTrainer.step`` for the high-resolution trainer: with ``images_raw`` the two frozen
+        backbone branches run on the undistorted frames first, then the branch and the head being trained"""
+        return self._step_from_images(images, labels, mask, max_workgroups, labelled=labelled, measure=measure,
+                                      threshold=threshold, images_raw=images_raw, confusion=confusion,
+                                      return_pseudo_pixels=return_pseudo_pixels)
+
+
 __all__ = ["FinalLayerTrainer", "LastBlockTrainer", "LastStageTrainer", "DecoderTailTrainer", "SemiSupervisedBlockTrainer",
            "SemiSupervisedStageTrainer", "SemiSupervisedTailTrainer", "DeepTailTrainer", "SemiSupervisedDeepTailTrainer",
            "DecoderTrainer", "SemiSupervisedDecoderTrainer", "ICNetHeadTrainer", "SemiSupervisedICNetHeadTrainer",
            "ICNetFusionTrainer", "ICNetCascadeTrainer", "SemiSupervisedICNetFusionTrainer",
-           "SemiSupervisedICNetCascadeTrainer", "ICNetHighResTrainer"]
+           "SemiSupervisedICNetCascadeTrainer", "ICNetHighResTrainer", "SemiSupervisedICNetHighResTrainer"]
