@@ -815,54 +815,20 @@ SSAL_API int ssal_icnet_endpoint_valid_after_score(const ssal_icnet *net, const 
 }
 
 // ------------------------------------------------------------------------------------------------
-// Training of ICNet's tail over a frozen trunk (include/ssal_icnet.h; DESIGN.md sections 23, 25 and 28-30).  Three depths --
-// the output layer (head), the last fusion stage, the whole cascade head -- each entered from cached features or from images,
-// plain or semi-supervised.  Every depth has ONE carve function, ONE byte count (the queries and the entries' workspace check
-// both read it) and ONE body (head_run, fusion_run, cascade_run) that takes the features, the features of the undistorted
-// frames and an optional SemiArgs; its features wrapper (*_grad_entry) and its images wrapper (*_train_entry) validate (dims,
-// then semi arguments, then NULL pointers, then raw all-or-none, then the workspace size, all before any launch), carve and
-// call it.  The public entries pack their arguments and call a wrapper.  The shared steps are ssal_train_host.h's, as for ENet.
+// Training of ICNet's tail over a frozen trunk (include/ssal_icnet.h; DESIGN.md sections 23, 25, 28-30, 32, 37 and 38).  Four
+// depths -- the output layer (head), the last fusion stage, the whole cascade head, the high-resolution branch down to the image
+// -- each entered from cached features or from images, plain or semi-supervised.  Every depth is ONE description (HeadDepth,
+// FusionDepth, CascadeDepth, HighresDepth), which states what differs and contains the depth above it.  What is done with a
+// description is written once: depth_carve and depth_bytes (the queries and the entries' workspace check both read it), the
+// body depth_run (the features, the features of the undistorted frames, an optional SemiArgs), its features wrapper
+// features_entry and its images wrapper images_entry, which validate (dims, then the capped-dims check, then semi arguments and
+// NULL pointers, then raw all-or-none, then the workspace size, all before any launch), carve and call it, and the two
+// workspace queries features_query and images_query.  The public entries pack their arguments and call a wrapper.  The shared
+// steps are ssal_train_host.h's, as for ENet.
 // ------------------------------------------------------------------------------------------------
 namespace {
 
 // ---- the steps the entries share ----
-bool net_dims_ok(const ssal_icnet *net, int n, int h, int w)
-{
-    return net && net->committed && n > 0 && h > 0 && w > 0 && h % 32 == 0 && w % 32 == 0;
-}
-
-int64_t trunk_bytes(const ssal_icnet *net, int n, int h, int w) { return carve(net, nullptr, 0, n, h, w).bytes; }
-
-// carves the forward workspace into W and returns a Bump positioned behind it (not ok when W is not)
-Bump carve_behind_trunk(const ssal_icnet *net, const CallArgs &a, int n, int h, int w, IcWorkspace *W)
-{
-    *W = carve(net, a.ws, a.ws_bytes, n, h, w);
-    Bump b(a.ws, a.ws_bytes);
-    b.off = W->bytes;
-    b.ok = W->ok;
-    return b;
-}
-
-// the frozen trunk of an images entry, on the undistorted (of_raw) or the training frames, through the same slots of W.  It
-// ends in front of the layers being trained (run_trunk: head = false; fusion / cascade as the depth says)
-auto frozen_trunk(const ssal_icnet *net, const IcWorkspace &W, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
-                  int h, int w, hipStream_t s, bool fusion, bool cascade)
-{
-    return [=, &W](bool of_raw) -> int {
-        std::vector<Grp> one(1);
-        one[0] = {W, of_raw ? x_raw_dev : x_dev, n, s};
-        HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false, fusion, cascade));
-        return SSAL_OK;
-    };
-}
-
-// the raw pointers of a features entry come all or none
-int raw_all_or_none(int given, int of)
-{
-    if (given != 0 && given != of) return fail(SSAL_EINVAL, "the raw feature pointers must be given together (%d of %d)", given, of);
-    return SSAL_OK;
-}
-
 // what a semi call adds behind the plain pieces (DESIGN.md sections 25 and 30): the confusion replicas, then (with_raw) the
 // packed pseudo-target plane of the undistorted frames, one byte per loss pixel.  Plain: nothing.
 struct SemiWs {
@@ -890,439 +856,318 @@ IcnetHeadSemi semi_of_grad(const SemiArgs &semi, const uint8_t *tgt, unsigned lo
     return {semi.labelled, semi.measure, semi.threshold, tgt, nullptr, rep, reps, (unsigned long long *)semi.pseudo_pixels};
 }
 
-// the undistorted frames' features matter only where an image is unlabelled
-bool wants_targets(const void *raw, const SemiArgs *semi) { return raw && semi && semi->labelled; }
+// what a gradient call is given besides CallArgs: its feature maps in the depth's own order, of the training frames (f) and of
+// the undistorted ones (raw: all or none), which the trunk brings about (an images entry: one after the other in the same
+// endpoints) or the caller has; the packed variables and the frozen moving statistics (the head has none); the grid cap; the
+// dims, h and w in the depth's unit; and, where the frame itself is the last input, its type and channel count
+struct DepthIn {
+    const void *f[3], *raw[3];
+    const float *params, *stats;
+    int max_workgroups, n, h, w, classes;
+    bool x_is_u8 = false;
+    int c_in = 0;
+};
 
-// ---- the output layer (DESIGN.md sections 23 and 25; kernels: ssal_train_icnet.hip) ----
-// the buffers of one gradient call behind `b`; own_acts: the logits live here (the images entry keeps them in the network's
-// conv6_cls endpoint instead)
-IcnetHeadWs head_carve(Bump &b, int64_t n, int h8, int w8, int classes, bool own_acts)
+const float *F(const void *p) { return static_cast<const float *>(p); }
+
+// ---- the four descriptions.  Each states: Ws and carve (the buffers of one gradient call behind `b`, in carve order; own_acts:
+// the activations live here, where an images entry keeps them in the network's endpoints and bind points at those); fits and
+// kNoun (its own limit and what the message calls it); kUnit (frame pixels per feature pixel and axis); kEndpoints (its feature
+// inputs, in order; kFrame: then the frame); kLevel (where an images entry's frozen trunk stops); kStats (the entries take the
+// frozen statistics); kImagesQueryFits (the images queries judge fits too); targets / grad (its launcher pair: the target
+// launch runs the trained layers on the raw features into t's slots and leaves one byte per loss pixel, then the training
+// features go through the same slots) ----
+
+// the output layer (DESIGN.md sections 23 and 25; kernels: ssal_train_icnet.hip): sub12_sum [n,h8,w8,128]
+struct HeadDepth {
+    using Ws = IcnetHeadWs;
+    static constexpr int kUnit = 8, kLevel = 0;
+    static constexpr bool kStats = false, kFrame = false, kImagesQueryFits = false;
+    static constexpr const char *kNoun = "head gradient kernel's", *kEndpoints[] = {"sub12_sum"};
+
+    static Ws carve(Bump &b, int64_t n, int h8, int w8, int classes, bool own_acts)
+    {
+        Ws t;
+        t.lq = own_acts ? b.take<float>(n * (2 * (int64_t)h8) * (2 * (int64_t)w8) * classes) : nullptr;
+        t.wt = b.take<float>(icnet_head_ws_floats_wt());
+        const int64_t G = IH_MAX_WG;  // (sized for the default grid: max_workgroups only lowers it)
+        t.part = b.take<float>(G * icnet_head_floats(classes));
+        t.lpart = b.take<double>(2 * G);
+        return t;
+    }
+    static void bind(Ws &t, const IcWorkspace &W) { t.lq = W.act.at("conv6_cls"); }
+    static bool fits(int n, int h8, int w8) { return icnet_head_fits(h8, w8) && (double)n * h8 * w8 <= 1099511627776.0; }
+    static hipError_t targets(const DepthIn &in, const Ws &t, const IcnetHeadSemi &sa, uint8_t *tgt, hipStream_t s)
+    {
+        return launch_icnet_head_targets(F(in.raw[0]), in.n, in.h, in.w, in.classes, in.params, in.max_workgroups, t, sa, tgt, s);
+    }
+    static hipError_t grad(const DepthIn &in, const CallArgs &a, const Ws &t, const IcnetHeadSemi *sa)
+    {
+        return launch_icnet_head_grad(F(in.f[0]), in.n, in.h, in.w, in.classes, in.params, a.labels, a.mask, a.weight,
+                                      a.label_smoothing, in.max_workgroups, t, a.loss, a.grad, a.s, sa);
+    }
+};
+
+// the last fusion stage (DESIGN.md sections 28 and 30; kernels: ssal_train_icnet_fusion.hip): sub24_sum [n,h16,w16,128] and
+// conv3_sub1 [n,2 h16,2 w16,64]; an images entry's block and head write conv3_sub1_proj, sub12_sum and conv6_cls
+struct FusionDepth {
+    using Ws = IcnetFusionWs;
+    static constexpr int kUnit = 16, kLevel = 1;
+    static constexpr bool kStats = true, kFrame = false, kImagesQueryFits = false;
+    static constexpr const char *kNoun = "fusion gradient kernels'", *kEndpoints[] = {"sub24_sum", "conv3_sub1"};
+
+    static Ws carve(Bump &b, int64_t n, int h16, int w16, int classes, bool own_acts)
+    {
+        Ws t;
+        const int h8 = 2 * h16, w8 = 2 * w16;
+        const int64_t act = n * h8 * (int64_t)w8 * 128;
+        t.wt_a = b.take<float>(FU_GA);
+        t.wt_b = b.take<float>(64 * 128);
+        t.rows = b.take<float>(512);
+        t.proj = own_acts ? b.take<float>(act) : nullptr;
+        t.sub12 = own_acts ? b.take<float>(act) : nullptr;
+        t.g = b.take<float>(act);
+        t.hw = b.take<float>(n * icnet_head_tiles(h8, w8) * 36 * classes);
+        t.part = b.take<float>((int64_t)FU_MAX_WG * FU_PART);  // (sized for the default grid: max_workgroups only lowers it)
+        t.fold = b.take<float>(FU_PART + 64);
+        t.head = HeadDepth::carve(b, n, h8, w8, classes, own_acts);
+        return t;
+    }
+    static void bind(Ws &t, const IcWorkspace &W)
+    {
+        t.proj = W.act.at("conv3_sub1_proj");
+        t.sub12 = W.act.at("sub12_sum");
+        HeadDepth::bind(t.head, W);
+    }
+    static bool fits(int n, int h16, int w16) { return icnet_fusion_fits(h16, w16) && (double)n * h16 * w16 <= 274877906944.0; }
+    static hipError_t targets(const DepthIn &in, const Ws &t, const IcnetHeadSemi &sa, uint8_t *tgt, hipStream_t s)
+    {
+        return launch_icnet_fusion_targets(F(in.raw[0]), F(in.raw[1]), in.n, in.h, in.w, in.classes, in.params, in.stats,
+                                           in.max_workgroups, t, sa, tgt, s);
+    }
+    static hipError_t grad(const DepthIn &in, const CallArgs &a, const Ws &t, const IcnetHeadSemi *sa)
+    {
+        return launch_icnet_fusion_grad(F(in.f[0]), F(in.f[1]), in.n, in.h, in.w, in.classes, in.params, in.stats, a.labels, a.mask,
+                                        a.weight, a.label_smoothing, in.max_workgroups, t, a.loss, a.grad, a.s, sa);
+    }
+};
+
+// the whole cascade head (DESIGN.md sections 29 and 30; kernels: ssal_train_icnet_cascade.hip): conv5_4_k1 [n,h32,w32,256],
+// conv3_1 [n,2 h32,2 w32,256] and conv3_sub1 [n,4 h32,4 w32,64]; an images entry's two blocks and head write the endpoints from
+// conv3_1_sub2_proj on
+struct CascadeDepth {
+    using Ws = IcnetCascadeWs;
+    static constexpr int kUnit = 32, kLevel = 2;
+    static constexpr bool kStats = true, kFrame = false, kImagesQueryFits = false;
+    static constexpr const char *kNoun = "cascade gradient kernels'", *kEndpoints[] = {"conv5_4_k1", "conv3_1", "conv3_sub1"};
+
+    static Ws carve(Bump &b, int64_t n, int h32, int w32, int classes, bool own_acts)
+    {
+        Ws t;
+        const int h16 = 2 * h32, w16 = 2 * w32;
+        const int64_t act = n * h16 * (int64_t)w16 * 128;
+        t.wt_c = b.take<float>(CA_GC);
+        t.wt_d = b.take<float>(256 * 128);
+        t.rows = b.take<float>(512);
+        t.proj = own_acts ? b.take<float>(act) : nullptr;
+        t.sub24 = own_acts ? b.take<float>(act) : nullptr;
+        t.du = b.take<float>(4 * act);
+        t.g24 = b.take<float>(act);
+        t.part = b.take<float>((int64_t)CA_MAX_WG * CA_PART);  // (sized for the default grid: max_workgroups only lowers it)
+        t.fold = b.take<float>(CA_PART);
+        t.fusion = FusionDepth::carve(b, n, h16, w16, classes, own_acts);
+        return t;
+    }
+    static void bind(Ws &t, const IcWorkspace &W)
+    {
+        t.proj = W.act.at("conv3_1_sub2_proj");
+        t.sub24 = W.act.at("sub24_sum");
+        FusionDepth::bind(t.fusion, W);
+    }
+    static bool fits(int n, int h32, int w32) { return icnet_cascade_fits(h32, w32) && FusionDepth::fits(n, 2 * h32, 2 * w32); }
+    static hipError_t targets(const DepthIn &in, const Ws &t, const IcnetHeadSemi &sa, uint8_t *tgt, hipStream_t s)
+    {
+        return launch_icnet_cascade_targets(F(in.raw[0]), F(in.raw[1]), F(in.raw[2]), in.n, in.h, in.w, in.classes, in.params,
+                                            in.stats, in.max_workgroups, t, sa, tgt, s);
+    }
+    static hipError_t grad(const DepthIn &in, const CallArgs &a, const Ws &t, const IcnetHeadSemi *sa)
+    {
+        return launch_icnet_cascade_grad(F(in.f[0]), F(in.f[1]), F(in.f[2]), in.n, in.h, in.w, in.classes, in.params, in.stats,
+                                         a.labels, a.mask, a.weight, a.label_smoothing, in.max_workgroups, t, a.loss, a.grad, a.s, sa);
+    }
+};
+
+// the high-resolution branch down to the image (DESIGN.md sections 32 and 37; kernels: ssal_train_icnet_highres.hip): conv5_4_k1
+// [n,h32,w32,256], conv3_1 [n,2 h32,2 w32,256] and the frame x [n,32 h32,32 w32,c_in], c_in 3 or 4; the trunk of an images entry
+// is the two frozen branches only, and its branch, blocks and head write conv1_sub1 / conv2_sub1 / conv3_sub1 / ...
+struct HighresDepth {
+    using Ws = IcnetHighresWs;
+    static constexpr int kUnit = 32, kLevel = 3;
+    static constexpr bool kStats = true, kFrame = true, kImagesQueryFits = true;
+    static constexpr const char *kNoun = "high-resolution gradient kernels'", *kEndpoints[] = {"conv5_4_k1", "conv3_1"};
+
+    static Ws carve(Bump &b, int64_t n, int h32, int w32, int classes, bool own_acts)
+    {
+        Ws t;
+        const int64_t px8 = n * (4 * (int64_t)h32) * (4 * (int64_t)w32);
+        t.wt2 = b.take<float>(9 * 32 * 32);
+        t.wt3 = b.take<float>(9 * 32 * 64);
+        t.rows = b.take<float>(256);
+        t.a1 = own_acts ? b.take<float>(16 * px8 * 32) : nullptr;
+        t.a2 = own_acts ? b.take<float>(4 * px8 * 32) : nullptr;
+        t.f3 = own_acts ? b.take<float>(px8 * 64) : nullptr;
+        t.gz3 = b.take<float>(px8 * 64);
+        t.gz2 = b.take<float>(4 * px8 * 32);
+        t.gz1 = b.take<float>(16 * px8 * 32);
+        t.part = b.take<float>((int64_t)HR_MAX_WG * HR_PART);  // (sized for the default grid: max_workgroups only lowers it)
+        t.fold = b.take<float>(HR_PART);
+        t.cascade = CascadeDepth::carve(b, n, h32, w32, classes, own_acts);
+        return t;
+    }
+    static void bind(Ws &t, const IcWorkspace &W)
+    {
+        t.a1 = W.act.at("conv1_sub1");
+        t.a2 = W.act.at("conv2_sub1");
+        t.f3 = W.act.at("conv3_sub1");
+        CascadeDepth::bind(t.cascade, W);
+    }
+    static bool fits(int n, int h32, int w32) { return icnet_highres_fits(n, h32, w32) && CascadeDepth::fits(n, h32, w32); }
+    static hipError_t targets(const DepthIn &in, const Ws &t, const IcnetHeadSemi &sa, uint8_t *tgt, hipStream_t s)
+    {
+        return launch_icnet_highres_targets(F(in.raw[0]), F(in.raw[1]), in.raw[2], in.x_is_u8, in.c_in, in.n, in.h, in.w,
+                                            in.classes, in.params, in.stats, in.max_workgroups, t, sa, tgt, s);
+    }
+    static hipError_t grad(const DepthIn &in, const CallArgs &a, const Ws &t, const IcnetHeadSemi *sa)
+    {
+        return launch_icnet_highres_grad(F(in.f[0]), F(in.f[1]), in.f[2], in.x_is_u8, in.c_in, in.n, in.h, in.w, in.classes, in.params,
+                                         in.stats, a.labels, a.mask, a.weight, a.label_smoothing, in.max_workgroups, t, a.loss, a.grad,
+                                         a.s, sa);
+    }
+};
+
+// ---- what is done with a description D, once.  h, w: in D's unit ----
+template <typename D>
+constexpr int feature_inputs() { return (int)(sizeof(D::kEndpoints) / sizeof(D::kEndpoints[0])) + D::kFrame; }
+
+template <typename D>
+struct DepthWs {
+    typename D::Ws t;
+    SemiWs sw;
+};
+
+template <typename D>
+DepthWs<D> depth_carve(Bump &b, int n, int h, int w, int classes, bool own_acts, bool semi, bool with_raw)
 {
-    IcnetHeadWs t;
-    t.lq = own_acts ? b.take<float>(n * (2 * (int64_t)h8) * (2 * (int64_t)w8) * classes) : nullptr;
-    t.wt = b.take<float>(icnet_head_ws_floats_wt());
-    const int64_t G = IH_MAX_WG;  // (sized for the default grid: max_workgroups only lowers it)
-    t.part = b.take<float>(G * icnet_head_floats(classes));
-    t.lpart = b.take<double>(2 * G);
-    return t;
+    DepthWs<D> c;
+    c.t = D::carve(b, n, h, w, classes, own_acts);
+    c.sw = semi_carve(b, n, D::kUnit / 8 * h, D::kUnit / 8 * w, classes, semi, with_raw);
+    return c;
 }
 
 // front: the bytes ahead of the call's own pieces (an images entry: the forward workspace)
-int64_t head_bytes(int64_t front, int n, int h8, int w8, int classes, bool own_acts, bool semi, bool with_raw)
+template <typename D>
+int64_t depth_bytes(int64_t front, int n, int h, int w, int classes, bool own_acts, bool semi, bool with_raw)
 {
     Bump b(nullptr, 0);
     b.off = front;
-    (void)head_carve(b, n, h8, w8, classes, own_acts);
-    (void)semi_carve(b, n, h8, w8, classes, semi, with_raw);
+    (void)depth_carve<D>(b, n, h, w, classes, own_acts, semi, with_raw);
     return b.off + 256;
 }
 
-// the images entry: the logits of the head being trained are this call's conv6_cls endpoint
-void head_bind(IcnetHeadWs &t, const IcWorkspace &W) { t.lq = W.act.at("conv6_cls"); }
-
-bool head_fits(int n, int h8, int w8) { return icnet_head_fits(h8, w8) && (double)n * h8 * w8 <= 1099511627776.0; }
-
-int head_check(int n, int h8, int w8, int classes, int max_workgroups)
+// (n <= 0 is capped_dims_check's first message, so the limit, which the high-resolution depth states of n too, is not asked)
+template <typename D>
+int depth_check(int n, int h, int w, int classes, int c_in, int max_workgroups)
 {
-    return capped_dims_check(n, h8, w8, classes, max_workgroups, head_fits(n, h8, w8), "head gradient kernel's");
-}
-
-// sub12 / sub12_raw [n,h8,w8,128]: sub12_sum of the training / the undistorted frames, which trunk(raw) brings about (an images
-// entry: one after the other in the same endpoint) or the caller has.  The target launch leaves one byte per loss pixel, so the
-// training features can go through the same t.lq afterwards.
-template <typename Trunk>
-int head_run(Trunk trunk, const float *sub12, const float *sub12_raw, int n, int h8, int w8, int classes, const float *head_dev,
-             int max_workgroups, const CallArgs &a, const SemiArgs *semi, const IcnetHeadWs &t, const SemiWs &sw)
-{
-    const uint8_t *tgt = nullptr;
-    if (wants_targets(sub12_raw, semi)) {
-        if (int rc = trunk(true)) return rc;
-        HIP_TRY(launch_icnet_head_targets(sub12_raw, n, h8, w8, classes, head_dev, max_workgroups, t, semi_of_targets(*semi),
-                                          sw.tgt, a.s));
-        tgt = sw.tgt;
-    }
-    if (int rc = trunk(false)) return rc;
-    return with_confusion(sw.rep, classes, semi ? semi->confusion : nullptr, a.s, [&](unsigned long long *rep, int reps) -> int {
-        IcnetHeadSemi sa = {};
-        if (semi) sa = semi_of_grad(*semi, tgt, rep, reps);
-        HIP_TRY(launch_icnet_head_grad(sub12, n, h8, w8, classes, head_dev, a.labels, a.mask, a.weight, a.label_smoothing,
-                                       max_workgroups, t, a.loss, a.grad, a.s, semi ? &sa : nullptr));
-        return SSAL_OK;
-    });
-}
-
-int head_grad_entry(const float *sub12_dev, const float *sub12_raw_dev, int n, int h, int w, int classes, const float *head_dev,
-                    int max_workgroups, const CallArgs &a, const SemiArgs *semi)
-{
-    if (int rc = head_check(n, h, w, classes, max_workgroups)) return rc;
-    if (int rc = args_check(sub12_dev && head_dev, a, semi)) return rc;
-    Bump b(a.ws, a.ws_bytes);
-    const IcnetHeadWs t = head_carve(b, n, h, w, classes, true);
-    const SemiWs sw = semi_carve(b, n, h, w, classes, semi != nullptr, sub12_raw_dev != nullptr);
-    if (int rc = ws_check(head_bytes(0, n, h, w, classes, true, semi != nullptr, sub12_raw_dev != nullptr), b, a)) return rc;
-    return head_run(no_trunk, sub12_dev, sub12_raw_dev, n, h, w, classes, head_dev, max_workgroups, a, semi, t, sw);
-}
-
-int head_train_entry(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h, int w,
-                     const float *head_dev, int max_workgroups, const CallArgs &a, const SemiArgs *semi)
-{
-    int rc = check_dims(net, n, h, w);
-    if (rc) return rc;
-    const int K = net->classes, h8 = h / 8, w8 = w / 8;
-    if ((rc = head_check(n, h8, w8, K, max_workgroups))) return rc;
-    if ((rc = args_check(x_dev && head_dev, a, semi))) return rc;
-    IcWorkspace W;
-    Bump b = carve_behind_trunk(net, a, n, h, w, &W);
-    IcnetHeadWs t = head_carve(b, n, h8, w8, K, false);
-    const SemiWs sw = semi_carve(b, n, h8, w8, K, semi != nullptr, x_raw_dev != nullptr);
-    if ((rc = ws_check(head_bytes(W.bytes, n, h8, w8, K, false, semi != nullptr, x_raw_dev != nullptr), b, a))) return rc;
-    head_bind(t, W);
-    const float *sub12 = W.act.at("sub12_sum");
-    return head_run(frozen_trunk(net, W, x_dev, x_raw_dev, x_is_u8, n, h, w, a.s, true, true), sub12,
-                    x_raw_dev ? sub12 : nullptr, n, h8, w8, K, head_dev, max_workgroups, a, semi, t, sw);
-}
-
-// ---- the last fusion stage (DESIGN.md sections 28 and 30; kernels: ssal_train_icnet_fusion.hip) ----
-// the buffers of one gradient call behind `b`; own_acts: proj / sub12_sum / lq live here (the images entry keeps them in the
-// network's conv3_sub1_proj / sub12_sum / conv6_cls endpoints instead)
-IcnetFusionWs fusion_carve(Bump &b, int64_t n, int h16, int w16, int classes, bool own_acts)
-{
-    IcnetFusionWs t;
-    const int h8 = 2 * h16, w8 = 2 * w16;
-    const int64_t act = n * h8 * (int64_t)w8 * 128;
-    t.wt_a = b.take<float>(FU_GA);
-    t.wt_b = b.take<float>(64 * 128);
-    t.rows = b.take<float>(512);
-    t.proj = own_acts ? b.take<float>(act) : nullptr;
-    t.sub12 = own_acts ? b.take<float>(act) : nullptr;
-    t.g = b.take<float>(act);
-    t.hw = b.take<float>(n * icnet_head_tiles(h8, w8) * 36 * classes);
-    t.part = b.take<float>((int64_t)FU_MAX_WG * FU_PART);  // (sized for the default grid: max_workgroups only lowers it)
-    t.fold = b.take<float>(FU_PART + 64);
-    t.head = head_carve(b, n, h8, w8, classes, own_acts);
-    return t;
-}
-
-int64_t fusion_bytes(int64_t front, int n, int h16, int w16, int classes, bool own_acts, bool semi, bool with_raw)
-{
-    Bump b(nullptr, 0);
-    b.off = front;
-    (void)fusion_carve(b, n, h16, w16, classes, own_acts);
-    (void)semi_carve(b, n, 2 * h16, 2 * w16, classes, semi, with_raw);
-    return b.off + 256;
-}
-
-// the images entry: the block and the head being trained write this call's conv3_sub1_proj, sub12_sum and conv6_cls endpoints
-void fusion_bind(IcnetFusionWs &t, const IcWorkspace &W)
-{
-    t.proj = W.act.at("conv3_sub1_proj");
-    t.sub12 = W.act.at("sub12_sum");
-    head_bind(t.head, W);
-}
-
-bool fusion_fits(int n, int h16, int w16) { return icnet_fusion_fits(h16, w16) && (double)n * h16 * w16 <= 274877906944.0; }
-
-int fusion_check(int n, int h16, int w16, int classes, int max_workgroups)
-{
-    return capped_dims_check(n, h16, w16, classes, max_workgroups, fusion_fits(n, h16, w16), "fusion gradient kernels'");
-}
-
-// sub24 [n,h16,w16,128] / c3 [n,2 h16,2 w16,64]: sub24_sum and conv3_sub1 of the training frames, *_raw: of the undistorted
-// frames (both or neither); trunk as for head_run.  The target launch runs the block and the head on the raw features into t's
-// slots; then the training features go through the same slots.
-template <typename Trunk>
-int fusion_run(Trunk trunk, const float *sub24, const float *c3, const float *sub24_raw, const float *c3_raw, int n, int h16,
-               int w16, int classes, const float *params_dev, const float *stats_dev, int max_workgroups, const CallArgs &a,
-               const SemiArgs *semi, const IcnetFusionWs &t, const SemiWs &sw)
-{
-    const uint8_t *tgt = nullptr;
-    if (wants_targets(sub24_raw, semi)) {
-        if (int rc = trunk(true)) return rc;
-        HIP_TRY(launch_icnet_fusion_targets(sub24_raw, c3_raw, n, h16, w16, classes, params_dev, stats_dev, max_workgroups, t,
-                                            semi_of_targets(*semi), sw.tgt, a.s));
-        tgt = sw.tgt;
-    }
-    if (int rc = trunk(false)) return rc;
-    return with_confusion(sw.rep, classes, semi ? semi->confusion : nullptr, a.s, [&](unsigned long long *rep, int reps) -> int {
-        IcnetHeadSemi sa = {};
-        if (semi) sa = semi_of_grad(*semi, tgt, rep, reps);
-        HIP_TRY(launch_icnet_fusion_grad(sub24, c3, n, h16, w16, classes, params_dev, stats_dev, a.labels, a.mask, a.weight,
-                                         a.label_smoothing, max_workgroups, t, a.loss, a.grad, a.s, semi ? &sa : nullptr));
-        return SSAL_OK;
-    });
-}
-
-int fusion_grad_entry(const float *sub24_dev, const float *conv3_sub1_dev, const float *sub24_raw_dev,
-                      const float *conv3_sub1_raw_dev, int n, int h, int w, int classes, const float *params_dev,
-                      const float *stats_dev, int max_workgroups, const CallArgs &a, const SemiArgs *semi)
-{
-    if (int rc = fusion_check(n, h, w, classes, max_workgroups)) return rc;
-    if (int rc = args_check(sub24_dev && conv3_sub1_dev && params_dev && stats_dev, a, semi)) return rc;
-    const bool raw = sub24_raw_dev != nullptr;
-    if (int rc = raw_all_or_none((sub24_raw_dev != nullptr) + (conv3_sub1_raw_dev != nullptr), 2)) return rc;
-    Bump b(a.ws, a.ws_bytes);
-    const IcnetFusionWs t = fusion_carve(b, n, h, w, classes, true);
-    const SemiWs sw = semi_carve(b, n, 2 * h, 2 * w, classes, semi != nullptr, raw);
-    if (int rc = ws_check(fusion_bytes(0, n, h, w, classes, true, semi != nullptr, raw), b, a)) return rc;
-    return fusion_run(no_trunk, sub24_dev, conv3_sub1_dev, sub24_raw_dev, conv3_sub1_raw_dev, n, h, w, classes, params_dev,
-                      stats_dev, max_workgroups, a, semi, t, sw);
-}
-
-int fusion_train_entry(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h, int w,
-                       const float *params_dev, const float *stats_dev, int max_workgroups, const CallArgs &a,
-                       const SemiArgs *semi)
-{
-    int rc = check_dims(net, n, h, w);
-    if (rc) return rc;
-    const int K = net->classes, h16 = h / 16, w16 = w / 16;
-    const bool raw = x_raw_dev != nullptr;
-    if ((rc = fusion_check(n, h16, w16, K, max_workgroups))) return rc;
-    if ((rc = args_check(x_dev && params_dev && stats_dev, a, semi))) return rc;
-    IcWorkspace W;
-    Bump b = carve_behind_trunk(net, a, n, h, w, &W);
-    IcnetFusionWs t = fusion_carve(b, n, h16, w16, K, false);
-    const SemiWs sw = semi_carve(b, n, h / 8, w / 8, K, semi != nullptr, raw);
-    if ((rc = ws_check(fusion_bytes(W.bytes, n, h16, w16, K, false, semi != nullptr, raw), b, a))) return rc;
-    fusion_bind(t, W);
-    const float *sub24 = W.act.at("sub24_sum"), *c3 = W.act.at("conv3_sub1");
-    return fusion_run(frozen_trunk(net, W, x_dev, x_raw_dev, x_is_u8, n, h, w, a.s, false, true), sub24, c3,
-                      raw ? sub24 : nullptr, raw ? c3 : nullptr, n, h16, w16, K, params_dev, stats_dev, max_workgroups, a, semi, t,
-                      sw);
-}
-
-// ---- the whole cascade head (DESIGN.md sections 29 and 30; kernels: ssal_train_icnet_cascade.hip) ----
-// the buffers of one gradient call behind `b`; own_acts: the block's projection / sub24_sum and the fusion stage's activations
-// live here (the images entry keeps them in the network's endpoints instead)
-IcnetCascadeWs cascade_carve(Bump &b, int64_t n, int h32, int w32, int classes, bool own_acts)
-{
-    IcnetCascadeWs t;
-    const int h16 = 2 * h32, w16 = 2 * w32;
-    const int64_t act = n * h16 * (int64_t)w16 * 128;
-    t.wt_c = b.take<float>(CA_GC);
-    t.wt_d = b.take<float>(256 * 128);
-    t.rows = b.take<float>(512);
-    t.proj = own_acts ? b.take<float>(act) : nullptr;
-    t.sub24 = own_acts ? b.take<float>(act) : nullptr;
-    t.du = b.take<float>(4 * act);
-    t.g24 = b.take<float>(act);
-    t.part = b.take<float>((int64_t)CA_MAX_WG * CA_PART);  // (sized for the default grid: max_workgroups only lowers it)
-    t.fold = b.take<float>(CA_PART);
-    t.fusion = fusion_carve(b, n, h16, w16, classes, own_acts);
-    return t;
-}
-
-int64_t cascade_bytes(int64_t front, int n, int h32, int w32, int classes, bool own_acts, bool semi, bool with_raw)
-{
-    Bump b(nullptr, 0);
-    b.off = front;
-    (void)cascade_carve(b, n, h32, w32, classes, own_acts);
-    (void)semi_carve(b, n, 4 * h32, 4 * w32, classes, semi, with_raw);
-    return b.off + 256;
-}
-
-// the images entry: both blocks and the head being trained write this call's endpoints from conv3_1_sub2_proj on
-void cascade_bind(IcnetCascadeWs &t, const IcWorkspace &W)
-{
-    t.proj = W.act.at("conv3_1_sub2_proj");
-    t.sub24 = W.act.at("sub24_sum");
-    fusion_bind(t.fusion, W);
-}
-
-bool cascade_fits(int n, int h32, int w32) { return icnet_cascade_fits(h32, w32) && fusion_fits(n, 2 * h32, 2 * w32); }
-
-int cascade_check(int n, int h32, int w32, int classes, int max_workgroups)
-{
-    return capped_dims_check(n, h32, w32, classes, max_workgroups, cascade_fits(n, h32, w32), "cascade gradient kernels'");
-}
-
-// c54 [n,h32,w32,256] / c31 [n,2 h32,2 w32,256] / c3 [n,4 h32,4 w32,64]: conv5_4_k1, conv3_1 and conv3_sub1 of the training
-// frames, *_raw: of the undistorted frames (all or none); trunk and the slots as for fusion_run, with both blocks.
-template <typename Trunk>
-int cascade_run(Trunk trunk, const float *c54, const float *c31, const float *c3, const float *c54_raw, const float *c31_raw,
-                const float *c3_raw, int n, int h32, int w32, int classes, const float *params_dev, const float *stats_dev,
-                int max_workgroups, const CallArgs &a, const SemiArgs *semi, const IcnetCascadeWs &t, const SemiWs &sw)
-{
-    const uint8_t *tgt = nullptr;
-    if (wants_targets(c54_raw, semi)) {
-        if (int rc = trunk(true)) return rc;
-        HIP_TRY(launch_icnet_cascade_targets(c54_raw, c31_raw, c3_raw, n, h32, w32, classes, params_dev, stats_dev,
-                                             max_workgroups, t, semi_of_targets(*semi), sw.tgt, a.s));
-        tgt = sw.tgt;
-    }
-    if (int rc = trunk(false)) return rc;
-    return with_confusion(sw.rep, classes, semi ? semi->confusion : nullptr, a.s, [&](unsigned long long *rep, int reps) -> int {
-        IcnetHeadSemi sa = {};
-        if (semi) sa = semi_of_grad(*semi, tgt, rep, reps);
-        HIP_TRY(launch_icnet_cascade_grad(c54, c31, c3, n, h32, w32, classes, params_dev, stats_dev, a.labels, a.mask, a.weight,
-                                          a.label_smoothing, max_workgroups, t, a.loss, a.grad, a.s, semi ? &sa : nullptr));
-        return SSAL_OK;
-    });
-}
-
-int cascade_grad_entry(const float *conv5_4_k1_dev, const float *conv3_1_dev, const float *conv3_sub1_dev,
-                       const float *conv5_4_k1_raw_dev, const float *conv3_1_raw_dev, const float *conv3_sub1_raw_dev, int n,
-                       int h, int w, int classes, const float *params_dev, const float *stats_dev, int max_workgroups,
-                       const CallArgs &a, const SemiArgs *semi)
-{
-    if (int rc = cascade_check(n, h, w, classes, max_workgroups)) return rc;
-    if (int rc = args_check(conv5_4_k1_dev && conv3_1_dev && conv3_sub1_dev && params_dev && stats_dev, a, semi)) return rc;
-    const bool raw = conv5_4_k1_raw_dev != nullptr;
-    if (int rc = raw_all_or_none((conv5_4_k1_raw_dev != nullptr) + (conv3_1_raw_dev != nullptr) + (conv3_sub1_raw_dev != nullptr),
-                                 3))
-        return rc;
-    Bump b(a.ws, a.ws_bytes);
-    const IcnetCascadeWs t = cascade_carve(b, n, h, w, classes, true);
-    const SemiWs sw = semi_carve(b, n, 4 * h, 4 * w, classes, semi != nullptr, raw);
-    if (int rc = ws_check(cascade_bytes(0, n, h, w, classes, true, semi != nullptr, raw), b, a)) return rc;
-    return cascade_run(no_trunk, conv5_4_k1_dev, conv3_1_dev, conv3_sub1_dev, conv5_4_k1_raw_dev, conv3_1_raw_dev,
-                       conv3_sub1_raw_dev, n, h, w, classes, params_dev, stats_dev, max_workgroups, a, semi, t, sw);
-}
-
-int cascade_train_entry(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h, int w,
-                        const float *params_dev, const float *stats_dev, int max_workgroups, const CallArgs &a,
-                        const SemiArgs *semi)
-{
-    int rc = check_dims(net, n, h, w);
-    if (rc) return rc;
-    const int K = net->classes, h32 = h / 32, w32 = w / 32;
-    const bool raw = x_raw_dev != nullptr;
-    if ((rc = cascade_check(n, h32, w32, K, max_workgroups))) return rc;
-    if ((rc = args_check(x_dev && params_dev && stats_dev, a, semi))) return rc;
-    IcWorkspace W;
-    Bump b = carve_behind_trunk(net, a, n, h, w, &W);
-    IcnetCascadeWs t = cascade_carve(b, n, h32, w32, K, false);
-    const SemiWs sw = semi_carve(b, n, h / 8, w / 8, K, semi != nullptr, raw);
-    if ((rc = ws_check(cascade_bytes(W.bytes, n, h32, w32, K, false, semi != nullptr, raw), b, a))) return rc;
-    cascade_bind(t, W);
-    const float *c54 = W.act.at("conv5_4_k1"), *c31 = W.act.at("conv3_1"), *c3 = W.act.at("conv3_sub1");
-    return cascade_run(frozen_trunk(net, W, x_dev, x_raw_dev, x_is_u8, n, h, w, a.s, false, false), c54, c31, c3,
-                       raw ? c54 : nullptr, raw ? c31 : nullptr, raw ? c3 : nullptr, n, h32, w32, K, params_dev, stats_dev,
-                       max_workgroups, a, semi, t, sw);
-}
-
-// ---- the high-resolution branch down to the image (kernels: ssal_train_icnet_highres.hip) ----
-// the buffers of one gradient call behind `b`; own_acts: a_1, a_2, conv3_sub1 and the cascade head's activations live here (the
-// images entry keeps them in the network's conv1_sub1 / conv2_sub1 / conv3_sub1 / ... endpoints instead)
-IcnetHighresWs highres_carve(Bump &b, int64_t n, int h32, int w32, int classes, bool own_acts)
-{
-    IcnetHighresWs t;
-    const int64_t px8 = n * (4 * (int64_t)h32) * (4 * (int64_t)w32);
-    t.wt2 = b.take<float>(9 * 32 * 32);
-    t.wt3 = b.take<float>(9 * 32 * 64);
-    t.rows = b.take<float>(256);
-    t.a1 = own_acts ? b.take<float>(16 * px8 * 32) : nullptr;
-    t.a2 = own_acts ? b.take<float>(4 * px8 * 32) : nullptr;
-    t.f3 = own_acts ? b.take<float>(px8 * 64) : nullptr;
-    t.gz3 = b.take<float>(px8 * 64);
-    t.gz2 = b.take<float>(4 * px8 * 32);
-    t.gz1 = b.take<float>(16 * px8 * 32);
-    t.part = b.take<float>((int64_t)HR_MAX_WG * HR_PART);  // (sized for the default grid: max_workgroups only lowers it)
-    t.fold = b.take<float>(HR_PART);
-    t.cascade = cascade_carve(b, n, h32, w32, classes, own_acts);
-    return t;
-}
-
-int64_t highres_bytes(int64_t front, int n, int h32, int w32, int classes, bool own_acts, bool semi, bool with_raw)
-{
-    Bump b(nullptr, 0);
-    b.off = front;
-    (void)highres_carve(b, n, h32, w32, classes, own_acts);
-    (void)semi_carve(b, n, 4 * h32, 4 * w32, classes, semi, with_raw);
-    return b.off + 256;
-}
-
-// the images entry: the branch, both blocks and the head being trained write this call's endpoints
-void highres_bind(IcnetHighresWs &t, const IcWorkspace &W)
-{
-    t.a1 = W.act.at("conv1_sub1");
-    t.a2 = W.act.at("conv2_sub1");
-    t.f3 = W.act.at("conv3_sub1");
-    cascade_bind(t.cascade, W);
-}
-
-bool highres_fits(int n, int h32, int w32) { return icnet_highres_fits(n, h32, w32) && cascade_fits(n, h32, w32); }
-
-int highres_check(int n, int h32, int w32, int classes, int c_in, int max_workgroups)
-{
-    if (int rc = capped_dims_check(n, h32, w32, classes, max_workgroups, n <= 0 || highres_fits(n, h32, w32),
-                                   "high-resolution gradient kernels'"))
-        return rc;
-    if (c_in != 3 && c_in != 4) return fail(SSAL_EINVAL, "the high-resolution trainer takes 3 or 4 input channels (got %d)", c_in);
+    if (int rc = capped_dims_check(n, h, w, classes, max_workgroups, n <= 0 || D::fits(n, h, w), D::kNoun)) return rc;
+    if (D::kFrame && c_in != 3 && c_in != 4)
+        return fail(SSAL_EINVAL, "the high-resolution trainer takes 3 or 4 input channels (got %d)", c_in);
     return SSAL_OK;
 }
 
-// c54 [n,h32,w32,256] / c31 [n,2 h32,2 w32,256]: conv5_4_k1 and conv3_1 of the training frames x [n,32 h32,32 w32,c_in], *_raw:
-// of the undistorted frames x_raw (all or none); trunk and the slots as for cascade_run, with the branch
-template <typename Trunk>
-int highres_run(Trunk trunk, const float *c54, const float *c31, const void *x, const float *c54_raw, const float *c31_raw,
-                const void *x_raw, bool x_is_u8, int c_in, int n, int h32, int w32, int classes, const float *params_dev,
-                const float *stats_dev, int max_workgroups, const CallArgs &a, const SemiArgs *semi, const IcnetHighresWs &t,
-                const SemiWs &sw)
+template <typename D, typename Trunk>
+int depth_run(Trunk trunk, const DepthIn &in, const CallArgs &a, const SemiArgs *semi, const DepthWs<D> &c)
 {
     const uint8_t *tgt = nullptr;
-    if (wants_targets(c54_raw, semi)) {
+    if (in.raw[0] && semi && semi->labelled) {  // the undistorted frames' features matter only where an image is unlabelled
         if (int rc = trunk(true)) return rc;
-        HIP_TRY(launch_icnet_highres_targets(c54_raw, c31_raw, x_raw, x_is_u8, c_in, n, h32, w32, classes, params_dev, stats_dev,
-                                             max_workgroups, t, semi_of_targets(*semi), sw.tgt, a.s));
-        tgt = sw.tgt;
+        HIP_TRY(D::targets(in, c.t, semi_of_targets(*semi), c.sw.tgt, a.s));
+        tgt = c.sw.tgt;
     }
     if (int rc = trunk(false)) return rc;
-    return with_confusion(sw.rep, classes, semi ? semi->confusion : nullptr, a.s, [&](unsigned long long *rep, int reps) -> int {
+    return with_confusion(c.sw.rep, in.classes, semi ? semi->confusion : nullptr, a.s, [&](unsigned long long *rep, int reps) -> int {
         IcnetHeadSemi sa = {};
         if (semi) sa = semi_of_grad(*semi, tgt, rep, reps);
-        HIP_TRY(launch_icnet_highres_grad(c54, c31, x, x_is_u8, c_in, n, h32, w32, classes, params_dev, stats_dev, a.labels,
-                                          a.mask, a.weight, a.label_smoothing, max_workgroups, t, a.loss, a.grad, a.s,
-                                          semi ? &sa : nullptr));
+        HIP_TRY(D::grad(in, a, c.t, semi ? &sa : nullptr));
         return SSAL_OK;
     });
 }
 
-int highres_grad_entry(const float *conv5_4_k1_dev, const float *conv3_1_dev, const void *x_dev, const float *conv5_4_k1_raw_dev,
-                       const float *conv3_1_raw_dev, const void *x_raw_dev, int x_is_u8, int c_in, int n, int h, int w,
-                       int classes, const float *params_dev, const float *stats_dev, int max_workgroups, const CallArgs &a,
-                       const SemiArgs *semi)
+template <typename D>
+int features_entry(const DepthIn &in, const CallArgs &a, const SemiArgs *semi)
 {
-    if (int rc = highres_check(n, h, w, classes, c_in, max_workgroups)) return rc;
-    if (int rc = args_check(conv5_4_k1_dev && conv3_1_dev && x_dev && params_dev && stats_dev, a, semi)) return rc;
-    const bool raw = conv5_4_k1_raw_dev != nullptr;
-    if (int rc = raw_all_or_none((conv5_4_k1_raw_dev != nullptr) + (conv3_1_raw_dev != nullptr) + (x_raw_dev != nullptr), 3))
-        return rc;
+    constexpr int N = feature_inputs<D>();
+    if (int rc = depth_check<D>(in.n, in.h, in.w, in.classes, in.c_in, in.max_workgroups)) return rc;
+    int given = 0, raw = 0;
+    for (int i = 0; i < N; ++i) given += in.f[i] != nullptr, raw += in.raw[i] != nullptr;
+    if (int rc = args_check(given == N && in.params && (in.stats || !D::kStats), a, semi)) return rc;
+    if (raw != 0 && raw != N) return fail(SSAL_EINVAL, "the raw feature pointers must be given together (%d of %d)", raw, N);
     Bump b(a.ws, a.ws_bytes);
-    const IcnetHighresWs t = highres_carve(b, n, h, w, classes, true);
-    const SemiWs sw = semi_carve(b, n, 4 * h, 4 * w, classes, semi != nullptr, raw);
-    if (int rc = ws_check(highres_bytes(0, n, h, w, classes, true, semi != nullptr, raw), b, a)) return rc;
-    return highres_run(no_trunk, conv5_4_k1_dev, conv3_1_dev, x_dev, conv5_4_k1_raw_dev, conv3_1_raw_dev, x_raw_dev,
-                       x_is_u8 != 0, c_in, n, h, w, classes, params_dev, stats_dev, max_workgroups, a, semi, t, sw);
+    const DepthWs<D> c = depth_carve<D>(b, in.n, in.h, in.w, in.classes, true, semi != nullptr, raw != 0);
+    if (int rc = ws_check(depth_bytes<D>(0, in.n, in.h, in.w, in.classes, true, semi != nullptr, raw != 0), b, a)) return rc;
+    return depth_run<D>(no_trunk, in, a, semi, c);
 }
 
-int highres_train_entry(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h, int w,
-                        const float *params_dev, const float *stats_dev, int max_workgroups, const CallArgs &a,
-                        const SemiArgs *semi)
+template <typename D>
+int images_entry(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h, int w,
+                 const float *params_dev, const float *stats_dev, int max_workgroups, const CallArgs &a, const SemiArgs *semi)
 {
     int rc = check_dims(net, n, h, w);
     if (rc) return rc;
-    const int K = net->classes, h32 = h / 32, w32 = w / 32;
+    const int K = net->classes, hu = h / D::kUnit, wu = w / D::kUnit;
     const bool raw = x_raw_dev != nullptr;
-    if ((rc = highres_check(n, h32, w32, K, net->c_in, max_workgroups))) return rc;
-    if ((rc = args_check(x_dev && params_dev && stats_dev, a, semi))) return rc;
-    IcWorkspace W;
-    Bump b = carve_behind_trunk(net, a, n, h, w, &W);
-    IcnetHighresWs t = highres_carve(b, n, h32, w32, K, false);
-    const SemiWs sw = semi_carve(b, n, h / 8, w / 8, K, semi != nullptr, raw);
-    if ((rc = ws_check(highres_bytes(W.bytes, n, h32, w32, K, false, semi != nullptr, raw), b, a))) return rc;
-    highres_bind(t, W);
+    if ((rc = depth_check<D>(n, hu, wu, K, net->c_in, max_workgroups))) return rc;
+    if ((rc = args_check(x_dev && params_dev && (stats_dev || !D::kStats), a, semi))) return rc;
+    // the call's pieces lie behind the forward workspace (not ok when that is not)
+    const IcWorkspace W = carve(net, a.ws, a.ws_bytes, n, h, w);
+    Bump b(a.ws, a.ws_bytes);
+    b.off = W.bytes;
+    b.ok = W.ok;
+    DepthWs<D> c = depth_carve<D>(b, n, hu, wu, K, false, semi != nullptr, raw);
+    if ((rc = ws_check(depth_bytes<D>(W.bytes, n, hu, wu, K, false, semi != nullptr, raw), b, a))) return rc;
+    D::bind(c.t, W);
+    DepthIn in = {{}, {}, params_dev, stats_dev, max_workgroups, n, hu, wu, K, x_is_u8 != 0, net->c_in};
+    int i = 0;
+    for (const char *name : D::kEndpoints) {
+        in.f[i] = W.act.at(name);
+        in.raw[i++] = raw ? W.act.at(name) : nullptr;
+    }
+    if constexpr (D::kFrame) in.f[i] = x_dev, in.raw[i] = x_raw_dev;
+    // the frozen trunk, on the undistorted (of_raw) or the training frames, through the same slots of W.  It ends in front of the
+    // layers being trained: run_trunk without the head, and from level 1 / 2 / 3 on without the last fusion stage / the first
+    // one / the high-resolution branch
     hipStream_t s = a.s;
-    // the two frozen branches only (run_trunk's stop in front of conv1_sub1), on the undistorted or the training frames, through
-    // the same endpoints
-    auto backbone = [=, &W](bool of_raw) -> int {
+    auto trunk = [=, &W](bool of_raw) -> int {
         std::vector<Grp> one(1);
         one[0] = {W, of_raw ? x_raw_dev : x_dev, n, s};
-        HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false, false, false, false));
+        HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false, D::kLevel < 1, D::kLevel < 2, D::kLevel < 3));
         return SSAL_OK;
     };
-    const float *c54 = W.act.at("conv5_4_k1"), *c31 = W.act.at("conv3_1");
-    return highres_run(backbone, c54, c31, x_dev, raw ? c54 : nullptr, raw ? c31 : nullptr, x_raw_dev, x_is_u8 != 0, net->c_in, n,
-                       h32, w32, K, params_dev, stats_dev, max_workgroups, a, semi, t, sw);
+    return depth_run<D>(trunk, in, a, semi, c);
+}
+
+template <typename D>
+int64_t features_query(int n, int h, int w, int classes, bool semi, bool with_raw)
+{
+    return capped_dims_ok(n, classes, D::fits(n, h, w)) ? depth_bytes<D>(0, n, h, w, classes, true, semi, with_raw) : -1;
+}
+
+template <typename D>
+int64_t images_query(const ssal_icnet *net, int n, int h, int w, bool semi, bool with_raw)
+{
+    const int hu = h / D::kUnit, wu = w / D::kUnit;
+    if (!net || !net->committed || n <= 0 || h <= 0 || w <= 0 || h % 32 || w % 32 || (D::kImagesQueryFits && !D::fits(n, hu, wu)))
+        return -1;
+    return depth_bytes<D>(carve(net, nullptr, 0, n, h, w).bytes, n, hu, wu, net->classes, false, semi, with_raw);
 }
 
 // ---- the trained variables back into the handle ----
@@ -1333,8 +1178,9 @@ struct HostUpdate {
     const float *host;
     int64_t count;
 };
+typedef std::vector<HostUpdate> HostUpdates;
 
-int update_packed(ssal_icnet *net, const std::vector<HostUpdate> &tensors, const std::set<std::string> &layers, void *stream)
+int update_packed(ssal_icnet *net, const HostUpdates &tensors, const std::set<std::string> &layers, void *stream)
 {
     if (!net->committed) return fail(SSAL_ESTATE, "ssal_icnet_commit() has not been called");
     int dev = -1;
@@ -1377,22 +1223,53 @@ int update_packed(ssal_icnet *net, const std::vector<HostUpdate> &tensors, const
     return SSAL_OK;
 }
 
-// the packed head (ssal_train_icnet.h) / the fusion trainer's packed vector (ssal_train_icnet_fusion.h) at p
-std::vector<HostUpdate> head_tensors(const float *kernel, const float *bias, int K)
+// One tensor table per depth: its own rows of the packed vector at p (ssal_train_icnet*.h), then the table of the depth above
+HostUpdates then(HostUpdates own, const HostUpdates &above)
+{
+    own.insert(own.end(), above.begin(), above.end());
+    return own;
+}
+
+HostUpdates head_tensors(const float *kernel, const float *bias, int K)
 {
     return {{"conv6_cls.kernel", kernel, 128 * (int64_t)K}, {"conv6_cls.bias", bias, K}};
 }
 
-std::vector<HostUpdate> fusion_tensors(const float *p, int K)
+HostUpdates fusion_tensors(const float *p, int K)
 {
-    std::vector<HostUpdate> t = {{"conv_sub2.kernel", p + FU_KA, FU_GA},
-                                 {"conv_sub2.gamma", p + FU_GA, 128},
-                                 {"conv_sub2.beta", p + FU_BA, 128},
-                                 {"conv3_sub1_proj.kernel", p + FU_KB, 64 * 128},
-                                 {"conv3_sub1_proj.gamma", p + FU_GB, 128},
-                                 {"conv3_sub1_proj.beta", p + FU_BB, 128}};
-    for (const HostUpdate &u : head_tensors(p + FU_HEAD, p + FU_HEAD + 128 * K, K)) t.push_back(u);
-    return t;
+    return then({{"conv_sub2.kernel", p + FU_KA, FU_GA},
+                 {"conv_sub2.gamma", p + FU_GA, 128},
+                 {"conv_sub2.beta", p + FU_BA, 128},
+                 {"conv3_sub1_proj.kernel", p + FU_KB, 64 * 128},
+                 {"conv3_sub1_proj.gamma", p + FU_GB, 128},
+                 {"conv3_sub1_proj.beta", p + FU_BB, 128}},
+                head_tensors(p + FU_HEAD, p + FU_HEAD + 128 * K, K));
+}
+
+HostUpdates cascade_tensors(const float *p, int K)
+{
+    return then({{"conv_sub4.kernel", p + CA_KC, CA_GC},
+                 {"conv_sub4.gamma", p + CA_GC, 128},
+                 {"conv_sub4.beta", p + CA_BC, 128},
+                 {"conv3_1_sub2_proj.kernel", p + CA_KD, 256 * 128},
+                 {"conv3_1_sub2_proj.gamma", p + CA_GD, 128},
+                 {"conv3_1_sub2_proj.beta", p + CA_BD, 128}},
+                fusion_tensors(p + CA_FUSION, K));
+}
+
+HostUpdates highres_tensors(const float *p, int c_in, int K)
+{
+    const IcnetHighresOff o = icnet_highres_offsets(c_in);
+    return then({{"conv1_sub1.kernel", p + o.k1, o.g1},
+                 {"conv1_sub1.gamma", p + o.g1, 32},
+                 {"conv1_sub1.beta", p + o.b1, 32},
+                 {"conv2_sub1.kernel", p + o.k2, 9 * 32 * 32},
+                 {"conv2_sub1.gamma", p + o.g2, 32},
+                 {"conv2_sub1.beta", p + o.b2, 32},
+                 {"conv3_sub1.kernel", p + o.k3, 9 * 32 * 64},
+                 {"conv3_sub1.gamma", p + o.g3, 64},
+                 {"conv3_sub1.beta", p + o.b3, 64}},
+                cascade_tensors(p + o.cascade, K));
 }
 
 }  // namespace
@@ -1400,7 +1277,7 @@ std::vector<HostUpdate> fusion_tensors(const float *p, int K)
 // ---- the output layer ----
 SSAL_API int64_t ssal_icnet_head_grad_workspace_bytes(int n, int h, int w, int classes)
 {
-    return capped_dims_ok(n, classes, head_fits(n, h, w)) ? head_bytes(0, n, h, w, classes, true, false, false) : -1;
+    return features_query<HeadDepth>(n, h, w, classes, false, false);
 }
 
 SSAL_API int ssal_icnet_head_grad_nhwc(const float *sub12_dev, int n, int h, int w, int classes, const float *head_dev,
@@ -1409,13 +1286,12 @@ SSAL_API int ssal_icnet_head_grad_nhwc(const float *sub12_dev, int n, int h, int
                                        void *ws_dev, int64_t ws_bytes, void *stream)
 {
     const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    return head_grad_entry(sub12_dev, nullptr, n, h, w, classes, head_dev, max_workgroups, a, nullptr);
+    return features_entry<HeadDepth>({{sub12_dev}, {}, head_dev, nullptr, max_workgroups, n, h, w, classes}, a, nullptr);
 }
 
 SSAL_API int64_t ssal_icnet_train_head_workspace_bytes(const ssal_icnet *net, int n, int h, int w)
 {
-    if (!net_dims_ok(net, n, h, w)) return -1;
-    return head_bytes(trunk_bytes(net, n, h, w), n, h / 8, w / 8, net->classes, false, false, false);
+    return images_query<HeadDepth>(net, n, h, w, false, false);
 }
 
 SSAL_API int ssal_icnet_train_head_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
@@ -1424,12 +1300,12 @@ SSAL_API int ssal_icnet_train_head_nhwc(ssal_icnet *net, const void *x_dev, int 
                                         float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
     const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    return head_train_entry(net, x_dev, nullptr, x_is_u8, n, h, w, head_dev, max_workgroups, a, nullptr);
+    return images_entry<HeadDepth>(net, x_dev, nullptr, x_is_u8, n, h, w, head_dev, nullptr, max_workgroups, a, nullptr);
 }
 
 SSAL_API int64_t ssal_icnet_head_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw)
 {
-    return capped_dims_ok(n, classes, head_fits(n, h, w)) ? head_bytes(0, n, h, w, classes, true, true, with_raw != 0) : -1;
+    return features_query<HeadDepth>(n, h, w, classes, true, with_raw != 0);
 }
 
 SSAL_API int ssal_icnet_head_grad_semi_nhwc(const float *sub12_dev, const float *sub12_raw_dev, int n, int h, int w,
@@ -1441,13 +1317,13 @@ SSAL_API int ssal_icnet_head_grad_semi_nhwc(const float *sub12_dev, const float 
 {
     const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
     const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, sub12_raw_dev != nullptr};
-    return head_grad_entry(sub12_dev, sub12_raw_dev, n, h, w, classes, head_dev, max_workgroups, a, &semi);
+    return features_entry<HeadDepth>({{sub12_dev}, {sub12_raw_dev}, head_dev, nullptr, max_workgroups, n, h, w, classes}, a,
+                                     &semi);
 }
 
 SSAL_API int64_t ssal_icnet_train_head_semi_workspace_bytes(const ssal_icnet *net, int n, int h, int w, int with_raw)
 {
-    if (!net_dims_ok(net, n, h, w)) return -1;
-    return head_bytes(trunk_bytes(net, n, h, w), n, h / 8, w / 8, net->classes, false, true, with_raw != 0);
+    return images_query<HeadDepth>(net, n, h, w, true, with_raw != 0);
 }
 
 SSAL_API int ssal_icnet_train_head_semi_nhwc(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
@@ -1459,7 +1335,7 @@ SSAL_API int ssal_icnet_train_head_semi_nhwc(ssal_icnet *net, const void *x_dev,
 {
     const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
     const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev != nullptr};
-    return head_train_entry(net, x_dev, x_raw_dev, x_is_u8, n, h, w, head_dev, max_workgroups, a, &semi);
+    return images_entry<HeadDepth>(net, x_dev, x_raw_dev, x_is_u8, n, h, w, head_dev, nullptr, max_workgroups, a, &semi);
 }
 
 SSAL_API int ssal_icnet_update_head(ssal_icnet *net, const float *kernel_host, const float *bias_host, void *stream)
@@ -1471,7 +1347,7 @@ SSAL_API int ssal_icnet_update_head(ssal_icnet *net, const float *kernel_host, c
 // ---- the last fusion stage ----
 SSAL_API int64_t ssal_icnet_fusion_grad_workspace_bytes(int n, int h, int w, int classes)
 {
-    return capped_dims_ok(n, classes, fusion_fits(n, h, w)) ? fusion_bytes(0, n, h, w, classes, true, false, false) : -1;
+    return features_query<FusionDepth>(n, h, w, classes, false, false);
 }
 
 SSAL_API int ssal_icnet_fusion_grad_nhwc(const float *sub24_dev, const float *conv3_sub1_dev, int n, int h, int w, int classes,
@@ -1480,14 +1356,13 @@ SSAL_API int ssal_icnet_fusion_grad_nhwc(const float *sub24_dev, const float *co
                                          double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
     const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    return fusion_grad_entry(sub24_dev, conv3_sub1_dev, nullptr, nullptr, n, h, w, classes, params_dev, stats_dev, max_workgroups,
-                             a, nullptr);
+    return features_entry<FusionDepth>({{sub24_dev, conv3_sub1_dev}, {}, params_dev, stats_dev, max_workgroups, n, h, w, classes},
+                                       a, nullptr);
 }
 
 SSAL_API int64_t ssal_icnet_train_fusion_workspace_bytes(const ssal_icnet *net, int n, int h, int w)
 {
-    if (!net_dims_ok(net, n, h, w)) return -1;
-    return fusion_bytes(trunk_bytes(net, n, h, w), n, h / 16, w / 16, net->classes, false, false, false);
+    return images_query<FusionDepth>(net, n, h, w, false, false);
 }
 
 SSAL_API int ssal_icnet_train_fusion_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
@@ -1496,12 +1371,12 @@ SSAL_API int ssal_icnet_train_fusion_nhwc(ssal_icnet *net, const void *x_dev, in
                                           double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
     const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    return fusion_train_entry(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, stats_dev, max_workgroups, a, nullptr);
+    return images_entry<FusionDepth>(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, stats_dev, max_workgroups, a, nullptr);
 }
 
 SSAL_API int64_t ssal_icnet_fusion_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw)
 {
-    return capped_dims_ok(n, classes, fusion_fits(n, h, w)) ? fusion_bytes(0, n, h, w, classes, true, true, with_raw != 0) : -1;
+    return features_query<FusionDepth>(n, h, w, classes, true, with_raw != 0);
 }
 
 SSAL_API int ssal_icnet_fusion_grad_semi_nhwc(const float *sub24_dev, const float *conv3_sub1_dev, const float *sub24_raw_dev,
@@ -1514,14 +1389,13 @@ SSAL_API int ssal_icnet_fusion_grad_semi_nhwc(const float *sub24_dev, const floa
 {
     const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
     const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, sub24_raw_dev != nullptr};
-    return fusion_grad_entry(sub24_dev, conv3_sub1_dev, sub24_raw_dev, conv3_sub1_raw_dev, n, h, w, classes, params_dev, stats_dev,
-                             max_workgroups, a, &semi);
+    return features_entry<FusionDepth>({{sub24_dev, conv3_sub1_dev}, {sub24_raw_dev, conv3_sub1_raw_dev}, params_dev, stats_dev,
+                                        max_workgroups, n, h, w, classes}, a, &semi);
 }
 
 SSAL_API int64_t ssal_icnet_train_fusion_semi_workspace_bytes(const ssal_icnet *net, int n, int h, int w, int with_raw)
 {
-    if (!net_dims_ok(net, n, h, w)) return -1;
-    return fusion_bytes(trunk_bytes(net, n, h, w), n, h / 16, w / 16, net->classes, false, true, with_raw != 0);
+    return images_query<FusionDepth>(net, n, h, w, true, with_raw != 0);
 }
 
 SSAL_API int ssal_icnet_train_fusion_semi_nhwc(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
@@ -1534,7 +1408,7 @@ SSAL_API int ssal_icnet_train_fusion_semi_nhwc(ssal_icnet *net, const void *x_de
 {
     const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
     const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev != nullptr};
-    return fusion_train_entry(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, stats_dev, max_workgroups, a, &semi);
+    return images_entry<FusionDepth>(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, stats_dev, max_workgroups, a, &semi);
 }
 
 SSAL_API int ssal_icnet_update_fusion(ssal_icnet *net, const float *params_host, void *stream)
@@ -1546,7 +1420,7 @@ SSAL_API int ssal_icnet_update_fusion(ssal_icnet *net, const float *params_host,
 // ---- the whole cascade head ----
 SSAL_API int64_t ssal_icnet_cascade_grad_workspace_bytes(int n, int h, int w, int classes)
 {
-    return capped_dims_ok(n, classes, cascade_fits(n, h, w)) ? cascade_bytes(0, n, h, w, classes, true, false, false) : -1;
+    return features_query<CascadeDepth>(n, h, w, classes, false, false);
 }
 
 SSAL_API int ssal_icnet_cascade_grad_nhwc(const float *conv5_4_k1_dev, const float *conv3_1_dev, const float *conv3_sub1_dev,
@@ -1556,14 +1430,13 @@ SSAL_API int ssal_icnet_cascade_grad_nhwc(const float *conv5_4_k1_dev, const flo
                                           float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
     const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    return cascade_grad_entry(conv5_4_k1_dev, conv3_1_dev, conv3_sub1_dev, nullptr, nullptr, nullptr, n, h, w, classes, params_dev,
-                              stats_dev, max_workgroups, a, nullptr);
+    return features_entry<CascadeDepth>({{conv5_4_k1_dev, conv3_1_dev, conv3_sub1_dev}, {}, params_dev, stats_dev, max_workgroups,
+                                         n, h, w, classes}, a, nullptr);
 }
 
 SSAL_API int64_t ssal_icnet_train_cascade_workspace_bytes(const ssal_icnet *net, int n, int h, int w)
 {
-    if (!net_dims_ok(net, n, h, w)) return -1;
-    return cascade_bytes(trunk_bytes(net, n, h, w), n, h / 32, w / 32, net->classes, false, false, false);
+    return images_query<CascadeDepth>(net, n, h, w, false, false);
 }
 
 SSAL_API int ssal_icnet_train_cascade_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
@@ -1572,12 +1445,12 @@ SSAL_API int ssal_icnet_train_cascade_nhwc(ssal_icnet *net, const void *x_dev, i
                                            double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
     const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    return cascade_train_entry(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, stats_dev, max_workgroups, a, nullptr);
+    return images_entry<CascadeDepth>(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, stats_dev, max_workgroups, a, nullptr);
 }
 
 SSAL_API int64_t ssal_icnet_cascade_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw)
 {
-    return capped_dims_ok(n, classes, cascade_fits(n, h, w)) ? cascade_bytes(0, n, h, w, classes, true, true, with_raw != 0) : -1;
+    return features_query<CascadeDepth>(n, h, w, classes, true, with_raw != 0);
 }
 
 SSAL_API int ssal_icnet_cascade_grad_semi_nhwc(const float *conv5_4_k1_dev, const float *conv3_1_dev,
@@ -1591,14 +1464,14 @@ SSAL_API int ssal_icnet_cascade_grad_semi_nhwc(const float *conv5_4_k1_dev, cons
 {
     const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
     const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, conv5_4_k1_raw_dev != nullptr};
-    return cascade_grad_entry(conv5_4_k1_dev, conv3_1_dev, conv3_sub1_dev, conv5_4_k1_raw_dev, conv3_1_raw_dev, conv3_sub1_raw_dev,
-                              n, h, w, classes, params_dev, stats_dev, max_workgroups, a, &semi);
+    return features_entry<CascadeDepth>({{conv5_4_k1_dev, conv3_1_dev, conv3_sub1_dev},
+                                         {conv5_4_k1_raw_dev, conv3_1_raw_dev, conv3_sub1_raw_dev}, params_dev, stats_dev,
+                                         max_workgroups, n, h, w, classes}, a, &semi);
 }
 
 SSAL_API int64_t ssal_icnet_train_cascade_semi_workspace_bytes(const ssal_icnet *net, int n, int h, int w, int with_raw)
 {
-    if (!net_dims_ok(net, n, h, w)) return -1;
-    return cascade_bytes(trunk_bytes(net, n, h, w), n, h / 32, w / 32, net->classes, false, true, with_raw != 0);
+    return images_query<CascadeDepth>(net, n, h, w, true, with_raw != 0);
 }
 
 SSAL_API int ssal_icnet_train_cascade_semi_nhwc(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
@@ -1611,26 +1484,20 @@ SSAL_API int ssal_icnet_train_cascade_semi_nhwc(ssal_icnet *net, const void *x_d
 {
     const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
     const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev != nullptr};
-    return cascade_train_entry(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, stats_dev, max_workgroups, a, &semi);
+    return images_entry<CascadeDepth>(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, stats_dev, max_workgroups, a, &semi);
 }
 
 SSAL_API int ssal_icnet_update_cascade(ssal_icnet *net, const float *params_host, void *stream)
 {
     if (!net || !params_host) return fail(SSAL_EINVAL, "NULL argument");
-    std::vector<HostUpdate> t = {{"conv_sub4.kernel", params_host + CA_KC, CA_GC},
-                                 {"conv_sub4.gamma", params_host + CA_GC, 128},
-                                 {"conv_sub4.beta", params_host + CA_BC, 128},
-                                 {"conv3_1_sub2_proj.kernel", params_host + CA_KD, 256 * 128},
-                                 {"conv3_1_sub2_proj.gamma", params_host + CA_GD, 128},
-                                 {"conv3_1_sub2_proj.beta", params_host + CA_BD, 128}};
-    for (const HostUpdate &u : fusion_tensors(params_host + CA_FUSION, net->classes)) t.push_back(u);
-    return update_packed(net, t, {"conv_sub4", "conv3_1_sub2_proj", "conv_sub2", "conv3_sub1_proj", "conv6_cls"}, stream);
+    return update_packed(net, cascade_tensors(params_host, net->classes),
+                         {"conv_sub4", "conv3_1_sub2_proj", "conv_sub2", "conv3_sub1_proj", "conv6_cls"}, stream);
 }
 
 // ---- the high-resolution branch down to the image ----
 SSAL_API int64_t ssal_icnet_highres_grad_workspace_bytes(int n, int h, int w, int classes)
 {
-    return capped_dims_ok(n, classes, highres_fits(n, h, w)) ? highres_bytes(0, n, h, w, classes, true, false, false) : -1;
+    return features_query<HighresDepth>(n, h, w, classes, false, false);
 }
 
 SSAL_API int ssal_icnet_highres_grad_nhwc(const float *conv5_4_k1_dev, const float *conv3_1_dev, const void *x_dev, int n, int h,
@@ -1640,14 +1507,13 @@ SSAL_API int ssal_icnet_highres_grad_nhwc(const float *conv5_4_k1_dev, const flo
                                           void *ws_dev, int64_t ws_bytes, void *stream)
 {
     const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    return highres_grad_entry(conv5_4_k1_dev, conv3_1_dev, x_dev, nullptr, nullptr, nullptr, x_is_u8, c_in, n, h, w, classes,
-                              params_dev, stats_dev, max_workgroups, a, nullptr);
+    return features_entry<HighresDepth>({{conv5_4_k1_dev, conv3_1_dev, x_dev}, {}, params_dev, stats_dev, max_workgroups, n, h, w,
+                                         classes, x_is_u8 != 0, c_in}, a, nullptr);
 }
 
 SSAL_API int64_t ssal_icnet_train_highres_workspace_bytes(const ssal_icnet *net, int n, int h, int w)
 {
-    if (!net_dims_ok(net, n, h, w) || !highres_fits(n, h / 32, w / 32)) return -1;
-    return highres_bytes(trunk_bytes(net, n, h, w), n, h / 32, w / 32, net->classes, false, false, false);
+    return images_query<HighresDepth>(net, n, h, w, false, false);
 }
 
 SSAL_API int ssal_icnet_train_highres_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
@@ -1656,12 +1522,12 @@ SSAL_API int ssal_icnet_train_highres_nhwc(ssal_icnet *net, const void *x_dev, i
                                            double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
     const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    return highres_train_entry(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, stats_dev, max_workgroups, a, nullptr);
+    return images_entry<HighresDepth>(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, stats_dev, max_workgroups, a, nullptr);
 }
 
 SSAL_API int64_t ssal_icnet_highres_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw)
 {
-    return capped_dims_ok(n, classes, highres_fits(n, h, w)) ? highres_bytes(0, n, h, w, classes, true, true, with_raw != 0) : -1;
+    return features_query<HighresDepth>(n, h, w, classes, true, with_raw != 0);
 }
 
 SSAL_API int ssal_icnet_highres_grad_semi_nhwc(const float *conv5_4_k1_dev, const float *conv3_1_dev, const void *x_dev,
@@ -1675,14 +1541,13 @@ SSAL_API int ssal_icnet_highres_grad_semi_nhwc(const float *conv5_4_k1_dev, cons
 {
     const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
     const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, conv5_4_k1_raw_dev != nullptr};
-    return highres_grad_entry(conv5_4_k1_dev, conv3_1_dev, x_dev, conv5_4_k1_raw_dev, conv3_1_raw_dev, x_raw_dev, x_is_u8, c_in, n,
-                              h, w, classes, params_dev, stats_dev, max_workgroups, a, &semi);
+    return features_entry<HighresDepth>({{conv5_4_k1_dev, conv3_1_dev, x_dev}, {conv5_4_k1_raw_dev, conv3_1_raw_dev, x_raw_dev},
+                                         params_dev, stats_dev, max_workgroups, n, h, w, classes, x_is_u8 != 0, c_in}, a, &semi);
 }
 
 SSAL_API int64_t ssal_icnet_train_highres_semi_workspace_bytes(const ssal_icnet *net, int n, int h, int w, int with_raw)
 {
-    if (!net_dims_ok(net, n, h, w) || !highres_fits(n, h / 32, w / 32)) return -1;
-    return highres_bytes(trunk_bytes(net, n, h, w), n, h / 32, w / 32, net->classes, false, true, with_raw != 0);
+    return images_query<HighresDepth>(net, n, h, w, true, with_raw != 0);
 }
 
 SSAL_API int ssal_icnet_train_highres_semi_nhwc(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
@@ -1695,7 +1560,7 @@ SSAL_API int ssal_icnet_train_highres_semi_nhwc(ssal_icnet *net, const void *x_d
 {
     const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
     const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev != nullptr};
-    return highres_train_entry(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, stats_dev, max_workgroups, a, &semi);
+    return images_entry<HighresDepth>(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, stats_dev, max_workgroups, a, &semi);
 }
 
 SSAL_API int ssal_icnet_update_highres(ssal_icnet *net, const float *params_host, void *stream)
@@ -1703,26 +1568,9 @@ SSAL_API int ssal_icnet_update_highres(ssal_icnet *net, const float *params_host
     if (!net || !params_host) return fail(SSAL_EINVAL, "NULL argument");
     if (net->c_in != 3 && net->c_in != 4)
         return fail(SSAL_EINVAL, "the high-resolution trainer takes 3 or 4 input channels (got %d)", net->c_in);
-    const IcnetHighresOff o = icnet_highres_offsets(net->c_in);
-    const float *p = params_host, *c = params_host + o.cascade;
-    std::vector<HostUpdate> t = {{"conv1_sub1.kernel", p + o.k1, o.g1},
-                                 {"conv1_sub1.gamma", p + o.g1, 32},
-                                 {"conv1_sub1.beta", p + o.b1, 32},
-                                 {"conv2_sub1.kernel", p + o.k2, 9 * 32 * 32},
-                                 {"conv2_sub1.gamma", p + o.g2, 32},
-                                 {"conv2_sub1.beta", p + o.b2, 32},
-                                 {"conv3_sub1.kernel", p + o.k3, 9 * 32 * 64},
-                                 {"conv3_sub1.gamma", p + o.g3, 64},
-                                 {"conv3_sub1.beta", p + o.b3, 64},
-                                 {"conv_sub4.kernel", c + CA_KC, CA_GC},
-                                 {"conv_sub4.gamma", c + CA_GC, 128},
-                                 {"conv_sub4.beta", c + CA_BC, 128},
-                                 {"conv3_1_sub2_proj.kernel", c + CA_KD, 256 * 128},
-                                 {"conv3_1_sub2_proj.gamma", c + CA_GD, 128},
-                                 {"conv3_1_sub2_proj.beta", c + CA_BD, 128}};
-    for (const HostUpdate &u : fusion_tensors(c + CA_FUSION, net->classes)) t.push_back(u);
-    return update_packed(net, t, {"conv1_sub1", "conv2_sub1", "conv3_sub1", "conv_sub4", "conv3_1_sub2_proj", "conv_sub2",
-                                  "conv3_sub1_proj", "conv6_cls"}, stream);
+    return update_packed(net, highres_tensors(params_host, net->c_in, net->classes),
+                         {"conv1_sub1", "conv2_sub1", "conv3_sub1", "conv_sub4", "conv3_1_sub2_proj", "conv_sub2", "conv3_sub1_proj",
+                          "conv6_cls"}, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1859,7 +1707,7 @@ SSAL_API int ssal_icnet_debug_conv_dispatch(int n, int h, int w, int cin, int co
 SSAL_API int ssal_icnet_debug_highres_raw_route(int c_in, int n, int h, int w, int *fused_out)
 {
     if (!fused_out) return fail(SSAL_EINVAL, "NULL output");
-    if (int rc = highres_check(n, h, w, 2, c_in, 0)) return rc;
+    if (int rc = depth_check<HighresDepth>(n, h, w, 2, c_in, 0)) return rc;
     *fused_out = icnet_highres_raw_fused(c_in, n, h, w, ssal::knobs().ic_front, ssal::mfma_family()) ? 1 : 0;
     return SSAL_OK;
 }

@@ -1,5 +1,5 @@
 // ssal_train_host.h -- the steps every training entry of the C ABI shares (ssal_api.hip: ENet's six depths; ssal_icnet_api.hip:
-// ICNet's three): what a call is given, the argument checks in their fixed order, the workspace check and the confusion-matrix
+// ICNet's four): what a call is given, the argument checks in their fixed order, the workspace check and the confusion-matrix
 // bracket around the launches.  Host C++ only.
 #pragma once
 #include "../../include/ssal_enet.h"

@@ -1226,25 +1226,34 @@ class ICNetHeadTrainer(FinalLayerTrainer):
         """the entries' arguments between the loss' knobs and ``max_workgroups``, for a call on ``batch``'s device: none here"""
         return ()
 
-    # ---- gradients and steps: one path for the three depths, plain and semi-supervised ----------------------------------------
+    def _feature_to_device(self, i, t):
+        """member ``i`` of ``feats`` / ``features_raw`` as the features entry takes it: a float32 map"""
+        return _lib.as_device_f32(t)
+
+    def _feature_c_args(self, xs, xr):
+        """``_extra_c_args`` of a features call on the device tensors ``xs`` (``xr``: their raw side, or Nones)"""
+        return self._extra_c_args(xs[0])
+
+    # ---- gradients and steps: one path for the four depths, plain and semi-supervised -----------------------------------------
     def _feature_call(self, feats, labels, mask, params, step, max_workgroups, labelled=None, measure=None, threshold=None,
                       features_raw=None, confusion=None, return_pseudo_pixels=False):
         """the features entry on the tuple ``feats``: -> (loss [1], packed gradient, pseudo pixels or None, device state or
         None); ``step``: on the weights of the device state, else on the host variables overridden by ``params``.  A plain
         class refuses the semi-supervised keywords here (``_no_semi``); everything is judged before any device work."""
-        semi = self._semi_call(feats[0], labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels)
+        semi = self._semi_call(feats[0], labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels,
+                               features_raw=features_raw)
         mw = self._check_features(*feats, labels, mask, max_workgroups)
         raw = self._check_raw(feats, features_raw, semi)
         packed = None if step else self._packed_with(params)
-        x = _lib.as_device_f32(feats[0])
-        xs = (x,) + tuple(_lib.as_device_f32(t).to(x.device) for t in feats[1:])
+        x = self._feature_to_device(0, feats[0])
+        xs = (x,) + tuple(self._feature_to_device(i, t).to(x.device) for i, t in enumerate(feats[1:], 1))
         xr = (None,) * len(xs)
         if semi is not None and raw is not None and any(r is not f for r, f in zip(raw, feats)):
-            xr = tuple(_lib.as_device_f32(t).to(x.device) for t in raw)
+            xr = tuple(self._feature_to_device(i, t).to(x.device) for i, t in enumerate(raw))
+        extra = self._feature_c_args(xs, xr) + (mw,)
         dev = self._device_state(x.device) if step else None
         vec = dev["w"] if step else _lib.require_gpu().from_numpy(packed).to(x.device)
-        loss, grad, pp = self._grad_call(xs, xr, labels, mask, vec, semi, confusion, return_pseudo_pixels,
-                                         self._extra_c_args(x) + (mw,))
+        loss, grad, pp = self._grad_call(xs, xr, labels, mask, vec, semi, confusion, return_pseudo_pixels, extra)
         return loss, grad, pp, dev
 
     def _gradient_from(self, feats, labels, mask, params, max_workgroups, return_pseudo_pixels=False, **semi_kw):
@@ -1639,29 +1648,15 @@ class ICNetHighResTrainer(ICNetCascadeTrainer):
             raise ValueError("images must be a floating-point or uint8 tensor (got %s)" % (dt or type(images).__name__))
         return mw
 
-    def _feature_call(self, feats, labels, mask, params, step, max_workgroups, labelled=None, measure=None, threshold=None,
-                      features_raw=None, confusion=None, return_pseudo_pixels=False):
-        """the parent's, with the frames as the third input: they stay uint8 when they are (the entry converts them as the
-        forward path does) and the entry is told their type and channel count"""
-        semi = self._semi_call(feats[0], labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels,
-                               features_raw=features_raw)
-        mw = self._check_features(*feats, labels, mask, max_workgroups)
-        raw = self._check_raw(feats, features_raw, semi)
-        packed = None if step else self._packed_with(params)
-        torch = _lib.require_gpu()
-        x = _lib.as_device_f32(feats[0])
-        xs = (x, _lib.as_device_f32(feats[1]).to(x.device), _lib.as_device_image(feats[2]).to(x.device))
-        xr = (None,) * 3
-        if semi is not None and raw is not None and any(r is not f for r, f in zip(raw, feats)):
-            xr = (_lib.as_device_f32(raw[0]).to(x.device), _lib.as_device_f32(raw[1]).to(x.device),
-                  _lib.as_device_image(raw[2]).to(x.device))
-            if xr[2].dtype != xs[2].dtype:
-                raise ValueError("features_raw: images_raw must have the dtype of images %s (got %s)" % (xs[2].dtype, xr[2].dtype))
-        dev = self._device_state(x.device) if step else None
-        vec = dev["w"] if step else torch.from_numpy(packed).to(x.device)
-        extra = self._extra_c_args(x) + (int(xs[2].dtype == torch.uint8), int(self.net._c_in), mw)
-        loss, grad, pp = self._grad_call(xs, xr, labels, mask, vec, semi, confusion, return_pseudo_pixels, extra)
-        return loss, grad, pp, dev
+    def _feature_to_device(self, i, t):
+        """the frames are the third input: they stay uint8 when they are (the entry converts them as the forward path does)"""
+        return _lib.as_device_image(t) if i == 2 else _lib.as_device_f32(t)
+
+    def _feature_c_args(self, xs, xr):
+        """the parent's, then the frames' type and channel count: one type for both sides of the call"""
+        if xr[2] is not None and xr[2].dtype != xs[2].dtype:
+            raise ValueError("features_raw: images_raw must have the dtype of images %s (got %s)" % (xs[2].dtype, xr[2].dtype))
+        return self._extra_c_args(xs[0]) + (int(xs[2].dtype == _lib.require_gpu().uint8), int(self.net._c_in))
 
     def _check_raw(self, feats, features_raw, semi):
         """the parent's on the triple ``(conv5_4_k1_raw, conv3_1_raw, images_raw)``: the frame is this trainer's third feature
