@@ -209,6 +209,38 @@ int ssal_icnet_train_cascade_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u
 /* ssal_icnet_update_fusion for the fourteen variables: only the five trained layers are re-laid-out, folded and uploaded */
 int ssal_icnet_update_cascade(ssal_icnet *net, const float *params_host, void *stream);
 
+/* ---- Training of the pyramid head: conv5_4_k1 = relu(BN(1 x 1 conv, 1024 -> 256, of conv5_3_sum)),
+ * the low-resolution branch's only path into the cascade, then the whole cascade head as above, over everything up to the
+ * pyramid-pooling sum and the two other frozen branches ----
+ * The seventeen trained variables travel PACKED, in this order: conv5_4_k1.kernel [1,1,1024,256] | .gamma [256] | .beta [256] |
+ * the fourteen of the cascade entries in their order (262656 floats, then theirs); params_dev and grad_dev have that layout.
+ * stats_dev [2 * 256 + 8 * 128] = conv5_4_k1 mean | variance | the eight rows of the cascade entries; batch-norm as there.  One
+ * call computes, for conv5_3_sum [n,h,w,1024] (1/32 resolution), conv3_1 [n,2h,2w,256], conv3_sub1 [n,4h,4w,64], labels uint8
+ * and mask fp32 [n,32h,32w]: conv5_4_k1 by the forward path's own launch on params_dev, the cascade head as
+ * ssal_icnet_cascade_grad_nhwc does, the loss -> loss_dev [1] float64, and the gradient of all seventeen variables -> grad_dev
+ * (without the regulariser).  Nothing below the three inputs gets a gradient.  The loss and the last fourteen gradients are the
+ * bits ssal_icnet_cascade_grad_nhwc gives on the same conv5_4_k1.  Determinism, statuses and the order of the checks as
+ * ssal_icnet_cascade_grad_nhwc's; the size query returns -1 beyond the cascade entries' limit.  max_workgroups (0: no limit)
+ * caps the FIRST grid index of every launch, as there; two launches of this depth have further indices that it does not cap:
+ * the data gradient through conv_sub4 runs 2 x that many workgroups (the two halves of its 256 input channels) and the weight
+ * gradient of conv5_4_k1 16 x that many (8 x 2 slabs of its 1024 x 256 output) -- max_workgroups = 1 is 2 and 16 workgroups. */
+int64_t ssal_icnet_pyramid_grad_workspace_bytes(int n, int h, int w, int classes);
+int ssal_icnet_pyramid_grad_nhwc(const float *conv5_3_sum_dev, const float *conv3_1_dev, const float *conv3_sub1_dev, int n,
+                                 int h, int w, int classes, const float *params_dev, const uint8_t *labels_dev,
+                                 const float *mask_dev, float weight, float label_smoothing, const float *stats_dev,
+                                 int max_workgroups, double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes,
+                                 void *stream);
+/* the same from frames x_dev [n,h,w,c_in] (fp32, or uint8 when x_is_u8 != 0): the frozen trunk until conv5_3_sum, conv3_1 and
+ * conv3_sub1 are written -- its low-resolution schedule ends after the pyramid pooling, conv5_4_k1 is not launched -- then the
+ * tail above; labels / mask [n,h,w].  After the call the endpoints from conv5_4_k1 on are those of params_dev. */
+int64_t ssal_icnet_train_pyramid_workspace_bytes(const ssal_icnet *net, int n, int h, int w);
+int ssal_icnet_train_pyramid_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                                  const uint8_t *labels_dev, const float *mask_dev, const float *params_dev, float weight,
+                                  float label_smoothing, const float *stats_dev, int max_workgroups, double *loss_dev,
+                                  float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream);
+/* ssal_icnet_update_fusion for the seventeen variables: only the six trained layers are re-laid-out, folded and uploaded */
+int ssal_icnet_update_pyramid(ssal_icnet *net, const float *params_host, void *stream);
+
 /* ---- The semi-supervised step of the fusion and the cascade trainer (active_learning.py:226-275, 339-342; DESIGN.md
  * section 30) ----
  * The four gradient calls above with the targets built inside the head's gradient kernel: labelled_dev, measure, threshold,

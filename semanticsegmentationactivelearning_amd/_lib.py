@@ -201,6 +201,13 @@ PROTOTYPES = {
     "ssal_icnet_train_cascade_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
     "ssal_icnet_train_cascade_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
     "ssal_icnet_update_cascade": (_i, [_vp, _vp, _vp]),
+    # ---- training of ICNet's pyramid head: conv5_4_k1 and the cascade head (include/ssal_icnet.h) ----
+    "ssal_icnet_pyramid_grad_workspace_bytes": (_i64, [_i, _i, _i, _i]),
+    "ssal_icnet_pyramid_grad_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64,
+                                          _vp]),
+    "ssal_icnet_train_pyramid_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
+    "ssal_icnet_train_pyramid_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_icnet_update_pyramid": (_i, [_vp, _vp, _vp]),
     # ---- the semi-supervised step of the two (include/ssal_icnet.h) ----
     "ssal_icnet_fusion_grad_semi_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
     "ssal_icnet_fusion_grad_semi_nhwc": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _vp, _i,

@@ -14,6 +14,7 @@
 #include "ssal_train_icnet_cascade.h"
 #include "ssal_train_icnet_fusion.h"
 #include "ssal_train_icnet_highres.h"
+#include "ssal_train_icnet_pyramid.h"
 
 #include <math.h>
 
@@ -256,11 +257,13 @@ struct Grp {
 // both fusion blocks; every fused launch above writes those three: none of them is swallowed)
 // highres = false (with cascade = false): the high-resolution branch is left out too -- only the two backbone branches run
 // (the high-resolution trainer runs conv1_sub1 .. conv3_sub1 on the weights it trains)
+// k1 = false (with cascade = false): the low-resolution schedule ends after the launch that writes conv5_3_sum -- conv5_4_k1 is
+// neither launched nor written (the pyramid trainer runs it on the weights it trains); the high-resolution branch still runs
 // arith: SSAL_ARITH_BF16X3 hands the mode to every run_conv (launch_igemm keeps what has no split kernel exact) and runs the
 // fused blocks on ENet's bf16x3 regular-block kernel; the training, evaluate and regions entries pass the default
 hipError_t run_trunk(const ssal_icnet *net, std::vector<Grp> &grp, bool x_is_u8, int h, int w, bool fused,
                      std::set<std::string> *written = nullptr, bool head = true, bool fusion = true, bool cascade = true,
-                     bool highres = true, int arith = SSAL_ARITH_F32)
+                     bool highres = true, int arith = SSAL_ARITH_F32, bool k1 = true)
 {
     const bool dry = written != nullptr;
 #define OUT(name) do { if (dry) written->insert(name); } while (0)
@@ -360,9 +363,9 @@ hipError_t run_trunk(const ssal_icnet *net, std::vector<Grp> &grp, bool x_is_u8,
     }
     // pyramid pooling + conv5_4_k1
     OUT("conv5_3_sum");
-    OUT("conv5_4_k1");
+    if (k1) OUT("conv5_4_k1");
     EACH(launch_ppm(q.A(cur), q.n, ch, cw, 1024, q.W.pooled, q.A("conv5_3_sum"), q.s));
-    EACH(run_conv(net, "conv5_4_k1", q.A("conv5_3_sum"), q.n, ch, cw, nullptr, true, false, q.A("conv5_4_k1"), q.s, arith));
+    if (k1) EACH(run_conv(net, "conv5_4_k1", q.A("conv5_3_sum"), q.n, ch, cw, nullptr, true, false, q.A("conv5_4_k1"), q.s, arith));
     // ---- high-resolution branch (section 3) ----
     if (!highres) return hipSuccess;
     if ((front & 1) && front2_supported(h, w, net->c_in, 1, 2)) {
@@ -882,6 +885,7 @@ const float *F(const void *p) { return static_cast<const float *>(p); }
 struct HeadDepth {
     using Ws = IcnetHeadWs;
     static constexpr int kUnit = 8, kLevel = 0;
+    static constexpr bool kK1 = true;
     static constexpr bool kStats = false, kFrame = false, kImagesQueryFits = false;
     static constexpr const char *kNoun = "head gradient kernel's", *kEndpoints[] = {"sub12_sum"};
 
@@ -913,6 +917,7 @@ struct HeadDepth {
 struct FusionDepth {
     using Ws = IcnetFusionWs;
     static constexpr int kUnit = 16, kLevel = 1;
+    static constexpr bool kK1 = true;
     static constexpr bool kStats = true, kFrame = false, kImagesQueryFits = false;
     static constexpr const char *kNoun = "fusion gradient kernels'", *kEndpoints[] = {"sub24_sum", "conv3_sub1"};
 
@@ -958,6 +963,7 @@ struct FusionDepth {
 struct CascadeDepth {
     using Ws = IcnetCascadeWs;
     static constexpr int kUnit = 32, kLevel = 2;
+    static constexpr bool kK1 = true;
     static constexpr bool kStats = true, kFrame = false, kImagesQueryFits = false;
     static constexpr const char *kNoun = "cascade gradient kernels'", *kEndpoints[] = {"conv5_4_k1", "conv3_1", "conv3_sub1"};
 
@@ -1003,6 +1009,7 @@ struct CascadeDepth {
 struct HighresDepth {
     using Ws = IcnetHighresWs;
     static constexpr int kUnit = 32, kLevel = 3;
+    static constexpr bool kK1 = true;
     static constexpr bool kStats = true, kFrame = true, kImagesQueryFits = true;
     static constexpr const char *kNoun = "high-resolution gradient kernels'", *kEndpoints[] = {"conv5_4_k1", "conv3_1"};
 
@@ -1042,6 +1049,49 @@ struct HighresDepth {
         return launch_icnet_highres_grad(F(in.f[0]), F(in.f[1]), in.f[2], in.x_is_u8, in.c_in, in.n, in.h, in.w, in.classes, in.params,
                                          in.stats, a.labels, a.mask, a.weight, a.label_smoothing, in.max_workgroups, t, a.loss, a.grad,
                                          a.s, sa);
+    }
+};
+
+// the pyramid head (kernels: ssal_train_icnet_pyramid.hip): conv5_3_sum [n,h32,w32,1024], conv3_1
+// [n,2 h32,2 w32,256] and conv3_sub1 [n,4 h32,4 w32,64].  A sibling of the high-resolution depth: both contain the cascade
+// depth (head < fusion < cascade < {high-resolution, pyramid}).  The trunk of an images entry stops where the cascade depth's
+// does, and its low-resolution schedule ends after conv5_3_sum (kK1 = false); conv5_4_k1, the two blocks and the head write the
+// endpoints from conv5_4_k1 on.  The semi-supervised entries are not built yet: there is no target launch.
+struct PyramidDepth {
+    using Ws = IcnetPyramidWs;
+    static constexpr int kUnit = 32, kLevel = 2;
+    static constexpr bool kK1 = false;
+    static constexpr bool kStats = true, kFrame = false, kImagesQueryFits = false;
+    static constexpr const char *kNoun = "pyramid gradient kernels'", *kEndpoints[] = {"conv5_3_sum", "conv3_1", "conv3_sub1"};
+
+    static Ws carve(Bump &b, int64_t n, int h32, int w32, int classes, bool own_acts)
+    {
+        Ws t;
+        const int64_t act = n * h32 * (int64_t)w32 * PY_CO;
+        t.wt = b.take<float>(PY_G);
+        t.rows = b.take<float>(2 * PY_CO);
+        t.f1 = own_acts ? b.take<float>(act) : nullptr;
+        t.du = b.take<float>(4 * act);
+        t.g32 = b.take<float>(act);
+        t.part = b.take<float>((int64_t)PY_MAX_WG * PY_PART);  // (sized for the default grid: max_workgroups only lowers it)
+        t.fold = b.take<float>(PY_PART);
+        t.cascade = CascadeDepth::carve(b, n, h32, w32, classes, own_acts);
+        return t;
+    }
+    static void bind(Ws &t, const IcWorkspace &W)
+    {
+        t.f1 = W.act.at("conv5_4_k1");
+        CascadeDepth::bind(t.cascade, W);
+    }
+    static bool fits(int n, int h32, int w32) { return icnet_pyramid_fits(h32, w32) && CascadeDepth::fits(n, h32, w32); }
+    static hipError_t targets(const DepthIn &, const Ws &, const IcnetHeadSemi &, uint8_t *, hipStream_t)
+    {
+        return hipErrorNotSupported;  // (no entry hands this depth a SemiArgs)
+    }
+    static hipError_t grad(const DepthIn &in, const CallArgs &a, const Ws &t, const IcnetHeadSemi *)
+    {
+        return launch_icnet_pyramid_grad(F(in.f[0]), F(in.f[1]), F(in.f[2]), in.n, in.h, in.w, in.classes, in.params, in.stats,
+                                         a.labels, a.mask, a.weight, a.label_smoothing, in.max_workgroups, t, a.loss, a.grad, a.s);
     }
 };
 
@@ -1144,12 +1194,13 @@ int images_entry(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int 
     if constexpr (D::kFrame) in.f[i] = x_dev, in.raw[i] = x_raw_dev;
     // the frozen trunk, on the undistorted (of_raw) or the training frames, through the same slots of W.  It ends in front of the
     // layers being trained: run_trunk without the head, and from level 1 / 2 / 3 on without the last fusion stage / the first
-    // one / the high-resolution branch
+    // one / the high-resolution branch; without conv5_4_k1 where the depth trains it (kK1)
     hipStream_t s = a.s;
     auto trunk = [=, &W](bool of_raw) -> int {
         std::vector<Grp> one(1);
         one[0] = {W, of_raw ? x_raw_dev : x_dev, n, s};
-        HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false, D::kLevel < 1, D::kLevel < 2, D::kLevel < 3));
+        HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false, D::kLevel < 1, D::kLevel < 2, D::kLevel < 3,
+                          SSAL_ARITH_F32, D::kK1));
         return SSAL_OK;
     };
     return depth_run<D>(trunk, in, a, semi, c);
@@ -1270,6 +1321,12 @@ HostUpdates highres_tensors(const float *p, int c_in, int K)
                  {"conv3_sub1.gamma", p + o.g3, 64},
                  {"conv3_sub1.beta", p + o.b3, 64}},
                 cascade_tensors(p + o.cascade, K));
+}
+
+HostUpdates pyramid_tensors(const float *p, int K)
+{
+    return then({{"conv5_4_k1.kernel", p + PY_K, PY_G}, {"conv5_4_k1.gamma", p + PY_G, PY_CO}, {"conv5_4_k1.beta", p + PY_B, PY_CO}},
+                cascade_tensors(p + PY_CASCADE, K));
 }
 
 }  // namespace
@@ -1492,6 +1549,44 @@ SSAL_API int ssal_icnet_update_cascade(ssal_icnet *net, const float *params_host
     if (!net || !params_host) return fail(SSAL_EINVAL, "NULL argument");
     return update_packed(net, cascade_tensors(params_host, net->classes),
                          {"conv_sub4", "conv3_1_sub2_proj", "conv_sub2", "conv3_sub1_proj", "conv6_cls"}, stream);
+}
+
+// ---- the pyramid head: conv5_4_k1 and the whole cascade head ----
+SSAL_API int64_t ssal_icnet_pyramid_grad_workspace_bytes(int n, int h, int w, int classes)
+{
+    return features_query<PyramidDepth>(n, h, w, classes, false, false);
+}
+
+SSAL_API int ssal_icnet_pyramid_grad_nhwc(const float *conv5_3_sum_dev, const float *conv3_1_dev, const float *conv3_sub1_dev,
+                                          int n, int h, int w, int classes, const float *params_dev,
+                                          const uint8_t *labels_dev, const float *mask_dev, float weight,
+                                          float label_smoothing, const float *stats_dev, int max_workgroups, double *loss_dev,
+                                          float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return features_entry<PyramidDepth>({{conv5_3_sum_dev, conv3_1_dev, conv3_sub1_dev}, {}, params_dev, stats_dev, max_workgroups,
+                                         n, h, w, classes}, a, nullptr);
+}
+
+SSAL_API int64_t ssal_icnet_train_pyramid_workspace_bytes(const ssal_icnet *net, int n, int h, int w)
+{
+    return images_query<PyramidDepth>(net, n, h, w, false, false);
+}
+
+SSAL_API int ssal_icnet_train_pyramid_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                                           const uint8_t *labels_dev, const float *mask_dev, const float *params_dev,
+                                           float weight, float label_smoothing, const float *stats_dev, int max_workgroups,
+                                           double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return images_entry<PyramidDepth>(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, stats_dev, max_workgroups, a, nullptr);
+}
+
+SSAL_API int ssal_icnet_update_pyramid(ssal_icnet *net, const float *params_host, void *stream)
+{
+    if (!net || !params_host) return fail(SSAL_EINVAL, "NULL argument");
+    return update_packed(net, pyramid_tensors(params_host, net->classes),
+                         {"conv5_4_k1", "conv_sub4", "conv3_1_sub2_proj", "conv_sub2", "conv3_sub1_proj", "conv6_cls"}, stream);
 }
 
 // ---- the high-resolution branch down to the image ----

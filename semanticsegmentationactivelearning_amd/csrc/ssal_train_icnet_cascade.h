@@ -28,6 +28,18 @@ constexpr int CA_PART = CaBlock::PART;              // floats of one split-K par
 constexpr int CA_MAX_WG = CaBlock::MAX_WG;          // split-K groups the finish kernel folds (x CA_TAPS x 2 workgroups)
 bool icnet_cascade_fits(int h32, int w32);
 
+// The two backward kernels of this block at 256 channels, for the layer below it (the profile's k_icnet_pyramid_dx /
+// k_icnet_pyramid_g32).  k_icnet_cascade_dx<256>: the data gradient through conv_sub4, g24 [N, h16, w16,
+// 128] (un-normalised, behind sub24_sum's ReLU), Kc [3,3,256,128], sc [128] its batch-norm scale -> du [N, h16, w16, 256]; grid
+// (tiles strided, 2 halves of the input channels); one accumulator adds its 9 * 128 products in the order (quarter of co, tap,
+// co).  k_icnet_cascade_g24<256>: the adjoint of the legacy 2x resize h16 -> h32 with the ReLU mask of f1 = conv5_4_k1
+// [N, h32, w32, 256] -> g32, each element its at most 3 x 3 terms, rows then columns ascending.
+// max_workgroups caps grid.x only: the data gradient launches 2 x that many workgroups.
+hipError_t launch_icnet_cascade_dx256(const float *g24, const float *Kc, const float *sc, int N, int h16, int w16,
+                                      int max_workgroups, float *du, hipStream_t s);
+hipError_t launch_icnet_cascade_g32(const float *du, const float *f1, int N, int h32, int w32, int max_workgroups, float *g32,
+                                    hipStream_t s);
+
 struct IcnetCascadeWs {
     float *wt_c;    // conv_sub4's kernel in igemm_relayout's layout [9][8][128][32]
     float *wt_d;    // conv3_1_sub2_proj's [1][8][128][32]

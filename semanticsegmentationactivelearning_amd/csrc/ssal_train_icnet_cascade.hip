@@ -38,10 +38,15 @@ bool icnet_cascade_fits(int h32, int w32)
 //   for each tap (ascending): K[tap, :, quarter] -> LDS as [co][ci]; 16 steps of two co each: lane (r = lane & 31,
 //   h = lane >> 5) feeds gs[pixel 32 j + r shifted by the tap][2 s + h] and K[2 s + h][32 w + r].
 // One accumulator therefore adds its 1152 products in the order (quarter, tap, co): the chain of section 29's bound.
+// CIN: the input channels of the convolution (K [9][CIN][128], du [.., CIN]).  128: conv_sub2, the kernel as it always was;
+// 256: conv_sub4 at 1/16 resolution -- blockIdx.y picks the half of 128 input channels a workgroup owns.
+template <int CIN>
 __global__ __launch_bounds__(256) void k_icnet_cascade_dx(const float *__restrict__ g, const float *__restrict__ Ka,
                                                           const float *__restrict__ sa, int N, int h8, int w8,
                                                           float *__restrict__ du)
 {
+    static_assert(CIN == 128 || CIN == 256, "the two fusion blocks of ICNet");
+    const int cb = CIN == 128 ? 0 : 128 * (int)blockIdx.y;  // first input channel of this workgroup
     __shared__ __attribute__((aligned(16))) float win[DX_WH * DX_WW * DX_LDA];
     __shared__ __attribute__((aligned(16))) float Wb[DX_CO * DX_LDB];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
@@ -73,7 +78,7 @@ __global__ __launch_bounds__(256) void k_icnet_cascade_dx(const float *__restric
                 if (tap) __syncthreads();  // the previous tap's MFMAs are done with Wb
                 for (int e = tid; e < 128 * (DX_CO / 4); e += 256) {
                     const int ci = e >> 3, q = e & 7;
-                    const float4 v = reinterpret_cast<const float4 *>(Ka + (tap * 128 + ci) * 128 + DX_CO * cc)[q];
+                    const float4 v = reinterpret_cast<const float4 *>(Ka + (tap * CIN + cb + ci) * 128 + DX_CO * cc)[q];
                     Wb[(4 * q + 0) * DX_LDB + ci] = v.x;
                     Wb[(4 * q + 1) * DX_LDB + ci] = v.y;
                     Wb[(4 * q + 2) * DX_LDB + ci] = v.z;
@@ -98,7 +103,7 @@ __global__ __launch_bounds__(256) void k_icnet_cascade_dx(const float *__restric
             for (int i = 0; i < 16; ++i) {
                 const int p = 32 * j + (i & 3) + 8 * (i >> 2) + 4 * hh;
                 const int y = y0 + (p >> 4), xx = x0 + (p & 15);
-                if (y < h8 && xx < w8) du[((n * h8 + y) * w8 + xx) * 128 + 32 * wave + r] = acc[j][i];
+                if (y < h8 && xx < w8) du[((n * h8 + y) * w8 + xx) * CIN + cb + 32 * wave + r] = acc[j][i];
             }
     }
 }
@@ -106,15 +111,18 @@ __global__ __launch_bounds__(256) void k_icnet_cascade_dx(const float *__restric
 // g24[q, ci] = sub24_sum[q, ci] > 0 ? sum_{p'} w(p', q) du[p', ci] : 0: the adjoint of launch_resize_bilinear's exact 2x (even
 // rows / columns copy, odd ones average with the +1 tap clamped to the map, so the last row / column collects its clamped tap
 // twice: weight 1/2 + 1/2).  Every pixel of sub24_sum gathers its at most 3 x 3 pixels of du, rows then columns ascending,
-// fmaf; the weights are powers of two.  One float4 of channels per thread.
+// fmaf; the weights are powers of two.  One float4 of channels per thread.  C: the channels of du and of the map below
+// (128: sub24_sum, the kernel as it always was; 256: conv5_4_k1).
+template <int C>
 __global__ __launch_bounds__(256) void k_icnet_cascade_g24(const float *__restrict__ du, const float *__restrict__ s24, int N,
                                                            int h16, int w16, float *__restrict__ g24)
 {
     const int h8 = 2 * h16, w8 = 2 * w16;
-    const long total = (long)N * h16 * w16 * 32;
+    constexpr int Q = C / 4, QS = C == 128 ? 5 : 6;
+    const long total = (long)N * h16 * w16 * Q;
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-        const int q = (int)(e & 31);
-        const long p = e >> 5;
+        const int q = (int)(e & (Q - 1));
+        const long p = e >> QS;
         const int c = (int)(p % w16), r = (int)((p / w16) % h16);
         const long n = p / ((long)w16 * h16);
         float4 o = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -126,17 +134,42 @@ __global__ __launch_bounds__(256) void k_icnet_cascade_g24(const float *__restri
                 const int xx = 2 * c + dx;
                 if (xx < 0) continue;
                 const float w = wy * (dx == 0 || (dx == 1 && c == w16 - 1) ? 1.0f : 0.5f);
-                const float4 v = reinterpret_cast<const float4 *>(du + ((n * h8 + y) * w8 + xx) * 128)[q];
+                const float4 v = reinterpret_cast<const float4 *>(du + ((n * h8 + y) * w8 + xx) * C)[q];
                 o.x = fmaf(w, v.x, o.x);
                 o.y = fmaf(w, v.y, o.y);
                 o.z = fmaf(w, v.z, o.z);
                 o.w = fmaf(w, v.w, o.w);
             }
         }
-        const float4 xv = reinterpret_cast<const float4 *>(s24 + p * 128)[q];
-        reinterpret_cast<float4 *>(g24 + p * 128)[q] =
+        const float4 xv = reinterpret_cast<const float4 *>(s24 + p * C)[q];
+        reinterpret_cast<float4 *>(g24 + p * C)[q] =
             make_float4(xv.x > 0.0f ? o.x : 0.0f, xv.y > 0.0f ? o.y : 0.0f, xv.z > 0.0f ? o.z : 0.0f, xv.w > 0.0f ? o.w : 0.0f);
     }
+}
+
+// The two kernels at 256 channels (ssal_train_icnet_cascade.h): conv_sub4's data gradient and the resize adjoint below it
+hipError_t launch_icnet_cascade_dx256(const float *g24, const float *Kc, const float *sc, int N, int h16, int w16,
+                                      int max_workgroups, float *du, hipStream_t s)
+{
+    if (N < 1 || max_workgroups < 0 || h16 < 2 || w16 < 2 || !icnet_cascade_fits(h16 / 2, w16 / 2)) return hipErrorInvalidValue;
+    const double pix16 = (double)N * h16 * w16;
+    const long tiles = (long)N * icnet_cdiv(h16, CA_DX_TH) * icnet_cdiv(w16, CA_DX_TW);
+    ProfScope prof("k_icnet_pyramid_dx", 2.0 * pix16 * 9 * 128 * 256, 4.0 * pix16 * (2 * 128 + 256) + 4.0 * (double)tiles * 9 * 256 * 128,
+                   s);
+    hipLaunchKernelGGL(k_icnet_cascade_dx<256>, dim3(icnet_grid(tiles, CA_DX_MAX_WG, max_workgroups), 2), dim3(256), 0, s, g24, Kc,
+                       sc, N, h16, w16, du);
+    return hipGetLastError();
+}
+
+hipError_t launch_icnet_cascade_g32(const float *du, const float *f1, int N, int h32, int w32, int max_workgroups, float *g32,
+                                    hipStream_t s)
+{
+    if (N < 1 || max_workgroups < 0 || !icnet_cascade_fits(h32, w32)) return hipErrorInvalidValue;
+    const double pix32 = (double)N * h32 * w32;
+    const int B = icnet_grid(icnet_cdiv((long)N * h32 * w32 * 64, 256), 65536, max_workgroups);
+    ProfScope prof("k_icnet_pyramid_g32", 18.0 * pix32 * 256, 4.0 * (4.0 * pix32 + 2.0 * pix32) * 256, s);
+    hipLaunchKernelGGL(k_icnet_cascade_g24<256>, dim3(B), dim3(256), 0, s, du, f1, N, h32, w32, g32);
+    return hipGetLastError();
 }
 
 // the pack, then the forward path's own launches (ssal_icnet_api.hip, run_trunk) on the weights being trained:
@@ -191,14 +224,14 @@ hipError_t launch_icnet_cascade_grad(const float *c54, const float *c31, const f
         const long tiles = (long)N * icnet_cdiv(h8, CA_DX_TH) * icnet_cdiv(w8, CA_DX_TW);
         ProfScope prof("k_icnet_cascade_dx", 2.0 * pix8 * 9 * 128 * 128, 8.0 * pix8 * 128 + 4.0 * (double)tiles * 9 * 128 * 128,
                        s);
-        hipLaunchKernelGGL(k_icnet_cascade_dx, dim3(icnet_grid(tiles, CA_DX_MAX_WG, max_workgroups)), dim3(256), 0, s,
+        hipLaunchKernelGGL(k_icnet_cascade_dx<128>, dim3(icnet_grid(tiles, CA_DX_MAX_WG, max_workgroups)), dim3(256), 0, s,
                            ws.fusion.g, params + CA_FUSION + FU_KA, ws.fusion.rows, N, h8, w8, ws.du);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     {
         const int B = icnet_grid(icnet_cdiv((long)N * h16 * w16 * 32, 256), 65536, max_workgroups);
         ProfScope prof("k_icnet_cascade_g24", 18.0 * pix16 * 128, 4.0 * (pix8 + 2.0 * pix16) * 128, s);
-        hipLaunchKernelGGL(k_icnet_cascade_g24, dim3(B), dim3(256), 0, s, ws.du, ws.sub24, N, h16, w16, ws.g24);
+        hipLaunchKernelGGL(k_icnet_cascade_g24<128>, dim3(B), dim3(256), 0, s, ws.du, ws.sub24, N, h16, w16, ws.g24);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     const int G = icnet_block_workgroups<256>(N, h32, w32, max_workgroups);

@@ -322,9 +322,10 @@ class FinalLayerTrainer:
                   + (_lib.dev_ptr(loss), _lib.dev_ptr(grad)) + after_grad + (_lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))))
         return loss, grad, pp
 
-    def _step_images(self, images, images_raw, labels, mask, semi, confusion, return_pseudo_pixels, extra=()):
-        """one Adam step through the images entry (the plain one, or with ``semi`` the semi-supervised one): the frozen
-        trunk, the training kernels, Adam.  -> loss before the step[, pseudo pixels]"""
+    def _images_call(self, images, images_raw, labels, mask, semi, confusion, return_pseudo_pixels, extra=(), weights=None):
+        """the images entry (the plain one, or with ``semi`` the semi-supervised one): the frozen trunk and the training
+        kernels on the weights of the device state (``weights``: on that packed device vector instead), the gradient into
+        the device state's ``grad``.  No update.  -> (loss [1], pseudo pixels or None, device state)"""
         torch = _lib.require_gpu()
         net = self.net
         x = net._prepare(images, False)
@@ -351,10 +352,18 @@ class FinalLayerTrainer:
             after_mask, after_grad = self._semi_c_args(semi, lbd, confusion, pp)
             _lib.check(getattr(L, stem + "_nhwc")(
                 *((handle, _lib.dev_ptr(x)) + tuple(_lib.dev_ptr(t) for t in raw) + (int(x.dtype == torch.uint8), n, h, w,
-                  _lib.dev_ptr(lab), _lib.dev_ptr(mk)) + after_mask + (_lib.dev_ptr(dev["w"]), self.weight,
+                  _lib.dev_ptr(lab), _lib.dev_ptr(mk)) + after_mask + (_lib.dev_ptr(dev["w"] if weights is None else weights),
+                  self.weight,
                   self.label_smoothing) + tuple(extra) + (_lib.dev_ptr(loss), _lib.dev_ptr(dev["grad"])) + after_grad
                   + (_lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr()))))
             net._note_call(ws, (n, h, w), "train")
+        return loss, pp, dev
+
+    def _step_images(self, images, images_raw, labels, mask, semi, confusion, return_pseudo_pixels, extra=()):
+        """one Adam step through the images entry: ``_images_call``, then Adam.  -> loss before the step[, pseudo pixels]"""
+        torch = _lib.require_gpu()
+        loss, pp, dev = self._images_call(images, images_raw, labels, mask, semi, confusion, return_pseudo_pixels, extra)
+        with torch.cuda.device(dev["w"].device):
             self._apply(dev, dev["grad"])
         return (loss[0], pp) if return_pseudo_pixels else loss[0]
 
@@ -1709,6 +1718,90 @@ class ICNetHighResTrainer(ICNetCascadeTrainer):
                                       return_pseudo_pixels=return_pseudo_pixels)
 
 
+# ---- ICNet's pyramid head: conv5_4_k1 over the pyramid-pooling sum, with the cascade head ----------------
+_PYRAMID_VARS = (("conv5_4_k1", "kernel", True), ("conv5_4_k1", "gamma", False), ("conv5_4_k1", "beta", False)) + _CASCADE_VARS
+# rows of mixed widths (256, 256, then the cascade trainer's eight of 128), concatenated unpadded
+_PYRAMID_STATS = (("conv5_4_k1", "mean"), ("conv5_4_k1", "variance")) + _CASCADE_STATS
+
+
+class ICNetPyramidTrainer(ICNetCascadeTrainer):
+    """Adam on ``conv5_4_k1`` -- the 1 x 1 convolution (1024 -> 256) + batch-norm + ReLU over the pyramid-pooling sum
+    ``conv5_3_sum``, the low-resolution branch's only path into the cascade (ICNET_SPEC section 2) -- and the cascade head
+    above it: everything ``ICNetCascadeTrainer`` trains.  Frozen (``training=False``): everything up to and including
+    ``conv5_3_sum`` [N, H/32, W/32, 1024] (the pyramid pooling and its sum have no parameters), ``conv3_1`` [N, H/16, W/16, 256]
+    and ``conv3_sub1`` [N, H/8, W/8, 64]; nothing below them gets a gradient.  Batch-norm, hyper-parameters, Adam and the
+    refusals are the parent's; the ``l1_l2`` regulariser goes to the six kernels only.  A sibling of ``ICNetHighResTrainer``:
+    both extend the cascade trainer, neither contains the other.
+
+    The 17 variables travel as one packed float32 vector in the order of ``variable_names``: ``conv5_4_k1``'s three, then the
+    parent's fourteen in the parent's order.  The semi-supervised keywords are refused."""
+
+    _C_FEATURES = ("ssal_icnet_pyramid_grad", None)
+    _C_IMAGES = ("ssal_icnet_train_pyramid", None)
+    _CHANNELS, _UP = 1024, 32
+    _VARS, _STATS, _C_UPDATE = _PYRAMID_VARS, _PYRAMID_STATS, "ssal_icnet_update_pyramid"
+    variable_names = ["%s.%s" % (layer, attr) for layer, attr, _ in _PYRAMID_VARS]
+
+    _SEMI_NOUN = "ICNet's pyramid trainer"
+    _FEATURE_NAMES = ("conv5_3_sum", "conv3_1", "conv3_sub1")
+
+    def _check_features(self, conv5_3_sum, conv3_1, conv3_sub1, labels, mask, max_workgroups):
+        mw = self._check_call(conv5_3_sum, 32, labels, mask, max_workgroups, 1024)
+        n, h, w, _ = tuple(np.shape(conv5_3_sum))
+        for name, t, want in (("conv3_1", conv3_1, (n, 2 * h, 2 * w, 256)), ("conv3_sub1", conv3_sub1, (n, 4 * h, 4 * w, 64))):
+            if tuple(np.shape(t)) != want:
+                raise ValueError("%s must be %s for conv5_3_sum %s (got %s)" % (name, want, (n, h, w, 1024), tuple(np.shape(t))))
+            dt = str(getattr(t, "dtype", ""))
+            if "float" not in dt:
+                raise ValueError("%s must be a floating-point tensor (got %s)" % (name, dt or type(t).__name__))
+        return mw
+
+    def gradient_features(self, conv5_3_sum, conv3_1, conv3_sub1, labels, mask, params=None, max_workgroups=0, labelled=None,
+                          confusion=None, return_pseudo_pixels=False):
+        """(loss float64 [1], {name: gradient} for ``variable_names``) on the device for ``conv5_3_sum`` [N, h, w, 1024],
+        ``conv3_1`` [N, 2h, 2w, 256], ``conv3_sub1`` [N, 4h, 4w, 64] and labels / mask [N, 32h, 32w].  ``params`` overrides
+        any of the 17 tensors; ``max_workgroups``: 0 = the default grids, a tuning knob.  No update."""
+        return self._gradient_from((conv5_3_sum, conv3_1, conv3_sub1), labels, mask, params, max_workgroups, labelled=labelled,
+                                   confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
+
+    def features(self, images):
+        """``(conv5_3_sum [N, H/32, W/32, 1024], conv3_1 [N, H/16, W/16, 256], conv3_sub1 [N, H/8, W/8, 64])`` for ``images``
+        (copies): what ``step_features`` and ``gradient_features`` take.  One forward pass of the frozen layers."""
+        self.net(images, training=False)
+        return tuple(self.net.endpoint(name).clone() for name in ("conv5_3_sum", "conv3_1", "conv3_sub1"))
+
+    def step_features(self, conv5_3_sum, conv3_1, conv3_sub1, labels, mask, max_workgroups=0, labelled=None, confusion=None,
+                      return_pseudo_pixels=False):
+        """one Adam step from cached features; returns the loss (float64 device scalar) BEFORE the step"""
+        return self._step_from((conv5_3_sum, conv3_1, conv3_sub1), labels, mask, max_workgroups, labelled=labelled,
+                               confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
+
+    def gradient(self, images, labels, mask, params=None, max_workgroups=0, labelled=None, confusion=None,
+                 return_pseudo_pixels=False):
+        """``gradient_features(*features(images), ...)`` through the images entry: the frozen trunk (its low-resolution
+        schedule ends after ``conv5_3_sum``), then ``conv5_4_k1``, the cascade head and their gradient kernels, on the host
+        variables overridden by ``params``.  No update."""
+        semi = self._semi_call(images, labels, mask, labelled, None, None, confusion, return_pseudo_pixels)
+        mw = self._check_call(images, 1, labels, mask, max_workgroups, None)
+        packed = self._packed_with(params)
+        torch = _lib.require_gpu()
+        x = self.net._prepare(images, False)
+        vec = torch.from_numpy(packed).to(x.device)
+        loss, _, dev = self._images_call(x, None, labels, mask, semi, confusion, return_pseudo_pixels,
+                                         self._extra_c_args(x) + (mw,), weights=vec)
+        with torch.cuda.device(x.device):
+            grad = torch.empty_like(dev["grad"])
+            grad.copy_(dev["grad"])
+        return loss, self._unpack(grad)
+
+    def step(self, images, labels, mask, max_workgroups=0, labelled=None, confusion=None, return_pseudo_pixels=False):
+        """one Adam step from images [N, H, W, C] (fp32 or decoded uint8) and labels / mask [N, H, W]: the frozen trunk up to
+        ``conv5_3_sum``, ``conv3_1`` and ``conv3_sub1``, then ``conv5_4_k1``, both fusion blocks and the head on the weights
+        being trained, their gradient kernels, Adam.  Returns the loss (float64 device scalar) before the step."""
+        return self._step_from_images(images, labels, mask, max_workgroups, labelled=labelled, confusion=confusion,
+                                      return_pseudo_pixels=return_pseudo_pixels)
+
+
 # ---- the semi-supervised step of ICNet's fusion and cascade trainers (DESIGN.md section 30) --------------------------------------
 class SemiSupervisedICNetFusionTrainer(_SemiKeywords, ICNetFusionTrainer):
     """``ICNetFusionTrainer`` with the reference's semi-supervised step (active_learning.py:226-275, 339-342) built into the
@@ -1825,4 +1918,5 @@ __all__ = ["FinalLayerTrainer", "LastBlockTrainer", "LastStageTrainer", "Decoder
            "SemiSupervisedStageTrainer", "SemiSupervisedTailTrainer", "DeepTailTrainer", "SemiSupervisedDeepTailTrainer",
            "DecoderTrainer", "SemiSupervisedDecoderTrainer", "ICNetHeadTrainer", "SemiSupervisedICNetHeadTrainer",
            "ICNetFusionTrainer", "ICNetCascadeTrainer", "SemiSupervisedICNetFusionTrainer",
-           "SemiSupervisedICNetCascadeTrainer", "ICNetHighResTrainer", "SemiSupervisedICNetHighResTrainer"]
+           "SemiSupervisedICNetCascadeTrainer", "ICNetHighResTrainer", "SemiSupervisedICNetHighResTrainer",
+           "ICNetPyramidTrainer"]
