@@ -1711,10 +1711,15 @@ SSAL_API int ssal_profile_collect(char *json_out, int64_t cap)
 // ------------------------------------------------------------------------------------------------
 // Training of ENet's tail over a frozen trunk (include/ssal_enet.h, "Output-layer training" to "Decoder training";
 // DESIGN.md sections 15-22).  Six depths -- the output layer, the last block, the last stage, the decoder tail, the deep tail,
-// the decoder -- each entered from cached features or from images, plain or semi-supervised.  Every depth has ONE body
-// (final_grad_run, train_block_run, train_stage_run, train_tail_run with R = 1 for the decoder tail and R = 2 for the deep
-// tail, train_decoder_run) that takes the features and an optional SemiArgs; the public entries validate (dims, then semi
-// arguments, then NULL pointers, then the workspace size, all before any launch), carve the workspace and call it.
+// the decoder -- each entered from cached features or from images, plain or semi-supervised.  The five depths below the output
+// layer are ONE description each (BlockDepth, StageDepth, TailDepth<R> with R = 1 for the decoder tail and R = 2 for the deep
+// tail, DecoderDepth), which states what differs and contains the depth above it.  What is done with a
+// description is written once: depth_carve and depth_bytes / enet_depth_bytes (the queries and the entries' workspace check
+// both read them), the body depth_run (the features, those of the undistorted frames, an optional SemiArgs), its wrappers
+// features_entry and images_entry, which validate (dims, then the depth's check, then semi arguments and NULL pointers, then
+// raw all-or-none, then the workspace size, all before any launch), carve and call it, and features_offset.  The public
+// entries pack their arguments and call one of these.  The output layer has no target launch, carves in its entries and
+// always gives its raw frames a slot of their own: it keeps its body (final_grad_run) and shares the steps and the packing.
 // CallArgs, SemiArgs, args_check, ws_check, no_trunk and with_confusion are ssal_train_host.h's: ICNet's entries share them.
 // ------------------------------------------------------------------------------------------------
 // ---- the steps ENet's entries share ----
@@ -1723,19 +1728,40 @@ static bool net_dims_ok(const ssal_enet *net, int n, int h, int w)
     return net && net->committed && n > 0 && h > 0 && w > 0 && h % 8 == 0 && w % 8 == 0;
 }
 
-// fits = the depth's own limit (final_grad_fits, train_block_fits, train_stage_fits)
+// fits = the depth's own limit (final_grad_fits, train_block_fits, train_stage_fits, ...)
 static bool grad_dims_ok(int n, int h, int w, int classes, bool (*fits)(int, int))
 {
     return classes >= 2 && classes <= 32 && n > 0 && h > 0 && w > 0 && fits(h, w);
 }
 
-static int final_grad_check(int n, int h, int w, int classes)
+// the same as a verdict, in the order of its messages: classes, dims, the grid cap, the limit (noun: what the message calls the
+// depth's kernels)
+static int grad_dims_check(int n, int h, int w, int classes, int max_workgroups, bool (*fits)(int, int), const char *noun)
 {
     if (classes < 2 || classes > 32) return fail(SSAL_EINVAL, "classes must be in [2,32] (got %d)", classes);
     if (n <= 0 || h <= 0 || w <= 0) return fail(SSAL_EINVAL, "bad dims n=%d h=%d w=%d", n, h, w);
-    if (!final_grad_fits(h, w))
-        return fail(SSAL_EINVAL, "feature map %dx%d is beyond the output-layer gradient kernel's limit", h, w);
+    if (max_workgroups < 0) return fail(SSAL_EINVAL, "max_workgroups must be >= 0 (got %d)", max_workgroups);
+    if (!fits(h, w)) return fail(SSAL_EINVAL, "feature map %dx%d is beyond the %s limit", h, w, noun);
     return SSAL_OK;
+}
+
+// (the output layer's entries, and the last block's, take no grid cap)
+static int final_grad_check(int n, int h, int w, int classes)
+{
+    return grad_dims_check(n, h, w, classes, 0, final_grad_fits, "output-layer gradient kernel's");
+}
+
+// CallArgs / SemiArgs from the public argument lists (raw: the entry's features or frames of the undistorted side, or NULL)
+static CallArgs call_args(const uint8_t *labels_dev, const float *mask_dev, float weight, float label_smoothing, double *loss_dev,
+                          float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    return {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+}
+
+static SemiArgs semi_args(const uint8_t *labelled_dev, int measure, float threshold, int64_t *confusion_dev,
+                          int64_t *pseudo_pixels_dev, const void *raw)
+{
+    return {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, raw != nullptr};
 }
 
 // carves the forward workspace into W and returns a Bump positioned behind it (not ok when W is not)
@@ -1855,7 +1881,7 @@ SSAL_API int ssal_final_grad_nhwc(const float *features_dev, int n, int h, int w
                                   const uint8_t *labels_dev, const float *mask_dev, float weight, float label_smoothing,
                                   double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    const CallArgs a = call_args(labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, stream);
     return final_grad_entry(features_dev, nullptr, n, h, w, classes, kernel_dev, a, nullptr);
 }
 
@@ -1869,7 +1895,7 @@ SSAL_API int ssal_enet_train_final_nhwc(ssal_enet *net, const void *x_dev, int x
                                         float weight, float label_smoothing, double *loss_dev, float *grad_dev,
                                         void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    const CallArgs a = call_args(labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, stream);
     return final_train_entry(net, x_dev, nullptr, x_is_u8, n, h, w, kernel_dev, a, nullptr);
 }
 
@@ -1885,8 +1911,8 @@ SSAL_API int ssal_final_grad_semi_nhwc(const float *features_dev, const float *f
                                        int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes,
                                        void *stream)
 {
-    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, features_raw_dev != nullptr};
+    const CallArgs a = call_args(labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, stream);
+    const SemiArgs semi = semi_args(labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, features_raw_dev);
     return final_grad_entry(features_dev, features_raw_dev, n, h, w, classes, kernel_dev, a, &semi);
 }
 
@@ -1902,8 +1928,8 @@ SSAL_API int ssal_enet_train_final_semi_nhwc(ssal_enet *net, const void *x_dev, 
                                              float *grad_dev, int64_t *confusion_dev, int64_t *pseudo_pixels_dev,
                                              void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev != nullptr};
+    const CallArgs a = call_args(labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, stream);
+    const SemiArgs semi = semi_args(labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev);
     return final_train_entry(net, x_dev, x_raw_dev, x_is_u8, n, h, w, kernel_dev, a, &semi);
 }
 
@@ -1918,21 +1944,9 @@ SSAL_API int ssal_adam_apply(float *var_dev, float *m_dev, float *v_dev, const f
     return SSAL_OK;
 }
 
-// ---- the last block: Bottleneck5_1 + Final (DESIGN.md sections 17 and 19) ----
-static TrainBlockWs train_block_carve(Bump &b, int64_t n, int h, int w, int classes)
-{
-    const int64_t G = train_block_workgroups(h, w);
-    TrainBlockWs t;
-    t.fold = b.take<float>(TB_FINAL);
-    t.dy = b.take<float>(n * h * w * 16);
-    t.part_f = b.take<float>(G * 9 * classes * 16);
-    t.part_b = b.take<float>(G * TB_ROWS * TB_TRAINED);
-    t.lpart = b.take<double>(2 * G);
-    return t;
-}
-
-// What a semi call of the block or the stage adds behind the plain workspace: the confusion replicas, then (with_raw) the
-// packed pseudo-target plane of the undistorted frames, one byte per output pixel (out_pix per image).  Plain: nothing.
+// ---- the five depths below the output layer (DESIGN.md sections 17-22 and 40) ----
+// What a semi call adds behind the plain workspace: the confusion replicas, then (with_raw) the packed pseudo-target plane of
+// the undistorted frames, one byte per output pixel (out_pix per image).  Plain: nothing.
 struct TrainSemiWs {
     unsigned long long *rep;
     uint8_t *tgt;
@@ -1953,74 +1967,311 @@ static TrainBlockSemi train_semi_args(const SemiArgs &semi, const TrainSemiWs &s
     return {semi.labelled, semi.measure, semi.threshold, sw.tgt, semi.with_raw && semi.labelled, rep, reps, semi.pseudo_pixels};
 }
 
-static int64_t train_block_bytes(int n, int h, int w, int classes, bool semi, bool with_raw)
+// what a gradient call is given besides CallArgs: the features of the training frames (x) and of the undistorted ones (x_raw, or
+// NULL), which the trunk brings about (an images entry: one after the other in the same slot of the forward workspace) or the
+// caller has, each with its pooled indices in the entry's order (an images entry gives none: the trunk leaves window codes);
+// the packed parameters; the grid cap; the dims, h and w in the depth's unit
+struct DepthIn {
+    const float *x, *x_raw;
+    const int64_t *argmax[2], *argmax_raw[2];
+    const float *params;
+    int max_workgroups, n, h, w, classes;
+};
+
+// ---- the five descriptions.  Each states: Ws and carve (the buffers of one gradient call behind `b`, in carve order; own: the
+// call brings no activation / window-code buffers of its own, where an images entry has them in the forward workspace and
+// bind points at those); kUnit (frame pixels per feature pixel and axis); kTrunk (where an images entry's frozen trunk stops:
+// the layers from there on run inside the training launches from params_dev, not from the handle's committed weights) and
+// kSlot (where its output lands in the forward workspace); kArgmax (pooled-index inputs of the features entry) and kRaw (what
+// the raw all-or-none message calls the raw pointers); kSemiPix (output pixels per feature pixel); kFits (the limit the byte
+// queries judge) and check (the entries' verdict and its messages); targets / grad (its launcher pair: the target launch runs
+// on the raw features and leaves one byte per output pixel, so the training features go through the same slots afterwards) ----
+
+// the last block: Bottleneck5_1 + Final (DESIGN.md sections 17 and 19); h, w = the dims of Bottleneck5_0's output.  Its entries
+// judge with the output layer's check and take no grid cap
+struct BlockDepth {
+    using Ws = TrainBlockWs;
+    static constexpr int kUnit = 2, kTrunk = kNumLayers - 2, kArgmax = 0, kSemiPix = 4;
+    static constexpr float *NetWorkspace::*kSlot = &NetWorkspace::a0;
+    static constexpr const char *kRaw = "";
+    static constexpr bool (*kFits)(int, int) = train_block_fits;
+
+    static Ws carve(Bump &b, int64_t n, int h, int w, int classes, bool = true)
+    {
+        const int64_t G = train_block_workgroups(h, w);
+        Ws t;
+        t.fold = b.take<float>(TB_FINAL);
+        t.dy = b.take<float>(n * h * w * 16);
+        t.part_f = b.take<float>(G * 9 * classes * 16);
+        t.part_b = b.take<float>(G * TB_ROWS * TB_TRAINED);
+        t.lpart = b.take<double>(2 * G);
+        return t;
+    }
+    static void bind(Ws &, const NetWorkspace &) {}
+    static int check(int n, int h, int w, int classes, int) { return final_grad_check(n, h, w, classes); }
+    static hipError_t targets(const DepthIn &in, const Ws &t, const TrainBlockSemi &sa, hipStream_t s)
+    {
+        return launch_train_block_targets(in.x_raw, in.n, in.h, in.w, in.classes, in.params, sa, t, s);
+    }
+    static hipError_t grad(const DepthIn &in, const CallArgs &a, const Ws &t, const TrainBlockSemi *sa)
+    {
+        return launch_train_block_grad(in.x, in.n, in.h, in.w, in.classes, in.params, a.labels, a.mask, a.weight, a.label_smoothing,
+                                       t, a.loss, a.grad, a.s, nullptr, 0, sa);
+    }
+};
+
+// the last stage: Bottleneck5_0 + the last block (DESIGN.md sections 18 and 19); h, w = the dims of Bottleneck4_2's output.  An
+// images entry has Bottleneck5_0 written to W.a0, where the forward leaves it, and Bottleneck1_0's window codes in W.code1
+struct StageDepth {
+    using Ws = TrainStageWs;
+    static constexpr int kUnit = 4, kTrunk = kNumLayers - 3, kArgmax = 1, kSemiPix = 16;
+    static constexpr float *NetWorkspace::*kSlot = &NetWorkspace::s1a;
+    static constexpr const char *kRaw = "features_raw_dev and argmax_raw_dev";
+    static constexpr bool (*kFits)(int, int) = train_stage_fits;
+
+    static Ws carve(Bump &b, int64_t n, int h, int w, int classes, bool own)
+    {
+        Ws t;
+        t.tb = BlockDepth::carve(b, n, 2 * h, 2 * w, classes);
+        t.dx = b.take<float>(n * 4 * h * w * 16);
+        t.sfold = b.take<float>(TF_FLOATS);
+        t.part_s = b.take<float>((int64_t)train_stage_workgroups(h, w, 0) * TS_TRAINED);
+        t.bad = b.take<int>(1);
+        t.a5 = own ? b.take<float>(n * 4 * h * w * 16) : nullptr;
+        t.code = own ? b.take<uint8_t>(n * h * w * 16) : nullptr;
+        return t;
+    }
+    static void bind(Ws &t, const NetWorkspace &W)
+    {
+        t.a5 = W.a0;
+        t.code = W.code1;
+    }
+    static int check(int n, int h, int w, int classes, int max_workgroups)
+    {
+        return grad_dims_check(n, h, w, classes, max_workgroups, train_stage_fits, "last-stage gradient kernels'");
+    }
+    static hipError_t targets(const DepthIn &in, const Ws &t, const TrainBlockSemi &sa, hipStream_t s)
+    {
+        return launch_train_stage_targets(in.x_raw, in.argmax_raw[0], in.n, in.h, in.w, in.classes, in.params, in.max_workgroups, t,
+                                          sa, s);
+    }
+    static hipError_t grad(const DepthIn &in, const CallArgs &a, const Ws &t, const TrainBlockSemi *sa)
+    {
+        return launch_train_stage_grad(in.x, in.argmax[0], in.n, in.h, in.w, in.classes, in.params, a.labels, a.mask, a.weight,
+                                       a.label_smoothing, in.max_workgroups, t, a.loss, a.grad, a.s, sa);
+    }
+};
+
+// the decoder tail: R regular blocks + the last stage (R = 1: Bottleneck4_2; R = 2: Bottleneck4_1 below it,
+// section 21); h, w = the dims of the lowest trained block's input (Bottleneck4_1's output; R = 2: Bottleneck4_0's).  R = 2
+// appends Bottleneck4_1's four pieces.  An images entry of R = 1 has Bottleneck4_2 written to W.s1a, where the forward leaves it;
+// one of R = 2 has a4_0 and a4_1 in the forward workspace's two quarter-resolution buffers, so its a4_2 is carved here
+template <int R>
+struct TailDepth {
+    using Ws = TrainTailWs;
+    static constexpr int kUnit = 4, kTrunk = kNumLayers - 3 - R, kArgmax = 1, kSemiPix = 16;
+    static constexpr float *NetWorkspace::*kSlot = R == 2 ? &NetWorkspace::s1a : &NetWorkspace::s1b;
+    static constexpr const char *kRaw = StageDepth::kRaw;
+    static constexpr bool (*kFits)(int, int) = train_tail_fits;
+
+    static Ws carve(Bump &b, int64_t n, int h, int w, int classes, bool own)
+    {
+        Ws t;
+        t.ts = StageDepth::carve(b, n, h, w, classes, own);
+        t.dx4 = b.take<float>(n * h * w * 64);
+        t.tfold = b.take<float>(TG_FLOATS);
+        t.part_t = b.take<float>((int64_t)train_stage_workgroups(h, w, 0) * TT_TRAINED);
+        t.a42 = own ? b.take<float>(n * h * w * 64) : nullptr;
+        t.a41 = t.dx41 = t.tfold2 = t.part_t2 = nullptr;
+        if (R == 2) {
+            t.dx41 = b.take<float>(n * h * w * 64);
+            t.tfold2 = b.take<float>(TG_FLOATS);
+            t.part_t2 = b.take<float>((int64_t)train_stage_workgroups(h, w, 0) * TT_TRAINED);
+            if (own) t.a41 = b.take<float>(n * h * w * 64);
+            else t.a42 = b.take<float>(n * h * w * 64);
+        }
+        return t;
+    }
+    static void bind(Ws &t, const NetWorkspace &W)
+    {
+        (R == 2 ? t.a41 : t.a42) = R == 2 ? W.s1b : W.s1a;
+        StageDepth::bind(t.ts, W);
+    }
+    // (the stage's verdict first: of the two "beyond the ... limit" messages the stage's leads)
+    static int check(int n, int h, int w, int classes, int max_workgroups)
+    {
+        if (int rc = StageDepth::check(n, h, w, classes, max_workgroups)) return rc;
+        if (!train_tail_fits(h, w))
+            return fail(SSAL_EINVAL, "feature map %dx%d is beyond the decoder-tail gradient kernels' limit", h, w);
+        return SSAL_OK;
+    }
+    static hipError_t targets(const DepthIn &in, const Ws &t, const TrainBlockSemi &sa, hipStream_t s)
+    {
+        return launch_train_tail_targets(in.x_raw, in.argmax_raw[0], in.n, in.h, in.w, in.classes, in.params, in.max_workgroups, t,
+                                         sa, s, R);
+    }
+    static hipError_t grad(const DepthIn &in, const CallArgs &a, const Ws &t, const TrainBlockSemi *sa)
+    {
+        return launch_train_tail_grad(in.x, in.argmax[0], in.n, in.h, in.w, in.classes, in.params, a.labels, a.mask, a.weight,
+                                      a.label_smoothing, in.max_workgroups, t, a.loss, a.grad, a.s, sa, R);
+    }
+};
+
+// the decoder: Bottleneck4_0 + the two-block tail; h, w = the dims of Bottleneck3_8's output (eighth
+// resolution).  The tail's pieces on the quarter-resolution map first, then Bottleneck4_0's.  An images entry has Bottleneck4_0
+// written to W.s1a and Bottleneck2_0's window codes in W.code2; the pooled indices are argmax2, then argmax1
+struct DecoderDepth {
+    using Ws = TrainDecoderWs;
+    static constexpr int kUnit = 8, kTrunk = kNumLayers - 6, kArgmax = 2, kSemiPix = 64;
+    static constexpr float *NetWorkspace::*kSlot = &NetWorkspace::s2a;
+    static constexpr const char *kRaw = "features_raw_dev, argmax2_raw_dev and argmax1_raw_dev";
+    static constexpr bool (*kFits)(int, int) = train_decoder_fits;
+
+    static Ws carve(Bump &b, int64_t n, int h, int w, int classes, bool own)
+    {
+        Ws t;
+        t.tt = TailDepth<2>::carve(b, n, 2 * h, 2 * w, classes, own);
+        t.dx40 = b.take<float>(n * 4 * h * w * 64);
+        t.dur = b.take<float>(n * h * w * 64);
+        t.dfold = b.take<float>(DF_FLOATS);
+        t.part_d = b.take<float>((int64_t)train_decoder_workgroups(h, w, 0) * TD_TRAINED);
+        t.bad2 = b.take<int>(1);
+        t.a40 = own ? b.take<float>(n * 4 * h * w * 64) : nullptr;
+        t.code2 = own ? b.take<uint8_t>(n * h * w * 64) : nullptr;
+        return t;
+    }
+    static void bind(Ws &t, const NetWorkspace &W)
+    {
+        t.a40 = W.s1a;
+        t.code2 = W.code2;
+        TailDepth<2>::bind(t.tt, W);
+    }
+    static int check(int n, int h, int w, int classes, int max_workgroups)
+    {
+        return grad_dims_check(n, h, w, classes, max_workgroups, train_decoder_fits, "decoder gradient kernels'");
+    }
+    static hipError_t targets(const DepthIn &in, const Ws &t, const TrainBlockSemi &sa, hipStream_t s)
+    {
+        return launch_train_decoder_targets(in.x_raw, in.argmax_raw[0], in.argmax_raw[1], in.n, in.h, in.w, in.classes, in.params,
+                                            in.max_workgroups, t, sa, s);
+    }
+    static hipError_t grad(const DepthIn &in, const CallArgs &a, const Ws &t, const TrainBlockSemi *sa)
+    {
+        return launch_train_decoder_grad(in.x, in.argmax[0], in.argmax[1], in.n, in.h, in.w, in.classes, in.params, a.labels, a.mask,
+                                         a.weight, a.label_smoothing, in.max_workgroups, t, a.loss, a.grad, a.s, sa);
+    }
+};
+
+// ---- what is done with a description D, once.  h, w: in D's unit ----
+template <typename D>
+struct DepthWs {
+    typename D::Ws t;
+    TrainSemiWs sw;
+};
+
+template <typename D>
+static DepthWs<D> depth_carve(Bump &b, int n, int h, int w, int classes, bool own, bool semi, bool with_raw)
 {
-    if (!grad_dims_ok(n, h, w, classes, train_block_fits)) return -1;
+    DepthWs<D> c;
+    c.t = D::carve(b, n, h, w, classes, own);
+    c.sw = train_semi_carve(b, n, D::kSemiPix * (int64_t)h * w, classes, semi, with_raw);
+    return c;
+}
+
+// bytes of a features entry (own) or of what an images entry puts behind the forward workspace
+template <typename D>
+static int64_t depth_bytes(int n, int h, int w, int classes, bool own, bool semi, bool with_raw)
+{
+    if (!grad_dims_ok(n, h, w, classes, D::kFits)) return -1;
     Bump b(nullptr, 0);
-    train_block_carve(b, n, h, w, classes);
-    train_semi_carve(b, n, 4 * (int64_t)h * w, classes, semi, with_raw);
+    (void)depth_carve<D>(b, n, h, w, classes, own, semi, with_raw);
     return b.off + 256;
 }
 
-static int64_t enet_train_block_bytes(const ssal_enet *net, int n, int h, int w, bool semi, bool with_raw)
+template <typename D>
+static int64_t enet_depth_bytes(const ssal_enet *net, int n, int h, int w, bool semi, bool with_raw)
 {
     if (!net_dims_ok(net, n, h, w)) return -1;
-    return behind_trunk_bytes(net, n, h, w, train_block_bytes(n, h / 2, w / 2, net->classes, semi, with_raw));
+    return behind_trunk_bytes(net, n, h, w, depth_bytes<D>(n, h / D::kUnit, w / D::kUnit, net->classes, false, semi, with_raw));
 }
 
-// b: where the call's own pieces go, need: the entry's whole workspace.  x5 / x5_raw [n,h,w,16]: Bottleneck5_0 of the training
-// / the undistorted frames, which trunk(raw) brings about (an images entry: one after the other in W.a0) or the caller has.
-// x5_raw not NULL: the target-only launch runs on it; it leaves one byte per output pixel, so the training frames can go
-// through the same slots afterwards.
-template <typename Trunk>
-static int train_block_run(Bump &b, int64_t need, Trunk trunk, const float *x5, const float *x5_raw, int n, int h, int w,
-                           int classes, const float *params_dev, const CallArgs &a, const SemiArgs *semi)
+// in.x_raw not NULL: trunk(true) brings the undistorted frames' features about and the target-only launch runs on them; then
+// trunk(false) and the gradient launch on the training frames'
+template <typename D, typename Trunk>
+static int depth_run(Trunk trunk, const DepthIn &in, const CallArgs &a, const SemiArgs *semi, const DepthWs<D> &c)
 {
-    const TrainBlockWs t = train_block_carve(b, n, h, w, classes);
-    const TrainSemiWs sw = train_semi_carve(b, n, 4 * (int64_t)h * w, classes, semi != nullptr, semi && semi->with_raw);
-    if (int rc = ws_check(need, b, a)) return rc;
-    return with_confusion(sw.rep, classes, semi ? semi->confusion : nullptr, a.s, [&](unsigned long long *rep, int reps) -> int {
+    return with_confusion(c.sw.rep, in.classes, semi ? semi->confusion : nullptr, a.s, [&](unsigned long long *rep, int reps) -> int {
         TrainBlockSemi sa = {};
-        if (semi) sa = train_semi_args(*semi, sw, rep, reps);
-        if (x5_raw) {
+        if (semi) sa = train_semi_args(*semi, c.sw, rep, reps);
+        if (in.x_raw) {
             if (int rc = trunk(true)) return rc;
-            HIP_TRY(launch_train_block_targets(x5_raw, n, h, w, classes, params_dev, sa, t, a.s));
+            HIP_TRY(D::targets(in, c.t, sa, a.s));
         }
         if (int rc = trunk(false)) return rc;
-        HIP_TRY(launch_train_block_grad(x5, n, h, w, classes, params_dev, a.labels, a.mask, a.weight, a.label_smoothing, t,
-                                        a.loss, a.grad, a.s, nullptr, 0, semi ? &sa : nullptr));
+        HIP_TRY(D::grad(in, a, c.t, semi ? &sa : nullptr));
         return SSAL_OK;
     });
 }
 
-static int train_block_grad_entry(const float *features_dev, const float *features_raw_dev, int n, int h, int w, int classes,
-                                  const float *params_dev, const CallArgs &a, const SemiArgs *semi)
+template <typename D>
+static int features_entry(const DepthIn &in, const CallArgs &a, const SemiArgs *semi)
 {
-    if (int rc = final_grad_check(n, h, w, classes)) return rc;
-    if (int rc = args_check(features_dev && params_dev, a, semi)) return rc;
+    if (int rc = D::check(in.n, in.h, in.w, in.classes, in.max_workgroups)) return rc;
+    bool inputs = in.x && in.params;
+    int raw = 0;
+    for (int i = 0; i < D::kArgmax; ++i) {
+        inputs = inputs && in.argmax[i];
+        raw += in.argmax_raw[i] != nullptr;
+    }
+    if (int rc = args_check(inputs, a, semi)) return rc;
+    if (raw != (in.x_raw ? D::kArgmax : 0)) return fail(SSAL_EINVAL, "%s are given together or not at all", D::kRaw);
     Bump b(a.ws, a.ws_bytes);
-    return train_block_run(b, train_block_bytes(n, h, w, classes, semi != nullptr, features_raw_dev != nullptr), no_trunk,
-                           features_dev, features_raw_dev, n, h, w, classes, params_dev, a, semi);
+    const DepthWs<D> c = depth_carve<D>(b, in.n, in.h, in.w, in.classes, true, semi != nullptr, semi && semi->with_raw);
+    const int64_t need = depth_bytes<D>(in.n, in.h, in.w, in.classes, true, semi != nullptr, in.x_raw != nullptr);
+    if (int rc = ws_check(need, b, a)) return rc;
+    return depth_run<D>(no_trunk, in, a, semi, c);
 }
 
-static int enet_train_block_entry(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h, int w,
-                                  const float *params_dev, const CallArgs &a, const SemiArgs *semi)
+template <typename D>
+static int images_entry(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h, int w,
+                        const float *params_dev, int max_workgroups, const CallArgs &a, const SemiArgs *semi)
 {
     int rc = check_dims(net, n, h, w);
     if (rc) return rc;
-    if ((rc = final_grad_check(n, h / 2, w / 2, net->classes))) return rc;
+    const int hu = h / D::kUnit, wu = w / D::kUnit;
+    if ((rc = D::check(n, hu, wu, net->classes, max_workgroups))) return rc;
     if ((rc = args_check(x_dev && params_dev, a, semi))) return rc;
     NetWorkspace W;
     Bump b = carve_behind_trunk(net, a, n, h, w, &W);
-    // the frozen trunk is Initial .. Bottleneck5_0 (its output lands in W.a0); Bottleneck5_1 is evaluated inside the training
-    // kernels from params_dev, not from the handle's committed weights
-    auto trunk = [&](bool of_raw) {
-        return run_trunk(net, kNumLayers - 2, of_raw ? x_raw_dev : x_dev, x_is_u8, W, n, h, w, a.s);
-    };
+    DepthWs<D> c = depth_carve<D>(b, n, hu, wu, net->classes, false, semi != nullptr, semi && semi->with_raw);
+    if ((rc = ws_check(enet_depth_bytes<D>(net, n, h, w, semi != nullptr, x_raw_dev != nullptr), b, a))) return rc;
+    D::bind(c.t, W);
+    // the frozen trunk, on the undistorted (of_raw) or the training frames, through the same slots of W
+    auto trunk = [&](bool of_raw) { return run_trunk(net, D::kTrunk, of_raw ? x_raw_dev : x_dev, x_is_u8, W, n, h, w, a.s); };
     // (the undistorted frames go through the trunk only with `labelled_dev`; the features entry goes by the raw features alone)
-    return train_block_run(b, enet_train_block_bytes(net, n, h, w, semi != nullptr, x_raw_dev != nullptr), trunk, W.a0,
-                           x_raw_dev && semi->labelled ? W.a0 : nullptr, n, h / 2, w / 2, net->classes, params_dev, a, semi);
+    const float *x = W.*D::kSlot;
+    const DepthIn in = {x, x_raw_dev && semi->labelled ? x : nullptr, {}, {}, params_dev, max_workgroups, n, hu, wu, net->classes};
+    return depth_run<D>(trunk, in, a, semi, c);
 }
+
+// byte offset of a slot of the forward workspace (into the workspace passed to forward / score / a training entry); -1 for
+// dims the net does not take
+template <typename T>
+static int64_t forward_offset(const ssal_enet *net, int n, int h, int w, T *NetWorkspace::*slot)
+{
+    if (!net_dims_ok(net, n, h, w)) return -1;
+    const NetWorkspace W = carve(net, (void *)256, ((int64_t)1 << 62), n, h, w);
+    return (const char *)(W.*slot) - (const char *)256;
+}
+
+// ... of the slot D's trunk leaves its output in: the features D's features entry takes
+template <typename D>
+static int64_t features_offset(const ssal_enet *net, int n, int h, int w)
+{
+    return forward_offset(net, n, h, w, D::kSlot);
+}
+
+// ---- the last block ----
 
 SSAL_API int64_t ssal_train_block_param_floats(int classes)
 {
@@ -2029,7 +2280,7 @@ SSAL_API int64_t ssal_train_block_param_floats(int classes)
 
 SSAL_API int64_t ssal_train_block_grad_workspace_bytes(int n, int h, int w, int classes)
 {
-    return train_block_bytes(n, h, w, classes, false, false);
+    return depth_bytes<BlockDepth>(n, h, w, classes, true, false, false);
 }
 
 SSAL_API int ssal_train_block_grad_nhwc(const float *features_dev, int n, int h, int w, int classes, const float *params_dev,
@@ -2037,22 +2288,20 @@ SSAL_API int ssal_train_block_grad_nhwc(const float *features_dev, int n, int h,
                                         float label_smoothing, double *loss_dev, float *grad_dev, void *ws_dev,
                                         int64_t ws_bytes, void *stream)
 {
-    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    return train_block_grad_entry(features_dev, nullptr, n, h, w, classes, params_dev, a, nullptr);
+    const CallArgs a = call_args(labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, stream);
+    return features_entry<BlockDepth>({features_dev, nullptr, {}, {}, params_dev, 0, n, h, w, classes}, a, nullptr);
 }
 
 SSAL_API int64_t ssal_enet_train_block_workspace_bytes(const ssal_enet *net, int n, int h, int w)
 {
-    return enet_train_block_bytes(net, n, h, w, false, false);
+    return enet_depth_bytes<BlockDepth>(net, n, h, w, false, false);
 }
 
 // byte offset (into the workspace passed to forward / score / train_block) of Bottleneck5_0's output [n,h/2,w/2,16],
 // the features ssal_train_block_grad_nhwc takes; valid until the next call.  -1 for dims the net does not take.
 SSAL_API int64_t ssal_enet_train_block_features_offset(const ssal_enet *net, int n, int h, int w)
 {
-    if (!net_dims_ok(net, n, h, w)) return -1;
-    NetWorkspace W = carve(net, (void *)256, ((int64_t)1 << 62), n, h, w);
-    return (const char *)W.a0 - (const char *)256;
+    return features_offset<BlockDepth>(net, n, h, w);
 }
 
 SSAL_API int ssal_enet_train_block_nhwc(ssal_enet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
@@ -2060,13 +2309,13 @@ SSAL_API int ssal_enet_train_block_nhwc(ssal_enet *net, const void *x_dev, int x
                                         float weight, float label_smoothing, double *loss_dev, float *grad_dev,
                                         void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    return enet_train_block_entry(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, a, nullptr);
+    const CallArgs a = call_args(labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, stream);
+    return images_entry<BlockDepth>(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, 0, a, nullptr);
 }
 
 SSAL_API int64_t ssal_train_block_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw)
 {
-    return train_block_bytes(n, h, w, classes, true, with_raw != 0);
+    return depth_bytes<BlockDepth>(n, h, w, classes, true, true, with_raw != 0);
 }
 
 SSAL_API int ssal_train_block_grad_semi_nhwc(const float *features_dev, const float *features_raw_dev, int n, int h, int w,
@@ -2076,14 +2325,14 @@ SSAL_API int ssal_train_block_grad_semi_nhwc(const float *features_dev, const fl
                                              float *grad_dev, int64_t *confusion_dev, int64_t *pseudo_pixels_dev,
                                              void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, features_raw_dev != nullptr};
-    return train_block_grad_entry(features_dev, features_raw_dev, n, h, w, classes, params_dev, a, &semi);
+    const CallArgs a = call_args(labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, stream);
+    const SemiArgs semi = semi_args(labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, features_raw_dev);
+    return features_entry<BlockDepth>({features_dev, features_raw_dev, {}, {}, params_dev, 0, n, h, w, classes}, a, &semi);
 }
 
 SSAL_API int64_t ssal_enet_train_block_semi_workspace_bytes(const ssal_enet *net, int n, int h, int w, int with_raw)
 {
-    return enet_train_block_bytes(net, n, h, w, true, with_raw != 0);
+    return enet_depth_bytes<BlockDepth>(net, n, h, w, true, with_raw != 0);
 }
 
 SSAL_API int ssal_enet_train_block_semi_nhwc(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
@@ -2093,111 +2342,12 @@ SSAL_API int ssal_enet_train_block_semi_nhwc(ssal_enet *net, const void *x_dev, 
                                              double *loss_dev, float *grad_dev, int64_t *confusion_dev,
                                              int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev != nullptr};
-    return enet_train_block_entry(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, a, &semi);
+    const CallArgs a = call_args(labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, stream);
+    const SemiArgs semi = semi_args(labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev);
+    return images_entry<BlockDepth>(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, 0, a, &semi);
 }
 
-// ---- the last stage: Bottleneck5_0 + Bottleneck5_1 + Final (DESIGN.md sections 18 and 19) ----
-// h, w = the dims of Bottleneck4_2's output; own = the call brings no a5_0 / window-code buffers of its own
-static TrainStageWs train_stage_carve(Bump &b, int64_t n, int h, int w, int classes, bool own)
-{
-    TrainStageWs t;
-    t.tb = train_block_carve(b, n, 2 * h, 2 * w, classes);
-    t.dx = b.take<float>(n * 4 * h * w * 16);
-    t.sfold = b.take<float>(TF_FLOATS);
-    t.part_s = b.take<float>((int64_t)train_stage_workgroups(h, w, 0) * TS_TRAINED);
-    t.bad = b.take<int>(1);
-    t.a5 = own ? b.take<float>(n * 4 * h * w * 16) : nullptr;
-    t.code = own ? b.take<uint8_t>(n * h * w * 16) : nullptr;
-    return t;
-}
-
-static int train_stage_check(int n, int h, int w, int classes, int max_workgroups)
-{
-    if (classes < 2 || classes > 32) return fail(SSAL_EINVAL, "classes must be in [2,32] (got %d)", classes);
-    if (n <= 0 || h <= 0 || w <= 0) return fail(SSAL_EINVAL, "bad dims n=%d h=%d w=%d", n, h, w);
-    if (max_workgroups < 0) return fail(SSAL_EINVAL, "max_workgroups must be >= 0 (got %d)", max_workgroups);
-    if (!train_stage_fits(h, w))
-        return fail(SSAL_EINVAL, "feature map %dx%d is beyond the last-stage gradient kernels' limit", h, w);
-    return SSAL_OK;
-}
-
-static int64_t train_stage_bytes(int n, int h, int w, int classes, bool own, bool semi, bool with_raw)
-{
-    if (!grad_dims_ok(n, h, w, classes, train_stage_fits)) return -1;
-    Bump b(nullptr, 0);
-    train_stage_carve(b, n, h, w, classes, own);
-    train_semi_carve(b, n, 16 * (int64_t)h * w, classes, semi, with_raw);
-    return b.off + 256;
-}
-
-static int64_t enet_train_stage_bytes(const ssal_enet *net, int n, int h, int w, bool semi, bool with_raw)
-{
-    if (!net_dims_ok(net, n, h, w)) return -1;
-    return behind_trunk_bytes(net, n, h, w, train_stage_bytes(n, h / 4, w / 4, net->classes, false, semi, with_raw));
-}
-
-// b, need, trunk and what x4_raw sets off: as for train_block_run.  x4 / x4_raw [n,h,w,64]: Bottleneck4_2 of the training /
-// the undistorted frames with their pooling indices argmax / argmax_raw; an images entry has both in W.s1a, one after the other,
-// gives no indices (trunk leaves the window codes in `code`) and has Bottleneck5_0 written to a5, where the forward leaves it.
-template <typename Trunk>
-static int train_stage_run(Bump &b, int64_t need, Trunk trunk, const float *x4, const int64_t *argmax, const float *x4_raw,
-                           const int64_t *argmax_raw, float *a5, uint8_t *code, int n, int h, int w, int classes,
-                           const float *params_dev, int max_workgroups, const CallArgs &a, const SemiArgs *semi)
-{
-    TrainStageWs t = train_stage_carve(b, n, h, w, classes, a5 == nullptr);
-    const TrainSemiWs sw = train_semi_carve(b, n, 16 * (int64_t)h * w, classes, semi != nullptr, semi && semi->with_raw);
-    if (int rc = ws_check(need, b, a)) return rc;
-    t.a5 = a5 ? a5 : t.a5;  // an images entry: both live in the forward workspace
-    t.code = a5 ? code : t.code;
-    return with_confusion(sw.rep, classes, semi ? semi->confusion : nullptr, a.s, [&](unsigned long long *rep, int reps) -> int {
-        TrainBlockSemi sa = {};
-        if (semi) sa = train_semi_args(*semi, sw, rep, reps);
-        if (x4_raw) {
-            if (int rc = trunk(true)) return rc;
-            HIP_TRY(launch_train_stage_targets(x4_raw, argmax_raw, n, h, w, classes, params_dev, max_workgroups, t, sa, a.s));
-        }
-        if (int rc = trunk(false)) return rc;
-        HIP_TRY(launch_train_stage_grad(x4, argmax, n, h, w, classes, params_dev, a.labels, a.mask, a.weight, a.label_smoothing,
-                                        max_workgroups, t, a.loss, a.grad, a.s, semi ? &sa : nullptr));
-        return SSAL_OK;
-    });
-}
-
-static int train_stage_grad_entry(const float *features_dev, const int64_t *argmax_dev, const float *features_raw_dev,
-                                  const int64_t *argmax_raw_dev, int n, int h, int w, int classes, const float *params_dev,
-                                  int max_workgroups, const CallArgs &a, const SemiArgs *semi)
-{
-    if (int rc = train_stage_check(n, h, w, classes, max_workgroups)) return rc;
-    if (int rc = args_check(features_dev && argmax_dev && params_dev, a, semi)) return rc;
-    if ((features_raw_dev == nullptr) != (argmax_raw_dev == nullptr))
-        return fail(SSAL_EINVAL, "features_raw_dev and argmax_raw_dev are given together or not at all");
-    Bump b(a.ws, a.ws_bytes);
-    return train_stage_run(b, train_stage_bytes(n, h, w, classes, true, semi != nullptr, features_raw_dev != nullptr), no_trunk,
-                           features_dev, argmax_dev, features_raw_dev, argmax_raw_dev, nullptr, nullptr, n, h, w, classes,
-                           params_dev, max_workgroups, a, semi);
-}
-
-static int enet_train_stage_entry(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h, int w,
-                                  const float *params_dev, int max_workgroups, const CallArgs &a, const SemiArgs *semi)
-{
-    int rc = check_dims(net, n, h, w);
-    if (rc) return rc;
-    if ((rc = train_stage_check(n, h / 4, w / 4, net->classes, max_workgroups))) return rc;
-    if ((rc = args_check(x_dev && params_dev, a, semi))) return rc;
-    NetWorkspace W;
-    Bump b = carve_behind_trunk(net, a, n, h, w, &W);
-    // the frozen trunk is Initial .. Bottleneck4_2 (its output lands in W.s1a, the window codes of Bottleneck1_0's pooling
-    // in W.code1); Bottleneck5_0 runs from params_dev into W.a0, where the forward leaves it
-    auto trunk = [&](bool of_raw) {
-        return run_trunk(net, kNumLayers - 3, of_raw ? x_raw_dev : x_dev, x_is_u8, W, n, h, w, a.s);
-    };
-    return train_stage_run(b, enet_train_stage_bytes(net, n, h, w, semi != nullptr, x_raw_dev != nullptr), trunk, W.s1a,
-                           nullptr, x_raw_dev && semi->labelled ? W.s1a : nullptr, nullptr, W.a0, W.code1, n, h / 4, w / 4,
-                           net->classes, params_dev, max_workgroups, a, semi);
-}
-
+// ---- the last stage ----
 SSAL_API int64_t ssal_train_stage_param_floats(int classes)
 {
     return classes < 2 || classes > 32 ? -1 : train_stage_floats(classes);
@@ -2205,7 +2355,7 @@ SSAL_API int64_t ssal_train_stage_param_floats(int classes)
 
 SSAL_API int64_t ssal_train_stage_grad_workspace_bytes(int n, int h, int w, int classes)
 {
-    return train_stage_bytes(n, h, w, classes, true, false, false);
+    return depth_bytes<StageDepth>(n, h, w, classes, true, false, false);
 }
 
 SSAL_API int ssal_train_stage_grad_nhwc(const float *features_dev, const int64_t *argmax_dev, int n, int h, int w, int classes,
@@ -2213,30 +2363,26 @@ SSAL_API int ssal_train_stage_grad_nhwc(const float *features_dev, const int64_t
                                         float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev,
                                         void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    return train_stage_grad_entry(features_dev, argmax_dev, nullptr, nullptr, n, h, w, classes, params_dev, max_workgroups, a,
-                                  nullptr);
+    const CallArgs a = call_args(labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, stream);
+    return features_entry<StageDepth>({features_dev, nullptr, {argmax_dev}, {}, params_dev, max_workgroups, n, h, w, classes}, a,
+                                      nullptr);
 }
 
 SSAL_API int64_t ssal_enet_train_stage_workspace_bytes(const ssal_enet *net, int n, int h, int w)
 {
-    return enet_train_stage_bytes(net, n, h, w, false, false);
+    return enet_depth_bytes<StageDepth>(net, n, h, w, false, false);
 }
 
 // byte offsets (into the workspace passed to forward / score / train_stage) of Bottleneck4_2's output [n,h/4,w/4,64] and of
 // the window codes [n,h/4,w/4,16] of Bottleneck1_0's pooling; valid until the next call.  -1 for dims the net does not take.
 SSAL_API int64_t ssal_enet_train_stage_features_offset(const ssal_enet *net, int n, int h, int w)
 {
-    if (!net_dims_ok(net, n, h, w)) return -1;
-    NetWorkspace W = carve(net, (void *)256, ((int64_t)1 << 62), n, h, w);
-    return (const char *)W.s1a - (const char *)256;
+    return features_offset<StageDepth>(net, n, h, w);
 }
 
 SSAL_API int64_t ssal_enet_train_stage_code_offset(const ssal_enet *net, int n, int h, int w)
 {
-    if (!net_dims_ok(net, n, h, w)) return -1;
-    NetWorkspace W = carve(net, (void *)256, ((int64_t)1 << 62), n, h, w);
-    return (const char *)W.code1 - (const char *)256;
+    return forward_offset(net, n, h, w, &NetWorkspace::code1);
 }
 
 SSAL_API int ssal_enet_train_stage_nhwc(ssal_enet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
@@ -2244,13 +2390,13 @@ SSAL_API int ssal_enet_train_stage_nhwc(ssal_enet *net, const void *x_dev, int x
                                         float weight, float label_smoothing, int max_workgroups, double *loss_dev,
                                         float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    return enet_train_stage_entry(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, max_workgroups, a, nullptr);
+    const CallArgs a = call_args(labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, stream);
+    return images_entry<StageDepth>(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, max_workgroups, a, nullptr);
 }
 
 SSAL_API int64_t ssal_train_stage_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw)
 {
-    return train_stage_bytes(n, h, w, classes, true, true, with_raw != 0);
+    return depth_bytes<StageDepth>(n, h, w, classes, true, true, with_raw != 0);
 }
 
 SSAL_API int ssal_train_stage_grad_semi_nhwc(const float *features_dev, const int64_t *argmax_dev,
@@ -2261,15 +2407,15 @@ SSAL_API int ssal_train_stage_grad_semi_nhwc(const float *features_dev, const in
                                              double *loss_dev, float *grad_dev, int64_t *confusion_dev,
                                              int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, features_raw_dev != nullptr};
-    return train_stage_grad_entry(features_dev, argmax_dev, features_raw_dev, argmax_raw_dev, n, h, w, classes, params_dev,
-                                  max_workgroups, a, &semi);
+    const CallArgs a = call_args(labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, stream);
+    const SemiArgs semi = semi_args(labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, features_raw_dev);
+    return features_entry<StageDepth>({features_dev, features_raw_dev, {argmax_dev}, {argmax_raw_dev}, params_dev, max_workgroups,
+                                       n, h, w, classes}, a, &semi);
 }
 
 SSAL_API int64_t ssal_enet_train_stage_semi_workspace_bytes(const ssal_enet *net, int n, int h, int w, int with_raw)
 {
-    return enet_train_stage_bytes(net, n, h, w, true, with_raw != 0);
+    return enet_depth_bytes<StageDepth>(net, n, h, w, true, with_raw != 0);
 }
 
 SSAL_API int ssal_enet_train_stage_semi_nhwc(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
@@ -2279,125 +2425,12 @@ SSAL_API int ssal_enet_train_stage_semi_nhwc(ssal_enet *net, const void *x_dev, 
                                              int max_workgroups, double *loss_dev, float *grad_dev, int64_t *confusion_dev,
                                              int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev != nullptr};
-    return enet_train_stage_entry(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, max_workgroups, a, &semi);
+    const CallArgs a = call_args(labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, stream);
+    const SemiArgs semi = semi_args(labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev);
+    return images_entry<StageDepth>(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, max_workgroups, a, &semi);
 }
 
-// ---- the decoder tail: R regular blocks + the last stage (R = 1: Bottleneck4_2; R = 2: Bottleneck4_1
-// below it, section 21).  One body for both depths; the entries of R = 1 pass no R and run what they ran before. ----
-// h, w = the dims of the lowest trained block's input; own = the call brings no a4_2 / a5_0 / window-code buffers of its own.
-// R = 2 appends Bottleneck4_1's four pieces; an images entry of R = 2 has a4_0 and a4_1 in the forward workspace's two
-// quarter-resolution buffers, so its a4_2 is carved here.
-static TrainTailWs train_tail_carve(Bump &b, int64_t n, int h, int w, int classes, bool own, int R = 1)
-{
-    TrainTailWs t;
-    t.ts = train_stage_carve(b, n, h, w, classes, own);
-    t.dx4 = b.take<float>(n * h * w * 64);
-    t.tfold = b.take<float>(TG_FLOATS);
-    t.part_t = b.take<float>((int64_t)train_stage_workgroups(h, w, 0) * TT_TRAINED);
-    t.a42 = own ? b.take<float>(n * h * w * 64) : nullptr;
-    t.a41 = t.dx41 = t.tfold2 = t.part_t2 = nullptr;
-    if (R == 2) {
-        t.dx41 = b.take<float>(n * h * w * 64);
-        t.tfold2 = b.take<float>(TG_FLOATS);
-        t.part_t2 = b.take<float>((int64_t)train_stage_workgroups(h, w, 0) * TT_TRAINED);
-        if (own) t.a41 = b.take<float>(n * h * w * 64);
-        else t.a42 = b.take<float>(n * h * w * 64);
-    }
-    return t;
-}
-
-static int train_tail_check(int n, int h, int w, int classes, int max_workgroups)
-{
-    if (int rc = train_stage_check(n, h, w, classes, max_workgroups)) return rc;
-    if (!train_tail_fits(h, w))
-        return fail(SSAL_EINVAL, "feature map %dx%d is beyond the decoder-tail gradient kernels' limit", h, w);
-    return SSAL_OK;
-}
-
-static int64_t train_tail_bytes(int n, int h, int w, int classes, bool own, bool semi, bool with_raw, int R = 1)
-{
-    if (!grad_dims_ok(n, h, w, classes, train_tail_fits)) return -1;
-    Bump b(nullptr, 0);
-    train_tail_carve(b, n, h, w, classes, own, R);
-    train_semi_carve(b, n, 16 * (int64_t)h * w, classes, semi, with_raw);
-    return b.off + 256;
-}
-
-static int64_t enet_train_tail_bytes(const ssal_enet *net, int n, int h, int w, bool semi, bool with_raw, int R = 1)
-{
-    if (!net_dims_ok(net, n, h, w)) return -1;
-    return behind_trunk_bytes(net, n, h, w, train_tail_bytes(n, h / 4, w / 4, net->classes, false, semi, with_raw, R));
-}
-
-// b, need, trunk and what x41_raw sets off: as for train_stage_run.  x41 / x41_raw [n,h,w,64]: the input of the lowest trained
-// block (Bottleneck4_1's output; R = 2: Bottleneck4_0's) of the training / the undistorted frames; an images entry has both in
-// one buffer of the forward workspace, one after the other, and has Bottleneck4_2 written to a42 (R = 2: Bottleneck4_1 to a42,
-// Bottleneck4_2 to the call's own buffer) and Bottleneck5_0 to a5, where the forward leaves them.
-template <typename Trunk>
-static int train_tail_run(Bump &b, int64_t need, Trunk trunk, const float *x41, const int64_t *argmax, const float *x41_raw,
-                          const int64_t *argmax_raw, float *a42, float *a5, uint8_t *code, int n, int h, int w, int classes,
-                          const float *params_dev, int max_workgroups, const CallArgs &a, const SemiArgs *semi, int R = 1)
-{
-    TrainTailWs t = train_tail_carve(b, n, h, w, classes, a42 == nullptr, R);
-    const TrainSemiWs sw = train_semi_carve(b, n, 16 * (int64_t)h * w, classes, semi != nullptr, semi && semi->with_raw);
-    if (int rc = ws_check(need, b, a)) return rc;
-    if (a42) {  // an images entry: the three live in the forward workspace
-        (R == 2 ? t.a41 : t.a42) = a42;
-        t.ts.a5 = a5;
-        t.ts.code = code;
-    }
-    return with_confusion(sw.rep, classes, semi ? semi->confusion : nullptr, a.s, [&](unsigned long long *rep, int reps) -> int {
-        TrainBlockSemi sa = {};
-        if (semi) sa = train_semi_args(*semi, sw, rep, reps);
-        if (x41_raw) {
-            if (int rc = trunk(true)) return rc;
-            HIP_TRY(launch_train_tail_targets(x41_raw, argmax_raw, n, h, w, classes, params_dev, max_workgroups, t, sa, a.s, R));
-        }
-        if (int rc = trunk(false)) return rc;
-        HIP_TRY(launch_train_tail_grad(x41, argmax, n, h, w, classes, params_dev, a.labels, a.mask, a.weight, a.label_smoothing,
-                                       max_workgroups, t, a.loss, a.grad, a.s, semi ? &sa : nullptr, R));
-        return SSAL_OK;
-    });
-}
-
-static int train_tail_grad_entry(const float *features_dev, const int64_t *argmax_dev, const float *features_raw_dev,
-                                 const int64_t *argmax_raw_dev, int n, int h, int w, int classes, const float *params_dev,
-                                 int max_workgroups, const CallArgs &a, const SemiArgs *semi, int R = 1)
-{
-    if (int rc = train_tail_check(n, h, w, classes, max_workgroups)) return rc;
-    if (int rc = args_check(features_dev && argmax_dev && params_dev, a, semi)) return rc;
-    if ((features_raw_dev == nullptr) != (argmax_raw_dev == nullptr))
-        return fail(SSAL_EINVAL, "features_raw_dev and argmax_raw_dev are given together or not at all");
-    Bump b(a.ws, a.ws_bytes);
-    return train_tail_run(b, train_tail_bytes(n, h, w, classes, true, semi != nullptr, features_raw_dev != nullptr, R), no_trunk,
-                          features_dev, argmax_dev, features_raw_dev, argmax_raw_dev, nullptr, nullptr, nullptr, n, h, w,
-                          classes, params_dev, max_workgroups, a, semi, R);
-}
-
-static int enet_train_tail_entry(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h, int w,
-                                 const float *params_dev, int max_workgroups, const CallArgs &a, const SemiArgs *semi,
-                                 int R = 1)
-{
-    int rc = check_dims(net, n, h, w);
-    if (rc) return rc;
-    if ((rc = train_tail_check(n, h / 4, w / 4, net->classes, max_workgroups))) return rc;
-    if ((rc = args_check(x_dev && params_dev, a, semi))) return rc;
-    NetWorkspace W;
-    Bump b = carve_behind_trunk(net, a, n, h, w, &W);
-    // the frozen trunk is Initial .. Bottleneck4_1 (its output lands in W.s1b, the window codes of Bottleneck1_0's pooling
-    // in W.code1); Bottleneck4_2 runs from params_dev into W.s1a and Bottleneck5_0 into W.a0, where the forward leaves them.
-    // R = 2: the trunk ends one layer earlier, at Bottleneck4_0 in W.s1a, and Bottleneck4_1 runs from params_dev into W.s1b
-    float *x41 = R == 2 ? W.s1a : W.s1b, *next = R == 2 ? W.s1b : W.s1a;
-    auto trunk = [&](bool of_raw) {
-        return run_trunk(net, kNumLayers - 3 - R, of_raw ? x_raw_dev : x_dev, x_is_u8, W, n, h, w, a.s);
-    };
-    return train_tail_run(b, enet_train_tail_bytes(net, n, h, w, semi != nullptr, x_raw_dev != nullptr, R), trunk, x41, nullptr,
-                          x_raw_dev && semi->labelled ? x41 : nullptr, nullptr, next, W.a0, W.code1, n, h / 4, w / 4,
-                          net->classes, params_dev, max_workgroups, a, semi, R);
-}
-
+// ---- the decoder tail (R = 1) ----
 SSAL_API int64_t ssal_train_tail_param_floats(int classes)
 {
     return classes < 2 || classes > 32 ? -1 : train_tail_floats(classes);
@@ -2405,7 +2438,7 @@ SSAL_API int64_t ssal_train_tail_param_floats(int classes)
 
 SSAL_API int64_t ssal_train_tail_grad_workspace_bytes(int n, int h, int w, int classes)
 {
-    return train_tail_bytes(n, h, w, classes, true, false, false);
+    return depth_bytes<TailDepth<1>>(n, h, w, classes, true, false, false);
 }
 
 SSAL_API int ssal_train_tail_grad_nhwc(const float *features_dev, const int64_t *argmax_dev, int n, int h, int w, int classes,
@@ -2413,23 +2446,21 @@ SSAL_API int ssal_train_tail_grad_nhwc(const float *features_dev, const int64_t 
                                        float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev,
                                        void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    return train_tail_grad_entry(features_dev, argmax_dev, nullptr, nullptr, n, h, w, classes, params_dev, max_workgroups, a,
-                                 nullptr);
+    const CallArgs a = call_args(labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, stream);
+    return features_entry<TailDepth<1>>({features_dev, nullptr, {argmax_dev}, {}, params_dev, max_workgroups, n, h, w, classes}, a,
+                                        nullptr);
 }
 
 SSAL_API int64_t ssal_enet_train_tail_workspace_bytes(const ssal_enet *net, int n, int h, int w)
 {
-    return enet_train_tail_bytes(net, n, h, w, false, false);
+    return enet_depth_bytes<TailDepth<1>>(net, n, h, w, false, false);
 }
 
 // byte offset (into the workspace passed to forward / score / train_tail) of Bottleneck4_1's output [n,h/4,w/4,64]; valid
 // until the next call.  -1 for dims the net does not take.
 SSAL_API int64_t ssal_enet_train_tail_features_offset(const ssal_enet *net, int n, int h, int w)
 {
-    if (!net_dims_ok(net, n, h, w)) return -1;
-    NetWorkspace W = carve(net, (void *)256, ((int64_t)1 << 62), n, h, w);
-    return (const char *)W.s1b - (const char *)256;
+    return features_offset<TailDepth<1>>(net, n, h, w);
 }
 
 SSAL_API int ssal_enet_train_tail_nhwc(ssal_enet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
@@ -2437,13 +2468,13 @@ SSAL_API int ssal_enet_train_tail_nhwc(ssal_enet *net, const void *x_dev, int x_
                                        float weight, float label_smoothing, int max_workgroups, double *loss_dev,
                                        float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    return enet_train_tail_entry(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, max_workgroups, a, nullptr);
+    const CallArgs a = call_args(labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, stream);
+    return images_entry<TailDepth<1>>(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, max_workgroups, a, nullptr);
 }
 
 SSAL_API int64_t ssal_train_tail_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw)
 {
-    return train_tail_bytes(n, h, w, classes, true, true, with_raw != 0);
+    return depth_bytes<TailDepth<1>>(n, h, w, classes, true, true, with_raw != 0);
 }
 
 SSAL_API int ssal_train_tail_grad_semi_nhwc(const float *features_dev, const int64_t *argmax_dev,
@@ -2454,15 +2485,15 @@ SSAL_API int ssal_train_tail_grad_semi_nhwc(const float *features_dev, const int
                                             double *loss_dev, float *grad_dev, int64_t *confusion_dev,
                                             int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, features_raw_dev != nullptr};
-    return train_tail_grad_entry(features_dev, argmax_dev, features_raw_dev, argmax_raw_dev, n, h, w, classes, params_dev,
-                                 max_workgroups, a, &semi);
+    const CallArgs a = call_args(labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, stream);
+    const SemiArgs semi = semi_args(labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, features_raw_dev);
+    return features_entry<TailDepth<1>>({features_dev, features_raw_dev, {argmax_dev}, {argmax_raw_dev}, params_dev,
+                                         max_workgroups, n, h, w, classes}, a, &semi);
 }
 
 SSAL_API int64_t ssal_enet_train_tail_semi_workspace_bytes(const ssal_enet *net, int n, int h, int w, int with_raw)
 {
-    return enet_train_tail_bytes(net, n, h, w, true, with_raw != 0);
+    return enet_depth_bytes<TailDepth<1>>(net, n, h, w, true, with_raw != 0);
 }
 
 SSAL_API int ssal_enet_train_tail_semi_nhwc(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
@@ -2472,9 +2503,9 @@ SSAL_API int ssal_enet_train_tail_semi_nhwc(ssal_enet *net, const void *x_dev, c
                                             int max_workgroups, double *loss_dev, float *grad_dev, int64_t *confusion_dev,
                                             int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev != nullptr};
-    return enet_train_tail_entry(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, max_workgroups, a, &semi);
+    const CallArgs a = call_args(labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, stream);
+    const SemiArgs semi = semi_args(labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev);
+    return images_entry<TailDepth<1>>(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, max_workgroups, a, &semi);
 }
 
 // ---- decoder-tail training, two regular blocks: Bottleneck4_1 + the tail.  The tail's entries with R = 2.
@@ -2485,7 +2516,7 @@ SSAL_API int64_t ssal_train_tail2_param_floats(int classes)
 
 SSAL_API int64_t ssal_train_tail2_grad_workspace_bytes(int n, int h, int w, int classes)
 {
-    return train_tail_bytes(n, h, w, classes, true, false, false, 2);
+    return depth_bytes<TailDepth<2>>(n, h, w, classes, true, false, false);
 }
 
 SSAL_API int ssal_train_tail2_grad_nhwc(const float *features_dev, const int64_t *argmax_dev, int n, int h, int w, int classes,
@@ -2493,14 +2524,14 @@ SSAL_API int ssal_train_tail2_grad_nhwc(const float *features_dev, const int64_t
                                         float label_smoothing, int max_workgroups, double *loss_dev, float *grad_dev,
                                         void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    return train_tail_grad_entry(features_dev, argmax_dev, nullptr, nullptr, n, h, w, classes, params_dev, max_workgroups, a,
-                                 nullptr, 2);
+    const CallArgs a = call_args(labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, stream);
+    return features_entry<TailDepth<2>>({features_dev, nullptr, {argmax_dev}, {}, params_dev, max_workgroups, n, h, w, classes}, a,
+                                        nullptr);
 }
 
 SSAL_API int64_t ssal_enet_train_tail2_workspace_bytes(const ssal_enet *net, int n, int h, int w)
 {
-    return enet_train_tail_bytes(net, n, h, w, false, false, 2);
+    return enet_depth_bytes<TailDepth<2>>(net, n, h, w, false, false);
 }
 
 // byte offset (into the workspace passed to train_tail2) of Bottleneck4_0's output [n,h/4,w/4,64]: where
@@ -2508,9 +2539,7 @@ SSAL_API int64_t ssal_enet_train_tail2_workspace_bytes(const ssal_enet *net, int
 // the next call.  -1 for dims the net does not take.
 SSAL_API int64_t ssal_enet_train_tail2_features_offset(const ssal_enet *net, int n, int h, int w)
 {
-    if (!net_dims_ok(net, n, h, w)) return -1;
-    NetWorkspace W = carve(net, (void *)256, ((int64_t)1 << 62), n, h, w);
-    return (const char *)W.s1a - (const char *)256;
+    return features_offset<TailDepth<2>>(net, n, h, w);
 }
 
 SSAL_API int ssal_enet_train_tail2_nhwc(ssal_enet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
@@ -2518,13 +2547,13 @@ SSAL_API int ssal_enet_train_tail2_nhwc(ssal_enet *net, const void *x_dev, int x
                                         float weight, float label_smoothing, int max_workgroups, double *loss_dev,
                                         float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    return enet_train_tail_entry(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, max_workgroups, a, nullptr, 2);
+    const CallArgs a = call_args(labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, stream);
+    return images_entry<TailDepth<2>>(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, max_workgroups, a, nullptr);
 }
 
 SSAL_API int64_t ssal_train_tail2_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw)
 {
-    return train_tail_bytes(n, h, w, classes, true, true, with_raw != 0, 2);
+    return depth_bytes<TailDepth<2>>(n, h, w, classes, true, true, with_raw != 0);
 }
 
 SSAL_API int ssal_train_tail2_grad_semi_nhwc(const float *features_dev, const int64_t *argmax_dev,
@@ -2535,15 +2564,15 @@ SSAL_API int ssal_train_tail2_grad_semi_nhwc(const float *features_dev, const in
                                              double *loss_dev, float *grad_dev, int64_t *confusion_dev,
                                              int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, features_raw_dev != nullptr};
-    return train_tail_grad_entry(features_dev, argmax_dev, features_raw_dev, argmax_raw_dev, n, h, w, classes, params_dev,
-                                 max_workgroups, a, &semi, 2);
+    const CallArgs a = call_args(labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, stream);
+    const SemiArgs semi = semi_args(labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, features_raw_dev);
+    return features_entry<TailDepth<2>>({features_dev, features_raw_dev, {argmax_dev}, {argmax_raw_dev}, params_dev,
+                                         max_workgroups, n, h, w, classes}, a, &semi);
 }
 
 SSAL_API int64_t ssal_enet_train_tail2_semi_workspace_bytes(const ssal_enet *net, int n, int h, int w, int with_raw)
 {
-    return enet_train_tail_bytes(net, n, h, w, true, with_raw != 0, 2);
+    return enet_depth_bytes<TailDepth<2>>(net, n, h, w, true, with_raw != 0);
 }
 
 SSAL_API int ssal_enet_train_tail2_semi_nhwc(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
@@ -2553,124 +2582,12 @@ SSAL_API int ssal_enet_train_tail2_semi_nhwc(ssal_enet *net, const void *x_dev, 
                                              int max_workgroups, double *loss_dev, float *grad_dev, int64_t *confusion_dev,
                                              int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev != nullptr};
-    return enet_train_tail_entry(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, max_workgroups, a, &semi, 2);
+    const CallArgs a = call_args(labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, stream);
+    const SemiArgs semi = semi_args(labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev);
+    return images_entry<TailDepth<2>>(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, max_workgroups, a, &semi);
 }
 
-// ---- decoder training: Bottleneck4_0 + the two-block tail.  One body, as for the other depths. ----
-// h, w = the dims of Bottleneck3_8's output (eighth resolution); own = the call brings no a4_0 / a4_1 / a5_0 / window-code
-// buffers of its own.  The tail's pieces on the quarter-resolution map first (an images entry's a4_2 is carved there, as section
-// 21 does), then Bottleneck4_0's.
-static TrainDecoderWs train_decoder_carve(Bump &b, int64_t n, int h, int w, int classes, bool own)
-{
-    TrainDecoderWs t;
-    t.tt = train_tail_carve(b, n, 2 * h, 2 * w, classes, own, 2);
-    t.dx40 = b.take<float>(n * 4 * h * w * 64);
-    t.dur = b.take<float>(n * h * w * 64);
-    t.dfold = b.take<float>(DF_FLOATS);
-    t.part_d = b.take<float>((int64_t)train_decoder_workgroups(h, w, 0) * TD_TRAINED);
-    t.bad2 = b.take<int>(1);
-    t.a40 = own ? b.take<float>(n * 4 * h * w * 64) : nullptr;
-    t.code2 = own ? b.take<uint8_t>(n * h * w * 64) : nullptr;
-    return t;
-}
-
-static int train_decoder_check(int n, int h, int w, int classes, int max_workgroups)
-{
-    if (classes < 2 || classes > 32) return fail(SSAL_EINVAL, "classes must be in [2,32] (got %d)", classes);
-    if (n <= 0 || h <= 0 || w <= 0) return fail(SSAL_EINVAL, "bad dims n=%d h=%d w=%d", n, h, w);
-    if (max_workgroups < 0) return fail(SSAL_EINVAL, "max_workgroups must be >= 0 (got %d)", max_workgroups);
-    if (!train_decoder_fits(h, w))
-        return fail(SSAL_EINVAL, "feature map %dx%d is beyond the decoder gradient kernels' limit", h, w);
-    return SSAL_OK;
-}
-
-static int64_t train_decoder_bytes(int n, int h, int w, int classes, bool own, bool semi, bool with_raw)
-{
-    if (!grad_dims_ok(n, h, w, classes, train_decoder_fits)) return -1;
-    Bump b(nullptr, 0);
-    train_decoder_carve(b, n, h, w, classes, own);
-    train_semi_carve(b, n, 64 * (int64_t)h * w, classes, semi, with_raw);
-    return b.off + 256;
-}
-
-static int64_t enet_train_decoder_bytes(const ssal_enet *net, int n, int h, int w, bool semi, bool with_raw)
-{
-    if (!net_dims_ok(net, n, h, w)) return -1;
-    return behind_trunk_bytes(net, n, h, w, train_decoder_bytes(n, h / 8, w / 8, net->classes, false, semi, with_raw));
-}
-
-// b, need, trunk and what x38_raw sets off: as for train_stage_run.  x38 / x38_raw [n,h,w,128]: Bottleneck3_8 of the training /
-// the undistorted frames with their pooling indices; an images entry has both in one buffer of the forward workspace, one after
-// the other, gives no indices (trunk leaves the window codes in code2 / code1) and has Bottleneck4_0 written to a40,
-// Bottleneck4_1 to a41 and Bottleneck5_0 to a5, where the forward leaves them.
-template <typename Trunk>
-static int train_decoder_run(Bump &b, int64_t need, Trunk trunk, const float *x38, const int64_t *argmax2, const int64_t *argmax1,
-                             const float *x38_raw, const int64_t *argmax2_raw, const int64_t *argmax1_raw, float *a40, float *a41,
-                             float *a5, uint8_t *code2, uint8_t *code1, int n, int h, int w, int classes, const float *params_dev,
-                             int max_workgroups, const CallArgs &a, const SemiArgs *semi)
-{
-    TrainDecoderWs t = train_decoder_carve(b, n, h, w, classes, a40 == nullptr);
-    const TrainSemiWs sw = train_semi_carve(b, n, 64 * (int64_t)h * w, classes, semi != nullptr, semi && semi->with_raw);
-    if (int rc = ws_check(need, b, a)) return rc;
-    if (a40) {  // an images entry: the five live in the forward workspace
-        t.a40 = a40;
-        t.code2 = code2;
-        t.tt.a41 = a41;
-        t.tt.ts.a5 = a5;
-        t.tt.ts.code = code1;
-    }
-    return with_confusion(sw.rep, classes, semi ? semi->confusion : nullptr, a.s, [&](unsigned long long *rep, int reps) -> int {
-        TrainBlockSemi sa = {};
-        if (semi) sa = train_semi_args(*semi, sw, rep, reps);
-        if (x38_raw) {
-            if (int rc = trunk(true)) return rc;
-            HIP_TRY(launch_train_decoder_targets(x38_raw, argmax2_raw, argmax1_raw, n, h, w, classes, params_dev, max_workgroups,
-                                                 t, sa, a.s));
-        }
-        if (int rc = trunk(false)) return rc;
-        HIP_TRY(launch_train_decoder_grad(x38, argmax2, argmax1, n, h, w, classes, params_dev, a.labels, a.mask, a.weight,
-                                          a.label_smoothing, max_workgroups, t, a.loss, a.grad, a.s, semi ? &sa : nullptr));
-        return SSAL_OK;
-    });
-}
-
-static int train_decoder_grad_entry(const float *features_dev, const int64_t *argmax2_dev, const int64_t *argmax1_dev,
-                                    const float *features_raw_dev, const int64_t *argmax2_raw_dev,
-                                    const int64_t *argmax1_raw_dev, int n, int h, int w, int classes, const float *params_dev,
-                                    int max_workgroups, const CallArgs &a, const SemiArgs *semi)
-{
-    if (int rc = train_decoder_check(n, h, w, classes, max_workgroups)) return rc;
-    if (int rc = args_check(features_dev && argmax2_dev && argmax1_dev && params_dev, a, semi)) return rc;
-    if ((features_raw_dev == nullptr) != (argmax2_raw_dev == nullptr) || (features_raw_dev == nullptr) != (argmax1_raw_dev == nullptr))
-        return fail(SSAL_EINVAL, "features_raw_dev, argmax2_raw_dev and argmax1_raw_dev are given together or not at all");
-    Bump b(a.ws, a.ws_bytes);
-    return train_decoder_run(b, train_decoder_bytes(n, h, w, classes, true, semi != nullptr, features_raw_dev != nullptr), no_trunk,
-                             features_dev, argmax2_dev, argmax1_dev, features_raw_dev, argmax2_raw_dev, argmax1_raw_dev, nullptr,
-                             nullptr, nullptr, nullptr, nullptr, n, h, w, classes, params_dev, max_workgroups, a, semi);
-}
-
-static int enet_train_decoder_entry(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n, int h, int w,
-                                    const float *params_dev, int max_workgroups, const CallArgs &a, const SemiArgs *semi)
-{
-    int rc = check_dims(net, n, h, w);
-    if (rc) return rc;
-    if ((rc = train_decoder_check(n, h / 8, w / 8, net->classes, max_workgroups))) return rc;
-    if ((rc = args_check(x_dev && params_dev, a, semi))) return rc;
-    NetWorkspace W;
-    Bump b = carve_behind_trunk(net, a, n, h, w, &W);
-    // the frozen trunk is Initial .. Bottleneck3_8 (its output lands in W.s2a, the window codes of Bottleneck2_0's and
-    // Bottleneck1_0's pooling in W.code2 / W.code1); Bottleneck4_0 runs from params_dev into W.s1a, Bottleneck4_1 into W.s1b and
-    // Bottleneck5_0 into W.a0, where the forward leaves them
-    auto trunk = [&](bool of_raw) {
-        return run_trunk(net, kNumLayers - 6, of_raw ? x_raw_dev : x_dev, x_is_u8, W, n, h, w, a.s);
-    };
-    return train_decoder_run(b, enet_train_decoder_bytes(net, n, h, w, semi != nullptr, x_raw_dev != nullptr), trunk, W.s2a,
-                             nullptr, nullptr, x_raw_dev && semi->labelled ? W.s2a : nullptr, nullptr, nullptr, W.s1a, W.s1b, W.a0,
-                             W.code2, W.code1, n, h / 8, w / 8, net->classes, params_dev, max_workgroups, a, semi);
-}
-
+// ---- the decoder ----
 SSAL_API int64_t ssal_train_decoder_param_floats(int classes)
 {
     return classes < 2 || classes > 32 ? -1 : train_decoder_floats(classes);
@@ -2678,7 +2595,7 @@ SSAL_API int64_t ssal_train_decoder_param_floats(int classes)
 
 SSAL_API int64_t ssal_train_decoder_grad_workspace_bytes(int n, int h, int w, int classes)
 {
-    return train_decoder_bytes(n, h, w, classes, true, false, false);
+    return depth_bytes<DecoderDepth>(n, h, w, classes, true, false, false);
 }
 
 SSAL_API int ssal_train_decoder_grad_nhwc(const float *features_dev, const int64_t *argmax2_dev, const int64_t *argmax1_dev, int n,
@@ -2686,14 +2603,14 @@ SSAL_API int ssal_train_decoder_grad_nhwc(const float *features_dev, const int64
                                           const float *mask_dev, float weight, float label_smoothing, int max_workgroups,
                                           double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    return train_decoder_grad_entry(features_dev, argmax2_dev, argmax1_dev, nullptr, nullptr, nullptr, n, h, w, classes,
-                                    params_dev, max_workgroups, a, nullptr);
+    const CallArgs a = call_args(labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, stream);
+    return features_entry<DecoderDepth>({features_dev, nullptr, {argmax2_dev, argmax1_dev}, {}, params_dev, max_workgroups, n, h, w,
+                                         classes}, a, nullptr);
 }
 
 SSAL_API int64_t ssal_enet_train_decoder_workspace_bytes(const ssal_enet *net, int n, int h, int w)
 {
-    return enet_train_decoder_bytes(net, n, h, w, false, false);
+    return enet_depth_bytes<DecoderDepth>(net, n, h, w, false, false);
 }
 
 // byte offset (into the workspace passed to train_decoder) of Bottleneck3_8's output [n,h/8,w/8,128]: where
@@ -2701,9 +2618,7 @@ SSAL_API int64_t ssal_enet_train_decoder_workspace_bytes(const ssal_enet *net, i
 // dims the net does not take.
 SSAL_API int64_t ssal_enet_train_decoder_features_offset(const ssal_enet *net, int n, int h, int w)
 {
-    if (!net_dims_ok(net, n, h, w)) return -1;
-    NetWorkspace W = carve(net, (void *)256, ((int64_t)1 << 62), n, h, w);
-    return (const char *)W.s2a - (const char *)256;
+    return features_offset<DecoderDepth>(net, n, h, w);
 }
 
 SSAL_API int ssal_enet_train_decoder_nhwc(ssal_enet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
@@ -2711,13 +2626,13 @@ SSAL_API int ssal_enet_train_decoder_nhwc(ssal_enet *net, const void *x_dev, int
                                           float weight, float label_smoothing, int max_workgroups, double *loss_dev,
                                           float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    return enet_train_decoder_entry(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, max_workgroups, a, nullptr);
+    const CallArgs a = call_args(labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, stream);
+    return images_entry<DecoderDepth>(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, max_workgroups, a, nullptr);
 }
 
 SSAL_API int64_t ssal_train_decoder_grad_semi_workspace_bytes(int n, int h, int w, int classes, int with_raw)
 {
-    return train_decoder_bytes(n, h, w, classes, true, true, with_raw != 0);
+    return depth_bytes<DecoderDepth>(n, h, w, classes, true, true, with_raw != 0);
 }
 
 SSAL_API int ssal_train_decoder_grad_semi_nhwc(const float *features_dev, const int64_t *argmax2_dev, const int64_t *argmax1_dev,
@@ -2729,15 +2644,15 @@ SSAL_API int ssal_train_decoder_grad_semi_nhwc(const float *features_dev, const 
                                                int64_t *confusion_dev, int64_t *pseudo_pixels_dev, void *ws_dev,
                                                int64_t ws_bytes, void *stream)
 {
-    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, features_raw_dev != nullptr};
-    return train_decoder_grad_entry(features_dev, argmax2_dev, argmax1_dev, features_raw_dev, argmax2_raw_dev, argmax1_raw_dev, n,
-                                    h, w, classes, params_dev, max_workgroups, a, &semi);
+    const CallArgs a = call_args(labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, stream);
+    const SemiArgs semi = semi_args(labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, features_raw_dev);
+    return features_entry<DecoderDepth>({features_dev, features_raw_dev, {argmax2_dev, argmax1_dev},
+                                         {argmax2_raw_dev, argmax1_raw_dev}, params_dev, max_workgroups, n, h, w, classes}, a, &semi);
 }
 
 SSAL_API int64_t ssal_enet_train_decoder_semi_workspace_bytes(const ssal_enet *net, int n, int h, int w, int with_raw)
 {
-    return enet_train_decoder_bytes(net, n, h, w, true, with_raw != 0);
+    return enet_depth_bytes<DecoderDepth>(net, n, h, w, true, with_raw != 0);
 }
 
 SSAL_API int ssal_enet_train_decoder_semi_nhwc(ssal_enet *net, const void *x_dev, const void *x_raw_dev, int x_is_u8, int n,
@@ -2747,7 +2662,7 @@ SSAL_API int ssal_enet_train_decoder_semi_nhwc(ssal_enet *net, const void *x_dev
                                                int max_workgroups, double *loss_dev, float *grad_dev, int64_t *confusion_dev,
                                                int64_t *pseudo_pixels_dev, void *ws_dev, int64_t ws_bytes, void *stream)
 {
-    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
-    const SemiArgs semi = {labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev != nullptr};
-    return enet_train_decoder_entry(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, max_workgroups, a, &semi);
+    const CallArgs a = call_args(labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, stream);
+    const SemiArgs semi = semi_args(labelled_dev, measure, threshold, confusion_dev, pseudo_pixels_dev, x_raw_dev);
+    return images_entry<DecoderDepth>(net, x_dev, x_raw_dev, x_is_u8, n, h, w, params_dev, max_workgroups, a, &semi);
 }

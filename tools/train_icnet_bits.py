@@ -301,9 +301,12 @@ def compare(path_a, path_b):
     return 1 if bad or not total else 0
 
 
-def main():
+def main(default_out=os.path.join(ROOT, "profiles", "r27_train_icnet_bits.json"), parts=None, cases=len(CASES)):
+    """``parts``: the (digests, workspace_bytes, refused) functions of a sibling tool (tools/train_enet_bits.py) and ``cases`` its
+    case count, else this file's"""
+    digests, workspace_bytes, refused = parts or (globals()[name] for name in ("digests", "workspace_bytes", "refused"))
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r27_train_icnet_bits.json"))
+    ap.add_argument("--out", default=default_out)
     ap.add_argument("--results", metavar="JSON", help="also write every result's own digest (a file of format 1, large): two "
                     "such files compare result by result, which names the tensor where a call's digest differs")
     ap.add_argument("--compare", nargs=2, metavar="JSON", help="compare two result files instead of running")
@@ -317,7 +320,7 @@ def main():
         with open(a.results, "w") as f:
             json.dump({"format": 1, "sha256": results}, f, indent=1, sort_keys=True)
     with open(a.out, "w") as f:
-        json.dump(dict(out, format=FORMAT, cases=len(CASES), results=len(results)), f, indent=1, sort_keys=True)
+        json.dump(dict(out, format=FORMAT, cases=cases, results=len(results)), f, indent=1, sort_keys=True)
     print("wrote %s: %s" % (a.out, ", ".join("%d %s" % (len(out[s]), s) for s in SECTIONS)))
 
 
