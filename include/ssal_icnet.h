@@ -241,6 +241,41 @@ int ssal_icnet_train_pyramid_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u
 /* ssal_icnet_update_fusion for the seventeen variables: only the six trained layers are re-laid-out, folded and uploaded */
 int ssal_icnet_update_pyramid(ssal_icnet *net, const float *params_host, void *stream);
 
+/* ---- Training through the pyramid pooling: conv5_3 = relu(BN(1 x 1 conv, 256 -> 1024, of conv5_3_3x3) +
+ * conv5_2), the increase layer of the backbone's last bottleneck, the parameter-free pyramid pooling over it (conv5_3_sum), then
+ * the whole pyramid head as above, over everything below conv5_3_3x3 and conv5_2 and the two other frozen branches ----
+ * The twenty trained variables travel PACKED, in this order: conv5_3_1x1_increase.kernel [1,1,256,1024] | .gamma [1024] | .beta
+ * [1024] | the seventeen of the pyramid entries in their order (264192 floats, then theirs); params_dev and grad_dev have that
+ * layout.  stats_dev [2 * 1024 + 2 * 256 + 8 * 128] = the increase layer's mean | variance | the rows of the pyramid entries;
+ * batch-norm as there.  One call computes, for conv5_3_3x3 [n,h,w,256] and conv5_2 [n,h,w,1024] (1/32 resolution; conv5_2 is the
+ * bottleneck's identity shortcut), conv3_1 [n,2h,2w,256], conv3_sub1 [n,4h,4w,64], labels uint8 and mask fp32 [n,32h,32w]:
+ * conv5_3 and conv5_3_sum by the forward path's own launches on params_dev, the pyramid head as ssal_icnet_pyramid_grad_nhwc
+ * does, the loss -> loss_dev [1] float64, and the gradient of all twenty variables -> grad_dev (without the regulariser).
+ * Nothing below the four inputs gets a gradient.  The loss and the last seventeen gradients are the bits
+ * ssal_icnet_pyramid_grad_nhwc gives on the same conv5_3_sum.  Determinism, statuses and the order of the checks as
+ * ssal_icnet_pyramid_grad_nhwc's; the size query returns -1 beyond the cascade entries' limit.  max_workgroups (0: no limit)
+ * caps the FIRST grid index of every launch, as there; besides the two launches named there, two launches of this depth have
+ * further indices that it does not cap: the data gradient through conv5_4_k1 runs 8 x that many workgroups (the eight slabs of
+ * 128 of its 1024 input channels) and the weight gradient of the increase layer 16 x that many (2 x 8 slabs of its 256 x 1024
+ * output) -- max_workgroups = 1 is 8 and 16 workgroups. */
+int64_t ssal_icnet_pool_grad_workspace_bytes(int n, int h, int w, int classes);
+int ssal_icnet_pool_grad_nhwc(const float *conv5_3_3x3_dev, const float *conv5_2_dev, const float *conv3_1_dev,
+                              const float *conv3_sub1_dev, int n, int h, int w, int classes, const float *params_dev,
+                              const uint8_t *labels_dev, const float *mask_dev, float weight, float label_smoothing,
+                              const float *stats_dev, int max_workgroups, double *loss_dev, float *grad_dev, void *ws_dev,
+                              int64_t ws_bytes, void *stream);
+/* the same from frames x_dev [n,h,w,c_in] (fp32, or uint8 when x_is_u8 != 0): the frozen trunk until conv5_3_3x3, conv5_2, conv3_1
+ * and conv3_sub1 are written -- its low-resolution schedule ends inside conv5_3, behind its 3 x 3: the increase layer, the
+ * pyramid pooling and conv5_4_k1 are not launched -- then the tail above; labels / mask [n,h,w].  After the call the endpoints
+ * from conv5_3 on are those of params_dev. */
+int64_t ssal_icnet_train_pool_workspace_bytes(const ssal_icnet *net, int n, int h, int w);
+int ssal_icnet_train_pool_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w, const uint8_t *labels_dev,
+                               const float *mask_dev, const float *params_dev, float weight, float label_smoothing,
+                               const float *stats_dev, int max_workgroups, double *loss_dev, float *grad_dev, void *ws_dev,
+                               int64_t ws_bytes, void *stream);
+/* ssal_icnet_update_fusion for the twenty variables: only the seven trained layers are re-laid-out, folded and uploaded */
+int ssal_icnet_update_pool(ssal_icnet *net, const float *params_host, void *stream);
+
 /* ---- The semi-supervised step of the fusion and the cascade trainer (active_learning.py:226-275, 339-342; DESIGN.md
  * section 30) ----
  * The four gradient calls above with the targets built inside the head's gradient kernel: labelled_dev, measure, threshold,

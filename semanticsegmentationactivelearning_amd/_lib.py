@@ -208,6 +208,13 @@ PROTOTYPES = {
     "ssal_icnet_train_pyramid_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
     "ssal_icnet_train_pyramid_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
     "ssal_icnet_update_pyramid": (_i, [_vp, _vp, _vp]),
+    # ---- training of ICNet through its pyramid pooling: conv5_3's increase layer and the pyramid head ----
+    "ssal_icnet_pool_grad_workspace_bytes": (_i64, [_i, _i, _i, _i]),
+    "ssal_icnet_pool_grad_nhwc": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64,
+                                       _vp]),
+    "ssal_icnet_train_pool_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
+    "ssal_icnet_train_pool_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_icnet_update_pool": (_i, [_vp, _vp, _vp]),
     # ---- the semi-supervised step of the two (include/ssal_icnet.h) ----
     "ssal_icnet_fusion_grad_semi_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
     "ssal_icnet_fusion_grad_semi_nhwc": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _vp, _i,

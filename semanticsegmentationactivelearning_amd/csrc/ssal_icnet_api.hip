@@ -14,6 +14,7 @@
 #include "ssal_train_icnet_cascade.h"
 #include "ssal_train_icnet_fusion.h"
 #include "ssal_train_icnet_highres.h"
+#include "ssal_train_icnet_pool.h"
 #include "ssal_train_icnet_pyramid.h"
 
 #include <math.h>
@@ -259,12 +260,17 @@ struct Grp {
 // (the high-resolution trainer runs conv1_sub1 .. conv3_sub1 on the weights it trains)
 // k1 = false (with cascade = false): the low-resolution schedule ends after the launch that writes conv5_3_sum -- conv5_4_k1 is
 // neither launched nor written (the pyramid trainer runs it on the weights it trains); the high-resolution branch still runs
+// increase = false (implies k1 = false): the low-resolution schedule ends inside conv5_3 -- conv5_1 and conv5_2 run as ever, conv5_3's
+// 1x1_reduce and 3x3 run as the separate run_conv launches they always are at 1024 channels (fused_bneck() is the 128-channel
+// family) and write conv5_3_1x1_reduce and conv5_3_3x3; its increase layer, launch_ppm and conv5_4_k1 are neither launched nor
+// written (the pooling trainer runs them on the weights it trains); the high-resolution branch still runs
 // arith: SSAL_ARITH_BF16X3 hands the mode to every run_conv (launch_igemm keeps what has no split kernel exact) and runs the
 // fused blocks on ENet's bf16x3 regular-block kernel; the training, evaluate and regions entries pass the default
 hipError_t run_trunk(const ssal_icnet *net, std::vector<Grp> &grp, bool x_is_u8, int h, int w, bool fused,
                      std::set<std::string> *written = nullptr, bool head = true, bool fusion = true, bool cascade = true,
-                     bool highres = true, int arith = SSAL_ARITH_F32, bool k1 = true)
+                     bool highres = true, int arith = SSAL_ARITH_F32, bool k1 = true, bool increase = true)
 {
+    if (!increase) k1 = false;  // a schedule that ends inside conv5_3 writes no conv5_3_sum for conv5_4_k1 to read
     const bool dry = written != nullptr;
 #define OUT(name) do { if (dry) written->insert(name); } while (0)
 #define EACH(expr)                                     \
@@ -345,11 +351,13 @@ hipError_t run_trunk(const ssal_icnet *net, std::vector<Grp> &grp, bool x_is_u8,
             EACH(run_conv(net, nm + "_1x1_proj", q.A(cur), q.n, ch, cw, nullptr, false, false, q.A(nm + "_1x1_proj"), q.s, arith));
             shortcut = nm + "_1x1_proj";
         }
+        const bool stop = !increase && i == kNumBnecks - 1;  // conv5_3 of a schedule that ends in front of its increase layer
         OUT(nm + "_1x1_reduce");
         OUT(nm + "_3x3");
-        OUT(nm);
+        if (!stop) OUT(nm);
         EACH(run_conv(net, nm + "_1x1_reduce", q.A(cur), q.n, ch, cw, nullptr, true, false, q.A(nm + "_1x1_reduce"), q.s, arith));
         EACH(run_conv(net, nm + "_3x3", q.A(nm + "_1x1_reduce"), q.n, oh, ow, nullptr, true, false, q.A(nm + "_3x3"), q.s, arith));
+        if (stop) break;
         if (dual) {
             const ConvDev &ci_ = net->convs.at(nm + "_1x1_increase"), &cp = net->convs.at(nm + "_1x1_proj");
             EACH(launch_igemm_dual(q.A(nm + "_3x3"), q.n, oh, ow, ci_.spec.cin, ci_.w, ci_.spec.cout, ci_.scale, ci_.shift,
@@ -362,9 +370,9 @@ hipError_t run_trunk(const ssal_icnet *net, std::vector<Grp> &grp, bool x_is_u8,
         cw = ow;
     }
     // pyramid pooling + conv5_4_k1
-    OUT("conv5_3_sum");
+    if (increase) OUT("conv5_3_sum");
     if (k1) OUT("conv5_4_k1");
-    EACH(launch_ppm(q.A(cur), q.n, ch, cw, 1024, q.W.pooled, q.A("conv5_3_sum"), q.s));
+    if (increase) EACH(launch_ppm(q.A(cur), q.n, ch, cw, 1024, q.W.pooled, q.A("conv5_3_sum"), q.s));
     if (k1) EACH(run_conv(net, "conv5_4_k1", q.A("conv5_3_sum"), q.n, ch, cw, nullptr, true, false, q.A("conv5_4_k1"), q.s, arith));
     // ---- high-resolution branch (section 3) ----
     if (!highres) return hipSuccess;
@@ -864,7 +872,7 @@ IcnetHeadSemi semi_of_grad(const SemiArgs &semi, const uint8_t *tgt, unsigned lo
 // endpoints) or the caller has; the packed variables and the frozen moving statistics (the head has none); the grid cap; the
 // dims, h and w in the depth's unit; and, where the frame itself is the last input, its type and channel count
 struct DepthIn {
-    const void *f[3], *raw[3];
+    const void *f[4], *raw[4];
     const float *params, *stats;
     int max_workgroups, n, h, w, classes;
     bool x_is_u8 = false;
@@ -885,7 +893,7 @@ const float *F(const void *p) { return static_cast<const float *>(p); }
 struct HeadDepth {
     using Ws = IcnetHeadWs;
     static constexpr int kUnit = 8, kLevel = 0;
-    static constexpr bool kK1 = true;
+    static constexpr bool kK1 = true, kIncrease = true;
     static constexpr bool kStats = false, kFrame = false, kImagesQueryFits = false;
     static constexpr const char *kNoun = "head gradient kernel's", *kEndpoints[] = {"sub12_sum"};
 
@@ -917,7 +925,7 @@ struct HeadDepth {
 struct FusionDepth {
     using Ws = IcnetFusionWs;
     static constexpr int kUnit = 16, kLevel = 1;
-    static constexpr bool kK1 = true;
+    static constexpr bool kK1 = true, kIncrease = true;
     static constexpr bool kStats = true, kFrame = false, kImagesQueryFits = false;
     static constexpr const char *kNoun = "fusion gradient kernels'", *kEndpoints[] = {"sub24_sum", "conv3_sub1"};
 
@@ -963,7 +971,7 @@ struct FusionDepth {
 struct CascadeDepth {
     using Ws = IcnetCascadeWs;
     static constexpr int kUnit = 32, kLevel = 2;
-    static constexpr bool kK1 = true;
+    static constexpr bool kK1 = true, kIncrease = true;
     static constexpr bool kStats = true, kFrame = false, kImagesQueryFits = false;
     static constexpr const char *kNoun = "cascade gradient kernels'", *kEndpoints[] = {"conv5_4_k1", "conv3_1", "conv3_sub1"};
 
@@ -1009,7 +1017,7 @@ struct CascadeDepth {
 struct HighresDepth {
     using Ws = IcnetHighresWs;
     static constexpr int kUnit = 32, kLevel = 3;
-    static constexpr bool kK1 = true;
+    static constexpr bool kK1 = true, kIncrease = true;
     static constexpr bool kStats = true, kFrame = true, kImagesQueryFits = true;
     static constexpr const char *kNoun = "high-resolution gradient kernels'", *kEndpoints[] = {"conv5_4_k1", "conv3_1"};
 
@@ -1060,7 +1068,7 @@ struct HighresDepth {
 struct PyramidDepth {
     using Ws = IcnetPyramidWs;
     static constexpr int kUnit = 32, kLevel = 2;
-    static constexpr bool kK1 = false;
+    static constexpr bool kK1 = false, kIncrease = true;
     static constexpr bool kStats = true, kFrame = false, kImagesQueryFits = false;
     static constexpr const char *kNoun = "pyramid gradient kernels'", *kEndpoints[] = {"conv5_3_sum", "conv3_1", "conv3_sub1"};
 
@@ -1092,6 +1100,57 @@ struct PyramidDepth {
     {
         return launch_icnet_pyramid_grad(F(in.f[0]), F(in.f[1]), F(in.f[2]), in.n, in.h, in.w, in.classes, in.params, in.stats,
                                          a.labels, a.mask, a.weight, a.label_smoothing, in.max_workgroups, t, a.loss, a.grad, a.s);
+    }
+};
+
+// through the pyramid pooling (kernels: ssal_train_icnet_pool.hip): conv5_3_3x3 [n,h32,w32,256], conv5_2
+// [n,h32,w32,1024] (the identity shortcut), conv3_1 and conv3_sub1.  Contains the pyramid depth (head < fusion < cascade <
+// pyramid < pooling).  The trunk of an images entry stops where the pyramid depth's does, and its low-resolution schedule ends
+// inside conv5_3, behind its 3 x 3 (kIncrease = false); the increase layer, the pyramid pooling, conv5_4_k1, the two blocks and
+// the head write the endpoints from conv5_3 on.  The semi-supervised entries are not built yet: there is no target launch.
+struct PoolDepth {
+    using Ws = IcnetPoolWs;
+    static constexpr int kUnit = 32, kLevel = 2;
+    static constexpr bool kK1 = false, kIncrease = false;
+    static constexpr bool kStats = true, kFrame = false, kImagesQueryFits = false;
+    static constexpr const char *kNoun = "pooling gradient kernels'",
+                                *kEndpoints[] = {"conv5_3_3x3", "conv5_2", "conv3_1", "conv3_sub1"};
+
+    static Ws carve(Bump &b, int64_t n, int h32, int w32, int classes, bool own_acts)
+    {
+        Ws t;
+        const int64_t act = n * h32 * (int64_t)w32 * PO_CO;
+        t.wt = b.take<float>(PO_G);
+        t.rows = b.take<float>(2 * PO_CO);
+        t.c53 = own_acts ? b.take<float>(act) : nullptr;
+        t.sum = own_acts ? b.take<float>(act) : nullptr;
+        t.pooled = own_acts ? b.take<float>(ppm_scratch_floats((int)n, h32, PO_CO)) : nullptr;
+        t.dsum = b.take<float>(act);
+        t.cols = b.take<float>(n * h32 * (int64_t)PO_CSLOTS * PO_CO);
+        t.gb = b.take<float>(n * (int64_t)PO_SLOTS * PO_CO);
+        t.g53 = b.take<float>(act);
+        t.part = b.take<float>((int64_t)PY_MAX_WG * PO_PART);  // (sized for the default grid: max_workgroups only lowers it)
+        t.fold = b.take<float>(PO_PART);
+        t.pyramid = PyramidDepth::carve(b, n, h32, w32, classes, own_acts);
+        return t;
+    }
+    static void bind(Ws &t, const IcWorkspace &W)
+    {
+        t.c53 = W.act.at("conv5_3");
+        t.sum = W.act.at("conv5_3_sum");
+        t.pooled = W.pooled;
+        PyramidDepth::bind(t.pyramid, W);
+    }
+    static bool fits(int n, int h32, int w32) { return icnet_pool_fits(h32, w32) && PyramidDepth::fits(n, h32, w32); }
+    static hipError_t targets(const DepthIn &, const Ws &, const IcnetHeadSemi &, uint8_t *, hipStream_t)
+    {
+        return hipErrorNotSupported;  // (no entry hands this depth a SemiArgs)
+    }
+    static hipError_t grad(const DepthIn &in, const CallArgs &a, const Ws &t, const IcnetHeadSemi *)
+    {
+        return launch_icnet_pool_grad(F(in.f[0]), F(in.f[1]), F(in.f[2]), F(in.f[3]), in.n, in.h, in.w, in.classes, in.params,
+                                      in.stats, a.labels, a.mask, a.weight, a.label_smoothing, in.max_workgroups, t, a.loss, a.grad,
+                                      a.s);
     }
 };
 
@@ -1194,13 +1253,14 @@ int images_entry(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int 
     if constexpr (D::kFrame) in.f[i] = x_dev, in.raw[i] = x_raw_dev;
     // the frozen trunk, on the undistorted (of_raw) or the training frames, through the same slots of W.  It ends in front of the
     // layers being trained: run_trunk without the head, and from level 1 / 2 / 3 on without the last fusion stage / the first
-    // one / the high-resolution branch; without conv5_4_k1 where the depth trains it (kK1)
+    // one / the high-resolution branch; without conv5_4_k1 where the depth trains it (kK1), and from conv5_3's increase layer on
+    // where it trains that (kIncrease)
     hipStream_t s = a.s;
     auto trunk = [=, &W](bool of_raw) -> int {
         std::vector<Grp> one(1);
         one[0] = {W, of_raw ? x_raw_dev : x_dev, n, s};
         HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false, D::kLevel < 1, D::kLevel < 2, D::kLevel < 3,
-                          SSAL_ARITH_F32, D::kK1));
+                          SSAL_ARITH_F32, D::kK1, D::kIncrease));
         return SSAL_OK;
     };
     return depth_run<D>(trunk, in, a, semi, c);
@@ -1327,6 +1387,13 @@ HostUpdates pyramid_tensors(const float *p, int K)
 {
     return then({{"conv5_4_k1.kernel", p + PY_K, PY_G}, {"conv5_4_k1.gamma", p + PY_G, PY_CO}, {"conv5_4_k1.beta", p + PY_B, PY_CO}},
                 cascade_tensors(p + PY_CASCADE, K));
+}
+
+HostUpdates pool_tensors(const float *p, int K)
+{
+    return then({{"conv5_3_1x1_increase.kernel", p + PO_K, PO_G}, {"conv5_3_1x1_increase.gamma", p + PO_G, PO_CO},
+                 {"conv5_3_1x1_increase.beta", p + PO_B, PO_CO}},
+                pyramid_tensors(p + PO_PYRAMID, K));
 }
 
 }  // namespace
@@ -1587,6 +1654,45 @@ SSAL_API int ssal_icnet_update_pyramid(ssal_icnet *net, const float *params_host
     if (!net || !params_host) return fail(SSAL_EINVAL, "NULL argument");
     return update_packed(net, pyramid_tensors(params_host, net->classes),
                          {"conv5_4_k1", "conv_sub4", "conv3_1_sub2_proj", "conv_sub2", "conv3_sub1_proj", "conv6_cls"}, stream);
+}
+
+// ---- through the pyramid pooling: conv5_3's increase layer and the whole pyramid head ----
+SSAL_API int64_t ssal_icnet_pool_grad_workspace_bytes(int n, int h, int w, int classes)
+{
+    return features_query<PoolDepth>(n, h, w, classes, false, false);
+}
+
+SSAL_API int ssal_icnet_pool_grad_nhwc(const float *conv5_3_3x3_dev, const float *conv5_2_dev, const float *conv3_1_dev,
+                                       const float *conv3_sub1_dev, int n, int h, int w, int classes, const float *params_dev,
+                                       const uint8_t *labels_dev, const float *mask_dev, float weight, float label_smoothing,
+                                       const float *stats_dev, int max_workgroups, double *loss_dev, float *grad_dev, void *ws_dev,
+                                       int64_t ws_bytes, void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return features_entry<PoolDepth>({{conv5_3_3x3_dev, conv5_2_dev, conv3_1_dev, conv3_sub1_dev}, {}, params_dev, stats_dev,
+                                      max_workgroups, n, h, w, classes}, a, nullptr);
+}
+
+SSAL_API int64_t ssal_icnet_train_pool_workspace_bytes(const ssal_icnet *net, int n, int h, int w)
+{
+    return images_query<PoolDepth>(net, n, h, w, false, false);
+}
+
+SSAL_API int ssal_icnet_train_pool_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                                        const uint8_t *labels_dev, const float *mask_dev, const float *params_dev, float weight,
+                                        float label_smoothing, const float *stats_dev, int max_workgroups, double *loss_dev,
+                                        float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return images_entry<PoolDepth>(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, stats_dev, max_workgroups, a, nullptr);
+}
+
+SSAL_API int ssal_icnet_update_pool(ssal_icnet *net, const float *params_host, void *stream)
+{
+    if (!net || !params_host) return fail(SSAL_EINVAL, "NULL argument");
+    return update_packed(net, pool_tensors(params_host, net->classes),
+                         {"conv5_3_1x1_increase", "conv5_4_k1", "conv_sub4", "conv3_1_sub2_proj", "conv_sub2", "conv3_sub1_proj",
+                          "conv6_cls"}, stream);
 }
 
 // ---- the high-resolution branch down to the image ----

@@ -45,4 +45,13 @@ hipError_t launch_icnet_pyramid_grad(const float *c53, const float *c31, const f
                                      float weight, float label_smoothing, int max_workgroups, const IcnetPyramidWs &ws,
                                      double *loss, float *grad, hipStream_t s);
 
+// k_icnet_pyramid_wgrad, its finish and its gamma kernel at 256 x 1024, for the layer below the pyramid pooling (DESIGN.md
+// section 41; the profile's k_icnet_pool_wgrad / _finish / _gamma): x [pixels, 256], g [pixels, 1024] (un-normalised, behind the
+// layer's ReLU, without its batch-norm scale), scale [1] = 1 / sum(mask), sl [1024] the layer's batch-norm scale, K [256][1024],
+// mean / var [1024] -> part [PY_MAX_WG][257 * 1024], fold [257 * 1024], gK [256][1024], gG, gB [1024].  Grid (G, 2, 8):
+// max_workgroups lowers G only, 16 G workgroups run.
+hipError_t launch_icnet_wgrad_256x1024(const float *x, const float *g, long pixels, int max_workgroups, const float *scale,
+                                       const float *sl, const float *K, const float *mean, const float *var, float *part,
+                                       float *fold, float *gK, float *gG, float *gB, hipStream_t s);
+
 }  // namespace ssal

@@ -44,10 +44,14 @@ __global__ __launch_bounds__(256) void k_icnet_pyramid_pack(const float *__restr
 // 16 steps of two pixels each: lane (r = lane & 31, h = lane >> 5) feeds x[pixel 2 s + h][32 w + r] and g[pixel 2 s + h][32 j + r].
 // One accumulator so adds the products of its group's pixels in ascending order.  The y = 0 workgroups also add the rows of g
 // (threads 0 .. 127, one co each, pixels ascending): dBeta's partial.
+// CIN x CO: the layer (1024 x 256: conv5_4_k1, the kernel as it always was, grid (G, 8, 2); 256 x 1024: conv5_3's increase
+// layer, DESIGN.md section 41, grid (G, 2, 8)); PART = (CIN + 1) CO floats per partial
 constexpr int PW_LD = 160;  // 2 pixels = 320 floats: the lane halves (pixel 2 s, 2 s + 1) fall on the two bank halves
+template <int CIN, int CO>
 __global__ __launch_bounds__(256) void k_icnet_pyramid_wgrad(const float *__restrict__ x, const float *__restrict__ g,
                                                              long pixels, float *__restrict__ part)
 {
+    constexpr int PART = (CIN + 1) * CO;
     __shared__ __attribute__((aligned(16))) float As[PY_PT * PW_LD];
     __shared__ __attribute__((aligned(16))) float Bs[PY_PT * PW_LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
@@ -68,8 +72,8 @@ __global__ __launch_bounds__(256) void k_icnet_pyramid_wgrad(const float *__rest
             const long p = p0 + pl;
             float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a;
             if (p < pixels) {
-                a = reinterpret_cast<const float4 *>(x + p * PY_CIN + ci0)[q];
-                b = reinterpret_cast<const float4 *>(g + p * PY_CO + co0)[q];
+                a = reinterpret_cast<const float4 *>(x + p * CIN + ci0)[q];
+                b = reinterpret_cast<const float4 *>(g + p * CO + co0)[q];
             }
             *reinterpret_cast<float4 *>(As + pl * PW_LD + 4 * q) = a;
             *reinterpret_cast<float4 *>(Bs + pl * PW_LD + 4 * q) = b;
@@ -86,43 +90,46 @@ __global__ __launch_bounds__(256) void k_icnet_pyramid_wgrad(const float *__rest
         if (ones)
             for (int p = 0; p < PY_PT; ++p) gsum += Bs[p * PW_LD + tid];
     }
-    float *pw = part + (long)blockIdx.x * PY_PART;
+    float *pw = part + (long)blockIdx.x * PART;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int row = (i & 3) + 8 * (i >> 2) + 4 * hh;
-            pw[(ci0 + 32 * wave + row) * PY_CO + co0 + 32 * j + r] = acc[j][i];
+            pw[(ci0 + 32 * wave + row) * CO + co0 + 32 * j + r] = acc[j][i];
         }
-    if (ones) pw[PY_CIN * PY_CO + co0 + tid] = gsum;
+    if (ones) pw[CIN * CO + co0 + tid] = gsum;
 }
 
 // The one-layer 1 x 1 form of k_icnet_block_finish (ssal_train_icnet_common.h): raw[o] = sum over split-K groups b = 0 .. G - 1
 // of part[b][o], fp32, in that order -> fold[o] ([1024 + 1][256]); dK = (raw scale) s[co], dBeta = raw[1024][co] scale; scale:
 // the one the fusion trainer's finish took from the head kernel's lpart
+template <int CIN, int CO>
 __global__ __launch_bounds__(256) void k_icnet_pyramid_finish(const float *__restrict__ part, int G,
                                                               const float *__restrict__ scale_p, const float *__restrict__ sl,
                                                               float *__restrict__ fold, float *__restrict__ gK,
                                                               float *__restrict__ gB)
 {
+    constexpr int PART = (CIN + 1) * CO;
     const int o = blockIdx.x * 256 + threadIdx.x;
-    if (o >= PY_PART) return;
+    if (o >= PART) return;
     const float scale = scale_p[0];
     float acc = 0.0f;
-    for (int gi = 0; gi < G; ++gi) acc += part[(long)gi * PY_PART + o];
+    for (int gi = 0; gi < G; ++gi) acc += part[(long)gi * PART + o];
     fold[o] = acc;
-    const int co = o & (PY_CO - 1);
-    if (o < PY_CIN * PY_CO) gK[o] = (acc * scale) * sl[co];
+    const int co = o & (CO - 1);
+    if (o < CIN * CO) gK[o] = (acc * scale) * sl[co];
     else gB[co] = acc * scale;
 }
 
-// The one-layer 1 x 1 form of k_icnet_block_gamma: its 1 x 1 branch (icnet_gamma_tap alone).  One workgroup of 256 threads (co).
+// The one-layer 1 x 1 form of k_icnet_block_gamma: its 1 x 1 branch (icnet_gamma_tap alone).  CO / 256 workgroups of 256 threads (co).
+template <int CIN, int CO>
 __global__ __launch_bounds__(256) void k_icnet_pyramid_gamma(const float *__restrict__ fold, const float *__restrict__ scale_p,
                                                              const float *__restrict__ K, const float *__restrict__ mean,
                                                              const float *__restrict__ var, float *__restrict__ gG)
 {
-    const int co = threadIdx.x;
-    gG[co] = icnet_dgamma(icnet_gamma_tap(K, fold, PY_CIN, PY_CO, co), mean[co], var[co], fold[PY_CIN * PY_CO + co], scale_p[0]);
+    const int co = (CO > 256 ? (int)blockIdx.x * 256 : 0) + (int)threadIdx.x;
+    gG[co] = icnet_dgamma(icnet_gamma_tap(K, fold, CIN, CO, co), mean[co], var[co], fold[CIN * CO + co], scale_p[0]);
 }
 
 hipError_t launch_icnet_pyramid_grad(const float *c53, const float *c31, const float *c3, int N, int h32, int w32, int K,
@@ -156,19 +163,45 @@ hipError_t launch_icnet_pyramid_grad(const float *c53, const float *c31, const f
     const int G = icnet_grid(icnet_cdiv(pixels, PY_PT), PY_MAX_WG, max_workgroups);
     {
         ProfScope prof("k_icnet_pyramid_wgrad", 2.0 * pix32 * PY_PART, 4.0 * pix32 * (PY_CIN + PY_CO) + 4.0 * G * PY_PART, s);
-        hipLaunchKernelGGL(k_icnet_pyramid_wgrad, dim3(G, PY_CIN / 128, PY_CO / 128), dim3(256), 0, s, c53, ws.g32, pixels,
-                           ws.part);
+        hipLaunchKernelGGL((k_icnet_pyramid_wgrad<PY_CIN, PY_CO>), dim3(G, PY_CIN / 128, PY_CO / 128), dim3(256), 0, s, c53, ws.g32,
+                           pixels, ws.part);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     {
         ProfScope prof("k_icnet_pyramid_finish", (double)G * PY_PART, 4.0 * (G + 2.0) * PY_PART, s);
-        hipLaunchKernelGGL(k_icnet_pyramid_finish, dim3(icnet_cdiv(PY_PART, 256)), dim3(256), 0, s, ws.part, G, scale, ws.rows,
-                           ws.fold, grad + PY_K, grad + PY_B);
+        hipLaunchKernelGGL((k_icnet_pyramid_finish<PY_CIN, PY_CO>), dim3(icnet_cdiv(PY_PART, 256)), dim3(256), 0, s, ws.part, G, scale,
+                           ws.rows, ws.fold, grad + PY_K, grad + PY_B);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     ProfScope prof("k_icnet_pyramid_gamma", 2.0 * PY_G, 8.0 * PY_PART, s);
-    hipLaunchKernelGGL(k_icnet_pyramid_gamma, dim3(1), dim3(PY_CO), 0, s, ws.fold, scale, params + PY_K, stats, stats + PY_CO,
-                       grad + PY_G);
+    hipLaunchKernelGGL((k_icnet_pyramid_gamma<PY_CIN, PY_CO>), dim3(PY_CO / 256), dim3(256), 0, s, ws.fold, scale, params + PY_K, stats,
+                       stats + PY_CO, grad + PY_G);
+    return hipGetLastError();
+}
+
+// The three kernels at 256 x 1024 (ssal_train_icnet_pyramid.h): the weight gradient of conv5_3's increase layer, its fold and
+// finish, its dGamma
+hipError_t launch_icnet_wgrad_256x1024(const float *x, const float *g, long pixels, int max_workgroups, const float *scale,
+                                       const float *sl, const float *K, const float *mean, const float *var, float *part,
+                                       float *fold, float *gK, float *gG, float *gB, hipStream_t s)
+{
+    constexpr int CIN = 256, CO = 1024, PART = (CIN + 1) * CO;
+    if (pixels < 1 || max_workgroups < 0) return hipErrorInvalidValue;
+    hipError_t e;
+    const int G = icnet_grid(icnet_cdiv(pixels, PY_PT), PY_MAX_WG, max_workgroups);
+    {
+        ProfScope prof("k_icnet_pool_wgrad", 2.0 * (double)pixels * PART, 4.0 * (double)pixels * (CIN + CO) + 4.0 * G * PART, s);
+        hipLaunchKernelGGL((k_icnet_pyramid_wgrad<CIN, CO>), dim3(G, CIN / 128, CO / 128), dim3(256), 0, s, x, g, pixels, part);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    {
+        ProfScope prof("k_icnet_pool_finish", (double)G * PART, 4.0 * (G + 2.0) * PART, s);
+        hipLaunchKernelGGL((k_icnet_pyramid_finish<CIN, CO>), dim3(icnet_cdiv(PART, 256)), dim3(256), 0, s, part, G, scale, sl, fold,
+                           gK, gB);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    ProfScope prof("k_icnet_pool_gamma", 2.0 * CIN * CO, 8.0 * PART, s);
+    hipLaunchKernelGGL((k_icnet_pyramid_gamma<CIN, CO>), dim3(CO / 256), dim3(256), 0, s, fold, scale, K, mean, var, gG);
     return hipGetLastError();
 }
 

@@ -1802,6 +1802,77 @@ class ICNetPyramidTrainer(ICNetCascadeTrainer):
                                       return_pseudo_pixels=return_pseudo_pixels)
 
 
+# ---- ICNet through its pyramid pooling: conv5_3's increase layer under the pyramid head -----------------
+_POOL_LAYER = "conv5_3_1x1_increase"
+_POOL_VARS = ((_POOL_LAYER, "kernel", True), (_POOL_LAYER, "gamma", False), (_POOL_LAYER, "beta", False)) + _PYRAMID_VARS
+# rows of mixed widths (1024, 1024, then the pyramid trainer's), concatenated unpadded
+_POOL_STATS = ((_POOL_LAYER, "mean"), (_POOL_LAYER, "variance")) + _PYRAMID_STATS
+
+
+class ICNetPoolingTrainer(ICNetPyramidTrainer):
+    """Adam on ``conv5_3_1x1_increase`` -- the 1 x 1 convolution (256 -> 1024) + batch-norm that, with the identity shortcut
+    ``conv5_2`` and a ReLU, closes the backbone's last bottleneck ``conv5_3`` (ICNET_SPEC section 2) -- through the
+    parameter-free pyramid pooling ``conv5_3_sum`` above it, and the pyramid head above that: everything
+    ``ICNetPyramidTrainer`` trains.  Frozen (``training=False``): everything up to and including ``conv5_3_3x3``
+    [N, H/32, W/32, 256] and ``conv5_2`` [N, H/32, W/32, 1024], ``conv3_1`` [N, H/16, W/16, 256] and ``conv3_sub1``
+    [N, H/8, W/8, 64]; nothing below them gets a gradient.  Batch-norm, hyper-parameters, Adam and the refusals are the
+    parent's; the ``l1_l2`` regulariser goes to the seven kernels only.
+
+    The 20 variables travel as one packed float32 vector in the order of ``variable_names``: the increase layer's three,
+    then the parent's seventeen in the parent's order.  The semi-supervised keywords are refused."""
+
+    _C_FEATURES = ("ssal_icnet_pool_grad", None)
+    _C_IMAGES = ("ssal_icnet_train_pool", None)
+    _CHANNELS, _UP = 256, 32
+    _VARS, _STATS, _C_UPDATE = _POOL_VARS, _POOL_STATS, "ssal_icnet_update_pool"
+    variable_names = ["%s.%s" % (layer, attr) for layer, attr, _ in _POOL_VARS]
+
+    _SEMI_NOUN = "ICNet's pooling trainer"
+    _FEATURE_NAMES = ("conv5_3_3x3", "conv5_2", "conv3_1", "conv3_sub1")
+
+    def _check_features(self, conv5_3_3x3, conv5_2, conv3_1, conv3_sub1, labels, mask, max_workgroups):
+        mw = self._check_call(conv5_3_3x3, 32, labels, mask, max_workgroups, 256)
+        n, h, w, _ = tuple(np.shape(conv5_3_3x3))
+        for name, t, want in (("conv5_2", conv5_2, (n, h, w, 1024)), ("conv3_1", conv3_1, (n, 2 * h, 2 * w, 256)),
+                              ("conv3_sub1", conv3_sub1, (n, 4 * h, 4 * w, 64))):
+            if tuple(np.shape(t)) != want:
+                raise ValueError("%s must be %s for conv5_3_3x3 %s (got %s)" % (name, want, (n, h, w, 256), tuple(np.shape(t))))
+            dt = str(getattr(t, "dtype", ""))
+            if "float" not in dt:
+                raise ValueError("%s must be a floating-point tensor (got %s)" % (name, dt or type(t).__name__))
+        return mw
+
+    def gradient_features(self, conv5_3_3x3, conv5_2, conv3_1, conv3_sub1, labels, mask, params=None, max_workgroups=0,
+                          labelled=None, confusion=None, return_pseudo_pixels=False):
+        """(loss float64 [1], {name: gradient} for ``variable_names``) on the device for ``conv5_3_3x3`` [N, h, w, 256],
+        ``conv5_2`` [N, h, w, 1024], ``conv3_1`` [N, 2h, 2w, 256], ``conv3_sub1`` [N, 4h, 4w, 64] and labels / mask
+        [N, 32h, 32w].  ``params`` overrides any of the 20 tensors; ``max_workgroups``: 0 = the default grids, a tuning knob.
+        No update."""
+        return self._gradient_from((conv5_3_3x3, conv5_2, conv3_1, conv3_sub1), labels, mask, params, max_workgroups,
+                                   labelled=labelled, confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
+
+    def features(self, images):
+        """``(conv5_3_3x3 [N, H/32, W/32, 256], conv5_2 [N, H/32, W/32, 1024], conv3_1 [N, H/16, W/16, 256], conv3_sub1
+        [N, H/8, W/8, 64])`` for ``images`` (copies): what ``step_features`` and ``gradient_features`` take.  One forward pass
+        of the frozen layers."""
+        self.net(images, training=False)
+        return tuple(self.net.endpoint(name).clone() for name in self._FEATURE_NAMES)
+
+    def step_features(self, conv5_3_3x3, conv5_2, conv3_1, conv3_sub1, labels, mask, max_workgroups=0, labelled=None,
+                      confusion=None, return_pseudo_pixels=False):
+        """one Adam step from cached features; returns the loss (float64 device scalar) BEFORE the step"""
+        return self._step_from((conv5_3_3x3, conv5_2, conv3_1, conv3_sub1), labels, mask, max_workgroups, labelled=labelled,
+                               confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
+
+    def step(self, images, labels, mask, max_workgroups=0, labelled=None, confusion=None, return_pseudo_pixels=False):
+        """one Adam step from images [N, H, W, C] (fp32 or decoded uint8) and labels / mask [N, H, W]: the frozen trunk up to
+        ``conv5_3_3x3``, ``conv5_2``, ``conv3_1`` and ``conv3_sub1``, then the increase layer, the pyramid pooling,
+        ``conv5_4_k1``, both fusion blocks and the head on the weights being trained, their gradient kernels, Adam.  Returns
+        the loss (float64 device scalar) before the step."""
+        return self._step_from_images(images, labels, mask, max_workgroups, labelled=labelled, confusion=confusion,
+                                      return_pseudo_pixels=return_pseudo_pixels)
+
+
 # ---- the semi-supervised step of ICNet's fusion and cascade trainers (DESIGN.md section 30) --------------------------------------
 class SemiSupervisedICNetFusionTrainer(_SemiKeywords, ICNetFusionTrainer):
     """``ICNetFusionTrainer`` with the reference's semi-supervised step (active_learning.py:226-275, 339-342) built into the
@@ -1919,4 +1990,4 @@ __all__ = ["FinalLayerTrainer", "LastBlockTrainer", "LastStageTrainer", "Decoder
            "DecoderTrainer", "SemiSupervisedDecoderTrainer", "ICNetHeadTrainer", "SemiSupervisedICNetHeadTrainer",
            "ICNetFusionTrainer", "ICNetCascadeTrainer", "SemiSupervisedICNetFusionTrainer",
            "SemiSupervisedICNetCascadeTrainer", "ICNetHighResTrainer", "SemiSupervisedICNetHighResTrainer",
-           "ICNetPyramidTrainer"]
+           "ICNetPyramidTrainer", "ICNetPoolingTrainer"]

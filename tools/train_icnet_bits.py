@@ -18,9 +18,17 @@ judgement, straight through the C ABI on dummy device pointers (nothing is launc
 images entry takes its class count from the handle and judges the frame's size before the depth's limit can be reached, so
 "classes out of range" and "feature map beyond the limit" are recorded for the features entries only.
 
-    python tools/train_icnet_bits.py --out profiles/r27_train_icnet_bits.json
+The two depths without semi-supervised entries, ``ICNetPyramidTrainer`` and ``ICNetPoolingTrainer`` (DESIGN.md sections 39 and
+41), are recorded in their plain parts: ``gradient_features``, one ``step``, the two plain size queries, the plain entries'
+refusals.  A depth whose trainer the package under test does not have is left out of the file.
+
+    python tools/train_icnet_bits.py --out profiles/r28_train_icnet_bits.json
     SSAL_LIB_PATH=/path/to/another/libssal_hip.so python tools/train_icnet_bits.py --out other.json
-    python tools/train_icnet_bits.py --compare other.json profiles/r27_train_icnet_bits.json
+    python tools/train_icnet_bits.py --compare other.json profiles/r28_train_icnet_bits.json
+    python tools/train_icnet_bits.py --compare other.json profiles/r28_train_icnet_bits.json --depths head,fusion,cascade,highres,pyramid
+
+``--depths`` restricts a comparison to the entries of those depths: a file written by this tool from an earlier tree (copy the
+tool next to that tree's package) has no entry of a depth that tree lacks.
 
 Run each library in a fresh process: the package loads one library per process.  ``--compare`` counts an entry that only one
 file has as differing, unless the files are of different formats (``profiles/r25_train_icnet_bits.json`` is of the first, which
@@ -42,7 +50,16 @@ SECTIONS = ("sha256", "workspace_bytes", "refused")
 SHAPES = [(1, 1, 1), (2, 2, 3), (1, 3, 5)]
 CASES = [(s, mw, k, wl) for s in SHAPES for mw in (1, 2) for k, wl in ((2, (0.0, 0.0)), (19, (1.02, 0.1)))]
 DEPTHS = ("head", "fusion", "cascade", "highres")
-FEATS = {"head": 1, "fusion": 2, "cascade": 3, "highres": 3}  # feature pointers of the features entry (highres: the frame last)
+PLAIN_DEPTHS = ("pyramid", "pool")  # no semi-supervised entries yet
+# feature pointers of the features entry (highres: the frame last)
+FEATS = {"head": 1, "fusion": 2, "cascade": 3, "highres": 3, "pyramid": 3, "pool": 4}
+PLAIN_TRAINERS = {"pyramid": "ICNetPyramidTrainer", "pool": "ICNetPoolingTrainer"}
+
+
+def plain_depths():
+    """the members of PLAIN_DEPTHS the package under test has"""
+    from semanticsegmentationactivelearning_amd import training as T
+    return tuple(d for d in PLAIN_DEPTHS if hasattr(T, PLAIN_TRAINERS[d]))
 
 
 def _sha(t):
@@ -103,6 +120,8 @@ def _step_records(out, tag, classes, net, seed, n, h, w, k, mw, kw, u8):
     mask = torch.as_tensor((rng.uniform(size=(n, h, w)) > 0.25).astype(np.float32)).cuda()
     labelled = torch.as_tensor([i % 2 for i in range(n)], dtype=torch.uint8)
     for kind, cls, raw in (("plain", classes[0], None), ("semi noraw", classes[1], None), ("semi raw", classes[1], x_raw)):
+        if cls is None:
+            continue  # a depth without semi-supervised entries
         syn.randomize_icnet(net, seed=5)
         tr = cls(net, 1e-3, measure="entropy", threshold=0.8 * float(np.log(k)), **kw)
         if kind == "plain":
@@ -168,15 +187,36 @@ def digests():
                 _semi_records(out, htag, T["highres"][1](net, 1e-3, **semi_kw), dev(c54, c31, frame), dev(r54, r31, raw),
                               labels, mask, d, mw, k, False)
 
+        plain = plain_depths()
+        if "pyramid" in plain:
+            import test_gpu_train_icnet_pyramid as tp
+            import icnet_pyramid_train_oracle as ipo
+            c53, c31, c3, d, labels, mask = ipo.case(9400 + i, n, h, w, k)
+            T["pyramid"] = (getattr(_training(), PLAIN_TRAINERS["pyramid"]), None)
+            _record(out, "pyramid " + tag, *T["pyramid"][0](tp._shared_net(k), 1e-3, **kw).gradient_features(
+                *dev(c53, c31, c3), labels, mask, params=d, max_workgroups=mw))
+        if "pool" in plain:
+            import test_gpu_train_icnet_pool as tq
+            import icnet_pool_train_oracle as po
+            a33, c52, c31, c3, d, labels, mask = po.case(9500 + i, n, h, w, k)
+            T["pool"] = (getattr(_training(), PLAIN_TRAINERS["pool"]), None)
+            _record(out, "pool " + tag, *T["pool"][0](tq._shared_net(k), 1e-3, **kw).gradient_features(
+                *dev(a33, c52, c31, c3), labels, mask, params=d, max_workgroups=mw))
+
         # the images entries, on models of their own (a step writes the trained variables back); frames of 32 h x 32 w for
         # every depth, the trunk's own unit
-        for depth in DEPTHS:
+        for depth in DEPTHS + plain:
             for c_in in ((3, 4) if depth == "highres" else (3,)):
                 net = _step_net(k, c_in)
                 _step_records(out, "%s c_in=%d %s" % (depth, c_in, tag), T[depth], net, 9300 + i, n, 32 * h, 32 * w, k, mw, kw,
                               c_in == 3)
     torch.cuda.synchronize()
     return out
+
+
+def _training():
+    from semanticsegmentationactivelearning_amd import training
+    return training
 
 
 _STEP_NETS = {}
@@ -200,14 +240,14 @@ def workspace_bytes():
         net = _step_net(k, 3)
         syn.randomize_icnet(net, seed=5)
         handle = net._sync_handle()
-        for depth in DEPTHS:
+        for depth in DEPTHS + plain_depths():
             for n, h, w in SHAPES:
                 tag = "%dx%dx%d K=%d" % (n, h, w, k)
                 out["ssal_icnet_%s_grad_workspace_bytes %s" % (depth, tag)] = int(
                     getattr(L, "ssal_icnet_%s_grad_workspace_bytes" % depth)(n, h, w, k))
                 out["ssal_icnet_train_%s_workspace_bytes %s" % (depth, tag)] = int(
                     getattr(L, "ssal_icnet_train_%s_workspace_bytes" % depth)(handle, n, 32 * h, 32 * w))
-                for raw in (0, 1):
+                for raw in (0, 1) if depth in DEPTHS else ():
                     out["ssal_icnet_%s_grad_semi_workspace_bytes %s raw=%d" % (depth, tag, raw)] = int(
                         getattr(L, "ssal_icnet_%s_grad_semi_workspace_bytes" % depth)(n, h, w, k, raw))
                     out["ssal_icnet_train_%s_semi_workspace_bytes %s raw=%d" % (depth, tag, raw)] = int(
@@ -243,11 +283,12 @@ def refused():
     handle = net._sync_handle()
     dummy = torch.zeros(4096, dtype=torch.uint8, device="cuda")
     P = _lib.dev_ptr(dummy)
-    beyond = {"head": (1 << 27) + 1, "fusion": (1 << 26) + 1, "cascade": (1 << 25) + 1, "highres": 512}
+    beyond = {"head": (1 << 27) + 1, "fusion": (1 << 26) + 1, "cascade": (1 << 25) + 1, "highres": 512,
+              "pyramid": (1 << 25) + 1, "pool": (1 << 25) + 1}
     out = {}
-    for depth in DEPTHS:
+    for depth in DEPTHS + plain_depths():
         for images in (False, True):
-            for semi in (False, True):
+            for semi in (False, True) if depth in DEPTHS else (False,):
                 stem = ("ssal_icnet_train_%s" if images else "ssal_icnet_%s_grad") % depth + ("_semi" if semi else "")
                 dims = (n, 32 * h, 32 * w) if images else (n, h, w)
                 query = (handle,) + dims if images else dims + (k,)
@@ -281,8 +322,20 @@ def refused():
     return out
 
 
-def compare(path_a, path_b):
+def depth_of(key):
+    """the depth an entry of any section belongs to"""
+    import re
+    m = re.match(r"ssal_icnet_(?:train_)?([a-z]+?)_(?:grad|semi|workspace|nhwc)", key)
+    return m.group(1) if m else key.split(" ", 1)[0]
+
+
+def compare(path_a, path_b, depths=None):
     a, b = (json.load(open(p)) for p in (path_a, path_b))
+    if depths is not None:
+        for f in (a, b):
+            for section in SECTIONS:
+                f[section] = {k: v for k, v in f.get(section, {}).items() if depth_of(k) in depths}
+        print("(entries of the depths %s only)" % ", ".join(depths))
     same_format = a.get("format", 1) == b.get("format", 1)
     total, alone, bad = 0, 0, []
     for section in SECTIONS:
@@ -301,7 +354,7 @@ def compare(path_a, path_b):
     return 1 if bad or not total else 0
 
 
-def main(default_out=os.path.join(ROOT, "profiles", "r27_train_icnet_bits.json"), parts=None, cases=len(CASES)):
+def main(default_out=os.path.join(ROOT, "profiles", "r28_train_icnet_bits.json"), parts=None, cases=len(CASES)):
     """``parts``: the (digests, workspace_bytes, refused) functions of a sibling tool (tools/train_enet_bits.py) and ``cases`` its
     case count, else this file's"""
     digests, workspace_bytes, refused = parts or (globals()[name] for name in ("digests", "workspace_bytes", "refused"))
@@ -310,9 +363,10 @@ def main(default_out=os.path.join(ROOT, "profiles", "r27_train_icnet_bits.json")
     ap.add_argument("--results", metavar="JSON", help="also write every result's own digest (a file of format 1, large): two "
                     "such files compare result by result, which names the tensor where a call's digest differs")
     ap.add_argument("--compare", nargs=2, metavar="JSON", help="compare two result files instead of running")
+    ap.add_argument("--depths", help="with --compare: a comma-separated list of depths, the only ones compared")
     a = ap.parse_args()
     if a.compare:
-        sys.exit(compare(*a.compare))
+        sys.exit(compare(*a.compare, depths=a.depths.split(",") if a.depths else None))
     results = digests()
     out = {"sha256": fold(results), "workspace_bytes": workspace_bytes(), "refused": refused()}
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
