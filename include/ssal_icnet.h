@@ -276,6 +276,42 @@ int ssal_icnet_train_pool_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, 
 /* ssal_icnet_update_fusion for the twenty variables: only the seven trained layers are re-laid-out, folded and uploaded */
 int ssal_icnet_update_pool(ssal_icnet *net, const float *params_host, void *stream);
 
+/* ---- Training of the last backbone bottleneck: conv5_3_1x1_reduce = relu(BN(1 x 1 conv, 1024 -> 256, of
+ * conv5_2)), conv5_3_3x3 = relu(BN(3 x 3 conv at dilation 4, 256 -> 256, SAME: four zero pixels on every side)), then everything
+ * the pooling entries above train (the increase layer takes conv5_2 as its identity shortcut), over everything below conv5_2
+ * and the two other frozen branches ----
+ * The 26 trained variables travel PACKED, in this order: conv5_3_1x1_reduce.kernel [1,1,1024,256] | .gamma [256] | .beta [256] |
+ * conv5_3_3x3.kernel [3,3,256,256] | .gamma [256] | .beta [256] | the twenty of the pooling entries in their order (852992
+ * floats, then theirs); params_dev and grad_dev have that layout.  stats_dev [4 * 256 + 2 * 1024 + 2 * 256 + 8 * 128] = the
+ * reduce layer's mean | variance | the 3 x 3's mean | variance | the rows of the pooling entries; batch-norm as there.  One call
+ * computes, for conv5_2 [n,h,w,1024] (1/32 resolution), conv3_1 [n,2h,2w,256], conv3_sub1 [n,4h,4w,64], labels uint8 and mask
+ * fp32 [n,32h,32w]: conv5_3_1x1_reduce and conv5_3_3x3 by the forward path's own launches on params_dev, everything above as
+ * ssal_icnet_pool_grad_nhwc does, the loss -> loss_dev [1] float64, and the gradient of all 26 variables -> grad_dev (without the
+ * regulariser).  Nothing below the three inputs gets a gradient.  The loss and the last twenty gradients are the bits
+ * ssal_icnet_pool_grad_nhwc gives on the same conv5_3_3x3.  Determinism, statuses and the order of the checks as
+ * ssal_icnet_pool_grad_nhwc's; the size query returns -1 beyond the cascade entries' limit.  max_workgroups (0: no limit) caps
+ * the FIRST grid index of every launch, as there; besides the launches named there, four launches of this depth have further
+ * indices that it does not cap: the two data gradients (through the increase layer and through the 3 x 3) run 2 x that many
+ * workgroups (two slabs of 128 of their 256 input channels), the 3 x 3 weight gradient 36 x that many (9 taps x 2 x 2 slabs of
+ * 128 x 128) and the reduce layer's weight gradient 16 x that many -- max_workgroups = 1 is 2, 2, 36 and 16 workgroups.  The
+ * split-K partials of the 3 x 3 weight gradient are at most 16 x 2.36 MB of the workspace. */
+int64_t ssal_icnet_bneck_grad_workspace_bytes(int n, int h, int w, int classes);
+int ssal_icnet_bneck_grad_nhwc(const float *conv5_2_dev, const float *conv3_1_dev, const float *conv3_sub1_dev, int n, int h,
+                               int w, int classes, const float *params_dev, const uint8_t *labels_dev, const float *mask_dev,
+                               float weight, float label_smoothing, const float *stats_dev, int max_workgroups, double *loss_dev,
+                               float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream);
+/* the same from frames x_dev [n,h,w,c_in] (fp32, or uint8 when x_is_u8 != 0): the frozen trunk until conv5_2, conv3_1 and
+ * conv3_sub1 are written -- its low-resolution schedule ends behind conv5_2: no layer of conv5_3, the pyramid pooling and
+ * conv5_4_k1 are not launched -- then the tail above; labels / mask [n,h,w].  After the call the endpoints from
+ * conv5_3_1x1_reduce on are those of params_dev. */
+int64_t ssal_icnet_train_bneck_workspace_bytes(const ssal_icnet *net, int n, int h, int w);
+int ssal_icnet_train_bneck_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w, const uint8_t *labels_dev,
+                                const float *mask_dev, const float *params_dev, float weight, float label_smoothing,
+                                const float *stats_dev, int max_workgroups, double *loss_dev, float *grad_dev, void *ws_dev,
+                                int64_t ws_bytes, void *stream);
+/* ssal_icnet_update_fusion for the 26 variables: only the nine trained layers are re-laid-out, folded and uploaded */
+int ssal_icnet_update_bneck(ssal_icnet *net, const float *params_host, void *stream);
+
 /* ---- The semi-supervised step of the fusion and the cascade trainer (active_learning.py:226-275, 339-342; DESIGN.md
  * section 30) ----
  * The four gradient calls above with the targets built inside the head's gradient kernel: labelled_dev, measure, threshold,

@@ -14,6 +14,7 @@
 #include "ssal_train_icnet_cascade.h"
 #include "ssal_train_icnet_fusion.h"
 #include "ssal_train_icnet_highres.h"
+#include "ssal_train_icnet_bneck.h"
 #include "ssal_train_icnet_pool.h"
 #include "ssal_train_icnet_pyramid.h"
 
@@ -264,12 +265,17 @@ struct Grp {
 // 1x1_reduce and 3x3 run as the separate run_conv launches they always are at 1024 channels (fused_bneck() is the 128-channel
 // family) and write conv5_3_1x1_reduce and conv5_3_3x3; its increase layer, launch_ppm and conv5_4_k1 are neither launched nor
 // written (the pooling trainer runs them on the weights it trains); the high-resolution branch still runs
+// reduce = false (implies increase = false): the low-resolution schedule ends after the launch that writes conv5_2 -- conv5_3's
+// 1x1_reduce and 3x3 are neither launched nor written either (the bottleneck trainer runs the whole of conv5_3 on the weights it
+// trains); the high-resolution branch still runs
 // arith: SSAL_ARITH_BF16X3 hands the mode to every run_conv (launch_igemm keeps what has no split kernel exact) and runs the
 // fused blocks on ENet's bf16x3 regular-block kernel; the training, evaluate and regions entries pass the default
 hipError_t run_trunk(const ssal_icnet *net, std::vector<Grp> &grp, bool x_is_u8, int h, int w, bool fused,
                      std::set<std::string> *written = nullptr, bool head = true, bool fusion = true, bool cascade = true,
-                     bool highres = true, int arith = SSAL_ARITH_F32, bool k1 = true, bool increase = true)
+                     bool highres = true, int arith = SSAL_ARITH_F32, bool k1 = true, bool increase = true,
+                     bool reduce = true)
 {
+    if (!reduce) increase = false;  // a schedule that ends in front of conv5_3 writes no conv5_3_3x3 for the increase layer to read
     if (!increase) k1 = false;  // a schedule that ends inside conv5_3 writes no conv5_3_sum for conv5_4_k1 to read
     const bool dry = written != nullptr;
 #define OUT(name) do { if (dry) written->insert(name); } while (0)
@@ -304,6 +310,7 @@ hipError_t run_trunk(const ssal_icnet *net, std::vector<Grp> &grp, bool x_is_u8,
     for (int i = 0; i < kNumBnecks; ++i) {
         const BneckSpec &b = kBnecks[i];
         const std::string nm = b.name;
+        if (!reduce && i == kNumBnecks - 1) break;  // conv5_3 of a schedule that ends behind conv5_2
         if (i == kStemBnecks) {
             // section 2: conv3_1_sub4 = resize_bilinear(conv3_1, 1/2)
             OUT("conv3_1_sub4");
@@ -893,7 +900,7 @@ const float *F(const void *p) { return static_cast<const float *>(p); }
 struct HeadDepth {
     using Ws = IcnetHeadWs;
     static constexpr int kUnit = 8, kLevel = 0;
-    static constexpr bool kK1 = true, kIncrease = true;
+    static constexpr bool kK1 = true, kIncrease = true, kReduce = true;
     static constexpr bool kStats = false, kFrame = false, kImagesQueryFits = false;
     static constexpr const char *kNoun = "head gradient kernel's", *kEndpoints[] = {"sub12_sum"};
 
@@ -925,7 +932,7 @@ struct HeadDepth {
 struct FusionDepth {
     using Ws = IcnetFusionWs;
     static constexpr int kUnit = 16, kLevel = 1;
-    static constexpr bool kK1 = true, kIncrease = true;
+    static constexpr bool kK1 = true, kIncrease = true, kReduce = true;
     static constexpr bool kStats = true, kFrame = false, kImagesQueryFits = false;
     static constexpr const char *kNoun = "fusion gradient kernels'", *kEndpoints[] = {"sub24_sum", "conv3_sub1"};
 
@@ -971,7 +978,7 @@ struct FusionDepth {
 struct CascadeDepth {
     using Ws = IcnetCascadeWs;
     static constexpr int kUnit = 32, kLevel = 2;
-    static constexpr bool kK1 = true, kIncrease = true;
+    static constexpr bool kK1 = true, kIncrease = true, kReduce = true;
     static constexpr bool kStats = true, kFrame = false, kImagesQueryFits = false;
     static constexpr const char *kNoun = "cascade gradient kernels'", *kEndpoints[] = {"conv5_4_k1", "conv3_1", "conv3_sub1"};
 
@@ -1017,7 +1024,7 @@ struct CascadeDepth {
 struct HighresDepth {
     using Ws = IcnetHighresWs;
     static constexpr int kUnit = 32, kLevel = 3;
-    static constexpr bool kK1 = true, kIncrease = true;
+    static constexpr bool kK1 = true, kIncrease = true, kReduce = true;
     static constexpr bool kStats = true, kFrame = true, kImagesQueryFits = true;
     static constexpr const char *kNoun = "high-resolution gradient kernels'", *kEndpoints[] = {"conv5_4_k1", "conv3_1"};
 
@@ -1068,7 +1075,7 @@ struct HighresDepth {
 struct PyramidDepth {
     using Ws = IcnetPyramidWs;
     static constexpr int kUnit = 32, kLevel = 2;
-    static constexpr bool kK1 = false, kIncrease = true;
+    static constexpr bool kK1 = false, kIncrease = true, kReduce = true;
     static constexpr bool kStats = true, kFrame = false, kImagesQueryFits = false;
     static constexpr const char *kNoun = "pyramid gradient kernels'", *kEndpoints[] = {"conv5_3_sum", "conv3_1", "conv3_sub1"};
 
@@ -1111,7 +1118,7 @@ struct PyramidDepth {
 struct PoolDepth {
     using Ws = IcnetPoolWs;
     static constexpr int kUnit = 32, kLevel = 2;
-    static constexpr bool kK1 = false, kIncrease = false;
+    static constexpr bool kK1 = false, kIncrease = false, kReduce = true;
     static constexpr bool kStats = true, kFrame = false, kImagesQueryFits = false;
     static constexpr const char *kNoun = "pooling gradient kernels'",
                                 *kEndpoints[] = {"conv5_3_3x3", "conv5_2", "conv3_1", "conv3_sub1"};
@@ -1151,6 +1158,55 @@ struct PoolDepth {
         return launch_icnet_pool_grad(F(in.f[0]), F(in.f[1]), F(in.f[2]), F(in.f[3]), in.n, in.h, in.w, in.classes, in.params,
                                       in.stats, a.labels, a.mask, a.weight, a.label_smoothing, in.max_workgroups, t, a.loss, a.grad,
                                       a.s);
+    }
+};
+
+// the last backbone bottleneck (kernels: ssal_train_icnet_bneck.hip): conv5_2 [n,h32,w32,1024] (the reduce
+// layer's input and the identity shortcut), conv3_1 and conv3_sub1.  Contains the pooling depth (head < fusion < cascade <
+// pyramid < pooling < bottleneck).  The trunk of an images entry stops where the pooling depth's does, and its low-resolution
+// schedule ends behind conv5_2 (kReduce = false); conv5_3's three layers, the pyramid pooling, conv5_4_k1, the two blocks and
+// the head write the endpoints from conv5_3_1x1_reduce on.  The semi-supervised entries are not built yet: there is no target
+// launch.
+struct BneckDepth {
+    using Ws = IcnetBneckWs;
+    static constexpr int kUnit = 32, kLevel = 2;
+    static constexpr bool kK1 = false, kIncrease = false, kReduce = false;
+    static constexpr bool kStats = true, kFrame = false, kImagesQueryFits = false;
+    static constexpr const char *kNoun = "bottleneck gradient kernels'", *kEndpoints[] = {"conv5_2", "conv3_1", "conv3_sub1"};
+
+    static Ws carve(Bump &b, int64_t n, int h32, int w32, int classes, bool own_acts)
+    {
+        Ws t;
+        const int64_t act = n * h32 * (int64_t)w32 * BK_C;
+        t.wt_r = b.take<float>(BK_GR);
+        t.wt_3 = b.take<float>(9 * BK_C * BK_C);
+        t.rows = b.take<float>(4 * BK_C);
+        t.rd = own_acts ? b.take<float>(act) : nullptr;
+        t.a33 = own_acts ? b.take<float>(act) : nullptr;
+        t.g3 = b.take<float>(act);
+        t.gr = b.take<float>(act);
+        t.part3 = b.take<float>((int64_t)BK_W3_MAX_WG * BK_PART3);  // (sized for the default grid: max_workgroups only lowers it)
+        t.fold3 = b.take<float>(BK_PART3);
+        t.partr = b.take<float>((int64_t)PY_MAX_WG * BK_PARTR);
+        t.foldr = b.take<float>(BK_PARTR);
+        t.pool = PoolDepth::carve(b, n, h32, w32, classes, own_acts);
+        return t;
+    }
+    static void bind(Ws &t, const IcWorkspace &W)
+    {
+        t.rd = W.act.at("conv5_3_1x1_reduce");
+        t.a33 = W.act.at("conv5_3_3x3");
+        PoolDepth::bind(t.pool, W);
+    }
+    static bool fits(int n, int h32, int w32) { return icnet_bneck_fits(h32, w32) && PoolDepth::fits(n, h32, w32); }
+    static hipError_t targets(const DepthIn &, const Ws &, const IcnetHeadSemi &, uint8_t *, hipStream_t)
+    {
+        return hipErrorNotSupported;  // (no entry hands this depth a SemiArgs)
+    }
+    static hipError_t grad(const DepthIn &in, const CallArgs &a, const Ws &t, const IcnetHeadSemi *)
+    {
+        return launch_icnet_bneck_grad(F(in.f[0]), F(in.f[1]), F(in.f[2]), in.n, in.h, in.w, in.classes, in.params, in.stats,
+                                       a.labels, a.mask, a.weight, a.label_smoothing, in.max_workgroups, t, a.loss, a.grad, a.s);
     }
 };
 
@@ -1254,13 +1310,13 @@ int images_entry(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int 
     // the frozen trunk, on the undistorted (of_raw) or the training frames, through the same slots of W.  It ends in front of the
     // layers being trained: run_trunk without the head, and from level 1 / 2 / 3 on without the last fusion stage / the first
     // one / the high-resolution branch; without conv5_4_k1 where the depth trains it (kK1), and from conv5_3's increase layer on
-    // where it trains that (kIncrease)
+    // where it trains that (kIncrease), and from conv5_3's reduce layer on where it trains the whole bottleneck (kReduce)
     hipStream_t s = a.s;
     auto trunk = [=, &W](bool of_raw) -> int {
         std::vector<Grp> one(1);
         one[0] = {W, of_raw ? x_raw_dev : x_dev, n, s};
         HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false, D::kLevel < 1, D::kLevel < 2, D::kLevel < 3,
-                          SSAL_ARITH_F32, D::kK1, D::kIncrease));
+                          SSAL_ARITH_F32, D::kK1, D::kIncrease, D::kReduce));
         return SSAL_OK;
     };
     return depth_run<D>(trunk, in, a, semi, c);
@@ -1394,6 +1450,14 @@ HostUpdates pool_tensors(const float *p, int K)
     return then({{"conv5_3_1x1_increase.kernel", p + PO_K, PO_G}, {"conv5_3_1x1_increase.gamma", p + PO_G, PO_CO},
                  {"conv5_3_1x1_increase.beta", p + PO_B, PO_CO}},
                 pyramid_tensors(p + PO_PYRAMID, K));
+}
+
+HostUpdates bneck_tensors(const float *p, int K)
+{
+    return then({{"conv5_3_1x1_reduce.kernel", p + BK_KR, BK_GR}, {"conv5_3_1x1_reduce.gamma", p + BK_GR, BK_C},
+                 {"conv5_3_1x1_reduce.beta", p + BK_BR, BK_C}, {"conv5_3_3x3.kernel", p + BK_K3, 9 * BK_C * BK_C},
+                 {"conv5_3_3x3.gamma", p + BK_G3, BK_C}, {"conv5_3_3x3.beta", p + BK_B3, BK_C}},
+                pool_tensors(p + BK_POOL, K));
 }
 
 }  // namespace
@@ -1693,6 +1757,45 @@ SSAL_API int ssal_icnet_update_pool(ssal_icnet *net, const float *params_host, v
     return update_packed(net, pool_tensors(params_host, net->classes),
                          {"conv5_3_1x1_increase", "conv5_4_k1", "conv_sub4", "conv3_1_sub2_proj", "conv_sub2", "conv3_sub1_proj",
                           "conv6_cls"}, stream);
+}
+
+// ---- the last backbone bottleneck: conv5_3's reduce layer and 3 x 3, and everything the pooling entries train ----
+SSAL_API int64_t ssal_icnet_bneck_grad_workspace_bytes(int n, int h, int w, int classes)
+{
+    return features_query<BneckDepth>(n, h, w, classes, false, false);
+}
+
+SSAL_API int ssal_icnet_bneck_grad_nhwc(const float *conv5_2_dev, const float *conv3_1_dev, const float *conv3_sub1_dev, int n,
+                                        int h, int w, int classes, const float *params_dev, const uint8_t *labels_dev,
+                                        const float *mask_dev, float weight, float label_smoothing, const float *stats_dev,
+                                        int max_workgroups, double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes,
+                                        void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return features_entry<BneckDepth>({{conv5_2_dev, conv3_1_dev, conv3_sub1_dev}, {}, params_dev, stats_dev, max_workgroups, n, h,
+                                       w, classes}, a, nullptr);
+}
+
+SSAL_API int64_t ssal_icnet_train_bneck_workspace_bytes(const ssal_icnet *net, int n, int h, int w)
+{
+    return images_query<BneckDepth>(net, n, h, w, false, false);
+}
+
+SSAL_API int ssal_icnet_train_bneck_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                                         const uint8_t *labels_dev, const float *mask_dev, const float *params_dev, float weight,
+                                         float label_smoothing, const float *stats_dev, int max_workgroups, double *loss_dev,
+                                         float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return images_entry<BneckDepth>(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, stats_dev, max_workgroups, a, nullptr);
+}
+
+SSAL_API int ssal_icnet_update_bneck(ssal_icnet *net, const float *params_host, void *stream)
+{
+    if (!net || !params_host) return fail(SSAL_EINVAL, "NULL argument");
+    return update_packed(net, bneck_tensors(params_host, net->classes),
+                         {"conv5_3_1x1_reduce", "conv5_3_3x3", "conv5_3_1x1_increase", "conv5_4_k1", "conv_sub4", "conv3_1_sub2_proj",
+                          "conv_sub2", "conv3_sub1_proj", "conv6_cls"}, stream);
 }
 
 // ---- the high-resolution branch down to the image ----

@@ -205,4 +205,31 @@ hipError_t launch_icnet_wgrad_256x1024(const float *x, const float *g, long pixe
     return hipGetLastError();
 }
 
+// The three kernels at 1024 x 256 for a second layer of that shape (ssal_train_icnet_pyramid.h): the weight gradient of conv5_3's
+// reduce layer, its fold and finish, its dGamma
+hipError_t launch_icnet_wgrad_1024x256(const float *x, const float *g, long pixels, int max_workgroups, const float *scale,
+                                       const float *sl, const float *K, const float *mean, const float *var, float *part,
+                                       float *fold, float *gK, float *gG, float *gB, hipStream_t s)
+{
+    if (pixels < 1 || max_workgroups < 0) return hipErrorInvalidValue;
+    hipError_t e;
+    const int G = icnet_grid(icnet_cdiv(pixels, PY_PT), PY_MAX_WG, max_workgroups);
+    {
+        ProfScope prof("k_icnet_bneck_wgrad_r", 2.0 * (double)pixels * PY_PART, 4.0 * (double)pixels * (PY_CIN + PY_CO) + 4.0 * G * PY_PART,
+                       s);
+        hipLaunchKernelGGL((k_icnet_pyramid_wgrad<PY_CIN, PY_CO>), dim3(G, PY_CIN / 128, PY_CO / 128), dim3(256), 0, s, x, g, pixels,
+                           part);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    {
+        ProfScope prof("k_icnet_bneck_finish_r", (double)G * PY_PART, 4.0 * (G + 2.0) * PY_PART, s);
+        hipLaunchKernelGGL((k_icnet_pyramid_finish<PY_CIN, PY_CO>), dim3(icnet_cdiv(PY_PART, 256)), dim3(256), 0, s, part, G, scale, sl,
+                           fold, gK, gB);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    ProfScope prof("k_icnet_bneck_gamma_r", 2.0 * PY_G, 8.0 * PY_PART, s);
+    hipLaunchKernelGGL((k_icnet_pyramid_gamma<PY_CIN, PY_CO>), dim3(PY_CO / 256), dim3(256), 0, s, fold, scale, K, mean, var, gG);
+    return hipGetLastError();
+}
+
 }  // namespace ssal
