@@ -312,6 +312,42 @@ int ssal_icnet_train_bneck_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8,
 /* ssal_icnet_update_fusion for the 26 variables: only the nine trained layers are re-laid-out, folded and uploaded */
 int ssal_icnet_update_bneck(ssal_icnet *net, const float *params_host, void *stream);
 
+/* ---- Training through conv5_2, the last backbone bottleneck but one: conv5_2_1x1_reduce = relu(BN(1 x 1
+ * conv, 1024 -> 256, of conv5_1)), conv5_2_3x3 = relu(BN(3 x 3 conv at dilation 4, 256 -> 256, SAME)), conv5_2 = relu(BN(1 x 1
+ * conv, 256 -> 1024, of it) + conv5_1), then everything the bottleneck entries above train (conv5_3 takes conv5_2 as its input
+ * and identity shortcut), over everything below conv5_1 and the two other frozen branches ----
+ * The 35 trained variables travel PACKED, in this order: conv5_2_1x1_reduce.kernel [1,1,1024,256] | .gamma [256] | .beta [256] |
+ * conv5_2_3x3.kernel [3,3,256,256] | .gamma [256] | .beta [256] | conv5_2_1x1_increase.kernel [1,1,256,1024] | .gamma [1024] |
+ * .beta [1024] | the 26 of the bottleneck entries in their order (1117184 floats, then theirs); params_dev and grad_dev have
+ * that layout.  stats_dev [4 * 256 + 2 * 1024, then the bottleneck entries' rows] = conv5_2's reduce layer's mean | variance |
+ * its 3 x 3's mean | variance | its increase layer's mean | variance | the rows of the bottleneck entries; batch-norm as there.
+ * One call computes, for conv5_1 [n,h,w,1024] (1/32 resolution), conv3_1 [n,2h,2w,256], conv3_sub1 [n,4h,4w,64], labels uint8
+ * and mask fp32 [n,32h,32w]: the three layers of conv5_2 by the forward path's own launches on params_dev, everything above as
+ * ssal_icnet_bneck_grad_nhwc does, the loss -> loss_dev [1] float64, and the gradient of all 35 variables -> grad_dev (without
+ * the regulariser).  Nothing below the three inputs gets a gradient.  The loss and the last 26 gradients are the bits
+ * ssal_icnet_bneck_grad_nhwc gives on the same conv5_2.  Determinism, statuses and the order of the checks as
+ * ssal_icnet_bneck_grad_nhwc's; the size query returns -1 beyond the cascade entries' limit.  max_workgroups (0: no limit) caps
+ * the FIRST grid index of every launch, as there; the launches of the bottleneck entries with further indices run a second
+ * time for conv5_2, and two more have further indices that it does not cap: the data gradient onto conv5_2 runs 8 x that many
+ * workgroups (eight slabs of 128 of its 1024 channels) and conv5_2's increase weight gradient 16 x that many.  The workspace
+ * holds no split-K partials beyond the bottleneck entries': conv5_2's weight gradients reuse them. */
+int64_t ssal_icnet_bneck2_grad_workspace_bytes(int n, int h, int w, int classes);
+int ssal_icnet_bneck2_grad_nhwc(const float *conv5_1_dev, const float *conv3_1_dev, const float *conv3_sub1_dev, int n, int h,
+                                int w, int classes, const float *params_dev, const uint8_t *labels_dev, const float *mask_dev,
+                                float weight, float label_smoothing, const float *stats_dev, int max_workgroups, double *loss_dev,
+                                float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream);
+/* the same from frames x_dev [n,h,w,c_in] (fp32, or uint8 when x_is_u8 != 0): the frozen trunk until conv5_1, conv3_1 and
+ * conv3_sub1 are written -- its low-resolution schedule ends behind conv5_1: no layer of conv5_2 or conv5_3, the pyramid
+ * pooling and conv5_4_k1 are not launched -- then the tail above; labels / mask [n,h,w].  After the call the endpoints from
+ * conv5_2_1x1_reduce on are those of params_dev. */
+int64_t ssal_icnet_train_bneck2_workspace_bytes(const ssal_icnet *net, int n, int h, int w);
+int ssal_icnet_train_bneck2_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w, const uint8_t *labels_dev,
+                                 const float *mask_dev, const float *params_dev, float weight, float label_smoothing,
+                                 const float *stats_dev, int max_workgroups, double *loss_dev, float *grad_dev, void *ws_dev,
+                                 int64_t ws_bytes, void *stream);
+/* ssal_icnet_update_fusion for the 35 variables: only the twelve trained layers are re-laid-out, folded and uploaded */
+int ssal_icnet_update_bneck2(ssal_icnet *net, const float *params_host, void *stream);
+
 /* ---- The semi-supervised step of the fusion and the cascade trainer (active_learning.py:226-275, 339-342; DESIGN.md
  * section 30) ----
  * The four gradient calls above with the targets built inside the head's gradient kernel: labelled_dev, measure, threshold,

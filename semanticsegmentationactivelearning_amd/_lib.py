@@ -221,6 +221,12 @@ PROTOTYPES = {
     "ssal_icnet_train_bneck_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
     "ssal_icnet_train_bneck_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
     "ssal_icnet_update_bneck": (_i, [_vp, _vp, _vp]),
+    # ---- training of ICNet through conv5_2: the last bottleneck but one under the bottleneck depth ----
+    "ssal_icnet_bneck2_grad_workspace_bytes": (_i64, [_i, _i, _i, _i]),
+    "ssal_icnet_bneck2_grad_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_icnet_train_bneck2_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
+    "ssal_icnet_train_bneck2_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
+    "ssal_icnet_update_bneck2": (_i, [_vp, _vp, _vp]),
     # ---- the semi-supervised step of the two (include/ssal_icnet.h) ----
     "ssal_icnet_fusion_grad_semi_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
     "ssal_icnet_fusion_grad_semi_nhwc": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _vp, _i,

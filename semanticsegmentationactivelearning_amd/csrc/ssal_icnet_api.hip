@@ -15,6 +15,7 @@
 #include "ssal_train_icnet_fusion.h"
 #include "ssal_train_icnet_highres.h"
 #include "ssal_train_icnet_bneck.h"
+#include "ssal_train_icnet_bneck2.h"
 #include "ssal_train_icnet_pool.h"
 #include "ssal_train_icnet_pyramid.h"
 
@@ -268,13 +269,17 @@ struct Grp {
 // reduce = false (implies increase = false): the low-resolution schedule ends after the launch that writes conv5_2 -- conv5_3's
 // 1x1_reduce and 3x3 are neither launched nor written either (the bottleneck trainer runs the whole of conv5_3 on the weights it
 // trains); the high-resolution branch still runs
+// block2 = false (implies reduce = false): the low-resolution schedule ends after the launch that writes conv5_1 -- no layer of
+// conv5_2 is launched or written either (the deep bottleneck trainer runs conv5_2 and conv5_3 on the weights it trains); the
+// high-resolution branch still runs
 // arith: SSAL_ARITH_BF16X3 hands the mode to every run_conv (launch_igemm keeps what has no split kernel exact) and runs the
 // fused blocks on ENet's bf16x3 regular-block kernel; the training, evaluate and regions entries pass the default
 hipError_t run_trunk(const ssal_icnet *net, std::vector<Grp> &grp, bool x_is_u8, int h, int w, bool fused,
                      std::set<std::string> *written = nullptr, bool head = true, bool fusion = true, bool cascade = true,
                      bool highres = true, int arith = SSAL_ARITH_F32, bool k1 = true, bool increase = true,
-                     bool reduce = true)
+                     bool reduce = true, bool block2 = true)
 {
+    if (!block2) reduce = false;  // a schedule that ends in front of conv5_2 writes no conv5_2 for conv5_3's reduce layer to read
     if (!reduce) increase = false;  // a schedule that ends in front of conv5_3 writes no conv5_3_3x3 for the increase layer to read
     if (!increase) k1 = false;  // a schedule that ends inside conv5_3 writes no conv5_3_sum for conv5_4_k1 to read
     const bool dry = written != nullptr;
@@ -311,6 +316,7 @@ hipError_t run_trunk(const ssal_icnet *net, std::vector<Grp> &grp, bool x_is_u8,
         const BneckSpec &b = kBnecks[i];
         const std::string nm = b.name;
         if (!reduce && i == kNumBnecks - 1) break;  // conv5_3 of a schedule that ends behind conv5_2
+        if (!block2 && i == kNumBnecks - 2) break;  // conv5_2 of a schedule that ends behind conv5_1
         if (i == kStemBnecks) {
             // section 2: conv3_1_sub4 = resize_bilinear(conv3_1, 1/2)
             OUT("conv3_1_sub4");
@@ -900,7 +906,7 @@ const float *F(const void *p) { return static_cast<const float *>(p); }
 struct HeadDepth {
     using Ws = IcnetHeadWs;
     static constexpr int kUnit = 8, kLevel = 0;
-    static constexpr bool kK1 = true, kIncrease = true, kReduce = true;
+    static constexpr bool kK1 = true, kIncrease = true, kReduce = true, kBlock2 = true;
     static constexpr bool kStats = false, kFrame = false, kImagesQueryFits = false;
     static constexpr const char *kNoun = "head gradient kernel's", *kEndpoints[] = {"sub12_sum"};
 
@@ -932,7 +938,7 @@ struct HeadDepth {
 struct FusionDepth {
     using Ws = IcnetFusionWs;
     static constexpr int kUnit = 16, kLevel = 1;
-    static constexpr bool kK1 = true, kIncrease = true, kReduce = true;
+    static constexpr bool kK1 = true, kIncrease = true, kReduce = true, kBlock2 = true;
     static constexpr bool kStats = true, kFrame = false, kImagesQueryFits = false;
     static constexpr const char *kNoun = "fusion gradient kernels'", *kEndpoints[] = {"sub24_sum", "conv3_sub1"};
 
@@ -978,7 +984,7 @@ struct FusionDepth {
 struct CascadeDepth {
     using Ws = IcnetCascadeWs;
     static constexpr int kUnit = 32, kLevel = 2;
-    static constexpr bool kK1 = true, kIncrease = true, kReduce = true;
+    static constexpr bool kK1 = true, kIncrease = true, kReduce = true, kBlock2 = true;
     static constexpr bool kStats = true, kFrame = false, kImagesQueryFits = false;
     static constexpr const char *kNoun = "cascade gradient kernels'", *kEndpoints[] = {"conv5_4_k1", "conv3_1", "conv3_sub1"};
 
@@ -1024,7 +1030,7 @@ struct CascadeDepth {
 struct HighresDepth {
     using Ws = IcnetHighresWs;
     static constexpr int kUnit = 32, kLevel = 3;
-    static constexpr bool kK1 = true, kIncrease = true, kReduce = true;
+    static constexpr bool kK1 = true, kIncrease = true, kReduce = true, kBlock2 = true;
     static constexpr bool kStats = true, kFrame = true, kImagesQueryFits = true;
     static constexpr const char *kNoun = "high-resolution gradient kernels'", *kEndpoints[] = {"conv5_4_k1", "conv3_1"};
 
@@ -1075,7 +1081,7 @@ struct HighresDepth {
 struct PyramidDepth {
     using Ws = IcnetPyramidWs;
     static constexpr int kUnit = 32, kLevel = 2;
-    static constexpr bool kK1 = false, kIncrease = true, kReduce = true;
+    static constexpr bool kK1 = false, kIncrease = true, kReduce = true, kBlock2 = true;
     static constexpr bool kStats = true, kFrame = false, kImagesQueryFits = false;
     static constexpr const char *kNoun = "pyramid gradient kernels'", *kEndpoints[] = {"conv5_3_sum", "conv3_1", "conv3_sub1"};
 
@@ -1118,7 +1124,7 @@ struct PyramidDepth {
 struct PoolDepth {
     using Ws = IcnetPoolWs;
     static constexpr int kUnit = 32, kLevel = 2;
-    static constexpr bool kK1 = false, kIncrease = false, kReduce = true;
+    static constexpr bool kK1 = false, kIncrease = false, kReduce = true, kBlock2 = true;
     static constexpr bool kStats = true, kFrame = false, kImagesQueryFits = false;
     static constexpr const char *kNoun = "pooling gradient kernels'",
                                 *kEndpoints[] = {"conv5_3_3x3", "conv5_2", "conv3_1", "conv3_sub1"};
@@ -1170,7 +1176,7 @@ struct PoolDepth {
 struct BneckDepth {
     using Ws = IcnetBneckWs;
     static constexpr int kUnit = 32, kLevel = 2;
-    static constexpr bool kK1 = false, kIncrease = false, kReduce = false;
+    static constexpr bool kK1 = false, kIncrease = false, kReduce = false, kBlock2 = true;
     static constexpr bool kStats = true, kFrame = false, kImagesQueryFits = false;
     static constexpr const char *kNoun = "bottleneck gradient kernels'", *kEndpoints[] = {"conv5_2", "conv3_1", "conv3_sub1"};
 
@@ -1207,6 +1213,52 @@ struct BneckDepth {
     {
         return launch_icnet_bneck_grad(F(in.f[0]), F(in.f[1]), F(in.f[2]), in.n, in.h, in.w, in.classes, in.params, in.stats,
                                        a.labels, a.mask, a.weight, a.label_smoothing, in.max_workgroups, t, a.loss, a.grad, a.s);
+    }
+};
+
+// through conv5_2 (kernels: ssal_train_icnet_bneck2.hip): conv5_1 [n,h32,w32,1024] (conv5_2's input and
+// identity shortcut), conv3_1 and conv3_sub1.  Contains the bottleneck depth (head < fusion < cascade < pyramid < pooling <
+// bottleneck < this one).  The trunk of an images entry stops where the bottleneck depth's does, and its low-resolution schedule
+// ends behind conv5_1 (kBlock2 = false); conv5_2's and conv5_3's layers, the pyramid pooling, conv5_4_k1, the two blocks and the
+// head write the endpoints from conv5_2_1x1_reduce on.  The semi-supervised entries are not built yet: there is no target launch.
+struct Bneck2Depth {
+    using Ws = IcnetBneck2Ws;
+    static constexpr int kUnit = 32, kLevel = 2;
+    static constexpr bool kK1 = false, kIncrease = false, kReduce = false, kBlock2 = false;
+    static constexpr bool kStats = true, kFrame = false, kImagesQueryFits = false;
+    static constexpr const char *kNoun = "deep bottleneck gradient kernels'", *kEndpoints[] = {"conv5_1", "conv3_1", "conv3_sub1"};
+
+    static Ws carve(Bump &b, int64_t n, int h32, int w32, int classes, bool own_acts)
+    {
+        Ws t;
+        const int64_t pix = n * h32 * (int64_t)w32;
+        t.wt_r = b.take<float>(BK_CIN * BK_C);
+        t.wt_3 = b.take<float>(9 * BK_C * BK_C);
+        t.wt_i = b.take<float>(PO_CIN * PO_CO);
+        t.rows = b.take<float>(B2_ROWS);
+        t.rd = own_acts ? b.take<float>(pix * BK_C) : nullptr;
+        t.a33 = own_acts ? b.take<float>(pix * BK_C) : nullptr;
+        t.c52 = own_acts ? b.take<float>(pix * BK_CIN) : nullptr;
+        t.g52 = b.take<float>(pix * BK_CIN);
+        t.bneck = BneckDepth::carve(b, n, h32, w32, classes, own_acts);  // (conv5_2's backward reuses its g3, gr, partials and folds)
+        return t;
+    }
+    static void bind(Ws &t, const IcWorkspace &W)
+    {
+        t.rd = W.act.at("conv5_2_1x1_reduce");
+        t.a33 = W.act.at("conv5_2_3x3");
+        t.c52 = W.act.at("conv5_2");
+        BneckDepth::bind(t.bneck, W);
+    }
+    static bool fits(int n, int h32, int w32) { return BneckDepth::fits(n, h32, w32); }
+    static hipError_t targets(const DepthIn &, const Ws &, const IcnetHeadSemi &, uint8_t *, hipStream_t)
+    {
+        return hipErrorNotSupported;  // (no entry hands this depth a SemiArgs)
+    }
+    static hipError_t grad(const DepthIn &in, const CallArgs &a, const Ws &t, const IcnetHeadSemi *)
+    {
+        return launch_icnet_bneck2_grad(F(in.f[0]), F(in.f[1]), F(in.f[2]), in.n, in.h, in.w, in.classes, in.params, in.stats,
+                                        a.labels, a.mask, a.weight, a.label_smoothing, in.max_workgroups, t, a.loss, a.grad, a.s);
     }
 };
 
@@ -1310,13 +1362,14 @@ int images_entry(ssal_icnet *net, const void *x_dev, const void *x_raw_dev, int 
     // the frozen trunk, on the undistorted (of_raw) or the training frames, through the same slots of W.  It ends in front of the
     // layers being trained: run_trunk without the head, and from level 1 / 2 / 3 on without the last fusion stage / the first
     // one / the high-resolution branch; without conv5_4_k1 where the depth trains it (kK1), and from conv5_3's increase layer on
-    // where it trains that (kIncrease), and from conv5_3's reduce layer on where it trains the whole bottleneck (kReduce)
+    // where it trains that (kIncrease), from conv5_3's reduce layer on where it trains the whole bottleneck (kReduce), and from
+    // conv5_2's reduce layer on where it trains that block too (kBlock2)
     hipStream_t s = a.s;
     auto trunk = [=, &W](bool of_raw) -> int {
         std::vector<Grp> one(1);
         one[0] = {W, of_raw ? x_raw_dev : x_dev, n, s};
         HIP_TRY(run_trunk(net, one, x_is_u8 != 0, h, w, true, nullptr, false, D::kLevel < 1, D::kLevel < 2, D::kLevel < 3,
-                          SSAL_ARITH_F32, D::kK1, D::kIncrease, D::kReduce));
+                          SSAL_ARITH_F32, D::kK1, D::kIncrease, D::kReduce, D::kBlock2));
         return SSAL_OK;
     };
     return depth_run<D>(trunk, in, a, semi, c);
@@ -1458,6 +1511,16 @@ HostUpdates bneck_tensors(const float *p, int K)
                  {"conv5_3_1x1_reduce.beta", p + BK_BR, BK_C}, {"conv5_3_3x3.kernel", p + BK_K3, 9 * BK_C * BK_C},
                  {"conv5_3_3x3.gamma", p + BK_G3, BK_C}, {"conv5_3_3x3.beta", p + BK_B3, BK_C}},
                 pool_tensors(p + BK_POOL, K));
+}
+
+HostUpdates bneck2_tensors(const float *p, int K)
+{
+    return then({{"conv5_2_1x1_reduce.kernel", p + B2_KR, B2_GR}, {"conv5_2_1x1_reduce.gamma", p + B2_GR, BK_C},
+                 {"conv5_2_1x1_reduce.beta", p + B2_BR, BK_C}, {"conv5_2_3x3.kernel", p + B2_K3, 9 * BK_C * BK_C},
+                 {"conv5_2_3x3.gamma", p + B2_G3, BK_C}, {"conv5_2_3x3.beta", p + B2_B3, BK_C},
+                 {"conv5_2_1x1_increase.kernel", p + B2_KI, PO_CIN * PO_CO}, {"conv5_2_1x1_increase.gamma", p + B2_GI, PO_CO},
+                 {"conv5_2_1x1_increase.beta", p + B2_BI, PO_CO}},
+                bneck_tensors(p + B2_BNECK, K));
 }
 
 }  // namespace
@@ -1796,6 +1859,46 @@ SSAL_API int ssal_icnet_update_bneck(ssal_icnet *net, const float *params_host, 
     return update_packed(net, bneck_tensors(params_host, net->classes),
                          {"conv5_3_1x1_reduce", "conv5_3_3x3", "conv5_3_1x1_increase", "conv5_4_k1", "conv_sub4", "conv3_1_sub2_proj",
                           "conv_sub2", "conv3_sub1_proj", "conv6_cls"}, stream);
+}
+
+// ---- through conv5_2: the last bottleneck but one, and everything the bottleneck entries train ----
+SSAL_API int64_t ssal_icnet_bneck2_grad_workspace_bytes(int n, int h, int w, int classes)
+{
+    return features_query<Bneck2Depth>(n, h, w, classes, false, false);
+}
+
+SSAL_API int ssal_icnet_bneck2_grad_nhwc(const float *conv5_1_dev, const float *conv3_1_dev, const float *conv3_sub1_dev, int n,
+                                         int h, int w, int classes, const float *params_dev, const uint8_t *labels_dev,
+                                         const float *mask_dev, float weight, float label_smoothing, const float *stats_dev,
+                                         int max_workgroups, double *loss_dev, float *grad_dev, void *ws_dev, int64_t ws_bytes,
+                                         void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return features_entry<Bneck2Depth>({{conv5_1_dev, conv3_1_dev, conv3_sub1_dev}, {}, params_dev, stats_dev, max_workgroups, n, h,
+                                        w, classes}, a, nullptr);
+}
+
+SSAL_API int64_t ssal_icnet_train_bneck2_workspace_bytes(const ssal_icnet *net, int n, int h, int w)
+{
+    return images_query<Bneck2Depth>(net, n, h, w, false, false);
+}
+
+SSAL_API int ssal_icnet_train_bneck2_nhwc(ssal_icnet *net, const void *x_dev, int x_is_u8, int n, int h, int w,
+                                          const uint8_t *labels_dev, const float *mask_dev, const float *params_dev, float weight,
+                                          float label_smoothing, const float *stats_dev, int max_workgroups, double *loss_dev,
+                                          float *grad_dev, void *ws_dev, int64_t ws_bytes, void *stream)
+{
+    const CallArgs a = {labels_dev, mask_dev, weight, label_smoothing, loss_dev, grad_dev, ws_dev, ws_bytes, (hipStream_t)stream};
+    return images_entry<Bneck2Depth>(net, x_dev, nullptr, x_is_u8, n, h, w, params_dev, stats_dev, max_workgroups, a, nullptr);
+}
+
+SSAL_API int ssal_icnet_update_bneck2(ssal_icnet *net, const float *params_host, void *stream)
+{
+    if (!net || !params_host) return fail(SSAL_EINVAL, "NULL argument");
+    return update_packed(net, bneck2_tensors(params_host, net->classes),
+                         {"conv5_2_1x1_reduce", "conv5_2_3x3", "conv5_2_1x1_increase", "conv5_3_1x1_reduce", "conv5_3_3x3",
+                          "conv5_3_1x1_increase", "conv5_4_k1", "conv_sub4", "conv3_1_sub2_proj", "conv_sub2", "conv3_sub1_proj",
+                          "conv6_cls"}, stream);
 }
 
 // ---- the high-resolution branch down to the image ----

@@ -58,6 +58,26 @@ struct IcnetBneckWs {
     IcnetPoolWs pool;
 };
 
+// The backward of one Bneck(256, 1024, 1, 4) below its output gradient, as a link of a chain: the data
+// gradient through the increase layer (k_icnet_bneck_dx_inc), the 3 x 3 weight gradient with its finish and gamma, the data
+// gradient through the dilated 3 x 3 (k_icnet_bneck_dx_3x3) and the reduce layer's weight gradient
+// (launch_icnet_wgrad_1024x256), in that order.  The increase layer's own weight gradient is the caller's.  What a block hands
+// over: gr, un-normalised behind the reduce layer's ReLU -- the data gradient onto the block's input is the next depth's.
+struct IcnetBneckLink {
+    const float *x;                           // [N, h32, w32, 1024]  the block's input
+    const float *rd, *a33;                    // [N, h32, w32, 256]   its stored 1x1_reduce and 3x3 (the fp32 forward values)
+    const float *gout;                        // [N, h32, w32, 1024]  un-normalised dL/d(block output) behind its ReLU
+    const float *Ki, *s_i;                    // the increase kernel [256][1024], its batch-norm scale [1024]
+    const float *K3, *s_3, *mean_3, *var_3;   // the 3 x 3 kernel [9][256][256], its scale and moving statistics [256]
+    const float *Kr, *s_r, *mean_r, *var_r;   // the reduce kernel [1024][256], its scale and moving statistics [256]
+    const float *scale;                       // [1]  1 / sum(mask)
+    float *g3, *gr, *part3, *fold3, *partr, *foldr;    // IcnetBneckWs's pieces of those names
+    float *gK3, *gG3, *gB3, *gKr, *gGr, *gBr;          // the six gradient slots
+    // the profile's names: dx_inc, wgrad3, finish3, gamma3, dx_3x3, then the reduce layer's wgrad, finish, gamma
+    const char *const *names;
+};
+hipError_t launch_icnet_bneck_link(const IcnetBneckLink &L, int N, int h32, int w32, int max_workgroups, hipStream_t s);
+
 // loss [1] float64; grad [icnet_bneck_floats(K)] fp32 in the packed order
 hipError_t launch_icnet_bneck_grad(const float *c52, const float *c31, const float *c3, int N, int h32, int w32, int K,
                                    const float *params, const float *stats, const uint8_t *labels, const float *mask,

@@ -12,6 +12,8 @@
 //   k_icnet_bneck_dx_3x3    the data gradient through the dilated 3 x 3 as an implicit GEMM over a tile window with four pixels
 //                           of halo, the ReLU mask of conv5_3_1x1_reduce in the epilogue: gr = relu'(r) (sum_tap (s_3 g3) K_3^T)
 //   k_icnet_pyramid_wgrad<1024, 256>, its finish and gamma (ssal_train_icnet_pyramid.hip; the profile's k_icnet_bneck_wgrad_r, ...)
+// The backward launches stand in launch_icnet_bneck_link, the block's backward below its output gradient: conv5_3's here,
+// conv5_2's in ssal_train_icnet_bneck2.hip.
 // g3 and gr are un-normalised and WITHOUT their layers' batch-norm scales: each finish kernel applies both once.  No
 // floating-point atomics, no inline assembly, 64-bit offsets, grids strided over the tiles: two runs give the same bits.
 #include "ssal_icnet.h"
@@ -308,14 +310,58 @@ __global__ __launch_bounds__(256) void k_icnet_bneck_gamma3(const float *__restr
     gG[co] = icnet_dgamma(icnet_gamma_3x3(K, fold, BK_C, BK_C, co), mean[co], var[co], fold[9 * BK_C * BK_C + co], scale_p[0]);
 }
 
+// The launches of one block's backward below its output gradient (ssal_train_icnet_bneck.h): conv5_3's here, conv5_2's in
+// ssal_train_icnet_bneck2.hip
+hipError_t launch_icnet_bneck_link(const IcnetBneckLink &L, int N, int h32, int w32, int max_workgroups, hipStream_t s)
+{
+    const long pixels = (long)N * h32 * w32;
+    const double pix32 = (double)pixels;
+    constexpr int K3 = 9 * BK_C * BK_C;
+    hipError_t e;
+    {
+        const int G = icnet_grid(icnet_cdiv(pixels, BK_DI_PT), BK_DX_MAX_WG, max_workgroups);
+        ProfScope prof(L.names[0], 2.0 * pix32 * PO_CIN * PO_CO,
+                       4.0 * pix32 * (2.0 * PO_CO + 2.0 * PO_CIN) + 4.0 * (double)icnet_cdiv(pixels, BK_DI_PT) * PO_CIN * PO_CO, s);
+        hipLaunchKernelGGL(k_icnet_bneck_dx_inc, dim3(G, BK_C / 128), dim3(256), 0, s, L.gout, L.Ki, L.s_i, L.a33, pixels, L.g3);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    const int G3 = icnet_grid(icnet_cdiv(pixels, PY_PT), BK_W3_MAX_WG, max_workgroups);
+    {
+        ProfScope prof(L.names[1], 2.0 * pix32 * BK_PART3, 4.0 * pix32 * 18.0 * BK_C + 4.0 * G3 * BK_PART3, s);
+        hipLaunchKernelGGL(k_icnet_bneck_wgrad3, dim3(G3, 18, BK_C / 128), dim3(256), 0, s, L.rd, L.g3, N, h32, w32, L.part3);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    {
+        ProfScope prof(L.names[2], (double)G3 * BK_PART3, 4.0 * (G3 + 2.0) * BK_PART3, s);
+        hipLaunchKernelGGL(k_icnet_bneck_finish3, dim3(icnet_cdiv(BK_PART3, 256)), dim3(256), 0, s, L.part3, G3, L.scale, L.s_3,
+                           L.fold3, L.gK3, L.gB3);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    {
+        ProfScope prof(L.names[3], 2.0 * K3, 8.0 * BK_PART3, s);
+        hipLaunchKernelGGL(k_icnet_bneck_gamma3, dim3(1), dim3(256), 0, s, L.fold3, L.scale, L.K3, L.mean_3, L.var_3,
+                           L.gG3);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    {
+        const long tiles = (long)N * icnet_cdiv(h32, BK_T) * icnet_cdiv(w32, BK_T);
+        const int G = icnet_grid(tiles, BK_DX_MAX_WG, max_workgroups);
+        ProfScope prof(L.names[4], 2.0 * pix32 * K3,
+                       4.0 * pix32 * 3.0 * BK_C + 4.0 * (double)tiles * (K3 + 2.0 * (B3_WIN * B3_WIN - BK_T * BK_T) * BK_C), s);
+        hipLaunchKernelGGL(k_icnet_bneck_dx_3x3, dim3(G, BK_C / 128), dim3(256), 0, s, L.g3, L.K3, L.s_3, L.rd, N, h32, w32,
+                           L.gr);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    return launch_icnet_wgrad_1024x256(L.x, L.gr, pixels, max_workgroups, L.scale, L.s_r, L.Kr, L.mean_r, L.var_r, L.partr, L.foldr,
+                                       L.gKr, L.gGr, L.gBr, s, L.names + 5);
+}
+
 hipError_t launch_icnet_bneck_grad(const float *c52, const float *c31, const float *c3, int N, int h32, int w32, int K,
                                    const float *params, const float *stats, const uint8_t *labels, const float *mask,
                                    float weight, float label_smoothing, int max_workgroups, const IcnetBneckWs &ws, double *loss,
                                    float *grad, hipStream_t s)
 {
     if (N < 1 || K < 2 || K > 32 || max_workgroups < 0 || !icnet_bneck_fits(h32, w32)) return hipErrorInvalidValue;
-    const long pixels = (long)N * h32 * w32;
-    const double pix32 = (double)pixels;
     constexpr int K3 = 9 * BK_C * BK_C;
     const float *s_r = ws.rows, *s_3 = ws.rows + 2 * BK_C;
     hipError_t e;
@@ -336,44 +382,15 @@ hipError_t launch_icnet_bneck_grad(const float *c52, const float *c31, const flo
                                label_smoothing, max_workgroups, ws.pool, loss, grad + BK_POOL, s);
     if (e != hipSuccess) return e;
     const float *scale = ws.pool.pyramid.cascade.fusion.fold + FU_PART;  // 1 / sum(mask), as the fusion trainer's finish left it
-    // ---- backward ----
-    {
-        const int G = icnet_grid(icnet_cdiv(pixels, BK_DI_PT), BK_DX_MAX_WG, max_workgroups);
-        ProfScope prof("k_icnet_bneck_dx_inc", 2.0 * pix32 * PO_CIN * PO_CO,
-                       4.0 * pix32 * (2.0 * PO_CO + 2.0 * PO_CIN) + 4.0 * (double)icnet_cdiv(pixels, BK_DI_PT) * PO_CIN * PO_CO, s);
-        hipLaunchKernelGGL(k_icnet_bneck_dx_inc, dim3(G, BK_C / 128), dim3(256), 0, s, ws.pool.g53, params + BK_POOL + PO_K,
-                           ws.pool.rows, ws.a33, pixels, ws.g3);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    const int G3 = icnet_grid(icnet_cdiv(pixels, PY_PT), BK_W3_MAX_WG, max_workgroups);
-    {
-        ProfScope prof("k_icnet_bneck_wgrad3", 2.0 * pix32 * BK_PART3, 4.0 * pix32 * 18.0 * BK_C + 4.0 * G3 * BK_PART3, s);
-        hipLaunchKernelGGL(k_icnet_bneck_wgrad3, dim3(G3, 18, BK_C / 128), dim3(256), 0, s, ws.rd, ws.g3, N, h32, w32, ws.part3);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    {
-        ProfScope prof("k_icnet_bneck_finish3", (double)G3 * BK_PART3, 4.0 * (G3 + 2.0) * BK_PART3, s);
-        hipLaunchKernelGGL(k_icnet_bneck_finish3, dim3(icnet_cdiv(BK_PART3, 256)), dim3(256), 0, s, ws.part3, G3, scale, s_3,
-                           ws.fold3, grad + BK_K3, grad + BK_B3);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    {
-        ProfScope prof("k_icnet_bneck_gamma3", 2.0 * K3, 8.0 * BK_PART3, s);
-        hipLaunchKernelGGL(k_icnet_bneck_gamma3, dim3(1), dim3(256), 0, s, ws.fold3, scale, params + BK_K3, stats + 2 * BK_C,
-                           stats + 3 * BK_C, grad + BK_G3);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    {
-        const long tiles = (long)N * icnet_cdiv(h32, BK_T) * icnet_cdiv(w32, BK_T);
-        const int G = icnet_grid(tiles, BK_DX_MAX_WG, max_workgroups);
-        ProfScope prof("k_icnet_bneck_dx_3x3", 2.0 * pix32 * K3,
-                       4.0 * pix32 * 3.0 * BK_C + 4.0 * (double)tiles * (K3 + 2.0 * (B3_WIN * B3_WIN - BK_T * BK_T) * BK_C), s);
-        hipLaunchKernelGGL(k_icnet_bneck_dx_3x3, dim3(G, BK_C / 128), dim3(256), 0, s, ws.g3, params + BK_K3, s_3, ws.rd, N, h32,
-                           w32, ws.gr);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    return launch_icnet_wgrad_1024x256(c52, ws.gr, pixels, max_workgroups, scale, s_r, params + BK_KR, stats, stats + BK_C,
-                                       ws.partr, ws.foldr, grad + BK_KR, grad + BK_GR, grad + BK_BR, s);
+    // ---- backward: conv5_3 as a link ----
+    static const char *const names[] = {"k_icnet_bneck_dx_inc", "k_icnet_bneck_wgrad3", "k_icnet_bneck_finish3", "k_icnet_bneck_gamma3",
+                                        "k_icnet_bneck_dx_3x3", "k_icnet_bneck_wgrad_r", "k_icnet_bneck_finish_r",
+                                        "k_icnet_bneck_gamma_r"};
+    const IcnetBneckLink L = {c52, ws.rd, ws.a33, ws.pool.g53, params + BK_POOL + PO_K, ws.pool.rows, params + BK_K3, s_3,
+                              stats + 2 * BK_C, stats + 3 * BK_C, params + BK_KR, s_r, stats, stats + BK_C, scale, ws.g3, ws.gr,
+                              ws.part3, ws.fold3, ws.partr, ws.foldr, grad + BK_K3, grad + BK_G3, grad + BK_B3, grad + BK_KR,
+                              grad + BK_GR, grad + BK_BR, names};
+    return launch_icnet_bneck_link(L, N, h32, w32, max_workgroups, s);
 }
 
 }  // namespace ssal

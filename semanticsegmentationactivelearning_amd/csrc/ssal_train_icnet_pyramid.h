@@ -52,13 +52,17 @@ hipError_t launch_icnet_pyramid_grad(const float *c53, const float *c31, const f
 // max_workgroups lowers G only, 16 G workgroups run.
 hipError_t launch_icnet_wgrad_256x1024(const float *x, const float *g, long pixels, int max_workgroups, const float *scale,
                                        const float *sl, const float *K, const float *mean, const float *var, float *part,
-                                       float *fold, float *gK, float *gG, float *gB, hipStream_t s);
+                                       float *fold, float *gK, float *gG, float *gB, hipStream_t s,
+                                       const char *const *names = nullptr);
 
 // the same three kernels at 1024 x 256 (conv5_4_k1's own instantiations) for conv5_3's reduce layer (the
 // profile's k_icnet_bneck_wgrad_r / _finish_r / _gamma_r): x [pixels, 1024], g [pixels, 256], sl / mean / var [256], K [1024][256]
 // -> part [PY_MAX_WG][PY_PART], fold [PY_PART], gK [1024][256], gG, gB [256].  Grid (G, 8, 2): max_workgroups lowers G only.
+// names (either launcher): the profile's names of the three launches where a further layer of the shape runs them (DESIGN.md
+// section 43), else the ones above.
 hipError_t launch_icnet_wgrad_1024x256(const float *x, const float *g, long pixels, int max_workgroups, const float *scale,
                                        const float *sl, const float *K, const float *mean, const float *var, float *part,
-                                       float *fold, float *gK, float *gG, float *gB, hipStream_t s);
+                                       float *fold, float *gK, float *gG, float *gB, hipStream_t s,
+                                       const char *const *names = nullptr);
 
 }  // namespace ssal

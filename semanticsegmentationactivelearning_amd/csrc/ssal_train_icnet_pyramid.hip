@@ -183,24 +183,24 @@ hipError_t launch_icnet_pyramid_grad(const float *c53, const float *c31, const f
 // finish, its dGamma
 hipError_t launch_icnet_wgrad_256x1024(const float *x, const float *g, long pixels, int max_workgroups, const float *scale,
                                        const float *sl, const float *K, const float *mean, const float *var, float *part,
-                                       float *fold, float *gK, float *gG, float *gB, hipStream_t s)
+                                       float *fold, float *gK, float *gG, float *gB, hipStream_t s, const char *const *names)
 {
     constexpr int CIN = 256, CO = 1024, PART = (CIN + 1) * CO;
     if (pixels < 1 || max_workgroups < 0) return hipErrorInvalidValue;
     hipError_t e;
     const int G = icnet_grid(icnet_cdiv(pixels, PY_PT), PY_MAX_WG, max_workgroups);
     {
-        ProfScope prof("k_icnet_pool_wgrad", 2.0 * (double)pixels * PART, 4.0 * (double)pixels * (CIN + CO) + 4.0 * G * PART, s);
+        ProfScope prof(names ? names[0] : "k_icnet_pool_wgrad", 2.0 * (double)pixels * PART, 4.0 * (double)pixels * (CIN + CO) + 4.0 * G * PART, s);
         hipLaunchKernelGGL((k_icnet_pyramid_wgrad<CIN, CO>), dim3(G, CIN / 128, CO / 128), dim3(256), 0, s, x, g, pixels, part);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     {
-        ProfScope prof("k_icnet_pool_finish", (double)G * PART, 4.0 * (G + 2.0) * PART, s);
+        ProfScope prof(names ? names[1] : "k_icnet_pool_finish", (double)G * PART, 4.0 * (G + 2.0) * PART, s);
         hipLaunchKernelGGL((k_icnet_pyramid_finish<CIN, CO>), dim3(icnet_cdiv(PART, 256)), dim3(256), 0, s, part, G, scale, sl, fold,
                            gK, gB);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    ProfScope prof("k_icnet_pool_gamma", 2.0 * CIN * CO, 8.0 * PART, s);
+    ProfScope prof(names ? names[2] : "k_icnet_pool_gamma", 2.0 * CIN * CO, 8.0 * PART, s);
     hipLaunchKernelGGL((k_icnet_pyramid_gamma<CIN, CO>), dim3(CO / 256), dim3(256), 0, s, fold, scale, K, mean, var, gG);
     return hipGetLastError();
 }
@@ -209,25 +209,25 @@ hipError_t launch_icnet_wgrad_256x1024(const float *x, const float *g, long pixe
 // reduce layer, its fold and finish, its dGamma
 hipError_t launch_icnet_wgrad_1024x256(const float *x, const float *g, long pixels, int max_workgroups, const float *scale,
                                        const float *sl, const float *K, const float *mean, const float *var, float *part,
-                                       float *fold, float *gK, float *gG, float *gB, hipStream_t s)
+                                       float *fold, float *gK, float *gG, float *gB, hipStream_t s, const char *const *names)
 {
     if (pixels < 1 || max_workgroups < 0) return hipErrorInvalidValue;
     hipError_t e;
     const int G = icnet_grid(icnet_cdiv(pixels, PY_PT), PY_MAX_WG, max_workgroups);
     {
-        ProfScope prof("k_icnet_bneck_wgrad_r", 2.0 * (double)pixels * PY_PART, 4.0 * (double)pixels * (PY_CIN + PY_CO) + 4.0 * G * PY_PART,
+        ProfScope prof(names ? names[0] : "k_icnet_bneck_wgrad_r", 2.0 * (double)pixels * PY_PART, 4.0 * (double)pixels * (PY_CIN + PY_CO) + 4.0 * G * PY_PART,
                        s);
         hipLaunchKernelGGL((k_icnet_pyramid_wgrad<PY_CIN, PY_CO>), dim3(G, PY_CIN / 128, PY_CO / 128), dim3(256), 0, s, x, g, pixels,
                            part);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     {
-        ProfScope prof("k_icnet_bneck_finish_r", (double)G * PY_PART, 4.0 * (G + 2.0) * PY_PART, s);
+        ProfScope prof(names ? names[1] : "k_icnet_bneck_finish_r", (double)G * PY_PART, 4.0 * (G + 2.0) * PY_PART, s);
         hipLaunchKernelGGL((k_icnet_pyramid_finish<PY_CIN, PY_CO>), dim3(icnet_cdiv(PY_PART, 256)), dim3(256), 0, s, part, G, scale, sl,
                            fold, gK, gB);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    ProfScope prof("k_icnet_bneck_gamma_r", 2.0 * PY_G, 8.0 * PY_PART, s);
+    ProfScope prof(names ? names[2] : "k_icnet_bneck_gamma_r", 2.0 * PY_G, 8.0 * PY_PART, s);
     hipLaunchKernelGGL((k_icnet_pyramid_gamma<PY_CIN, PY_CO>), dim3(PY_CO / 256), dim3(256), 0, s, fold, scale, K, mean, var, gG);
     return hipGetLastError();
 }

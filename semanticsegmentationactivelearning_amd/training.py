@@ -1940,6 +1940,75 @@ class ICNetBottleneckTrainer(ICNetPoolingTrainer):
                                       return_pseudo_pixels=return_pseudo_pixels)
 
 
+# ---- ICNet through conv5_2: the last bottleneck but one under the bottleneck trainer ----------------------
+_BNECK2_LAYERS = ("conv5_2_1x1_reduce", "conv5_2_3x3", "conv5_2_1x1_increase")
+_BNECK2_VARS = tuple((layer, attr, attr == "kernel") for layer in _BNECK2_LAYERS for attr in ("kernel", "gamma", "beta")) + _BNECK_VARS
+# rows of mixed widths (four of 256, two of 1024, then the bottleneck trainer's), concatenated unpadded
+_BNECK2_STATS = tuple((layer, attr) for layer in _BNECK2_LAYERS for attr in ("mean", "variance")) + _BNECK_STATS
+
+
+class ICNetDeepBottleneckTrainer(ICNetBottleneckTrainer):
+    """Adam on ``conv5_2`` and ``conv5_3``, the backbone's last two bottlenecks (ICNET_SPEC section 2): ``conv5_2_1x1_reduce``
+    (1 x 1, 1024 -> 256), ``conv5_2_3x3`` (3 x 3 at dilation 4, 256 -> 256) and ``conv5_2_1x1_increase`` (1 x 1, 256 -> 1024,
+    + ``conv5_1``), each with batch-norm and a ReLU, under everything ``ICNetBottleneckTrainer`` trains.  Frozen
+    (``training=False``): everything up to and including ``conv5_1`` [N, H/32, W/32, 1024] -- the block's input and identity
+    shortcut --, ``conv3_1`` [N, H/16, W/16, 256] and ``conv3_sub1`` [N, H/8, W/8, 64]; nothing below them gets a gradient.
+    Batch-norm, hyper-parameters, Adam and the refusals are the parent's; the ``l1_l2`` regulariser goes to the twelve kernels
+    only.
+
+    The 35 variables travel as one packed float32 vector in the order of ``variable_names``: the reduce layer's three, the
+    3 x 3's three, the increase layer's three, then the parent's 26 in the parent's order.  The semi-supervised keywords are
+    refused."""
+
+    _C_FEATURES = ("ssal_icnet_bneck2_grad", None)
+    _C_IMAGES = ("ssal_icnet_train_bneck2", None)
+    _CHANNELS, _UP = 1024, 32
+    _VARS, _STATS, _C_UPDATE = _BNECK2_VARS, _BNECK2_STATS, "ssal_icnet_update_bneck2"
+    variable_names = ["%s.%s" % (layer, attr) for layer, attr, _ in _BNECK2_VARS]
+
+    _SEMI_NOUN = "ICNet's deep bottleneck trainer"
+    _FEATURE_NAMES = ("conv5_1", "conv3_1", "conv3_sub1")
+
+    def _check_features(self, conv5_1, conv3_1, conv3_sub1, labels, mask, max_workgroups):
+        mw = self._check_call(conv5_1, 32, labels, mask, max_workgroups, 1024)
+        n, h, w, _ = tuple(np.shape(conv5_1))
+        for name, t, want in (("conv3_1", conv3_1, (n, 2 * h, 2 * w, 256)), ("conv3_sub1", conv3_sub1, (n, 4 * h, 4 * w, 64))):
+            if tuple(np.shape(t)) != want:
+                raise ValueError("%s must be %s for conv5_1 %s (got %s)" % (name, want, (n, h, w, 1024), tuple(np.shape(t))))
+            dt = str(getattr(t, "dtype", ""))
+            if "float" not in dt:
+                raise ValueError("%s must be a floating-point tensor (got %s)" % (name, dt or type(t).__name__))
+        return mw
+
+    def gradient_features(self, conv5_1, conv3_1, conv3_sub1, labels, mask, params=None, max_workgroups=0, labelled=None,
+                          confusion=None, return_pseudo_pixels=False):
+        """(loss float64 [1], {name: gradient} for ``variable_names``) on the device for ``conv5_1`` [N, h, w, 1024],
+        ``conv3_1`` [N, 2h, 2w, 256], ``conv3_sub1`` [N, 4h, 4w, 64] and labels / mask [N, 32h, 32w].  ``params`` overrides
+        any of the 35 tensors; ``max_workgroups``: 0 = the default grids, a tuning knob.  No update."""
+        return self._gradient_from((conv5_1, conv3_1, conv3_sub1), labels, mask, params, max_workgroups, labelled=labelled,
+                                   confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
+
+    def features(self, images):
+        """``(conv5_1 [N, H/32, W/32, 1024], conv3_1 [N, H/16, W/16, 256], conv3_sub1 [N, H/8, W/8, 64])`` for ``images``
+        (copies): what ``step_features`` and ``gradient_features`` take.  One forward pass of the frozen layers."""
+        self.net(images, training=False)
+        return tuple(self.net.endpoint(name).clone() for name in self._FEATURE_NAMES)
+
+    def step_features(self, conv5_1, conv3_1, conv3_sub1, labels, mask, max_workgroups=0, labelled=None, confusion=None,
+                      return_pseudo_pixels=False):
+        """one Adam step from cached features; returns the loss (float64 device scalar) BEFORE the step"""
+        return self._step_from((conv5_1, conv3_1, conv3_sub1), labels, mask, max_workgroups, labelled=labelled,
+                               confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
+
+    def step(self, images, labels, mask, max_workgroups=0, labelled=None, confusion=None, return_pseudo_pixels=False):
+        """one Adam step from images [N, H, W, C] (fp32 or decoded uint8) and labels / mask [N, H, W]: the frozen trunk up to
+        ``conv5_1``, ``conv3_1`` and ``conv3_sub1``, then the three layers of ``conv5_2`` and of ``conv5_3``, the pyramid
+        pooling, ``conv5_4_k1``, both fusion blocks and the head on the weights being trained, their gradient kernels, Adam.
+        Returns the loss (float64 device scalar) before the step."""
+        return self._step_from_images(images, labels, mask, max_workgroups, labelled=labelled, confusion=confusion,
+                                      return_pseudo_pixels=return_pseudo_pixels)
+
+
 # ---- the semi-supervised step of ICNet's fusion and cascade trainers (DESIGN.md section 30) --------------------------------------
 class SemiSupervisedICNetFusionTrainer(_SemiKeywords, ICNetFusionTrainer):
     """``ICNetFusionTrainer`` with the reference's semi-supervised step (active_learning.py:226-275, 339-342) built into the
@@ -2057,4 +2126,5 @@ __all__ = ["FinalLayerTrainer", "LastBlockTrainer", "LastStageTrainer", "Decoder
            "DecoderTrainer", "SemiSupervisedDecoderTrainer", "ICNetHeadTrainer", "SemiSupervisedICNetHeadTrainer",
            "ICNetFusionTrainer", "ICNetCascadeTrainer", "SemiSupervisedICNetFusionTrainer",
            "SemiSupervisedICNetCascadeTrainer", "ICNetHighResTrainer", "SemiSupervisedICNetHighResTrainer",
-           "ICNetPyramidTrainer", "ICNetPoolingTrainer", "ICNetBottleneckTrainer"]
+           "ICNetPyramidTrainer", "ICNetPoolingTrainer", "ICNetBottleneckTrainer",
+           "ICNetDeepBottleneckTrainer"]

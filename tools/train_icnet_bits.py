@@ -18,14 +18,14 @@ judgement, straight through the C ABI on dummy device pointers (nothing is launc
 images entry takes its class count from the handle and judges the frame's size before the depth's limit can be reached, so
 "classes out of range" and "feature map beyond the limit" are recorded for the features entries only.
 
-The three depths without semi-supervised entries, ``ICNetPyramidTrainer``, ``ICNetPoolingTrainer`` and
-``ICNetBottleneckTrainer`` (DESIGN.md sections 39, 41 and 42), are recorded in their plain parts: ``gradient_features``, one ``step``, the two plain size queries, the plain entries'
+The four depths without semi-supervised entries, ``ICNetPyramidTrainer``, ``ICNetPoolingTrainer``,
+``ICNetBottleneckTrainer`` and ``ICNetDeepBottleneckTrainer`` (DESIGN.md sections 39, 41, 42 and 43), are recorded in their plain parts: ``gradient_features``, one ``step``, the two plain size queries, the plain entries'
 refusals.  A depth whose trainer the package under test does not have is left out of the file.
 
-    python tools/train_icnet_bits.py --out profiles/r29_train_icnet_bits.json
+    python tools/train_icnet_bits.py --out profiles/r30_train_icnet_bits.json
     SSAL_LIB_PATH=/path/to/another/libssal_hip.so python tools/train_icnet_bits.py --out other.json
-    python tools/train_icnet_bits.py --compare other.json profiles/r29_train_icnet_bits.json
-    python tools/train_icnet_bits.py --compare other.json profiles/r29_train_icnet_bits.json --depths head,fusion,cascade,highres,pyramid,pool
+    python tools/train_icnet_bits.py --compare other.json profiles/r30_train_icnet_bits.json
+    python tools/train_icnet_bits.py --compare other.json profiles/r30_train_icnet_bits.json --depths head,fusion,cascade,highres,pyramid,pool,bneck
 
 ``--depths`` restricts a comparison to the entries of those depths: a file written by this tool from an earlier tree (copy the
 tool next to that tree's package) has no entry of a depth that tree lacks.
@@ -50,10 +50,11 @@ SECTIONS = ("sha256", "workspace_bytes", "refused")
 SHAPES = [(1, 1, 1), (2, 2, 3), (1, 3, 5)]
 CASES = [(s, mw, k, wl) for s in SHAPES for mw in (1, 2) for k, wl in ((2, (0.0, 0.0)), (19, (1.02, 0.1)))]
 DEPTHS = ("head", "fusion", "cascade", "highres")
-PLAIN_DEPTHS = ("pyramid", "pool", "bneck")  # no semi-supervised entries yet
+PLAIN_DEPTHS = ("pyramid", "pool", "bneck", "bneck2")  # no semi-supervised entries yet
 # feature pointers of the features entry (highres: the frame last)
-FEATS = {"head": 1, "fusion": 2, "cascade": 3, "highres": 3, "pyramid": 3, "pool": 4, "bneck": 3}
-PLAIN_TRAINERS = {"pyramid": "ICNetPyramidTrainer", "pool": "ICNetPoolingTrainer", "bneck": "ICNetBottleneckTrainer"}
+FEATS = {"head": 1, "fusion": 2, "cascade": 3, "highres": 3, "pyramid": 3, "pool": 4, "bneck": 3, "bneck2": 3}
+PLAIN_TRAINERS = {"pyramid": "ICNetPyramidTrainer", "pool": "ICNetPoolingTrainer", "bneck": "ICNetBottleneckTrainer",
+                  "bneck2": "ICNetDeepBottleneckTrainer"}
 
 
 def plain_depths():
@@ -209,6 +210,13 @@ def digests():
             T["bneck"] = (getattr(_training(), PLAIN_TRAINERS["bneck"]), None)
             _record(out, "bneck " + tag, *T["bneck"][0](tb._shared_net(k), 1e-3, **kw).gradient_features(
                 *dev(c52, c31, c3), labels, mask, params=d, max_workgroups=mw))
+        if "bneck2" in plain:
+            import test_gpu_train_icnet_bneck2 as t2
+            import icnet_bneck2_train_oracle as b2
+            c51, c31, c3, d, labels, mask = b2.case(9700 + i, n, h, w, k)
+            T["bneck2"] = (getattr(_training(), PLAIN_TRAINERS["bneck2"]), None)
+            _record(out, "bneck2 " + tag, *T["bneck2"][0](t2._shared_net(k), 1e-3, **kw).gradient_features(
+                *dev(c51, c31, c3), labels, mask, params=d, max_workgroups=mw))
 
         # the images entries, on models of their own (a step writes the trained variables back); frames of 32 h x 32 w for
         # every depth, the trunk's own unit
@@ -291,7 +299,7 @@ def refused():
     dummy = torch.zeros(4096, dtype=torch.uint8, device="cuda")
     P = _lib.dev_ptr(dummy)
     beyond = {"head": (1 << 27) + 1, "fusion": (1 << 26) + 1, "cascade": (1 << 25) + 1, "highres": 512,
-              "pyramid": (1 << 25) + 1, "pool": (1 << 25) + 1, "bneck": (1 << 25) + 1}
+              "pyramid": (1 << 25) + 1, "pool": (1 << 25) + 1, "bneck": (1 << 25) + 1, "bneck2": (1 << 25) + 1}
     out = {}
     for depth in DEPTHS + plain_depths():
         for images in (False, True):
@@ -332,7 +340,7 @@ def refused():
 def depth_of(key):
     """the depth an entry of any section belongs to"""
     import re
-    m = re.match(r"ssal_icnet_(?:train_)?([a-z]+?)_(?:grad|semi|workspace|nhwc)", key)
+    m = re.match(r"ssal_icnet_(?:train_)?([a-z0-9]+?)_(?:grad|semi|workspace|nhwc)", key)
     return m.group(1) if m else key.split(" ", 1)[0]
 
 
