@@ -10,6 +10,8 @@ import warnings
 
 import numpy as np
 
+from . import _icnet_depths
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SSAL_LIB_PATH: measurement builds only (tools/phase_trace.py loads a -DSSAL_PHASE_TRACE build)
 LIB_PATH = os.environ.get("SSAL_LIB_PATH") or os.path.join(_HERE, "libssal_hip.so")
@@ -86,7 +88,8 @@ def arithmetic_code(arithmetic):
 _c = ctypes
 _vp, _i, _i64, _f = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float
 
-# symbol -> (restype, argtypes); one row per declaration in include/ssal_enet.h and include/ssal_icnet.h
+# symbol -> (restype, argtypes); one row per declaration in include/ssal_enet.h and include/ssal_icnet.h (the training entries
+# of ICNet's depths follow the table, generated from the depths' rows)
 PROTOTYPES = {
     "ssal_version": (_c.c_char_p, []),
     "ssal_last_error": (_c.c_char_p, []),
@@ -176,84 +179,6 @@ PROTOTYPES = {
     "ssal_pyramid_pooling": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i64, _vp]),
     "ssal_upscore_workspace_bytes": (_i64, [_i, _i, _i]),
     "ssal_upscore_logits_nhwc": (_i, [_vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
-    # ---- output-layer training of ICNet (include/ssal_icnet.h) ----
-    "ssal_icnet_head_grad_workspace_bytes": (_i64, [_i, _i, _i, _i]),
-    "ssal_icnet_head_grad_nhwc": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _i64, _vp]),
-    "ssal_icnet_train_head_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
-    "ssal_icnet_train_head_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _i64, _vp]),
-    "ssal_icnet_head_grad_semi_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
-    "ssal_icnet_head_grad_semi_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _i, _vp, _vp, _vp,
-                                            _vp, _vp, _i64, _vp]),
-    "ssal_icnet_train_head_semi_workspace_bytes": (_i64, [_vp, _i, _i, _i, _i]),
-    "ssal_icnet_train_head_semi_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _f, _f, _i, _vp,
-                                             _vp, _vp, _vp, _vp, _i64, _vp]),
-    "ssal_icnet_update_head": (_i, [_vp, _vp, _vp, _vp]),
-    # ---- training of ICNet's last fusion stage (include/ssal_icnet.h) ----
-    "ssal_icnet_fusion_grad_workspace_bytes": (_i64, [_i, _i, _i, _i]),
-    "ssal_icnet_fusion_grad_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
-    "ssal_icnet_train_fusion_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
-    "ssal_icnet_train_fusion_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
-    "ssal_icnet_update_fusion": (_i, [_vp, _vp, _vp]),
-    # ---- training of ICNet's whole cascade head (include/ssal_icnet.h) ----
-    "ssal_icnet_cascade_grad_workspace_bytes": (_i64, [_i, _i, _i, _i]),
-    "ssal_icnet_cascade_grad_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64,
-                                          _vp]),
-    "ssal_icnet_train_cascade_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
-    "ssal_icnet_train_cascade_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
-    "ssal_icnet_update_cascade": (_i, [_vp, _vp, _vp]),
-    # ---- training of ICNet's pyramid head: conv5_4_k1 and the cascade head (include/ssal_icnet.h) ----
-    "ssal_icnet_pyramid_grad_workspace_bytes": (_i64, [_i, _i, _i, _i]),
-    "ssal_icnet_pyramid_grad_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64,
-                                          _vp]),
-    "ssal_icnet_train_pyramid_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
-    "ssal_icnet_train_pyramid_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
-    "ssal_icnet_update_pyramid": (_i, [_vp, _vp, _vp]),
-    # ---- training of ICNet through its pyramid pooling: conv5_3's increase layer and the pyramid head ----
-    "ssal_icnet_pool_grad_workspace_bytes": (_i64, [_i, _i, _i, _i]),
-    "ssal_icnet_pool_grad_nhwc": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64,
-                                       _vp]),
-    "ssal_icnet_train_pool_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
-    "ssal_icnet_train_pool_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
-    "ssal_icnet_update_pool": (_i, [_vp, _vp, _vp]),
-    # ---- training of ICNet's last backbone bottleneck: conv5_3's reduce layer and 3 x 3 under the pooling depth ----
-    "ssal_icnet_bneck_grad_workspace_bytes": (_i64, [_i, _i, _i, _i]),
-    "ssal_icnet_bneck_grad_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
-    "ssal_icnet_train_bneck_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
-    "ssal_icnet_train_bneck_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
-    "ssal_icnet_update_bneck": (_i, [_vp, _vp, _vp]),
-    # ---- training of ICNet through conv5_2: the last bottleneck but one under the bottleneck depth ----
-    "ssal_icnet_bneck2_grad_workspace_bytes": (_i64, [_i, _i, _i, _i]),
-    "ssal_icnet_bneck2_grad_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
-    "ssal_icnet_train_bneck2_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
-    "ssal_icnet_train_bneck2_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
-    "ssal_icnet_update_bneck2": (_i, [_vp, _vp, _vp]),
-    # ---- the semi-supervised step of the two (include/ssal_icnet.h) ----
-    "ssal_icnet_fusion_grad_semi_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
-    "ssal_icnet_fusion_grad_semi_nhwc": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _vp, _i,
-                                              _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
-    "ssal_icnet_train_fusion_semi_workspace_bytes": (_i64, [_vp, _i, _i, _i, _i]),
-    "ssal_icnet_train_fusion_semi_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _f, _f, _vp, _i, _vp,
-                                               _vp, _vp, _vp, _vp, _i64, _vp]),
-    "ssal_icnet_cascade_grad_semi_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
-    "ssal_icnet_cascade_grad_semi_nhwc": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _f,
-                                               _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
-    "ssal_icnet_train_cascade_semi_workspace_bytes": (_i64, [_vp, _i, _i, _i, _i]),
-    "ssal_icnet_train_cascade_semi_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _f, _f, _vp, _i, _vp,
-                                                _vp, _vp, _vp, _vp, _i64, _vp]),
-    # ---- training of ICNet's high-resolution branch down to the image (include/ssal_icnet.h) ----
-    "ssal_icnet_highres_grad_workspace_bytes": (_i64, [_i, _i, _i, _i]),
-    "ssal_icnet_highres_grad_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _i, _i, _vp, _vp, _vp,
-                                          _i64, _vp]),
-    "ssal_icnet_train_highres_workspace_bytes": (_i64, [_vp, _i, _i, _i]),
-    "ssal_icnet_train_highres_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
-    "ssal_icnet_update_highres": (_i, [_vp, _vp, _vp]),
-    # ---- its semi-supervised step ----
-    "ssal_icnet_highres_grad_semi_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
-    "ssal_icnet_highres_grad_semi_nhwc": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _f,
-                                               _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
-    "ssal_icnet_train_highres_semi_workspace_bytes": (_i64, [_vp, _i, _i, _i, _i]),
-    "ssal_icnet_train_highres_semi_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _f, _f, _vp, _i, _vp,
-                                                _vp, _vp, _vp, _vp, _i64, _vp]),
     "ssal_icnet_debug_highres_raw_route": (_i, [_i, _i, _i, _i, _c.POINTER(_i)]),
     # ---- PNG decode (include/ssal_enet.h) ----
     "ssal_png_plan": (_i64, [_i64, _vp]),
@@ -342,6 +267,32 @@ PROTOTYPES = {
     "ssal_profile_enable": (_i, [_i]),
     "ssal_profile_collect": (_i, [_c.c_char_p, _i64]),
 }
+
+
+def _icnet_training_prototypes(depth):
+    """the training entries of one depth of ICNet (include/ssal_icnet.h, "Training of ICNet's tail"; the depth's row in
+    ``_icnet_depths.DEPTHS``).  The depths differ in the number of feature pointers, in the stats pointer (every depth but
+    the head) and in the frame's (x_is_u8, c_in) pair where the frame is a feature; a semi entry takes the raw side's pointers
+    after its own, (labelled, measure, threshold) after the mask and (confusion, pseudo pixels) after the gradient."""
+    stem, head = depth.stem, depth.parent is None
+    feats = [_vp] * len(depth.features)
+    knobs = [_f, _f] + ([] if head else [_vp])                                    # weight, label smoothing[, stats]
+    frame = [_i, _i] * sum(f.kind == _icnet_depths.FRAME for f in depth.features)  # x_is_u8, c_in
+    rule, tail = [_vp, _i, _f], [_vp, _i64, _vp]                                  # the workspace, its bytes, the stream
+    out = {"ssal_icnet_update_%s" % stem: (_i, [_vp, _vp] + ([_vp] if head else []) + [_vp])}
+    for semi in (False, True) if depth.semi else (False,):
+        s = "_semi" if semi else ""
+        out["ssal_icnet_%s_grad%s_workspace_bytes" % (stem, s)] = (_i64, [_i] * (5 if semi else 4))
+        out["ssal_icnet_%s_grad%s_nhwc" % (stem, s)] = (_i, feats * (2 if semi else 1) + [_i] * 4 + [_vp] * 3
+                                                        + rule * semi + knobs + frame + [_i] + [_vp] * (4 if semi else 2) + tail)
+        out["ssal_icnet_train_%s%s_workspace_bytes" % (stem, s)] = (_i64, [_vp, _i, _i, _i] + [_i] * semi)
+        out["ssal_icnet_train_%s%s_nhwc" % (stem, s)] = (_i, [_vp, _vp] + [_vp] * semi + [_i] * 4 + [_vp] * 2 + rule * semi
+                                                         + [_vp] + knobs + [_i] + [_vp] * (4 if semi else 2) + tail)
+    return out
+
+
+for _depth in _icnet_depths.DEPTHS.values():
+    PROTOTYPES.update(_icnet_training_prototypes(_depth))
 
 # extra entry points of the measurement libraries only (csrc/ssal_measure_api.h; tools/mem_probe.py, tools/mfma_peak.py)
 MEASURE_PROTOTYPES = {

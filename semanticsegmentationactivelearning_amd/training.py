@@ -14,9 +14,11 @@ inside it: ``labelled`` marks, per image, whether the caller's annotation or the
 confusion matrix and ``return_pseudo_pixels`` the count of pixels the threshold lets through.
 """
 import collections
+import inspect
 
 import numpy as np
 
+from . import _icnet_depths as _depths
 from . import _lib
 from .models.enet import enet_modules as _mod
 
@@ -1048,11 +1050,134 @@ class SemiSupervisedDecoderTrainer(_SemiKeywords, DecoderTrainer):
     targets; ``state`` / ``load_state`` are interchangeable with its."""
 
 
+# ---- ICNet's trainers: a class per depth of ``_icnet_depths.DEPTHS`` (DESIGN.md section 44) --------------------------------------
+# ``@_icnet_depth(stem)`` gives a class what its depth's row states: the class attributes the shared code reads and the public
+# methods ``gradient_features``, ``features``, ``step_features``, ``step`` (and ``gradient`` where the row has it), whose leading
+# parameters are the row's features under their own names.  What a class body still holds is the depth's own.
+def _shape(f, unit=None):
+    """a feature's shape as a docstring writes it: in the first feature's h x w, or (``unit``: the depth's label up-factor) in
+    the frame's H x W"""
+    c = "C_in" if f.channels is None else f.channels
+    if unit is None:
+        m = "" if f.factor == 1 else str(f.factor)
+        return "[N, %sh, %sw, %s]" % (m, m, c)
+    return "[N, H/%d, W/%d, %s]" % (unit // f.factor, unit // f.factor, c)
+
+
+def _listed(words):
+    return ", ".join(words[:-1]) + " and " + words[-1] if len(words) > 1 else words[0]
+
+
+def _method(name, lead, optional, target, feature_names, doc):
+    """the public method ``name(self, *lead, *optional)`` -- ``optional``: (name, default) pairs; every parameter passable by
+    position or by name -- which calls ``self.<target>([the tuple of the parameters feature_names, ]**the others by name)``"""
+    P = inspect.Parameter
+    sig = inspect.Signature([P(n, P.POSITIONAL_OR_KEYWORD) for n in ("self",) + tuple(lead)]
+                            + [P(n, P.POSITIONAL_OR_KEYWORD, default=d) for n, d in optional])
+
+    def method(*args, **kwargs):
+        bound = sig.bind(*args, **kwargs)  # (TypeError for a call the signature does not take, as for any method)
+        bound.apply_defaults()
+        a = bound.arguments
+        self = a.pop("self")
+        feats = tuple(a.pop(n) for n in feature_names)
+        return getattr(self, target)(*((feats,) if feature_names else ()), **a)
+
+    method.__name__, method.__doc__, method.__signature__ = name, doc, sig
+    return method
+
+
+def _public_methods(d, variables, semi):
+    """the public methods of depth ``d`` (a row of ``_icnet_depths.DEPTHS``; ``variables``: its packed (layer, attribute,
+    regularised) rows) as the plain class has them, or with ``semi`` the semi-supervised one"""
+    names = tuple(f.name for f in d.features)
+    maps = [f for f in d.features if f.kind == _depths.MAP]
+    has_frame = len(maps) < len(d.features)
+    layers = list(collections.OrderedDict.fromkeys(layer for layer, _, _ in variables))
+    inputs = ", ".join("``%s`` %s%s" % (f.name, _shape(f), " (fp32 or decoded uint8)" if f.kind == _depths.FRAME else "")
+                       for f in d.features)
+    targets = "labels / mask [N, %dh, %dw]" % (d.up, d.up)
+    trunk = "the frozen trunk up to %s, then %s" % (
+        _listed(["``%s``" % f.name for f in maps]), _listed(["``%s``" % layer for layer in layers]))
+    raw = "``sub12_sum`` of the undistorted frames" if d.parent is None else \
+        "the tuple (%s) of the undistorted frames, given whole or not at all" % ", ".join(n + "_raw" for n in names)
+    if semi:
+        knobs = [("labelled", None), ("measure", None), ("threshold", None), ("features_raw", None), ("confusion", None),
+                 ("return_pseudo_pixels", False)]
+        knobs_doc = ("  The semi-supervised keywords are those of ``FinalLayerTrainer.gradient_features``: ``labelled`` [N], "
+                     "``measure`` / ``threshold`` (defaults: the trainer's), ``features_raw`` (%s), ``confusion`` (int64 [K, K] "
+                     "device tensor, added to), ``return_pseudo_pixels`` (appends the int64 [N] counts to the result)." % raw)
+        again = ("  The keywords are those of ``gradient_features``; with ``return_pseudo_pixels`` the result is ``(loss, "
+                 "pseudo_pixels)``.")
+        raw_frames = ("  ``images_raw``: the undistorted frames (same shape and dtype as ``images``) -- the trunk and the trained "
+                      "layers run on them first and the pseudo annotation comes from their logits (active_learning.py:231).")
+    else:
+        knobs = [("labelled", None), ("confusion", None), ("return_pseudo_pixels", False)]
+        knobs_doc = again = ("  ``labelled``, ``confusion`` and ``return_pseudo_pixels`` are semi-supervised keywords: refused "
+                             "unless left as they are (%s).%s"
+                             % (d.noun, "" if d.semi else "  There is no semi-supervised form yet."))
+        raw_frames = ""
+    image_knobs = [(n, v) for n, v in knobs if n != "features_raw"]
+    image_knobs[3:3] = [("images_raw", None)] if semi else []
+    mw = ("max_workgroups", 0)
+    out = [
+        _method("gradient_features", names + ("labels", "mask"), [("params", None), mw] + knobs, "_gradient_from", names,
+                "(loss float64 [1], {name: gradient} for ``variable_names``) on the device for %s and %s.  ``params`` overrides "
+                "any of the %d tensors; ``max_workgroups``: 0 = the default grids, a tuning knob.  No update.%s"
+                % (inputs, targets, len(variables), knobs_doc)),
+        _method("features", ("images",), [], "_features", (),
+                "%s for ``images`` (%s): what ``step_features`` and ``gradient_features`` take%s.  One forward pass of the frozen "
+                "trunk; it never changes, so the result can be cached across steps."
+                % (", ".join("``%s`` %s" % (f.name, _shape(f, d.up)) for f in maps), "copies" if len(maps) > 1 else "a copy",
+                   " next to the frames" if has_frame else "")),
+        _method("step_features", names + ("labels", "mask"), [mw] + knobs, "_step_from", names,
+                "one Adam step from cached features (``features(images)``%s): %s and %s.  Returns the loss (float64 device "
+                "scalar) BEFORE the step, as ``sess.run([loss, train_op])`` does.%s"
+                % (" and the frames" if has_frame else "", inputs, targets, again)),
+        _method("step", ("images", "labels", "mask"), [mw] + image_knobs, "_step_from_images", (),
+                "one Adam step from images [N, H, W, C] (fp32 or decoded uint8) and labels / mask [N, H, W]: %s on the weights "
+                "being trained, their gradient kernels, Adam.  Returns the loss (float64 device scalar) before the step.%s%s"
+                % (trunk, raw_frames, again)),
+    ]
+    if d.image_gradient:
+        out.append(_method("gradient", ("images", "labels", "mask"), [("params", None), mw] + image_knobs,
+                           "_gradient_from_images", (),
+                           "``gradient_features(*features(images), ...)`` through the images entry, ``(loss, {name: gradient})``: "
+                           "%s and their gradient kernels, on the host variables overridden by ``params``.  No update.%s"
+                           % (trunk, again)))
+    return out
+
+
+def _icnet_depth(stem, semi=False):
+    """class decorator: the class is the trainer of depth ``stem`` (``semi``: its semi-supervised form, on the ``_semi`` entries
+    next to the plain ones)"""
+    d = _depths.DEPTHS[stem]
+    assert d.semi or not semi, "depth %s has no semi-supervised entries" % stem
+
+    def describe(cls):
+        cls._DEPTH = d
+        cls._VARS, cls._STATS = _depths.variables(stem), _depths.stats(stem)  # (layer, attribute[, regularised]), packed order
+        cls.variable_names = ["%s.%s" % (layer, attr) for layer, attr, _ in cls._VARS]
+        cls._FEATURE_NAMES = tuple(f.name for f in d.features if f.kind == _depths.MAP)  # the endpoints features() returns
+        cls._SEMI_NOUN = d.noun                                                          # in the refusal of a semi keyword
+        cls._CHANNELS, cls._UP = d.features[0].channels, d.up
+        grad, train = "ssal_icnet_%s_grad" % stem, "ssal_icnet_train_%s" % stem
+        cls._C_FEATURES = (grad, grad + "_semi" if semi else None)
+        cls._C_IMAGES = (train, train + "_semi" if semi else None)
+        cls._C_UPDATE = "ssal_icnet_update_%s" % stem
+        for m in _public_methods(d, cls._VARS, semi):
+            m.__qualname__ = "%s.%s" % (cls.__qualname__, m.__name__)
+            setattr(cls, m.__name__, m)
+        return cls
+    return describe
+
+
 # ---- ICNet's output layer: conv6_cls over a frozen trunk (DESIGN.md section 23) ------------------------------------------------
-_HEAD = "conv6_cls"
+_HEAD = _depths.HEAD
 _HEAD_NAMES = (_HEAD + ".kernel", _HEAD + ".bias")
 
 
+@_icnet_depth("head")
 class ICNetHeadTrainer(FinalLayerTrainer):
     """Adam on ``net.conv6_cls.kernel`` [1, 1, 128, K] and ``net.conv6_cls.bias`` [K] of an ``ICNet``: the reference's
     ``-r/--reinitialize-output-layer`` slice (active_learning.py:905-909, 461-462) for the second model -- the only weights
@@ -1067,9 +1192,6 @@ class ICNetHeadTrainer(FinalLayerTrainer):
     and ``weight_reg.glorot_scaling`` are refused."""
 
     _semi_keywords = False
-    _C_FEATURES = ("ssal_icnet_head_grad", None)
-    _C_IMAGES = ("ssal_icnet_train_head", None)
-    _CHANNELS, _UP = 128, 8
 
     @staticmethod
     def _check_model(net):
@@ -1091,8 +1213,6 @@ class ICNetHeadTrainer(FinalLayerTrainer):
             raise RuntimeError("build the model (call it once, or .build(input_shape)) before training")
         layer = getattr(self.net, _HEAD)
         return layer.kernel, layer.bias
-
-    variable_names = list(_HEAD_NAMES)
 
     def _split(self):
         return 128 * int(self.net.classes)
@@ -1165,11 +1285,8 @@ class ICNetHeadTrainer(FinalLayerTrainer):
         self._set_state(self._pack(state["m"]), self._pack(state["v"]), state["t"])
 
     # ---- arguments, judged on the host before any device work -----------------------------------------------------------------
-    _SEMI_NOUN = "ICNet's output layer"  # what the refusal of a semi-supervised keyword calls the class
-    _FEATURE_NAMES = ("sub12_sum",)      # the endpoints the features entry takes, in its order
-
     def _no_semi(self, **kw):
-        """``_semi_call``'s refusal for the three plain ICNet trainers"""
+        """``_semi_call``'s refusal for the plain ICNet trainers"""
         for name, value in kw.items():
             if value is not None and value is not False:
                 raise NotImplementedError("%s: the semi-supervised step is not implemented for %s" % (name, self._SEMI_NOUN))
@@ -1190,7 +1307,8 @@ class ICNetHeadTrainer(FinalLayerTrainer):
             raise ValueError("expected a [N,h,w,%s] batch (got %s)" % (channels or "C", shape))
         dt = str(getattr(batch, "dtype", ""))
         if channels is not None and not ("float" in dt):
-            raise ValueError("sub12_sum must be a floating-point tensor (got %s)" % (dt or type(batch).__name__))
+            raise ValueError("%s must be a floating-point tensor (got %s)"
+                             % (self._DEPTH.features[0].name, dt or type(batch).__name__))
         want = (shape[0], up * shape[1], up * shape[2])
         for name, t in (("labels", labels), ("mask", mask)):
             if tuple(np.shape(t)) != want:
@@ -1214,8 +1332,26 @@ class ICNetHeadTrainer(FinalLayerTrainer):
             packed = over
         return packed
 
-    def _check_features(self, sub12_sum, labels, mask, max_workgroups):
-        return self._check_call(sub12_sum, 8, labels, mask, max_workgroups, 128)
+    def _check_features(self, feats, labels, mask, max_workgroups):
+        """the features of a call against the depth's row: the first one with the targets (``_check_call``), then each other
+        one's shape -- the first one's by its factor, its channel count -- and type, in entry order"""
+        first = self._DEPTH.features[0]
+        mw = self._check_call(feats[0], self._UP, labels, mask, max_workgroups, first.channels)
+        shape = n, h, w, _ = tuple(np.shape(feats[0]))
+        for f, t in zip(self._DEPTH.features[1:], feats[1:]):
+            channels, types, kind = f.channels, ("float",), "a floating-point"
+            if f.kind == _depths.FRAME:  # the caller's frames: the model's channel count, fp32 or decoded uint8
+                self._vars()  # (the model is built)
+                channels, types, kind = int(self.net._c_in), ("float", "uint8"), "a floating-point or uint8"
+                if channels not in (3, 4):
+                    raise ValueError("the high-resolution trainer takes 3 or 4 input channels (the model has %d)" % channels)
+            want = (n, f.factor * h, f.factor * w, channels)
+            if tuple(np.shape(t)) != want:
+                raise ValueError("%s must be %s for %s %s (got %s)" % (f.name, want, first.name, shape, tuple(np.shape(t))))
+            dt = str(getattr(t, "dtype", ""))
+            if not any(word in dt for word in types):
+                raise ValueError("%s must be %s tensor (got %s)" % (f.name, kind, dt or type(t).__name__))
+        return mw
 
     def _check_raw(self, feats, features_raw, semi):
         """``features_raw`` as given -> its members (None: no raw side), judged on the host: the tuple ``features()`` returns"""
@@ -1243,7 +1379,7 @@ class ICNetHeadTrainer(FinalLayerTrainer):
         """``_extra_c_args`` of a features call on the device tensors ``xs`` (``xr``: their raw side, or Nones)"""
         return self._extra_c_args(xs[0])
 
-    # ---- gradients and steps: one path for the four depths, plain and semi-supervised -----------------------------------------
+    # ---- gradients and steps: one path for every depth, plain and semi-supervised -----------------------------------------
     def _feature_call(self, feats, labels, mask, params, step, max_workgroups, labelled=None, measure=None, threshold=None,
                       features_raw=None, confusion=None, return_pseudo_pixels=False):
         """the features entry on the tuple ``feats``: -> (loss [1], packed gradient, pseudo pixels or None, device state or
@@ -1251,7 +1387,7 @@ class ICNetHeadTrainer(FinalLayerTrainer):
         class refuses the semi-supervised keywords here (``_no_semi``); everything is judged before any device work."""
         semi = self._semi_call(feats[0], labels, mask, labelled, measure, threshold, confusion, return_pseudo_pixels,
                                features_raw=features_raw)
-        mw = self._check_features(*feats, labels, mask, max_workgroups)
+        mw = self._check_features(feats, labels, mask, max_workgroups)
         raw = self._check_raw(feats, features_raw, semi)
         packed = None if step else self._packed_with(params)
         x = self._feature_to_device(0, feats[0])
@@ -1283,35 +1419,30 @@ class ICNetHeadTrainer(FinalLayerTrainer):
         return self._step_images(images, images_raw, labels, mask, semi, confusion, return_pseudo_pixels,
                                  self._extra_c_args(images) + (mw,))
 
-    def gradient_features(self, sub12_sum, labels, mask, params=None, max_workgroups=0, labelled=None, confusion=None,
-                          return_pseudo_pixels=False):
-        """(loss float64 [1], {"conv6_cls.kernel": [1, 1, 128, K], "conv6_cls.bias": [K]}) on the device for ``sub12_sum``
-        [N, h, w, 128] and labels / mask [N, 8h, 8w].  ``params`` overrides either tensor of the head; ``max_workgroups``: 0 =
-        min(tiles, 1024), a tuning knob.  No update."""
-        return self._gradient_from((sub12_sum,), labels, mask, params, max_workgroups, labelled=labelled, confusion=confusion,
-                                   return_pseudo_pixels=return_pseudo_pixels)
+    def _gradient_from_images(self, images, labels, mask, params, max_workgroups, labelled, confusion, return_pseudo_pixels):
+        """the images entry on the host variables overridden by ``params``, without the update -> (loss [1], {name: gradient})"""
+        semi = self._semi_call(images, labels, mask, labelled, None, None, confusion, return_pseudo_pixels)
+        mw = self._check_call(images, 1, labels, mask, max_workgroups, None)
+        packed = self._packed_with(params)
+        torch = _lib.require_gpu()
+        x = self.net._prepare(images, False)
+        vec = torch.from_numpy(packed).to(x.device)
+        loss, _, dev = self._images_call(x, None, labels, mask, semi, confusion, return_pseudo_pixels,
+                                         self._extra_c_args(x) + (mw,), weights=vec)
+        with torch.cuda.device(x.device):
+            grad = torch.empty_like(dev["grad"])
+            grad.copy_(dev["grad"])
+        return loss, self._unpack(grad)
 
-    def features(self, images):
-        """``sub12_sum`` [N, H/8, W/8, 128] for ``images`` (a copy): what ``step_features`` and ``gradient_features`` take.
-        One forward pass of the frozen trunk; it never changes, so the result can be cached across steps."""
+    def _features(self, images):
+        """copies of the endpoints the features entry takes, after one forward pass (the head's one endpoint comes bare)"""
         self.net(images, training=False)
-        return self.net.endpoint("sub12_sum").clone()
-
-    def step_features(self, sub12_sum, labels, mask, max_workgroups=0, labelled=None, confusion=None,
-                      return_pseudo_pixels=False):
-        """one Adam step from cached ``sub12_sum`` features; returns the loss (float64 device scalar) BEFORE the step, as
-        ``sess.run([loss, train_op])`` does"""
-        return self._step_from((sub12_sum,), labels, mask, max_workgroups, labelled=labelled, confusion=confusion,
-                               return_pseudo_pixels=return_pseudo_pixels)
-
-    def step(self, images, labels, mask, max_workgroups=0, labelled=None, confusion=None, return_pseudo_pixels=False):
-        """one Adam step from images [N, H, W, C] (fp32 or decoded uint8) and labels / mask [N, H, W]: the frozen trunk up
-        to ``sub12_sum``, the head and its gradient kernel, Adam.  Returns the loss (float64 device scalar) before the step."""
-        return self._step_from_images(images, labels, mask, max_workgroups, labelled=labelled, confusion=confusion,
-                                      return_pseudo_pixels=return_pseudo_pixels)
+        out = tuple(self.net.endpoint(name).clone() for name in self._FEATURE_NAMES)
+        return out if len(out) > 1 else out[0]
 
 
 # ---- the semi-supervised step of ICNet's output-layer trainer (DESIGN.md section 25) --------------------------------------------
+@_icnet_depth("head", semi=True)
 class SemiSupervisedICNetHeadTrainer(_SemiKeywords, ICNetHeadTrainer):
     """``ICNetHeadTrainer`` with the reference's semi-supervised step (active_learning.py:226-275, 339-342) built into its
     gradient kernel: ``gradient_features``, ``step_features`` and ``step`` accept ``labelled``, ``measure``, ``threshold``,
@@ -1320,9 +1451,6 @@ class SemiSupervisedICNetHeadTrainer(_SemiKeywords, ICNetHeadTrainer):
     side, of the undistorted frames' logits).  Loss, dKernel and dBias are bit-identical to ``ICNetHeadTrainer`` on the
     composed targets; with none of the keywords a call goes through the plain entry.  ``state`` /
     ``load_state`` are interchangeable with ``ICNetHeadTrainer``'s."""
-
-    _C_FEATURES = ("ssal_icnet_head_grad", "ssal_icnet_head_grad_semi")
-    _C_IMAGES = ("ssal_icnet_train_head", "ssal_icnet_train_head_semi")
 
     def _check_raw(self, feats, features_raw, semi):
         """the head's raw side is one tensor, looked at only in a call that is semi-supervised"""
@@ -1333,43 +1461,9 @@ class SemiSupervisedICNetHeadTrainer(_SemiKeywords, ICNetHeadTrainer):
                              % (tuple(np.shape(feats[0])), tuple(np.shape(features_raw))))
         return (features_raw,)
 
-    def gradient_features(self, sub12_sum, labels, mask, params=None, max_workgroups=0, labelled=None, measure=None,
-                          threshold=None, features_raw=None, confusion=None, return_pseudo_pixels=False):
-        """``ICNetHeadTrainer.gradient_features`` with the semi-supervised keywords of ``FinalLayerTrainer.gradient_features``:
-        ``labelled`` [N], ``measure`` / ``threshold`` (defaults: the trainer's), ``features_raw`` (``sub12_sum`` of the
-        undistorted frames), ``confusion`` (int64 [K, K] device tensor, added to), ``return_pseudo_pixels`` (appends the int64
-        [N] counts to the result)."""
-        return self._gradient_from((sub12_sum,), labels, mask, params, max_workgroups, labelled=labelled, measure=measure,
-                                   threshold=threshold, features_raw=features_raw, confusion=confusion,
-                                   return_pseudo_pixels=return_pseudo_pixels)
-
-    def step_features(self, sub12_sum, labels, mask, max_workgroups=0, labelled=None, measure=None, threshold=None,
-                      features_raw=None, confusion=None, return_pseudo_pixels=False):
-        """one Adam step from cached ``sub12_sum`` features; the keywords are those of ``gradient_features``; with
-        ``return_pseudo_pixels`` the result is ``(loss, pseudo_pixels)``"""
-        return self._step_from((sub12_sum,), labels, mask, max_workgroups, labelled=labelled, measure=measure,
-                               threshold=threshold, features_raw=features_raw, confusion=confusion,
-                               return_pseudo_pixels=return_pseudo_pixels)
-
-    def step(self, images, labels, mask, max_workgroups=0, labelled=None, measure=None, threshold=None, images_raw=None,
-             confusion=None, return_pseudo_pixels=False):
-        """one Adam step from images; ``images_raw``: the undistorted frames (same shape and dtype as ``images``) -- the trunk
-        runs on them first and the pseudo annotation comes from their logits (active_learning.py:231).  The other keywords
-        as in ``gradient_features``; with ``return_pseudo_pixels`` the result is ``(loss, pseudo_pixels)``."""
-        return self._step_from_images(images, labels, mask, max_workgroups, labelled=labelled, measure=measure,
-                                      threshold=threshold, images_raw=images_raw, confusion=confusion,
-                                      return_pseudo_pixels=return_pseudo_pixels)
-
 
 # ---- ICNet's last fusion stage: conv_sub2 + conv3_sub1_proj + conv6_cls over a frozen trunk (DESIGN.md section 28) -------------
-# (layer, attribute, regularised) of the packed vector, in packed order
-_FUSION_VARS = (("conv_sub2", "kernel", True), ("conv_sub2", "gamma", False), ("conv_sub2", "beta", False),
-                ("conv3_sub1_proj", "kernel", True), ("conv3_sub1_proj", "gamma", False), ("conv3_sub1_proj", "beta", False),
-                (_HEAD, "kernel", True), (_HEAD, "bias", False))
-_FUSION_NAMES = tuple("%s.%s" % (layer, attr) for layer, attr, _ in _FUSION_VARS)
-_FUSION_STATS = (("conv_sub2", "mean"), ("conv_sub2", "variance"), ("conv3_sub1_proj", "mean"), ("conv3_sub1_proj", "variance"))
-
-
+@_icnet_depth("fusion")
 class ICNetFusionTrainer(ICNetHeadTrainer):
     """Adam on ICNet's last cascade-feature-fusion block and its output layer: ``sub12_sum = relu(BN(conv_sub2(resize_2x(
     sub24_sum))) + BN(conv3_sub1_proj(conv3_sub1)))`` (ICNET_SPEC section 4) and ``conv6_cls``, over a trunk frozen below
@@ -1382,13 +1476,7 @@ class ICNetFusionTrainer(ICNetHeadTrainer):
     returns and ``state`` / ``load_state`` use a dict keyed by those names.  The semi-supervised keywords,
     ``softmax.multiscale`` and ``weight_reg.glorot_scaling`` are refused."""
 
-    _semi_keywords = False
-    _C_FEATURES = ("ssal_icnet_fusion_grad", None)
-    _C_IMAGES = ("ssal_icnet_train_fusion", None)
-    _CHANNELS, _UP = 128, 16
     _LIMIT = ("kernels'", "kernels'")
-    _VARS, _STATS, _C_UPDATE = _FUSION_VARS, _FUSION_STATS, "ssal_icnet_update_fusion"  # what a subclass widens
-    variable_names = list(_FUSION_NAMES)
 
     # ---- the packed vector ---------------------------------------------------------------------------------------------------
     def _vars(self):
@@ -1490,20 +1578,6 @@ class ICNetFusionTrainer(ICNetHeadTrainer):
         self._set_state(self._pack(state["m"]), self._pack(state["v"]), state["t"])
 
     # ---- arguments, judged on the host before any device work -----------------------------------------------------------------
-    _SEMI_NOUN = "ICNet's fusion trainer"
-    _FEATURE_NAMES = ("sub24_sum", "conv3_sub1")
-
-    def _check_features(self, sub24_sum, conv3_sub1, labels, mask, max_workgroups):
-        mw = self._check_call(sub24_sum, 16, labels, mask, max_workgroups, 128)
-        s24, s3 = tuple(np.shape(sub24_sum)), tuple(np.shape(conv3_sub1))
-        if s3 != (s24[0], 2 * s24[1], 2 * s24[2], 64):
-            raise ValueError("conv3_sub1 must be [N,2h,2w,64] = %s for sub24_sum %s (got %s)"
-                             % ((s24[0], 2 * s24[1], 2 * s24[2], 64), s24, s3))
-        dt = str(getattr(conv3_sub1, "dtype", ""))
-        if "float" not in dt:
-            raise ValueError("conv3_sub1 must be a floating-point tensor (got %s)" % (dt or type(conv3_sub1).__name__))
-        return mw
-
     def _packed_with(self, params):
         params = dict(params or {})
         unknown = set(params) - set(self.variable_names)
@@ -1520,43 +1594,9 @@ class ICNetFusionTrainer(ICNetHeadTrainer):
         device = batch.device if getattr(batch, "is_cuda", False) else torch.device("cuda", torch.cuda.current_device())
         return (_lib.dev_ptr(self._stats(device)),)
 
-    # ---- gradients and steps ---------------------------------------------------------------------------------------------
-    def gradient_features(self, sub24_sum, conv3_sub1, labels, mask, params=None, max_workgroups=0, labelled=None,
-                          confusion=None, return_pseudo_pixels=False):
-        """(loss float64 [1], {name: gradient} for ``variable_names``) on the device for ``sub24_sum`` [N, h, w, 128],
-        ``conv3_sub1`` [N, 2h, 2w, 64] and labels / mask [N, 16h, 16w].  ``params`` overrides any of the eight tensors;
-        ``max_workgroups``: 0 = the default grids, a tuning knob.  No update."""
-        return self._gradient_from((sub24_sum, conv3_sub1), labels, mask, params, max_workgroups, labelled=labelled,
-                                   confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
-
-    def features(self, images):
-        """``(sub24_sum [N, H/16, W/16, 128], conv3_sub1 [N, H/8, W/8, 64])`` for ``images`` (copies): what ``step_features``
-        and ``gradient_features`` take.  One forward pass of the frozen trunk; the result can be cached across steps."""
-        self.net(images, training=False)
-        return self.net.endpoint("sub24_sum").clone(), self.net.endpoint("conv3_sub1").clone()
-
-    def step_features(self, sub24_sum, conv3_sub1, labels, mask, max_workgroups=0, labelled=None, confusion=None,
-                      return_pseudo_pixels=False):
-        """one Adam step from cached features; returns the loss (float64 device scalar) BEFORE the step"""
-        return self._step_from((sub24_sum, conv3_sub1), labels, mask, max_workgroups, labelled=labelled, confusion=confusion,
-                               return_pseudo_pixels=return_pseudo_pixels)
-
-    def step(self, images, labels, mask, max_workgroups=0, labelled=None, confusion=None, return_pseudo_pixels=False):
-        """one Adam step from images [N, H, W, C] (fp32 or decoded uint8) and labels / mask [N, H, W]: the frozen trunk up
-        to ``sub24_sum`` and ``conv3_sub1``, the block and the head on the weights being trained, their gradient kernels,
-        Adam.  Returns the loss (float64 device scalar) before the step."""
-        return self._step_from_images(images, labels, mask, max_workgroups, labelled=labelled, confusion=confusion,
-                                      return_pseudo_pixels=return_pseudo_pixels)
-
 
 # ---- ICNet's whole cascade head: both fusion blocks + conv6_cls over the three frozen branches (DESIGN.md section 29) -----------
-_CASCADE_VARS = (("conv_sub4", "kernel", True), ("conv_sub4", "gamma", False), ("conv_sub4", "beta", False),
-                 ("conv3_1_sub2_proj", "kernel", True), ("conv3_1_sub2_proj", "gamma", False),
-                 ("conv3_1_sub2_proj", "beta", False)) + _FUSION_VARS
-_CASCADE_STATS = (("conv_sub4", "mean"), ("conv_sub4", "variance"), ("conv3_1_sub2_proj", "mean"),
-                  ("conv3_1_sub2_proj", "variance")) + _FUSION_STATS
-
-
+@_icnet_depth("cascade")
 class ICNetCascadeTrainer(ICNetFusionTrainer):
     """Adam on ICNet's cascade head -- everything ICNET_SPEC section 4 defines: ``sub24_sum = relu(BN(conv_sub4(resize_2x(
     conv5_4_k1))) + BN(conv3_1_sub2_proj(conv3_1)))``, the last fusion block of ``ICNetFusionTrainer`` and ``conv6_cls`` --
@@ -1567,55 +1607,9 @@ class ICNetCascadeTrainer(ICNetFusionTrainer):
     The fourteen variables travel as one packed float32 vector in the order of ``variable_names``: the new block's six, then the
     parent's eight in the parent's order."""
 
-    _C_FEATURES = ("ssal_icnet_cascade_grad", None)
-    _C_IMAGES = ("ssal_icnet_train_cascade", None)
-    _CHANNELS, _UP = 256, 32
-    _VARS, _STATS, _C_UPDATE = _CASCADE_VARS, _CASCADE_STATS, "ssal_icnet_update_cascade"
-    variable_names = ["%s.%s" % (layer, attr) for layer, attr, _ in _CASCADE_VARS]
-
-    _SEMI_NOUN = "ICNet's cascade trainer"
-    _FEATURE_NAMES = ("conv5_4_k1", "conv3_1", "conv3_sub1")
-
-    def _check_features(self, conv5_4_k1, conv3_1, conv3_sub1, labels, mask, max_workgroups):
-        mw = self._check_call(conv5_4_k1, 32, labels, mask, max_workgroups, 256)
-        n, h, w, _ = tuple(np.shape(conv5_4_k1))
-        for name, t, want in (("conv3_1", conv3_1, (n, 2 * h, 2 * w, 256)), ("conv3_sub1", conv3_sub1, (n, 4 * h, 4 * w, 64))):
-            if tuple(np.shape(t)) != want:
-                raise ValueError("%s must be %s for conv5_4_k1 %s (got %s)" % (name, want, (n, h, w, 256), tuple(np.shape(t))))
-            dt = str(getattr(t, "dtype", ""))
-            if "float" not in dt:
-                raise ValueError("%s must be a floating-point tensor (got %s)" % (name, dt or type(t).__name__))
-        return mw
-
-    def gradient_features(self, conv5_4_k1, conv3_1, conv3_sub1, labels, mask, params=None, max_workgroups=0, labelled=None,
-                          confusion=None, return_pseudo_pixels=False):
-        """(loss float64 [1], {name: gradient} for ``variable_names``) on the device for ``conv5_4_k1`` [N, h, w, 256],
-        ``conv3_1`` [N, 2h, 2w, 256], ``conv3_sub1`` [N, 4h, 4w, 64] and labels / mask [N, 32h, 32w].  ``params`` overrides
-        any of the fourteen tensors; ``max_workgroups``: 0 = the default grids, a tuning knob.  No update."""
-        return self._gradient_from((conv5_4_k1, conv3_1, conv3_sub1), labels, mask, params, max_workgroups, labelled=labelled,
-                                   confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
-
-    def features(self, images):
-        """``(conv5_4_k1 [N, H/32, W/32, 256], conv3_1 [N, H/16, W/16, 256], conv3_sub1 [N, H/8, W/8, 64])`` for ``images``
-        (copies): what ``step_features`` and ``gradient_features`` take.  One forward pass of the frozen branches."""
-        self.net(images, training=False)
-        return tuple(self.net.endpoint(name).clone() for name in ("conv5_4_k1", "conv3_1", "conv3_sub1"))
-
-    def step_features(self, conv5_4_k1, conv3_1, conv3_sub1, labels, mask, max_workgroups=0, labelled=None, confusion=None,
-                      return_pseudo_pixels=False):
-        """one Adam step from cached features; returns the loss (float64 device scalar) BEFORE the step"""
-        return self._step_from((conv5_4_k1, conv3_1, conv3_sub1), labels, mask, max_workgroups, labelled=labelled,
-                               confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
-
 
 # ---- ICNet's high-resolution branch down to the image, with the cascade head (DESIGN.md section 32) ----------------------------
-_HIGHRES_LAYERS = ("conv1_sub1", "conv2_sub1", "conv3_sub1")
-_HIGHRES_VARS = tuple((layer, attr, attr == "kernel") for layer in _HIGHRES_LAYERS
-                      for attr in ("kernel", "gamma", "beta")) + _CASCADE_VARS
-# rows of mixed widths (32, 32, 32, 32, 64, 64, then the cascade trainer's eight of 128), concatenated unpadded
-_HIGHRES_STATS = tuple((layer, attr) for layer in _HIGHRES_LAYERS for attr in ("mean", "variance")) + _CASCADE_STATS
-
-
+@_icnet_depth("highres")
 class ICNetHighResTrainer(ICNetCascadeTrainer):
     """Adam on ICNet's high-resolution branch (ICNET_SPEC section 3) and the cascade head above it: ``conv1_sub1``,
     ``conv2_sub1`` and ``conv3_sub1`` -- three 3 x 3 stride-2 convolutions + batch-norm + ReLU, ``C_in -> 32 -> 32 -> 64`` on
@@ -1626,36 +1620,6 @@ class ICNetHighResTrainer(ICNetCascadeTrainer):
 
     The 23 variables travel as one packed float32 vector in the order of ``variable_names``: the branch's nine, then the
     parent's fourteen in the parent's order."""
-
-    _C_FEATURES = ("ssal_icnet_highres_grad", None)
-    _C_IMAGES = ("ssal_icnet_train_highres", None)
-    _CHANNELS, _UP = 256, 32
-    _VARS, _STATS, _C_UPDATE = _HIGHRES_VARS, _HIGHRES_STATS, "ssal_icnet_update_highres"
-    variable_names = ["%s.%s" % (layer, attr) for layer, attr, _ in _HIGHRES_VARS]
-
-    _SEMI_NOUN = "ICNet's high-resolution trainer"
-    _FEATURE_NAMES = ("conv5_4_k1", "conv3_1")
-
-    def _check_features(self, conv5_4_k1, conv3_1, images, labels, mask, max_workgroups):
-        mw = self._check_call(conv5_4_k1, 32, labels, mask, max_workgroups, 256)
-        n, h, w, _ = tuple(np.shape(conv5_4_k1))
-        if tuple(np.shape(conv3_1)) != (n, 2 * h, 2 * w, 256):
-            raise ValueError("conv3_1 must be %s for conv5_4_k1 %s (got %s)"
-                             % ((n, 2 * h, 2 * w, 256), (n, h, w, 256), tuple(np.shape(conv3_1))))
-        dt = str(getattr(conv3_1, "dtype", ""))
-        if "float" not in dt:
-            raise ValueError("conv3_1 must be a floating-point tensor (got %s)" % (dt or type(conv3_1).__name__))
-        self._vars()  # (the model is built)
-        c_in = int(self.net._c_in)
-        if c_in not in (3, 4):
-            raise ValueError("the high-resolution trainer takes 3 or 4 input channels (the model has %d)" % c_in)
-        if tuple(np.shape(images)) != (n, 32 * h, 32 * w, c_in):
-            raise ValueError("images must be %s for conv5_4_k1 %s (got %s)"
-                             % ((n, 32 * h, 32 * w, c_in), (n, h, w, 256), tuple(np.shape(images))))
-        dt = str(getattr(images, "dtype", ""))
-        if not ("float" in dt or "uint8" in dt):
-            raise ValueError("images must be a floating-point or uint8 tensor (got %s)" % (dt or type(images).__name__))
-        return mw
 
     def _feature_to_device(self, i, t):
         """the frames are the third input: they stay uint8 when they are (the entry converts them as the forward path does)"""
@@ -1688,42 +1652,9 @@ class ICNetHighResTrainer(ICNetCascadeTrainer):
                 raise ValueError("features_raw: %s must be a floating-point tensor" % name)
         return tuple(features_raw)
 
-    def gradient_features(self, conv5_4_k1, conv3_1, images, labels, mask, params=None, max_workgroups=0, labelled=None,
-                          confusion=None, return_pseudo_pixels=False):
-        """(loss float64 [1], {name: gradient} for ``variable_names``) on the device for ``conv5_4_k1`` [N, h, w, 256],
-        ``conv3_1`` [N, 2h, 2w, 256], ``images`` [N, 32h, 32w, C_in] (fp32 or decoded uint8) and labels / mask [N, 32h, 32w].
-        ``params`` overrides any of the 23 tensors; ``max_workgroups``: 0 = the default grids, a tuning knob.  No update."""
-        return self._gradient_from((conv5_4_k1, conv3_1, images), labels, mask, params, max_workgroups, labelled=labelled,
-                                   confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
-
-    def features(self, images):
-        """``(conv5_4_k1 [N, H/32, W/32, 256], conv3_1 [N, H/16, W/16, 256])`` for ``images`` (copies): what ``step_features``
-        and ``gradient_features`` take next to the frames.  One forward pass; the two backbone branches are frozen, so the
-        result can be cached across steps."""
-        self.net(images, training=False)
-        return tuple(self.net.endpoint(name).clone() for name in ("conv5_4_k1", "conv3_1"))
-
-    def step_features(self, conv5_4_k1, conv3_1, images, labels, mask, max_workgroups=0, labelled=None, confusion=None,
-                      return_pseudo_pixels=False):
-        """one Adam step from cached backbone features and the frames; returns the loss (float64 device scalar) BEFORE the
-        step"""
-        return self._step_from((conv5_4_k1, conv3_1, images), labels, mask, max_workgroups, labelled=labelled,
-                               confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
-
-    def step(self, images, labels, mask, max_workgroups=0, labelled=None, confusion=None, return_pseudo_pixels=False):
-        """one Adam step from images [N, H, W, C_in] (fp32 or decoded uint8) and labels / mask [N, H, W]: the two frozen
-        backbone branches, then the high-resolution branch, both fusion blocks and the head on the weights being trained,
-        their gradient kernels down to the frame, Adam.  Returns the loss (float64 device scalar) before the step."""
-        return self._step_from_images(images, labels, mask, max_workgroups, labelled=labelled, confusion=confusion,
-                                      return_pseudo_pixels=return_pseudo_pixels)
-
 
 # ---- ICNet's pyramid head: conv5_4_k1 over the pyramid-pooling sum, with the cascade head (DESIGN.md section 39) ----------------
-_PYRAMID_VARS = (("conv5_4_k1", "kernel", True), ("conv5_4_k1", "gamma", False), ("conv5_4_k1", "beta", False)) + _CASCADE_VARS
-# rows of mixed widths (256, 256, then the cascade trainer's eight of 128), concatenated unpadded
-_PYRAMID_STATS = (("conv5_4_k1", "mean"), ("conv5_4_k1", "variance")) + _CASCADE_STATS
-
-
+@_icnet_depth("pyramid")
 class ICNetPyramidTrainer(ICNetCascadeTrainer):
     """Adam on ``conv5_4_k1`` -- the 1 x 1 convolution (1024 -> 256) + batch-norm + ReLU over the pyramid-pooling sum
     ``conv5_3_sum``, the low-resolution branch's only path into the cascade (ICNET_SPEC section 2) -- and the cascade head
@@ -1736,79 +1667,9 @@ class ICNetPyramidTrainer(ICNetCascadeTrainer):
     The 17 variables travel as one packed float32 vector in the order of ``variable_names``: ``conv5_4_k1``'s three, then the
     parent's fourteen in the parent's order.  The semi-supervised keywords are refused."""
 
-    _C_FEATURES = ("ssal_icnet_pyramid_grad", None)
-    _C_IMAGES = ("ssal_icnet_train_pyramid", None)
-    _CHANNELS, _UP = 1024, 32
-    _VARS, _STATS, _C_UPDATE = _PYRAMID_VARS, _PYRAMID_STATS, "ssal_icnet_update_pyramid"
-    variable_names = ["%s.%s" % (layer, attr) for layer, attr, _ in _PYRAMID_VARS]
-
-    _SEMI_NOUN = "ICNet's pyramid trainer"
-    _FEATURE_NAMES = ("conv5_3_sum", "conv3_1", "conv3_sub1")
-
-    def _check_features(self, conv5_3_sum, conv3_1, conv3_sub1, labels, mask, max_workgroups):
-        mw = self._check_call(conv5_3_sum, 32, labels, mask, max_workgroups, 1024)
-        n, h, w, _ = tuple(np.shape(conv5_3_sum))
-        for name, t, want in (("conv3_1", conv3_1, (n, 2 * h, 2 * w, 256)), ("conv3_sub1", conv3_sub1, (n, 4 * h, 4 * w, 64))):
-            if tuple(np.shape(t)) != want:
-                raise ValueError("%s must be %s for conv5_3_sum %s (got %s)" % (name, want, (n, h, w, 1024), tuple(np.shape(t))))
-            dt = str(getattr(t, "dtype", ""))
-            if "float" not in dt:
-                raise ValueError("%s must be a floating-point tensor (got %s)" % (name, dt or type(t).__name__))
-        return mw
-
-    def gradient_features(self, conv5_3_sum, conv3_1, conv3_sub1, labels, mask, params=None, max_workgroups=0, labelled=None,
-                          confusion=None, return_pseudo_pixels=False):
-        """(loss float64 [1], {name: gradient} for ``variable_names``) on the device for ``conv5_3_sum`` [N, h, w, 1024],
-        ``conv3_1`` [N, 2h, 2w, 256], ``conv3_sub1`` [N, 4h, 4w, 64] and labels / mask [N, 32h, 32w].  ``params`` overrides
-        any of the 17 tensors; ``max_workgroups``: 0 = the default grids, a tuning knob.  No update."""
-        return self._gradient_from((conv5_3_sum, conv3_1, conv3_sub1), labels, mask, params, max_workgroups, labelled=labelled,
-                                   confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
-
-    def features(self, images):
-        """``(conv5_3_sum [N, H/32, W/32, 1024], conv3_1 [N, H/16, W/16, 256], conv3_sub1 [N, H/8, W/8, 64])`` for ``images``
-        (copies): what ``step_features`` and ``gradient_features`` take.  One forward pass of the frozen layers."""
-        self.net(images, training=False)
-        return tuple(self.net.endpoint(name).clone() for name in ("conv5_3_sum", "conv3_1", "conv3_sub1"))
-
-    def step_features(self, conv5_3_sum, conv3_1, conv3_sub1, labels, mask, max_workgroups=0, labelled=None, confusion=None,
-                      return_pseudo_pixels=False):
-        """one Adam step from cached features; returns the loss (float64 device scalar) BEFORE the step"""
-        return self._step_from((conv5_3_sum, conv3_1, conv3_sub1), labels, mask, max_workgroups, labelled=labelled,
-                               confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
-
-    def gradient(self, images, labels, mask, params=None, max_workgroups=0, labelled=None, confusion=None,
-                 return_pseudo_pixels=False):
-        """``gradient_features(*features(images), ...)`` through the images entry: the frozen trunk (its low-resolution
-        schedule ends after ``conv5_3_sum``), then ``conv5_4_k1``, the cascade head and their gradient kernels, on the host
-        variables overridden by ``params``.  No update."""
-        semi = self._semi_call(images, labels, mask, labelled, None, None, confusion, return_pseudo_pixels)
-        mw = self._check_call(images, 1, labels, mask, max_workgroups, None)
-        packed = self._packed_with(params)
-        torch = _lib.require_gpu()
-        x = self.net._prepare(images, False)
-        vec = torch.from_numpy(packed).to(x.device)
-        loss, _, dev = self._images_call(x, None, labels, mask, semi, confusion, return_pseudo_pixels,
-                                         self._extra_c_args(x) + (mw,), weights=vec)
-        with torch.cuda.device(x.device):
-            grad = torch.empty_like(dev["grad"])
-            grad.copy_(dev["grad"])
-        return loss, self._unpack(grad)
-
-    def step(self, images, labels, mask, max_workgroups=0, labelled=None, confusion=None, return_pseudo_pixels=False):
-        """one Adam step from images [N, H, W, C] (fp32 or decoded uint8) and labels / mask [N, H, W]: the frozen trunk up to
-        ``conv5_3_sum``, ``conv3_1`` and ``conv3_sub1``, then ``conv5_4_k1``, both fusion blocks and the head on the weights
-        being trained, their gradient kernels, Adam.  Returns the loss (float64 device scalar) before the step."""
-        return self._step_from_images(images, labels, mask, max_workgroups, labelled=labelled, confusion=confusion,
-                                      return_pseudo_pixels=return_pseudo_pixels)
-
 
 # ---- ICNet through its pyramid pooling: conv5_3's increase layer under the pyramid head (DESIGN.md section 41) -----------------
-_POOL_LAYER = "conv5_3_1x1_increase"
-_POOL_VARS = ((_POOL_LAYER, "kernel", True), (_POOL_LAYER, "gamma", False), (_POOL_LAYER, "beta", False)) + _PYRAMID_VARS
-# rows of mixed widths (1024, 1024, then the pyramid trainer's), concatenated unpadded
-_POOL_STATS = ((_POOL_LAYER, "mean"), (_POOL_LAYER, "variance")) + _PYRAMID_STATS
-
-
+@_icnet_depth("pool")
 class ICNetPoolingTrainer(ICNetPyramidTrainer):
     """Adam on ``conv5_3_1x1_increase`` -- the 1 x 1 convolution (256 -> 1024) + batch-norm that, with the identity shortcut
     ``conv5_2`` and a ReLU, closes the backbone's last bottleneck ``conv5_3`` (ICNET_SPEC section 2) -- through the
@@ -1821,65 +1682,9 @@ class ICNetPoolingTrainer(ICNetPyramidTrainer):
     The 20 variables travel as one packed float32 vector in the order of ``variable_names``: the increase layer's three,
     then the parent's seventeen in the parent's order.  The semi-supervised keywords are refused."""
 
-    _C_FEATURES = ("ssal_icnet_pool_grad", None)
-    _C_IMAGES = ("ssal_icnet_train_pool", None)
-    _CHANNELS, _UP = 256, 32
-    _VARS, _STATS, _C_UPDATE = _POOL_VARS, _POOL_STATS, "ssal_icnet_update_pool"
-    variable_names = ["%s.%s" % (layer, attr) for layer, attr, _ in _POOL_VARS]
-
-    _SEMI_NOUN = "ICNet's pooling trainer"
-    _FEATURE_NAMES = ("conv5_3_3x3", "conv5_2", "conv3_1", "conv3_sub1")
-
-    def _check_features(self, conv5_3_3x3, conv5_2, conv3_1, conv3_sub1, labels, mask, max_workgroups):
-        mw = self._check_call(conv5_3_3x3, 32, labels, mask, max_workgroups, 256)
-        n, h, w, _ = tuple(np.shape(conv5_3_3x3))
-        for name, t, want in (("conv5_2", conv5_2, (n, h, w, 1024)), ("conv3_1", conv3_1, (n, 2 * h, 2 * w, 256)),
-                              ("conv3_sub1", conv3_sub1, (n, 4 * h, 4 * w, 64))):
-            if tuple(np.shape(t)) != want:
-                raise ValueError("%s must be %s for conv5_3_3x3 %s (got %s)" % (name, want, (n, h, w, 256), tuple(np.shape(t))))
-            dt = str(getattr(t, "dtype", ""))
-            if "float" not in dt:
-                raise ValueError("%s must be a floating-point tensor (got %s)" % (name, dt or type(t).__name__))
-        return mw
-
-    def gradient_features(self, conv5_3_3x3, conv5_2, conv3_1, conv3_sub1, labels, mask, params=None, max_workgroups=0,
-                          labelled=None, confusion=None, return_pseudo_pixels=False):
-        """(loss float64 [1], {name: gradient} for ``variable_names``) on the device for ``conv5_3_3x3`` [N, h, w, 256],
-        ``conv5_2`` [N, h, w, 1024], ``conv3_1`` [N, 2h, 2w, 256], ``conv3_sub1`` [N, 4h, 4w, 64] and labels / mask
-        [N, 32h, 32w].  ``params`` overrides any of the 20 tensors; ``max_workgroups``: 0 = the default grids, a tuning knob.
-        No update."""
-        return self._gradient_from((conv5_3_3x3, conv5_2, conv3_1, conv3_sub1), labels, mask, params, max_workgroups,
-                                   labelled=labelled, confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
-
-    def features(self, images):
-        """``(conv5_3_3x3 [N, H/32, W/32, 256], conv5_2 [N, H/32, W/32, 1024], conv3_1 [N, H/16, W/16, 256], conv3_sub1
-        [N, H/8, W/8, 64])`` for ``images`` (copies): what ``step_features`` and ``gradient_features`` take.  One forward pass
-        of the frozen layers."""
-        self.net(images, training=False)
-        return tuple(self.net.endpoint(name).clone() for name in self._FEATURE_NAMES)
-
-    def step_features(self, conv5_3_3x3, conv5_2, conv3_1, conv3_sub1, labels, mask, max_workgroups=0, labelled=None,
-                      confusion=None, return_pseudo_pixels=False):
-        """one Adam step from cached features; returns the loss (float64 device scalar) BEFORE the step"""
-        return self._step_from((conv5_3_3x3, conv5_2, conv3_1, conv3_sub1), labels, mask, max_workgroups, labelled=labelled,
-                               confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
-
-    def step(self, images, labels, mask, max_workgroups=0, labelled=None, confusion=None, return_pseudo_pixels=False):
-        """one Adam step from images [N, H, W, C] (fp32 or decoded uint8) and labels / mask [N, H, W]: the frozen trunk up to
-        ``conv5_3_3x3``, ``conv5_2``, ``conv3_1`` and ``conv3_sub1``, then the increase layer, the pyramid pooling,
-        ``conv5_4_k1``, both fusion blocks and the head on the weights being trained, their gradient kernels, Adam.  Returns
-        the loss (float64 device scalar) before the step."""
-        return self._step_from_images(images, labels, mask, max_workgroups, labelled=labelled, confusion=confusion,
-                                      return_pseudo_pixels=return_pseudo_pixels)
-
 
 # ---- ICNet's last backbone bottleneck: conv5_3's reduce layer and 3 x 3 under the pooling trainer (DESIGN.md section 42) --------
-_BNECK_LAYERS = ("conv5_3_1x1_reduce", "conv5_3_3x3")
-_BNECK_VARS = tuple((layer, attr, attr == "kernel") for layer in _BNECK_LAYERS for attr in ("kernel", "gamma", "beta")) + _POOL_VARS
-# rows of mixed widths (four of 256, then the pooling trainer's), concatenated unpadded
-_BNECK_STATS = tuple((layer, attr) for layer in _BNECK_LAYERS for attr in ("mean", "variance")) + _POOL_STATS
-
-
+@_icnet_depth("bneck")
 class ICNetBottleneckTrainer(ICNetPoolingTrainer):
     """Adam on the whole of ``conv5_3``, the backbone's last bottleneck (ICNET_SPEC section 2): ``conv5_3_1x1_reduce`` (1 x 1,
     1024 -> 256, batch-norm, ReLU) and ``conv5_3_3x3`` (3 x 3 at dilation 4, 256 -> 256, batch-norm, ReLU) under everything
@@ -1891,62 +1696,9 @@ class ICNetBottleneckTrainer(ICNetPoolingTrainer):
     The 26 variables travel as one packed float32 vector in the order of ``variable_names``: the reduce layer's three, the
     3 x 3's three, then the parent's twenty in the parent's order.  The semi-supervised keywords are refused."""
 
-    _C_FEATURES = ("ssal_icnet_bneck_grad", None)
-    _C_IMAGES = ("ssal_icnet_train_bneck", None)
-    _CHANNELS, _UP = 1024, 32
-    _VARS, _STATS, _C_UPDATE = _BNECK_VARS, _BNECK_STATS, "ssal_icnet_update_bneck"
-    variable_names = ["%s.%s" % (layer, attr) for layer, attr, _ in _BNECK_VARS]
-
-    _SEMI_NOUN = "ICNet's bottleneck trainer"
-    _FEATURE_NAMES = ("conv5_2", "conv3_1", "conv3_sub1")
-
-    def _check_features(self, conv5_2, conv3_1, conv3_sub1, labels, mask, max_workgroups):
-        mw = self._check_call(conv5_2, 32, labels, mask, max_workgroups, 1024)
-        n, h, w, _ = tuple(np.shape(conv5_2))
-        for name, t, want in (("conv3_1", conv3_1, (n, 2 * h, 2 * w, 256)), ("conv3_sub1", conv3_sub1, (n, 4 * h, 4 * w, 64))):
-            if tuple(np.shape(t)) != want:
-                raise ValueError("%s must be %s for conv5_2 %s (got %s)" % (name, want, (n, h, w, 1024), tuple(np.shape(t))))
-            dt = str(getattr(t, "dtype", ""))
-            if "float" not in dt:
-                raise ValueError("%s must be a floating-point tensor (got %s)" % (name, dt or type(t).__name__))
-        return mw
-
-    def gradient_features(self, conv5_2, conv3_1, conv3_sub1, labels, mask, params=None, max_workgroups=0, labelled=None,
-                          confusion=None, return_pseudo_pixels=False):
-        """(loss float64 [1], {name: gradient} for ``variable_names``) on the device for ``conv5_2`` [N, h, w, 1024],
-        ``conv3_1`` [N, 2h, 2w, 256], ``conv3_sub1`` [N, 4h, 4w, 64] and labels / mask [N, 32h, 32w].  ``params`` overrides
-        any of the 26 tensors; ``max_workgroups``: 0 = the default grids, a tuning knob.  No update."""
-        return self._gradient_from((conv5_2, conv3_1, conv3_sub1), labels, mask, params, max_workgroups, labelled=labelled,
-                                   confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
-
-    def features(self, images):
-        """``(conv5_2 [N, H/32, W/32, 1024], conv3_1 [N, H/16, W/16, 256], conv3_sub1 [N, H/8, W/8, 64])`` for ``images``
-        (copies): what ``step_features`` and ``gradient_features`` take.  One forward pass of the frozen layers."""
-        self.net(images, training=False)
-        return tuple(self.net.endpoint(name).clone() for name in self._FEATURE_NAMES)
-
-    def step_features(self, conv5_2, conv3_1, conv3_sub1, labels, mask, max_workgroups=0, labelled=None, confusion=None,
-                      return_pseudo_pixels=False):
-        """one Adam step from cached features; returns the loss (float64 device scalar) BEFORE the step"""
-        return self._step_from((conv5_2, conv3_1, conv3_sub1), labels, mask, max_workgroups, labelled=labelled,
-                               confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
-
-    def step(self, images, labels, mask, max_workgroups=0, labelled=None, confusion=None, return_pseudo_pixels=False):
-        """one Adam step from images [N, H, W, C] (fp32 or decoded uint8) and labels / mask [N, H, W]: the frozen trunk up to
-        ``conv5_2``, ``conv3_1`` and ``conv3_sub1``, then the three layers of ``conv5_3``, the pyramid pooling, ``conv5_4_k1``,
-        both fusion blocks and the head on the weights being trained, their gradient kernels, Adam.  Returns the loss (float64
-        device scalar) before the step."""
-        return self._step_from_images(images, labels, mask, max_workgroups, labelled=labelled, confusion=confusion,
-                                      return_pseudo_pixels=return_pseudo_pixels)
-
 
 # ---- ICNet through conv5_2: the last bottleneck but one under the bottleneck trainer (DESIGN.md section 43) ----------------------
-_BNECK2_LAYERS = ("conv5_2_1x1_reduce", "conv5_2_3x3", "conv5_2_1x1_increase")
-_BNECK2_VARS = tuple((layer, attr, attr == "kernel") for layer in _BNECK2_LAYERS for attr in ("kernel", "gamma", "beta")) + _BNECK_VARS
-# rows of mixed widths (four of 256, two of 1024, then the bottleneck trainer's), concatenated unpadded
-_BNECK2_STATS = tuple((layer, attr) for layer in _BNECK2_LAYERS for attr in ("mean", "variance")) + _BNECK_STATS
-
-
+@_icnet_depth("bneck2")
 class ICNetDeepBottleneckTrainer(ICNetBottleneckTrainer):
     """Adam on ``conv5_2`` and ``conv5_3``, the backbone's last two bottlenecks (ICNET_SPEC section 2): ``conv5_2_1x1_reduce``
     (1 x 1, 1024 -> 256), ``conv5_2_3x3`` (3 x 3 at dilation 4, 256 -> 256) and ``conv5_2_1x1_increase`` (1 x 1, 256 -> 1024,
@@ -1960,56 +1712,9 @@ class ICNetDeepBottleneckTrainer(ICNetBottleneckTrainer):
     3 x 3's three, the increase layer's three, then the parent's 26 in the parent's order.  The semi-supervised keywords are
     refused."""
 
-    _C_FEATURES = ("ssal_icnet_bneck2_grad", None)
-    _C_IMAGES = ("ssal_icnet_train_bneck2", None)
-    _CHANNELS, _UP = 1024, 32
-    _VARS, _STATS, _C_UPDATE = _BNECK2_VARS, _BNECK2_STATS, "ssal_icnet_update_bneck2"
-    variable_names = ["%s.%s" % (layer, attr) for layer, attr, _ in _BNECK2_VARS]
-
-    _SEMI_NOUN = "ICNet's deep bottleneck trainer"
-    _FEATURE_NAMES = ("conv5_1", "conv3_1", "conv3_sub1")
-
-    def _check_features(self, conv5_1, conv3_1, conv3_sub1, labels, mask, max_workgroups):
-        mw = self._check_call(conv5_1, 32, labels, mask, max_workgroups, 1024)
-        n, h, w, _ = tuple(np.shape(conv5_1))
-        for name, t, want in (("conv3_1", conv3_1, (n, 2 * h, 2 * w, 256)), ("conv3_sub1", conv3_sub1, (n, 4 * h, 4 * w, 64))):
-            if tuple(np.shape(t)) != want:
-                raise ValueError("%s must be %s for conv5_1 %s (got %s)" % (name, want, (n, h, w, 1024), tuple(np.shape(t))))
-            dt = str(getattr(t, "dtype", ""))
-            if "float" not in dt:
-                raise ValueError("%s must be a floating-point tensor (got %s)" % (name, dt or type(t).__name__))
-        return mw
-
-    def gradient_features(self, conv5_1, conv3_1, conv3_sub1, labels, mask, params=None, max_workgroups=0, labelled=None,
-                          confusion=None, return_pseudo_pixels=False):
-        """(loss float64 [1], {name: gradient} for ``variable_names``) on the device for ``conv5_1`` [N, h, w, 1024],
-        ``conv3_1`` [N, 2h, 2w, 256], ``conv3_sub1`` [N, 4h, 4w, 64] and labels / mask [N, 32h, 32w].  ``params`` overrides
-        any of the 35 tensors; ``max_workgroups``: 0 = the default grids, a tuning knob.  No update."""
-        return self._gradient_from((conv5_1, conv3_1, conv3_sub1), labels, mask, params, max_workgroups, labelled=labelled,
-                                   confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
-
-    def features(self, images):
-        """``(conv5_1 [N, H/32, W/32, 1024], conv3_1 [N, H/16, W/16, 256], conv3_sub1 [N, H/8, W/8, 64])`` for ``images``
-        (copies): what ``step_features`` and ``gradient_features`` take.  One forward pass of the frozen layers."""
-        self.net(images, training=False)
-        return tuple(self.net.endpoint(name).clone() for name in self._FEATURE_NAMES)
-
-    def step_features(self, conv5_1, conv3_1, conv3_sub1, labels, mask, max_workgroups=0, labelled=None, confusion=None,
-                      return_pseudo_pixels=False):
-        """one Adam step from cached features; returns the loss (float64 device scalar) BEFORE the step"""
-        return self._step_from((conv5_1, conv3_1, conv3_sub1), labels, mask, max_workgroups, labelled=labelled,
-                               confusion=confusion, return_pseudo_pixels=return_pseudo_pixels)
-
-    def step(self, images, labels, mask, max_workgroups=0, labelled=None, confusion=None, return_pseudo_pixels=False):
-        """one Adam step from images [N, H, W, C] (fp32 or decoded uint8) and labels / mask [N, H, W]: the frozen trunk up to
-        ``conv5_1``, ``conv3_1`` and ``conv3_sub1``, then the three layers of ``conv5_2`` and of ``conv5_3``, the pyramid
-        pooling, ``conv5_4_k1``, both fusion blocks and the head on the weights being trained, their gradient kernels, Adam.
-        Returns the loss (float64 device scalar) before the step."""
-        return self._step_from_images(images, labels, mask, max_workgroups, labelled=labelled, confusion=confusion,
-                                      return_pseudo_pixels=return_pseudo_pixels)
-
 
 # ---- the semi-supervised step of ICNet's fusion and cascade trainers (DESIGN.md section 30) --------------------------------------
+@_icnet_depth("fusion", semi=True)
 class SemiSupervisedICNetFusionTrainer(_SemiKeywords, ICNetFusionTrainer):
     """``ICNetFusionTrainer`` with the reference's semi-supervised step (active_learning.py:226-275, 339-342) built into the
     head's gradient kernel: ``gradient_features``, ``step_features`` and ``step`` accept ``labelled``, ``measure``,
@@ -2020,70 +1725,17 @@ class SemiSupervisedICNetFusionTrainer(_SemiKeywords, ICNetFusionTrainer):
     ``ICNetFusionTrainer`` on the composed targets; with none of the keywords a call goes through the
     plain entry.  ``state`` / ``load_state`` are interchangeable with ``ICNetFusionTrainer``'s."""
 
-    _C_FEATURES = ("ssal_icnet_fusion_grad", "ssal_icnet_fusion_grad_semi")
-    _C_IMAGES = ("ssal_icnet_train_fusion", "ssal_icnet_train_fusion_semi")
 
-    def gradient_features(self, sub24_sum, conv3_sub1, labels, mask, params=None, max_workgroups=0, labelled=None,
-                          measure=None, threshold=None, features_raw=None, confusion=None, return_pseudo_pixels=False):
-        """``ICNetFusionTrainer.gradient_features`` with the semi-supervised keywords of
-        ``FinalLayerTrainer.gradient_features``: ``labelled`` [N], ``measure`` / ``threshold`` (defaults: the trainer's),
-        ``features_raw`` (``features(images_raw)``: both tensors), ``confusion`` (int64 [K, K] device tensor, added to),
-        ``return_pseudo_pixels`` (appends the int64 [N] counts to the result)."""
-        return self._gradient_from((sub24_sum, conv3_sub1), labels, mask, params, max_workgroups, labelled=labelled,
-                                   measure=measure, threshold=threshold, features_raw=features_raw, confusion=confusion,
-                                   return_pseudo_pixels=return_pseudo_pixels)
-
-    def step_features(self, sub24_sum, conv3_sub1, labels, mask, max_workgroups=0, labelled=None, measure=None, threshold=None,
-                      features_raw=None, confusion=None, return_pseudo_pixels=False):
-        """one Adam step from cached features; the keywords are those of ``gradient_features``; with
-        ``return_pseudo_pixels`` the result is ``(loss, pseudo_pixels)``"""
-        return self._step_from((sub24_sum, conv3_sub1), labels, mask, max_workgroups, labelled=labelled, measure=measure,
-                               threshold=threshold, features_raw=features_raw, confusion=confusion,
-                               return_pseudo_pixels=return_pseudo_pixels)
-
-    def step(self, images, labels, mask, max_workgroups=0, labelled=None, measure=None, threshold=None, images_raw=None,
-             confusion=None, return_pseudo_pixels=False):
-        """one Adam step from images; ``images_raw``: the undistorted frames (same shape and dtype as ``images``) -- the trunk,
-        the trained blocks and the head run on them first and the pseudo annotation comes from their logits
-        (active_learning.py:231).  The other keywords as in ``gradient_features``; with ``return_pseudo_pixels`` the result
-        is ``(loss, pseudo_pixels)``."""
-        return self._step_from_images(images, labels, mask, max_workgroups, labelled=labelled, measure=measure,
-                                      threshold=threshold, images_raw=images_raw, confusion=confusion,
-                                      return_pseudo_pixels=return_pseudo_pixels)
-
-
+@_icnet_depth("cascade", semi=True)
 class SemiSupervisedICNetCascadeTrainer(_SemiKeywords, ICNetCascadeTrainer):
     """``ICNetCascadeTrainer`` with the semi-supervised step built into the head's gradient kernel (see
     ``SemiSupervisedICNetFusionTrainer``); ``features_raw`` is the three tensors ``features(images_raw)`` returns.  Loss and
     the fourteen gradients are bit-identical to ``ICNetCascadeTrainer`` on the composed targets; ``state`` / ``load_state``
     are interchangeable with its."""
 
-    _C_FEATURES = ("ssal_icnet_cascade_grad", "ssal_icnet_cascade_grad_semi")
-    _C_IMAGES = ("ssal_icnet_train_cascade", "ssal_icnet_train_cascade_semi")
-
-    def gradient_features(self, conv5_4_k1, conv3_1, conv3_sub1, labels, mask, params=None, max_workgroups=0, labelled=None,
-                          measure=None, threshold=None, features_raw=None, confusion=None, return_pseudo_pixels=False):
-        """``ICNetCascadeTrainer.gradient_features`` with the keywords of ``SemiSupervisedICNetFusionTrainer``'s"""
-        return self._gradient_from((conv5_4_k1, conv3_1, conv3_sub1), labels, mask, params, max_workgroups, labelled=labelled,
-                                   measure=measure, threshold=threshold, features_raw=features_raw, confusion=confusion,
-                                   return_pseudo_pixels=return_pseudo_pixels)
-
-    def step_features(self, conv5_4_k1, conv3_1, conv3_sub1, labels, mask, max_workgroups=0, labelled=None, measure=None,
-                      threshold=None, features_raw=None, confusion=None, return_pseudo_pixels=False):
-        """one Adam step from cached features; the keywords are those of ``gradient_features``"""
-        return self._step_from((conv5_4_k1, conv3_1, conv3_sub1), labels, mask, max_workgroups, labelled=labelled,
-                               measure=measure, threshold=threshold, features_raw=features_raw, confusion=confusion,
-                               return_pseudo_pixels=return_pseudo_pixels)
-
-    def step(self, images, labels, mask, max_workgroups=0, labelled=None, measure=None, threshold=None, images_raw=None,
-             confusion=None, return_pseudo_pixels=False):
-        """``SemiSupervisedICNetFusionTrainer.step`` for the cascade head"""
-        return self._step_from_images(images, labels, mask, max_workgroups, labelled=labelled, measure=measure,
-                                      threshold=threshold, images_raw=images_raw, confusion=confusion,
-                                      return_pseudo_pixels=return_pseudo_pixels)
-
 
 # ---- the semi-supervised step of ICNet's high-resolution trainer (DESIGN.md section 37) -----------------------------------------
+@_icnet_depth("highres", semi=True)
 class SemiSupervisedICNetHighResTrainer(_SemiKeywords, ICNetHighResTrainer):
     """``ICNetHighResTrainer`` with the semi-supervised step built into the head's gradient kernel (see
     ``SemiSupervisedICNetFusionTrainer``).  ``features_raw`` is the triple ``(conv5_4_k1_raw, conv3_1_raw, images_raw)``:
@@ -2093,32 +1745,6 @@ class SemiSupervisedICNetHighResTrainer(_SemiKeywords, ICNetHighResTrainer):
     being trained.  Loss and the 23 gradients are bit-identical to ``ICNetHighResTrainer`` on the composed targets (DESIGN.md
     section 37); with none of the keywords a call goes through the plain entry.  ``state`` / ``load_state`` are interchangeable
     with ``ICNetHighResTrainer``'s."""
-
-    _C_FEATURES = ("ssal_icnet_highres_grad", "ssal_icnet_highres_grad_semi")
-    _C_IMAGES = ("ssal_icnet_train_highres", "ssal_icnet_train_highres_semi")
-
-    def gradient_features(self, conv5_4_k1, conv3_1, images, labels, mask, params=None, max_workgroups=0, labelled=None,
-                          measure=None, threshold=None, features_raw=None, confusion=None, return_pseudo_pixels=False):
-        """``ICNetHighResTrainer.gradient_features`` with the keywords of ``SemiSupervisedICNetFusionTrainer``'s;
-        ``features_raw``: ``(conv5_4_k1_raw, conv3_1_raw, images_raw)``"""
-        return self._gradient_from((conv5_4_k1, conv3_1, images), labels, mask, params, max_workgroups, labelled=labelled,
-                                   measure=measure, threshold=threshold, features_raw=features_raw, confusion=confusion,
-                                   return_pseudo_pixels=return_pseudo_pixels)
-
-    def step_features(self, conv5_4_k1, conv3_1, images, labels, mask, max_workgroups=0, labelled=None, measure=None,
-                      threshold=None, features_raw=None, confusion=None, return_pseudo_pixels=False):
-        """one Adam step from cached backbone features and the frames; the keywords are those of ``gradient_features``"""
-        return self._step_from((conv5_4_k1, conv3_1, images), labels, mask, max_workgroups, labelled=labelled,
-                               measure=measure, threshold=threshold, features_raw=features_raw, confusion=confusion,
-                               return_pseudo_pixels=return_pseudo_pixels)
-
-    def step(self, images, labels, mask, max_workgroups=0, labelled=None, measure=None, threshold=None, images_raw=None,
-             confusion=None, return_pseudo_pixels=False):
-        """``SemiSupervisedICNetFusionTrainer.step`` for the high-resolution trainer: with ``images_raw`` the two frozen
-        backbone branches run on the undistorted frames first, then the branch and the head being trained"""
-        return self._step_from_images(images, labels, mask, max_workgroups, labelled=labelled, measure=measure,
-                                      threshold=threshold, images_raw=images_raw, confusion=confusion,
-                                      return_pseudo_pixels=return_pseudo_pixels)
 
 
 __all__ = ["FinalLayerTrainer", "LastBlockTrainer", "LastStageTrainer", "DecoderTailTrainer", "SemiSupervisedBlockTrainer",
